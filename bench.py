@@ -22,6 +22,9 @@ already resident in HBM.  Rank 0 prints ONE JSON line.
              pinned); the oracle also checks the GPU output of >= 1024 random streams bit for bit.
   config2/3/4   the other single-GPU BASELINE configs at full size in the same run (rank 0, N == 1):
              library-default and tuned plan, roofline fraction, oracle parity on >= 1024 random streams.
+
+--dump-outputs DIR writes what the headline's last timed step returned (rank 0's shard) as float32 .npy files, at most
+64 MB in all: see dump_outputs().  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 from __future__ import annotations
 
@@ -41,6 +44,33 @@ os.environ.setdefault("FLOWZ_HIP_NO_PLAN_CACHE", "1")
 HBM_PEAK_GBS = 8000.0
 PARITY_STREAMS = 1024
 PARITY_STREAMS_OTHER_RANKS = 128
+DUMP_BYTES = 64 << 20                                        # --dump-outputs: bytes of all files together
+DUMP_SEED = 5
+
+
+def load_oracle():
+    """The compiled oracle that the parity checks and the CPU baseline call: oracle/libflowz_oracle.so and libflowz_oracle_std.so, which
+    build() makes.  coracle would make a missing one in place, which fails in a tree that cannot be written; bench.py compiles it with
+    oracle/Makefile into a temporary directory instead and hands coracle the loaded library."""
+    import ctypes
+    import shutil
+    import subprocess
+    import tempfile
+
+    from oracle import coracle
+
+    here = os.path.join(ROOT, "oracle")
+    missing = [n for n in ("libflowz_oracle.so", "libflowz_oracle_std.so") if not os.path.exists(os.path.join(here, n))]
+    if not missing:
+        return
+    tmp = tempfile.mkdtemp(prefix="bench_oracle_")
+    try:
+        subprocess.check_call(["make", "-s", "-C", tmp, "-f", os.path.join(here, "Makefile"), "VPATH=" + here] + missing)
+        libs = {n: ctypes.CDLL(os.path.join(tmp, n)) for n in missing}
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)                # (a loaded library stays mapped)
+    coracle._LIB = libs.get("libflowz_oracle.so", coracle._LIB)
+    coracle._LIB_STD = libs.get("libflowz_oracle_std.so", coracle._LIB_STD)
 
 
 # ---- CPU baseline --------------------------------------------------------------------------------------------------
@@ -355,6 +385,40 @@ def sample_ids(ns, k, seed):
     rng = np.random.default_rng(seed)
     edge = [i for i in (0, 1, 63, 64, ns - 1) if 0 <= i < ns]
     return np.unique(np.concatenate([edge, rng.integers(0, ns, k)]))
+
+
+def dump_stream_ids(ns, k):
+    """--dump-outputs: the fixed, seeded sample of k of the ns streams (sorted local indices; all of them when k >= ns)"""
+    import numpy as np
+
+    if k >= ns:
+        return np.arange(ns)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(ns, k, replace=False))
+
+
+def dump_outputs(torch, path, y, state, tile):
+    """What one run_block call returned -- out frames y and state -- as float32 .npy files under `path`:
+      out_last_sample.npy  [streams, n_out]     the block's last sample of every stream (a seeded sample of the streams beyond 16 MB)
+      out_streams.npy      [T, k, n_out]        every sample of the block for the seeded sample dump_stream_ids(ns, k)
+      state_streams.npy    [n_state, k]         the state those k streams carry into the next block
+    k is as many streams as fit in half of DUMP_BYTES."""
+    import numpy as np
+
+    ns, T, n_out = (y.shape[0] * y.shape[2], y.shape[1], y.shape[3]) if tile else (y.shape[1], y.shape[0], y.shape[2])
+    last = (y[:, -1] if tile else y[-1]).reshape(ns, n_out)
+    n_last = min(ns, DUMP_BYTES // 4 // (4 * n_out))
+    if n_last < ns:
+        last = last[torch.as_tensor(dump_stream_ids(ns, n_last), device=y.device)]
+    k = max(1, min(ns, DUMP_BYTES // 2 // (4 * (T * n_out + state.shape[0]))))
+    ids = dump_stream_ids(ns, k)
+    arrays = {"out_last_sample": last.cpu().numpy(),
+              "out_streams": gather(torch, y, ids, "tiled" if tile else "time_major", tile),
+              "state_streams": state[:, torch.as_tensor(ids, device=state.device)].cpu().numpy()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        raise SystemExit(f"--dump-outputs: {T}-sample blocks do not fit in {DUMP_BYTES >> 20} MB")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
 
 def ndiff_bits(a, b):
@@ -850,7 +914,14 @@ def main():
     ap.add_argument("--no-layout-legs", action="store_true",
                     help="skip the headline workload on the other layouts: stream tiles and stream-major buffers [stream][t] "
                          "(the reference's calling convention, test/benchmark.cpp:137-147)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the headline workload's last step returned (out frames and state; rank 0's shard) "
+                         "as DIR/<name>.npy, float32, at most 64 MB in all (a fixed, seeded sample of the streams)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs and args.only:
+        ap.error("--dump-outputs writes the headline workload's outputs, which --only does not run")
     if args.no_autotune:
         os.environ["FLOWZ_HIP_AUTOTUNE"] = "0"               # (the library's default since round 6: nothing is measured on first use)
 
@@ -870,6 +941,7 @@ def main():
     from zignal_amd import flowz as F
     from zignal_amd import workloads as W
 
+    load_oracle()
     SEED = W.SEED
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1011,6 +1083,8 @@ def main():
     barrier()
     wall = time.perf_counter() - t0
     kern_avg_s = ev0.elapsed_time(ev1) / args.steps / 1e3
+    if args.dump_outputs and rank == 0:                      # (before the sustained run launches the kernel again)
+        dump_outputs(torch, args.dump_outputs, y, state, tile)
 
     checksum = zdist.bits_checksum(y[:, -1] if tile else y[-1])      # last time step of every stream: exact, shard-independent
     stats = zdist.reduce_stats(wall, float(ns) * T * args.steps, checksum, device=stats_dev)

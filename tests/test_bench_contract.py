@@ -58,6 +58,39 @@ def test_compact_line_of_a_full_record_fits_the_driver(tmp_path):
     assert d["roofline"]["frac"] == full["roofline"]["frac"] and d["roofline"]["traffic"] == full["roofline"]["traffic"] and "truncated" in d
 
 
+def test_dump_outputs_writes_the_same_bounded_sample_from_either_frame_layout(tmp_path):
+    """bench.dump_outputs on host tensors: float32 files of at most 64 MB, the values of the seeded sample of streams, the same
+    files from time-major and stream-tiled frames of the same data; the last sample is itself sampled beyond 4 M streams"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    for ns, T, n_state, tile in ((65536, 512, 24, 8192), ((1 << 22) + 8, 2, 3, 8)):
+        g = torch.Generator().manual_seed(ns)
+        y = torch.randn((T, ns, 1), generator=g)
+        st = torch.randn((n_state, ns), generator=g)
+        tiled = y.reshape(T, ns // tile, tile, 1).permute(1, 0, 2, 3).contiguous()
+        a, b = tmp_path / f"tm{ns}", tmp_path / f"tiled{ns}"
+        bench.dump_outputs(torch, str(a), y, st, 0)
+        bench.dump_outputs(torch, str(b), tiled, st, tile)
+        names = sorted(os.listdir(a))
+        assert names == ["out_last_sample.npy", "out_streams.npy", "state_streams.npy"] and sorted(os.listdir(b)) == names
+        assert sum(os.path.getsize(a / n) for n in names) <= bench.DUMP_BYTES
+        got = {n[:-4]: np.load(a / n) for n in names}
+        for n in names:
+            assert got[n[:-4]].dtype == np.float32 and np.array_equal(got[n[:-4]], np.load(b / n)), n
+        k = got["state_streams"].shape[1]
+        ids = bench.dump_stream_ids(ns, k)
+        assert 0 < k < ns and len(np.unique(ids)) == k
+        assert np.array_equal(got["out_streams"], y[:, ids].numpy()) and np.array_equal(got["state_streams"], st[:, ids].numpy())
+        last = y[-1].numpy()
+        if ns * 4 <= bench.DUMP_BYTES // 4:
+            assert np.array_equal(got["out_last_sample"], last)
+        else:
+            n_last = got["out_last_sample"].shape[0]
+            assert n_last < ns and np.array_equal(got["out_last_sample"], last[bench.dump_stream_ids(ns, n_last)])
+
+
 def _last_line_as_the_driver_sees_it(stdout):
     """the driver keeps the tail of stdout: the JSON line must be recoverable from the last 4096 bytes alone"""
     tail = stdout[-LINE_LIMIT:]
@@ -117,6 +150,35 @@ def test_bench_json_contract_small_workload(tmp_path):
     assert 0.5 < c["Msamples_per_s_per_core"] * c["cores"] / c["value"] < 2.0
 
 
+@pytest.mark.gpu
+def test_bench_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs: what the last timed step returned, the same from run to run.  One untimed block, warmup - 1 more, then --steps
+    timed ones: --steps 3 --warmup 1 and --steps 2 --warmup 2 both end on the fourth block, which the oracle computes from the same
+    seeded input run four times with the state carried"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import coracle, flowz_oracle as O
+    from zignal_amd import workloads as W
+    ns, T = 16384, 512
+    common = ["--gpus", "1", "--streams", str(ns), "--samples", str(T), "--no-cpu-baseline", "--no-autotune", "--no-config2", "--no-config34",
+              "--no-sustained", "--no-layout-legs", "--no-extras", "--no-next-rows"]
+    a, b = tmp_path / "a", tmp_path / "b"
+    _run_bench(common + ["--steps", "3", "--warmup", "1", "--dump-outputs", str(a)])
+    _run_bench(common + ["--steps", "2", "--warmup", "2", "--dump-outputs", str(b)])
+    names = sorted(os.listdir(a))
+    assert names == ["out_last_sample.npy", "out_streams.npy", "state_streams.npy"] and sorted(os.listdir(b)) == names
+    got = {n[:-4]: np.load(a / n) for n in names}
+    for n in names:
+        assert got[n[:-4]].dtype == np.float32 and np.array_equal(got[n[:-4]].view(np.uint32), np.load(b / n).view(np.uint32)), n
+    ids = bench.dump_stream_ids(ns, got["state_streams"].shape[1])
+    assert got["out_streams"].shape == (T, len(ids), 1) and got["out_last_sample"].shape == (ns, 1)
+    x = O.synth_input(W.SEED, ids, T)
+    want = coracle.df1_cascade([W.STABLE] * 6, np.concatenate([x] * 4))[3 * T:]
+    assert np.array_equal(got["out_streams"].view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(got["out_last_sample"][ids].view(np.uint32), want[-1].view(np.uint32))
+
+
 def _run_bench(args, nproc=1, timeout=900, launcher=False, env=None):
     if nproc > 1 or launcher:
         import socket
@@ -159,35 +221,41 @@ def test_bench_two_ranks_on_one_gpu_rehearse_the_sharded_path():
     assert strong["checksum"] == one["checksum"]
 
 
+# ranks of the many-rank rehearsal: they all hold device 0 at once, next to the pytest process itself, and a shared GPU takes at
+# most six processes that have it open
+RANKS_ON_ONE_GPU = 4
+
+
 @pytest.mark.gpu
-def test_bench_eight_ranks_on_one_gpu_rehearse_the_drivers_scaling_run():
+def test_bench_four_ranks_on_one_gpu_rehearse_the_drivers_scaling_run():
     """What `bench.py --gpus 8` does on a node, rehearsed on ONE GPU (round 6: the driver's first 8-GPU run is also the first execution with more
-    than one RCCL rank, so everything around the collective is exercised here): eight ranks under torch.distributed.run share device 0 and
-    reduce over gloo, 131 072 streams each.  Every rank measures its plan at the same time (fz_program_tune: eight processes appending to
+    than one RCCL rank, so everything around the collective is exercised here): four ranks under torch.distributed.run share device 0 and
+    reduce over gloo, 131 072 streams each.  Every rank measures its plan at the same time (fz_program_tune: four processes appending to
     the ONE plans.txt of the shared kernel cache, none of them torn), runs its shard, checks streams of its own shard against the oracle;
-    the integer checksum over the eight shards equals a one-rank run over the union; the line stays below 4 KB with eight per-rank times."""
+    the integer checksum over the four shards equals a one-rank run over the union; the line stays below 4 KB with the per-rank times."""
+    n = RANKS_ON_ONE_GPU
     plans = os.path.join(os.environ.get("FLOWZ_HIP_CACHE") or os.path.join(ROOT, "zignal_amd", "_kcache"), "plans.txt")   # (the library's kernel cache directory)
     before = open(plans).read().splitlines() if os.path.exists(plans) else []
     common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-config2", "--no-config34", "--no-sustained", "--no-layout-legs", "--no-extras", "--no-next-rows"]
-    # (bench.py switches the persisted plans off for itself -- every run measures; the rehearsal switches them back on so that the eight tunes also
-    #  meet at the one plans.txt, which a caller's eight processes would)
-    weak = _run_bench(["--gpus", "8", "--streams", "131072", "--dist-backend", "gloo"] + common, nproc=8, timeout=1200, env={"FLOWZ_HIP_NO_PLAN_CACHE": "0"})
-    assert weak["n_gpus"] == 8 and weak["scaling"] == "weak" and weak["config"]["streams_total"] == 8 * 131072 and weak["config"]["streams_per_gpu"] == 131072
-    assert weak["parity"].startswith("bitwise-equal on") and "every one of the 8 ranks" in weak["parity"]
+    # (bench.py switches the persisted plans off for itself -- every run measures; the rehearsal switches them back on so that the tunes of all
+    #  ranks also meet at the one plans.txt, which a caller's processes would)
+    weak = _run_bench(["--gpus", str(n), "--streams", "131072", "--dist-backend", "gloo"] + common, nproc=n, timeout=1200, env={"FLOWZ_HIP_NO_PLAN_CACHE": "0"})
+    assert weak["n_gpus"] == n and weak["scaling"] == "weak" and weak["config"]["streams_total"] == n * 131072 and weak["config"]["streams_per_gpu"] == 131072
+    assert weak["parity"].startswith("bitwise-equal on") and f"every one of the {n} ranks" in weak["parity"]
     assert weak["dist_backend"] == "gloo" and weak["rccl_ranks"] == 0
-    assert len(weak["ms_per_step_per_rank"]) == 8 and min(weak["ms_per_step_per_rank"]) > 0
-    assert "x8" in weak["config"]["parallelism"] and weak["roofline"]["bound"] == "hbm" and 0 < weak["roofline"]["frac"] < 1 and "cpu_baseline" not in weak
+    assert len(weak["ms_per_step_per_rank"]) == n and min(weak["ms_per_step_per_rank"]) > 0
+    assert f"x{n}" in weak["config"]["parallelism"] and weak["roofline"]["bound"] == "hbm" and 0 < weak["roofline"]["frac"] < 1 and "cpu_baseline" not in weak
     # value = the samples ALL ranks processed / the slowest rank's wall time (barrier to barrier)
-    assert abs(weak["value"] - 8 * 131072 * 4096 * 2 / (weak["ms_per_step"] * 2 / 1e3) / 1e6) / weak["value"] < 1e-2
-    assert abs(weak["per_gpu"] * 8 - weak["value"]) / weak["value"] < 1e-3
+    assert abs(weak["value"] - n * 131072 * 4096 * 2 / (weak["ms_per_step"] * 2 / 1e3) / 1e6) / weak["value"] < 1e-2
+    assert abs(weak["per_gpu"] * n - weak["value"]) / weak["value"] < 1e-3
     after = open(plans).read().splitlines() if os.path.exists(plans) else []
     new = after[len(before):]
     mine = [l.split() for l in new if l.split()[2:4] == ["131072", "0"]]
-    assert len(mine) >= 8 and all(len(f) == 11 and f[0] == "fzplan3" for f in mine), new[-10:]      # eight tunes, eight whole lines
-    one = _run_bench(["--gpus", "1", "--streams", str(8 * 131072), "--no-autotune"] + common)
+    assert len(mine) >= n and all(len(f) == 11 and f[0] == "fzplan3" for f in mine), new[-10:]      # one tune per rank, every line whole
+    one = _run_bench(["--gpus", "1", "--streams", str(n * 131072), "--no-autotune"] + common)
     assert weak["checksum"] == one["checksum"] and isinstance(weak["checksum"], int)
-    strong = _run_bench(["--gpus", "8", "--scaling", "strong", "--streams-total", str(8 * 131072 + 5), "--dist-backend", "gloo", "--no-autotune"] + common, nproc=8, timeout=1200)
-    assert strong["scaling"] == "strong" and strong["config"]["streams_total"] == 8 * 131072 + 5 and len(strong["ms_per_step_per_rank"]) == 8
+    strong = _run_bench(["--gpus", str(n), "--scaling", "strong", "--streams-total", str(n * 131072 + 5), "--dist-backend", "gloo", "--no-autotune"] + common, nproc=n, timeout=1200)
+    assert strong["scaling"] == "strong" and strong["config"]["streams_total"] == n * 131072 + 5 and len(strong["ms_per_step_per_rank"]) == n
     assert strong["parity"].startswith("bitwise-equal on")
 
 
