@@ -270,6 +270,31 @@ expr<I, 1> operator-(const expr<I, O>& a)
    return expr<I, 1>(detail::handle(fz_arith(FZ_OP_NEG, a.h.get(), nullptr)), a.refs);
 }
 
+// ---- graph functions: std::fabs, std::sqrt, std::exp, std::tanh, std::min, std::max (include/flowz_hip.h, FZ_OP_ABS ..) -------------
+// In the wire's C++ type (a double scalar stays a double terminal, as for the operators); min / max take an expression on either side.
+// flowz::tanh(0.5 * _1) is what `std::tanh(0.5 * x)` is in the reference's closures.
+#define FLOWZ_UNARY_FN(NAME, OP)                                                                          \
+   template <int I, int O>                                                                              \
+   expr<I, 1> NAME(const expr<I, O>& a)                                                                 \
+   {                                                                                                    \
+      static_assert(O == 1, "flowz: an arithmetic operand must have exactly one output wire");          \
+      return expr<I, 1>(detail::handle(fz_arith(OP, a.h.get(), nullptr)), a.refs);                     \
+   }
+FLOWZ_UNARY_FN(abs, FZ_OP_ABS)
+FLOWZ_UNARY_FN(sqrt, FZ_OP_SQRT)
+FLOWZ_UNARY_FN(exp, FZ_OP_EXP)
+FLOWZ_UNARY_FN(tanh, FZ_OP_TANH)
+#undef FLOWZ_UNARY_FN
+#define FLOWZ_BINARY_FN(NAME, OP)                                                                        \
+   template <class A, class B, class = detail::enable_binary<A, B>>                                     \
+   auto NAME(const A& a, const B& b)->decltype(detail::arith(OP, detail::as_expr(a), detail::as_expr(b))) \
+   {                                                                                                    \
+      return detail::arith(OP, detail::as_expr(a), detail::as_expr(b));                                 \
+   }
+FLOWZ_BINARY_FN(min, FZ_OP_MIN)
+FLOWZ_BINARY_FN(max, FZ_OP_MAX)
+#undef FLOWZ_BINARY_FN
+
 // ---- block composition operators (flowz.hpp:90-93) --------------------------------------------------------------
 template <int Ia, int Oa, int Ib, int Ob>
 expr<detail::imax(Ia, Ib), Oa + Ob> operator,(const expr<Ia, Oa>& a, const expr<Ib, Ob>& b)        // channel

@@ -51,7 +51,35 @@ typedef enum fz_op { FZ_OP_ADD = 1, FZ_OP_SUB = 2, FZ_OP_MUL = 3, FZ_OP_DIV = 4,
                         (every comparison with a NaN is false, != true).  Not for std::complex wires.  a && b, a || b, !a test their
                         operands against zero as C++ does for arithmetic types; both sides are always evaluated (no side effects to skip). */
                      FZ_OP_LT = 6, FZ_OP_LE = 7, FZ_OP_GT = 8, FZ_OP_GE = 9, FZ_OP_EQ = 10, FZ_OP_NE = 11,
-                     FZ_OP_NOT = 12, FZ_OP_AND = 13, FZ_OP_OR = 14 } fz_op;
+                     FZ_OP_NOT = 12, FZ_OP_AND = 13, FZ_OP_OR = 14,
+                     /* Graph functions: std::fabs, std::sqrt, std::exp, std::tanh (unary: b is ignored, the operand's input arity is
+                        kept, it must have exactly one output wire) and std::min, std::max of <algorithm> (binary).  Each counts as ONE
+                        node in fz_info.n_ops.  They work in the wire's C++ type: float, or double when an operand is double (a
+                        fz_literal_f64 below it, or a typed FZ_DT_F64 wire); min / max compare and return in the operands' common type.
+                          abs(a)    clears the sign bit (exact).
+                          sqrt(a)   IEEE correctly rounded; sqrt(-0) = -0, a negative operand gives NaN.
+                          min(a, b) (b < a) ? b : a,   max(a, b) (a < b) ? b : a  -- std::min / std::max exactly, signed zeros and the
+                                    position of a NaN included: min(NaN, 1) = NaN, min(1, NaN) = 1.
+                          exp(a)    within 2 ulp of the correctly rounded result (float: 0.957 ulp at most over all 2^32 inputs;
+                                    double: 0.95 ulp at most on 2^22 stratified inputs); exp(+-0) = 1,
+                                    exp(-inf) = +0, exp(+inf) = +inf, +inf exactly where the correctly rounded result overflows
+                                    (a > 0x1.62e42ep+6 float, a > 0x1.62e42fefa39efp+9 double), gradual underflow.
+                          tanh(a)   within 2 ulp (float: 1.437 ulp at most over all 2^32 inputs; double: 1.43 ulp at most on 2^22
+                                    stratified inputs); odd bitwise (tanh(-x) = -tanh(x), tanh(+-0) = +-0), |tanh| <= 1, exactly +-1 for
+                                    |a| > 10 (float) / 20 (double) and at +-inf, tanh(x) = x for tiny and subnormal x.  Monotone: over all
+                                    2^32 float inputs in increasing order the float tanh never steps down, the switch point at 0.55
+                                    included (float exp likewise; tools/graph_functions_exhaustive.py).
+                        exp and tanh are the library's own algorithm, built from IEEE +, -, *, correctly rounded /, exact scaling by
+                        powers of two through the exponent bits and round-to-nearest-even to integer (the 1.5 * 2^(p-1) trick): no FMA,
+                        no hardware approximation (v_exp_f32, v_log_f32, a bare v_rcp_f32), no ocml / libm call, no tables.
+                          exp:  k = rint(a / ln 2), r = (a - k ln2_hi) - k ln2_lo (k ln2_hi exact), e^r = 1 + (r + r^2 q(r)) with a
+                                Chebyshev-fitted q by Horner's rule, then * 2^(k >> 1) (exact) * 2^(k - (k >> 1)) (rounds once).
+                          tanh: |a| < 0.55: |a| + |a| (z P(z)), z = a^2; else 1 - 2 / (exp(2 |a|) + 1); the sign of a put back last.
+                        A numpy restatement in float32 / float64 arrays gives the kernels' bits for every non-NaN result
+                        (tests/fn_ref.py); a NaN result is a NaN, its payload is not specified.
+                        std::complex operands: min / max -> FZ_E_GRAPH (C++ has no such operator); abs, sqrt, exp, tanh ->
+                        FZ_E_UNSUPPORTED (valid C++, not built here). */
+                     FZ_OP_ABS = 15, FZ_OP_SQRT = 16, FZ_OP_EXP = 17, FZ_OP_TANH = 18, FZ_OP_MIN = 19, FZ_OP_MAX = 20 } fz_op;
 
 fz_expr* fz_placeholder(uint32_t i);                 /* _i          make_placeholder<i>() :78-82   */
 fz_expr* fz_delayed(uint32_t i, uint32_t n);         /* _i[_n]      delayed_placeholder   :84-85   */
@@ -93,8 +121,9 @@ fz_expr* fz_modulator(uint32_t k);                   /* the std::ref(x) terminal
                                                         for all streams, read from the array fz_program_set_modulation names --
                                                         an input wire without the per-stream HBM traffic (scalar loads)       */
 fz_expr* fz_arith(fz_op op, fz_expr* a, fz_expr* b); /* any C++ arithmetic, comparison or logical operator,
-                                                        _default :769-772; b is ignored (may be NULL) for
-                                                        FZ_OP_NEG and FZ_OP_NOT                       */
+                                                        _default :769-772, or a graph function; b is ignored
+                                                        (may be NULL) for FZ_OP_NEG, FZ_OP_NOT, FZ_OP_ABS,
+                                                        FZ_OP_SQRT, FZ_OP_EXP and FZ_OP_TANH           */
 fz_expr* fz_channel (fz_expr* a, fz_expr* b);        /* a , b       channel_operator   :90           */
 fz_expr* fz_parallel(fz_expr* a, fz_expr* b);        /* a | b       parallel_operator  :91           */
 fz_expr* fz_sequence(fz_expr* a, fz_expr* b);        /* a |= b      sequence_operator  :92           */
@@ -119,7 +148,7 @@ typedef struct fz_info {
    uint32_t n_in;        /* external input wires  (frame width of `in`)                       */
    uint32_t n_out;       /* output wires          (frame width of `out`)                      */
    uint32_t n_nodes;     /* nodes of the lowered per-sample DAG                               */
-   uint32_t n_ops;       /* arithmetic nodes = float32 operations per stream-sample           */
+   uint32_t n_ops;       /* arithmetic nodes = float32 operations per stream-sample (a graph function node counts as one) */
    uint32_t n_lines;     /* delay lines (one per delayed wire, shared by all its readers)     */
    uint32_t n_state;     /* floats of state per stream = sum of line depths                   */
    uint32_t n_const;     /* distinct uniform float32 coefficients (literal terminals)         */
@@ -183,8 +212,10 @@ typedef enum fz_ir_kind {
    FZ_IR_MOD = 12,    /* a = modulator index: value of sample-rate modulator a at this sample (fz_modulator)          */
    FZ_IR_ABSLT = 13,  /* |a| < |b| ? 1 : 0  (in the operands' type)                                                    */
    FZ_IR_SELECT = 14, /* a != 0 ? b : c   (the data-dependent branch of __divdc3; both sides are evaluated)            */
-   FZ_IR_LT = 15, FZ_IR_LE = 16, FZ_IR_GT = 17, FZ_IR_GE = 18, FZ_IR_EQ = 19, FZ_IR_NE = 20
+   FZ_IR_LT = 15, FZ_IR_LE = 16, FZ_IR_GT = 17, FZ_IR_GE = 18, FZ_IR_EQ = 19, FZ_IR_NE = 20,
                       /* a (cmp) b ? 1.0f : 0.0f -- a float32 node (dtype 0) whose operands are compared in double when one of them is     */
+   FZ_IR_ABS = 21, FZ_IR_SQRT = 22, FZ_IR_EXP = 23, FZ_IR_TANH = 24,   /* f(a), in a's type (see FZ_OP_ABS ..)                 */
+   FZ_IR_MIN = 25, FZ_IR_MAX = 26     /* std::min / std::max of a and b in their common type; never stage-packed (kinds >= ABSLT) */
 } fz_ir_kind;
 
 typedef struct fz_ir_node {

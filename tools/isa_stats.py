@@ -18,7 +18,38 @@ from zignal_amd import flowz as F  # noqa: E402
 GRAPHS = {"cascade6": lambda: G.df1_cascade(6), "par4": G.par4_sum, "par4f": G.par4_sum_fanout,
           "osc": lambda: G.osc_chain(6), "gain": lambda: G.mul(G.lit(0.5), G.IN(1)), "cascade2": lambda: G.df1_cascade(2), "cascade4": lambda: G.df1_cascade(4), "df1": G.df1, "integrator": G.integrator,
           "mod6": lambda: G.df1_cascade_modulated(6), "ldsring": G.lds_ring_comb,
-          "ring": lambda: G.seq(G.add(G.IN(1), G.mul(G.lit(0.5), G.DEL(1, 40))), G.fb(G.add(G.mul(G.lit(0.7), G.DEL(1, 23)), G.IN(2))))}
+          "ring": lambda: G.seq(G.add(G.IN(1), G.mul(G.lit(0.5), G.DEL(1, 40))), G.fb(G.add(G.mul(G.lit(0.7), G.DEL(1, 23)), G.IN(2)))),
+          "moog": G.moog_ladder, "softclip": G.soft_clip_cascade, "envelope": G.envelope_follower,
+          "tanh": lambda: ("tanh", G.IN(1)), "exp": lambda: ("exp", G.IN(1)), "sqrt": lambda: ("sqrt", G.IN(1)), "min": lambda: ("min", G.IN(1), G.lit(0.5)),
+          "wire": lambda: G.IN(1)}
+
+
+def valu_count(expr, P, U=1, block=256, flags=0):
+    """v_* instructions in the code object of a variant of the graph `expr` (s-expression): JIT into a scratch cache, disassemble"""
+    with tempfile.TemporaryDirectory() as td:
+        old = os.environ.get("FLOWZ_HIP_CACHE")
+        os.environ["FLOWZ_HIP_CACHE"] = td
+        try:
+            F.compile(F.from_sexpr(expr)).build(F.make_variant(P, U, block, flags))
+            f = glob.glob(td + "/*.hsaco")[0]
+            dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", f], text=True)
+        finally:
+            if old is None:
+                os.environ.pop("FLOWZ_HIP_CACHE", None)
+            else:
+                os.environ["FLOWZ_HIP_CACHE"] = old
+    return sum(1 for line in dis.splitlines() if line.split() and line.split()[0].startswith("v_"))
+
+
+def valu_per_step(expr, P):
+    """VALU instructions per step of the graph in a kernel of P streams per lane, unroll 1: its count minus that of the bare wire _1,
+    divided by the copies of the step the kernel holds (measured with a chain of 32 additions, which is 32 instructions a step)"""
+    base = valu_count(G.IN(1), P)
+    chain = G.IN(1)
+    for _ in range(32):
+        chain = G.add(chain, G.lit(0.5))
+    copies = (valu_count(chain, P) - base) / 32.0
+    return (valu_count(expr, P) - base) / copies
 
 
 def main():

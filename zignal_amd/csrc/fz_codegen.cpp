@@ -158,6 +158,100 @@ std::string gen_config(const Graph& g, const Variant& v)
 
 static std::string gen_body_skew(const Graph& g, const StageSplit& sp);
 
+// The graph functions (FZ_IR_ABS .. FZ_IR_MAX) for V and VD, written only into the text of graphs that use them: every other graph keeps
+// its kernel source byte for byte.  Branch-free per lane (both sides computed, the lane's one selected); exp and tanh are IEEE +, -, *,
+// correctly rounded / and exact power-of-two scaling through the exponent bits, no FMA (-ffp-contract=off), no hardware approximation and
+// no library call -- tests/fn_ref.py restates them operation for operation.  The polynomials run on V / VD themselves, so that two or four
+// streams per lane issue packed v_pk_mul_f32 / v_pk_add_f32; the comparisons and the exponent bits are per element (vector ternaries).
+static void emit_functions(std::ostringstream& o, const Graph& g)
+{
+   bool has[FZ_IR_MAX + 1] = {};
+   for (const Node& nd : g.nodes)
+      if (nd.kind >= FZ_IR_ABS && nd.kind <= FZ_IR_MAX) has[nd.kind] = true;
+   if (has[FZ_IR_TANH]) has[FZ_IR_EXP] = true;
+   bool any = false;
+   for (uint32_t k = FZ_IR_ABS; k <= FZ_IR_MAX; ++k) any = any || has[k];
+   if (!any) return;
+   o << "#if FZ_P == 1\ntypedef int fz_vi;\ntypedef long long fz_vl;\n#else\n"
+        "typedef int fz_vi __attribute__((ext_vector_type(FZ_P)));\ntypedef long long fz_vl __attribute__((ext_vector_type(FZ_P)));\n#endif\n";
+   struct Ty {
+      const char *T, *I, *sfx, *magic, *log2e, *ln2hi, *ln2lo, *xlo, *xhi, *xmax, *sw, *sat, *sign, *bias;
+      int shift;
+      std::vector<const char*> q, p;
+   };
+   const Ty tys[2] = {
+      {"V", "fz_vi", "f", "0x1.8p+23f", "0x1.715476p+0f", "0x1.62ep-1f", "0x1.0bfbe8p-15f", "-104.0f", "89.0f", "0x1.62e42ep+6f",
+       "0x1.19999ap-1f", "10.0f", "(fz_vi)(-2147483647 - 1)", "127", 23,
+       {"0x1.a127fcp-13f", "0x1.6d469p-10f", "0x1.1110ep-7f", "0x1.5554e6p-5f", "0x1.555556p-3f", "0x1p-1f"},
+       {"0x1.4b0ed2p-9f", "-0x1.176084p-7f", "0x1.6578cap-6f", "-0x1.ba1428p-5f", "0x1.111104p-3f", "-0x1.555556p-2f"}},
+      {"VD", "fz_vl", "", "0x1.8p+52", "0x1.71547652b82fep+0", "0x1.62e42fee00000p-1", "0x1.a39ef35793c76p-33", "-746.0", "710.0",
+       "0x1.62e42fefa39efp+9", "0x1.19999ap-1", "20.0", "(fz_vl)(-9223372036854775807LL - 1)", "1023", 52,
+       {"0x1.1f74882ae4b27p-29", "0x1.af509232e2477p-26", "0x1.27e4daa87b888p-22", "0x1.71de00e89dd34p-19", "0x1.a01a01a714245p-16",
+        "0x1.a01a01ac50533p-13", "0x1.6c16c16c16266p-10", "0x1.111111111001cp-7", "0x1.5555555555556p-5", "0x1.5555555555557p-3", "0x1p-1"},
+       {"0x1.081656de10f02p-17", "-0x1.1ad1adfc0e63cp-15", "0x1.8c8f32860a20fp-14", "-0x1.f41c32178e2b0p-13", "0x1.3547b24884a3fp-11",
+        "-0x1.7da25c9e6e474p-10", "0x1.d6d3c5f32768dp-9", "-0x1.226e353986e33p-7", "0x1.664f48822db68p-6", "-0x1.ba1ba1ba1a711p-5",
+        "0x1.1111111111109p-3", "-0x1.5555555555555p-2"}},
+   };
+   for (const Ty& t : tys) {
+      const std::string T = t.T, I = t.I, c = "(" + T + ")";
+      auto head = [&](const char* name, bool two) {
+         o << "__device__ __forceinline__ " << T << " " << name << "(" << T << " a" << (two ? ", " + T + " b" : std::string()) << ")\n{\n";
+      };
+      if (has[FZ_IR_ABS]) {
+         head("fz_abs", false);
+         o << "   return __builtin_bit_cast(" << T << ", __builtin_bit_cast(" << I << ", a) & ~" << t.sign << ");   // std::fabs: clear the sign bit\n}\n";
+      }
+      if (has[FZ_IR_SQRT]) {   // correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt; the double expansion is exact too)
+         head("fz_sqrt", false);
+         o << "#if FZ_P == 1\n   return __builtin_sqrt" << t.sfx << "(a);\n#else\n   " << T << " r;\n#pragma unroll\n   for (int j = 0; j < FZ_P; ++j) r[j] = __builtin_sqrt"
+           << t.sfx << "(a[j]);\n   return r;\n#endif\n}\n";
+      }
+      if (has[FZ_IR_MIN]) {
+         head("fz_min", true);
+         o << "   return (b < a) ? b : a;   // std::min\n}\n";
+      }
+      if (has[FZ_IR_MAX]) {
+         head("fz_max", true);
+         o << "   return (a < b) ? b : a;   // std::max\n}\n";
+      }
+      if (has[FZ_IR_EXP]) {
+         head("fz_exp", false);
+         o << "   // k = rint(a / ln 2) by the 1.5 * 2^(p-1) trick, r = (a - k ln2_hi) - k ln2_lo (k ln2_hi exact), e^r = 1 + (r + r^2 q(r)),\n"
+              "   // then * 2^(k >> 1) (exact) * 2^(k - (k >> 1)) (one rounding, also into the subnormals)\n";
+         o << "   " << T << " x = a < " << c << "(" << t.xlo << ") ? " << c << "(" << t.xlo << ") : a;\n";
+         o << "   x = x > " << c << "(" << t.xhi << ") ? " << c << "(" << t.xhi << ") : x;\n";
+         o << "   x = x == x ? x : " << c << "(0);\n";
+         o << "   const " << T << " tm = x * " << c << "(" << t.log2e << ") + " << c << "(" << t.magic << ");\n";
+         o << "   const " << T << " kf = tm - " << c << "(" << t.magic << ");\n";
+         o << "   const " << T << " r = (x - kf * " << c << "(" << t.ln2hi << ")) - kf * " << c << "(" << t.ln2lo << ");\n";
+         o << "   " << T << " q = " << c << "(" << t.q[0] << ");\n";
+         for (size_t k = 1; k < t.q.size(); ++k) o << "   q = " << c << "(" << t.q[k] << ") + r * q;\n";
+         o << "   const " << T << " p = " << c << "(1) + (r + (r * r) * q);\n";
+         o << "   const " << I << " k = __builtin_bit_cast(" << I << ", tm) - __builtin_bit_cast(" << I << ", " << c << "(" << t.magic << "));\n";
+         o << "   const " << I << " k1 = k >> 1, k2 = k - k1;\n";
+         o << "   " << T << " y = (p * __builtin_bit_cast(" << T << ", (k1 + " << t.bias << ") << " << t.shift << ")) * __builtin_bit_cast(" << T
+           << ", (k2 + " << t.bias << ") << " << t.shift << ");\n";
+         o << "   y = a > " << c << "(" << t.xmax << ") ? " << c << "(__builtin_huge_val" << t.sfx << "()) : y;\n";
+         o << "   return a != a ? a : y;\n}\n";
+      }
+      if (has[FZ_IR_TANH]) {
+         head("fz_tanh", false);
+         o << "   // odd: f(|a|) with the sign bit of a put back; |a| < 0.55: |a| + |a| (z P(z)), z = a^2; else 1 - 2 / (exp(2|a|) + 1); saturated: 1\n";
+         o << "   const " << T << " x = __builtin_bit_cast(" << T << ", __builtin_bit_cast(" << I << ", a) & ~" << t.sign << ");\n";
+         o << "   const " << T << " z = x * x;\n";
+         o << "   " << T << " p = " << c << "(" << t.p[0] << ");\n";
+         for (size_t k = 1; k < t.p.size(); ++k) o << "   p = " << c << "(" << t.p[k] << ") + z * p;\n";
+         o << "   const " << T << " ys = x + x * (z * p);\n";
+         o << "   const " << T << " xc = x > " << c << "(" << t.sat << ") ? " << c << "(" << t.sat << ") : x;\n";
+         o << "   const " << T << " yb = " << c << "(1) - " << c << "(2) / (fz_exp(xc + xc) + " << c << "(1));\n";
+         o << "   " << T << " y = x < " << c << "(" << t.sw << ") ? ys : yb;\n";
+         o << "   y = x > " << c << "(" << t.sat << ") ? " << c << "(1) : y;\n";
+         o << "   y = __builtin_bit_cast(" << T << ", __builtin_bit_cast(" << I << ", y) | (__builtin_bit_cast(" << I << ", a) & " << t.sign << "));\n";
+         o << "   return a != a ? a : y;\n}\n";
+      }
+   }
+}
+
 std::string gen_body(const Graph& g, const Variant& v)
 {
    if (const uint32_t W = ws_parts(v.flags)) {
@@ -232,6 +326,7 @@ std::string gen_body(const Graph& g, const Variant& v)
          o << "template <int K> __device__ __forceinline__ V fz_cmp(" << T << " a, " << T << " b)\n{\n   V r;\n#pragma unroll\n   for (int j = 0; j < FZ_P; ++j) r[j] = fz_cmp1<K>(a[j], b[j]) ? 1.f : 0.f;\n   return r;\n}\n";
       o << "#endif\n";
    }
+   emit_functions(o, g);
    // operand `id` as seen by a node of type f64/f32 (C++ usual arithmetic conversions: float -> double is exact)
    auto opnd = [&](uint32_t id, bool want64) {
       return (want64 && !g.nodes[id].f64) ? "fz_cvt_d(" + val(id) + ")" : val(id);
@@ -461,6 +556,12 @@ std::string gen_body(const Graph& g, const Variant& v)
             break;
          }
          case FZ_IR_ABSLT: o << "fz_abs_lt(" << opnd(nd.a, d) << ", " << opnd(nd.b, d) << ")"; break;
+         case FZ_IR_ABS: o << "fz_abs(" << val(nd.a) << ")"; break;
+         case FZ_IR_SQRT: o << "fz_sqrt(" << val(nd.a) << ")"; break;
+         case FZ_IR_EXP: o << "fz_exp(" << val(nd.a) << ")"; break;
+         case FZ_IR_TANH: o << "fz_tanh(" << val(nd.a) << ")"; break;
+         case FZ_IR_MIN: o << "fz_min(" << opnd(nd.a, d) << ", " << opnd(nd.b, d) << ")"; break;
+         case FZ_IR_MAX: o << "fz_max(" << opnd(nd.a, d) << ", " << opnd(nd.b, d) << ")"; break;
          case FZ_IR_SELECT: o << "fz_select(" << val(nd.a) << ", " << opnd(nd.b, d) << ", " << opnd(nd.c, d) << ")"; break;
          case FZ_IR_WIDEN: o << "fz_cvt_d(" << val(nd.a) << ")"; break;
          case FZ_IR_NARROW: o << "fz_cvt_f(" << val(nd.a) << ")"; break;

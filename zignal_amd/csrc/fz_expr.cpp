@@ -72,7 +72,8 @@ std::vector<uint32_t> max_input_delays(const fz_expr* e)
       case EK::Parallel: return cat(max_input_delays(e->a), max_input_delays(e->b));              // :479-482
       case EK::Sequence:                                                                          // :483-492
          return cat(max_input_delays(e->a), drop(max_input_delays(e->b), (size_t)e->a->out_arity));
-      case EK::Neg: return max_input_delays(e->a);
+      case EK::Neg:
+      case EK::Fn1: return max_input_delays(e->a);
       case EK::Arith:
       case EK::Channel: return zipmax(max_input_delays(e->a), max_input_delays(e->b));            // :493-496
    }
@@ -116,7 +117,8 @@ static std::vector<int> min_input_delays(const fz_expr* e)
       case EK::Feedback: return dropn(min_input_delays(e->a), (size_t)e->a->out_arity);
       case EK::Parallel: return catn(min_input_delays(e->a), min_input_delays(e->b));
       case EK::Sequence: return catn(min_input_delays(e->a), dropn(min_input_delays(e->b), (size_t)e->a->out_arity));
-      case EK::Neg: return min_input_delays(e->a);
+      case EK::Neg:
+      case EK::Fn1: return min_input_delays(e->a);
       case EK::Arith:
       case EK::Channel: return zipmin(min_input_delays(e->a), min_input_delays(e->b));
    }
@@ -214,6 +216,7 @@ std::string serialize_expr(const fz_expr* root)
          case EK::Modulator: std::snprintf(buf, sizeof buf, "M %u\n", e->i); break;
          case EK::Arith: std::snprintf(buf, sizeof buf, "A %d %lu %lu\n", (int)e->op, a, b); break;
          case EK::Neg: std::snprintf(buf, sizeof buf, "N %lu\n", a); break;
+         case EK::Fn1: std::snprintf(buf, sizeof buf, "G %d %lu\n", (int)e->op, a); break;   // abs, sqrt, exp, tanh (min / max: "A")
          case EK::Channel: std::snprintf(buf, sizeof buf, "C %lu %lu\n", a, b); break;
          case EK::Parallel: std::snprintf(buf, sizeof buf, "B %lu %lu\n", a, b); break;
          case EK::Sequence: std::snprintf(buf, sizeof buf, "S %lu %lu\n", a, b); break;
@@ -259,6 +262,9 @@ fz_expr* parse_expr(const std::string& text)
          case 'M': if (std::sscanf(s, "%u", &i) == 1) e = fz_modulator(i); break;
          case 'A': if (std::sscanf(s, "%d %lu %lu", &op, &a, &b) == 3 && ref(a) && ref(b)) e = fz_arith((fz_op)op, ref(a), ref(b)); break;
          case 'N': if (std::sscanf(s, "%lu", &a) == 1 && ref(a)) e = fz_arith(FZ_OP_NEG, ref(a), nullptr); break;
+         case 'G':
+            if (std::sscanf(s, "%d %lu", &op, &a) == 2 && ref(a) && op >= FZ_OP_ABS && op <= FZ_OP_TANH) e = fz_arith((fz_op)op, ref(a), nullptr);
+            break;
          case 'C': if (std::sscanf(s, "%lu %lu", &a, &b) == 2 && ref(a) && ref(b)) e = fz_channel(ref(a), ref(b)); break;
          case 'B': if (std::sscanf(s, "%lu %lu", &a, &b) == 2 && ref(a) && ref(b)) e = fz_parallel(ref(a), ref(b)); break;
          case 'S': if (std::sscanf(s, "%lu %lu", &a, &b) == 2 && ref(a) && ref(b)) e = fz_sequence(ref(a), ref(b)); break;
@@ -425,8 +431,17 @@ fz_expr* fz_arith(fz_op op, fz_expr* a, fz_expr* b)
          Hold sum{check(fz_arith(FZ_OP_ADD, ta.e, tb.e))};
          return check(fz_arith(FZ_OP_NE, sum.e, zero.e));
       }
+      // the unary graph functions (std::fabs, std::sqrt, std::exp, std::tanh): a node of their own kind, like the negation
+      if (op >= FZ_OP_ABS && op <= FZ_OP_TANH) {
+         if (a->out_arity != 1) fail(FZ_E_GRAPH, "function operand must have exactly one output wire");
+         auto* e = mk(EK::Fn1, a);
+         e->op = op;
+         e->in_arity = a->in_arity;
+         return e;
+      }
       if (!b) fail(FZ_E_INVALID, "null operand");
-      if (!((op >= FZ_OP_ADD && op <= FZ_OP_DIV) || (op >= FZ_OP_LT && op <= FZ_OP_NE))) fail(FZ_E_INVALID, "unknown arithmetic operator");
+      if (!((op >= FZ_OP_ADD && op <= FZ_OP_DIV) || (op >= FZ_OP_LT && op <= FZ_OP_NE) || op == FZ_OP_MIN || op == FZ_OP_MAX))
+         fail(FZ_E_INVALID, "unknown arithmetic operator");
       if (a->out_arity != 1 || b->out_arity != 1)
          fail(FZ_E_GRAPH, "arithmetic operand must have exactly one output wire");
       auto* e = mk(EK::Arith, a, b);

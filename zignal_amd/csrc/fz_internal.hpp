@@ -25,7 +25,8 @@ struct Error {
 [[noreturn]] void fail(int code, const std::string& msg);
 
 // ---- expression tree (the EDSL surface, flowz.hpp:68-93) ---------------------------------------
-enum class EK : uint8_t { Placeholder, Delayed, Literal, Uniform, Param, Arith, Neg, Channel, Parallel, Sequence, Feedback, Modulator };
+enum class EK : uint8_t { Placeholder, Delayed, Literal, Uniform, Param, Arith, Neg, Channel, Parallel, Sequence, Feedback, Modulator,
+                          Fn1 };   // Fn1: a unary graph function (op = FZ_OP_ABS .. FZ_OP_TANH); min / max are Arith nodes
 
 }  // namespace fz
 
@@ -127,6 +128,9 @@ struct Graph {
    std::vector<double> consts64;     // float64 literal terminals
    std::map<uint32_t, uint32_t> uniform_slot;   // fz_uniform id -> coefficient slot (never shared)
    uint32_t n_state = 0, max_delay = 0, n_ops = 0, n_lds_slots = 0;
+   // n_ops weighted by what a node costs in instructions, for the planner's thresholds: 1 for every operator (so the plans of graphs
+   // without functions stay what they were), more for the graph functions (fn_weight in fz_lower.cpp)
+   uint32_t op_weight = 0;
    std::vector<int> line_of_node;    // node -> line index or -1
    StageSplit split;                 // stage packing, when the graph allows it
    std::vector<FarRead> far_reads;   // distinct (far line, delay) pairs, in first-use order

@@ -119,6 +119,10 @@ struct Elab {
          case EK::Modulator: return {add(FZ_IR_MOD, -1, -1, 0.f, e->i)};
          case EK::Arith: {                                              // _default<eval_it> :769-772
             int a = one(e->a, ins), b = one(e->b, ins);
+            if (e->op == FZ_OP_MIN || e->op == FZ_OP_MAX) {              // std::min / std::max: in the operands' common type
+               if (imag_of.count(a) || imag_of.count(b)) fail(FZ_E_GRAPH, "std::min / std::max do not apply to std::complex wires (no operator< in C++)");
+               return {arith(e->op == FZ_OP_MIN ? FZ_IR_MIN : FZ_IR_MAX, a, b)};
+            }
             if (e->op >= FZ_OP_LT && e->op <= FZ_OP_NE) {               // a comparison: 1.0f / 0.0f, a float whatever was compared
                if (imag_of.count(a) || imag_of.count(b)) fail(FZ_E_GRAPH, "comparison operators do not apply to std::complex wires");
                return {add(FZ_IR_LT + (uint32_t)(e->op - FZ_OP_LT), a, b)};
@@ -133,6 +137,11 @@ struct Elab {
             int re = arith(FZ_IR_NEG, a);
             if (imag_of.count(a)) imag_of[re] = arith(FZ_IR_NEG, imag_of[a]);
             return {re};
+         }
+         case EK::Fn1: {                                                // std::fabs / sqrt / exp / tanh: in the operand's type
+            int a = one(e->a, ins);
+            if (imag_of.count(a)) fail(FZ_E_UNSUPPORTED, "abs, sqrt, exp and tanh of a std::complex wire are valid C++ but not built here");
+            return {arith(FZ_IR_ABS + (uint32_t)(e->op - FZ_OP_ABS), a)};
          }
          case EK::Channel: {                                            // :765-768 same inputs to both
             auto l = run(e->a, ins), r = run(e->b, ins);
@@ -360,6 +369,22 @@ uint64_t bits_of64(double f)
    return u;
 }
 
+// VALU instructions per stream-sample of a node for the planner (Graph::op_weight): 1 for every operator; the graph functions as
+// tools/isa_stats.py (valu_per_step) counts them in the kernel of a one-node graph: one stream per lane, float (tanh 74, exp 40,
+// sqrt 17, min 2.7); double is not measured and weighs the same
+uint32_t fn_weight(uint32_t kind, bool f64)
+{
+   (void)f64;
+   switch (kind) {
+      case FZ_IR_ABS: return 1;
+      case FZ_IR_MIN: case FZ_IR_MAX: return 3;
+      case FZ_IR_SQRT: return 17;
+      case FZ_IR_EXP: return 40;
+      case FZ_IR_TANH: return 74;
+      default: return 1;
+   }
+}
+
 }  // namespace
 
 Graph lower(const fz_expr* e, const LowerOptions& opt)
@@ -488,6 +513,8 @@ Graph lower(const fz_expr* e, const LowerOptions& opt)
             r.f64 = raw[(size_t)r.a].f64 || raw[(size_t)r.b].f64;
             break;
          case FZ_IR_NEG: r.f64 = raw[(size_t)r.a].f64; break;
+         case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH: r.f64 = raw[(size_t)r.a].f64; break;
+         case FZ_IR_MIN: case FZ_IR_MAX: r.f64 = raw[(size_t)r.a].f64 || raw[(size_t)r.b].f64; break;
          case FZ_IR_ABSLT: r.f64 = raw[(size_t)r.a].f64 || raw[(size_t)r.b].f64; break;
          case FZ_IR_SELECT: r.f64 = raw[(size_t)r.b].f64 || raw[(size_t)r.n].f64; break;
          case FZ_IR_CONST: break;
@@ -547,7 +574,8 @@ Graph lower(const fz_expr* e, const LowerOptions& opt)
                break;
             case FZ_IR_PARAM: case FZ_IR_MOD: key = {r.kind, -1, -1, -1, r.n}; break;
             case FZ_IR_DELAY: key = {r.kind, rep[(size_t)r.a], -1, -1, r.n}; break;
-            case FZ_IR_NEG: case FZ_IR_WIDEN: case FZ_IR_NARROW: key = {r.kind, rep[(size_t)r.a], -1, -1, 0}; break;
+            case FZ_IR_NEG: case FZ_IR_WIDEN: case FZ_IR_NARROW:
+            case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH: key = {r.kind, rep[(size_t)r.a], -1, -1, 0}; break;
             case FZ_IR_SELECT: key = {r.kind, rep[(size_t)r.a], rep[(size_t)r.b], rep[(size_t)r.n], 0}; break;
             default: key = {r.kind, rep[(size_t)r.a], rep[(size_t)r.b], -1, 0}; break;
          }
@@ -582,9 +610,11 @@ Graph lower(const fz_expr* e, const LowerOptions& opt)
          case FZ_IR_MOD: n.a = r.n; g.n_mod = std::max(g.n_mod, r.n + 1); break;
          case FZ_IR_DELAY: n.a = nid(r.a); n.b = r.n; break;
          case FZ_IR_NEG: case FZ_IR_WIDEN: case FZ_IR_NARROW: n.a = nid(r.a); ++g.n_ops; break;
+         case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH: n.a = nid(r.a); ++g.n_ops; break;
          case FZ_IR_SELECT: n.a = nid(r.a); n.b = nid(r.b); n.c = nid((int)r.n); ++g.n_ops; break;
          default: n.a = nid(r.a); n.b = nid(r.b); ++g.n_ops; break;
       }
+      if (n.kind >= FZ_IR_ADD && n.kind != FZ_IR_DELAY && n.kind != FZ_IR_MOD) g.op_weight += fn_weight(n.kind, n.f64);
    }
    g.n_in = n_in;
    g.typed = opt.typed;

@@ -173,7 +173,7 @@ static bool lockstep_default(const Graph& g, Variant& v, uint64_t n_streams, uin
          g.n_lds_slots == 0 && !((g.typed || far) && (n_streams % 4)) && !(far && (wide || g.far_min_read < 4))))
       return false;
    const uint32_t cap = wide ? 1u : allow_lockstep >= 3 ? 4u : allow_lockstep;
-   const TmGeometry geo = time_major_geometry(n_streams, cap, g.n_ops > 30, !g.typed && !far);
+   const TmGeometry geo = time_major_geometry(n_streams, cap, g.op_weight > 30, !g.typed && !far);
    v.P = geo.P;
    // wide frames: one row per buffer in one lap; in several laps chunks of THREE rows (the 4-wire sum at 1 M streams, rows 16 MiB apart:
    // 14.09-14.17 ms against 14.52-14.55 with two, 14.8 with four, 14.4-14.6 with five to seven; profiles/r05/lane_groups.txt)
@@ -203,13 +203,13 @@ static Variant resolve_stream_major(const Graph& g, const Request& rq, Variant v
    //  one-stream body was level or ahead on every bench line since -- +1 ... +5 %, never behind: profiles/NOTES.md "Round 6")
    const bool enough = n_streams >= (1u << 19);
    if (!uv_has_shape(uv) && g.n_in == 1 && g.n_out == 1 && g.n_lds_slots == 0 && g.far_lines.empty() && g.n_param <= 32 && g.n_mod == 0 &&
-       !g.typed && g.n_ops > 27 && g.n_state <= 20 && enough && n_streams % 2 == 0 && n_samples >= 256) {
+       !g.typed && g.op_weight > 27 && g.n_state <= 20 && enough && n_streams % 2 == 0 && n_samples >= 256) {
       v.P = 2;
       v.flags |= FZ_VF_SM_LONG;
    }
    // stage packing (one stream per lane) carries over; automatic only for graphs deep enough to be VALU-bound with one stream per lane
    if (v.P != 1 || !g.split.ok) v.flags &= ~(uint32_t)FZ_VF_STAGE_PACK;
-   else if (!(uv && (uv->flags & FZ_VF_NO_STAGE_PACK)) && n_samples >= 16u * (g.split.atoms() - 1) && g.n_ops > 27) v.flags |= FZ_VF_STAGE_PACK;
+   else if (!(uv && (uv->flags & FZ_VF_NO_STAGE_PACK)) && n_samples >= 16u * (g.split.atoms() - 1) && g.op_weight > 27) v.flags |= FZ_VF_STAGE_PACK;
    const uint32_t nw = std::max<uint32_t>(std::max(g.n_in, g.n_out), 1);
    const bool long_ok = g.n_in == 1 && g.n_out == 1 && v.P == 1 && g.n_lds_slots == 0 && (!g.split.ok || g.split.atoms() <= 13);
    const bool pair_ok = g.n_in == 1 && g.n_out == 1 && v.P == 2 && g.n_lds_slots == 0 && !g.typed;
@@ -314,7 +314,7 @@ Variant resolve_variant(const Graph& g, const fz_variant* uv, uint64_t n_streams
       // -- where four tuples fit a workgroup's LDS (and its registers: finalize_variant checks after the build), for graphs the lone wave does not spend all
       // its time on arithmetic with (two boards: cascades of 2 / 4 / 6 stages +5-8 / +5 / +0-4 %, the cascade with a gain behind it +22 %, 40 960 streams +6 %,
       // the oscillator chain level; 8 stages -1 ... -2 %, 10 level: profiles/r06/config2_io_waves_default.txt)
-      if (n_streams > 32768 && n_streams <= 65536 && g.n_ops <= 64 && g.wave_roles(1)) {
+      if (n_streams > 32768 && n_streams <= 65536 && g.op_weight <= 64 && g.wave_roles(1)) {
          fz_variant q{1, rq.U ? rq.U : 16u, 0, v.flags | FZ_VF_IO_WAVE | FZ_VF_IO_WAVE2};
          const Variant r = resolve_variant(g, &q, n_streams, n_samples, tile_streams, allow_lockstep);
          if (r.block == 256) return r;
@@ -362,7 +362,7 @@ uint64_t lockstep_streams(const Graph& g, const fz_variant* uv, const Variant& v
 {
    // (tiles and LDS rings walk in lockstep at geometries of their own -- whole tiles, 256-lane workgroups: nothing is peeled off)
    if (uv_has_shape(uv) || !(v.flags & FZ_VF_LOCKSTEP) || (tile_streams && tile_streams < n_streams) || g.n_lds_slots) return n_streams;
-   return time_major_geometry(n_streams, v.P, g.n_ops > 30, !g.typed && g.far_lines.empty()).main_streams;
+   return time_major_geometry(n_streams, v.P, g.op_weight > 30, !g.typed && g.far_lines.empty()).main_streams;
 }
 
 // The kernel of the REMAINDER launch (the last `rem` streams of a plain time-major block whose laps cover whole workgroups only): one-wave

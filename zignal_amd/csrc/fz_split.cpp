@@ -433,12 +433,14 @@ static bool extract_part(const Graph& g, const std::vector<char>* before, const 
             if (op(n.a) < 0) return false;
             n.a = (uint32_t)op(n.a);
             ++r.n_ops;
+            ++r.op_weight;
             break;
          case FZ_IR_ADD: case FZ_IR_SUB: case FZ_IR_MUL: case FZ_IR_DIV:
             if (op(n.a) < 0 || op(n.b) < 0) return false;  // an operand from an earlier part that is not the cut wire
             n.a = (uint32_t)op(n.a);
             n.b = (uint32_t)op(n.b);
             ++r.n_ops;
+            ++r.op_weight;
             break;
          default: return false;                            // per-stream coefficients, modulators, typed nodes: not split
       }

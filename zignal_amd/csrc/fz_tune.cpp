@@ -157,7 +157,7 @@ std::vector<fz_variant> tune_candidates(const Graph& g, uint64_t n_streams, uint
       if (!(d.flags & FZ_VF_STAGE_PACK)) {
          for (uint32_t P : {d.P * 2, d.P / 2}) {                                                    // the next packing up and down, each at its own geometry
             if (P < 1 || P > 4 || n_streams % P) continue;
-            const TmGeometry o = time_major_geometry(n_streams, P, g.n_ops > 30, false, P);
+            const TmGeometry o = time_major_geometry(n_streams, P, g.op_weight > 30, false, P);
             if (o.P != P || o.main_streams != n_streams) continue;
             cands.push_back(fz_variant{P, o.U, o.lanes, FZ_VF_LOCKSTEP | G | (o.U == 1 ? (uint32_t)FZ_VF_PREFETCH3 : 0u)});
          }

@@ -21,6 +21,7 @@ A Program evaluates blocks on the GPU only (Program.run_block / Bank); there is 
 """
 from __future__ import annotations
 
+import builtins as _bi   # (the module's own abs / min / max are graph functions)
 import ctypes
 from typing import Iterable, Optional, Sequence
 
@@ -55,7 +56,7 @@ class Expr:
 
     def max_input_delays(self):
         n = C.check(C.lib.fz_max_input_delays(self._h, None, 0))
-        buf = (ctypes.c_uint32 * max(n, 1))()
+        buf = (ctypes.c_uint32 * _bi.max(n, 1))()
         C.check(C.lib.fz_max_input_delays(self._h, buf, n))
         return tuple(buf[i] for i in range(n))
 
@@ -86,9 +87,10 @@ class Expr:
     def logical_and(self, o): return self._ar(C.FZ_OP_AND, o)
     def logical_or(self, o): return self._ar(C.FZ_OP_OR, o)
     def logical_not(self): return Expr(C.lib.fz_arith(C.FZ_OP_NOT, self._h, None))
+    def __abs__(self): return Expr(C.lib.fz_arith(C.FZ_OP_ABS, self._h, None))     # std::fabs (graph function)
 
     def __bool__(self):
-        # (`_1 < _2` is an expression, not a Python truth value: `if a < b`, `max(a, b)`, `a and b` would silently take the wrong branch)
+        # (`_1 < _2` is an expression, not a Python truth value: `if a < b`, builtin `max(a, b)`, `a and b` would silently take the wrong branch)
         raise TypeError("a Flowz expression has no truth value: comparisons build graph nodes (use .logical_and / .logical_or / .logical_not to combine them)")
 
     # -- combinators -----------------------------------------------------------------------
@@ -108,7 +110,7 @@ class Placeholder(Expr):
 
     def __getitem__(self, d):
         """_i[_n] (reference syntax), _i[-n] (delay_expression.cpp:99-100 spelling) or _i[n]."""
-        n = d.index if isinstance(d, Placeholder) else abs(int(d))
+        n = d.index if isinstance(d, Placeholder) else _bi.abs(int(d))
         return Expr(C.lib.fz_delayed(self.index, n))
 
 
@@ -191,6 +193,51 @@ def seq(*xs) -> Expr:
     return r
 
 
+# ---- graph functions (include/flowz_hip.h, FZ_OP_ABS ..): std::fabs, std::sqrt, std::exp, std::tanh, std::min, std::max ---------
+def _fn1(op, a) -> Expr:
+    a = as_expr(a)                      # (held: a temporary's handle would be released before fz_arith retains it)
+    return Expr(C.lib.fz_arith(op, a._h, None))
+
+
+def _fn2(op, a, b) -> Expr:
+    a, b = as_expr(a), as_expr(b)
+    return Expr(C.lib.fz_arith(op, a._h, b._h))
+
+
+def abs(a) -> Expr:  # noqa: A001  (mirrors flowz::abs)
+    """std::fabs: the sign bit cleared"""
+    return _fn1(C.FZ_OP_ABS, a)
+
+
+def sqrt(a) -> Expr:
+    """std::sqrt, correctly rounded"""
+    return _fn1(C.FZ_OP_SQRT, a)
+
+
+def exp(a) -> Expr:
+    """std::exp: the library's algorithm, within 2 ulp"""
+    return _fn1(C.FZ_OP_EXP, a)
+
+
+def tanh(a) -> Expr:
+    """std::tanh: the library's algorithm, within 2 ulp, odd, |tanh| <= 1"""
+    return _fn1(C.FZ_OP_TANH, a)
+
+
+def min(a, b) -> Expr:  # noqa: A001  (mirrors flowz::min)
+    """std::min: (b < a) ? b : a, in the operands' common type; either side may be a scalar (a float literal)"""
+    return _fn2(C.FZ_OP_MIN, a, b)
+
+
+def max(a, b) -> Expr:  # noqa: A001  (mirrors flowz::max)
+    """std::max: (a < b) ? b : a, in the operands' common type; either side may be a scalar (a float literal)"""
+    return _fn2(C.FZ_OP_MAX, a, b)
+
+
+_FN1 = {"abs": C.FZ_OP_ABS, "sqrt": C.FZ_OP_SQRT, "exp": C.FZ_OP_EXP, "tanh": C.FZ_OP_TANH}
+_FN2 = {"min": C.FZ_OP_MIN, "max": C.FZ_OP_MAX}
+
+
 _CMP_OPS = {"lt": C.FZ_OP_LT, "le": C.FZ_OP_LE, "gt": C.FZ_OP_GT, "ge": C.FZ_OP_GE, "eq": C.FZ_OP_EQ, "ne": C.FZ_OP_NE, "and": C.FZ_OP_AND, "or": C.FZ_OP_OR}
 
 
@@ -209,12 +256,14 @@ def from_sexpr(e) -> Expr:
     if k == "neg": return -from_sexpr(e[1])
     if k == "not": return from_sexpr(e[1]).logical_not()
     if k == "fb": return ~from_sexpr(e[1])
+    if k in _FN1: return _fn1(_FN1[k], from_sexpr(e[1]))
     a, b = from_sexpr(e[1]), from_sexpr(e[2])
     if k == "add": return a + b
     if k == "sub": return a - b
     if k == "mul": return a * b
     if k == "div": return a / b
     if k in _CMP_OPS: return a._ar(_CMP_OPS[k], b)
+    if k in _FN2: return _fn2(_FN2[k], a, b)
     if k == "chan": return chan(a, b)
     if k == "par": return a | b
     if k == "seq": return a >> b
@@ -265,7 +314,7 @@ class Program:
             # ResultType semantics (flowz.hpp:585-644): wire types carried through inputs, state and outputs
             n = self.expr.ins
             dts = list(in_dtypes) if in_dtypes is not None else ["f32"] * n
-            arr = (ctypes.c_uint32 * max(len(dts), 1))(*[C.DTYPES[d] for d in dts])
+            arr = (ctypes.c_uint32 * _bi.max(len(dts), 1))(*[C.DTYPES[d] for d in dts])
             C.check(C.lib.fz_compile_typed(self.expr._h, arr, len(dts), ctypes.byref(h)))
         else:
             C.check(C.lib.fz_compile(self.expr._h, ctypes.byref(h)))
@@ -302,7 +351,7 @@ class Program:
     # -- inspection ------------------------------------------------------------------------
     def ir(self):
         n = C.check(C.lib.fz_program_ir(self._h, None, 0))
-        buf = (C.IrNode * max(n, 1))()
+        buf = (C.IrNode * _bi.max(n, 1))()
         C.check(C.lib.fz_program_ir(self._h, buf, n))
         # 4th field: the literal of a 'const' node; the third operand of a 'select' node (a != 0 ? b : c)
         return [(C.IR_KINDS[buf[i].kind], buf[i].a, buf[i].b,
@@ -312,19 +361,19 @@ class Program:
     def ir_dtypes(self):
         """per IR node: 'f32' or 'f64' (the node's C++ arithmetic type)"""
         n = C.check(C.lib.fz_program_ir(self._h, None, 0))
-        buf = (C.IrNode * max(n, 1))()
+        buf = (C.IrNode * _bi.max(n, 1))()
         C.check(C.lib.fz_program_ir(self._h, buf, n))
         return ["f64" if buf[i].dtype else "f32" for i in range(n)]
 
     def outputs(self):
-        buf = (ctypes.c_uint32 * max(self.n_out, 1))()
+        buf = (ctypes.c_uint32 * _bi.max(self.n_out, 1))()
         C.check(C.lib.fz_program_outputs(self._h, buf, self.n_out))
         return [buf[i] for i in range(self.n_out)]
 
     def output_dtypes(self):
         """'f32' / 'f64' / 'cf32' per output WIRE: its C++ type before narrowing to the float32 frame
         (a 'cf32' wire, std::complex<float>, takes two frame slots: re, im)."""
-        buf = (ctypes.c_uint32 * max(self.n_out, 1))()
+        buf = (ctypes.c_uint32 * _bi.max(self.n_out, 1))()
         C.check(C.lib.fz_program_output_dtypes(self._h, buf, self.n_out))
         names = {0: "f32", 1: "f64", 2: "cf32", 4: "f64", 6: "cf64", 10: "cf64"}   # the first slot of a wire names it
         return [names[buf[i]] for i in range(self.n_out) if buf[i] in names]
@@ -334,13 +383,13 @@ class Program:
         of a complex wire, 4 / 5 low / high word of a double wire (typed programs), 6 / 7 / 8 / 9 low / high word of the
         real, low / high word of the imaginary part of a std::complex<double> wire (typed programs), 10 / 11 re / im of a
         std::complex<double> wire narrowed to the float frame (compile())"""
-        buf = (ctypes.c_uint32 * max(self.n_out, 1))()
+        buf = (ctypes.c_uint32 * _bi.max(self.n_out, 1))()
         C.check(C.lib.fz_program_output_dtypes(self._h, buf, self.n_out))
         return [buf[i] for i in range(self.n_out)]
 
     def input_dtypes(self):
         """'f32' / 'f64' / 'cf32' per input WIRE (typed programs; all 'f32' otherwise)"""
-        n = max(self.n_in_wires, 1)
+        n = _bi.max(self.n_in_wires, 1)
         buf = (ctypes.c_uint32 * n)()
         k = C.check(C.lib.fz_program_input_dtypes(self._h, buf, n))
         return [("f32", "f64", "cf32", "cf64")[buf[i]] for i in range(k)]
@@ -348,14 +397,14 @@ class Program:
     def line_dtypes(self):
         """storage type per delay line (in lines() order): 'f32', 'f64' (two state rows per slot), 're' / 'im' (the
         float lines of a std::complex<float> wire)"""
-        n = max(self.n_lines, 1)
+        n = _bi.max(self.n_lines, 1)
         buf = (ctypes.c_uint32 * n)()
         k = C.check(C.lib.fz_program_line_dtypes(self._h, buf, n))
         return [("f32", "f64", "re", "im", "re64", "im64")[buf[i]] for i in range(k)]
 
     def lines(self):
         n = self.n_lines
-        s, d = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+        s, d = (ctypes.c_uint32 * _bi.max(n, 1))(), (ctypes.c_uint32 * _bi.max(n, 1))()
         C.check(C.lib.fz_program_lines(self._h, s, d, n))
         return [(s[i], d[i]) for i in range(n)]
 
@@ -428,7 +477,7 @@ class Program:
     def tune_candidates(self, n_streams: int, n_samples: int, tile_streams: int = 0):
         """The variants Program.tune would measure for this shape (the first one is the library default)."""
         n = C.check(C.lib.fz_program_tune_candidates(self._h, int(n_streams), int(n_samples), int(tile_streams), None, 0))
-        buf = (Variant * max(n, 1))()
+        buf = (Variant * _bi.max(n, 1))()
         C.check(C.lib.fz_program_tune_candidates(self._h, int(n_streams), int(n_samples), int(tile_streams), buf, n))
         return [Variant(buf[i].streams_per_lane, buf[i].unroll, buf[i].block_threads, buf[i].flags) for i in range(n)]
 
@@ -467,7 +516,7 @@ class Program:
         more samples than the block): fz_run_block_window.  state advances; params as for run_block."""
         import torch
 
-        _check_frames(x, max(self.n_in, 1))
+        _check_frames(x, _bi.max(self.n_in, 1))
         if x.dim() == 4:
             n_tiles, rows, tile, _ = x.shape
             ns = n_tiles * tile
@@ -495,15 +544,15 @@ class Program:
 
         if x.dim() == 2:
             x = x.unsqueeze(-1)
-        _check_frames(x, max(self.n_in, 1))
+        _check_frames(x, _bi.max(self.n_in, 1))
         ns, rows, _ = x.shape
         n = rows - row0 if n_samples is None else int(n_samples)
         if out is None:
             out = torch.empty((ns, rows, self.n_out), dtype=torch.float32, device=x.device)
         if state is None:
-            state = torch.zeros((max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
+            state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
         _check_dev(out, (ns, rows, self.n_out), "out")
-        _check_dev(state, (max(self.n_state, 1), ns), "state")
+        _check_dev(state, (_bi.max(self.n_state, 1), ns), "state")
         pp = _check_dev(params, (self.n_param, ns), "params").data_ptr() if self.n_param else None
         vp = ctypes.byref(variant) if variant is not None else None
         C.check(C.lib.fz_run_block_stream_major(self._h, x.data_ptr() if self.n_in else None, out.data_ptr(),
@@ -540,7 +589,7 @@ class Program:
             out = torch.empty(oshape, dtype=odt, device=x.device)
         _check_dev(out, oshape, "out", odt)
         if state is None:
-            state = torch.zeros((max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
+            state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
         if self.n_state:
             _check_dev(state, (self.n_state, ns), "state")
         pp = None
@@ -573,9 +622,9 @@ def _tune(self, x, state=None, params=None, out=None):
     if out is None:
         out = torch.empty(oshape, dtype=torch.float32, device=x.device)
     if state is None:
-        state = torch.zeros((max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
+        state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
     _check_dev(out, oshape, "out")
-    _check_dev(state, (max(self.n_state, 1), ns), "state")
+    _check_dev(state, (_bi.max(self.n_state, 1), ns), "state")
     pp = _check_dev(params, (self.n_param, ns), "params").data_ptr() if self.n_param else None
     chosen, ms = Variant(0, 0, 0, 0), ctypes.c_float(0)
     C.check(C.lib.fz_program_tune(self._h, x.data_ptr() if self.n_in else None, out.data_ptr(),
@@ -618,7 +667,7 @@ class Bank:
         (CUDA float32 [n_blocks, n_param, n_streams]); fz_bank_process_blocks."""
         import torch
 
-        _require(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[-1] == max(self.prog.n_in, 1), "x: wrong shape, dtype, layout or device for this call")
+        _require(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[-1] == _bi.max(self.prog.n_in, 1), "x: wrong shape, dtype, layout or device for this call")
         rows, tile = (x.shape[1], x.shape[2]) if x.dim() == 4 else (x.shape[0], 0)
         ns = x.shape[0] * x.shape[2] if x.dim() == 4 else x.shape[1]
         if ns != self.n_streams:
@@ -651,7 +700,7 @@ class Bank:
             if out is None:
                 out = np.empty((self.n_streams, T, self.prog.n_out), np.float32)
             xp, op = x.ctypes.data, out.ctypes.data
-        _require(tuple(x.shape) in ((self.n_streams, T, max(self.prog.n_in, 1)), (self.n_streams, T)), x.shape)
+        _require(tuple(x.shape) in ((self.n_streams, T, _bi.max(self.prog.n_in, 1)), (self.n_streams, T)), x.shape)
         _require(tuple(out.shape) == (self.n_streams, T, self.prog.n_out) and (out.is_contiguous() if is_torch else out.flags.c_contiguous), "out: wrong shape, dtype, layout or device for this call")
         _require((out.dtype == torch.float32) if is_torch else (out.dtype == np.float32), "out: wrong shape, dtype, layout or device for this call")
         C.check(C.lib.fz_bank_process_host_stream_major(self._h, xp if self.prog.n_in else None, op, T))
@@ -757,7 +806,7 @@ def manifest_build(path: str, workers: int = 0) -> dict:
     import os
     import tempfile
 
-    workers = workers or max(1, len(os.sched_getaffinity(0)))
+    workers = workers or _bi.max(1, len(os.sched_getaffinity(0)))
     counts = (ctypes.c_uint32 * 4)()
     if path.endswith(".gz"):
         with tempfile.NamedTemporaryFile(suffix=".fzm") as tmp:

@@ -245,6 +245,56 @@ def complex_one_pole(c=(0.6, 0.7)):
     return fb(add(mul(litc(*c), DEL(1, 1)), IN(2)))
 
 
+# ---- graph functions (abs, sqrt, exp, tanh, min, max): nonlinear filters.  Not BASELINE graphs: bench.py does not run them ----------
+def fn(name, *args):
+    """('abs'|'sqrt'|'exp'|'tanh', a) or ('min'|'max', a, b): std::fabs, std::sqrt, std::exp, std::tanh, std::min, std::max"""
+    return (name, *args)
+
+
+def uniform(k, initial):
+    return ("uniform", k, float(F32(initial)))
+
+
+MOOG_RESONANCE = F32(1.5)
+SOFT_CLIP = (F32(0.2), F32(-0.3), F32(1.1), F32(0.2), F32(-0.8))
+
+
+def moog_ladder(k=MOOG_RESONANCE):
+    """A Moog-style transistor ladder: four one-pole stages, each driven through tanh, and the global feedback through tanh.
+    The cutoff g is per-stream parameter 0, the resonance k uniform coefficient 0.  With y_i' the stage's value one sample ago:
+        u  = tanh(x - k*y4')
+        y1 = y1' + g*(u - tanh(y1'))          y_i = y_i' + g*(tanh(y_{i-1}) - tanh(y_i'))   (i = 2, 3, 4)
+    as one feedback over the four stage wires, the output y4:  ~( y1, y2, y3, y4 ) |= _4  (x is the loop's external input _5)."""
+    g, kk = param(0), uniform(0, k)
+    y = [DEL(i, 1) for i in range(1, 5)]
+    u = fn("tanh", sub(IN(5), mul(kk, y[3])))
+    n = [add(y[0], mul(g, sub(u, fn("tanh", y[0]))))]
+    for i in range(1, 4):
+        n.append(add(y[i], mul(g, sub(fn("tanh", n[i - 1]), fn("tanh", y[i])))))
+    return seq(fb(chan(*n)), IN(4))
+
+
+def soft_clip_biquad(b0, b1, b2, a1, a2):
+    """DF1 biquad whose recursion runs through tanh:  fwd |= ~tanh( _2 + a1*_1[_1] + a2*_1[_2] )"""
+    return seq(fwd(b0, b1, b2), fb(fn("tanh", add(add(IN(2), mul(lit(a1), DEL(1, 1))), mul(lit(a2), DEL(1, 2))))))
+
+
+def soft_clip_cascade(n=4, coeffs=SOFT_CLIP):
+    """n soft-clipping DF1 biquads in series"""
+    return seq(*[soft_clip_biquad(*coeffs) for _ in range(n)])
+
+
+ENV_ATTACK, ENV_RELEASE = F32(0.5), F32(0.01)
+
+
+def envelope_follower(attack=ENV_ATTACK, release=ENV_RELEASE):
+    """Peak envelope follower: r = |x|, then a one-pole that rises with the attack coefficient and falls with the release one:
+        e = max(e' + attack*(r - e'), e' + release*(r - e'))     i.e.  abs(_1) |= ~max(_1[_1] + a*(_2 - _1[_1]), _1[_1] + r*(_2 - _1[_1]))"""
+    e, r = DEL(1, 1), IN(2)
+    d = sub(r, e)
+    return seq(fn("abs", IN(1)), fb(fn("max", add(e, mul(lit(attack), d)), add(e, mul(lit(release), d)))))
+
+
 # ---- synthetic inputs and per-stream coefficients (SURVEY 8d) -------------------------------------------
 SEED = 20160512
 
