@@ -4,8 +4,10 @@ exp and tanh follow the kernels' algorithm operation for operation (include/flow
 the operand's type, no FMA, no libm.  numpy float32 / float64 arrays round every operation the same way, so the restatement gives
 the kernels' bits for every non-NaN result.  The constants below are the ones zignal_amd/csrc/fz_codegen.cpp prints.
 
-The evaluator follows tests/ir_interp.py (which it does not change): one delay line per delayed wire, row (row0 + j) of a line holds
-the wire's value j + 1 samples ago, float32 rows for the untyped programs it is used with here.  The hand-written recurrences at the
+The evaluator follows tests/ir_interp.py (which it does not change): one delay line per delayed wire, row (row0 + j) of a float line
+holds the wire's value j + 1 samples ago; a double line (typed programs) takes two float rows per slot, slot j being ONE row of
+n_streams doubles over float rows (row0 + 2j, row0 + 2j + 1).  Double input wires are (low word, high word) frame slots, double
+outputs of typed programs leave as such slot pairs; sample-rate modulators are rows of a [n_mod, T] array.  The hand-written recurrences at the
 end restate the workloads of zignal_amd/workloads.py from their equations, not from the IR, so they check the lowering too.
 """
 import numpy as np
@@ -123,29 +125,42 @@ _UN = {"neg": np.negative, "abs": fabs, "sqrt": sqrt, "exp": exp, "tanh": tanh}
 _CMP = {"lt": np.less, "le": np.less_equal, "gt": np.greater, "ge": np.greater_equal, "eq": np.equal, "ne": np.not_equal}
 
 
-def run_ir(prog, x, params=None, state=None):
-    """Evaluate an untyped program (float32 delay lines) on frames x [T, n_streams, n_in] from `state` (None: zeros, else
-    [n_state, n_streams]).  Returns (y [T, n_streams, n_out] float32, the state after the block)."""
+def run_ir(prog, x, params=None, state=None, mod=None, out_f64=False):
+    """Evaluate a program on frames x [T, n_streams, n_in slots] from `state` (None: zeros, else [n_state, n_streams] float32 rows).
+    mod: [n_mod, >= T], sample t reads mod[k][t] (as Program.set_modulation rows from the block's first sample).  out_f64: float64
+    output frames (FZ_VF_OUT_F64: double results unrounded).  Returns (y [T, n_streams, n_out], the state after the block)."""
     x = np.asarray(x, F32)
     if x.ndim == 2:
         x = x[:, :, None]
     Tn, ns, _ = x.shape
-    ir, dts, outs = prog.ir(), prog.ir_dtypes(), prog.outputs()
+    ir, dts, outs, codes = prog.ir(), prog.ir_dtypes(), prog.outputs(), prog.output_slot_codes()
     row0, r = {}, 0
-    for src, depth in prog.lines():
-        row0[src] = (r, depth)
-        r += depth
+    for (src, depth), ldt in zip(prog.lines(), prog.line_dtypes()):
+        f64 = ldt == "f64"
+        assert ldt in ("f32", "f64"), ldt
+        row0[src] = (r, depth, f64)
+        r += depth * (2 if f64 else 1)
     st = np.zeros((max(r, 1), ns), F32) if state is None else np.array(state, F32, copy=True)
-    y = np.empty((Tn, ns, len(outs)), F32)
+    flat = st.reshape(-1)
+
+    def drow(rr):                                          # the row of ns doubles that starts at float row rr
+        return flat[rr * ns:(rr + 2) * ns].view(F64)
+
+    y = np.empty((Tn, ns, len(outs)), F64 if out_f64 else F32)
     with np.errstate(all="ignore"):
         for t in range(Tn):
             v = [None] * len(ir)
             for i, (kind, a, b, val) in enumerate(ir):
                 T = F64 if dts[i] == "f64" else F32
-                if kind == "input": r_ = x[t, :, a]
+                if kind == "input":
+                    r_ = np.stack([x[t, :, a], x[t, :, a + 1]], -1).view(F64)[:, 0] if T == F64 else x[t, :, a]
                 elif kind == "const": r_ = np.full(ns, T(val), T)
                 elif kind == "param": r_ = np.asarray(params[a], F32)
-                elif kind == "delay": r_ = st[row0[a][0] + b - 1].copy()
+                elif kind == "mod": r_ = np.full(ns, F32(mod[a][t]), F32)
+                elif kind == "delay":
+                    r0, depth, f64 = row0[a]
+                    assert 1 <= b <= depth and f64 == (T == F64)
+                    r_ = drow(r0 + 2 * (b - 1)).copy() if f64 else st[r0 + b - 1].copy()
                 elif kind in _BIN: r_ = _BIN[kind](v[a].astype(T), v[b].astype(T))
                 elif kind in _UN: r_ = _UN[kind](v[a].astype(T))
                 elif kind in _CMP:
@@ -155,10 +170,18 @@ def run_ir(prog, x, params=None, state=None):
                     raise NotImplementedError(kind)
                 v[i] = np.asarray(r_).astype(T)
             for j, o in enumerate(outs):
-                y[t, :, j] = v[o].astype(F32)
-            for src, (r0, depth) in row0.items():         # pushes last: every read above saw the previous samples
-                st[r0 + 1:r0 + depth] = st[r0:r0 + depth - 1].copy()
-                st[r0] = v[src].astype(F32)
+                if codes[j] in (4, 5):                     # a double wire of a typed program: its low / high word
+                    y[t, :, j] = np.ascontiguousarray(v[o], F64)[:, None].view(F32)[:, codes[j] - 4]
+                else:
+                    y[t, :, j] = v[o].astype(y.dtype)
+            for src, (r0, depth, f64) in row0.items():    # pushes last: every read above saw the previous samples
+                if f64:
+                    for k in range(depth - 1, 0, -1):
+                        drow(r0 + 2 * k)[:] = drow(r0 + 2 * (k - 1))
+                    drow(r0)[:] = v[src]
+                else:
+                    st[r0 + 1:r0 + depth] = st[r0:r0 + depth - 1].copy()
+                    st[r0] = v[src].astype(F32)
     return y, st
 
 

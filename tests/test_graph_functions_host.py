@@ -235,3 +235,88 @@ def test_cpp_front_end_graph_functions():
     out = subprocess.run([build_cpp("test_fn_host")], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "all graph-function host checks passed" in out.stdout
+
+
+# ---- the kernel bodies function graphs reach (tests/fn_bodies.py; run on the GPU by test_graph_functions_bodies_gpu.py) ----------
+def test_body_matrix_cells_resolve_to_their_bodies():
+    """every cell of the GPU matrix runs the body it is there for, and the block after its cut another one"""
+    import fn_bodies as B
+    for c in B.CELLS:
+        prog = B.graph(c[1])
+        assert B.cell_name(prog, c) == c[7], c[0]
+        assert prog.kernel_name(B.variant(c[9], c[2]), c[4], c[5], c[6]) != c[7], c[0]
+
+
+def test_default_plan_sends_function_graphs_to_the_matrix_bodies():
+    """the library's own choice for the function graphs at full size -- among them the LDS-ring lockstep step-down (one row per chunk,
+    three buffers) at 2^27 streams: every one of these bodies is a cell of the GPU matrix"""
+    import fn_bodies as B
+    cells = {(c[1], c[7]) for c in B.CELLS}
+    for name, ns, T, tile, sm, want in B.DEFAULT_BODIES:
+        prog = B.graph(name)
+        assert B.default_name(prog, ns, T, tile, sm, name in B.OUT_F64) == want, (name, ns, T, tile, sm)
+        if not sm:
+            assert prog.kernel_name(None, ns, T, tile) == want, (name, ns, T, tile)
+        assert any(w.startswith(want.rstrip("M")) for _, w in cells), want
+    f64 = B.graph("f64lit")
+    assert B.default_name(f64, 1 << 20, 4096, 0, False, True) == "fz_block_kernel_p4u1b1024f%dL" % (B.L | B.GS | B.P3 | B.OUT64)
+
+
+@pytest.mark.parametrize("ns", [16384, 40000, 65536, 65600])
+def test_flags_only_lockstep_request_resolves_to_the_frame_kernel(ns):
+    """a variant that asks for the lockstep frame kernel by its flags alone gets it at every stream count -- also where the library's own
+    choice is a wave-split kernel (<= 65 536 streams), which takes neither flag"""
+    p = F.compile(F.from_sexpr(W.df1_cascade(6)))
+    L, GS, SP = F.C.FZ_VF_LOCKSTEP, F.C.FZ_VF_GRID_SYNC, F.C.FZ_VF_STAGE_PACK
+    for T in (4096, 1100):
+        assert p.kernel_name(F.make_variant(0, 0, 0, L), ns, T) == "fz_block_kernel_p1u16b256s6f%d" % (L | SP)
+        assert p.kernel_name(F.make_variant(0, 0, 0, L | GS), ns, T) == "fz_block_kernel_p1u16b256s6f%d" % (L | GS | SP)
+    if ns <= 65536:                                            # (the library's own choice there stays the wave-split kernel)
+        assert re.search(r"b\d+w\d", p.kernel_name(None, ns, 4096))
+
+
+# ---- the evaluator on typed programs and modulators ---------------------------------------------------------------------------
+def test_evaluator_double_lines_and_modulators_agree_with_ir_interp():
+    """fn_ref.run_ir on function-free programs with double delay lines (typed) and sample-rate modulators: the bits and the state of
+    tests/ir_interp.py"""
+    import graphs as G
+    import ir_interp
+    rng = np.random.default_rng(11)
+    ns, T = 24, 40
+    t = F.compile(F.from_sexpr(W.df1_double()), typed=True)
+    a = rng.standard_normal((T, ns)) * 2
+    x = F.pack_typed([a], t.input_dtypes())
+    st0 = ir_interp.run_ir(t, x[:7])[1]
+    for args in ({}, {"state": st0}):
+        y1, s1 = R.run_ir(t, x, **args)
+        y2, s2 = ir_interp.run_ir(t, x, **args)
+        assert "f64" in t.line_dtypes() and np.array_equal(y1.view(np.uint32), y2.view(np.uint32)) and np.array_equal(s1.view(np.uint32), s2.view(np.uint32))
+    m = F.compile(F.from_sexpr(G.modulated_mix()))
+    x = rng.standard_normal((T, ns, m.n_in)).astype(F32)
+    mod = rng.uniform(-0.9, 0.9, (m.n_mod, T)).astype(F32)
+    y1, s1 = R.run_ir(m, x, mod=mod)
+    y2, s2 = ir_interp.run_ir(m, x, mod=mod)
+    assert np.array_equal(y1.view(np.uint32), y2.view(np.uint32)) and np.array_equal(s1.view(np.uint32), s2.view(np.uint32))
+
+
+def test_evaluator_typed_tanh_loop_and_double_output_frames_follow_their_equations():
+    """y = tanh(0.9f * y[-1] + x) with a double input wire: a double recursion, its double output as two float words; tanh(0.5 * (x +
+    x[-3])) with the double literal on float64 output frames: the double result unrounded"""
+    import fn_bodies as B
+    rng = np.random.default_rng(12)
+    ns, T = 16, 30
+    p = B.graph("typed")
+    a = rng.standard_normal((T, ns)) * 3
+    y, st = R.run_ir(p, F.pack_typed([a], ["f64"]))
+    w, prev = np.empty((T, ns)), np.zeros(ns)
+    for t in range(T):
+        prev = R.tanh(F64(F32(0.9)) * prev + a[t])
+        w[t] = prev
+    assert np.array_equal(F.unpack_typed(y, ["f64"])[0].view(np.uint64), w.view(np.uint64))
+    assert np.array_equal(st.view(np.uint64).reshape(-1), w[-1].view(np.uint64))        # (one double row: two float rows)
+    p = B.graph("f64lit")
+    x = (rng.standard_normal((T, ns)) * 3).astype(F32)
+    y, _ = R.run_ir(p, x, out_f64=True)
+    xd = np.concatenate([np.zeros((3, ns), F32), x])
+    want = R.tanh(F64(0.5) * (xd[3:] + xd[:-3]).astype(F64))
+    assert y.dtype == F64 and np.array_equal(y[..., 0].view(np.uint64), want.view(np.uint64))

@@ -298,9 +298,10 @@ Variant resolve_variant(const Graph& g, const fz_variant* uv, uint64_t n_streams
       v.U = std::min(v.U, cap);
    }
    // few streams: the most parts whose waves still find a SIMD each (<= 16 384 streams: four or three, <= 32 768: two), with an I/O wave;
-   // up to 65 536: the whole graph in one compute wave next to two I/O waves
+   // up to 65 536: the whole graph in one compute wave next to two I/O waves.  (A caller's frame-kernel flag -- lockstep, grid sync -- keeps the
+   // frame kernel: the wave-split kernels take neither)
    if (!rq.P && !rq.B && n_samples >= 256 && (rq.U == 0 || rq.U == 8 || rq.U == 16 || rq.U == 32) &&
-       !(v.flags & (FZ_VF_STAGE_PACK | FZ_VF_NO_STAGE_PACK | FZ_VF_OUT_F64 | FZ_VF_PREFETCH3 | FZ_VF_STREAM_MAJOR))) {
+       !(v.flags & (FZ_VF_STAGE_PACK | FZ_VF_NO_STAGE_PACK | FZ_VF_OUT_F64 | FZ_VF_PREFETCH3 | FZ_VF_STREAM_MAJOR | FZ_VF_LOCKSTEP | FZ_VF_GRID_SYNC))) {
       uint32_t W = 0;
       if (n_streams <= 16384) W = g.wave_roles(4) ? 4 : g.wave_roles(3) ? 3 : 0;
       if (!W && n_streams <= 32768 && g.wave_roles(2)) W = 2;
