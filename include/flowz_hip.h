@@ -456,6 +456,80 @@ int fz_program_plan(fz_program* p, uint64_t n_streams, uint32_t tile_streams, fz
 int fz_program_tune_candidates(fz_program* p, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams, fz_variant* out, uint32_t cap);
 
 /* ------------------------------------------------------------------------------------------
+ * fz_run_block_grad -- the backward of ONE block (reverse mode).  The forward block maps
+ * (x[0..T), s0, p, c) to (y[0..T), s_T): x the input frames, s0 the state before the block, p the
+ * per-stream coefficients (fz_stream_param), c the uniform coefficient slots (literals and
+ * fz_uniform: fz_info.n_const).  Given ybar = dL/dy and (optionally) sbar_T = dL/ds_T it computes
+ * xbar, sbar0, pbar and cbar, where cbar is PER STREAM ([n_const][n_streams]: no reduction over the
+ * streams).  The result is the reverse-mode derivative of exactly the float32 computation of the
+ * forward kernels: the lowered IR (fz_program_ir) in evaluation order.
+ *
+ * Rules per node (g its adjoint, v its forward value, a / b its operands):
+ *   ADD  abar += g, bbar += g          SUB  abar += g, bbar -= g          NEG  abar -= g
+ *   MUL  abar += g*b, bbar += g*a      DIV  q = g/b; abar += q, bbar -= q*v
+ *   SQRT abar += g*(0.5/v)             EXP  abar += g*v                   TANH abar += g*(1 - v*v)
+ *   ABS  abar += g if a > 0, abar -= g if a < 0, nothing otherwise (a = +-0 or NaN)
+ *   MIN  (b < a) ? bbar += g : abar += g      MAX  (a < b) ? bbar += g : abar += g   -- all of g to the operand std::min /
+ *        std::max returned (their NaN and signed-zero rules decide which)
+ *   LT .. NE (and !, &&, || after lowering): derivative zero, NO arithmetic -- an infinite or NaN adjoint never leaks through a
+ *        comparison; a node that only feeds comparisons has no adjoint and contributes nothing either.
+ *   CONST slot k: cbar[k] += g (equal literal bit patterns share a slot: its cbar sums all uses -- the derivative with respect to
+ *        the slot's value, which fz_program_set_const changes for every use at once); PARAM k: pbar[k] += g; INPUT wire w: xbar[w] = g
+ *        (the sum of the wire's input nodes in node order; +0 for a wire no adjoint reaches).
+ * Delay lines: the adjoint state has exactly the layout of the state (fz_program_lines): row start + j holds the adjoint of the
+ * wire's value at t-1-j.  sbar_T comes in that layout and sbar0 goes out in it, so blocks chain backwards: sbar0 of block k is the
+ * sbar_T of block k-1 (the same buffer may be passed as both).
+ *
+ * ORDER OF OPERATIONS (float32, one rounding per operation, no FMA).  Rows t = T-1 down to 0.  At row t every node's adjoint starts
+ * as -0.0f (the identity of IEEE addition: the first contribution IS the adjoint, bit for bit) and receives, in this order:
+ *   1. the ybar of every output slot that names the node, in slot order;
+ *   2. the pending line adjoint: for the line whose source the node is, row `start` of the adjoint state after row t;
+ *      then that line's rows move one up (row start + j - 1 := row start + j) and its deepest row becomes -0.0f;
+ *   3. the contributions of its consumers, in DECREASING node order (a consumer gives to operand a, then to operand b;
+ *      a contribution is formed -- e.g. g*b -- before it is added).
+ * Then, in the same decreasing walk, the node's finished adjoint g goes on: a DELAY node adds g into the adjoint state row it
+ * reads, a PARAM / CONST node adds g into its pbar / cbar accumulator (one addition per row and node: the step's adjoint is
+ * formed before it is added).  The accumulators run over the rows T-1 .. 0 starting from what the caller passed in, so the bits
+ * depend on the inputs only -- not on launch geometry, checkpoint stride or stream count, and no atomics are used -- and
+ * the backward of block 2 followed by the backward of block 1 on the same accumulators gives the bits of one block of 2T.
+ * tests/adjoint_ref.py restates this order in numpy.
+ *
+ * Scope: fz_compile programs whose lowered graph is float32 throughout (no float64 literal, no complex wire), whose delay lines
+ * all live in registers (max_delay <= 8: no LDS or HBM ring) and which read no modulator; node kinds INPUT, CONST, PARAM, DELAY,
+ * ADD, SUB, MUL, DIV, NEG, LT .. NE, ABS, SQRT, EXP, TANH, MIN, MAX.  Anything else: FZ_E_UNSUPPORTED, fz_last_error() names why.
+ * Time-major frames only: in / out_grad / in_grad as [T][n_streams][wire].
+ *
+ * Pointers as for fz_run_block: device pointers, 16-byte aligned, asynchronous on hip_stream (hipStream_t, NULL = default).
+ * Output buffers must not overlap the inputs, the workspace or each other, except state0_grad == state_grad.  The uniform
+ * coefficients are the program's current constants, as for a forward launch.  n_streams == 0 or n_samples == 0: FZ_OK, nothing
+ * is touched.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct fz_grad_args {
+   uint32_t struct_size;         /* sizeof(fz_grad_args); a smaller or unknown size is FZ_E_INVALID        */
+   uint32_t checkpoint_rows;     /* 0 = library default; else a power of two <= 32: the stride of the saved states */
+   const float* in;              /* [T][n_streams][n_in]    forward input of the block (NULL iff n_in == 0) */
+   const float* state;           /* [n_state][n_streams]    state BEFORE the block (read only)              */
+   const float* params;          /* [n_param][n_streams]                                                    */
+   const float* out_grad;        /* [T][n_streams][n_out]                                                   */
+   const float* state_grad;      /* [n_state][n_streams]    dL/d(state after the block); NULL = zero        */
+   float* in_grad;               /* [T][n_streams][n_in]    written;  NULL = not computed                   */
+   float* state0_grad;           /* [n_state][n_streams]    written;  NULL = not computed; may == state_grad */
+   float* param_grad;            /* [n_param][n_streams]    ADDED TO; NULL = not computed                   */
+   float* const_grad;            /* [n_const][n_streams]    ADDED TO; NULL = not computed                   */
+   void*  workspace; uint64_t workspace_bytes;   /* device scratch of at least fz_program_grad_workspace bytes */
+} fz_grad_args;
+/* FZ_OK, or FZ_E_UNSUPPORTED with the reason in fz_last_error(); host only */
+int fz_program_grad_check(const fz_program* p);
+/* workspace bytes of a backward of this shape: ceil(n_samples / C) * n_state * n_streams * 4, C the checkpoint stride
+ * (checkpoint_rows, or the library default for 0) -- the state before every C-th row */
+int fz_program_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_samples, uint32_t checkpoint_rows, uint64_t* bytes);
+/* registers and scratch of the adjoint kernel (JITs it, no device needed); `unroll` = the checkpoint stride it uses */
+int fz_program_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out);
+/* its symbol, fz_adjoint_kernel_c<C>b<lanes per workgroup>_g<graph tag>; returns the length, writes <= cap bytes */
+long fz_program_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+int fz_run_block_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
  * fz_bank -- device-resident closure state for n_streams streams: the `state_` member of
  * stateful_lambda (flowz.hpp:1190-1191).  clone == copying the closure (snapshot, :1206).
  * The *_host entry points stage through device memory (H2D, kernel, D2H, synchronous); they

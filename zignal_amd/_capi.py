@@ -70,6 +70,13 @@ class Variant(ctypes.Structure):
                 ("block_threads", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class GradArgs(ctypes.Structure):
+    """fz_grad_args (include/flowz_hip.h): the arguments of fz_run_block_grad; struct_size first"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("checkpoint_rows", ctypes.c_uint32)] + \
+               [(n, ctypes.c_void_p) for n in ("in_", "state", "params", "out_grad", "state_grad", "in_grad", "state0_grad", "param_grad",
+                                               "const_grad", "workspace")] + [("workspace_bytes", ctypes.c_uint64)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -146,6 +153,11 @@ def _load():
         "fz_bank_process_host": (ctypes.c_int, [P, P, P, u32]),
         "fz_bank_process_host_stream_major": (ctypes.c_int, [P, P, P, u32]),
         "fz_bank_process_host_f64": (ctypes.c_int, [P, P, P, u32]),
+        "fz_program_grad_check": (ctypes.c_int, [P]),
+        "fz_program_grad_workspace": (ctypes.c_int, [P, u64, u32, u32, ctypes.POINTER(u64)]),
+        "fz_program_grad_resources": (ctypes.c_int, [P, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_grad_kernel_symbol": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_run_block_grad": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, P]),
         "fz_device_count": (ctypes.c_int, []),
         "fz_synth_fill": (ctypes.c_int, [P, u64, u32, u32, u32, u64, u64, u32, P]),
         "fz_rbj_lowpass": (ctypes.c_int, [P, P, f32, u64, P, P, P]),

@@ -20,12 +20,15 @@ extern const char* const kSkeletonHead;
 extern const char* const kSkeletonBody_stream_major;
 extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
+extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a kernel text of its own
 
 // the hand-written text of a variant's kernel: the common head + the ONE body its flags select
 const std::string& skeleton_source(uint32_t flags)
 {
    static const std::string sm = std::string(kSkeletonHead) + kSkeletonBody_stream_major, ws = std::string(kSkeletonHead) + kSkeletonBody_wave_split,
                             fr = std::string(kSkeletonHead) + kSkeletonBody_frames;
+   static const std::string adj = kSkeletonAdjoint;
+   if (flags & FZ_VF_ADJOINT) return adj;
    return (flags & FZ_VF_STREAM_MAJOR) ? sm : ws_parts(flags) ? ws : fr;
 }
 
@@ -33,6 +36,7 @@ const std::string& skeleton_source(uint32_t flags)
 // fz_block_kernel_p<streams/lane>u<unroll>b<block>[s<segments>]f<flags>
 std::string kernel_name(const Graph& g, const Variant& v)
 {
+   if (v.flags & FZ_VF_ADJOINT) return "fz_adjoint_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
    std::string n = "fz_block_kernel_p" + std::to_string(v.P) + "u" + std::to_string(v.U) + "b" + std::to_string(v.block);
    if ((v.flags & FZ_VF_STAGE_PACK) && g.split.ok) n += "s" + std::to_string(g.split.K) + (g.split.m > 1 ? "a" + std::to_string(g.split.m) : "");
    if (ws_parts(v.flags)) n += "w" + std::to_string(ws_parts(v.flags)) + (ws_io(v.flags) ? (ws_io_waves(v.flags) == 2 ? "io2" : "io") : "");
@@ -110,6 +114,7 @@ RingPlan ring_plan(const Graph& g, const Variant& v)
 
 std::string gen_config(const Graph& g, const Variant& v)
 {
+   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_config(g, v);
    std::ostringstream o;
    o << "// generated by libflowz_hip -- graph configuration\n";
    o << "#define FZ_NIN " << g.n_in << "\n";
@@ -254,6 +259,7 @@ static void emit_functions(std::ostringstream& o, const Graph& g)
 
 std::string gen_body(const Graph& g, const Variant& v)
 {
+   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_body(g);
    if (const uint32_t W = ws_parts(v.flags)) {
       // the parts of the graph, each a stage-packed body of its own (struct fz_r0::fz_graph, fz_r1::fz_graph, ...)
       const std::vector<Graph>* roles = g.wave_roles(W);
@@ -918,6 +924,165 @@ std::string full_source(const Graph& g, const Variant& v)
    s += "// ==== fz_block_kernel.hip.inc ====\n";
    s += skeleton_source(v.flags);
    return s;
+}
+
+
+// ---- the adjoint kernel (fz_kernel_adjoint.hip.inc, fz_grad.cpp) ----------------------------------------------------------------------
+std::string gen_adjoint_config(const Graph& g, const Variant& v)
+{
+   std::ostringstream o;
+   o << "// generated by libflowz_hip -- adjoint kernel configuration\n";
+   o << "#define FZ_NIN " << g.n_in << "\n";
+   o << "#define FZ_NOUT " << g.n_out << "\n";
+   o << "#define FZ_NCONST " << g.consts.size() << "\n";
+   o << "#define FZ_NPARAM " << g.n_param << "\n";
+   o << "#define FZ_NSTATE " << g.n_state << "\n";
+   o << "#define FZ_C " << v.U << "   // checkpoint rows: the chunk sweep 2 re-runs and walks backwards\n";
+   o << "#define FZ_BLOCK " << v.block << "\n";
+   o << "#define FZ_KERNEL " << kernel_symbol(g, v) << "\n";
+   return o.str();
+}
+
+// struct fz_adj: fwd() -- the state after one step, from the state before it and the step's frame (the forward step() of gen_body for
+// one stream per lane, outputs left out) -- and bwd() -- the same step re-evaluated, then the adjoint statements in reverse node order.
+// The order of every sum is the one include/flowz_hip.h documents (fz_run_block_grad); tests/adjoint_ref.py restates it.  A node's
+// adjoint starts as -0.0f, the identity of IEEE addition: a first contribution is the contribution itself, bit for bit, and the
+// compiler folds the addition away.  Nodes no adjoint reaches (those that only feed comparisons) emit nothing at all.
+std::string gen_adjoint_body(const Graph& g)
+{
+   std::ostringstream o;
+   auto val = [&](uint32_t id) { return "v" + std::to_string(id); };
+   auto adj = [&](uint32_t id) { return "g" + std::to_string(id); };
+   o << "// generated by libflowz_hip -- adjoint graph body: " << g.nodes.size() << " nodes, " << g.lines.size() << " delay lines, " << g.n_state
+     << " state floats\n";
+   emit_functions(o, g);
+   auto row = [&](uint32_t src, uint32_t age) {          // state row of node src's value `age` samples ago (age >= 1)
+      const Line& L = g.lines[(size_t)g.line_of_node[src]];
+      return L.row0 + age - 1;
+   };
+   auto values = [&](const char* indent) {
+      for (size_t id = 0; id < g.nodes.size(); ++id) {
+         const Node& nd = g.nodes[id];
+         o << indent << "const float " << val((uint32_t)id) << " = ";
+         switch (nd.kind) {
+            case FZ_IR_INPUT: o << "x[" << nd.a << "]"; break;
+            case FZ_IR_CONST: o << "c[" << nd.a << "]"; break;
+            case FZ_IR_PARAM: o << "p[" << nd.a << "]"; break;
+            case FZ_IR_DELAY: o << "s[" << row(nd.a, nd.b) << "]"; break;
+            case FZ_IR_ADD: o << val(nd.a) << " + " << val(nd.b); break;
+            case FZ_IR_SUB: o << val(nd.a) << " - " << val(nd.b); break;
+            case FZ_IR_MUL: o << val(nd.a) << " * " << val(nd.b); break;
+            case FZ_IR_DIV: o << val(nd.a) << " / " << val(nd.b); break;
+            case FZ_IR_NEG: o << "-" << val(nd.a); break;
+            case FZ_IR_LT: o << "(" << val(nd.a) << " < " << val(nd.b) << ") ? 1.f : 0.f"; break;
+            case FZ_IR_LE: o << "(" << val(nd.a) << " <= " << val(nd.b) << ") ? 1.f : 0.f"; break;
+            case FZ_IR_GT: o << "(" << val(nd.a) << " > " << val(nd.b) << ") ? 1.f : 0.f"; break;
+            case FZ_IR_GE: o << "(" << val(nd.a) << " >= " << val(nd.b) << ") ? 1.f : 0.f"; break;
+            case FZ_IR_EQ: o << "(" << val(nd.a) << " == " << val(nd.b) << ") ? 1.f : 0.f"; break;
+            case FZ_IR_NE: o << "(" << val(nd.a) << " != " << val(nd.b) << ") ? 1.f : 0.f"; break;
+            case FZ_IR_ABS: o << "fz_abs(" << val(nd.a) << ")"; break;
+            case FZ_IR_SQRT: o << "fz_sqrt(" << val(nd.a) << ")"; break;
+            case FZ_IR_EXP: o << "fz_exp(" << val(nd.a) << ")"; break;
+            case FZ_IR_TANH: o << "fz_tanh(" << val(nd.a) << ")"; break;
+            case FZ_IR_MIN: o << "fz_min(" << val(nd.a) << ", " << val(nd.b) << ")"; break;
+            case FZ_IR_MAX: o << "fz_max(" << val(nd.a) << ", " << val(nd.b) << ")"; break;
+            default: fail(FZ_E_UNSUPPORTED, "internal: a node kind the adjoint kernel does not take");
+         }
+         o << ";\n";
+      }
+   };
+   o << "struct fz_adj {\n";
+   o << "   // the state after one step: row (row0 + j) of a line holds its source's value j + 1 samples ago\n";
+   o << "   __device__ __forceinline__ static void fwd(const float* x, const float* c, const float* p, const float* s, float* sn)\n   {\n";
+   o << "      (void)x; (void)c; (void)p; (void)s; (void)sn;\n";
+   values("      ");
+   for (const Line& L : g.lines) {
+      o << "      sn[" << L.row0 << "] = " << val(L.src) << ";\n";
+      for (uint32_t a = 1; a < L.depth; ++a) o << "      sn[" << L.row0 + a << "] = s[" << L.row0 + a - 1 << "];\n";
+   }
+   o << "   }\n";
+   o << "   // one step backwards: yb = dL/dy of the step, R = the pending line adjoints (the state after the step on entry, before it on\n"
+        "   // return), pb / cb += this step's parameter / coefficient adjoints, xb = dL/dx of the step\n";
+   o << "   __device__ __forceinline__ static void bwd(const float* x, const float* c, const float* p, const float* s, const float* yb, float* xb,\n"
+        "                                              float* R, float* pb, float* cb)\n   {\n";
+   o << "      (void)x; (void)c; (void)p; (void)s; (void)yb; (void)xb; (void)R; (void)pb; (void)cb;\n";
+   values("      ");
+   const size_t n = g.nodes.size();
+   std::vector<char> has(n, 0);
+   for (size_t id = 0; id < n; ++id) o << "      float " << adj((uint32_t)id) << " = -0.0f;\n";
+   o << "      // 1. output slots, in slot order\n";
+   for (size_t j = 0; j < g.outputs.size(); ++j) {
+      o << "      " << adj(g.outputs[j]) << " = " << adj(g.outputs[j]) << " + yb[" << j << "];\n";
+      has[g.outputs[j]] = 1;
+   }
+   o << "      // 2. the pending line adjoint: row row0 of the state after the step is the line source's value; the other rows move one up\n";
+   for (const Line& L : g.lines) {
+      o << "      " << adj(L.src) << " = " << adj(L.src) << " + R[" << L.row0 << "];\n";
+      has[L.src] = 1;
+      for (uint32_t a = 0; a + 1 < L.depth; ++a) o << "      R[" << L.row0 + a << "] = R[" << L.row0 + a + 1 << "];\n";
+      o << "      R[" << L.row0 + L.depth - 1 << "] = -0.0f;\n";
+   }
+   o << "      // 3. consumers in decreasing node order\n";
+   auto plus = [&](uint32_t to, const std::string& e) {
+      o << "      " << adj(to) << " = " << adj(to) << " + " << e << ";\n";
+      has[to] = 1;
+   };
+   auto minus = [&](uint32_t to, const std::string& e) {
+      o << "      " << adj(to) << " = " << adj(to) << " - " << e << ";\n";
+      has[to] = 1;
+   };
+   for (size_t k = n; k-- > 0;) {
+      const Node& nd = g.nodes[k];
+      if (!has[k]) continue;
+      const std::string gk = adj((uint32_t)k), va = val(nd.a), vb = val(nd.b), vk = val((uint32_t)k);
+      switch (nd.kind) {
+         case FZ_IR_INPUT: break;
+         case FZ_IR_CONST: o << "      cb[" << nd.a << "] = cb[" << nd.a << "] + " << gk << ";\n"; break;
+         case FZ_IR_PARAM: o << "      pb[" << nd.a << "] = pb[" << nd.a << "] + " << gk << ";\n"; break;
+         case FZ_IR_DELAY: {
+            const uint32_t r = row(nd.a, nd.b);
+            o << "      R[" << r << "] = R[" << r << "] + " << gk << ";\n";
+            break;
+         }
+         case FZ_IR_ADD: plus(nd.a, gk); plus(nd.b, gk); break;
+         case FZ_IR_SUB: plus(nd.a, gk); minus(nd.b, gk); break;
+         case FZ_IR_MUL: plus(nd.a, gk + " * " + vb); plus(nd.b, gk + " * " + va); break;
+         case FZ_IR_DIV:
+            o << "      const float q" << k << " = " << gk << " / " << vb << ";\n";
+            plus(nd.a, "q" + std::to_string(k));
+            minus(nd.b, "q" + std::to_string(k) + " * " + vk);
+            break;
+         case FZ_IR_NEG: minus(nd.a, gk); break;
+         case FZ_IR_SQRT: plus(nd.a, gk + " * (0.5f / " + vk + ")"); break;
+         case FZ_IR_EXP: plus(nd.a, gk + " * " + vk); break;
+         case FZ_IR_TANH: plus(nd.a, gk + " * (1.0f - " + vk + " * " + vk + ")"); break;
+         case FZ_IR_ABS:
+            o << "      " << adj(nd.a) << " = " << va << " > 0.f ? " << adj(nd.a) << " + " << gk << " : " << va << " < 0.f ? " << adj(nd.a) << " - " << gk
+              << " : " << adj(nd.a) << ";\n";
+            has[nd.a] = 1;
+            break;
+         case FZ_IR_MIN: case FZ_IR_MAX: {
+            // all of g to the operand std::min / std::max returned: min = (b < a) ? b : a, max = (a < b) ? b : a
+            const std::string m = "m" + std::to_string(k);
+            o << "      const bool " << m << " = " << (nd.kind == FZ_IR_MIN ? vb + " < " + va : va + " < " + vb) << ";\n";
+            o << "      " << adj(nd.a) << " = " << m << " ? " << adj(nd.a) << " : " << adj(nd.a) << " + " << gk << ";\n";
+            o << "      " << adj(nd.b) << " = " << m << " ? " << adj(nd.b) << " + " << gk << " : " << adj(nd.b) << ";\n";
+            has[nd.a] = has[nd.b] = 1;
+            break;
+         }
+         default: break;                                   // comparisons: derivative zero, no arithmetic
+      }
+   }
+   o << "      // 4. the step's input adjoints (+0 for a wire no adjoint reaches)\n";
+   for (uint32_t w = 0; w < g.n_in; ++w) {
+      std::string e = "0.0f";
+      for (size_t id = 0; id < n; ++id)
+         if (g.nodes[id].kind == FZ_IR_INPUT && g.nodes[id].a == w && has[id]) e = e == "0.0f" ? adj((uint32_t)id) : e + " + " + adj((uint32_t)id);
+      o << "      xb[" << w << "] = " << e << ";\n";
+   }
+   o << "   }\n";
+   o << "};\n";
+   return o.str();
 }
 
 }  // namespace fz

@@ -174,6 +174,10 @@ constexpr uint32_t FZ_VF_LANE_PAIRS = 1u << 30;
 // internal: ... as SINGLE streams 64 apart (two or four streams per lane of frames with four floats per stream: every 16-byte access of a
 // lane is one stream's frame, contiguous across the lanes of the wave)
 constexpr uint32_t FZ_VF_LANE_SINGLES = 1u << 31;
+// internal: the ADJOINT kernel of a block (fz_grad.cpp, fz_kernel_adjoint.hip.inc): a reserved bit, so that no caller's variant names
+// it.  Such a Variant is {P = 1, U = checkpoint rows, block = lanes per workgroup, flags = FZ_VF_ADJOINT}; it shares the kernel cache
+// with the forward kernels (its own source is its key) and none of the forward planner's paths ever sees it.
+constexpr uint32_t FZ_VF_ADJOINT = 1u << 27;
 constexpr uint32_t kChipCUs = 256;       // MI355X (gfx950): 8 XCDs x 32 CUs -- what chip_cus() answers on a box without a GPU
 unsigned chip_cus();                     // compute units of the current device (fz_launch.cpp)
 
@@ -217,6 +221,13 @@ std::string gen_config(const Graph& g, const Variant& v); // generated "fz_graph
 std::string gen_body(const Graph& g, const Variant& v);   // generated "fz_graph_body.h"
 const std::string& skeleton_source(uint32_t flags);      // hand-written kernel text of a variant: the common head + the one body its flags select
 std::string full_source(const Graph& g, const Variant& v);
+// the adjoint kernel (a Variant with FZ_VF_ADJOINT): gen_config / gen_body / skeleton_source hand over to these for it
+std::string gen_adjoint_config(const Graph& g, const Variant& v);
+std::string gen_adjoint_body(const Graph& g);
+// why the backward of a block does not support this graph ("" = it does): fz_grad.cpp
+std::string grad_unsupported_reason(const Graph& g);
+// the library's default checkpoint stride for the adjoint kernel of this graph (a power of two)
+uint32_t grad_default_checkpoint(const Graph& g);
 
 // ---- runtime ---------------------------------------------------------------------------------------------
 // what the code object's metadata says the kernel needs (AMDGPU msgpack notes)

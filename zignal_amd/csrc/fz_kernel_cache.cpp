@@ -552,6 +552,7 @@ static void manifest_record(const fz_program* p, const Variant& v)
 {
    static const char* const path = std::getenv("FLOWZ_HIP_MANIFEST");
    if (!path || !*path || p->recipe.empty()) return;
+   if (v.flags & FZ_VF_ADJOINT) return;                  // (adjoint kernels are built on first use; a manifest lists forward launches)
    char head[96];
    std::snprintf(head, sizeof head, "FZM1 %u %u %u %u %zu\n", v.P, v.U, v.block, v.flags, p->recipe.size());
    const std::string rec = head + p->recipe;

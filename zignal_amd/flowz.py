@@ -602,6 +602,97 @@ class Program:
                            torch.cuda.current_stream().cuda_stream, tile)
         return out, state
 
+    # -- the backward of a block (fz_run_block_grad) ------------------------------------------------
+    GRAD_WANT = ("x", "state", "params", "consts")
+
+    def grad_supported(self) -> bool:
+        """True when fz_run_block_grad takes this program (grad_unsupported_reason() says why not)."""
+        return C.lib.fz_program_grad_check(self._h) == C.FZ_OK
+
+    def grad_unsupported_reason(self) -> str:
+        return "" if self.grad_supported() else C.last_error()
+
+    def grad_workspace_bytes(self, n_streams: int, T: int, checkpoint_rows: int = 0) -> int:
+        b = ctypes.c_uint64()
+        C.check(C.lib.fz_program_grad_workspace(self._h, int(n_streams), int(T), int(checkpoint_rows), ctypes.byref(b)))
+        return int(b.value)
+
+    def grad_resources(self, checkpoint_rows: int = 0) -> dict:
+        """registers / scratch bytes of the adjoint kernel (JITs it; needs no GPU); 'unroll' = the checkpoint stride it uses"""
+        r = C.KernelResources()
+        C.check(C.lib.fz_program_grad_resources(self._h, int(checkpoint_rows), ctypes.byref(r)))
+        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+    def grad_kernel_symbol(self, checkpoint_rows: int = 0) -> str:
+        buf = ctypes.create_string_buffer(160)
+        C.check(C.lib.fz_program_grad_kernel_symbol(self._h, int(checkpoint_rows), buf, 160))
+        return buf.value.decode()
+
+    def run_block_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0):
+        """Reverse-mode gradients of the block run_block(x, state, params) computes (time-major frames only): out_grad = dL/dy
+        [T, n_streams, n_out], state_grad = dL/d(state after the block) [n_state, n_streams] (None: zero).  state = the state BEFORE
+        the block (None: zeros; read only).  want: which of "x" (dL/dx, like x), "state" (dL/d(state before), [n_state, n_streams]),
+        "params" ([n_param, n_streams]) and "consts" ([n_const, n_streams]: per stream, not summed) to compute.  accum: optional dict
+        with "params" / "consts" tensors the gradients are ADDED to (returned as those entries); otherwise they start from zero.
+        The uniform coefficients are the program's current constants.  Launches on torch's current stream; returns a dict."""
+        import torch
+
+        _require(self.grad_supported(), self.grad_unsupported_reason())
+        want = tuple(want)
+        _require(set(want) <= set(self.GRAD_WANT), f"want: a subset of {self.GRAD_WANT}")
+        if x.dim() == 2 and self.n_in == 1:
+            x = x.unsqueeze(-1)
+        _check_frames(x, self.n_in)
+        _require(x.dim() == 3, "run_block_grad takes time-major frames [T, n_streams, n_in]")
+        T, ns, _ = x.shape
+        dev = x.device
+        if out_grad.dim() == 2 and self.n_out == 1:
+            out_grad = out_grad.unsqueeze(-1)
+        _check_dev(out_grad, (T, ns, self.n_out), "out_grad")
+        if state is None:
+            state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=dev)
+        if self.n_state:
+            _check_dev(state, (self.n_state, ns), "state")
+        if self.n_param:
+            _require(params is not None, f"params: the graph has {self.n_param} per-stream coefficient(s), none given")
+            _check_dev(params, (self.n_param, ns), "params")
+        if state_grad is not None and self.n_state:
+            _check_dev(state_grad, (self.n_state, ns), "state_grad")
+        accum = dict(accum or {})
+        out = {}
+        if "x" in want:
+            out["x"] = torch.empty_like(x)
+        if "state" in want:
+            out["state"] = torch.empty((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=dev)
+        for key, rows in (("params", self.n_param), ("consts", self.n_const)):
+            if key in want:
+                if key in accum:
+                    out[key] = _check_dev(accum[key], (rows, ns), f"accum[{key!r}]")
+                else:
+                    out[key] = torch.zeros((_bi.max(rows, 1), ns), dtype=torch.float32, device=dev)
+        wsb = self.grad_workspace_bytes(ns, T, checkpoint_rows)
+        ws = torch.empty((_bi.max(wsb, 16) + 3) // 4, dtype=torch.float32, device=dev)
+
+        def ptr(t, rows=1):
+            return t.data_ptr() if t is not None and rows else None
+        a = C.GradArgs()
+        a.struct_size = ctypes.sizeof(C.GradArgs)
+        a.checkpoint_rows = int(checkpoint_rows)
+        a.in_ = ptr(x, self.n_in)
+        a.state = ptr(state, self.n_state)
+        a.params = ptr(params, self.n_param)
+        a.out_grad = ptr(out_grad, self.n_out)
+        a.state_grad = ptr(state_grad, self.n_state)
+        a.in_grad = ptr(out.get("x"), self.n_in)
+        a.state0_grad = ptr(out.get("state"), self.n_state)
+        a.param_grad = ptr(out.get("params"), self.n_param)
+        a.const_grad = ptr(out.get("consts"), self.n_const)
+        a.workspace = ws.data_ptr()
+        a.workspace_bytes = ws.numel() * 4
+        # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
+        C.check(C.lib.fz_run_block_grad(self._h, ctypes.byref(a), int(ns), int(T), torch.cuda.current_stream().cuda_stream))
+        return out
+
 
 def _tune(self, x, state=None, params=None, out=None):
     """Measure the candidate kernel variants for this shape on these buffers (fz_program_tune) and
