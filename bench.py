@@ -6,6 +6,11 @@ torch.distributed.run with one rank per GPU.  One "step" = one fz_run_block laun
 4096-sample block of every stream of this rank (state carried from step to step), input frames
 already resident in HBM.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up and plan selection, the warm-up and the K timed steps,
+--dump-outputs, the line.  Everything else the line can carry -- oracle parity, the sustained run, the row-walk and copy
+yardsticks, the CPU baseline, the other configs and layouts -- is measured with --full (every --no-* option but --no-autotune
+trims it there).
+
   value      whole-job Msamples/s = streams(all ranks) * 4096 * K / max-over-ranks wall time
   roofline   dominant kernel fz_block_kernel: algorithmic bytes per launch / its average launch
              duration = HIP-event time over the K back-to-back launches of the timed region / K,
@@ -13,14 +18,15 @@ already resident in HBM.  Rank 0 prints ONE JSON line.
              peak = 8000 GB/s (HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md);
              traffic = PMC bytes of THIS kernel symbol on THIS workload (profiles/pmc_traffic.json,
              collected by tools/profile_bench.sh, keyed by the kernel's code id), null when that code was not profiled;
-             sustained = the same launches back to back for >= 2 s (power-managed clocks settle), with
+             measured_row_walk_GBs / measured_copy_GBs (--full) = the identity graph and a plain copy on the same frames;
+             sustained (--full) = the same launches back to back for >= 2 s (power-managed clocks settle), with
              sustained.board = package power / power cap / shader clock sampled through rocm-smi meanwhile
              (this workload runs at the board's power cap: profiles/r03/power_and_clocks.txt)
-  cpu_baseline  the compiled scalar oracle (one closure per stream, one call per sample: what
+  cpu_baseline  (--full) the compiled scalar oracle (one closure per stream, one call per sample: what
              the reference's compile()-callable does) timed on this box's host cores on a
              bounded sample of the same workload, rank 0, N == 1 only (buffers pre-touched, threads
              pinned); the oracle also checks the GPU output of >= 1024 random streams bit for bit.
-  config2/3/4   the other single-GPU BASELINE configs at full size in the same run (rank 0, N == 1):
+  config2/3/4   (--full) the other single-GPU BASELINE configs at full size in the same run (rank 0, N == 1):
              library-default and tuned plan, roofline fraction, oracle parity on >= 1024 random streams.
 
 --dump-outputs DIR writes what the headline's last timed step returned (rank 0's shard) as float32 .npy files, at most
@@ -900,6 +906,9 @@ def main():
                          "(stream-tiled layout [tile][t][stream])")
     ap.add_argument("--secondary-tile", type=int, default=8192,
                     help="streams per frame tile of the tiled-layout legs (1-wire frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: oracle parity, the sustained run, the row-walk and copy yardsticks, the CPU baseline and the "
+                         "other configs, layouts and shapes (every --no-* option but --no-autotune leaves a part of it out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config2", action="store_true", help="skip the 65 536 / 32 768 / 16 384-stream objects (BASELINE configs[1] and below)")
     ap.add_argument("--no-config34", action="store_true", help="skip BASELINE configs[2] and [3] (4-parallel sum, oscillator chain)")
@@ -941,7 +950,8 @@ def main():
     from zignal_amd import flowz as F
     from zignal_amd import workloads as W
 
-    load_oracle()
+    if args.full or args.only:                               # (the parity checks and the CPU baseline call it)
+        load_oracle()
     SEED = W.SEED
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1065,9 +1075,11 @@ def main():
     # first block from zero state: kept for the parity check (>= 1024 random streams across all tiles)
     prog.run_block(x, state=state, out=y, variant=variant)
     torch.cuda.synchronize()
-    # (every rank checks streams of its OWN shard against the oracle: rank 0 >= 1024, the others >= 128)
-    par_ids = sample_ids(ns, PARITY_STREAMS if rank == 0 else PARITY_STREAMS_OTHER_RANKS, 11 + rank)
-    first_block = gather(torch, y, par_ids, "tiled" if tile else "time_major", tile)
+    parity = args.full and (not args.no_cpu_baseline or world > 1)
+    if parity:
+        # (every rank checks streams of its OWN shard against the oracle: rank 0 >= 1024, the others >= 128)
+        par_ids = sample_ids(ns, PARITY_STREAMS if rank == 0 else PARITY_STREAMS_OTHER_RANKS, 11 + rank)
+        first_block = gather(torch, y, par_ids, "tiled" if tile else "time_major", tile)
     for _ in range(max(args.warmup - 1, 0)):
         prog.run_block(x, state=state, out=y, variant=variant)
 
@@ -1092,14 +1104,14 @@ def main():
     per_rank_ms = zdist.gather_floats(kern_avg_s * 1e3, device=stats_dev)        # HIP-event ms per launch of every rank
     # parity of every rank's shard (the oracle is the checker, outside the timed region; global stream ids = begin + local)
     nd_all = n_checked = None
-    if not args.no_cpu_baseline or world > 1:
+    if parity:
         from oracle import coracle, flowz_oracle as O
         want = coracle.df1_cascade([W.STABLE] * 6, O.synth_input(SEED, par_ids + begin, T))
         nd_all, n_checked = (int(v) for v in zdist.sum_ints([ndiff_bits(first_block, want), len(par_ids)], device=stats_dev))
 
     # the same launches back to back for >= 2 s: whatever the power management does to the clocks has happened by then
     sustained = None
-    if rank == 0 and world == 1 and not args.no_sustained:
+    if args.full and rank == 0 and world == 1 and not args.no_sustained:
         n_sus, ms_tot, board = sustained_run(torch, lambda: prog.run_block(x, state=state, out=y, variant=variant), kern_avg_s * 1e3, dev.index or 0,
                                              seconds=2.0, min_batch=args.steps)
         ms_sus = ms_tot / n_sus
@@ -1112,7 +1124,7 @@ def main():
     # lockstep / XCD-synchronised skeleton, same frames): what this layout gives a kernel that only moves the rows; (2) the plain
     # one-shot float4 copy kernel (fz_copy_probe)
     copy_gbs = walk_gbs = walk_kernel = None
-    if rank == 0:
+    if args.full and rank == 0:
         F.copy_probe(x, y)
         torch.cuda.synchronize()
         copy_gbs = 2.0 * x.numel() * 4 / (event_ms(torch, lambda: F.copy_probe(x, y), 3) / 1e3) / 1e9
@@ -1126,7 +1138,7 @@ def main():
         walk_kernel = ident.kernel_symbol(ident.plan(ns, tile), ns, T, tile)
 
     secondary = {}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         del x, y, state
         torch.cuda.empty_cache()
         if not args.no_layout_legs:
@@ -1200,7 +1212,7 @@ def main():
             line["dist_backend"] = args.dist_backend
             line["rccl_ranks"] = dist.get_world_size() if args.dist_backend == "nccl" else 0
             line["ms_per_step_per_rank"] = [round(v, 4) for v in per_rank_ms]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(T, SEED, [W.STABLE] * 6)
         # the full record goes to a file; stdout carries ONE line the driver can parse (< 4 KB)
         details_path = os.environ.get("BENCH_DETAILS", os.path.join(ROOT, "bench_details.json"))

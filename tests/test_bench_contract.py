@@ -103,7 +103,7 @@ def _last_line_as_the_driver_sees_it(stdout):
 def test_bench_json_contract_small_workload(tmp_path):
     details = str(tmp_path / "details.json")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--streams", "16384", "--samples", "512"], capture_output=True, text=True, timeout=600, env=dict(os.environ, BENCH_DETAILS=details))
+                          "--streams", "16384", "--samples", "512", "--full"], capture_output=True, text=True, timeout=600, env=dict(os.environ, BENCH_DETAILS=details))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -148,6 +148,22 @@ def test_bench_json_contract_small_workload(tmp_path):
     assert c["Msamples_per_s_per_core"] > 0 and c["physical_cores"] >= 1 and c["logical_cpus"] >= c["physical_cores"]
     assert c["cores"] <= c["threads"] and (c["cgroup_cpu_quota"] is None or c["cores"] <= max(1, round(c["cgroup_cpu_quota"])))
     assert 0.5 < c["Msamples_per_s_per_core"] * c["cores"] / c["value"] < 2.0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_measures_the_headline_alone():
+    """Without --full: the driver's keys, the roofline of the timed launches and the checksum -- no parity check, sustained run, row walk,
+    copy, CPU baseline or other object"""
+    sys.path.insert(0, ROOT)
+    import bench
+    d = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--streams", "16384", "--samples", "512"])
+    assert set(d) == set(bench.CONTRACT_KEYS) | {"config", "roofline", "checksum"}, sorted(d)
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 16384 * 512 * 3 / (d["ms_per_step"] * 3 / 1e3) / 1e6) / d["value"] < 1e-2
+    r = d["roofline"]
+    assert r["kernel"].startswith("fz_block_kernel_p") and r["avg_launch_ms"] > 0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
+    assert "sustained" not in r and r["measured_row_walk_GBs"] is None and r["measured_copy_GBs"] is None
+    assert isinstance(d["checksum"], int)
 
 
 @pytest.mark.gpu
@@ -205,7 +221,7 @@ def test_bench_two_ranks_on_one_gpu_rehearse_the_sharded_path():
     """The N > 1 path of bench.py (launcher env, shard_range, per-rank generator offset, barrier, max-over-ranks time,
     the statistics all-reduce) with 2 ranks that share device 0 and reduce over gloo: the integer checksum of the two
     shards must equal a single-process run over the union of the global stream ids.  Weak and strong scaling modes."""
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-autotune", "--no-config2", "--no-config34", "--no-sustained",
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-autotune", "--no-config2", "--no-config34", "--no-sustained",
               "--no-layout-legs"]
     one = _run_bench(["--gpus", "1", "--streams", "262144"] + common)
     weak = _run_bench(["--gpus", "2", "--streams", "131072", "--dist-backend", "gloo"] + common, nproc=2)
@@ -236,7 +252,8 @@ def test_bench_four_ranks_on_one_gpu_rehearse_the_drivers_scaling_run():
     n = RANKS_ON_ONE_GPU
     plans = os.path.join(os.environ.get("FLOWZ_HIP_CACHE") or os.path.join(ROOT, "zignal_amd", "_kcache"), "plans.txt")   # (the library's kernel cache directory)
     before = open(plans).read().splitlines() if os.path.exists(plans) else []
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-config2", "--no-config34", "--no-sustained", "--no-layout-legs", "--no-extras", "--no-next-rows"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-config2", "--no-config34", "--no-sustained", "--no-layout-legs", "--no-extras",
+              "--no-next-rows"]
     # (bench.py switches the persisted plans off for itself -- every run measures; the rehearsal switches them back on so that the tunes of all
     #  ranks also meet at the one plans.txt, which a caller's processes would)
     weak = _run_bench(["--gpus", str(n), "--streams", "131072", "--dist-backend", "gloo"] + common, nproc=n, timeout=1200, env={"FLOWZ_HIP_NO_PLAN_CACHE": "0"})

@@ -6,7 +6,7 @@ for set in "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTC
            "TCP_UTCL1_PERMISSION_MISS_sum TCP_TA_TCP_STATE_READ_sum TCP_PENDING_STALL_CYCLES_sum"; do
   i=$((i+1))
   for tile in 8192 0; do
-    rocprofv3 --pmc $set --output-format csv -d $O/s${i}_t${tile} -o b -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-autotune --no-config2 --tile $tile > $O/s${i}_t${tile}.log 2>&1
+    rocprofv3 --pmc $set --output-format csv -d $O/s${i}_t${tile} -o b -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-autotune --no-config2 --tile $tile > $O/s${i}_t${tile}.log 2>&1
   done
 done
 python - <<PY
