@@ -23,6 +23,34 @@ static void note_divergence(const Graph& g)
                 "std::min(0, ...)); this library routes per the arity table (flowz.hpp:162-246), so its results differ from the reference's closure");
 }
 
+// a string result: its length, and as much of it as fits `cap` (NUL-terminated) in `buf`; an error: its code, the message in fz_last_error
+template <class Text>
+static long string_result(char* buf, size_t cap, Text text)
+{
+   try {
+      const std::string s = text();
+      if (buf && cap) {
+         const size_t n = std::min(cap - 1, s.size());
+         std::memcpy(buf, s.data(), n);
+         buf[n] = 0;
+      }
+      return (long)s.size();
+   } catch (const fz::Error& er) {
+      set_error(er.msg);
+      return er.code;
+   }
+}
+
+// the kernel a launch of that shape runs (a shape left 0: 2^20 streams / samples), as `of` names it
+template <class Of>
+static long kernel_string(fz_program* p, const fz_variant* v, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams, char* buf, size_t cap, Of of)
+{
+   return string_result(buf, cap, [&] {
+      if (!p) fail(FZ_E_INVALID, "null program");
+      return of(plan_launch(p, v, n_streams ? n_streams : (1ull << 20), n_samples ? n_samples : (1u << 20), tile_streams, 0, true, false).main);
+   });
+}
+
 extern "C" {
 
 int fz_compile(const fz_expr* e, fz_program** out)
@@ -227,13 +255,10 @@ int fz_program_build_for(fz_program* p, const fz_variant* v, uint64_t n_streams,
 {
    FZ_GUARD(
       if (!p || !n_streams || !n_samples) fail(FZ_E_INVALID, "fz_program_build_for: bad arguments");
-      const Variant rv = finalize_variant(p, v, n_streams, n_samples, tile_streams);
-      (void)get_kernel(p, rv, nullptr);
+      const LaunchPlan lp = plan_launch(p, v, n_streams, n_samples, tile_streams);
+      (void)get_kernel(p, lp.main, nullptr);
       // (a plain time-major block whose laps leave a few streams over launches a second kernel next to them)
-      if (!(tile_streams && tile_streams < n_streams) && !(v && (v->flags & FZ_VF_STREAM_MAJOR))) {
-         const uint64_t main_streams = lockstep_streams(p->g, v, rv, n_streams, tile_streams);
-         if (main_streams < n_streams) (void)get_kernel(p, remainder_variant(p, v, n_streams, n_samples, n_streams - main_streams), nullptr);
-      }
+      if (lp.main_streams < n_streams) (void)get_kernel(p, lp.rem, nullptr);
       return FZ_OK;)
 }
 
@@ -242,7 +267,7 @@ int fz_program_kernel_resources(fz_program* p, const fz_variant* v, uint64_t n_s
 {
    FZ_GUARD(
       if (!p || !out || !n_streams || !n_samples) fail(FZ_E_INVALID, "fz_program_kernel_resources: bad arguments");
-      const Variant rv = finalize_variant(p, v, n_streams, n_samples, tile_streams, as_launched != 0);
+      const Variant rv = plan_launch(p, v, n_streams, n_samples, tile_streams, 0, as_launched != 0, false).main;
       const auto k = get_kernel(p, rv, nullptr);
       *out = fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills,
                                  k->res.sgpr_spills, rv.U};
@@ -252,72 +277,27 @@ int fz_program_kernel_resources(fz_program* p, const fz_variant* v, uint64_t n_s
 long fz_program_kernel_name(fz_program* p, const fz_variant* v, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams,
                             char* buf, size_t cap)
 {
-   try {
-      if (!p) fail(FZ_E_INVALID, "null program");
-      const std::string s = kernel_name(p->g, finalize_variant(p, v, n_streams ? n_streams : (1ull << 20), n_samples ? n_samples : (1u << 20), tile_streams));
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
+   return kernel_string(p, v, n_streams, n_samples, tile_streams, buf, cap, [&](const Variant& rv) { return kernel_name(p->g, rv); });
 }
 
 long fz_program_kernel_symbol(fz_program* p, const fz_variant* v, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams,
                             char* buf, size_t cap)
 {
-   try {
-      if (!p) fail(FZ_E_INVALID, "null program");
-      const std::string s = kernel_symbol(p->g, finalize_variant(p, v, n_streams ? n_streams : (1ull << 20), n_samples ? n_samples : (1u << 20), tile_streams));
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
+   return kernel_string(p, v, n_streams, n_samples, tile_streams, buf, cap, [&](const Variant& rv) { return kernel_symbol(p->g, rv); });
 }
 
 long fz_program_kernel_code_id(fz_program* p, const fz_variant* v, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams,
                                char* buf, size_t cap)
 {
-   try {
-      if (!p) fail(FZ_E_INVALID, "null program");
-      const std::string s = kernel_code_id(p, finalize_variant(p, v, n_streams ? n_streams : (1ull << 20), n_samples ? n_samples : (1u << 20), tile_streams));
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
+   return kernel_string(p, v, n_streams, n_samples, tile_streams, buf, cap, [&](const Variant& rv) { return kernel_code_id(p, rv); });
 }
 
 long fz_expr_recipe(const fz_expr* e, char* buf, size_t cap)
 {
-   try {
+   return string_result(buf, cap, [&] {
       if (!e) fail(FZ_E_INVALID, "null expression");
-      const std::string s = serialize_expr(e);
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
+      return serialize_expr(e);
+   });
 }
 
 fz_expr* fz_expr_from_recipe(const char* text) { return text ? parse_expr(text) : nullptr; }
@@ -331,19 +311,10 @@ int fz_manifest_build(const char* path, uint32_t n_workers, uint32_t* counts)
 
 long fz_program_source(fz_program* p, const fz_variant* v, char* buf, size_t cap)
 {
-   try {
+   return string_result(buf, cap, [&] {
       if (!p) fail(FZ_E_INVALID, "null program");
-      const std::string s = full_source(p->g, resolve_variant(p->g, v, 1ull << 20));
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
+      return full_source(p->g, resolve_variant(p->g, v, 1ull << 20));
+   });
 }
 
 uint32_t fz_recommended_tile_streams(const fz_program* p)

@@ -7,6 +7,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <set>
 #include <string>
 #include <tuple>
@@ -165,11 +166,11 @@ constexpr uint32_t FZ_VF_RESERVED = 1u | 2u | 4u | (7u << 12) | (7u << 16) | (1u
 constexpr uint32_t FZ_VF_RAGGED = 1u << 28;
 // internal: output rows of plain time-major frames that do not start on the store grid (kStoreGridBytes): neighbouring waves share the
 // sectors / lines at the ends of their footprints, and the frame stores must let L2 merge them (nt instead of nt | sc1; set by
-// finalize_variant, profiles/r04/rows_off_the_grid_store_policy.txt)
+// fit_variant, profiles/r04/rows_off_the_grid_store_policy.txt)
 constexpr uint32_t FZ_VF_ST_MERGE = 1u << 29;
 // internal: four streams per lane as TWO PAIRS 128 streams apart (the wave still covers 256 adjacent streams): frames whose lane slice
 // would leave in two 16-byte stores -- typed frames of 8 bytes per stream -- then store whole 32-byte sectors per instruction (lanes'
-// 16-byte pieces side by side) and can be written through like every other frame (fz_block_kernel.hip.inc: FZ_PAIRS; set by finalize_variant)
+// 16-byte pieces side by side) and can be written through like every other frame (fz_block_kernel.hip.inc: FZ_PAIRS; set by fit_variant)
 constexpr uint32_t FZ_VF_LANE_PAIRS = 1u << 30;
 // internal: ... as SINGLE streams 64 apart (two or four streams per lane of frames with four floats per stream: every 16-byte access of a
 // lane is one stream's frame, contiguous across the lanes of the wave)
@@ -291,6 +292,8 @@ struct fz_program {
 };
 
 namespace fz {
+// what the caller asked for in a variant's flags (no variant: nothing)
+inline bool uv_flag(const fz_variant* uv, uint32_t flag) { return uv && (uv->flags & flag); }
 // the library's choice for a block shape; tile_streams 0 = plain time-major rows (stream-major frames: FZ_VF_STREAM_MAJOR in v->flags)
 // allow_lockstep: the most streams per lane the CU-wide lockstep workgroups of plain time-major frames may use (0: not chosen at all)
 Variant resolve_variant(const Graph& g, const fz_variant* v, uint64_t n_streams, uint32_t n_samples = 1u << 20, uint32_t tile_streams = 0,
@@ -303,11 +306,25 @@ struct TmGeometry {
    double score = 0.0;
 };
 TmGeometry time_major_geometry(uint64_t n_streams, uint32_t max_p, bool heavy_ops, bool ragged_ok, uint32_t only_p = 0);
-uint64_t lockstep_streams(const Graph& g, const fz_variant* uv, const Variant& v, uint64_t n_streams, uint32_t tile_streams);
+// planner rules that more than one file applies (fz_plan.cpp)
+bool stage_pack_pays(const Graph& g, uint32_t n_samples);   // stage packing is automatic for blocks this long
+bool heavy_ops(const Graph& g);                             // VALU-bound with one stream per lane (time_major_geometry's heavy_ops)
+bool chunk_below_4gib(const Graph& g, uint64_t row_streams, bool out_f64, uint32_t U);   // U rows of the widest frame in one descriptor
+bool sm_deep(const Graph& g);                              // stream-major: deep enough to be VALU-bound with one stream per lane
+bool sm_long_stage_packs(const Graph& g);                   // the one-stream long-run body runs stage-packed by the library's choice
 // the kernel a launch of that shape runs: resolved, fitted to the tile / the 4 GiB chunk limit, unroll lowered until nothing spills
 Variant finalize_variant(fz_program* p, const fz_variant* v, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams, bool settle = true);
-// the second kernel of a launch whose lockstep laps leave `rem` streams to a remainder launch (lockstep_streams(...) < n_streams)
-Variant remainder_variant(fz_program* p, const fz_variant* uv, uint64_t n_streams, uint32_t n_samples, uint64_t rem);
+// what a launch runs: `main` over the streams [0, main_streams), and -- only when main_streams < n_streams -- `rem`, the remainder
+// launch over the rest (lockstep laps of whole workgroups leave a few streams over)
+struct LaunchPlan {
+   Variant main;
+   uint64_t main_streams = 0;
+   Variant rem;
+};
+// rows_total: the rows of a stream-major buffer, 0 = not known (the pair body is not stepped down for long buffers);
+// settle: as for finalize_variant; with_remainder = false: `rem` is not resolved (nothing is built for it)
+LaunchPlan plan_launch(fz_program* p, const fz_variant* uv, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams, uint32_t rows_total = 0,
+                       bool settle = true, bool with_remainder = true);
 // builds (or fetches from the caches) the kernel of variant v; fn_out != null: also load it on the
 // current device and return its hipFunction_t
 std::shared_ptr<Kernel> get_kernel(fz_program* p, const Variant& v, void** fn_out);
@@ -319,6 +336,10 @@ int launch(fz_program* p, const float* in, float* out, float* state, const float
 int tune(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
          uint32_t n_samples, uint32_t tile_streams, void* stream, fz_variant* chosen, float* chosen_ms, bool implicit = false);
 std::vector<fz_variant> tune_candidates(const Graph& g, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams);
+// the plan a launch without a variant runs: measured by fz_program_tune (this process or, persisted, an earlier one), or -- with
+// FLOWZ_HIP_AUTOTUNE=1 -- measured now by the first big launch of the shape on the caller's buffers; none: the library's static choice
+std::optional<fz_variant> launch_plan_of_shape(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
+                                               uint32_t n_samples, uint32_t tile_streams, uint32_t rows_total, uint32_t row0, void* stream);
 int device_count();
 uint64_t graph_structure_hash(const Graph& g);
 // the plan a launch without a variant would use for this shape on the current device: in memory, else persisted, else {0,0,0,0}

@@ -93,7 +93,7 @@ static std::vector<const char*> build_options(const Graph& g, const Variant& v)
    // it waits for, 857 s_nop in the cascade's code) would run at the latency of the chain.  The iterative ILP scheduler overlaps
    // the stages of consecutive steps (286 s_nop, two to three chains in flight).
    // (deep graphs only: on shallow ones it hoists every LDS read of the unrolled steps and runs out of registers)
-   if ((v.flags & FZ_VF_STREAM_MAJOR) && (v.flags & FZ_VF_SM_LONG) && v.P == 2 && g.op_weight > 27) {
+   if ((v.flags & FZ_VF_STREAM_MAJOR) && (v.flags & FZ_VF_SM_LONG) && v.P == 2 && sm_deep(g)) {
       o.push_back("-mllvm");
       o.push_back("-amdgpu-sched-strategy=iterative-ilp");
    }
@@ -472,8 +472,8 @@ Variant settle_variant(fz_program* p, Variant v)
          if ((v.flags & FZ_VF_SM_LONG) && v.P == 2) {
             v.P = 1;
             v.U = 128;
-            // (with the stage packing the one-stream body would have had by itself: resolve_variant's rule for deep graphs)
-            if (p->g.split.ok && p->g.split.atoms() <= 13 && p->g.op_weight > 27) v.flags |= FZ_VF_STAGE_PACK;
+            // (with the stage packing the one-stream body would have had by itself)
+            if (sm_long_stage_packs(p->g)) v.flags |= FZ_VF_STAGE_PACK;
             continue;
          }
          return v;

@@ -1,10 +1,11 @@
-// The launch of the fused block kernel: argument checks, plan lookup / first-launch measurement, kernarg image.
+// The launch of the fused block kernel: argument checks, plan (fz_plan.cpp, a measured one: fz_tune.cpp), kernarg image, the launches.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <optional>
 
 #include "fz_runtime.hpp"
 
@@ -144,7 +145,7 @@ int launch(fz_program* p, const float* in, float* out, float* state, const float
 {
    if (rows_total == 0) rows_total = n_samples;             // the block is the whole buffer
    if ((uint64_t)row0 + n_samples > rows_total) fail(FZ_E_INVALID, "row0 + n_samples exceeds rows_total");
-   const bool stream_major = uv && (uv->flags & FZ_VF_STREAM_MAJOR);
+   const bool stream_major = uv_flag(uv, FZ_VF_STREAM_MAJOR);
    if (stream_major) {
       if (tile_streams) fail(FZ_E_INVALID, "stream-major frames are not tiled");
       if ((uint64_t)rows_total * std::max(p->g.n_in, p->g.n_out) >= ((uv->flags & FZ_VF_SM_LONG) && uv->streams_per_lane == 2 ? (1ull << 23) : (1ull << 24)))
@@ -162,140 +163,24 @@ int launch(fz_program* p, const float* in, float* out, float* state, const float
    if (g.n_param && !params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
    auto mis = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) != 0; };
    if (mis(in) || mis(out) || mis(state) || mis(params)) fail(FZ_E_INVALID, "device pointers must be 16-byte aligned");
-   const uint64_t wmax = std::max<uint64_t>(std::max(g.n_in, g.n_out), 1);
    if (tile_streams == 0 || tile_streams >= n_streams) tile_streams = 0;    // one tile == plain time-major
    const uint64_t row_streams = tile_streams ? tile_streams : n_streams;
-   const uint64_t out_w = (uint64_t)std::max<uint32_t>(g.n_out, 1) * ((uv && (uv->flags & FZ_VF_OUT_F64)) ? 2 : 1);
-   if (!stream_major && row_streams * std::max(wmax, out_w) >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "row longer than 4 GiB: shard or tile the streams");
+   if (!stream_major && !chunk_below_4gib(g, row_streams, uv_flag(uv, FZ_VF_OUT_F64), 1)) fail(FZ_E_UNSUPPORTED, "row longer than 4 GiB: shard or tile the streams");
    // (state and coefficient rows go through one-row buffer descriptors: 32-bit byte offsets and sizes, n_streams * 4 < 2^32)
    if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams");
    if (tile_streams && n_streams % tile_streams) fail(FZ_E_INVALID, "n_streams must be a multiple of tile_streams");
    require_device();
-   fz_variant planned;
-   bool from_plan = false;
-   if (!uv) {                                               // a measured plan for this shape on this device?
-      int dev = 0;
-      FZ_HIP(hipGetDevice(&dev));
-      const auto key = std::make_tuple(n_streams, tile_streams, dev);
-      bool known = false;
-      (void)planned_variant(p, n_streams, tile_streams);      // first launch of this shape: a plan persisted by an earlier process?
-      // A launch without a variant runs the plan fz_program_tune measured for the shape (this process or an earlier one: plans.txt), else
-      // the library's static choice.  Round 6: the measurement is never made behind the caller's back any more -- FLOWZ_HIP_AUTOTUNE=1
-      // opts in to what round 3-5 did by default: the first BIG block of a shape (>= 2^26 stream-samples) measures the candidates whose
-      // code objects are at hand on the caller's buffers (the state is saved and restored around it, `out` is recomputed below; about
-      // ten launches each, nothing is JIT-compiled for it).
-      const char* const at_env = std::getenv("FLOWZ_HIP_AUTOTUNE");      // (read at every launch: a process may turn it on for some of its work)
-      const bool autotune = at_env && *at_env == '1';
-      bool may_tune = autotune && rows_total == n_samples && row0 == 0 && n_streams * (uint64_t)n_samples >= (1ull << 26);
-      if (may_tune) {
-         // not while the stream is being captured into a hipGraph (the measurement allocates and synchronises), and not
-         // in place: the candidates run on the caller's buffers, an aliased `in` would be overwritten before the real launch
-         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-         if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) (void)hipGetLastError();
-         const char* ib = reinterpret_cast<const char*>(in);
-         const char* ob = reinterpret_cast<const char*>(out);
-         const size_t ibytes = (size_t)n_streams * n_samples * g.n_in * 4, obytes = (size_t)n_streams * n_samples * out_w * 4;
-         const bool overlap = in && ib < ob + obytes && ob < ib + ibytes;
-         may_tune = cap == hipStreamCaptureStatusNone && !overlap;
-      }
-      bool can_tune = false;
-      {
-         // (another thread's first big launch of this shape may be measuring the plan right now, on ITS buffers: wait for the
-         //  result instead of racing it -- the measuring thread's own launches carry explicit variants and never come here)
-         // ONE critical section decides who measures: the thread whose insert into `measuring` succeeds; everybody else of the
-         // shape waits above until that thread is done
-         std::unique_lock<std::mutex> lock(p->mu);
-         p->measured.wait(lock, [&] { return p->measuring.count(key) == 0; });
-         auto it = p->plans.find(key);
-         known = it != p->plans.end() || p->tuned_default.count(key) != 0;
-         // (a plan is measured on blocks of thousands of samples: the wave-split kernels pay several masked rounds per launch and
-         //  are not what a short block -- the per-sample call protocol -- should run, whatever was tuned for the shape)
-         if (it != p->plans.end() && !(ws_parts(it->second.flags) && n_samples < 256)) {
-            planned = it->second;
-            uv = &planned;
-            from_plan = true;
-         }
-         if (may_tune && !known) {
-            p->tuned_default.insert(key);                   // (also stops the recursion through tune -> launch)
-            can_tune = p->measuring.insert(key).second;     // other launches of this shape wait until the plan is known
-         }
-      }
-      if (can_tune) {
-         struct Done {                                      // ... on every exit path
-            fz_program* p;
-            decltype(key) k;
-            ~Done()
-            {
-               {
-                  std::lock_guard<std::mutex> lock(p->mu);
-                  p->measuring.erase(k);
-               }
-               p->measured.notify_all();
-            }
-         } done{p, key};
-         const size_t sb = (size_t)g.n_state * n_streams * 4;
-         // The candidates run on the caller's buffers: the state is saved before and restored after the measurement, and the
-         // restore is CHECKED -- a state that could not be put back is an error of this launch, never a silent one.  A failure
-         // inside the measurement itself (a candidate's HIP error) is not the caller's problem: the default launch below goes ahead.
-         float* copy = nullptr;
-         bool have_copy = true;
-         if (sb) {
-            if (hipMalloc((void**)&copy, sb) != hipSuccess) {           // no room for the snapshot (multi-GiB state): do not tune
-               (void)hipGetLastError();
-               copy = nullptr;
-               have_copy = false;
-            } else if (hipMemcpyAsync(copy, state, sb, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
-               (void)hipGetLastError();
-               (void)hipFree(copy);
-               copy = nullptr;
-               have_copy = false;
-            }
-         }
-         if (have_copy) {
-            fz_variant chosen{0, 0, 0, 0};
-            int rc = FZ_E_INVALID;
-            std::string why;
-            try {
-               rc = tune(p, in, out, state, params, n_streams, n_samples, tile_streams, stream, &chosen, nullptr, true);
-            } catch (const Error& er) {
-               rc = er.code;
-               why = er.msg;
-               if (er.code == FZ_E_HIP) (void)hipGetLastError();
-            }
-            if (copy) {
-               hipError_t e1 = hipMemcpyAsync(state, copy, sb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-               hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-               (void)hipFree(copy);
-               if (e1 != hipSuccess || e2 != hipSuccess)
-                  fail(FZ_E_HIP, std::string("the closure state could not be restored after the plan measurement of this shape (") +
-                                    hipGetErrorString(e1 != hipSuccess ? e1 : e2) + "): `state` is advanced by the measurement's blocks -- reset it (the measurement was asked for with FLOWZ_HIP_AUTOTUNE=1)");
-            }
-            if (rc == FZ_OK && (chosen.streams_per_lane || chosen.unroll || chosen.block_threads || chosen.flags)) {
-               planned = chosen;
-               uv = &planned;
-               from_plan = true;
-            } else if (rc != FZ_OK && std::getenv("FLOWZ_HIP_DEBUG")) {
-               std::fprintf(stderr, "[flowz_hip] plan measurement of this shape failed (%s): the library default runs\n", why.c_str());
-            }
-         }
-      }
-   }
-   Variant v;
+   const std::optional<fz_variant> planned = uv ? std::nullopt : launch_plan_of_shape(p, in, out, state, params, n_streams, n_samples, tile_streams,
+                                                                                      rows_total, row0, stream);
+   LaunchPlan lp;
    try {
-      v = finalize_variant(p, uv, n_streams, n_samples, tile_streams);
+      lp = plan_launch(p, planned ? &*planned : uv, n_streams, n_samples, tile_streams, rows_total);
    } catch (const Error&) {
       // a remembered plan that does not resolve any more (persisted by another build of the library, a damaged line that passed the
       // range checks): forget it and run the library's own choice instead of failing every default launch of this shape
-      if (!from_plan) throw;
+      if (!planned) throw;
       drop_plan(p, n_streams, tile_streams);
-      uv = nullptr;
-      v = finalize_variant(p, nullptr, n_streams, n_samples, tile_streams);
-   }
-   if (stream_major && (v.flags & FZ_VF_SM_LONG) && v.P == 2 && (uint64_t)rows_total >= (1ull << 23)) {
-      // the library's own choice of the pair body (128 rows per descriptor) on buffers too long for it: one stream per lane
-      fz_variant one = *uv;
-      one.streams_per_lane = 1;
-      v = finalize_variant(p, &one, n_streams, n_samples, tile_streams);
+      lp = plan_launch(p, nullptr, n_streams, n_samples, tile_streams, rows_total);
    }
    // sample-rate modulators: one array for all streams
    const float* mod_dev = nullptr;
@@ -372,28 +257,23 @@ int launch(fz_program* p, const float* in, float* out, float* state, const float
                       k->res.vgprs + k->res.agprs, k->res.scratch_bytes);
       }
    };
-   // the library's own lockstep choice may cover whole laps only and leave the last few streams to a launch of their own
-   // (time_major_geometry): those run what a block of that few streams runs by itself
-   const uint64_t main_streams = stream_major ? n_streams : lockstep_streams(g, uv, v, n_streams, tile_streams);
-   if (main_streams == n_streams) {
-      run_part(v, 0, n_streams, stream);
+   if (lp.main_streams == n_streams) {
+      run_part(lp.main, 0, n_streams, stream);
       return FZ_OK;
    }
    // The remainder runs NEXT TO the laps, not behind them: on a side stream of the program, forked from and joined to the caller's
    // stream by events (capturable like any fork / join).  Its few waves walk all the rows of the block on their own -- every row
    // another page, ~1.4 ms per 4096 rows for ONE stream behind a million (measured: 7.07 ms for 1 048 577 streams against 5.62 ms for
    // 1 048 576 when it ran behind the lap) -- and the lap's workgroups leave room for them (92 of a SIMD's 128 registers per lane).
-   const uint64_t rem = n_streams - main_streams;
-   const Variant r = remainder_variant(p, uv, n_streams, n_samples, rem);
-   (void)get_kernel(p, r, nullptr);                          // (resolved -- built, if need be -- before the side stream's mutex is taken)
-   (void)get_kernel(p, v, nullptr);
+   (void)get_kernel(p, lp.rem, nullptr);                    // (resolved -- built, if need be -- before the side stream's mutex is taken)
+   (void)get_kernel(p, lp.main, nullptr);
    SideStream& side = side_stream(p);
    std::lock_guard<std::mutex> fork_join(*side.mu);
    FZ_HIP(hipEventRecord((hipEvent_t)side.fork, (hipStream_t)stream));
    FZ_HIP(hipStreamWaitEvent((hipStream_t)side.stream, (hipEvent_t)side.fork, 0));
-   run_part(r, main_streams, rem, side.stream);
+   run_part(lp.rem, lp.main_streams, n_streams - lp.main_streams, side.stream);
    FZ_HIP(hipEventRecord((hipEvent_t)side.join, (hipStream_t)side.stream));
-   run_part(v, 0, main_streams, stream);
+   run_part(lp.main, 0, lp.main_streams, stream);
    FZ_HIP(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)side.join, 0));
    return FZ_OK;
 }

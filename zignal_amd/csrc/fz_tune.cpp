@@ -1,4 +1,5 @@
-// Measured plans: what fz_program_tune measures (tune_candidates), the measurement, and the winners' persistence per board.
+// Measured plans: what fz_program_tune measures (tune_candidates), the measurement, the winners' persistence per board, and the plan a
+// launch without a variant runs (launch_plan_of_shape: a measured one, or the opt-in measurement of the first big launch).
 // The static choice they compete with: fz_plan.cpp.
 #include <sys/stat.h>
 
@@ -7,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <optional>
 #include <sstream>
 
 #include "fz_runtime.hpp"
@@ -157,11 +159,11 @@ std::vector<fz_variant> tune_candidates(const Graph& g, uint64_t n_streams, uint
       if (!(d.flags & FZ_VF_STAGE_PACK)) {
          for (uint32_t P : {d.P * 2, d.P / 2}) {                                                    // the next packing up and down, each at its own geometry
             if (P < 1 || P > 4 || n_streams % P) continue;
-            const TmGeometry o = time_major_geometry(n_streams, P, g.op_weight > 30, false, P);
+            const TmGeometry o = time_major_geometry(n_streams, P, heavy_ops(g), false, P);
             if (o.P != P || o.main_streams != n_streams) continue;
             cands.push_back(fz_variant{P, o.U, o.lanes, FZ_VF_LOCKSTEP | G | (o.U == 1 ? (uint32_t)FZ_VF_PREFETCH3 : 0u)});
          }
-         if (g.split.ok && n_samples >= 16u * (g.split.atoms() - 1)) cands.push_back(fz_variant{1, 4, 1024, FZ_VF_LOCKSTEP | G | FZ_VF_STAGE_PACK});   // (register-heavy graphs)
+         if (stage_pack_pays(g, n_samples)) cands.push_back(fz_variant{1, 4, 1024, FZ_VF_LOCKSTEP | G | FZ_VF_STAGE_PACK});   // (register-heavy graphs)
       }
    } else if (d.P == 2) {                                 // stream tiles, many streams: workgroups per CU, and the lockstep geometries on tiles
       cands.push_back(fz_variant{2, 16, 256, (d.flags & FZ_VF_MAX_WG(7)) ? 0u : FZ_VF_MAX_WG(2)});
@@ -175,6 +177,104 @@ std::vector<fz_variant> tune_candidates(const Graph& g, uint64_t n_streams, uint
       if (!g.n_lds_slots && n_streams >= (1u << 17) && n_streams % 2 == 0 && g.n_in <= 2 && g.n_out <= 2) cands.push_back(fz_variant{2, 16, 0, 0});
    }
    return cands;
+}
+
+// ---- the plan of a launch without a variant ---------------------------------------------------------------------------------
+std::optional<fz_variant> launch_plan_of_shape(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
+                                               uint32_t n_samples, uint32_t tile_streams, uint32_t rows_total, uint32_t row0, void* stream)
+{
+   const Graph& g = p->g;
+   int dev = 0;
+   FZ_HIP(hipGetDevice(&dev));
+   const auto key = std::make_tuple(n_streams, tile_streams, dev);
+   std::optional<fz_variant> planned;
+   (void)planned_variant(p, n_streams, tile_streams);      // first launch of this shape: a plan persisted by an earlier process?
+   // A launch without a variant runs the plan fz_program_tune measured for the shape (this process or an earlier one: plans.txt), else
+   // the library's static choice.  Round 6: the measurement is never made behind the caller's back any more -- FLOWZ_HIP_AUTOTUNE=1
+   // opts in to what round 3-5 did by default: the first BIG block of a shape (>= 2^26 stream-samples) measures the candidates whose
+   // code objects are at hand on the caller's buffers (the state is saved and restored around it, `out` is recomputed by the launch;
+   // about ten launches each, nothing is JIT-compiled for it).
+   const char* const at_env = std::getenv("FLOWZ_HIP_AUTOTUNE");      // (read at every launch: a process may turn it on for some of its work)
+   const bool autotune = at_env && *at_env == '1';
+   bool may_tune = autotune && rows_total == n_samples && row0 == 0 && n_streams * (uint64_t)n_samples >= (1ull << 26);
+   if (may_tune) {
+      // not while the stream is being captured into a hipGraph (the measurement allocates and synchronises), and not
+      // in place: the candidates run on the caller's buffers, an aliased `in` would be overwritten before the real launch
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) (void)hipGetLastError();
+      const char* ib = reinterpret_cast<const char*>(in);
+      const char* ob = reinterpret_cast<const char*>(out);
+      const size_t ibytes = (size_t)n_streams * n_samples * g.n_in * 4, obytes = (size_t)n_streams * n_samples * std::max<uint32_t>(g.n_out, 1) * 4;
+      const bool overlap = in && ib < ob + obytes && ob < ib + ibytes;
+      may_tune = cap == hipStreamCaptureStatusNone && !overlap;
+   }
+   bool can_tune = false;
+   {
+      // (another thread's first big launch of this shape may be measuring the plan right now, on ITS buffers: wait for the
+      //  result instead of racing it -- the measuring thread's own launches carry explicit variants and never come here)
+      // ONE critical section decides who measures: the thread whose insert into `measuring` succeeds; everybody else of the
+      // shape waits above until that thread is done
+      std::unique_lock<std::mutex> lock(p->mu);
+      p->measured.wait(lock, [&] { return p->measuring.count(key) == 0; });
+      auto it = p->plans.find(key);
+      const bool known = it != p->plans.end() || p->tuned_default.count(key) != 0;
+      // (a plan is measured on blocks of thousands of samples: the wave-split kernels pay several masked rounds per launch and
+      //  are not what a short block -- the per-sample call protocol -- should run, whatever was tuned for the shape)
+      if (it != p->plans.end() && !(ws_parts(it->second.flags) && n_samples < 256)) planned = it->second;
+      if (may_tune && !known) {
+         p->tuned_default.insert(key);                   // (also stops the recursion through tune -> launch)
+         can_tune = p->measuring.insert(key).second;     // other launches of this shape wait until the plan is known
+      }
+   }
+   if (!can_tune) return planned;
+   struct Done {                                      // ... on every exit path
+      fz_program* p;
+      decltype(key) k;
+      ~Done()
+      {
+         {
+            std::lock_guard<std::mutex> lock(p->mu);
+            p->measuring.erase(k);
+         }
+         p->measured.notify_all();
+      }
+   } done{p, key};
+   const size_t sb = (size_t)g.n_state * n_streams * 4;
+   // The candidates run on the caller's buffers: the state is saved before and restored after the measurement, and the
+   // restore is CHECKED -- a state that could not be put back is an error of this launch, never a silent one.  A failure
+   // inside the measurement itself (a candidate's HIP error) is not the caller's problem: the default launch goes ahead.
+   float* copy = nullptr;
+   if (sb && hipMalloc((void**)&copy, sb) != hipSuccess) {           // no room for the snapshot (multi-GiB state): do not tune
+      (void)hipGetLastError();
+      return planned;
+   }
+   if (sb && hipMemcpyAsync(copy, state, sb, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(copy);
+      return planned;
+   }
+   fz_variant chosen{0, 0, 0, 0};
+   int rc = FZ_E_INVALID;
+   std::string why;
+   try {
+      rc = tune(p, in, out, state, params, n_streams, n_samples, tile_streams, stream, &chosen, nullptr, true);
+   } catch (const Error& er) {
+      rc = er.code;
+      why = er.msg;
+      if (er.code == FZ_E_HIP) (void)hipGetLastError();
+   }
+   if (copy) {
+      hipError_t e1 = hipMemcpyAsync(state, copy, sb, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+      hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
+      (void)hipFree(copy);
+      if (e1 != hipSuccess || e2 != hipSuccess)
+         fail(FZ_E_HIP, std::string("the closure state could not be restored after the plan measurement of this shape (") +
+                           hipGetErrorString(e1 != hipSuccess ? e1 : e2) + "): `state` is advanced by the measurement's blocks -- reset it (the measurement was asked for with FLOWZ_HIP_AUTOTUNE=1)");
+   }
+   if (rc == FZ_OK && (chosen.streams_per_lane || chosen.unroll || chosen.block_threads || chosen.flags)) return chosen;
+   if (rc != FZ_OK && std::getenv("FLOWZ_HIP_DEBUG"))
+      std::fprintf(stderr, "[flowz_hip] plan measurement of this shape failed (%s): the library default runs\n", why.c_str());
+   return planned;
 }
 
 // ---- plan selection ------------------------------------------------------------------------------------------
