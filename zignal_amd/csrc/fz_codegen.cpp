@@ -7,6 +7,8 @@
 //                      compiler cannot re-associate; contraction is disabled on the command line).
 #include <algorithm>
 #include <cstdio>
+#include <functional>
+#include <iterator>
 #include <map>
 #include <set>
 #include <sstream>
@@ -112,6 +114,31 @@ RingPlan ring_plan(const Graph& g, const Variant& v)
    return rp;
 }
 
+// LDS ring reads of a chunk, fetched TOGETHER at the start of the chunk (round 4).  A read `n - d` inside step() cannot be moved
+// above the ring write of the step before it (the compiler cannot tell the slots apart), so every step waited one LDS round trip per
+// line with nothing to hide it behind (one or two waves per SIMD: the rings fill the LDS) -- 240 clocks per step for the two combs of
+// the bench line's lds_ring graph.  A read whose delay is at least the chunk length refers to a slot written BEFORE the chunk
+// started, for every step of the chunk: all of a chunk's reads can be issued up front, into registers (`lr<k>[u]`), one round
+// trip per chunk.  Float lines, frame kernels (the stream-major bodies call step() without a chunk position and read in place);
+// at most 96 registers.  Vectorised rings (ring_plan) fetch every read of a sub-chunk this way.
+struct RingRead { uint32_t line, d, m, nv; };              // m: slots between the 16-byte grid and the read's first slot; nv: vectors per sub-chunk
+static std::vector<RingRead> ring_reads(const Graph& g, const Variant& v, const RingPlan& rp)
+{
+   std::vector<RingRead> r;
+   if (!rp.vec && ((v.flags & FZ_VF_STREAM_MAJOR) || v.U < 2)) return r;
+   for (const Node& nd : g.nodes) {
+      if (nd.kind != FZ_IR_DELAY) continue;
+      const uint32_t l = (uint32_t)g.line_of_node[nd.a];
+      const Line& L = g.lines[l];
+      if (!L.in_lds || (!rp.vec && (L.f64 || L.far || nd.b < v.U))) continue;
+      if (std::any_of(r.begin(), r.end(), [&](const RingRead& x) { return x.line == l && x.d == nd.b; })) continue;
+      const uint32_t m = rp.vec ? (rp.TW - nd.b % rp.TW) % rp.TW : 0;
+      r.push_back(RingRead{l, nd.b, m, rp.vec ? (m + rp.G + rp.TW - 1) / rp.TW : 0});
+   }
+   if (!rp.vec && r.size() * v.U * v.P > 96) r.clear();
+   return r;
+}
+
 std::string gen_config(const Graph& g, const Variant& v)
 {
    if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_config(g, v);
@@ -159,6 +186,59 @@ std::string gen_config(const Graph& g, const Variant& v)
          o << "#define FZ_WS_K" << k << " " << (k < W && roles ? (*roles)[k].split.atoms() : 0u) << "   // skewed units (segments x atoms) of part " << k << "\n";
    }
    return o.str();
+}
+
+// How every operation kind is written in C++, for all the generated bodies.  `op`: the operator where C++ has one; `fn`: the device
+// function the text calls.  Division and the comparisons have both: the frame body calls fz_div / fz_cmp<K> on a lane's streams, the
+// scalar bodies (stage packing, the adjoint) use the operator -- a comparison as (a < b) ? 1.f : 0.f.
+struct OpSpelling { uint32_t kind; const char* op; const char* fn; uint32_t arity; };
+static const OpSpelling kOps[] = {
+   {FZ_IR_ADD, "+", nullptr, 2}, {FZ_IR_SUB, "-", nullptr, 2}, {FZ_IR_MUL, "*", nullptr, 2}, {FZ_IR_DIV, "/", "fz_div", 2},
+   {FZ_IR_NEG, "-", nullptr, 1}, {FZ_IR_WIDEN, nullptr, "fz_cvt_d", 1}, {FZ_IR_NARROW, nullptr, "fz_cvt_f", 1},
+   {FZ_IR_ABSLT, nullptr, "fz_abs_lt", 2}, {FZ_IR_SELECT, nullptr, "fz_select", 3},
+   {FZ_IR_LT, "<", "fz_cmp", 2}, {FZ_IR_LE, "<=", "fz_cmp", 2}, {FZ_IR_GT, ">", "fz_cmp", 2}, {FZ_IR_GE, ">=", "fz_cmp", 2},
+   {FZ_IR_EQ, "==", "fz_cmp", 2}, {FZ_IR_NE, "!=", "fz_cmp", 2},
+   {FZ_IR_ABS, nullptr, "fz_abs", 1}, {FZ_IR_SQRT, nullptr, "fz_sqrt", 1}, {FZ_IR_EXP, nullptr, "fz_exp", 1}, {FZ_IR_TANH, nullptr, "fz_tanh", 1},
+   {FZ_IR_MIN, nullptr, "fz_min", 2}, {FZ_IR_MAX, nullptr, "fz_max", 2},
+};
+
+static bool is_cmp(uint32_t kind) { return kind >= FZ_IR_LT && kind <= FZ_IR_NE; }
+
+// operand k (0: a, 1: b, 2: c) of a node
+static uint32_t operand(const Node& nd, uint32_t k) { return k == 0 ? nd.a : k == 1 ? nd.b : nd.c; }
+
+// The right-hand side of an operation node, "" for any other kind (inputs, coefficients, delayed reads: each body reads those from
+// where it keeps them).  x(k, common) writes operand k as the body names it; common: the operand is taken in the operation's common
+// type (every operand of a binary operation, the two sides of a selection), which the frame body reaches by promoting float to double.
+// frame: the frame body's spelling, else the scalar bodies'.
+static std::string op_expr(uint32_t kind, bool frame, const std::function<std::string(uint32_t, bool)>& x)
+{
+   const OpSpelling* s = std::find_if(std::begin(kOps), std::end(kOps), [&](const OpSpelling& t) { return t.kind == kind; });
+   if (s == std::end(kOps)) return "";
+   if (s->op && !(frame && s->fn)) {
+      if (s->arity == 1) return s->op + x(0, false);
+      const std::string e = x(0, true) + " " + s->op + " " + x(1, true);
+      return is_cmp(kind) ? "(" + e + ") ? 1.f : 0.f" : e;
+   }
+   std::string e = std::string(s->fn) + (is_cmp(kind) ? "<" + std::to_string(kind) + ">" : "") + "(";
+   for (uint32_t k = 0; k < s->arity; ++k) e += (k ? ", " : "") + x(k, s->arity > 1 && !(kind == FZ_IR_SELECT && k == 0));
+   return e + ")";
+}
+
+// One step of a delay line kept in registers: age a takes age a - 1 (a = depth .. 2), age 1 takes the new value `in`; reg(a) names the
+// register of age a.  With a guard (the masked steps of a stage-packed body: does the line's segment run?) a register keeps its value
+// where the guard is false; a packed pair of lines has a guard per half (guard: .x, guard_y: .y).
+static void shift_line(std::ostringstream& o, uint32_t depth, const std::function<std::string(uint32_t)>& reg, const std::string& in,
+                       const std::string& guard = "", const std::string& guard_y = "")
+{
+   for (uint32_t a = depth; a >= 1; --a) {
+      const std::string r = reg(a), nv = a == 1 ? in : reg(a - 1);
+      o << "      " << r << " = ";
+      if (guard.empty()) o << nv;
+      else if (guard_y.empty()) o << guard << " ? " << nv << " : " << r;
+      else o << "(fz_f2){" << guard << " ? " << nv << ".x : " << r << ".x, " << guard_y << " ? " << nv << ".y : " << r << ".y}";
+      o << ";\n";
+   }
 }
 
 static std::string gen_body_skew(const Graph& g, const StageSplit& sp);
@@ -257,21 +337,9 @@ static void emit_functions(std::ostringstream& o, const Graph& g)
    }
 }
 
-std::string gen_body(const Graph& g, const Variant& v)
+// the frame kernels' body: struct fz_graph with the graph's state and step(), one sample of the whole graph
+static std::string gen_body_frames(const Graph& g, const Variant& v)
 {
-   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_body(g);
-   if (const uint32_t W = ws_parts(v.flags)) {
-      // the parts of the graph, each a stage-packed body of its own (struct fz_r0::fz_graph, fz_r1::fz_graph, ...)
-      const std::vector<Graph>* roles = g.wave_roles(W);
-      if (!roles) fail(FZ_E_UNSUPPORTED, "wave split: the graph is not that many isomorphic parts in series");
-      std::string s;
-      for (uint32_t r = 0; r < 4; ++r) {
-         if (r < W) s += "namespace fz_r" + std::to_string(r) + " {\n" + gen_body_skew((*roles)[r], (*roles)[r].split) + "}\n#undef FZ_NSEG\n";
-         else s += "namespace fz_r" + std::to_string(r) + " { typedef fz_r0::fz_graph fz_graph; }\n";   // (unused: keeps the dispatch uniform)
-      }
-      return s;
-   }
-   if (v.flags & FZ_VF_STAGE_PACK) return gen_body_skew(g, g.split);
    std::ostringstream o;
    auto val = [&](uint32_t id) { return "v" + std::to_string(id); };
    auto reg = [&](size_t line, uint32_t age) { return "r" + std::to_string(line) + "_" + std::to_string(age); };
@@ -318,12 +386,13 @@ std::string gen_body(const Graph& g, const Variant& v)
    o << "__device__ __forceinline__ V fz_div(V a, V b) { return a / b; }\n";
    o << "__device__ __forceinline__ VD fz_div(VD a, VD b) { return a / b; }\n";
    bool has_cmp = false;
-   for (const Node& nd : g.nodes) has_cmp = has_cmp || (nd.kind >= FZ_IR_LT && nd.kind <= FZ_IR_NE);
+   for (const Node& nd : g.nodes) has_cmp = has_cmp || is_cmp(nd.kind);
    if (has_cmp) {
       // the comparison operators of C++ on the streams of a lane: 1.0f / 0.0f (IEEE: every comparison with a NaN is false, != true); operands in
       // their common type.  Part of the GRAPH's text: kernels of graphs without comparisons keep their code.
-      o << "template <int K, typename T> __device__ __forceinline__ bool fz_cmp1(T a, T b) { return K == " << FZ_IR_LT << " ? a < b : K == " << FZ_IR_LE
-        << " ? a <= b : K == " << FZ_IR_GT << " ? a > b : K == " << FZ_IR_GE << " ? a >= b : K == " << FZ_IR_EQ << " ? a == b : a != b; }\n";
+      o << "template <int K, typename T> __device__ __forceinline__ bool fz_cmp1(T a, T b) { return ";
+      for (const OpSpelling& s : kOps)
+         if (is_cmp(s.kind)) o << (s.kind < FZ_IR_NE ? "K == " + std::to_string(s.kind) + " ? " : std::string()) << "a " << s.op << " b" << (s.kind < FZ_IR_NE ? " : " : "; }\n");
       o << "#if FZ_P == 1\n";
       o << "template <int K> __device__ __forceinline__ V fz_cmp(V a, V b) { return fz_cmp1<K>(a, b) ? 1.f : 0.f; }\n";
       o << "template <int K> __device__ __forceinline__ V fz_cmp(VD a, VD b) { return fz_cmp1<K>(a, b) ? 1.f : 0.f; }\n";
@@ -357,44 +426,21 @@ std::string gen_body(const Graph& g, const Variant& v)
       o << ";   // line " << l << ": node " << L.src << " delayed by 1.." << L.depth << (L.f64 ? " (double state)" : "") << "\n";
    }
    for (uint32_t k = 0; k < g.n_param; ++k) o << "   V p" << k << ";\n";
-   // LDS ring reads of a chunk, fetched TOGETHER at the start of the chunk (round 4).  A read `n - d` inside step() cannot be moved
-   // above the ring write of the step before it (the compiler cannot tell the slots apart), so every step waited one LDS round trip per
-   // line with nothing to hide it behind (one or two waves per SIMD: the rings fill the LDS) -- 240 clocks per step for the two combs of
-   // the bench line's lds_ring graph.  A read whose delay is at least the chunk length refers to a slot written BEFORE the chunk
-   // started, for every step of the chunk: all of a chunk's reads can be issued up front, into registers (`lr<k>[u]`), one round
-   // trip per chunk.  Float lines, frame kernels (the stream-major bodies call step() without a chunk position and read in place);
-   // at most 96 registers.
-   struct RingRead { uint32_t line, d, m, nv; };              // m: slots between the 16-byte grid and the read's first slot; nv: vectors per sub-chunk
-   std::vector<RingRead> ring_reads;
-   std::map<std::pair<uint32_t, uint32_t>, size_t> ring_read_of;
+   const std::vector<RingRead> reads = ring_reads(g, v, rp);
+   auto read_of = [&](uint32_t line, uint32_t d) {            // index of that read in `reads`, reads.size(): read in place
+      size_t k = 0;
+      while (k < reads.size() && !(reads[k].line == line && reads[k].d == d)) ++k;
+      return k;
+   };
    if (rp.vec) {
-      for (const Node& nd : g.nodes) {
-         if (nd.kind != FZ_IR_DELAY) continue;
-         const int l = g.line_of_node[nd.a];
-         if (!g.lines[(size_t)l].in_lds) continue;
-         const uint32_t m = (rp.TW - nd.b % rp.TW) % rp.TW;
-         if (ring_read_of.emplace(std::make_pair((uint32_t)l, nd.b), ring_reads.size()).second)
-            ring_reads.push_back(RingRead{(uint32_t)l, nd.b, m, (m + rp.G + rp.TW - 1) / rp.TW});
-      }
-      for (size_t k = 0; k < ring_reads.size(); ++k)
-         o << "   fz_f4 lr" << k << "[" << ring_reads[k].nv << "];   // line " << ring_reads[k].line << " read " << ring_reads[k].d
-           << " samples back: the sub-chunk's slots as 16-byte vectors, the first value " << ring_reads[k].m << " slots in\n";
+      for (size_t k = 0; k < reads.size(); ++k)
+         o << "   fz_f4 lr" << k << "[" << reads[k].nv << "];   // line " << reads[k].line << " read " << reads[k].d
+           << " samples back: the sub-chunk's slots as 16-byte vectors, the first value " << reads[k].m << " slots in\n";
       for (size_t l = 0; l < g.lines.size(); ++l)
          if (g.lines[l].in_lds) o << "   fz_f4 wb" << l << "[" << rp.G / rp.TW << "];   // the sub-chunk's pushes of line " << l << "\n";
-   } else if (!(v.flags & FZ_VF_STREAM_MAJOR) && v.U >= 2) {
-      for (const Node& nd : g.nodes) {
-         if (nd.kind != FZ_IR_DELAY) continue;
-         const int l = g.line_of_node[nd.a];
-         const Line& L = g.lines[(size_t)l];
-         if (!L.in_lds || L.f64 || L.far || nd.b < v.U) continue;
-         if (ring_read_of.emplace(std::make_pair((uint32_t)l, nd.b), ring_reads.size()).second) ring_reads.push_back(RingRead{(uint32_t)l, nd.b, 0, 0});
-      }
-      if (ring_reads.size() * v.U * v.P > 96) {
-         ring_reads.clear();
-         ring_read_of.clear();
-      }
-      for (size_t k = 0; k < ring_reads.size(); ++k)
-         o << "   V lr" << k << "[FZ_U];   // line " << ring_reads[k].line << " read " << ring_reads[k].d << " samples back, the steps of the chunk at hand\n";
+   } else {
+      for (size_t k = 0; k < reads.size(); ++k)
+         o << "   V lr" << k << "[FZ_U];   // line " << reads[k].line << " read " << reads[k].d << " samples back, the steps of the chunk at hand\n";
    }
    o << "   const float* mod = nullptr;   // sample-rate modulators [n_mod][mod_stride], set by the kernel (row 0 of the block)\n";
    o << "   unsigned mod_stride = 0;\n";
@@ -431,58 +477,48 @@ std::string gen_body(const Graph& g, const Variant& v)
       o << "      p" << k << " = fz_ld_row(pp + (size_t)" << k << " * ns, soff, ns);\n";
    o << "   }\n";
 
-   // ---- state in: row (row0 + j) holds the wire's value at t-1-j
+   // ---- the state rows of line l, in (load_state) or out (store_state): row (row0 + j) holds the wire's value at t-1-j, a double
+   // line's low and high words in rows (row0 + 2j, row0 + 2j + 1).  A register line is written out row by row; an LDS ring is a loop
+   // over j, its value of age j + 1 at ring position `n - 1u - j` (n: the samples done, "0u" for the state in)
+   auto state_rows = [&](size_t l, bool in, const std::string& n) {
+      const Line& L = g.lines[l];
+      const std::string fn = std::string(in ? "fz_ld_row" : "fz_st_row") + (L.f64 ? "64" : ""), args = L.f64 ? ", soff" : ", soff, ns";
+      auto move = [&](const char* ind, const std::string& row, const std::string& value) {
+         if (in) o << ind << value << " = " << fn << "(st + (size_t)" << row << " * ns" << args << ");\n";
+         else o << ind << fn << "(st + (size_t)" << row << " * ns" << args << ", " << value << ");\n";
+      };
+      if (!L.in_lds) {
+         for (uint32_t j = 0; j < L.depth; ++j) move("      ", std::to_string(L.row0 + (L.f64 ? 2 : 1) * j), reg(l, j + 1));
+         return;
+      }
+      const std::string row = "(" + std::to_string(L.row0) + (L.f64 ? "u + 2u * j)" : "u + j)"), pos = n + " - 1u - j";
+      o << "      for (unsigned j = 0; j < " << L.depth << "u; ++j)" << (L.f64 && in ? " {\n" : "\n");
+      if (!L.f64) move("         ", row, ring_at(L, pos));
+      else if (!in) move("         ", row, "fz_join_d(" + ring_at(L, pos) + ", " + ring_hi(L, pos) + ")");
+      else {
+         move("         ", row, "const VD d_");
+         o << "         " << ring_at(L, pos) << " = fz_lo_d(d_);\n";
+         o << "         " << ring_hi(L, pos) << " = fz_hi_d(d_);\n";
+         o << "      }\n";
+      }
+   };
    o << "   __device__ __forceinline__ void load_state(const float* st, size_t ns, unsigned soff, V* ring, unsigned tid, const unsigned* ph)\n   {\n";
    o << "      (void)st; (void)ns; (void)soff; (void)ring; (void)tid; (void)ph;\n";
    for (size_t l = 0; l < g.lines.size(); ++l) {
       const Line& L = g.lines[l];
-      if (L.far) {
-         // the newest values sit just behind the ring phase: age j+1 at slot (ph - 1 - j) mod D
+      if (!L.far) state_rows(l, true, "0u");
+      else   // the newest values sit just behind the ring phase: age j+1 at slot (ph - 1 - j) mod D
          for (uint32_t j = 0; j < L.shadow; ++j)
             o << "      " << shadow(l, j + 1) << " = fz_ld_row(st + (size_t)(" << L.row0 << "u + (ph[" << fidx(l) << "] + " << (L.depth - 1 - j)
               << "u) % " << L.depth << "u) * ns, soff, ns);\n";
-         continue;
-      }
-      if (L.f64 && L.in_lds) {
-         o << "      for (unsigned j = 0; j < " << L.depth << "u; ++j) {\n";
-         o << "         const VD d_ = fz_ld_row64(st + (size_t)(" << L.row0 << "u + 2u * j) * ns, soff);\n";
-         o << "         " << ring_at(L, "0u - 1u - j") << " = fz_lo_d(d_);\n";
-         o << "         " << ring_hi(L, "0u - 1u - j") << " = fz_hi_d(d_);\n";
-         o << "      }\n";
-      } else if (L.f64) {
-         for (uint32_t j = 0; j < L.depth; ++j)
-            o << "      " << reg(l, j + 1) << " = fz_ld_row64(st + (size_t)" << (L.row0 + 2 * j) << " * ns, soff);\n";
-      } else if (!L.in_lds) {
-         for (uint32_t j = 0; j < L.depth; ++j)
-            o << "      " << reg(l, j + 1) << " = fz_ld_row(st + (size_t)" << (L.row0 + j) << " * ns, soff, ns);\n";
-      } else {
-         o << "      for (unsigned j = 0; j < " << L.depth << "u; ++j)\n";
-         o << "         " << ring_at(L, "0u - 1u - j") << " = fz_ld_row(st + (size_t)(" << L.row0 << "u + j) * ns, soff, ns);\n";
-      }
    }
    o << "   }\n";
 
    // ---- state out after n_done samples
    o << "   __device__ __forceinline__ void store_state(float* st, size_t ns, unsigned soff, V* ring, unsigned tid, unsigned n_done)\n   {\n";
    o << "      (void)st; (void)ns; (void)soff; (void)ring; (void)tid; (void)n_done;\n";
-   for (size_t l = 0; l < g.lines.size(); ++l) {
-      const Line& L = g.lines[l];
-      if (L.far) continue;                 // the ring rows are written sample by sample
-      if (L.f64 && L.in_lds) {
-         o << "      for (unsigned j = 0; j < " << L.depth << "u; ++j)\n";
-         o << "         fz_st_row64(st + (size_t)(" << L.row0 << "u + 2u * j) * ns, soff, fz_join_d(" << ring_at(L, "n_done - 1u - j") << ", "
-           << ring_hi(L, "n_done - 1u - j") << "));\n";
-      } else if (L.f64) {
-         for (uint32_t j = 0; j < L.depth; ++j)
-            o << "      fz_st_row64(st + (size_t)" << (L.row0 + 2 * j) << " * ns, soff, " << reg(l, j + 1) << ");\n";
-      } else if (!L.in_lds) {
-         for (uint32_t j = 0; j < L.depth; ++j)
-            o << "      fz_st_row(st + (size_t)" << (L.row0 + j) << " * ns, soff, ns, " << reg(l, j + 1) << ");\n";
-      } else {
-         o << "      for (unsigned j = 0; j < " << L.depth << "u; ++j)\n";
-         o << "         fz_st_row(st + (size_t)(" << L.row0 << "u + j) * ns, soff, ns, " << ring_at(L, "n_done - 1u - j") << ");\n";
-      }
-   }
+   for (size_t l = 0; l < g.lines.size(); ++l)
+      if (!g.lines[l].far) state_rows(l, false, "n_done");   // (a far line's ring rows are written sample by sample)
    o << "   }\n";
 
    // ---- one sample
@@ -493,13 +529,13 @@ std::string gen_body(const Graph& g, const Variant& v)
    o << "      (void)ring; (void)tid; (void)n0;\n";
    if (rp.vec) {
       // n0: first sample of the sub-chunk (a multiple of FZ_RING_G); vector j of read k starts at sample n0 - d - m + j * (4 / P)
-      for (size_t k = 0; k < ring_reads.size(); ++k)
-         for (uint32_t j = 0; j < ring_reads[k].nv; ++j)
-            o << "      lr" << k << "[" << j << "] = " << ring_vec_at(g.lines[ring_reads[k].line], "n0 + " + std::to_string(j * rp.TW) + "u - " + std::to_string(ring_reads[k].d + ring_reads[k].m) + "u") << ";\n";
-   } else if (!ring_reads.empty()) {
+      for (size_t k = 0; k < reads.size(); ++k)
+         for (uint32_t j = 0; j < reads[k].nv; ++j)
+            o << "      lr" << k << "[" << j << "] = " << ring_vec_at(g.lines[reads[k].line], "n0 + " + std::to_string(j * rp.TW) + "u - " + std::to_string(reads[k].d + reads[k].m) + "u") << ";\n";
+   } else if (!reads.empty()) {
       o << "      _Pragma(\"unroll\") for (int u = 0; u < FZ_U; ++u)\n      {\n";
-      for (size_t k = 0; k < ring_reads.size(); ++k)
-         o << "         lr" << k << "[u] = " << ring_at(g.lines[ring_reads[k].line], "n0 + (unsigned)u - " + std::to_string(ring_reads[k].d) + "u") << ";\n";
+      for (size_t k = 0; k < reads.size(); ++k)
+         o << "         lr" << k << "[u] = " << ring_at(g.lines[reads[k].line], "n0 + (unsigned)u - " + std::to_string(reads[k].d) + "u") << ";\n";
       o << "      }\n";
    }
    o << "   }\n";
@@ -543,35 +579,21 @@ std::string gen_body(const Graph& g, const Variant& v)
             } else if (!L.in_lds) o << reg((size_t)l, nd.b);
             else if (L.f64) o << "fz_join_d(" << ring_at(L, "n - " + std::to_string(nd.b) + "u") << ", " << ring_hi(L, "n - " + std::to_string(nd.b) + "u") << ")";
             else {
-               const auto it = ring_read_of.find(std::make_pair((uint32_t)l, nd.b));
-               if (it != ring_read_of.end() && rp.vec)
-                  o << "(u >= 0 ? fz_ring_pick(lr" << it->second << ", " << ring_reads[it->second].m << " + (u % " << rp.G << ")) : " << ring_at(L, "n - " + std::to_string(nd.b) + "u") << ")";
-               else if (it != ring_read_of.end()) o << "(u >= 0 ? lr" << it->second << "[u] : " << ring_at(L, "n - " + std::to_string(nd.b) + "u") << ")";
+               const size_t k = read_of((uint32_t)l, nd.b);
+               if (k < reads.size() && rp.vec)
+                  o << "(u >= 0 ? fz_ring_pick(lr" << k << ", " << reads[k].m << " + (u % " << rp.G << ")) : " << ring_at(L, "n - " + std::to_string(nd.b) + "u") << ")";
+               else if (k < reads.size()) o << "(u >= 0 ? lr" << k << "[u] : " << ring_at(L, "n - " + std::to_string(nd.b) + "u") << ")";
                else o << ring_at(L, "n - " + std::to_string(nd.b) + "u");
             }
             break;
          }
-         case FZ_IR_ADD: o << opnd(nd.a, d) << " + " << opnd(nd.b, d); break;
-         case FZ_IR_SUB: o << opnd(nd.a, d) << " - " << opnd(nd.b, d); break;
-         case FZ_IR_MUL: o << opnd(nd.a, d) << " * " << opnd(nd.b, d); break;
-         case FZ_IR_DIV: o << "fz_div(" << opnd(nd.a, d) << ", " << opnd(nd.b, d) << ")"; break;
-         case FZ_IR_NEG: o << "-" << val(nd.a); break;
-         case FZ_IR_LT: case FZ_IR_LE: case FZ_IR_GT: case FZ_IR_GE: case FZ_IR_EQ: case FZ_IR_NE: {
-            const bool dd = g.nodes[nd.a].f64 || g.nodes[nd.b].f64;   // compared in double when one operand is; the node itself is a float
-            o << "fz_cmp<" << nd.kind << ">(" << opnd(nd.a, dd) << ", " << opnd(nd.b, dd) << ")";
-            break;
+         default: {
+            // compared in double when one operand is (the node itself is a float); every other operation in the node's own type
+            const bool wide = is_cmp(nd.kind) ? g.nodes[nd.a].f64 || g.nodes[nd.b].f64 : d;
+            const std::string e = op_expr(nd.kind, true, [&](uint32_t k, bool common) { return common ? opnd(operand(nd, k), wide) : val(operand(nd, k)); });
+            if (e.empty()) fail(FZ_E_GRAPH, "internal: unknown IR node kind");
+            o << e;
          }
-         case FZ_IR_ABSLT: o << "fz_abs_lt(" << opnd(nd.a, d) << ", " << opnd(nd.b, d) << ")"; break;
-         case FZ_IR_ABS: o << "fz_abs(" << val(nd.a) << ")"; break;
-         case FZ_IR_SQRT: o << "fz_sqrt(" << val(nd.a) << ")"; break;
-         case FZ_IR_EXP: o << "fz_exp(" << val(nd.a) << ")"; break;
-         case FZ_IR_TANH: o << "fz_tanh(" << val(nd.a) << ")"; break;
-         case FZ_IR_MIN: o << "fz_min(" << opnd(nd.a, d) << ", " << opnd(nd.b, d) << ")"; break;
-         case FZ_IR_MAX: o << "fz_max(" << opnd(nd.a, d) << ", " << opnd(nd.b, d) << ")"; break;
-         case FZ_IR_SELECT: o << "fz_select(" << val(nd.a) << ", " << opnd(nd.b, d) << ", " << opnd(nd.c, d) << ")"; break;
-         case FZ_IR_WIDEN: o << "fz_cvt_d(" << val(nd.a) << ")"; break;
-         case FZ_IR_NARROW: o << "fz_cvt_f(" << val(nd.a) << ")"; break;
-         default: fail(FZ_E_GRAPH, "internal: unknown IR node kind");
       }
       o << ";\n";
    }
@@ -587,13 +609,9 @@ std::string gen_body(const Graph& g, const Variant& v)
       const Line& L = g.lines[l];
       if (L.far) {
          o << "      hw[" << fidx(l) << "] = " << as_f32(L.src) << ";\n";
-         for (uint32_t a = L.shadow; a >= 2; --a) o << "      " << shadow(l, a) << " = " << shadow(l, a - 1) << ";\n";
-         if (L.shadow) o << "      " << shadow(l, 1) << " = " << as_f32(L.src) << ";\n";
-         continue;
-      }
-      if (!L.in_lds) {
-         for (uint32_t a = L.depth; a >= 2; --a) o << "      " << reg(l, a) << " = " << reg(l, a - 1) << ";\n";
-         o << "      " << reg(l, 1) << " = " << (L.f64 ? val(L.src) : as_f32(L.src)) << ";\n";
+         shift_line(o, L.shadow, [&](uint32_t a) { return shadow(l, a); }, as_f32(L.src));
+      } else if (!L.in_lds) {
+         shift_line(o, L.depth, [&](uint32_t a) { return reg(l, a); }, L.f64 ? val(L.src) : as_f32(L.src));
       } else if (L.f64) {
          o << "      " << ring_at(L, "n") << " = fz_lo_d(" << val(L.src) << ");\n";
          o << "      " << ring_hi(L, "n") << " = fz_hi_d(" << val(L.src) << ");\n";
@@ -607,6 +625,27 @@ std::string gen_body(const Graph& g, const Variant& v)
    o << "   }\n";
    o << "};\n";
    return o.str();
+}
+
+// the wave split: the parts of the graph, each a stage-packed body of its own (struct fz_r0::fz_graph, fz_r1::fz_graph, ...)
+static std::string gen_body_waves(const Graph& g, uint32_t W)
+{
+   const std::vector<Graph>* roles = g.wave_roles(W);
+   if (!roles) fail(FZ_E_UNSUPPORTED, "wave split: the graph is not that many isomorphic parts in series");
+   std::string s;
+   for (uint32_t r = 0; r < 4; ++r) {
+      if (r < W) s += "namespace fz_r" + std::to_string(r) + " {\n" + gen_body_skew((*roles)[r], (*roles)[r].split) + "}\n#undef FZ_NSEG\n";
+      else s += "namespace fz_r" + std::to_string(r) + " { typedef fz_r0::fz_graph fz_graph; }\n";   // (unused: keeps the dispatch uniform)
+   }
+   return s;
+}
+
+std::string gen_body(const Graph& g, const Variant& v)
+{
+   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_body(g);
+   if (const uint32_t W = ws_parts(v.flags)) return gen_body_waves(g, W);
+   if (v.flags & FZ_VF_STAGE_PACK) return gen_body_skew(g, g.split);
+   return gen_body_frames(g, v);
 }
 
 // Stage-packed body (FZ_VF_STAGE_PACK, one stream per lane): K isomorphic segments, segment j at
@@ -789,26 +828,20 @@ static std::string gen_body_skew(const Graph& g, const StageSplit& sp)
             if (sp.lines[l].frame == frame && sp.lines[l].srcs[pz] == src && age <= sp.lines[l].depth) return q(l, pz % NS, age) + (pz >= NS ? ".y" : ".x");
       fail(FZ_E_GRAPH, "internal: a scalar prefix / suffix reads a delay line that is not materialised in its time frame");
    };
+   // an operation of the chain or of a scalar part: one of the kinds the split takes (fz_split.cpp: is_arith), x(k) its operand k
+   auto arith = [&](const Node& nd, const std::function<std::string(uint32_t)>& x) {
+      if (!is_arith(nd.kind)) fail(FZ_E_GRAPH, "internal: a node kind stage packing does not take");
+      return op_expr(nd.kind, false, [&](uint32_t k, bool) { return x(k); });
+   };
    for (uint32_t v : sp.prefix) {
       const Node& nd = g.nodes[v];
+      const int l = nd.kind == FZ_IR_DELAY ? g.line_of_node[nd.a] : -1;
       o << "      const float u" << v << " = ";
-      switch (nd.kind) {
-         case FZ_IR_INPUT: o << "x[0]"; break;
-         case FZ_IR_CONST: o << "c[" << nd.a << "]"; break;
-         case FZ_IR_PARAM: o << "pf" << nd.a; break;
-         case FZ_IR_DELAY: {
-            const int l = g.line_of_node[nd.a];
-            if (l >= 0 && is_prefix_line[(size_t)l]) o << ps((uint32_t)l, nd.b);
-            else o << packed_comp_of(nd.a, nd.b, 0);
-            break;
-         }
-         case FZ_IR_ADD: o << "u" << nd.a << " + u" << nd.b; break;
-         case FZ_IR_SUB: o << "u" << nd.a << " - u" << nd.b; break;
-         case FZ_IR_MUL: o << "u" << nd.a << " * u" << nd.b; break;
-         case FZ_IR_DIV: o << "u" << nd.a << " / u" << nd.b; break;
-         case FZ_IR_NEG: o << "-u" << nd.a; break;
-         default: fail(FZ_E_GRAPH, "internal: unknown IR node kind");
-      }
+      if (nd.kind == FZ_IR_INPUT) o << "x[0]";
+      else if (nd.kind == FZ_IR_CONST) o << "c[" << nd.a << "]";
+      else if (nd.kind == FZ_IR_PARAM) o << "pf" << nd.a;
+      else if (nd.kind == FZ_IR_DELAY) o << (l >= 0 && is_prefix_line[(size_t)l] ? ps((uint32_t)l, nd.b) : packed_comp_of(nd.a, nd.b, 0));
+      else o << arith(nd, [&](uint32_t k) { return "u" + std::to_string(operand(nd, k)); });
       o << ";\n";
    }
    const std::string chain_in = g.nodes[sp.cuts[0]].kind == FZ_IR_INPUT ? std::string("x[0]") : "u" + std::to_string(sp.cuts[0]);
@@ -826,18 +859,9 @@ static std::string gen_body_skew(const Graph& g, const StageSplit& sp)
             continue;
          }
          const uint32_t rs = sp.sub.empty() ? 0u : sp.sub[k];                 // the atom this operation belongs to
-         switch (n0.kind) {
-            case FZ_IR_INPUT:
-               break;
-            case FZ_IR_CONST: o << "(fz_f2){c[" << na.a << "], c[" << nb.a << "]}"; break;
-            case FZ_IR_PARAM: o << "pp" << k << "_" << i; break;
-            case FZ_IR_ADD: o << w(operand_tuple(t, false), i, rs) << " + " << w(operand_tuple(t, true), i, rs); break;
-            case FZ_IR_SUB: o << w(operand_tuple(t, false), i, rs) << " - " << w(operand_tuple(t, true), i, rs); break;
-            case FZ_IR_MUL: o << w(operand_tuple(t, false), i, rs) << " * " << w(operand_tuple(t, true), i, rs); break;
-            case FZ_IR_DIV: o << w(operand_tuple(t, false), i, rs) << " / " << w(operand_tuple(t, true), i, rs); break;
-            case FZ_IR_NEG: o << "-" << w(operand_tuple(t, false), i, rs); break;
-            default: fail(FZ_E_GRAPH, "internal: unknown IR node kind");
-         }
+         if (n0.kind == FZ_IR_CONST) o << "(fz_f2){c[" << na.a << "], c[" << nb.a << "]}";
+         else if (n0.kind == FZ_IR_PARAM) o << "pp" << k << "_" << i;
+         else o << arith(n0, [&](uint32_t j) { return w(operand_tuple(t, j == 1), i, rs); });
          o << ";\n";
       }
    }
@@ -858,21 +882,10 @@ static std::string gen_body_skew(const Graph& g, const StageSplit& sp)
       for (uint32_t v : sp.suffix) {
          const Node& nd = g.nodes[v];
          if (nd.kind == FZ_IR_CONST || nd.kind == FZ_IR_PARAM) continue;
+         const int l = nd.kind == FZ_IR_DELAY ? g.line_of_node[nd.a] : -1;
          o << "      const float z" << v << " = ";
-         switch (nd.kind) {
-            case FZ_IR_DELAY: {
-               const int l = g.line_of_node[nd.a];
-               if (l >= 0 && is_suffix_line[(size_t)l]) o << ss((uint32_t)l, nd.b);
-               else o << packed_comp_of(nd.a, nd.b, M - 1);
-               break;
-            }
-            case FZ_IR_ADD: o << sval(nd.a) << " + " << sval(nd.b); break;
-            case FZ_IR_SUB: o << sval(nd.a) << " - " << sval(nd.b); break;
-            case FZ_IR_MUL: o << sval(nd.a) << " * " << sval(nd.b); break;
-            case FZ_IR_DIV: o << sval(nd.a) << " / " << sval(nd.b); break;
-            case FZ_IR_NEG: o << "-" << sval(nd.a); break;
-            default: fail(FZ_E_GRAPH, "internal: unexpected node in the scalar suffix");
-         }
+         if (nd.kind == FZ_IR_DELAY) o << (l >= 0 && is_suffix_line[(size_t)l] ? ss((uint32_t)l, nd.b) : packed_comp_of(nd.a, nd.b, M - 1));
+         else o << arith(nd, [&](uint32_t k) { return sval(operand(nd, k)); });
          o << ";\n";
       }
       o << "      y[0] = " << sval(g.outputs[0]) << ";\n";
@@ -882,12 +895,7 @@ static std::string gen_body_skew(const Graph& g, const StageSplit& sp)
    for (size_t l = 0; l < sp.lines.size(); ++l)
       for (uint32_t i = 0; i < NS; ++i) {
          const uint32_t fr = sp.lines[l].frame;                               // the line lives in the time frame of atom fr: pushed when that atom runs
-         const std::string cur = w(sp.lines[l].srcs, i, fr);
-         for (uint32_t a = sp.lines[l].depth; a >= 1; --a) {
-            const std::string nv = a == 1 ? cur : q(l, i, a - 1);
-            o << "      " << q(l, i, a) << " = (fz_f2){" << act(i, fr) << " ? " << nv << ".x : " << q(l, i, a) << ".x, "
-              << act(i + NS, fr) << " ? " << nv << ".y : " << q(l, i, a) << ".y};\n";
-         }
+         shift_line(o, sp.lines[l].depth, [&](uint32_t a) { return q(l, i, a); }, w(sp.lines[l].srcs, i, fr), act(i, fr), act(i + NS, fr));
       }
    for (uint32_t a = 1; a < M; ++a)                                           // the internal cut wires travel on to the next atom
       for (uint32_t i = 0; i < NS; ++i) {
@@ -898,14 +906,12 @@ static std::string gen_body_skew(const Graph& g, const StageSplit& sp)
    for (uint32_t l : sp.prefix_lines) {
       const Line& L = g.lines[l];
       const std::string cur = g.nodes[L.src].kind == FZ_IR_INPUT ? std::string("x[0]") : "u" + std::to_string(L.src);
-      for (uint32_t a = L.depth; a >= 1; --a)
-         o << "      " << ps(l, a) << " = " << act(0, 0) << " ? " << (a == 1 ? cur : ps(l, a - 1)) << " : " << ps(l, a) << ";\n";
+      shift_line(o, L.depth, [&](uint32_t a) { return ps(l, a); }, cur, act(0, 0));
    }
    for (uint32_t l : sp.suffix_lines) {
       const Line& L = g.lines[l];
       const std::string cur = L.src == sp.cuts[K] ? w(root, NS - 1) + ".y" : "z" + std::to_string(L.src);
-      for (uint32_t a = L.depth; a >= 1; --a)
-         o << "      " << ss(l, a) << " = " << act(K - 1, M - 1) << " ? " << (a == 1 ? cur : ss(l, a - 1)) << " : " << ss(l, a) << ";\n";
+      shift_line(o, L.depth, [&](uint32_t a) { return ss(l, a); }, cur, act(K - 1, M - 1));
    }
    for (uint32_t i = 0; i < NS; ++i)
       o << "      cq" << i << " = (fz_f2){" << act(i, M - 1) << " ? " << w(root, i) << ".x : cq" << i << ".x, " << act(i + NS, M - 1) << " ? "
@@ -943,6 +949,10 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
    return o.str();
 }
 
+// the node kinds the adjoint kernel takes: inputs, coefficients, delayed reads and float arithmetic (INPUT .. NEG), the comparisons
+// and the graph functions (LT .. MAX) -- not the conversions, modulators, |a| < |b| and selections between them
+bool adjoint_takes(uint32_t kind) { return (kind >= FZ_IR_INPUT && kind <= FZ_IR_NEG) || (kind >= FZ_IR_LT && kind <= FZ_IR_MAX); }
+
 // struct fz_adj: fwd() -- the state after one step, from the state before it and the step's frame (the forward step() of gen_body for
 // one stream per lane, outputs left out) -- and bwd() -- the same step re-evaluated, then the adjoint statements in reverse node order.
 // The order of every sum is the one include/flowz_hip.h documents (fz_run_block_grad); tests/adjoint_ref.py restates it.  A node's
@@ -963,30 +973,14 @@ std::string gen_adjoint_body(const Graph& g)
    auto values = [&](const char* indent) {
       for (size_t id = 0; id < g.nodes.size(); ++id) {
          const Node& nd = g.nodes[id];
+         if (!adjoint_takes(nd.kind)) fail(FZ_E_UNSUPPORTED, "internal: a node kind the adjoint kernel does not take");
          o << indent << "const float " << val((uint32_t)id) << " = ";
          switch (nd.kind) {
             case FZ_IR_INPUT: o << "x[" << nd.a << "]"; break;
             case FZ_IR_CONST: o << "c[" << nd.a << "]"; break;
             case FZ_IR_PARAM: o << "p[" << nd.a << "]"; break;
             case FZ_IR_DELAY: o << "s[" << row(nd.a, nd.b) << "]"; break;
-            case FZ_IR_ADD: o << val(nd.a) << " + " << val(nd.b); break;
-            case FZ_IR_SUB: o << val(nd.a) << " - " << val(nd.b); break;
-            case FZ_IR_MUL: o << val(nd.a) << " * " << val(nd.b); break;
-            case FZ_IR_DIV: o << val(nd.a) << " / " << val(nd.b); break;
-            case FZ_IR_NEG: o << "-" << val(nd.a); break;
-            case FZ_IR_LT: o << "(" << val(nd.a) << " < " << val(nd.b) << ") ? 1.f : 0.f"; break;
-            case FZ_IR_LE: o << "(" << val(nd.a) << " <= " << val(nd.b) << ") ? 1.f : 0.f"; break;
-            case FZ_IR_GT: o << "(" << val(nd.a) << " > " << val(nd.b) << ") ? 1.f : 0.f"; break;
-            case FZ_IR_GE: o << "(" << val(nd.a) << " >= " << val(nd.b) << ") ? 1.f : 0.f"; break;
-            case FZ_IR_EQ: o << "(" << val(nd.a) << " == " << val(nd.b) << ") ? 1.f : 0.f"; break;
-            case FZ_IR_NE: o << "(" << val(nd.a) << " != " << val(nd.b) << ") ? 1.f : 0.f"; break;
-            case FZ_IR_ABS: o << "fz_abs(" << val(nd.a) << ")"; break;
-            case FZ_IR_SQRT: o << "fz_sqrt(" << val(nd.a) << ")"; break;
-            case FZ_IR_EXP: o << "fz_exp(" << val(nd.a) << ")"; break;
-            case FZ_IR_TANH: o << "fz_tanh(" << val(nd.a) << ")"; break;
-            case FZ_IR_MIN: o << "fz_min(" << val(nd.a) << ", " << val(nd.b) << ")"; break;
-            case FZ_IR_MAX: o << "fz_max(" << val(nd.a) << ", " << val(nd.b) << ")"; break;
-            default: fail(FZ_E_UNSUPPORTED, "internal: a node kind the adjoint kernel does not take");
+            default: o << op_expr(nd.kind, false, [&](uint32_t k, bool) { return val(operand(nd, k)); });
          }
          o << ";\n";
       }

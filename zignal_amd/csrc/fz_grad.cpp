@@ -27,14 +27,8 @@ std::string grad_unsupported_reason(const Graph& g)
    if (g.n_lds_slots || g.max_delay > kRegMaxDepth) return "delay lines deeper than 8 samples are not supported by the backward";
    for (const Node& nd : g.nodes) {
       if (nd.f64) return "float64 nodes (a C++ double literal, fz_literal_f64) are not supported by the backward";
-      switch (nd.kind) {
-         case FZ_IR_INPUT: case FZ_IR_CONST: case FZ_IR_PARAM: case FZ_IR_DELAY: case FZ_IR_ADD: case FZ_IR_SUB: case FZ_IR_MUL:
-         case FZ_IR_DIV: case FZ_IR_NEG: case FZ_IR_LT: case FZ_IR_LE: case FZ_IR_GT: case FZ_IR_GE: case FZ_IR_EQ: case FZ_IR_NE:
-         case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH: case FZ_IR_MIN: case FZ_IR_MAX:
-            break;
-         case FZ_IR_MOD: return "sample-rate modulators (fz_modulator) are not supported by the backward";
-         default: return "IR node kind " + std::to_string(nd.kind) + " (complex arithmetic) is not supported by the backward";
-      }
+      if (nd.kind == FZ_IR_MOD) return "sample-rate modulators (fz_modulator) are not supported by the backward";
+      if (!adjoint_takes(nd.kind)) return "IR node kind " + std::to_string(nd.kind) + " (complex arithmetic) is not supported by the backward";
    }
    return "";
 }

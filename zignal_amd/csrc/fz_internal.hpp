@@ -149,6 +149,8 @@ struct Graph {
 // force_atoms: cut every segment into atoms even when the chain has three or more packed pairs (a wave that carries ONE pair needs them)
 StageSplit find_stage_split(const Graph& g, bool plain = false, uint32_t divisor = 0, uint32_t max_atoms = 13, bool force_atoms = false);
 std::vector<Graph> find_wave_roles(const Graph& g, uint32_t W);   // fz_split.cpp; {} or W graphs
+// the operation kinds stage packing takes (ADD, SUB, MUL, DIV, NEG: a packed float pair has an instruction for each): fz_split.cpp
+bool is_arith(uint32_t kind);
 // number of waves per stream tuple a variant asks for (flags bits 10..11: 1024 -> 2, 2048 -> 3, 3072 -> 4), 0 = no wave split
 inline uint32_t wave_split_of(uint32_t flags) { const uint32_t b = (flags >> 10) & 3u; return b ? b + 1 : 0; }
 // FZ_VF_IO_WAVE: one more wave per tuple does the frame I/O.  Parts of the graph a tuple's compute waves evaluate (0: the ordinary
@@ -225,6 +227,8 @@ std::string full_source(const Graph& g, const Variant& v);
 // the adjoint kernel (a Variant with FZ_VF_ADJOINT): gen_config / gen_body / skeleton_source hand over to these for it
 std::string gen_adjoint_config(const Graph& g, const Variant& v);
 std::string gen_adjoint_body(const Graph& g);
+// the node kinds gen_adjoint_body writes (fz_codegen.cpp); grad_unsupported_reason refuses a graph with any other
+bool adjoint_takes(uint32_t kind);
 // why the backward of a block does not support this graph ("" = it does): fz_grad.cpp
 std::string grad_unsupported_reason(const Graph& g);
 // the library's default checkpoint stride for the adjoint kernel of this graph (a power of two)

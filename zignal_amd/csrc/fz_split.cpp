@@ -23,9 +23,9 @@
 
 namespace fz {
 
-namespace {
-
 bool is_arith(uint32_t k) { return k == FZ_IR_ADD || k == FZ_IR_SUB || k == FZ_IR_MUL || k == FZ_IR_DIV || k == FZ_IR_NEG; }
+
+namespace {
 
 using Tuple = std::vector<uint32_t>;
 
