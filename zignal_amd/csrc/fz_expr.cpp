@@ -182,7 +182,7 @@ uint32_t feedback_promise_inputs(const fz_expr* fb)
    return 0;                                                // (no cut: a delay-free loop, rejected by the lowering)
 }
 
-// ---- recipes: an expression as text (kernel manifests, fz_kernel_cache.cpp) --------------------------------------------------
+// ---- recipes: an expression as text (kernel manifests, fz_manifest.cpp) --------------------------------------------------
 // One line per node of the DAG in dependency order, shared sub-expressions once: "<kind letter> <fields>"; operands are line numbers.
 // Floating-point values travel as bit patterns.
 static uint32_t bits32(float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; }

@@ -330,9 +330,9 @@ struct LaunchPlan {
 LaunchPlan plan_launch(fz_program* p, const fz_variant* uv, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams, uint32_t rows_total = 0,
                        bool settle = true, bool with_remainder = true);
 // builds (or fetches from the caches) the kernel of variant v; fn_out != null: also load it on the
-// current device and return its hipFunction_t
-std::shared_ptr<Kernel> get_kernel(fz_program* p, const Variant& v, void** fn_out);
-// the variant that runs: `v` with its unroll lowered until the kernel keeps its values in registers (no scratch memory)
+// current device and return its hipFunction_t; build_in_own_process: a missing kernel is compiled by a process of its own (fz_rtc.cpp)
+std::shared_ptr<Kernel> get_kernel(fz_program* p, const Variant& v, void** fn_out, bool build_in_own_process = false);
+// the variant that runs: `v` with its unroll lowered until the kernel keeps its values in registers (no scratch memory): fz_plan.cpp
 Variant settle_variant(fz_program* p, Variant v);
 int launch(fz_program* p, const float* in, float* out, float* state, const float* params,
            uint64_t n_streams, uint32_t n_samples, const fz_variant* v, void* stream, uint32_t tile_streams = 0,
@@ -359,5 +359,5 @@ struct NoJitScope {
 // is the kernel's code object at hand (in memory or in the on-disk cache), i.e. can it run without a hiprtc build?
 bool kernel_at_hand(fz_program* p, const Variant& v);
 std::string kernel_code_id(fz_program* p, const Variant& v);
-int manifest_build(const std::string& path, unsigned n_workers, uint32_t counts[4]);
+int manifest_build(const std::string& path, unsigned n_workers, uint32_t counts[4]);   // fz_manifest.cpp
 }  // namespace fz

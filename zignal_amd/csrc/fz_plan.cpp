@@ -1,6 +1,7 @@
 // Which kernel variant runs: the library's static choice (plan_launch: resolve_variant, finalize_variant).  Measured plans, their
 // persistence per board and the measurement itself: fz_tune.cpp.
 #include <algorithm>
+#include <cstdlib>
 
 #include "fz_runtime.hpp"
 
@@ -455,6 +456,43 @@ static Variant fit_variant(fz_program* p, const fz_variant* uv, Variant v, uint6
        n_streams % (64u * v.P) == 0 && (!tile_streams || tile_streams % (64u * v.P) == 0))
       v.flags |= group == 2 ? FZ_VF_LANE_PAIRS : FZ_VF_LANE_SINGLES;
    return settle ? settle_variant(p, v) : v;
+}
+
+// A frame kernel that spills keeps part of its prefetch buffers / delay lines in scratch memory.  There the unroll is only
+// the prefetch depth, so it is an UPPER bound: halved until nothing spills.  A graph that spills even at unroll 1 runs as it
+// is.  Stream-major kernels are left alone: their unroll is also the length of a stream's run in memory, and the 4-wire sum
+// measured 0.98 ms with 32-sample chunks and 64 spilled registers against 1.33 ms with 16-sample chunks and none.
+Variant settle_variant(fz_program* p, Variant v)
+{
+   static const bool off = std::getenv("FLOWZ_HIP_KEEP_SPILLS") != nullptr;   // (developer switch: measure the spilling kernel itself)
+   if (off) return v;
+   for (;;) {
+      const auto k = get_kernel(p, v, nullptr);
+      if (k->res.scratch_bytes == 0) return v;
+      if (v.flags & FZ_VF_STREAM_MAJOR) {
+         // the long-run body with 64-sample phases shares a SIMD between two waves (256 registers each): where that spills (the
+         // ROCm 7.0 compiler: 60 bytes for the 6-biquad cascade) the 128-sample phases of a lone wave (512 registers) run instead
+         if ((v.flags & FZ_VF_SM_LONG) && v.U == 64 && v.P == 1) {
+            v.U = 128;
+            continue;
+         }
+         // (the pair long-run body keeps 256 staging registers next to the graph's: a graph that does not fit runs the one-stream body)
+         if ((v.flags & FZ_VF_SM_LONG) && v.P == 2) {
+            v.P = 1;
+            v.U = 128;
+            // (with the stage packing the one-stream body would have had by itself)
+            if (sm_long_stage_packs(p->g)) v.flags |= FZ_VF_STAGE_PACK;
+            continue;
+         }
+         return v;
+      }
+      if (ws_parts(v.flags) && v.block * ws_waves(v.flags) > 256 && v.block > 64) {
+         v.block /= 2;                                   // more than four waves per workgroup cap the registers of a lane at 256: fewer tuples per workgroup first
+         continue;
+      }
+      if (v.U <= (ws_parts(v.flags) ? 8u : 1u)) return v;
+      v.U /= 2;
+   }
 }
 
 // The library's own lockstep choice needs its kernel in the 128 registers of a 1024-lane workgroup with the rows in flight it was chosen
