@@ -157,3 +157,21 @@ def make_cmp(seed, max_in=3, depth=3, p=0.35):
     """as make(), with C++ comparison and logical operators among the arithmetic (round 6: proto::_default applies whatever operator a node is)"""
     g, n_in, n_out = make(seed, max_in, depth)
     return _gate(np.random.default_rng(seed + 55000), g, p), n_in, n_out
+
+
+DEEP_DELAYS = tuple(range(9, 41)) + tuple(range(60, 71)) + tuple(range(250, 261)) + tuple(range(300, 401))
+
+
+def _deepen(rng, e, p):
+    if not isinstance(e, tuple):
+        return e
+    if e[0] == "del":
+        return ("del", e[1], int(rng.choice(DEEP_DELAYS))) if rng.random() < p else e
+    return tuple(_deepen(rng, c, p) if isinstance(c, tuple) else c for c in e)
+
+
+def make_deep(seed, max_in=3, depth=3, p=0.3):
+    """as make(), with a share p of the delays re-drawn from beyond the registers: LDS rings (9..40, 60..70, 250..256) and HBM rings
+    (257..260, 300..400).  Its own random stream: the graphs of make() stay what they were"""
+    g, n_in, n_out = make(seed, max_in, depth)
+    return _deepen(np.random.default_rng(seed + 31000), g, p), n_in, n_out

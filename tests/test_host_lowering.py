@@ -1053,3 +1053,19 @@ def test_typed_frames_take_lane_pairs(tmp_path, monkeypatch):
     # per step: the lane's two pairs as two 8-byte loads (4 bytes per stream in) and two 16-byte stores (8 bytes per stream out), nothing narrower
     assert h["buffer_load_dwordx2"] == h["buffer_store_dwordx4"] == 32 and "buffer_store_dwordx2" not in h and "buffer_store_dword" not in h, h
     assert " nt sc1" in [ln for ln in dis.splitlines() if "buffer_store_dwordx4" in ln][0]                              # written through, like every whole-sector frame store
+
+
+def test_a_wheel_imported_after_the_library_does_not_lend_it_its_compiler(tmp_path):
+    """The library imported first, PyTorch (which bundles an older comgr) after it, the first kernel built after that: hiprtc would load the
+    compiler that is already in the process.  The library notices the foreign comgr and builds in the compiler worker -- the same kernel as
+    a process without torch settles on (with the wheel's compiler the pair long-run body of the oscillator chain spills and steps down) --
+    and loads nothing into the host process: the only comgr mapped afterwards is still the wheel's, so the wheel's libraries keep theirs."""
+    import subprocess
+    import sys
+    code = ("from zignal_amd import flowz as F\nimport torch, os\nfrom zignal_amd import workloads as W\n"
+            "print(F.compile(F.from_sexpr(W.osc_chain(6))).kernel_name(F.make_variant(0, 0, 0, F.C.FZ_VF_STREAM_MAJOR), 1 << 20, 4096))\n"
+            "print(sorted({os.path.realpath(l.split()[-1]) for l in open('/proc/self/maps') if 'libamd_comgr' in l}))\n")
+    out = subprocess.check_output([sys.executable, "-c", code], env=dict(os.environ, FLOWZ_HIP_CACHE=str(tmp_path)), cwd=ROOT, text=True).splitlines()
+    assert out[-2].split()[-1] == "fz_block_kernel_p2u64b64f384", out
+    mapped = eval(out[-1])
+    assert mapped and all("/torch/" in m for m in mapped), mapped

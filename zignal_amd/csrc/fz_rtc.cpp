@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 #include <fcntl.h>
 #include <limits.h>
+#include <link.h>
 #include <spawn.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -163,6 +164,23 @@ static std::string worker_refusal(const std::string& w, const std::string& ours)
    return real_path(its) != ours ? "the worker is bound to " + its : "";
 }
 
+// hiprtc loads the compiler itself (libamd_comgr) at its first build, by soname: a process that is bound to the installation's hiprtc but has
+// loaded ANOTHER comgr by then (the library imported first, a PyTorch wheel -- with the comgr it bundles -- after it, the first kernel built
+// after that) would compile with the wheel's older compiler under the installation's name.  So every in-process build until the first one
+// that found no foreign comgr (from then on hiprtc holds the installation's) asks: is a comgr loaded that is not the installation's?  If so
+// that build goes to the worker, like the builds of a process bound to a foreign hiprtc.  Nothing is loaded on the host process's behalf.
+static bool foreign_comgr_loaded()
+{
+   const std::string ours = real_path(std::string(FZ_ROCM_LIB_DIR) + "/libamd_comgr.so");
+   struct Ctx { const std::string* ours; bool foreign; } ctx{&ours, false};
+   dl_iterate_phdr([](struct dl_phdr_info* i, size_t, void* c) {
+      Ctx& x = *static_cast<Ctx*>(c);
+      if (i->dlpi_name && std::strstr(i->dlpi_name, "libamd_comgr") && real_path(i->dlpi_name) != *x.ours) x.foreign = true;
+      return 0;
+   }, &ctx);
+   return ctx.foreign;
+}
+
 static const Rtc& rtc()
 {
    static const Rtc r = [] {
@@ -253,6 +271,13 @@ std::vector<char> compile_kernel(const Graph& g, const Variant& v, bool in_own_p
    if (!worker.empty()) return jit_compile_in_worker(worker, skel, cfg, body, opts);
    static std::mutex in_process;                          // (hiprtc in one process: one build at a time)
    std::lock_guard<std::mutex> lock(in_process);
+   static bool comgr_is_ours = false;                     // (an in-process build has run with no foreign comgr around: hiprtc holds the installation's)
+   if (!comgr_is_ours && compiler_identity() == preferred_identity()) {
+      if (foreign_comgr_loaded() && ::access(worker_path().c_str(), X_OK) == 0) return jit_compile_in_worker(worker_path(), skel, cfg, body, opts);
+      std::vector<char> code = jit_compile_in_process(skel, cfg, body, opts);
+      comgr_is_ours = !foreign_comgr_loaded();
+      return code;
+   }
    return jit_compile_in_process(skel, cfg, body, opts);
 }
 
