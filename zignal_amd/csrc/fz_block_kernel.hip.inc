@@ -474,6 +474,9 @@ __device__ __forceinline__ void fz_ring_put(fz_f4* a, int e, V v) { a[e] = v; }
 
 // ONE of the three bodies follows, chosen by the library from the variant's flags when it assembles the source (fz_codegen.cpp:
 // skeleton_source): a kernel's text -- and with it the name of its code object in the kernel cache -- holds only the body it runs
-//@body stream_major fz_kernel_stream_major.hip.inc
+//@body sm_common fz_kernel_sm_common.hip.inc
+//@body sm_pair fz_kernel_sm_pair.hip.inc
+//@body sm_long fz_kernel_sm_long.hip.inc
+//@body sm_short fz_kernel_sm_short.hip.inc
 //@body wave_split fz_kernel_wave_split.hip.inc
 //@body frames fz_kernel_frames.hip.inc

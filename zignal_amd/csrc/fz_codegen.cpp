@@ -17,21 +17,26 @@
 
 namespace fz {
 
-// fz_block_kernel.hip.inc and the three kernel bodies, embedded at build time (embed.py)
+// fz_block_kernel.hip.inc and the kernel bodies, embedded at build time (embed.py)
 extern const char* const kSkeletonHead;
-extern const char* const kSkeletonBody_stream_major;
+extern const char* const kSkeletonBody_sm_common;    // what the three stream-major bodies share: in front of each of them
+extern const char* const kSkeletonBody_sm_pair;
+extern const char* const kSkeletonBody_sm_long;
+extern const char* const kSkeletonBody_sm_short;
 extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
 extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a kernel text of its own
 
-// the hand-written text of a variant's kernel: the common head + the ONE body its flags select
-const std::string& skeleton_source(uint32_t flags)
+// the hand-written text of a variant's kernel: the common head + the ONE body its flags (stream-major: and its streams per lane) select
+const std::string& skeleton_source(const Variant& v)
 {
-   static const std::string sm = std::string(kSkeletonHead) + kSkeletonBody_stream_major, ws = std::string(kSkeletonHead) + kSkeletonBody_wave_split,
-                            fr = std::string(kSkeletonHead) + kSkeletonBody_frames;
+   static const std::string head = kSkeletonHead, sm = head + kSkeletonBody_sm_common;
+   static const std::string sm_pair = sm + kSkeletonBody_sm_pair, sm_long = sm + kSkeletonBody_sm_long, sm_short = sm + kSkeletonBody_sm_short,
+                            ws = head + kSkeletonBody_wave_split, fr = head + kSkeletonBody_frames;
    static const std::string adj = kSkeletonAdjoint;
-   if (flags & FZ_VF_ADJOINT) return adj;
-   return (flags & FZ_VF_STREAM_MAJOR) ? sm : ws_parts(flags) ? ws : fr;
+   if (v.flags & FZ_VF_ADJOINT) return adj;
+   if (v.flags & FZ_VF_STREAM_MAJOR) return !(v.flags & FZ_VF_SM_LONG) ? sm_short : v.P == 2 ? sm_pair : sm_long;
+   return ws_parts(v.flags) ? ws : fr;
 }
 
 // one symbol per variant, so that profilers (rocprofv3 --stats) keep the variants apart:
@@ -928,7 +933,7 @@ std::string full_source(const Graph& g, const Variant& v)
    s += "// ==== fz_graph_config.h ====\n" + gen_config(g, v);
    s += "// ==== fz_graph_body.h ====\n" + gen_body(g, v);
    s += "// ==== fz_block_kernel.hip.inc ====\n";
-   s += skeleton_source(v.flags);
+   s += skeleton_source(v);
    return s;
 }
 

@@ -222,7 +222,7 @@ struct RingPlan {
 RingPlan ring_plan(const Graph& g, const Variant& v);
 std::string gen_config(const Graph& g, const Variant& v); // generated "fz_graph_config.h"
 std::string gen_body(const Graph& g, const Variant& v);   // generated "fz_graph_body.h"
-const std::string& skeleton_source(uint32_t flags);      // hand-written kernel text of a variant: the common head + the one body its flags select
+const std::string& skeleton_source(const Variant& v);   // hand-written kernel text of a variant: the common head + the one body it selects
 std::string full_source(const Graph& g, const Variant& v);
 // the adjoint kernel (a Variant with FZ_VF_ADJOINT): gen_config / gen_body / skeleton_source hand over to these for it
 std::string gen_adjoint_config(const Graph& g, const Variant& v);

@@ -267,7 +267,7 @@ std::vector<char> compile_kernel(const Graph& g, const Variant& v, bool in_own_p
    const std::vector<const char*> opts = build_options(g, v);
    std::string worker = rtc().worker;
    if (worker.empty() && in_own_process && compiler_identity() == preferred_identity() && ::access(worker_path().c_str(), X_OK) == 0) worker = worker_path();
-   const std::string& skel = skeleton_source(v.flags);
+   const std::string& skel = skeleton_source(v);
    if (!worker.empty()) return jit_compile_in_worker(worker, skel, cfg, body, opts);
    static std::mutex in_process;                          // (hiprtc in one process: one build at a time)
    std::lock_guard<std::mutex> lock(in_process);
