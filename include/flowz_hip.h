@@ -497,12 +497,23 @@ int fz_program_tune_candidates(fz_program* p, uint64_t n_streams, uint32_t n_sam
  * Scope: fz_compile programs whose lowered graph is float32 throughout (no float64 literal, no complex wire), whose delay lines
  * all live in registers (max_delay <= 8: no LDS or HBM ring) and which read no modulator; node kinds INPUT, CONST, PARAM, DELAY,
  * ADD, SUB, MUL, DIV, NEG, LT .. NE, ABS, SQRT, EXP, TANH, MIN, MAX.  Anything else: FZ_E_UNSUPPORTED, fz_last_error() names why.
- * Time-major frames only: in / out_grad / in_grad as [T][n_streams][wire].
+ * Two frame layouts, one entry point each: fz_run_block_grad takes time-major frames, in / out_grad / in_grad as
+ * [T][n_streams][wire]; fz_run_block_grad_stream_major takes stream-major buffers [n_streams][rows_total][wire] -- the layout of
+ * fz_run_block_stream_major, and of a [batch, time] tensor -- and differentiates the window of rows [row0, row0 + n_samples).
+ * Stream-tiled frames are not taken.  The order of operations above holds for both: the layout moves the frames, it does not
+ * change a bit of any result.  State, parameters, the accumulators and the workspace are [row][n_streams] in both.
  *
  * Pointers as for fz_run_block: device pointers, 16-byte aligned, asynchronous on hip_stream (hipStream_t, NULL = default).
  * Output buffers must not overlap the inputs, the workspace or each other, except state0_grad == state_grad.  The uniform
  * coefficients are the program's current constants, as for a forward launch.  n_streams == 0 or n_samples == 0: FZ_OK, nothing
  * is touched.
+ *
+ * fz_run_block_grad_stream_major: the same fz_grad_args; in / out_grad / in_grad are buffers of rows_total rows per stream (their
+ * extents, n_streams * rows_total * wires floats, are what the overlap rule looks at), the workspace is what
+ * fz_program_grad_workspace answers for (n_streams, n_samples, checkpoint_rows).  row0 + n_samples <= rows_total; rows_total * n_in,
+ * row0 * n_in, rows_total * n_out and row0 * n_out are multiples of 4 floats (the rule of fz_run_block_stream_major; n_samples is
+ * free): FZ_E_INVALID otherwise.  Rows of in_grad outside the window are not written, so consecutive windows fill one buffer; they
+ * chain through state0_grad and the accumulators like consecutive blocks.
  * ---------------------------------------------------------------------------------------- */
 typedef struct fz_grad_args {
    uint32_t struct_size;         /* sizeof(fz_grad_args); a smaller or unknown size is FZ_E_INVALID        */
@@ -528,6 +539,17 @@ int fz_program_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel
 /* its symbol, fz_adjoint_kernel_c<C>b<lanes per workgroup>_g<graph tag>; returns the length, writes <= cap bytes */
 long fz_program_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
 int fz_run_block_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
+int fz_run_block_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                   uint32_t n_samples, void* hip_stream);
+/* The same inspection per frame layout.  FZ_GRAD_TIME_MAJOR answers what the two functions above answer.  FZ_GRAD_STREAM_MAJOR is
+ * the kernel of fz_run_block_grad_stream_major: its symbol is fz_adjoint_sm_kernel_c<C>r<R>b<lanes per workgroup>_g<graph tag>, R the
+ * rows of the LDS patch its frames move through (a multiple of C and of 4); lds_bytes is the patches of one workgroup.
+ * fz_program_grad_source_for: the kernel's whole source (generated configuration and body, hand-written skeleton), as
+ * fz_program_source gives it for a forward kernel. */
+enum { FZ_GRAD_TIME_MAJOR = 0, FZ_GRAD_STREAM_MAJOR = 1 };
+int fz_program_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out);
+long fz_program_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 
 /* ------------------------------------------------------------------------------------------
  * fz_bank -- device-resident closure state for n_streams streams: the `state_` member of

@@ -7,7 +7,16 @@ checkpoint stride.  HIP events around each launch after warm-up; printed per leg
 adjoint kernel's registers, and its HBM traffic per the formula of DESIGN.md (4 (2 n_in + n_out + n_in) + 8 n_state / C bytes per
 stream-sample, plus the coefficient rows) as a fraction of 8 TB/s.
 
-usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all]
+--layout stream-major: the same table for stream-major buffers [n_streams, T, wire] (run_block_stream_major against
+run_block_grad_stream_major, the stream-major adjoint kernel).
+
+--layout compare: the stream-major backward against the route a caller with stream-major buffers had before it existed, end to end:
+fz_transpose_frames of x and of dL/dy to time-major, fz_run_block_grad, fz_transpose_frames of dL/dx back (every buffer allocated
+beforehand).  Same process, legs interleaved: the time-major backward runs for at least 100 ms first (the boards are power-managed),
+then every leg is timed --steps times in a forward and again in a backward pass over the list.  Printed per line: the median of
+each leg, the yardstick's spread (max - min over its own repeats: the noise), and the ratio to the time-major backward alone.
+
+usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare]
 """
 import argparse
 import datetime
@@ -49,22 +58,91 @@ def timed(fn, warmup, steps, torch):
     return float(np.median(times))
 
 
+def samples(fn, steps, torch):
+    out = []
+    for _ in range(steps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        torch.cuda.synchronize()
+        out.append(t0.elapsed_time(t1))
+    return out
+
+
+def compare(a, torch):
+    """the stream-major backward against transpose + time-major backward + transpose, interleaved in one process"""
+    import time
+    print(f"# stream-major backward vs the transposing route, HIP events, {a.steps} launches per leg and pass, a forward and a backward pass over the legs")
+    print(f"{'graph':20s} {'streams x T':>16s} {'route ms':>9s} {'spread':>7s} {'sm ms':>9s} {'tm ms':>9s} {'sm/route':>9s} {'sm/tm':>6s} {'vgprs':>6s} {'lds':>6s}  stream-major adjoint kernel")
+    shapes = SHAPES["small"] + SHAPES["large"] if a.legs == "all" else SHAPES[a.legs]
+    for ns, T in shapes:
+        x_sm = torch.empty((ns, T, 1), dtype=torch.float32, device="cuda")
+        F.synth_fill(x_sm, seed=W.SEED)
+        gy_sm = torch.empty_like(x_sm)
+        F.synth_fill(gy_sm, seed=W.SEED + 1)
+        gx_sm, gx_back = torch.empty_like(x_sm), torch.empty_like(x_sm)
+        x_tm, gy_tm = (torch.empty((T, ns, 1), dtype=torch.float32, device="cuda") for _ in range(2))
+        for name, fn in GRAPHS.items():
+            prog = F.compile(F.from_sexpr(fn()))
+            pp = params_for(name, prog, ns, torch)
+            s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+
+            def route():
+                F.frames_from_stream_major(x_sm, 0, out=x_tm)
+                F.frames_from_stream_major(gy_sm, 0, out=gy_tm)
+                r = prog.run_block_grad(x_tm, gy_tm, s0, pp, state_grad=s0)
+                F.frames_to_stream_major(r["x"], out=gx_back)
+
+            def sm():
+                prog.run_block_grad_stream_major(x_sm, gy_sm, s0, pp, state_grad=s0, in_grad=gx_sm)
+
+            def tm():
+                prog.run_block_grad(x_tm, gy_tm, s0, pp, state_grad=s0)
+            legs = {"route": route, "sm": sm, "tm": tm}
+            for f in legs.values():                            # JIT, allocator
+                f()
+            torch.cuda.synchronize()
+            t_end = time.time() + 0.1
+            while time.time() < t_end:                          # at least 100 ms of the default before the first timing
+                tm()
+                torch.cuda.synchronize()
+            got = {k: [] for k in legs}
+            for order in (list(legs), list(legs)[::-1]):
+                for k in order:
+                    got[k] += samples(legs[k], a.steps, torch)
+            med = {k: float(np.median(v)) for k, v in got.items()}
+            res = prog.grad_resources(stream_major=True)
+            print(f"{name:20s} {f'{ns} x {T}':>16s} {med['route']:9.3f} {max(got['route']) - min(got['route']):7.3f} {med['sm']:9.3f} {med['tm']:9.3f} "
+                  f"{med['sm'] / med['route']:9.3f} {med['sm'] / med['tm']:6.3f} {res['vgprs'] + res['agprs']:6d} {res['lds_bytes']:6d}  "
+                  f"{prog.grad_kernel_symbol(stream_major=True)}", flush=True)
+            print("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()), flush=True)
+            del pp, s0
+        del x_sm, gy_sm, gx_sm, gx_back, x_tm, gy_tm
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--legs", choices=("small", "large", "all"), default="all")
+    ap.add_argument("--layout", choices=("time-major", "stream-major", "compare"), default="time-major")
     a = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
     props = torch.cuda.get_device_properties(0)
+    if a.layout == "compare":
+        print(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+        return compare(a, torch)
+    sm = a.layout == "stream-major"
     print(f"# backward vs forward of one block, HIP events, median of {a.steps} launches after {a.warmup} warm-up")
     print(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
     print(f"{'graph':20s} {'streams x T':>16s} {'fwd ms':>9s} {'bwd ms':>9s} {'bwd/fwd':>8s} {'C':>3s} {'vgprs':>6s} {'bwd B/s / 8TB/s':>16s}  adjoint kernel")
     shapes = SHAPES["small"] + SHAPES["large"] if a.legs == "all" else SHAPES[a.legs]
     for ns, T in shapes:
-        x = torch.empty((T, ns, 1), dtype=torch.float32, device="cuda")
+        x = torch.empty((ns, T, 1) if sm else (T, ns, 1), dtype=torch.float32, device="cuda")
         F.synth_fill(x, seed=W.SEED)
         gy = torch.empty_like(x)
         F.synth_fill(gy, seed=W.SEED + 1)
@@ -77,16 +155,17 @@ def main():
 
             def fwd():
                 st.copy_(s0)
-                prog.run_block(x, state=st, params=pp, out=y)
+                (prog.run_block_stream_major if sm else prog.run_block)(x, state=st, params=pp, out=y)
             fwd_ms = timed(fwd, a.warmup, a.steps, torch)
             # (the state copy is inside the forward's window: n_state rows, < 1 % of a block's bytes)
-            bwd_ms = timed(lambda: prog.run_block_grad(x, gy, s0, pp, state_grad=s0), a.warmup, a.steps, torch)
-            res = prog.grad_resources()
+            bwd = prog.run_block_grad_stream_major if sm else prog.run_block_grad
+            bwd_ms = timed(lambda: bwd(x, gy, s0, pp, state_grad=s0), a.warmup, a.steps, torch)
+            res = prog.grad_resources(stream_major=sm)
             C = res["unroll"]
             nbytes = 4.0 * ns * T * (2 * prog.n_in + prog.n_out + prog.n_in) + 8.0 * ns * T * prog.n_state / C \
                 + 4.0 * ns * (2 * prog.n_state + prog.n_param * 2 + prog.n_const * 2)
             print(f"{name:20s} {f'{ns} x {T}':>16s} {fwd_ms:9.3f} {bwd_ms:9.3f} {bwd_ms / fwd_ms:8.2f} {C:3d} {res['vgprs'] + res['agprs']:6d} "
-                  f"{nbytes / (bwd_ms / 1e3) / HBM:16.3f}  {prog.grad_kernel_symbol()}", flush=True)
+                  f"{nbytes / (bwd_ms / 1e3) / HBM:16.3f}  {prog.grad_kernel_symbol(stream_major=sm)}", flush=True)
             del pp, s0, st
         del x, gy, y
         torch.cuda.empty_cache()

@@ -158,6 +158,10 @@ def _load():
         "fz_program_grad_resources": (ctypes.c_int, [P, u32, ctypes.POINTER(KernelResources)]),
         "fz_program_grad_kernel_symbol": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_run_block_grad": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, P]),
+        "fz_run_block_grad_stream_major": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, u32, u32, P]),
+        "fz_program_grad_resources_for": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_grad_kernel_symbol_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_grad_source_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_device_count": (ctypes.c_int, []),
         "fz_synth_fill": (ctypes.c_int, [P, u64, u32, u32, u32, u64, u64, u32, P]),
         "fz_rbj_lowpass": (ctypes.c_int, [P, P, f32, u64, P, P, P]),

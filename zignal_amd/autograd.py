@@ -4,6 +4,8 @@ The forward is Program.run_block with the library's default plan (the fast kerne
 generated adjoint kernel (include/flowz_hip.h: fz_run_block_grad).  Differentiable in x, state, params and consts; chaining run()
 over consecutive blocks back-propagates through time across them (the state gradient of block k is the state_out gradient of block
 k-1).  Time-major frames [T, n_streams, n_in] (or [T, n_streams] for one input wire) on the GPU; there is no CPU path.
+run(..., stream_major=True) takes stream-major tensors instead, [n_streams, T, n_in] or [n_streams, T] -- a [batch, time] tensor as it
+lies: the forward is Program.run_block_stream_major, the backward Program.run_block_grad_stream_major, and nothing is transposed.
 """
 from __future__ import annotations
 
@@ -23,11 +25,13 @@ def _apply_consts(prog: Program, consts):
 
 class _Block(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, prog, x, state, params, consts):
+    def forward(ctx, prog, x, state, params, consts, stream_major=False):
         _apply_consts(prog, consts)
         st = state.detach().clone() if state is not None else None    # (the caller's state is never advanced in place)
-        y, st = prog.run_block(x.detach(), st, params.detach() if params is not None else None)
+        fwd = prog.run_block_stream_major if stream_major else prog.run_block
+        y, st = fwd(x.detach(), st, params.detach() if params is not None else None)
         ctx.prog = prog
+        ctx.stream_major = stream_major
         ctx.consts = consts.detach().clone() if consts is not None else None
         ctx.x_shape = x.shape
         ctx.save_for_backward(x, state, params)
@@ -38,18 +42,18 @@ class _Block(torch.autograd.Function):
     def backward(ctx, gy, gs):
         prog = ctx.prog
         x, state, params = ctx.saved_tensors
-        _, need_x, need_s, need_p, need_c = ctx.needs_input_grad
+        _, need_x, need_s, need_p, need_c = ctx.needs_input_grad[:5]
         want = [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
         if not want:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
-        T, ns, _ = xx.shape
         if gy is None:
-            gy = torch.zeros((T, ns, prog.n_out), dtype=torch.float32, device=x.device)
+            gy = torch.zeros(tuple(xx.shape[:2]) + (prog.n_out,), dtype=torch.float32, device=x.device)
         sg = gs.contiguous() if gs is not None and prog.n_state else None
         _apply_consts(prog, ctx.consts)                               # (the constants of the forward launch)
-        r = prog.run_block_grad(xx, gy.contiguous(), state.detach() if state is not None else None,
-                                params.detach() if params is not None else None, state_grad=sg, want=want)
+        bwd = prog.run_block_grad_stream_major if ctx.stream_major else prog.run_block_grad
+        r = bwd(xx, gy.contiguous(), state.detach() if state is not None else None,
+                params.detach() if params is not None else None, state_grad=sg, want=want)
         gx = r["x"].reshape(ctx.x_shape) if need_x else None
         gst = r["state"] if need_s else None
         gp = r["params"] if need_p else None
@@ -57,11 +61,12 @@ class _Block(torch.autograd.Function):
         if need_c:
             # per-stream coefficient adjoints, summed over the streams in float64
             gc = r["consts"][:prog.n_const].double().sum(1).to(ctx.consts.dtype).to(ctx.consts.device)
-        return None, gx, gst, gp, gc
+        return None, gx, gst, gp, gc, None
 
 
-def run(prog: Program, x, state=None, params=None, consts=None):
+def run(prog: Program, x, state=None, params=None, consts=None, stream_major=False):
     """One block through autograd: returns (y [T, n_streams, n_out], state after the block [n_state, n_streams]).
+    stream_major: x is [n_streams, T, n_in] (or [n_streams, T] for one input wire) and y comes back as [n_streams, T, n_out].
     state: the state before the block (None: zeros; never modified), params: [n_param, n_streams] per-stream coefficients,
     consts: an optional CPU float32 tensor [n_const] of uniform coefficient slots (Program.consts() order), applied with
     set_const before the forward launch and again before the backward one (None: the program's current values, constant)."""
@@ -69,11 +74,11 @@ def run(prog: Program, x, state=None, params=None, consts=None):
         raise FlowzError(C.FZ_E_UNSUPPORTED, prog.grad_unsupported_reason())
     if x.dim() == 2:
         if prog.n_in != 1:
-            raise FlowzError(C.FZ_E_INVALID, f"x: [T, n_streams] frames are for one input wire, the graph has {prog.n_in}")
-    ns = x.shape[1]
+            raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
+    ns = x.shape[0 if stream_major else 1]
     if state is None:
         state = torch.zeros((max(prog.n_state, 1), ns), dtype=torch.float32, device=x.device)
     if consts is not None:
         if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
             raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    return _Block.apply(prog, x, state, params, consts)
+    return _Block.apply(prog, x, state, params, consts, bool(stream_major))

@@ -26,6 +26,7 @@ extern const char* const kSkeletonBody_sm_short;
 extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
 extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a kernel text of its own
+extern const char* const kSkeletonAdjointSm; // fz_kernel_adjoint_sm.hip.inc: the same for stream-major buffers
 
 // the hand-written text of a variant's kernel: the common head + the ONE body its flags (stream-major: and its streams per lane) select
 const std::string& skeleton_source(const Variant& v)
@@ -33,8 +34,8 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string head = kSkeletonHead, sm = head + kSkeletonBody_sm_common;
    static const std::string sm_pair = sm + kSkeletonBody_sm_pair, sm_long = sm + kSkeletonBody_sm_long, sm_short = sm + kSkeletonBody_sm_short,
                             ws = head + kSkeletonBody_wave_split, fr = head + kSkeletonBody_frames;
-   static const std::string adj = kSkeletonAdjoint;
-   if (v.flags & FZ_VF_ADJOINT) return adj;
+   static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm;
+   if (v.flags & FZ_VF_ADJOINT) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_sm : adj;
    if (v.flags & FZ_VF_STREAM_MAJOR) return !(v.flags & FZ_VF_SM_LONG) ? sm_short : v.P == 2 ? sm_pair : sm_long;
    return ws_parts(v.flags) ? ws : fr;
 }
@@ -43,6 +44,8 @@ const std::string& skeleton_source(const Variant& v)
 // fz_block_kernel_p<streams/lane>u<unroll>b<block>[s<segments>]f<flags>
 std::string kernel_name(const Graph& g, const Variant& v)
 {
+   if (v.flags & FZ_VF_ADJOINT_SM)
+      return "fz_adjoint_sm_kernel_c" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block);
    if (v.flags & FZ_VF_ADJOINT) return "fz_adjoint_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
    std::string n = "fz_block_kernel_p" + std::to_string(v.P) + "u" + std::to_string(v.U) + "b" + std::to_string(v.block);
    if ((v.flags & FZ_VF_STAGE_PACK) && g.split.ok) n += "s" + std::to_string(g.split.K) + (g.split.m > 1 ? "a" + std::to_string(g.split.m) : "");
@@ -949,6 +952,7 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
    o << "#define FZ_NPARAM " << g.n_param << "\n";
    o << "#define FZ_NSTATE " << g.n_state << "\n";
    o << "#define FZ_C " << v.U << "   // checkpoint rows: the chunk sweep 2 re-runs and walks backwards\n";
+   if (v.flags & FZ_VF_ADJOINT_SM) o << "#define FZ_R " << v.P << "   // rows per LDS patch of the stream-major frames\n";
    o << "#define FZ_BLOCK " << v.block << "\n";
    o << "#define FZ_KERNEL " << kernel_symbol(g, v) << "\n";
    return o.str();

@@ -1,6 +1,7 @@
-// The backward of a block (include/flowz_hip.h: fz_run_block_grad): what the adjoint kernel supports, its checkpoint stride and
-// workspace, argument checks and the launch.  The kernel text is fz_kernel_adjoint.hip.inc plus gen_adjoint_body (fz_codegen.cpp);
-// its code objects go through the kernel cache as a Variant with FZ_VF_ADJOINT.
+// The backward of a block (include/flowz_hip.h: fz_run_block_grad, fz_run_block_grad_stream_major): what the adjoint kernels support,
+// their checkpoint stride, patch length and workspace, argument checks and the launch.  The kernel text is fz_kernel_adjoint.hip.inc
+// (time-major frames) or fz_kernel_adjoint_sm.hip.inc (stream-major buffers) plus gen_adjoint_body (fz_codegen.cpp); the code objects
+// go through the kernel cache as a Variant with FZ_VF_ADJOINT (and FZ_VF_ADJOINT_SM).
 #include <algorithm>
 #include <cstring>
 #include <utility>
@@ -43,6 +44,22 @@ uint32_t grad_default_checkpoint(const Graph& g)
    return C;
 }
 
+// The stream-major adjoint kernel moves its frames through a wave-private LDS patch of R rows (fz_kernel_adjoint_sm.hip.inc): a patch
+// row is R * (n_in + n_out) + 4 floats, a workgroup holds 4 x 64 of them.  R is a power of two >= 4: long enough that the run of ONE
+// stream is a whole 128-byte cache line in the WIDER of the two frames, then doubled towards a line in the narrower one while the
+// workgroup's patches stay within half a CU's 160 KB of LDS (two workgroups per CU); and at least C -- so a multiple of C (a power of
+// two) and of 4.  A 1-in / 1-out graph: R = 32, 17 KB per wave, 68 KB per workgroup.
+constexpr uint32_t kLdsBytes = 160u * 1024u;   // per CU and the most one workgroup may declare (gfx950)
+static uint32_t sm_patch_bytes(const Graph& g, uint32_t R) { return (R * (g.n_in + g.n_out) + 4u) * 4u * kGradBlock; }
+uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C)
+{
+   const uint32_t wide = std::max<uint32_t>(std::max(g.n_in, g.n_out), 1), narrow = std::max<uint32_t>(g.n_in && g.n_out ? std::min(g.n_in, g.n_out) : wide, 1);
+   uint32_t R = 4;
+   while (R * wide < 32) R *= 2;
+   while (R * narrow < 32 && sm_patch_bytes(g, 2 * R) <= kLdsBytes / 2) R *= 2;
+   return std::max(R, C);
+}
+
 static uint32_t checkpoint_of(const Graph& g, uint32_t checkpoint_rows)
 {
    if (checkpoint_rows == 0) return grad_default_checkpoint(g);
@@ -57,15 +74,25 @@ static void require_supported(const Graph& g)
    if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
 }
 
-static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows)
+static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool stream_major = false)
 {
    require_supported(g);
    Variant v;
    v.P = 1;
    v.U = checkpoint_of(g, checkpoint_rows);
    v.block = kGradBlock;
-   v.flags = FZ_VF_ADJOINT;
+   v.flags = FZ_VF_ADJOINT | (stream_major ? FZ_VF_ADJOINT_SM : 0u);
+   if (stream_major) v.P = grad_sm_patch_rows(g, v.U);      // (the patch rows travel in P: codegen puts them into FZ_R and the symbol)
+   if (stream_major && sm_patch_bytes(g, v.P) > kLdsBytes)
+      fail(FZ_E_UNSUPPORTED, "stream-major backward: a patch of " + std::to_string(v.U) + " checkpoint rows of " + std::to_string(g.n_in + g.n_out) +
+                                " wires does not fit the LDS of a workgroup: choose smaller checkpoint_rows");
    return v;
+}
+
+static bool layout_is_stream_major(uint32_t layout)
+{
+   if (layout != FZ_GRAD_TIME_MAJOR && layout != FZ_GRAD_STREAM_MAJOR) fail(FZ_E_INVALID, "layout must be FZ_GRAD_TIME_MAJOR or FZ_GRAD_STREAM_MAJOR");
+   return layout == FZ_GRAD_STREAM_MAJOR;
 }
 
 static uint64_t workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t n_samples, uint32_t C)
@@ -92,16 +119,39 @@ struct AdjArgsHeader {
 };
 static_assert(sizeof(AdjArgsHeader) == 10 * 8 + 8 + 2 * 4, "AdjArgsHeader must match the head of the kernel's fz_adj_args without padding");
 
-static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* stream)
+// kernarg image of `struct fz_adj_sm_args` (fz_kernel_adjoint_sm.hip.inc) up to the coefficient tail
+struct AdjSmArgsHeader {
+   AdjArgsHeader tm;
+   unsigned int rows_total;
+   unsigned int row0;
+};
+static_assert(sizeof(AdjSmArgsHeader) == sizeof(AdjArgsHeader) + 2 * 4, "AdjSmArgsHeader must match the head of the kernel's fz_adj_sm_args without padding");
+
+// the window of a stream-major launch: rows [row0, row0 + n_samples) of buffers [n_streams][rows_total][wire]; null: time-major frames
+struct SmWindow {
+   uint32_t rows_total, row0;
+};
+
+static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm = nullptr)
 {
    if (!p) fail(FZ_E_INVALID, "null program");
    if (!a) fail(FZ_E_INVALID, "fz_run_block_grad: null arguments");
    if (a->struct_size != sizeof(fz_grad_args))
       fail(FZ_E_INVALID, "fz_grad_args.struct_size is " + std::to_string(a->struct_size) + ", this library knows " + std::to_string(sizeof(fz_grad_args)));
    const Graph& g = p->g;
-   const Variant v = adjoint_variant(g, a->checkpoint_rows);
+   const Variant v = adjoint_variant(g, a->checkpoint_rows, sm != nullptr);
    if (n_streams == 0 || n_samples == 0) return FZ_OK;     // an empty block: nothing to differentiate, nothing touched
    if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
+   if (sm) {
+      if ((uint64_t)sm->row0 + n_samples > sm->rows_total)
+         fail(FZ_E_INVALID, "the window [row0, row0 + n_samples) = [" + std::to_string(sm->row0) + ", " + std::to_string((uint64_t)sm->row0 + n_samples) +
+                               ") reaches beyond rows_total = " + std::to_string(sm->rows_total));
+      // (the forward stream-major rule: every stream's buffer and the window's first row on the 16-byte grid of the float4 pieces)
+      if (((uint64_t)sm->rows_total * g.n_in) % 4 || ((uint64_t)sm->rows_total * g.n_out) % 4)
+         fail(FZ_E_INVALID, "stream-major buffers: rows_total * n_in and rows_total * n_out must be multiples of 4 floats");
+      if (((uint64_t)sm->row0 * g.n_in) % 4 || ((uint64_t)sm->row0 * g.n_out) % 4)
+         fail(FZ_E_INVALID, "stream-major buffers: row0 * n_in and row0 * n_out must be multiples of 4 floats");
+   }
    if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams");
    if (g.n_in && !a->in) fail(FZ_E_INVALID, "in is null but the graph has input wires");
    if (g.n_state && !a->state) fail(FZ_E_INVALID, "state is null but the graph has delay lines");
@@ -111,7 +161,8 @@ static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, ui
    if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: fz_program_grad_workspace says " + std::to_string(need) + " bytes");
    if (need && a->workspace_bytes < need)
       fail(FZ_E_INVALID, "workspace_bytes " + std::to_string(a->workspace_bytes) + " is less than the " + std::to_string(need) + " bytes fz_program_grad_workspace asks for");
-   const uint64_t fr = (uint64_t)n_samples * n_streams * 4u, row = n_streams * 4u;
+   // (bytes of one wire's frames: a stream-major buffer is touched over its whole extent, n_streams * rows_total rows)
+   const uint64_t fr = (uint64_t)(sm ? sm->rows_total : n_samples) * n_streams * 4u, row = n_streams * 4u;
    struct Buf {
       const void* ptr;
       uint64_t bytes;
@@ -140,21 +191,45 @@ static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, ui
    void* fn = nullptr;
    (void)get_kernel(p, v, &fn);
    // (the size of the kernel's argument struct: 8-byte aligned -- a buffer of another size does not launch that struct)
-   const size_t kbytes = (sizeof(AdjArgsHeader) + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
+   const size_t hbytes = sm ? sizeof(AdjSmArgsHeader) : sizeof(AdjArgsHeader);
+   const size_t kbytes = (hbytes + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
    std::vector<char> kbuf(kbytes, 0);
    const AdjArgsHeader h{a->in,      a->state,       a->params,     a->out_grad, a->state_grad, a->in_grad,
                          a->state0_grad, a->param_grad, a->const_grad, static_cast<float*>(a->workspace), (unsigned long long)n_streams, n_samples,
                          (unsigned int)((n_samples + (uint64_t)v.U - 1) / v.U)};
-   std::memcpy(kbuf.data(), &h, sizeof h);
+   if (sm) {
+      const AdjSmArgsHeader hs{h, sm->rows_total, sm->row0};
+      std::memcpy(kbuf.data(), &hs, sizeof hs);
+   } else
+      std::memcpy(kbuf.data(), &h, sizeof h);
    {
       std::lock_guard<std::mutex> lock(p->mu);
-      if (!g.consts.empty()) std::memcpy(kbuf.data() + sizeof h, g.consts.data(), sizeof(float) * g.consts.size());
+      if (!g.consts.empty()) std::memcpy(kbuf.data() + hbytes, g.consts.data(), sizeof(float) * g.consts.size());
    }
    size_t size = kbytes;
    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
    const unsigned grid = (unsigned)((n_streams + v.block - 1) / v.block);
    FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
    return FZ_OK;
+}
+
+// a string result of the inspection calls: the length, at most cap bytes written; an error code (negative) on failure
+template <class Fn>
+static long grad_string(fz_program* p, char* buf, size_t cap, Fn make)
+{
+   try {
+      if (!p) fail(FZ_E_INVALID, "null program");
+      const std::string s = make();
+      if (buf && cap) {
+         const size_t n = std::min(cap - 1, s.size());
+         std::memcpy(buf, s.data(), n);
+         buf[n] = 0;
+      }
+      return (long)s.size();
+   } catch (const fz::Error& er) {
+      set_error(er.msg);
+      return er.code;
+   }
 }
 
 }  // namespace fz
@@ -182,9 +257,14 @@ int fz_program_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t 
 
 int fz_program_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
 {
+   return fz_program_grad_resources_for(p, checkpoint_rows, FZ_GRAD_TIME_MAJOR, out);
+}
+
+int fz_program_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
+{
    FZ_GUARD(
       if (!p || !out) fail(FZ_E_INVALID, "fz_program_grad_resources: bad arguments");
-      const Variant v = adjoint_variant(p->g, checkpoint_rows);
+      const Variant v = adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout));
       const auto k = get_kernel(p, v, nullptr);
       *out = fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills,
                                  k->res.sgpr_spills, v.U};
@@ -193,24 +273,30 @@ int fz_program_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel
 
 long fz_program_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
 {
-   try {
-      if (!p) fail(FZ_E_INVALID, "null program");
-      const std::string s = kernel_symbol(p->g, adjoint_variant(p->g, checkpoint_rows));
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
+   return fz_program_grad_kernel_symbol_for(p, checkpoint_rows, FZ_GRAD_TIME_MAJOR, buf, cap);
+}
+
+long fz_program_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout))); });
+}
+
+long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout))); });
 }
 
 int fz_run_block_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
    FZ_GUARD(return run_grad(p, a, n_streams, n_samples, hip_stream);)
+}
+
+int fz_run_block_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
+                                   void* hip_stream)
+{
+   FZ_GUARD(
+      const SmWindow w{rows_total, row0};
+      return run_grad(p, a, n_streams, n_samples, hip_stream, &w);)
 }
 
 }  // extern "C"

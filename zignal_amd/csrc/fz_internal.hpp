@@ -181,6 +181,10 @@ constexpr uint32_t FZ_VF_LANE_SINGLES = 1u << 31;
 // it.  Such a Variant is {P = 1, U = checkpoint rows, block = lanes per workgroup, flags = FZ_VF_ADJOINT}; it shares the kernel cache
 // with the forward kernels (its own source is its key) and none of the forward planner's paths ever sees it.
 constexpr uint32_t FZ_VF_ADJOINT = 1u << 27;
+// internal, with FZ_VF_ADJOINT: the adjoint kernel for STREAM-MAJOR buffers (fz_kernel_adjoint_sm.hip.inc), a text and a symbol of its
+// own; one of the reserved bits, so no caller's variant names it either.  Such a Variant carries the rows of its LDS patch in P
+// (fz_grad.cpp: grad_sm_patch_rows is their one home; the kernel itself runs one stream per lane).
+constexpr uint32_t FZ_VF_ADJOINT_SM = 1u << 18;
 constexpr uint32_t kChipCUs = 256;       // MI355X (gfx950): 8 XCDs x 32 CUs -- what chip_cus() answers on a box without a GPU
 unsigned chip_cus();                     // compute units of the current device (fz_launch.cpp)
 
@@ -233,6 +237,8 @@ bool adjoint_takes(uint32_t kind);
 std::string grad_unsupported_reason(const Graph& g);
 // the library's default checkpoint stride for the adjoint kernel of this graph (a power of two)
 uint32_t grad_default_checkpoint(const Graph& g);
+// rows per LDS patch of the stream-major adjoint kernel at checkpoint stride C: a multiple of C and of 4 (fz_grad.cpp)
+uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C);
 
 // ---- runtime ---------------------------------------------------------------------------------------------
 // what the code object's metadata says the kernel needs (AMDGPU msgpack notes)

@@ -617,24 +617,46 @@ class Program:
         C.check(C.lib.fz_program_grad_workspace(self._h, int(n_streams), int(T), int(checkpoint_rows), ctypes.byref(b)))
         return int(b.value)
 
-    def grad_resources(self, checkpoint_rows: int = 0) -> dict:
-        """registers / scratch bytes of the adjoint kernel (JITs it; needs no GPU); 'unroll' = the checkpoint stride it uses"""
+    def grad_resources(self, checkpoint_rows: int = 0, stream_major: bool = False) -> dict:
+        """registers / scratch / LDS bytes of the adjoint kernel (JITs it; needs no GPU); 'unroll' = the checkpoint stride it uses.
+        stream_major: the kernel of run_block_grad_stream_major"""
         r = C.KernelResources()
-        C.check(C.lib.fz_program_grad_resources(self._h, int(checkpoint_rows), ctypes.byref(r)))
+        C.check(C.lib.fz_program_grad_resources_for(self._h, int(checkpoint_rows), int(bool(stream_major)), ctypes.byref(r)))
         return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
 
-    def grad_kernel_symbol(self, checkpoint_rows: int = 0) -> str:
+    def grad_kernel_symbol(self, checkpoint_rows: int = 0, stream_major: bool = False) -> str:
         buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_grad_kernel_symbol(self._h, int(checkpoint_rows), buf, 160))
+        C.check(C.lib.fz_program_grad_kernel_symbol_for(self._h, int(checkpoint_rows), int(bool(stream_major)), buf, 160))
+        return buf.value.decode()
+
+    def grad_source(self, checkpoint_rows: int = 0, stream_major: bool = False) -> str:
+        """the adjoint kernel's whole source: generated configuration and body, then the hand-written skeleton"""
+        n = C.check(C.lib.fz_program_grad_source_for(self._h, int(checkpoint_rows), int(bool(stream_major)), None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        C.check(C.lib.fz_program_grad_source_for(self._h, int(checkpoint_rows), int(bool(stream_major)), buf, n + 1))
         return buf.value.decode()
 
     def run_block_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0):
-        """Reverse-mode gradients of the block run_block(x, state, params) computes (time-major frames only): out_grad = dL/dy
+        """Reverse-mode gradients of the block run_block(x, state, params) computes (time-major frames; run_block_grad_stream_major takes [n_streams, rows, wire]): out_grad = dL/dy
         [T, n_streams, n_out], state_grad = dL/d(state after the block) [n_state, n_streams] (None: zero).  state = the state BEFORE
         the block (None: zeros; read only).  want: which of "x" (dL/dx, like x), "state" (dL/d(state before), [n_state, n_streams]),
         "params" ([n_param, n_streams]) and "consts" ([n_const, n_streams]: per stream, not summed) to compute.  accum: optional dict
         with "params" / "consts" tensors the gradients are ADDED to (returned as those entries); otherwise they start from zero.
         The uniform coefficients are the program's current constants.  Launches on torch's current stream; returns a dict."""
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None)
+
+    def run_block_grad_stream_major(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None,
+                                    checkpoint_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None, in_grad=None):
+        """run_block_grad on stream-major buffers, the layout of run_block_stream_major: x [n_streams, rows, n_in] (or [n_streams, rows]
+        for one input wire), out_grad [n_streams, rows, n_out]; the block is rows [row0, row0 + n_samples) (n_samples None: to the last
+        row).  No layout pass (fz_run_block_grad_stream_major), and not a bit differs from run_block_grad on the transposed frames.
+        Returns the same dict, "x" laid out like x: only the rows of the window are written.  in_grad: the tensor to write them to
+        (returned as "x"), so that consecutive windows fill one tensor; otherwise a new one, zero outside the window."""
+        n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad))
+
+    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window):
+        """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers"""
         import torch
 
         _require(self.grad_supported(), self.grad_unsupported_reason())
@@ -643,12 +665,20 @@ class Program:
         if x.dim() == 2 and self.n_in == 1:
             x = x.unsqueeze(-1)
         _check_frames(x, self.n_in)
-        _require(x.dim() == 3, "run_block_grad takes time-major frames [T, n_streams, n_in]")
-        T, ns, _ = x.shape
+        if window is None:
+            _require(x.dim() == 3, "run_block_grad takes time-major frames [T, n_streams, n_in]")
+            T, ns, _ = x.shape
+            gshape = (T, ns, self.n_out)
+        else:
+            _require(x.dim() == 3, "run_block_grad_stream_major takes stream-major buffers [n_streams, rows, n_in]")
+            ns, rows, _ = x.shape
+            row0, T, in_grad = window
+            _require(0 <= row0 and 0 <= T and row0 + T <= rows, f"the window [{row0}, {row0 + T}) reaches beyond the {rows} rows of x")
+            gshape = (ns, rows, self.n_out)
         dev = x.device
         if out_grad.dim() == 2 and self.n_out == 1:
             out_grad = out_grad.unsqueeze(-1)
-        _check_dev(out_grad, (T, ns, self.n_out), "out_grad")
+        _check_dev(out_grad, gshape, "out_grad")
         if state is None:
             state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=dev)
         if self.n_state:
@@ -661,15 +691,20 @@ class Program:
         accum = dict(accum or {})
         out = {}
         if "x" in want:
-            out["x"] = torch.empty_like(x)
+            if window is None:
+                out["x"] = torch.empty_like(x)
+            elif in_grad is not None:
+                out["x"] = _check_dev(in_grad.unsqueeze(-1) if in_grad.dim() == 2 and self.n_in == 1 else in_grad, tuple(x.shape), "in_grad")
+            else:
+                out["x"] = torch.empty_like(x) if (row0, T) == (0, rows) else torch.zeros_like(x)
         if "state" in want:
             out["state"] = torch.empty((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=dev)
-        for key, rows in (("params", self.n_param), ("consts", self.n_const)):
+        for key, nrow in (("params", self.n_param), ("consts", self.n_const)):
             if key in want:
                 if key in accum:
-                    out[key] = _check_dev(accum[key], (rows, ns), f"accum[{key!r}]")
+                    out[key] = _check_dev(accum[key], (nrow, ns), f"accum[{key!r}]")
                 else:
-                    out[key] = torch.zeros((_bi.max(rows, 1), ns), dtype=torch.float32, device=dev)
+                    out[key] = torch.zeros((_bi.max(nrow, 1), ns), dtype=torch.float32, device=dev)
         wsb = self.grad_workspace_bytes(ns, T, checkpoint_rows)
         ws = torch.empty((_bi.max(wsb, 16) + 3) // 4, dtype=torch.float32, device=dev)
 
@@ -690,7 +725,10 @@ class Program:
         a.workspace = ws.data_ptr()
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
-        C.check(C.lib.fz_run_block_grad(self._h, ctypes.byref(a), int(ns), int(T), torch.cuda.current_stream().cuda_stream))
+        if window is None:
+            C.check(C.lib.fz_run_block_grad(self._h, ctypes.byref(a), int(ns), int(T), torch.cuda.current_stream().cuda_stream))
+        else:
+            C.check(C.lib.fz_run_block_grad_stream_major(self._h, ctypes.byref(a), int(ns), int(rows), row0, T, torch.cuda.current_stream().cuda_stream))
         return out
 
 
