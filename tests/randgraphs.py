@@ -132,12 +132,13 @@ def make_typed(seed, max_in=3, depth=3):
     return _retype(rng, g, 0.35), n_in, n_out, "double"
 
 
-def _gate(rng, e, p):
+def _gate(rng, e, p, in_double=True):
     """sprinkle comparison / logical operators over arithmetic nodes: (a op b) becomes (a op b) * (a cmp b), (a op b) + c * ((a cmp x) && / || (b cmp y))
-    or (a op b) * !(a cmp b) -- the operands of the node itself are compared, so arities and delays stay what they were"""
+    or (a op b) * !(a cmp b) -- the operands of the node itself are compared, so arities and delays stay what they were.  in_double False:
+    the last kind compares in float like the others (no float64 node anywhere: what the backward takes)"""
     if not isinstance(e, tuple):
         return e
-    e = tuple(_gate(rng, c, p) if isinstance(c, tuple) else c for c in e)
+    e = tuple(_gate(rng, c, p, in_double) if isinstance(c, tuple) else c for c in e)
     if e[0] in ("add", "sub", "mul") and rng.random() < p:
         a, b = e[1], e[2]
         cmp_ = lambda x, y: (str(rng.choice(["lt", "le", "gt", "ge", "eq", "ne"])), x, y)   # noqa: E731
@@ -149,6 +150,8 @@ def _gate(rng, e, p):
             return ("add", e, ("mul", lit(float(rng.uniform(-0.1, 0.1))), (str(rng.choice(["and", "or"])), cmp_(a, th()), cmp_(b, th()))))
         if r < 0.85:
             return ("mul", e, ("not", cmp_(a, b)))
+        if not in_double:
+            return ("sub", e, ("mul", lit(0.05), cmp_(a, b)))
         return ("sub", e, ("mul", lit(0.05), cmp_(("mul", ("lit64", 1.0), a), b)))             # compared in double
     return e
 
@@ -175,3 +178,77 @@ def make_deep(seed, max_in=3, depth=3, p=0.3):
     (257..260, 300..400).  Its own random stream: the graphs of make() stay what they were"""
     g, n_in, n_out = make(seed, max_in, depth)
     return _deepen(np.random.default_rng(seed + 31000), g, p), n_in, n_out
+
+
+def make_cmp_grad(seed, max_in=3, depth=3, p=0.35):
+    """as make_cmp() for the backward, which refuses float64 nodes: every comparison is made in float.  Its own random stream: the
+    graphs of make_cmp() stay what they were"""
+    g, n_in, n_out = make(seed, max_in, depth)
+    return _gate(np.random.default_rng(seed + 56000), g, p, in_double=False), n_in, n_out
+
+
+P_REDELAY, P_PARAM, P_FUNCTION = 0.6, 0.3, 0.35     # make_grad: the share of delays re-drawn, of coefficients made parameters, of terms wrapped
+_STRUCTURE = ("seq", "par", "chan", "fb")
+
+
+def _first_leaf(e):
+    if e[0] in ("in", "del"):
+        return e
+    for c in e[1:]:
+        if isinstance(c, tuple):
+            leaf = _first_leaf(c)
+            if leaf is not None:
+                return leaf
+    return None
+
+
+def _wrap(rng, t):
+    """a feed-forward term inside a graph function: the value stays bounded where the term is, the derivative finite everywhere"""
+    r = rng.random()
+    if r < 0.2:
+        return ("tanh", t)
+    if r < 0.4:
+        return ("abs", t)
+    if r < 0.55:
+        return ("min", t, lit(float(rng.uniform(0.02, 0.15)) * (1 if rng.random() < 0.5 else -1)))   # (a threshold both sides of which a term visits within a few rows)
+    if r < 0.7:
+        leaf = _first_leaf(t)
+        return ("max", t, mul(_coef(rng), leaf) if leaf is not None else lit(float(rng.uniform(-0.5, 0.5))))
+    if r < 0.85:
+        return ("sqrt", add(mul(t, t), lit(0.25)))
+    return ("exp", mul(lit(-0.5), ("abs", t)))
+
+
+def _regrad(rng, e, in_fb, term, count):
+    """the three rewrites of make_grad; in_fb: inside a feedback's body (terms stay what they are: the loop keeps its small gain);
+    term: e is a summand of its box; count: [parameters so far]"""
+    if not isinstance(e, tuple):
+        return e
+    k = e[0]
+    if k in _STRUCTURE:
+        return (k,) + tuple(_regrad(rng, c, in_fb or k == "fb", True, count) for c in e[1:])
+    if k == "del":
+        return ("del", e[1], int(rng.integers(1, 9))) if rng.random() < P_REDELAY else e
+    if k in ("in", "lit"):
+        return e
+    if k in ("add", "sub"):
+        return (k,) + tuple(_regrad(rng, c, in_fb, True, count) for c in e[1:])
+    if k == "div":
+        return (k, _regrad(rng, e[1], in_fb, True, count), e[2])
+    out = (k,) + tuple(_regrad(rng, c, in_fb, False, count) if isinstance(c, tuple) else c for c in e[1:])
+    if k == "mul" and out[1][0] == "lit" and rng.random() < P_PARAM:
+        out = ("mul", ("param", count[0]), out[2])
+        count[0] += 1
+    if term and not in_fb and rng.random() < P_FUNCTION:
+        out = _wrap(rng, out)
+    return out
+
+
+def make_grad(seed, max_in=3, depth=3):
+    """as make(), rewritten for the backward (fz_run_block_grad): delays re-drawn from 1..8 (register lines up to the deepest the backward
+    takes), coefficients turned into per-stream parameters (indices dense from 0; the caller draws them like _coef does), feed-forward terms
+    wrapped in the graph functions.  Its own random stream: the graphs of make() stay what they were.  Returns (sexpr, n_in, n_out, n_param)"""
+    g, n_in, n_out = make(seed, max_in, depth)
+    count = [0]
+    g = _regrad(np.random.default_rng(seed + 43000), g, False, True, count)
+    return g, n_in, n_out, count[0]

@@ -45,23 +45,29 @@ def same(a, b):
     return bool(np.all(eq | (np.isnan(a) & np.isnan(b))))
 
 
-def make_inputs(p, name, ns, T, seed):
+def make_inputs(p, name, ns, T, seed, ties=None, draw_params=None, special_every=1):
+    """x, state, params, dL/dy, dL/d(state after) and the two accumulators, none of them zero.  ties (default: by name): the ties and
+    specials below mixed into x -- special_every = k: only into every k-th stream, the others stay finite (behind a feedback a NaN
+    never leaves its stream); draw_params(p, ns, rng): the per-stream coefficients of a graph that is none of the named ones"""
     rng = np.random.default_rng(seed)
     x = (rng.standard_normal((T, ns, p.n_in)) * 0.5).astype(F32)
     if name == "div_sqrt_exp":
         x = np.abs(x)
-    if name in ("rules", "envelope_follower", "clipped_biquad"):
+    if name in ("rules", "envelope_follower", "clipped_biquad") if ties is None else ties:
         # ties of MIN / MAX (equal values, +0 against -0), +-0 under ABS, NaN and inf through the comparisons
         special = np.array([0.0, -0.0, 1.0, 0.5, np.nan, np.inf, -np.inf, 0.75], F32)
         m = rng.random(x.shape) < 0.2
+        m[:, np.arange(ns) % special_every != 0] = False
         x[m] = special[rng.integers(0, special.size, int(m.sum()))]
-        if p.n_in == 2:
+        if p.n_in >= 2:
             tie = rng.random((T, ns)) < 0.2
             x[:, :, 1][tie] = x[:, :, 0][tie]
     s0 = (rng.standard_normal((p.n_state, ns)) * 0.1).astype(F32)
     par = None
     if p.n_param:
-        if name == "moog_ladder":
+        if draw_params is not None:
+            par = draw_params(p, ns, rng)
+        elif name == "moog_ladder":
             par = rng.uniform(0.05, 0.5, (1, ns)).astype(F32)
         elif name == "osc_chain6":
             import graphs as G

@@ -35,7 +35,9 @@ std::string grad_unsupported_reason(const Graph& g)
 }
 
 // The chunk of sweep 2 keeps C steps of state and frame in registers, (n_state + n_in) * C floats, next to one step's node values
-// and the accumulators: at most 64 saved floats, 16 rows at most (measured: no graph of tests/test_grad_host.py spills).
+// and the accumulators: at most 64 saved floats, 16 rows at most.  Measured: no graph of tests/test_grad_host.py spills; random graphs
+// (tests/grad_fuzz_cells.py) do spill SGPRs into VGPR lanes -- one-state graphs at C = 16 as well as 72-state ones at C = 1, with two
+// coefficients as with twenty, so counting n_const here removes nothing -- and none uses scratch: correct, slower.
 uint32_t grad_default_checkpoint(const Graph& g)
 {
    const uint32_t per_row = std::max<uint32_t>(g.n_state + g.n_in, 1);
@@ -58,6 +60,24 @@ uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C)
    while (R * wide < 32) R *= 2;
    while (R * narrow < 32 && sm_patch_bytes(g, 2 * R) <= kLdsBytes / 2) R *= 2;
    return std::max(R, C);
+}
+
+// the longest patch any graph can have: the largest power of two R whose patch of ONE wire in all, (R + 4) floats per lane, fits
+// the LDS of a workgroup (128 on gfx950)
+uint32_t grad_sm_max_patch_rows()
+{
+   uint32_t R = 4;
+   while ((2u * R * 1u + 4u) * 4u * kGradBlock <= kLdsBytes) R *= 2;   // (does the next power of two still fit?)
+   return R;
+}
+
+// could adjoint_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
+bool adjoint_variant_fits(const Graph& g, const Variant& v)
+{
+   if (!(v.flags & FZ_VF_ADJOINT) || (v.flags & ~(FZ_VF_ADJOINT | FZ_VF_ADJOINT_SM)) || !grad_unsupported_reason(g).empty()) return false;
+   if (v.block != kGradBlock || v.U == 0 || v.U > kGradMaxCheckpoint || (v.U & (v.U - 1))) return false;
+   if (!(v.flags & FZ_VF_ADJOINT_SM)) return v.P == 1;
+   return v.P >= 4 && !(v.P & (v.P - 1)) && v.P % v.U == 0 && v.P <= grad_sm_max_patch_rows() && sm_patch_bytes(g, v.P) <= kLdsBytes;
 }
 
 static uint32_t checkpoint_of(const Graph& g, uint32_t checkpoint_rows)

@@ -239,6 +239,8 @@ std::string grad_unsupported_reason(const Graph& g);
 uint32_t grad_default_checkpoint(const Graph& g);
 // rows per LDS patch of the stream-major adjoint kernel at checkpoint stride C: a multiple of C and of 4 (fz_grad.cpp)
 uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C);
+uint32_t grad_sm_max_patch_rows();                                 // the longest patch any graph can have (one wire, the whole LDS)
+bool adjoint_variant_fits(const Graph& g, const Variant& v);       // an adjoint Variant the backward could have made for this graph
 
 // ---- runtime ---------------------------------------------------------------------------------------------
 // what the code object's metadata says the kernel needs (AMDGPU msgpack notes)

@@ -45,6 +45,8 @@ typedef double VD;
 #define FZ_API (FZ_AX / 4)                    /* float4 pieces per stream and patch */
 #define FZ_APO (FZ_AY / 4)
 
+#define FZ_AFLIGHT 8                          /* float4 pieces a lane has in flight while a patch part is fetched */
+
 typedef float fz_f4 __attribute__((ext_vector_type(4)));
 
 struct fz_adj_sm_args {
@@ -87,6 +89,9 @@ __device__ __forceinline__ void fz_adj_fetch(float* part, const float* g, size_t
       const unsigned e = (unsigned)i * 64u + lane, row = e / PP, q = e % PP;
       const unsigned grow = row < rows ? row : rows - 1u, gq = q * 4u < nval ? q * 4u : 0u;
       *reinterpret_cast<fz_f4*>(part + row * FZ_AROW + q * 4u) = *reinterpret_cast<const fz_f4*>(g + grow * gstride + gq);
+      // at most FZ_AFLIGHT pieces in flight: the pieces before are parked before the next are fetched (a wide frame's patch is 20 and
+      // more pieces: all of them in registers at once, on top of a chunk's saved states, passed 256 registers)
+      if ((i + 1) % FZ_AFLIGHT == 0 && i + 1 < PIECES) asm volatile("" ::: "memory");
    }
 }
 

@@ -20,7 +20,6 @@ void manifest_record(const fz_program* p, const Variant& v)
 {
    static const char* const path = std::getenv("FLOWZ_HIP_MANIFEST");
    if (!path || !*path || p->recipe.empty()) return;
-   if (v.flags & FZ_VF_ADJOINT) return;                  // (adjoint kernels are built on first use; a manifest lists forward launches)
    char head[96];
    std::snprintf(head, sizeof head, "FZM1 %u %u %u %u %zu\n", v.P, v.U, v.block, v.flags, p->recipe.size());
    const std::string rec = head + p->recipe;
@@ -43,6 +42,14 @@ void manifest_record(const fz_program* p, const Variant& v)
    ::close(fd);
 }
 
+// What a record's variant must satisfy before anything is generated from it: a forward kernel runs 1, 2 or 4 streams per lane.  An adjoint
+// variant has rules of its own and one home for them, fz_grad.cpp: adjoint_variant_fits -- asked below, once the record's graph is compiled.
+static bool variant_is_sane(const Variant& v)
+{
+   if (v.flags & FZ_VF_ADJOINT) return true;
+   return (v.P == 1 || v.P == 2 || v.P == 4) && v.U != 0 && v.U <= 128 && v.block != 0 && v.block % 64 == 0 && v.block <= 1024;
+}
+
 int manifest_build(const std::string& path, unsigned n_workers, uint32_t counts[4])
 {
    const std::string text = slurp(path);
@@ -61,7 +68,7 @@ int manifest_build(const std::string& path, unsigned n_workers, uint32_t counts[
       pos = eol + 1 + n;
       // (the file is data from elsewhere: a variant no launch could have resolved -- it would divide by P or size a workgroup by `block`
       //  further down -- is counted as failed, not built)
-      if ((v.P != 1 && v.P != 2 && v.P != 4) || v.U == 0 || v.U > 128 || v.block == 0 || v.block % 64 != 0 || v.block > 1024) {
+      if (!variant_is_sane(v)) {
          ++bad_records;
          continue;
       }
@@ -92,7 +99,10 @@ int manifest_build(const std::string& path, unsigned n_workers, uint32_t counts[
          continue;
       }
       programs.emplace_back(p);
-      for (const Variant& v : kv.second) items.push_back(Item{p, v});
+      for (const Variant& v : kv.second) {
+         if ((v.flags & FZ_VF_ADJOINT) && !adjoint_variant_fits(p->g, v)) ++counts[3];   // (no variant the backward makes: C, the patch rows in P, a patch this graph's frames do not fit, a graph it refuses)
+         else items.push_back(Item{p, v});
+      }
    }
    std::atomic<size_t> next{0};
    std::atomic<uint32_t> at_hand{0}, built{0}, failed{0};
