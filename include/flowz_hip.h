@@ -312,7 +312,8 @@ enum { FZ_VF_STAGE_PACK = 8u,   /* one stream per lane; the K isomorphic segment
  * on the board -- let fz_program_tune measure it                                                   */
 #define FZ_VF_MAX_WG(n) (((uint32_t)(n) & 7u) << 20)
 /* bits 0..2, 12..14, 16..18 and 27 are reserved (FZ_E_INVALID): rounds 1-5 had experiment knobs there (cache policies, the SLP vectoriser, the
- * plain block order); those are compile-time switches of the kernel source now (FLOWZ_HIP_EXTRA_OPTS) */
+ * plain block order); those are compile-time switches of the kernel source now (FLOWZ_HIP_EXTRA_OPTS).  The library
+ * names kernels of its own with some of them (the adjoint kernels, the PCM kernel): no caller's variant can */
 
 int fz_program_build(fz_program* p, const fz_variant* v);           /* JIT (or cache hit) only   */
 /* the same with the variant's automatic fields resolved as a launch of this block shape would: the shape of a launch is
@@ -552,6 +553,47 @@ long fz_program_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, 
 long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 
 /* ------------------------------------------------------------------------------------------
+ * 16-bit PCM frames.  fz_run_block_pcm16 is fz_run_block for a block whose frames are int16 on one side or on both: the caller
+ * sends and receives 2 bytes per sample instead of 4, the conversions happen in the kernel.
+ *
+ * THE CONVERSION RULE (stated here once; the kernel, the host path and the tests follow it):
+ *   in    x = (float)q * 2^-15 for q in [-32768, 32767].  Exact: no rounding, and -32768 gives -1.0f.
+ *   out   r = y * 32768.0f, ONE float32 multiplication (exact unless it overflows, and an overflow saturates anyway); then, in this
+ *         order:  y NaN -> 0;  r >= 32767.0f -> 32767;  r <= -32768.0f -> -32768;  else r rounded to the nearest integer, ties to even.
+ *   No dither, no noise shaping.
+ * Between the two conversions the arithmetic is that of fz_run_block (one IEEE float32 rounding per graph node, no FMA, correctly
+ * rounded division and square root, denormals kept): a float32 output equals fz_run_block on the converted input bit for bit, an
+ * int16 output is the rule applied to that float32 output.  No tolerance is involved anywhere.
+ *
+ * Frames are time-major, in [n_samples][n_streams][n_in] and out [n_samples][n_streams][n_out], each side int16_t (FZ_FRAMES_I16) or
+ * float (FZ_FRAMES_F32) as in_type / out_type say; state and params are those of fz_run_block -- the state layout does not depend
+ * on the frame type, so float32 blocks and PCM blocks chain on one state buffer.  Any n_streams >= 1: where n_streams * wires is odd
+ * on an int16 side, its rows start off the dword grid and a second instantiation of the kernel (2-byte accesses) runs.
+ *
+ * Argument checks as for fz_run_block, all made before the device is needed: device pointers 16-byte aligned; a pointer NULL iff its
+ * width is 0; an unknown frame type is FZ_E_INVALID; float32 on both sides is FZ_E_INVALID (that block is fz_run_block); an empty
+ * block is FZ_OK and touches nothing; a row of 4 GiB or more is FZ_E_UNSUPPORTED.  `in` and `out` may be the SAME buffer when both
+ * sides are int16 and n_in == n_out (in place); any other overlap of the two is FZ_E_INVALID.
+ *
+ * Scope: fz_compile programs that are float32 throughout and whose delay lines live in registers (max_delay <= 8).  Typed programs,
+ * float64 nodes, complex wires, modulators and delay lines in LDS or HBM rings are FZ_E_UNSUPPORTED, fz_last_error() names which
+ * (fz_program_pcm16_check asks without a device).  Not built: stream-tiled and stream-major PCM frames, windows, 24-bit and
+ * float16 frames, dither, PCM in the backward, fz_program_tune for this kernel (its plan is static).
+ * ---------------------------------------------------------------------------------------- */
+enum { FZ_FRAMES_F32 = 0, FZ_FRAMES_I16 = 1 };
+/* FZ_OK, or FZ_E_UNSUPPORTED with the reason in fz_last_error(); host only */
+int  fz_program_pcm16_check(const fz_program* p);
+int  fz_run_block_pcm16(fz_program* p, const void* in, void* out, float* state, const float* params,
+                        uint64_t n_streams, uint32_t n_samples, uint32_t in_type, uint32_t out_type, void* hip_stream);
+/* The kernel a block of (in_type, out_type, n_streams) runs (n_streams 0: 2^20), without a device: its registers and scratch
+ * (`unroll` = rows per chunk), its symbol fz_pcm16_kernel_i<0|1>o<0|1>p<streams per lane>u<rows per chunk>b<lanes per workgroup>[h][m]_g<graph tag>
+ * -- i / o: that side is int16; h: 2-byte accesses (int16 rows off the dword grid); m: stores that let L2 merge sectors (output
+ * rows off the 64-byte grid) -- and its whole source.  The stream count matters only through those two letters. */
+int  fz_program_pcm16_resources(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, fz_kernel_resources* out);
+long fz_program_pcm16_kernel_symbol(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, char* buf, size_t cap);
+long fz_program_pcm16_source(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, char* buf, size_t cap);
+
+/* ------------------------------------------------------------------------------------------
  * fz_bank -- device-resident closure state for n_streams streams: the `state_` member of
  * stateful_lambda (flowz.hpp:1190-1191).  clone == copying the closure (snapshot, :1206).
  * The *_host entry points stage through device memory (H2D, kernel, D2H, synchronous); they
@@ -590,6 +632,12 @@ int  fz_bank_process_host_stream_major(fz_bank* b, const float* in_host, float* 
 /* the same with float64 result frames (FZ_VF_OUT_F64): what a closure with double literals returns
  * in the reference (tuple<double>, flowz.hpp:1225-1229 with the ResultType of test/tests.cpp:201) */
 int  fz_bank_process_host_f64(fz_bank* b, const float* in_host, double* out_host, uint32_t n_samples);
+/* fz_run_block_pcm16 on the bank's state (device frames, asynchronous on hip_stream), and the host path of fz_bank_process_host for a
+ * caller that holds interleaved 16-bit PCM: int16 frames in, int16 frames out, through int16 staging buffers, the same time chunks
+ * and the same three streams -- half the PCIe bytes in each direction */
+int  fz_bank_process_pcm16(fz_bank* b, const void* in_dev, void* out_dev, uint32_t n_samples, uint32_t in_type, uint32_t out_type,
+                           void* hip_stream);
+int  fz_bank_process_host_pcm16(fz_bank* b, const int16_t* in_host, int16_t* out_host, uint32_t n_samples);
 
 /* ------------------------------------------------------------------------------------------
  * Device utilities used by the measurement harness (bench.py) and tests.

@@ -47,6 +47,7 @@ IR_KINDS = {1: "input", 2: "const", 3: "param", 4: "delay", 5: "add", 6: "sub", 
             21: "abs", 22: "sqrt", 23: "exp", 24: "tanh", 25: "min", 26: "max"}
 FZ_IR_ABS, FZ_IR_SQRT, FZ_IR_EXP, FZ_IR_TANH, FZ_IR_MIN, FZ_IR_MAX = 21, 22, 23, 24, 25, 26
 FZ_DT_F32, FZ_DT_F64, FZ_DT_CF32, FZ_DT_CF64 = 0, 1, 2, 3
+FZ_FRAMES_F32, FZ_FRAMES_I16 = 0, 1   # frame types of fz_run_block_pcm16
 DTYPES = {"f32": 0, "f64": 1, "cf32": 2, "cf64": 3}
 
 
@@ -162,6 +163,13 @@ def _load():
         "fz_program_grad_resources_for": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),
         "fz_program_grad_kernel_symbol_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_grad_source_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_pcm16_check": (ctypes.c_int, [P]),
+        "fz_run_block_pcm16": (ctypes.c_int, [P, P, P, P, P, u64, u32, u32, u32, P]),
+        "fz_program_pcm16_resources": (ctypes.c_int, [P, u32, u32, u64, ctypes.POINTER(KernelResources)]),
+        "fz_program_pcm16_kernel_symbol": (ctypes.c_long, [P, u32, u32, u64, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_pcm16_source": (ctypes.c_long, [P, u32, u32, u64, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_bank_process_pcm16": (ctypes.c_int, [P, P, P, u32, u32, u32, P]),
+        "fz_bank_process_host_pcm16": (ctypes.c_int, [P, P, P, u32]),
         "fz_device_count": (ctypes.c_int, []),
         "fz_synth_fill": (ctypes.c_int, [P, u64, u32, u32, u32, u64, u64, u32, P]),
         "fz_rbj_lowpass": (ctypes.c_int, [P, P, f32, u64, P, P, P]),

@@ -204,24 +204,34 @@ static void drain_pipeline(fz_bank* b)
 // which run back to back on one stream).  With pinned host memory (hipHostMalloc / hipHostRegister /
 // torch pin_memory) both PCIe directions run concurrently; pageable memory still works, HIP then
 // stages the copies itself.
-static int bank_process_host(fz_bank* b, const float* in_host, void* out_host, uint32_t n_samples, bool f64)
+// (frames: float32 in and out, float32 in and float64 out, or int16 in and out -- fz_bank_process_host_pcm16)
+enum class HostFrames { F32, OutF64, Pcm16 };
+static int bank_process_host(fz_bank* b, const void* in_host, void* out_host, uint32_t n_samples, HostFrames frames)
 {
    FZ_GUARD(
       if (!b || !out_host || !n_samples) fail(FZ_E_INVALID, "fz_bank_process_host: bad arguments");
       check_bank_device(b);
       const Graph& g = b->prog->g;
-      const size_t irow = (size_t)b->n_streams * g.n_in * 4, orow = (size_t)b->n_streams * g.n_out * (f64 ? 8 : 4);
+      const bool f64 = frames == HostFrames::OutF64, pcm = frames == HostFrames::Pcm16;
+      const size_t irow = (size_t)b->n_streams * g.n_in * (pcm ? 2 : 4), orow = (size_t)b->n_streams * g.n_out * (f64 ? 8 : pcm ? 2 : 4);
       if (irow && !in_host) fail(FZ_E_INVALID, "in_host is null but the graph has input wires");
       const fz_variant v64{0, 0, 0, FZ_VF_OUT_F64};
       const fz_variant* uv = f64 ? &v64 : nullptr;
+      // one block of nt rows from / to device buffers, starting at sample t0 of the call
+      auto run = [&](const float* din, float* dout, uint32_t nt, void* stream, uint32_t t0) {
+         if (pcm)
+            return fz::launch_pcm16(b->prog, g.n_in ? din : nullptr, dout, g.n_state ? b->state : nullptr, b->params, b->n_streams, nt,
+                                    FZ_FRAMES_I16, FZ_FRAMES_I16, stream);
+         return fz::launch(b->prog, g.n_in ? din : nullptr, dout, g.n_state ? b->state : nullptr, b->params, b->n_streams, nt, uv, stream,
+                           0, 0, 0, t0);                       // (sample-rate modulators: this chunk starts at sample t0)
+      };
       constexpr size_t kChunkBytes = 32u << 20;            // per direction and pipeline slot
       const size_t row = std::max(irow, orow);
       uint32_t chunk_t = (uint32_t)std::max<size_t>(1, kChunkBytes / std::max<size_t>(row, 1));
       if ((size_t)n_samples * row <= 2 * kChunkBytes || chunk_t >= n_samples) {                    // one round trip
          ensure_stage(b, irow * n_samples, orow * n_samples);
          if (irow) FZ_HIP(hipMemcpy(b->stage_in, in_host, irow * n_samples, hipMemcpyHostToDevice));
-         int rc = fz::launch(b->prog, g.n_in ? b->stage_in : nullptr, b->stage_out, g.n_state ? b->state : nullptr, b->params,
-                             b->n_streams, n_samples, uv, nullptr, 0);
+         int rc = run(b->stage_in, b->stage_out, n_samples, nullptr, 0);
          if (rc != FZ_OK) return rc;
          FZ_HIP(hipMemcpy(out_host, b->stage_out, orow * n_samples, hipMemcpyDeviceToHost));
          return FZ_OK;
@@ -258,8 +268,7 @@ static int bank_process_host(fz_bank* b, const float* in_host, void* out_host, u
          if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_out[slot], 0));            // D2H k-2 has drained this slot
          int rc = FZ_OK;
          try {
-            rc = fz::launch(b->prog, g.n_in ? din : nullptr, dout, g.n_state ? b->state : nullptr, b->params, b->n_streams, nt, uv,
-                            b->s_run, 0, 0, 0, t0);              // (sample-rate modulators: this chunk starts at sample t0)
+            rc = run(din, dout, nt, b->s_run, t0);
          } catch (...) {                                    // chunks already in flight still write into the caller's memory
             drain_pipeline(b);
             throw;
@@ -280,7 +289,7 @@ static int bank_process_host(fz_bank* b, const float* in_host, void* out_host, u
 
 int fz_bank_process_host(fz_bank* b, const float* in_host, float* out_host, uint32_t n_samples)
 {
-   return bank_process_host(b, in_host, out_host, n_samples, false);
+   return bank_process_host(b, in_host, out_host, n_samples, HostFrames::F32);
 }
 
 // Host buffers in the reference's own calling convention: one contiguous sample buffer per stream
@@ -354,7 +363,26 @@ int fz_bank_process_host_stream_major(fz_bank* b, const float* in_host, float* o
 
 int fz_bank_process_host_f64(fz_bank* b, const float* in_host, double* out_host, uint32_t n_samples)
 {
-   return bank_process_host(b, in_host, out_host, n_samples, true);
+   return bank_process_host(b, in_host, out_host, n_samples, HostFrames::OutF64);
+}
+
+int fz_bank_process_pcm16(fz_bank* b, const void* in_dev, void* out_dev, uint32_t n_samples, uint32_t in_type, uint32_t out_type, void* hip_stream)
+{
+   FZ_GUARD(
+      if (!b) fail(FZ_E_INVALID, "null bank");
+      check_bank_device(b);
+      const Graph& g = b->prog->g;
+      return fz::launch_pcm16(b->prog, in_dev, out_dev, g.n_state ? b->state : nullptr, b->params, b->n_streams, n_samples, in_type, out_type,
+                              hip_stream);)
+}
+
+int fz_bank_process_host_pcm16(fz_bank* b, const int16_t* in_host, int16_t* out_host, uint32_t n_samples)
+{
+   FZ_GUARD(
+      if (!b) fail(FZ_E_INVALID, "null bank");
+      const std::string why = fz::pcm16_unsupported_reason(b->prog->g);
+      if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);)
+   return bank_process_host(b, in_host, out_host, n_samples, HostFrames::Pcm16);
 }
 
 }  // extern "C"

@@ -185,6 +185,12 @@ constexpr uint32_t FZ_VF_ADJOINT = 1u << 27;
 // own; one of the reserved bits, so no caller's variant names it either.  Such a Variant carries the rows of its LDS patch in P
 // (fz_grad.cpp: grad_sm_patch_rows is their one home; the kernel itself runs one stream per lane).
 constexpr uint32_t FZ_VF_ADJOINT_SM = 1u << 18;
+// internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
+// names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte
+// accesses).  FZ_VF_ST_MERGE means for it what it means for the frame kernel.  Such a Variant shares the kernel cache and the manifests
+// with every other; the forward planner never sees it (fz_pcm16.cpp: pcm16_plan is the one place that makes one).
+constexpr uint32_t FZ_VF_PCM16 = 1u << 12;
+constexpr uint32_t FZ_VF_PCM16_IN = 1u, FZ_VF_PCM16_OUT = 2u, FZ_VF_PCM16_B16 = 4u;
 constexpr uint32_t kChipCUs = 256;       // MI355X (gfx950): 8 XCDs x 32 CUs -- what chip_cus() answers on a box without a GPU
 unsigned chip_cus();                     // compute units of the current device (fz_launch.cpp)
 
@@ -241,6 +247,10 @@ uint32_t grad_default_checkpoint(const Graph& g);
 uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C);
 uint32_t grad_sm_max_patch_rows();                                 // the longest patch any graph can have (one wire, the whole LDS)
 bool adjoint_variant_fits(const Graph& g, const Variant& v);       // an adjoint Variant the backward could have made for this graph
+// 16-bit PCM frames (fz_pcm16.cpp): why the PCM kernel does not take this graph ("" = it does), and whether v is a Variant
+// fz_run_block_pcm16 could have made for it
+std::string pcm16_unsupported_reason(const Graph& g);
+bool pcm16_variant_fits(const Graph& g, const Variant& v);
 
 // ---- runtime ---------------------------------------------------------------------------------------------
 // what the code object's metadata says the kernel needs (AMDGPU msgpack notes)
@@ -345,6 +355,9 @@ Variant settle_variant(fz_program* p, Variant v);
 int launch(fz_program* p, const float* in, float* out, float* state, const float* params,
            uint64_t n_streams, uint32_t n_samples, const fz_variant* v, void* stream, uint32_t tile_streams = 0,
            uint32_t rows_total = 0, uint32_t row0 = 0, uint32_t mod_row0 = 0);   // mod_row0: row of the modulator arrays that goes with row 0 of the frame buffers
+// fz_run_block_pcm16: argument checks, the static plan, the launch (fz_pcm16.cpp)
+int launch_pcm16(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams, uint32_t n_samples,
+                 uint32_t in_type, uint32_t out_type, void* stream);
 int tune(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
          uint32_t n_samples, uint32_t tile_streams, void* stream, fz_variant* chosen, float* chosen_ms, bool implicit = false);
 std::vector<fz_variant> tune_candidates(const Graph& g, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams);

@@ -1,0 +1,219 @@
+// Blocks whose frames are 16-bit PCM on one side or on both (include/flowz_hip.h: fz_run_block_pcm16): what the PCM kernel supports,
+// its static plan, argument checks and the launch.  The kernel text is the common head of fz_block_kernel.hip.inc, the generated body
+// of the frame kernels (gen_body) and fz_kernel_pcm16.hip.inc; the code objects go through the kernel cache as a Variant with
+// FZ_VF_PCM16.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "fz_runtime.hpp"
+
+namespace fz {
+
+constexpr uint32_t kPcmBlock = 256;       // lanes per workgroup
+constexpr uint32_t kPcmUnroll = 8;        // rows per chunk buffer (halved until nothing spills: settle_variant)
+constexpr uint64_t kPcmStoreGrid = 64;    // output rows that start off this grid share sectors between waves (FZ_VF_ST_MERGE)
+
+std::string pcm16_unsupported_reason(const Graph& g)
+{
+   if (g.typed) return "typed programs (fz_compile_typed) are not supported with PCM frames";
+   if (g.n_mod) return "sample-rate modulators (fz_modulator) are not supported with PCM frames";
+   for (uint8_t part : g.out_part)
+      if (part) return "complex wires are not supported with PCM frames";
+   for (const Line& L : g.lines) {
+      if (L.far) return "delay lines deeper than 256 samples (rings in HBM) are not supported with PCM frames";
+      if (L.in_lds) return "delay lines deeper than 8 samples (rings in LDS) are not supported with PCM frames";
+      if (L.part || L.f64) return "complex or double delay lines are not supported with PCM frames";
+   }
+   if (g.n_lds_slots || g.max_delay > kRegMaxDepth) return "delay lines deeper than 8 samples are not supported with PCM frames";
+   if (!g.consts64.empty()) return "float64 nodes (a C++ double literal, fz_literal_f64) are not supported with PCM frames";
+   for (const Node& nd : g.nodes) {
+      if (nd.f64) return "float64 nodes (a C++ double literal, fz_literal_f64) are not supported with PCM frames";
+      if (nd.kind == FZ_IR_MOD) return "sample-rate modulators (fz_modulator) are not supported with PCM frames";
+   }
+   return "";
+}
+
+static void require_supported(const Graph& g)
+{
+   const std::string why = pcm16_unsupported_reason(g);
+   if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
+}
+
+static void check_types(uint32_t in_type, uint32_t out_type)
+{
+   if (in_type > FZ_FRAMES_I16 || out_type > FZ_FRAMES_I16) fail(FZ_E_INVALID, "unknown frame type: FZ_FRAMES_F32 or FZ_FRAMES_I16");
+   if (in_type == FZ_FRAMES_F32 && out_type == FZ_FRAMES_F32)
+      fail(FZ_E_INVALID, "float32 frames on both sides: that block is fz_run_block");
+}
+
+static uint32_t bytes_of(uint32_t type) { return type == FZ_FRAMES_I16 ? 2u : 4u; }
+
+// The plan: ONE choice per (graph width, int16 rows on / off the dword grid).
+//   up to two wires a side, on the grid    four streams per lane: a wire's int16 slice is a b64 access, its floats a b128
+//   wider frames                           two streams per lane: a slice of eight samples and more per row fills the chunk buffers
+//   off the grid (streams x wires odd on an int16 side)   two streams per lane, 2-byte accesses on the int16 sides
+// 256 lanes per workgroup, chunks of 8 rows; free-running waves.
+static Variant pcm16_plan(const Graph& g, uint32_t in_type, uint32_t out_type, uint64_t n_streams)
+{
+   const bool i16_in = in_type == FZ_FRAMES_I16, i16_out = out_type == FZ_FRAMES_I16;
+   const bool off_grid = (i16_in && ((n_streams * g.n_in) & 1u)) || (i16_out && ((n_streams * g.n_out) & 1u));
+   Variant v;
+   v.P = (std::max(g.n_in, g.n_out) > 2 || off_grid) ? 2 : 4;
+   v.U = kPcmUnroll;
+   v.block = kPcmBlock;
+   v.flags = FZ_VF_PCM16 | (i16_in ? FZ_VF_PCM16_IN : 0u) | (i16_out ? FZ_VF_PCM16_OUT : 0u) | (off_grid ? FZ_VF_PCM16_B16 : 0u);
+   if ((n_streams * g.n_out * bytes_of(out_type)) % kPcmStoreGrid || n_streams % v.P) v.flags |= FZ_VF_ST_MERGE;
+   return v;
+}
+
+// could pcm16_plan (and the halving of the unroll behind it) have made v for this graph?  (kernel manifests are data from elsewhere)
+bool pcm16_variant_fits(const Graph& g, const Variant& v)
+{
+   constexpr uint32_t sub = FZ_VF_PCM16_IN | FZ_VF_PCM16_OUT | FZ_VF_PCM16_B16;
+   if (!(v.flags & FZ_VF_PCM16) || (v.flags & ~(FZ_VF_PCM16 | sub | FZ_VF_ST_MERGE)) || !(v.flags & (FZ_VF_PCM16_IN | FZ_VF_PCM16_OUT))) return false;
+   if (!pcm16_unsupported_reason(g).empty()) return false;
+   if (v.block != kPcmBlock || v.U == 0 || v.U > kPcmUnroll || (v.U & (v.U - 1))) return false;
+   const bool two = std::max(g.n_in, g.n_out) > 2 || (v.flags & FZ_VF_PCM16_B16);
+   return v.P == (two ? 2u : 4u);
+}
+
+// the kernel a block of this shape runs
+static Variant pcm16_variant(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams)
+{
+   if (!p) fail(FZ_E_INVALID, "null program");
+   require_supported(p->g);
+   check_types(in_type, out_type);
+   return settle_variant(p, pcm16_plan(p->g, in_type, out_type, n_streams ? n_streams : (1ull << 20)));
+}
+
+// kernarg image of `struct fz_pcm_args` (fz_kernel_pcm16.hip.inc) up to the coefficient tail
+struct PcmArgsHeader {
+   const void* in;
+   void* out;
+   float* state;
+   const float* params;
+   unsigned long long n_streams;
+   unsigned int n_samples;
+   unsigned int n_groups;
+};
+static_assert(sizeof(PcmArgsHeader) == 4 * 8 + 8 + 2 * 4, "PcmArgsHeader must match the head of the kernel's fz_pcm_args without padding");
+
+int launch_pcm16(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams, uint32_t n_samples,
+                 uint32_t in_type, uint32_t out_type, void* stream)
+{
+   if (!p) fail(FZ_E_INVALID, "null program");
+   const Graph& g = p->g;
+   require_supported(g);
+   check_types(in_type, out_type);
+   if (n_streams == 0 || n_samples == 0) return FZ_OK;      // an empty block: nothing to evaluate, state unchanged
+   if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
+   if (g.n_out && !out) fail(FZ_E_INVALID, "out is null but the graph has output wires");
+   if (g.n_in && !in) fail(FZ_E_INVALID, "in is null but the graph has input wires");
+   if (g.n_state && !state) fail(FZ_E_INVALID, "state is null but the graph has delay lines");
+   if (g.n_param && !params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
+   auto mis = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) != 0; };
+   if (mis(in) || mis(out) || mis(state) || mis(params)) fail(FZ_E_INVALID, "device pointers must be 16-byte aligned");
+   // a row through one descriptor, and the last lane's byte offset (its four streams may reach past the row) in 32 bits
+   const uint64_t irow = n_streams * g.n_in * bytes_of(in_type), orow = n_streams * g.n_out * bytes_of(out_type);
+   const uint64_t lane_streams = (n_streams + 3) / 4 * 4;
+   if (lane_streams * std::max<uint64_t>((uint64_t)g.n_in * bytes_of(in_type), (uint64_t)g.n_out * bytes_of(out_type)) >= (1ull << 32))
+      fail(FZ_E_UNSUPPORTED, "row longer than 4 GiB: shard the streams");
+   if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams");
+   // in place: every lane reads a row's slice before it writes the same bytes -- int16 on both sides, as many wires out as in
+   const uint64_t ibytes = irow * n_samples, obytes = orow * n_samples;
+   if (in && out && ibytes && obytes) {
+      const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+      const bool in_place = i0 == o0 && in_type == FZ_FRAMES_I16 && out_type == FZ_FRAMES_I16 && g.n_in == g.n_out;
+      if (!in_place && i0 < o0 + obytes && o0 < i0 + ibytes)
+         fail(FZ_E_INVALID, "in and out overlap: in place only with int16 frames on both sides, as many output wires as input wires and in == out");
+   }
+   require_device();
+   const Variant v = settle_variant(p, pcm16_plan(g, in_type, out_type, n_streams));
+   void* fn = nullptr;
+   (void)get_kernel(p, v, &fn);
+   const size_t kbytes = (sizeof(PcmArgsHeader) + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
+   alignas(8) char small[1024];
+   std::vector<char> big;
+   char* const kbuf = kbytes <= sizeof small ? small : (big.resize(kbytes), big.data());
+   std::memset(kbuf, 0, kbytes);
+   const unsigned groups = (unsigned)((n_streams + v.P - 1) / v.P);
+   const PcmArgsHeader h{in, out, state, params, (unsigned long long)n_streams, n_samples, groups};
+   std::memcpy(kbuf, &h, sizeof h);
+   {
+      std::lock_guard<std::mutex> lock(p->mu);
+      if (!g.consts.empty()) std::memcpy(kbuf + sizeof h, g.consts.data(), sizeof(float) * g.consts.size());
+   }
+   size_t size = kbytes;
+   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+   const unsigned grid = (groups + v.block - 1) / v.block;
+   FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+   return FZ_OK;
+}
+
+// a string result of the inspection calls: the length, at most cap bytes written; an error code (negative) on failure
+template <class Fn>
+static long pcm16_string(char* buf, size_t cap, Fn make)
+{
+   try {
+      const std::string s = make();
+      if (buf && cap) {
+         const size_t n = std::min(cap - 1, s.size());
+         std::memcpy(buf, s.data(), n);
+         buf[n] = 0;
+      }
+      return (long)s.size();
+   } catch (const fz::Error& er) {
+      set_error(er.msg);
+      return er.code;
+   }
+}
+
+}  // namespace fz
+
+using namespace fz;
+
+extern "C" {
+
+int fz_program_pcm16_check(const fz_program* p)
+{
+   FZ_GUARD(
+      if (!p) fail(FZ_E_INVALID, "null program");
+      require_supported(p->g);
+      return FZ_OK;)
+}
+
+int fz_run_block_pcm16(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams, uint32_t n_samples,
+                       uint32_t in_type, uint32_t out_type, void* hip_stream)
+{
+   FZ_GUARD(return launch_pcm16(p, in, out, state, params, n_streams, n_samples, in_type, out_type, hip_stream);)
+}
+
+int fz_program_pcm16_resources(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!out) fail(FZ_E_INVALID, "fz_program_pcm16_resources: bad arguments");
+      const Variant v = pcm16_variant(p, in_type, out_type, n_streams);
+      const auto k = get_kernel(p, v, nullptr);
+      *out = fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills,
+                                 k->res.sgpr_spills, v.U};
+      return FZ_OK;)
+}
+
+long fz_program_pcm16_kernel_symbol(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, char* buf, size_t cap)
+{
+   return pcm16_string(buf, cap, [&] {
+      const Variant v = pcm16_variant(p, in_type, out_type, n_streams);
+      return kernel_symbol(p->g, v);
+   });
+}
+
+long fz_program_pcm16_source(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, char* buf, size_t cap)
+{
+   return pcm16_string(buf, cap, [&] {
+      const Variant v = pcm16_variant(p, in_type, out_type, n_streams);
+      return full_source(p->g, v);
+   });
+}
+
+}  // extern "C"

@@ -602,6 +602,78 @@ class Program:
                            torch.cuda.current_stream().cuda_stream, tile)
         return out, state
 
+    # -- 16-bit PCM frames (fz_run_block_pcm16) ------------------------------------------------------
+    def pcm16_supported(self) -> bool:
+        """True when fz_run_block_pcm16 takes this program (pcm16_unsupported_reason() says why not)."""
+        return C.lib.fz_program_pcm16_check(self._h) == C.FZ_OK
+
+    def pcm16_unsupported_reason(self) -> str:
+        return "" if self.pcm16_supported() else C.last_error()
+
+    @staticmethod
+    def _frame_type(dtype, what):
+        """FZ_FRAMES_* of a torch / numpy dtype or of the strings "int16" / "float32" """
+        name = str(dtype).replace("torch.", "").replace("<class 'numpy.", "").replace("'>", "")
+        _require(name in ("int16", "float32"), f"{what}: frames are int16 or float32, not {dtype}")
+        return C.FZ_FRAMES_I16 if name == "int16" else C.FZ_FRAMES_F32
+
+    def pcm16_resources(self, in_dtype="int16", out_dtype="int16", n_streams: int = 0) -> dict:
+        """registers / scratch bytes of the PCM kernel a block of these frame types and this stream count (0: 2^20) runs (JITs it; needs
+        no GPU); 'unroll' = rows per chunk"""
+        r = C.KernelResources()
+        C.check(C.lib.fz_program_pcm16_resources(self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"),
+                                                 int(n_streams), ctypes.byref(r)))
+        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+    def pcm16_kernel_symbol(self, in_dtype="int16", out_dtype="int16", n_streams: int = 0) -> str:
+        buf = ctypes.create_string_buffer(160)
+        C.check(C.lib.fz_program_pcm16_kernel_symbol(self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"),
+                                                     int(n_streams), buf, 160))
+        return buf.value.decode()
+
+    def pcm16_source(self, in_dtype="int16", out_dtype="int16", n_streams: int = 0) -> str:
+        """the PCM kernel's whole source: generated configuration and body, the common head, the PCM frame walk"""
+        it, ot = self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype")
+        n = C.check(C.lib.fz_program_pcm16_source(self._h, it, ot, int(n_streams), None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        C.check(C.lib.fz_program_pcm16_source(self._h, it, ot, int(n_streams), buf, n + 1))
+        return buf.value.decode()
+
+    def run_block_pcm16(self, x, state=None, params=None, out=None, out_dtype=None):
+        """run_block with 16-bit PCM frames on one side or on both: x is a CUDA int16 or float32 tensor [T, n_streams, n_in] (or
+        [T, n_streams] for one wire), the output int16 or float32 as out_dtype says (default: x.dtype); one side at least is int16.
+        In: x = q / 32768, exact.  Out: y * 32768 rounded to nearest, ties to even, saturated to [-32768, 32767], NaN -> 0
+        (include/flowz_hip.h states the rule).  out may be x itself when both sides are int16 and n_out == n_in.
+        state / params as for run_block; returns (out, state)."""
+        import torch
+
+        if not x.is_cuda:
+            raise NoDeviceError(C.FZ_E_NO_DEVICE, "run_block_pcm16 needs CUDA (ROCm) tensors: zignal_amd has no CPU path")
+        if x.dim() == 2:
+            x = x.unsqueeze(-1)
+        it = self._frame_type(x.dtype, "x")
+        _require(x.dim() == 3 and x.is_contiguous() and x.shape[-1] == _bi.max(self.n_in, 1),
+                 f"x: expected contiguous frames [T, n_streams, {self.n_in}], got {tuple(x.shape)}")
+        T, ns, _ = x.shape
+        odt = x.dtype if out_dtype is None else out_dtype
+        ot = self._frame_type(odt, "out_dtype")
+        odt = torch.int16 if ot == C.FZ_FRAMES_I16 else torch.float32
+        if out is None:
+            out = torch.empty((T, ns, self.n_out), dtype=odt, device=x.device)
+        _check_dev(out, (T, ns, self.n_out), "out", odt)
+        if state is None:
+            state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
+        if self.n_state:
+            _check_dev(state, (self.n_state, ns), "state")
+        pp = None
+        if self.n_param:
+            if params is None:
+                raise FlowzError(C.FZ_E_INVALID, f"params: the graph has {self.n_param} per-stream coefficient(s), none given")
+            pp = _check_dev(params, (self.n_param, ns), "params").data_ptr()
+        C.check(C.lib.fz_run_block_pcm16(self._h, x.data_ptr() if self.n_in else None, out.data_ptr(), state.data_ptr() if self.n_state else None,
+                                         pp, ns, T, it, ot, torch.cuda.current_stream().cuda_stream))
+        return out, state
+
     # -- the backward of a block (fz_run_block_grad) ------------------------------------------------
     GRAD_WANT = ("x", "state", "params", "consts")
 
@@ -861,6 +933,33 @@ class Bank:
         _require(out.dtype == want_dt, (out.dtype, want_dt))
         fn = C.lib.fz_bank_process_host_f64 if out_f64 else C.lib.fz_bank_process_host
         C.check(fn(self._h, xp if self.prog.n_in else None, op, T))
+        return out
+
+    def process_host_pcm16(self, x, out=None):
+        """process_host for a caller that holds interleaved 16-bit PCM: int16 frames [T, n_streams, n_in] (or [T, n_streams]) in,
+        int16 frames [T, n_streams, n_out] out -- numpy arrays or CPU torch tensors, half the PCIe bytes of process_host each way;
+        the conversion rule of run_block_pcm16."""
+        import numpy as np
+
+        is_torch = hasattr(x, "data_ptr")
+        T = int(x.shape[0])
+        if is_torch:
+            import torch
+            _require(x.dtype == torch.int16 and x.is_contiguous() and not x.is_cuda, "x: wrong shape, dtype, layout or device for this call")
+            if out is None:
+                out = torch.empty((T, self.n_streams, self.prog.n_out), dtype=torch.int16, pin_memory=x.is_pinned())
+            xp, op = x.data_ptr(), out.data_ptr()
+        else:
+            _require(np.asarray(x).dtype == np.int16, "x: int16 frames expected")
+            x = np.ascontiguousarray(x)
+            if out is None:
+                out = np.empty((T, self.n_streams, self.prog.n_out), np.int16)
+            xp, op = x.ctypes.data, out.ctypes.data
+        _require(tuple(x.shape[1:]) in ((self.n_streams, self.prog.n_in), (self.n_streams,)) or self.prog.n_in == 0, "x: wrong shape, dtype, layout or device for this call")
+        _require(tuple(out.shape) == (T, self.n_streams, self.prog.n_out) and (out.is_contiguous() if is_torch else out.flags.c_contiguous), "out: wrong shape, dtype, layout or device for this call")
+        _require((out.dtype == torch.int16) if is_torch else (out.dtype == np.int16), "out: int16 frames expected")
+        _require(x.ndim == 3 or self.prog.n_in <= 1, "x: [T, n_streams] only for one input wire")
+        C.check(C.lib.fz_bank_process_host_pcm16(self._h, xp if self.prog.n_in else None, op, T))
         return out
 
 
