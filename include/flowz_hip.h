@@ -577,8 +577,21 @@ long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_
  *
  * Scope: fz_compile programs that are float32 throughout and whose delay lines live in registers (max_delay <= 8).  Typed programs,
  * float64 nodes, complex wires, modulators and delay lines in LDS or HBM rings are FZ_E_UNSUPPORTED, fz_last_error() names which
- * (fz_program_pcm16_check asks without a device).  Not built: stream-tiled and stream-major PCM frames, windows, 24-bit and
- * float16 frames, dither, PCM in the backward, fz_program_tune for this kernel (its plan is static).
+ * (fz_program_pcm16_check asks without a device).
+ *
+ * STREAM-MAJOR buffers -- a [batch, time] int16 tensor as it lies: fz_run_block_pcm16_stream_major is fz_run_block_stream_major with
+ * a frame type per side.  in [n_streams][rows_total][n_in], out [n_streams][rows_total][n_out]; the block is the window of rows
+ * [row0, row0 + n_samples), rows outside it are never written.  Same rule, same state: float32 blocks, time-major PCM blocks and
+ * stream-major PCM blocks chain on one state buffer, and a float32 output equals fz_run_block_stream_major on the converted input
+ * bit for bit.  n_samples is free.  THE ALIGNMENT RULE: frames travel as 16-byte pieces, so every stream's buffer and the window's
+ * first row start on that grid -- rows_total * wires and row0 * wires are multiples of 8 on an int16 side and of 4 on a float32
+ * side, else FZ_E_INVALID (fz_last_error() names the side and the multiple).  Checks, in this order and before a device is needed:
+ * the scope above; the frame types; an empty block is FZ_OK; row0 + n_samples <= rows_total; the alignment rule; pointers 16-byte
+ * aligned, `in` / `out` NULL iff that side has no wires; in == out allowed with int16 on both sides and n_in == n_out, every other
+ * overlap of the two whole buffers FZ_E_INVALID; 2^30 streams or more FZ_E_UNSUPPORTED.
+ *
+ * Not built: stream-tiled PCM frames, windows of time-major PCM frames, 24-bit and float16 frames, dither, PCM in the backward,
+ * fz_program_tune for these kernels (their plans are static).
  * ---------------------------------------------------------------------------------------- */
 enum { FZ_FRAMES_F32 = 0, FZ_FRAMES_I16 = 1 };
 /* FZ_OK, or FZ_E_UNSUPPORTED with the reason in fz_last_error(); host only */
@@ -592,6 +605,15 @@ int  fz_run_block_pcm16(fz_program* p, const void* in, void* out, float* state, 
 int  fz_program_pcm16_resources(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, fz_kernel_resources* out);
 long fz_program_pcm16_kernel_symbol(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, char* buf, size_t cap);
 long fz_program_pcm16_source(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, char* buf, size_t cap);
+int  fz_run_block_pcm16_stream_major(fz_program* p, const void* in, void* out, float* state, const float* params,
+                                     uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
+                                     uint32_t in_type, uint32_t out_type, void* hip_stream);
+/* The kernel a stream-major block of (in_type, out_type) runs, without a device: its registers, scratch and LDS (`unroll` = rows per
+ * chunk; lds_bytes = 64 * (rows * (n_in * ie + n_out * oe) + 16), ie / oe = 2 for int16 and 4 for float32), its symbol
+ * fz_pcm16_sm_kernel_i<0|1>o<0|1>u<rows per chunk>b<lanes per workgroup>_g<graph tag>, and its whole source. */
+int  fz_program_pcm16_stream_major_resources(fz_program* p, uint32_t in_type, uint32_t out_type, fz_kernel_resources* out);
+long fz_program_pcm16_stream_major_kernel_symbol(fz_program* p, uint32_t in_type, uint32_t out_type, char* buf, size_t cap);
+long fz_program_pcm16_stream_major_source(fz_program* p, uint32_t in_type, uint32_t out_type, char* buf, size_t cap);
 
 /* ------------------------------------------------------------------------------------------
  * fz_bank -- device-resident closure state for n_streams streams: the `state_` member of
@@ -638,6 +660,12 @@ int  fz_bank_process_host_f64(fz_bank* b, const float* in_host, double* out_host
 int  fz_bank_process_pcm16(fz_bank* b, const void* in_dev, void* out_dev, uint32_t n_samples, uint32_t in_type, uint32_t out_type,
                            void* hip_stream);
 int  fz_bank_process_host_pcm16(fz_bank* b, const int16_t* in_host, int16_t* out_host, uint32_t n_samples);
+/* fz_run_block_pcm16_stream_major on the bank's state, and fz_bank_process_host_stream_major for a caller that holds [batch, time]
+ * int16: host buffers in [n_streams][n_samples][n_in] -> out [n_streams][n_samples][n_out], any n_samples (the 2-D copies take any
+ * host pitch), time chunks of whole 32 rows in compact int16 device patches, the same three streams */
+int  fz_bank_process_pcm16_stream_major(fz_bank* b, const void* in_dev, void* out_dev, uint32_t rows_total, uint32_t row0,
+                                        uint32_t n_samples, uint32_t in_type, uint32_t out_type, void* hip_stream);
+int  fz_bank_process_host_pcm16_stream_major(fz_bank* b, const int16_t* in_host, int16_t* out_host, uint32_t n_samples);
 
 /* ------------------------------------------------------------------------------------------
  * Device utilities used by the measurement harness (bench.py) and tests.

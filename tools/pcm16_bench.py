@@ -11,7 +11,12 @@ the same run, and the kernel.
 
 The host path the same way: Bank.process_host_pcm16 against Bank.process_host on pinned host frames, alternating.
 
-usage: tools/pcm16_bench.py [--steps K] [--shapes large|small|all] [--host-rows T] [--out FILE]
+--layout stream-major times the same cases on stream-major buffers [stream][row][wire] (a [batch, time] tensor as it lies):
+Program.run_block_pcm16_stream_major against Program.run_block_stream_major, Bank.process_host_pcm16_stream_major against
+Bank.process_host_stream_major; uniform noise at half of full scale as the signal; the record goes to
+profiles/r10/pcm16_stream_major.txt.  Without the option nothing changes.
+
+usage: tools/pcm16_bench.py [--steps K] [--shapes large|small|all] [--host-rows T] [--layout time-major|stream-major] [--out FILE]
 """
 import argparse
 import datetime
@@ -56,20 +61,35 @@ def device_cases(a, torch, prog):
     say(f"# device path: one block per launch, HIP events, {a.steps} launches per case and pass, a forward and a backward pass over the cases")
     say(f"{'streams x T':>16s} {'case':>9s} {'ms':>8s} {'min':>8s} {'max':>8s} {'GSamples/s':>11s} {'B/sample':>9s} {'of 8 TB/s':>10s} {'vs f32':>7s}  kernel")
     shapes = SHAPES["large"] + SHAPES["small"] if a.shapes == "all" else SHAPES[a.shapes]
+    sm = a.layout == "stream-major"
     for ns, T in shapes:
-        xf = torch.empty((T, ns, 1), dtype=torch.float32, device="cuda")
-        F.synth_fill(xf, seed=W.SEED)
-        xq = torch.empty((T, ns, 1), dtype=torch.int16, device="cuda")
-        for t0 in range(0, T, 256):                          # the same signal on both sides: q = round(32767 x), x = q / 32768
-            xq[t0:t0 + 256] = torch.round(xf[t0:t0 + 256] * 32767.0).to(torch.int16)
-            xf[t0:t0 + 256] = xq[t0:t0 + 256].to(torch.float32) * (1.0 / 32768.0)
-        yf = torch.empty((T, ns, 1), dtype=torch.float32, device="cuda")
-        yq = torch.empty((T, ns, 1), dtype=torch.int16, device="cuda")
+        shape = (ns, T, 1) if sm else (T, ns, 1)
+        xf = torch.empty(shape, dtype=torch.float32, device="cuda")
+        xq = torch.empty(shape, dtype=torch.int16, device="cuda")
+        if sm:
+            torch.manual_seed(W.SEED)
+            step = 16384                                     # streams per slice
+            for i in range(0, ns, step):
+                xf[i:i + step].uniform_(-0.5, 0.5)
+        else:
+            F.synth_fill(xf, seed=W.SEED)
+            step = 256                                       # rows per slice
+        for t0 in range(0, shape[0], step):                  # the same signal on both sides: q = round(32767 x), x = q / 32768
+            xq[t0:t0 + step] = torch.round(xf[t0:t0 + step] * 32767.0).to(torch.int16)
+            xf[t0:t0 + step] = xq[t0:t0 + step].to(torch.float32) * (1.0 / 32768.0)
+        yf = torch.empty(shape, dtype=torch.float32, device="cuda")
+        yq = torch.empty(shape, dtype=torch.int16, device="cuda")
         s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
         legs, names = {}, {}
         for case, it, ot in CASES:
             x, y = (xq if it == "int16" else xf), (yq if ot == "int16" else yf)
-            if case == "f32->f32":
+            if case == "f32->f32" and sm:
+                legs[case] = lambda x=x, y=y: prog.run_block_stream_major(x, state=s0, out=y)
+                names[case] = prog.kernel_symbol(F.make_variant(0, 0, 0, F.C.FZ_VF_STREAM_MAJOR), ns, T)
+            elif sm:
+                legs[case] = lambda x=x, y=y, ot=ot: prog.run_block_pcm16_stream_major(x, state=s0, out=y, out_dtype=ot)
+                names[case] = prog.pcm16_stream_major_kernel_symbol(it, ot)
+            elif case == "f32->f32":
                 legs[case] = lambda x=x, y=y: prog.run_block(x, state=s0, out=y)
                 names[case] = prog.kernel_symbol(None, ns, T)
             else:
@@ -102,12 +122,17 @@ def host_cases(a, torch, prog):
     say()
     say(f"# host path: pinned host frames in and out, wall clock around each call (it returns when the output is on the host), {a.steps} calls each, alternating")
     say(f"{'streams x T':>16s} {'call':>20s} {'ms':>9s} {'min':>9s} {'max':>9s} {'GSamples/s':>11s} {'PCIe B/sample':>14s} {'vs float32':>11s}")
-    q = torch.from_numpy(np.random.default_rng(1).integers(-32768, 32768, (T, ns, 1), dtype=np.int16)).pin_memory()
+    sm = a.layout == "stream-major"
+    shape = (ns, T, 1) if sm else (T, ns, 1)
+    q = torch.from_numpy(np.random.default_rng(1).integers(-32768, 32768, shape, dtype=np.int16)).pin_memory()
     x = (q.to(torch.float32) * (1.0 / 32768.0)).pin_memory()
-    oq = torch.empty((T, ns, 1), dtype=torch.int16).pin_memory()
-    of = torch.empty((T, ns, 1), dtype=torch.float32).pin_memory()
+    oq = torch.empty(shape, dtype=torch.int16).pin_memory()
+    of = torch.empty(shape, dtype=torch.float32).pin_memory()
     bq, bf = prog.bank(ns), prog.bank(ns)
-    legs = {"process_host": lambda: bf.process_host(x, out=of), "process_host_pcm16": lambda: bq.process_host_pcm16(q, out=oq)}
+    if sm:
+        legs = {"process_host": lambda: bf.process_host_stream_major(x, out=of), "process_host_pcm16": lambda: bq.process_host_pcm16_stream_major(q, out=oq)}
+    else:
+        legs = {"process_host": lambda: bf.process_host(x, out=of), "process_host_pcm16": lambda: bq.process_host_pcm16(q, out=oq)}
     for f in legs.values():
         f()
     got = {k: [] for k in legs}
@@ -129,19 +154,23 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--shapes", choices=("large", "small", "all"), default="all")
     ap.add_argument("--host-rows", type=int, default=2048)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09", "pcm16.txt"))
+    ap.add_argument("--layout", choices=("time-major", "stream-major"), default="time-major")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    sm = a.layout == "stream-major"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "r10", "pcm16_stream_major.txt") if sm else os.path.join(ROOT, "profiles", "r09", "pcm16.txt")
     import torch
 
     assert torch.cuda.is_available(), "pcm16_bench needs an MI355X: there is nothing to time without one"
     torch.cuda.set_device(0)
     props = torch.cuda.get_device_properties(0)
     prog = F.compile(F.from_sexpr(W.df1_cascade(6)))
-    say("# 16-bit PCM frames against the float32 default: the 6-biquad cascade, time-major frames (tools/pcm16_bench.py)")
+    say(f"# 16-bit PCM frames against the float32 default: the 6-biquad cascade, {'stream-major buffers' if sm else 'time-major frames'} (tools/pcm16_bench.py{' --layout stream-major' if sm else ''})")
     say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
     for it, ot in (("int16", "int16"), ("int16", "float32"), ("float32", "int16")):
-        r = prog.pcm16_resources(it, ot, 1 << 20)
-        say(f"# {prog.pcm16_kernel_symbol(it, ot, 1 << 20)}: {r['vgprs'] + r['agprs']} vgprs, {r['sgprs']} sgprs, {r['lds_bytes']} B LDS, {r['scratch_bytes']} B scratch, chunks of {r['unroll']} rows")
+        r = prog.pcm16_stream_major_resources(it, ot) if sm else prog.pcm16_resources(it, ot, 1 << 20)
+        say(f"# {prog.pcm16_stream_major_kernel_symbol(it, ot) if sm else prog.pcm16_kernel_symbol(it, ot, 1 << 20)}: {r['vgprs'] + r['agprs']} vgprs, {r['sgprs']} sgprs, {r['lds_bytes']} B LDS, {r['scratch_bytes']} B scratch, chunks of {r['unroll']} rows")
     device_cases(a, torch, prog)
     host_cases(a, torch, prog)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

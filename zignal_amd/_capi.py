@@ -170,6 +170,12 @@ def _load():
         "fz_program_pcm16_source": (ctypes.c_long, [P, u32, u32, u64, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_bank_process_pcm16": (ctypes.c_int, [P, P, P, u32, u32, u32, P]),
         "fz_bank_process_host_pcm16": (ctypes.c_int, [P, P, P, u32]),
+        "fz_run_block_pcm16_stream_major": (ctypes.c_int, [P, P, P, P, P, u64, u32, u32, u32, u32, u32, P]),
+        "fz_program_pcm16_stream_major_resources": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_pcm16_stream_major_kernel_symbol": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_pcm16_stream_major_source": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_bank_process_pcm16_stream_major": (ctypes.c_int, [P, P, P, u32, u32, u32, u32, u32, P]),
+        "fz_bank_process_host_pcm16_stream_major": (ctypes.c_int, [P, P, P, u32]),
         "fz_device_count": (ctypes.c_int, []),
         "fz_synth_fill": (ctypes.c_int, [P, u64, u32, u32, u32, u64, u64, u32, P]),
         "fz_rbj_lowpass": (ctypes.c_int, [P, P, f32, u64, P, P, P]),

@@ -1,6 +1,7 @@
 // fz_bank: the closure's state_ member (flowz.hpp:1190-1191) for n_streams streams, resident in HBM, and the
 // host-frames paths (the reference's per-sample call protocol; long blocks through a three-stream H2D / kernel / D2H pipeline).
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 
@@ -296,19 +297,26 @@ int fz_bank_process_host(fz_bank* b, const float* in_host, float* out_host, uint
 // ([n_streams][n_samples][wires]).  Time chunks travel as 2-D copies (one row per stream) into compact
 // device patches [n_streams][chunk][wires], run through the stream-major kernel and travel back; the
 // same three-stream pipeline as the frame path.
-int fz_bank_process_host_stream_major(fz_bank* b, const float* in_host, float* out_host, uint32_t n_samples)
+// (pcm: int16 samples on both sides through int16 staging and the stream-major PCM kernel -- fz_bank_process_host_pcm16_stream_major;
+//  chunks of whole 32 rows keep every device patch on the 16-byte grid of that kernel's pieces)
+static int bank_process_host_stream_major(fz_bank* b, const void* in_host, void* out_host, uint32_t n_samples, bool pcm)
 {
    FZ_GUARD(
       if (!b || !out_host || !n_samples) fail(FZ_E_INVALID, "fz_bank_process_host_stream_major: bad arguments");
+      const size_t es = pcm ? 2 : 4;                          // bytes per sample
       check_bank_device(b);
       const Graph& g = b->prog->g;
       if (g.n_in && !in_host) fail(FZ_E_INVALID, "in_host is null but the graph has input wires");
       const uint32_t nw = std::max<uint32_t>(std::max(g.n_in, g.n_out), 1);
-      constexpr size_t kChunkBytes = 32u << 20;
-      uint32_t chunk_t = (uint32_t)std::max<size_t>(32, kChunkBytes / ((size_t)b->n_streams * nw * 4) / 32 * 32);
+      // (developer switch FLOWZ_HIP_HOST_CHUNK_BYTES: another chunk size, so that a test reaches the pipeline's second and third chunk
+      //  with kilobytes instead of 64 MiB)
+      size_t kChunkBytes = 32u << 20;
+      if (const char* e = std::getenv("FLOWZ_HIP_HOST_CHUNK_BYTES"))
+         if (const unsigned long long n = std::strtoull(e, nullptr, 10)) kChunkBytes = (size_t)n;
+      uint32_t chunk_t = (uint32_t)std::max<size_t>(32, kChunkBytes / ((size_t)b->n_streams * nw * es) / 32 * 32);
       chunk_t = std::min(chunk_t, (n_samples + 31u) / 32u * 32u);
-      const size_t ipitch = (size_t)chunk_t * g.n_in * 4, opitch = (size_t)chunk_t * g.n_out * 4;     // device rows
-      const size_t hip = (size_t)n_samples * g.n_in * 4, hop = (size_t)n_samples * g.n_out * 4;       // host rows
+      const size_t ipitch = (size_t)chunk_t * g.n_in * es, opitch = (size_t)chunk_t * g.n_out * es;     // device rows
+      const size_t hip = (size_t)n_samples * g.n_in * es, hop = (size_t)n_samples * g.n_out * es;       // host rows
       ensure_stage(b, 2 * ipitch * b->n_streams, 2 * opitch * b->n_streams);
       if (!b->s_h2d) {
          FZ_HIP(hipStreamCreateWithFlags(&b->s_h2d, hipStreamNonBlocking));
@@ -332,7 +340,7 @@ int fz_bank_process_host_stream_major(fz_bank* b, const float* in_host, float* o
          float* dout = reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_out) + (size_t)slot * opitch * b->n_streams);
          if (g.n_in) {
             if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_h2d, b->ev_run[slot], 0));
-            FZ_HIP(hipMemcpy2DAsync(din, ipitch, hin + (size_t)t0 * g.n_in * 4, hip, (size_t)nt * g.n_in * 4, b->n_streams,
+            FZ_HIP(hipMemcpy2DAsync(din, ipitch, hin + (size_t)t0 * g.n_in * es, hip, (size_t)nt * g.n_in * es, b->n_streams,
                                     hipMemcpyHostToDevice, b->s_h2d));
             FZ_HIP(hipEventRecord(b->ev_in[slot], b->s_h2d));
             FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_in[slot], 0));
@@ -340,8 +348,12 @@ int fz_bank_process_host_stream_major(fz_bank* b, const float* in_host, float* o
          if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_out[slot], 0));
          int rc = FZ_OK;
          try {
-            rc = fz::launch(b->prog, g.n_in ? din : nullptr, dout, g.n_state ? b->state : nullptr, b->params, b->n_streams, nt, &sm,
-                            b->s_run, 0, chunk_t, 0, t0);
+            if (pcm)
+               rc = fz::launch_pcm16_sm(b->prog, g.n_in ? din : nullptr, g.n_out ? dout : nullptr, g.n_state ? b->state : nullptr, b->params,
+                                        b->n_streams, chunk_t, 0, nt, FZ_FRAMES_I16, FZ_FRAMES_I16, b->s_run);
+            else
+               rc = fz::launch(b->prog, g.n_in ? din : nullptr, dout, g.n_state ? b->state : nullptr, b->params, b->n_streams, nt, &sm,
+                               b->s_run, 0, chunk_t, 0, t0);
          } catch (...) {
             drain_pipeline(b);
             throw;
@@ -352,13 +364,18 @@ int fz_bank_process_host_stream_major(fz_bank* b, const float* in_host, float* o
          }
          FZ_HIP(hipEventRecord(b->ev_run[slot], b->s_run));
          FZ_HIP(hipStreamWaitEvent(b->s_d2h, b->ev_run[slot], 0));
-         FZ_HIP(hipMemcpy2DAsync(hout + (size_t)t0 * g.n_out * 4, hop, dout, opitch, (size_t)nt * g.n_out * 4, b->n_streams,
+         FZ_HIP(hipMemcpy2DAsync(hout + (size_t)t0 * g.n_out * es, hop, dout, opitch, (size_t)nt * g.n_out * es, b->n_streams,
                                  hipMemcpyDeviceToHost, b->s_d2h));
          FZ_HIP(hipEventRecord(b->ev_out[slot], b->s_d2h));
       }
       FZ_HIP(hipStreamSynchronize(b->s_d2h));
       FZ_HIP(hipStreamSynchronize(b->s_run));
       return FZ_OK;)
+}
+
+int fz_bank_process_host_stream_major(fz_bank* b, const float* in_host, float* out_host, uint32_t n_samples)
+{
+   return bank_process_host_stream_major(b, in_host, out_host, n_samples, false);
 }
 
 int fz_bank_process_host_f64(fz_bank* b, const float* in_host, double* out_host, uint32_t n_samples)
@@ -383,6 +400,26 @@ int fz_bank_process_host_pcm16(fz_bank* b, const int16_t* in_host, int16_t* out_
       const std::string why = fz::pcm16_unsupported_reason(b->prog->g);
       if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);)
    return bank_process_host(b, in_host, out_host, n_samples, HostFrames::Pcm16);
+}
+
+int fz_bank_process_pcm16_stream_major(fz_bank* b, const void* in_dev, void* out_dev, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
+                                       uint32_t in_type, uint32_t out_type, void* hip_stream)
+{
+   FZ_GUARD(
+      if (!b) fail(FZ_E_INVALID, "null bank");
+      check_bank_device(b);
+      const Graph& g = b->prog->g;
+      return fz::launch_pcm16_sm(b->prog, in_dev, out_dev, g.n_state ? b->state : nullptr, b->params, b->n_streams, rows_total, row0, n_samples,
+                                 in_type, out_type, hip_stream);)
+}
+
+int fz_bank_process_host_pcm16_stream_major(fz_bank* b, const int16_t* in_host, int16_t* out_host, uint32_t n_samples)
+{
+   FZ_GUARD(
+      if (!b) fail(FZ_E_INVALID, "null bank");
+      const std::string why = fz::pcm16_unsupported_reason(b->prog->g);
+      if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);)
+   return bank_process_host_stream_major(b, in_host, out_host, n_samples, true);
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@ extern const char* const kSkeletonBody_frames;
 extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a kernel text of its own
 extern const char* const kSkeletonAdjointSm; // fz_kernel_adjoint_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
+extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
 // the hand-written text of a variant's kernel: the common head + the ONE body its flags (stream-major: and its streams per lane) select
 const std::string& skeleton_source(const Variant& v)
@@ -35,9 +36,9 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string head = kSkeletonHead, sm = head + kSkeletonBody_sm_common;
    static const std::string sm_pair = sm + kSkeletonBody_sm_pair, sm_long = sm + kSkeletonBody_sm_long, sm_short = sm + kSkeletonBody_sm_short,
                             ws = head + kSkeletonBody_wave_split, fr = head + kSkeletonBody_frames;
-   static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm, pcm = head + kSkeletonPcm16;
+   static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm, pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
    if (v.flags & FZ_VF_ADJOINT) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_sm : adj;
-   if (v.flags & FZ_VF_PCM16) return pcm;
+   if (v.flags & FZ_VF_PCM16) return (v.flags & FZ_VF_PCM16_SM) ? pcm_sm : pcm;
    if (v.flags & FZ_VF_STREAM_MAJOR) return !(v.flags & FZ_VF_SM_LONG) ? sm_short : v.P == 2 ? sm_pair : sm_long;
    return ws_parts(v.flags) ? ws : fr;
 }
@@ -49,6 +50,9 @@ std::string kernel_name(const Graph& g, const Variant& v)
    if (v.flags & FZ_VF_ADJOINT_SM)
       return "fz_adjoint_sm_kernel_c" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block);
    if (v.flags & FZ_VF_ADJOINT) return "fz_adjoint_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
+   if ((v.flags & FZ_VF_PCM16) && (v.flags & FZ_VF_PCM16_SM))   // (stream-major PCM: which side is int16, rows per chunk, lanes)
+      return "fz_pcm16_sm_kernel_i" + std::to_string((v.flags & FZ_VF_PCM16_IN) ? 1 : 0) + "o" + std::to_string((v.flags & FZ_VF_PCM16_OUT) ? 1 : 0) + "u" +
+             std::to_string(v.U) + "b" + std::to_string(v.block);
    // (PCM frames: which side is int16, then h = 2-byte accesses -- int16 rows off the dword grid --, m = merging stores)
    if (v.flags & FZ_VF_PCM16)
       return "fz_pcm16_kernel_i" + std::to_string((v.flags & FZ_VF_PCM16_IN) ? 1 : 0) + "o" + std::to_string((v.flags & FZ_VF_PCM16_OUT) ? 1 : 0) + "p" +

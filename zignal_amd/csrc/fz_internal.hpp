@@ -191,6 +191,10 @@ constexpr uint32_t FZ_VF_ADJOINT_SM = 1u << 18;
 // with every other; the forward planner never sees it (fz_pcm16.cpp: pcm16_plan is the one place that makes one).
 constexpr uint32_t FZ_VF_PCM16 = 1u << 12;
 constexpr uint32_t FZ_VF_PCM16_IN = 1u, FZ_VF_PCM16_OUT = 2u, FZ_VF_PCM16_B16 = 4u;
+// internal, with FZ_VF_PCM16: the PCM kernel for STREAM-MAJOR buffers (fz_kernel_pcm16_sm.hip.inc), a text and a symbol of its own; one
+// more of the reserved bits.  Such a Variant is {P = 1, U = rows per chunk, block = 64, flags = these two + the IN / OUT bits}
+// (fz_pcm16.cpp: pcm16_sm_chunk_rows is the one home of U).
+constexpr uint32_t FZ_VF_PCM16_SM = 1u << 13;
 constexpr uint32_t kChipCUs = 256;       // MI355X (gfx950): 8 XCDs x 32 CUs -- what chip_cus() answers on a box without a GPU
 unsigned chip_cus();                     // compute units of the current device (fz_launch.cpp)
 
@@ -251,6 +255,7 @@ bool adjoint_variant_fits(const Graph& g, const Variant& v);       // an adjoint
 // fz_run_block_pcm16 could have made for it
 std::string pcm16_unsupported_reason(const Graph& g);
 bool pcm16_variant_fits(const Graph& g, const Variant& v);
+bool pcm16_sm_variant_fits(const Graph& g, const Variant& v);      // ... that fz_run_block_pcm16_stream_major could have made
 
 // ---- runtime ---------------------------------------------------------------------------------------------
 // what the code object's metadata says the kernel needs (AMDGPU msgpack notes)
@@ -358,6 +363,9 @@ int launch(fz_program* p, const float* in, float* out, float* state, const float
 // fz_run_block_pcm16: argument checks, the static plan, the launch (fz_pcm16.cpp)
 int launch_pcm16(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams, uint32_t n_samples,
                  uint32_t in_type, uint32_t out_type, void* stream);
+// fz_run_block_pcm16_stream_major: the same for the window [row0, row0 + n_samples) of stream-major buffers
+int launch_pcm16_sm(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams, uint32_t rows_total,
+                    uint32_t row0, uint32_t n_samples, uint32_t in_type, uint32_t out_type, void* stream);
 int tune(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
          uint32_t n_samples, uint32_t tile_streams, void* stream, fz_variant* chosen, float* chosen_ms, bool implicit = false);
 std::vector<fz_variant> tune_candidates(const Graph& g, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams);

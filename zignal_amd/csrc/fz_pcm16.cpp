@@ -2,6 +2,8 @@
 // its static plan, argument checks and the launch.  The kernel text is the common head of fz_block_kernel.hip.inc, the generated body
 // of the frame kernels (gen_body) and fz_kernel_pcm16.hip.inc; the code objects go through the kernel cache as a Variant with
 // FZ_VF_PCM16.
+// The same for stream-major buffers (fz_run_block_pcm16_stream_major): fz_kernel_pcm16_sm.hip.inc behind the same head and body, a
+// Variant with FZ_VF_PCM16 | FZ_VF_PCM16_SM whose U carries the rows of a chunk (pcm16_sm_chunk_rows is their one home).
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -151,6 +153,139 @@ int launch_pcm16(fz_program* p, const void* in, void* out, float* state, const f
    return FZ_OK;
 }
 
+// ---- stream-major buffers --------------------------------------------------------------------------------------------------------
+constexpr uint32_t kPcmSmBlock = 64;             // one wave per workgroup: the LDS patch is wave-private and limits occupancy per wave
+constexpr uint32_t kPcmSmMaxRows = 64, kPcmSmMinRows = 8;   // rows per chunk (8 int16 samples are one 16-byte piece)
+constexpr uint32_t kPcmSmLdsBytes = 160u * 1024u, kPcmSmMinWaves = 4;   // a CU's LDS, and the waves that must fit into it
+
+// bytes of a wave's LDS patch at U rows per chunk: 64 rows of [U x n_in samples][U x n_out samples][16 bytes of padding]
+static uint32_t pcm16_sm_patch_bytes(const Graph& g, bool i16_in, bool i16_out, uint32_t U)
+{
+   return 64u * (U * (g.n_in * (i16_in ? 2u : 4u) + g.n_out * (i16_out ? 2u : 4u)) + 16u);
+}
+
+// Rows per chunk, the ONE rule: the shortest power of two at which a stream's run on every int16 side is a whole 128-byte line
+// (64 rows for one wire, 32 for two, 16 for four: half-line write runs are what HBM punishes), halved until four waves' patches
+// fit a CU's LDS; never below 8 rows.
+static uint32_t pcm16_sm_chunk_rows(const Graph& g, bool i16_in, bool i16_out)
+{
+   uint32_t wires = 0;                                     // the narrowest int16 side
+   if (i16_in && g.n_in) wires = g.n_in;
+   if (i16_out && g.n_out) wires = wires ? std::min(wires, g.n_out) : g.n_out;
+   uint32_t U = kPcmSmMaxRows;
+   while (wires && U > kPcmSmMinRows && (U / 2) * wires * 2u >= 128u) U /= 2;
+   while (U > kPcmSmMinRows && (uint64_t)pcm16_sm_patch_bytes(g, i16_in, i16_out, U) * kPcmSmMinWaves > kPcmSmLdsBytes) U /= 2;
+   return U;
+}
+
+static Variant pcm16_sm_plan(const Graph& g, uint32_t in_type, uint32_t out_type)
+{
+   const bool i16_in = in_type == FZ_FRAMES_I16, i16_out = out_type == FZ_FRAMES_I16;
+   Variant v;
+   v.P = 1;
+   v.U = pcm16_sm_chunk_rows(g, i16_in, i16_out);
+   v.block = kPcmSmBlock;
+   v.flags = FZ_VF_PCM16 | FZ_VF_PCM16_SM | (i16_in ? FZ_VF_PCM16_IN : 0u) | (i16_out ? FZ_VF_PCM16_OUT : 0u);
+   return v;
+}
+
+// could pcm16_sm_plan (and the halving of the chunk behind it) have made v for this graph?
+bool pcm16_sm_variant_fits(const Graph& g, const Variant& v)
+{
+   constexpr uint32_t sides = FZ_VF_PCM16_IN | FZ_VF_PCM16_OUT;
+   if ((v.flags & ~sides) != (FZ_VF_PCM16 | FZ_VF_PCM16_SM) || !(v.flags & sides)) return false;
+   if (!pcm16_unsupported_reason(g).empty()) return false;
+   if (v.P != 1 || v.block != kPcmSmBlock || v.U < kPcmSmMinRows || (v.U & (v.U - 1))) return false;
+   return v.U <= pcm16_sm_chunk_rows(g, (v.flags & FZ_VF_PCM16_IN) != 0, (v.flags & FZ_VF_PCM16_OUT) != 0);
+}
+
+// The variant that runs: the plan with its chunk halved while the kernel spills into scratch memory -- down to kPcmSmMinRows, one
+// int16 piece, and no further: a graph that spills even there runs that kernel as it is, spills and all, as the other kernels do
+// (settle_variant would go on to chunks the kernel text has no pieces for).
+static Variant pcm16_sm_settle(fz_program* p, Variant v)
+{
+   while (v.U > kPcmSmMinRows && get_kernel(p, v, nullptr)->res.scratch_bytes != 0) v.U /= 2;
+   return v;
+}
+
+// the kernel a stream-major block of these frame types runs
+static Variant pcm16_sm_variant(fz_program* p, uint32_t in_type, uint32_t out_type)
+{
+   if (!p) fail(FZ_E_INVALID, "null program");
+   require_supported(p->g);
+   check_types(in_type, out_type);
+   return pcm16_sm_settle(p, pcm16_sm_plan(p->g, in_type, out_type));
+}
+
+// kernarg image of `struct fz_pcm_sm_args` (fz_kernel_pcm16_sm.hip.inc) up to the coefficient tail
+struct PcmSmArgsHeader {
+   const void* in;
+   void* out;
+   float* state;
+   const float* params;
+   unsigned long long n_streams;
+   unsigned int n_samples;
+   unsigned int rows_total;
+   unsigned int row0;
+   unsigned int reserved0;
+};
+static_assert(sizeof(PcmSmArgsHeader) == 4 * 8 + 8 + 4 * 4, "PcmSmArgsHeader must match the head of the kernel's fz_pcm_sm_args without padding");
+
+int launch_pcm16_sm(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams, uint32_t rows_total,
+                    uint32_t row0, uint32_t n_samples, uint32_t in_type, uint32_t out_type, void* stream)
+{
+   if (!p) fail(FZ_E_INVALID, "null program");
+   const Graph& g = p->g;
+   require_supported(g);
+   check_types(in_type, out_type);
+   if (n_streams == 0 || n_samples == 0) return FZ_OK;      // an empty block: nothing to evaluate, nothing touched
+   if ((uint64_t)row0 + n_samples > rows_total) fail(FZ_E_INVALID, "the window [row0, row0 + n_samples) reaches past rows_total");
+   // the 16-byte grid of the pieces: every stream's buffer and the window's first row start on it
+   auto on_grid = [&](const char* side, uint32_t wires, uint32_t type) {
+      const uint64_t m = type == FZ_FRAMES_I16 ? 8u : 4u;
+      if (((uint64_t)rows_total * wires) % m || ((uint64_t)row0 * wires) % m)
+         fail(FZ_E_INVALID, std::string(side) + ": rows_total x wires and row0 x wires must be multiples of " + std::to_string(m) + " on " +
+                               (type == FZ_FRAMES_I16 ? "an int16" : "a float32") + " side (16-byte pieces)");
+   };
+   on_grid("in", g.n_in, in_type);
+   on_grid("out", g.n_out, out_type);
+   if ((g.n_in != 0) != (in != nullptr)) fail(FZ_E_INVALID, g.n_in ? "in is null but the graph has input wires" : "in must be null: the graph has no input wires");
+   if ((g.n_out != 0) != (out != nullptr)) fail(FZ_E_INVALID, g.n_out ? "out is null but the graph has output wires" : "out must be null: the graph has no output wires");
+   if (g.n_state && !state) fail(FZ_E_INVALID, "state is null but the graph has delay lines");
+   if (g.n_param && !params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
+   auto mis = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) != 0; };
+   if (mis(in) || mis(out) || mis(state) || mis(params)) fail(FZ_E_INVALID, "device pointers must be 16-byte aligned");
+   // in place: every piece and every row is read before the same bytes are written -- int16 on both sides, as many wires out as in
+   const uint64_t ibytes = n_streams * rows_total * g.n_in * bytes_of(in_type), obytes = n_streams * rows_total * g.n_out * bytes_of(out_type);
+   if (in && out && ibytes && obytes) {
+      const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+      const bool in_place = i0 == o0 && in_type == FZ_FRAMES_I16 && out_type == FZ_FRAMES_I16 && g.n_in == g.n_out;
+      if (!in_place && i0 < o0 + obytes && o0 < i0 + ibytes)
+         fail(FZ_E_INVALID, "in and out overlap: in place only with int16 frames on both sides, as many output wires as input wires and in == out");
+   }
+   if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams");
+   require_device();
+   const Variant v = pcm16_sm_settle(p, pcm16_sm_plan(g, in_type, out_type));
+   void* fn = nullptr;
+   (void)get_kernel(p, v, &fn);
+   const size_t kbytes = (sizeof(PcmSmArgsHeader) + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
+   alignas(8) char small[1024];
+   std::vector<char> big;
+   char* const kbuf = kbytes <= sizeof small ? small : (big.resize(kbytes), big.data());
+   std::memset(kbuf, 0, kbytes);
+   const PcmSmArgsHeader h{in, out, state, params, (unsigned long long)n_streams, n_samples, rows_total, row0, 0u};
+   std::memcpy(kbuf, &h, sizeof h);
+   {
+      std::lock_guard<std::mutex> lock(p->mu);
+      if (!g.consts.empty()) std::memcpy(kbuf + sizeof h, g.consts.data(), sizeof(float) * g.consts.size());
+   }
+   size_t size = kbytes;
+   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+   const unsigned grid = (unsigned)((n_streams + 63u) / 64u);           // one wave of 64 streams per workgroup
+   FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+   return FZ_OK;
+}
+
 // a string result of the inspection calls: the length, at most cap bytes written; an error code (negative) on failure
 template <class Fn>
 static long pcm16_string(char* buf, size_t cap, Fn make)
@@ -212,6 +347,39 @@ long fz_program_pcm16_source(fz_program* p, uint32_t in_type, uint32_t out_type,
 {
    return pcm16_string(buf, cap, [&] {
       const Variant v = pcm16_variant(p, in_type, out_type, n_streams);
+      return full_source(p->g, v);
+   });
+}
+
+int fz_run_block_pcm16_stream_major(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams,
+                                    uint32_t rows_total, uint32_t row0, uint32_t n_samples, uint32_t in_type, uint32_t out_type, void* hip_stream)
+{
+   FZ_GUARD(return launch_pcm16_sm(p, in, out, state, params, n_streams, rows_total, row0, n_samples, in_type, out_type, hip_stream);)
+}
+
+int fz_program_pcm16_stream_major_resources(fz_program* p, uint32_t in_type, uint32_t out_type, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!out) fail(FZ_E_INVALID, "fz_program_pcm16_stream_major_resources: bad arguments");
+      const Variant v = pcm16_sm_variant(p, in_type, out_type);
+      const auto k = get_kernel(p, v, nullptr);
+      *out = fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills,
+                                 k->res.sgpr_spills, v.U};
+      return FZ_OK;)
+}
+
+long fz_program_pcm16_stream_major_kernel_symbol(fz_program* p, uint32_t in_type, uint32_t out_type, char* buf, size_t cap)
+{
+   return pcm16_string(buf, cap, [&] {
+      const Variant v = pcm16_sm_variant(p, in_type, out_type);
+      return kernel_symbol(p->g, v);
+   });
+}
+
+long fz_program_pcm16_stream_major_source(fz_program* p, uint32_t in_type, uint32_t out_type, char* buf, size_t cap)
+{
+   return pcm16_string(buf, cap, [&] {
+      const Variant v = pcm16_sm_variant(p, in_type, out_type);
       return full_source(p->g, v);
    });
 }

@@ -674,6 +674,69 @@ class Program:
                                          pp, ns, T, it, ot, torch.cuda.current_stream().cuda_stream))
         return out, state
 
+    # -- 16-bit PCM frames on stream-major buffers (fz_run_block_pcm16_stream_major) -----------------
+    def pcm16_stream_major_resources(self, in_dtype="int16", out_dtype="int16") -> dict:
+        """registers / scratch / LDS bytes of the kernel a stream-major PCM block of these frame types runs (JITs it; needs no GPU);
+        'unroll' = rows per chunk"""
+        r = C.KernelResources()
+        C.check(C.lib.fz_program_pcm16_stream_major_resources(self._h, self._frame_type(in_dtype, "in_dtype"),
+                                                              self._frame_type(out_dtype, "out_dtype"), ctypes.byref(r)))
+        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+    def pcm16_stream_major_kernel_symbol(self, in_dtype="int16", out_dtype="int16") -> str:
+        buf = ctypes.create_string_buffer(160)
+        C.check(C.lib.fz_program_pcm16_stream_major_kernel_symbol(self._h, self._frame_type(in_dtype, "in_dtype"),
+                                                                  self._frame_type(out_dtype, "out_dtype"), buf, 160))
+        return buf.value.decode()
+
+    def pcm16_stream_major_source(self, in_dtype="int16", out_dtype="int16") -> str:
+        """that kernel's whole source: generated configuration and body, the common head, the stream-major PCM walk"""
+        it, ot = self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype")
+        n = C.check(C.lib.fz_program_pcm16_stream_major_source(self._h, it, ot, None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        C.check(C.lib.fz_program_pcm16_stream_major_source(self._h, it, ot, buf, n + 1))
+        return buf.value.decode()
+
+    def run_block_pcm16_stream_major(self, x, state=None, params=None, out=None, out_dtype=None, row0=0, n_samples=None):
+        """run_block_stream_major with 16-bit PCM frames on one side or on both: x is a CUDA int16 or float32 tensor
+        [n_streams, rows, n_in] (or [n_streams, rows] for one wire: a [batch, time] tensor as it lies), the output
+        [n_streams, rows, n_out] int16 or float32 as out_dtype says (default: x.dtype); one side at least is int16.  The block is
+        the window of rows [row0, row0 + n_samples) (default: to the end); rows of out outside it are not written.  The
+        conversion rule of run_block_pcm16.  rows * wires and row0 * wires are multiples of 8 on an int16 side, of 4 on a float32
+        side.  out may be x itself when both sides are int16 and n_out == n_in.  Returns (out, state)."""
+        import torch
+
+        if not x.is_cuda:
+            raise NoDeviceError(C.FZ_E_NO_DEVICE, "run_block_pcm16_stream_major needs CUDA (ROCm) tensors: zignal_amd has no CPU path")
+        if x.dim() == 2:
+            x = x.unsqueeze(-1)
+        it = self._frame_type(x.dtype, "x")
+        _require(x.dim() == 3 and x.is_contiguous() and x.shape[-1] == _bi.max(self.n_in, 1),
+                 f"x: expected contiguous buffers [n_streams, rows, {self.n_in}], got {tuple(x.shape)}")
+        ns, rows, _ = x.shape
+        row0 = int(row0)
+        T = rows - row0 if n_samples is None else int(n_samples)
+        _require(row0 >= 0 and T >= 0, "row0 / n_samples: a window inside the buffers")
+        odt = x.dtype if out_dtype is None else out_dtype
+        ot = self._frame_type(odt, "out_dtype")
+        odt = torch.int16 if ot == C.FZ_FRAMES_I16 else torch.float32
+        if out is None:
+            out = torch.zeros((ns, rows, self.n_out), dtype=odt, device=x.device)
+        _check_dev(out, (ns, rows, self.n_out), "out", odt)
+        if state is None:
+            state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
+        if self.n_state:
+            _check_dev(state, (self.n_state, ns), "state")
+        pp = None
+        if self.n_param:
+            if params is None:
+                raise FlowzError(C.FZ_E_INVALID, f"params: the graph has {self.n_param} per-stream coefficient(s), none given")
+            pp = _check_dev(params, (self.n_param, ns), "params").data_ptr()
+        C.check(C.lib.fz_run_block_pcm16_stream_major(self._h, x.data_ptr() if self.n_in else None, out.data_ptr() if self.n_out else None,
+                                                      state.data_ptr() if self.n_state else None, pp, ns, rows, row0, T, it, ot,
+                                                      torch.cuda.current_stream().cuda_stream))
+        return out, state
+
     # -- the backward of a block (fz_run_block_grad) ------------------------------------------------
     GRAD_WANT = ("x", "state", "params", "consts")
 
@@ -960,6 +1023,59 @@ class Bank:
         _require((out.dtype == torch.int16) if is_torch else (out.dtype == np.int16), "out: int16 frames expected")
         _require(x.ndim == 3 or self.prog.n_in <= 1, "x: [T, n_streams] only for one input wire")
         C.check(C.lib.fz_bank_process_host_pcm16(self._h, xp if self.prog.n_in else None, op, T))
+        return out
+
+    def process_pcm16_stream_major(self, x, out=None, out_dtype=None, row0=0, n_samples=None):
+        """Program.run_block_pcm16_stream_major on the bank's state and per-stream coefficients (fz_bank_process_pcm16_stream_major):
+        x CUDA int16 or float32 [n_streams, rows, n_in] (or [n_streams, rows]); returns out."""
+        import torch
+
+        if x.dim() == 2:
+            x = x.unsqueeze(-1)
+        it = Program._frame_type(x.dtype, "x")
+        _require(x.is_cuda and x.dim() == 3 and x.is_contiguous() and x.shape[-1] == _bi.max(self.prog.n_in, 1),
+                 "x: wrong shape, dtype, layout or device for this call")
+        ns, rows, _ = x.shape
+        if ns != self.n_streams:
+            raise FlowzError(C.FZ_E_INVALID, f"buffers hold {ns} streams, the bank {self.n_streams}")
+        row0 = int(row0)
+        T = rows - row0 if n_samples is None else int(n_samples)
+        _require(row0 >= 0 and T >= 0, "row0 / n_samples: a window inside the buffers")
+        ot = Program._frame_type(x.dtype if out_dtype is None else out_dtype, "out_dtype")
+        odt = torch.int16 if ot == C.FZ_FRAMES_I16 else torch.float32
+        if out is None:
+            out = torch.zeros((ns, rows, self.prog.n_out), dtype=odt, device=x.device)
+        _check_dev(out, (ns, rows, self.prog.n_out), "out", odt)
+        C.check(C.lib.fz_bank_process_pcm16_stream_major(self._h, x.data_ptr() if self.prog.n_in else None,
+                                                         out.data_ptr() if self.prog.n_out else None, rows, row0, T, it, ot,
+                                                         torch.cuda.current_stream().cuda_stream))
+        return out
+
+    def process_host_pcm16_stream_major(self, x, out=None):
+        """process_host_stream_major for a caller that holds [batch, time] 16-bit PCM: int16 buffers [n_streams, T, n_in] (or
+        [n_streams, T]) in, int16 [n_streams, T, n_out] out -- numpy arrays or CPU torch tensors, any T, half the PCIe bytes of
+        process_host_stream_major each way; the conversion rule of run_block_pcm16."""
+        import numpy as np
+
+        is_torch = hasattr(x, "data_ptr")
+        T = int(x.shape[1])
+        if is_torch:
+            import torch
+            _require(x.dtype == torch.int16 and x.is_contiguous() and not x.is_cuda, "x: wrong shape, dtype, layout or device for this call")
+            if out is None:
+                out = torch.empty((self.n_streams, T, self.prog.n_out), dtype=torch.int16, pin_memory=x.is_pinned())
+            xp, op = x.data_ptr(), out.data_ptr()
+        else:
+            _require(np.asarray(x).dtype == np.int16, "x: int16 buffers expected")
+            x = np.ascontiguousarray(x)
+            if out is None:
+                out = np.empty((self.n_streams, T, self.prog.n_out), np.int16)
+            xp, op = x.ctypes.data, out.ctypes.data
+        _require(tuple(x.shape) in ((self.n_streams, T, _bi.max(self.prog.n_in, 1)), (self.n_streams, T)), "x: wrong shape, dtype, layout or device for this call")
+        _require(x.ndim == 3 or self.prog.n_in <= 1, "x: [n_streams, T] only for one input wire")
+        _require(tuple(out.shape) == (self.n_streams, T, self.prog.n_out) and (out.is_contiguous() if is_torch else out.flags.c_contiguous), "out: wrong shape, dtype, layout or device for this call")
+        _require((out.dtype == torch.int16) if is_torch else (out.dtype == np.int16), "out: int16 buffers expected")
+        C.check(C.lib.fz_bank_process_host_pcm16_stream_major(self._h, xp if self.prog.n_in else None, op, T))
         return out
 
 
