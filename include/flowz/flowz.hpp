@@ -270,7 +270,7 @@ expr<I, 1> operator-(const expr<I, O>& a)
    return expr<I, 1>(detail::handle(fz_arith(FZ_OP_NEG, a.h.get(), nullptr)), a.refs);
 }
 
-// ---- graph functions: std::fabs, std::sqrt, std::exp, std::tanh, std::min, std::max (include/flowz_hip.h, FZ_OP_ABS ..) -------------
+// ---- graph functions: std::fabs, std::sqrt, std::exp, std::tanh, std::sin, std::cos, std::log, std::min, std::max (include/flowz_hip.h, FZ_OP_ABS ..) -------------
 // In the wire's C++ type (a double scalar stays a double terminal, as for the operators); min / max take an expression on either side.
 // flowz::tanh(0.5 * _1) is what `std::tanh(0.5 * x)` is in the reference's closures.
 #define FLOWZ_UNARY_FN(NAME, OP)                                                                          \
@@ -284,6 +284,9 @@ FLOWZ_UNARY_FN(abs, FZ_OP_ABS)
 FLOWZ_UNARY_FN(sqrt, FZ_OP_SQRT)
 FLOWZ_UNARY_FN(exp, FZ_OP_EXP)
 FLOWZ_UNARY_FN(tanh, FZ_OP_TANH)
+FLOWZ_UNARY_FN(sin, FZ_OP_SIN)   // float32 wires; |a| >= 2^20 gives NaN (include/flowz_hip.h)
+FLOWZ_UNARY_FN(cos, FZ_OP_COS)
+FLOWZ_UNARY_FN(log, FZ_OP_LOG)
 #undef FLOWZ_UNARY_FN
 #define FLOWZ_BINARY_FN(NAME, OP)                                                                        \
    template <class A, class B, class = detail::enable_binary<A, B>>                                     \

@@ -79,7 +79,39 @@ typedef enum fz_op { FZ_OP_ADD = 1, FZ_OP_SUB = 2, FZ_OP_MUL = 3, FZ_OP_DIV = 4,
                         (tests/fn_ref.py); a NaN result is a NaN, its payload is not specified.
                         std::complex operands: min / max -> FZ_E_GRAPH (C++ has no such operator); abs, sqrt, exp, tanh ->
                         FZ_E_UNSUPPORTED (valid C++, not built here). */
-                     FZ_OP_ABS = 15, FZ_OP_SQRT = 16, FZ_OP_EXP = 17, FZ_OP_TANH = 18, FZ_OP_MIN = 19, FZ_OP_MAX = 20 } fz_op;
+                     FZ_OP_ABS = 15, FZ_OP_SQRT = 16, FZ_OP_EXP = 17, FZ_OP_TANH = 18, FZ_OP_MIN = 19, FZ_OP_MAX = 20,
+                     /* std::sin, std::cos, std::log: unary graph functions under the rules above (b is ignored, the operand has exactly one
+                        output wire and keeps its input arity, ONE node in n_ops), the library's own algorithms from the same allowed
+                        operations: IEEE +, -, *, correctly rounded /, exact exponent-bit scaling, conversions; no FMA, no hardware
+                        approximation (v_sin_f32, v_cos_f32, v_log_f32, a bare v_rcp_f32), no ocml / libm call, no tables; branch-free per
+                        lane.  tests/fn_ref_trig.py restates them in numpy operation for operation and gives the kernels' bits for every
+                        non-NaN result.
+                          sin(a), cos(a)  FLOAT32 operands only (a double operand -- a fz_literal_f64 below it or a typed FZ_DT_F64 wire --
+                                    is FZ_E_UNSUPPORTED: valid C++, not built here).  The algorithm and constants of the RBJ generator's
+                                    sine and cosine: x = (double)a; t = x * 2/pi; k = (int)(t + (t < 0 ? -0.5 : 0.5)) (the conversion
+                                    truncates); r = ((x - k h1) - k h2) - k h3 with a three-part pi/2 whose head h1 has 33 bits (k h1
+                                    exact); z = r r; s = r + r (z S(z)), c = 1 + z C(z) with the Taylor polynomials (8 and 9 terms) by
+                                    Horner's rule; quadrant q = k & 3: sin = s, c, -s, -c and cos = c, -s, -c, s; rounded to float ONCE;
+                                    sin returns a itself for a = +-0 (the sum r + r (z S) loses the sign of -0).
+                                    The double is within 2^-60 of the true value, so the float is the correctly rounded result except for
+                                    arguments within that distance of a rounding boundary: measured below 0.500001 ulp for sin and for cos
+                                    over every float with |a| < 2^20 against float64 numpy (tools/graph_functions_exhaustive.py).
+                                    DOMAIN: |a| >= 2^20, +-inf and NaN give NaN (beyond that point k h1 is no longer exact; a wider
+                                    domain needs a Payne-Hanek reduction).  sin(+-0) = +-0, cos(+-0) = 1; sin is odd bitwise and cos
+                                    even bitwise, |sin|, |cos| <= 1, sin(a) = a for tiny and subnormal a (all checked over that domain).
+                          log(a)    in the wire's C++ type (float, or double when the operand is double, like exp).  The fdlibm scheme:
+                                    a = m 2^e through the exponent bits with m in [sqrt(1/2), sqrt 2) (bits + (bits(1) - bits(sqrt(1/2))),
+                                    exponent field - bias = e, mantissa field + bits(sqrt(1/2)) = m; subnormals first scaled by 2^25 /
+                                    2^54, exact); f = m - 1, s = f / (2 + f), z = s s, w = z z; R = z (L1 + w (L3 + ..)) + w (L2 + w (L4 + ..))
+                                    with L fitted here (Chebyshev fit of (log((1+s)/(1-s))/s - 2)/z on z in [0, 0.0295]: 4 coefficients
+                                    float, 7 double); h = (0.5 f) f; t = s (h + R); u = t + e ln2_lo; v = f - (h - u); log = e ln2_hi + v
+                                    with exp's two-part ln 2 (e ln2_hi exact).  Within 2 ulp of the correctly rounded result (float:
+                                    0.840 ulp at most over all 2^32 inputs; double: 0.826 ulp at most on 2^22 stratified inputs against
+                                    mpmath).  log(+-0) = -inf, log(a < 0) = NaN, log(+inf) = +inf, log(1) = +0, NaN gives NaN (payload
+                                    unspecified).  Monotone: over all 2^32 float inputs in increasing order the float log never steps
+                                    down (tools/graph_functions_exhaustive.py).
+                        std::complex operands of sin, cos, log -> FZ_E_UNSUPPORTED (valid C++, not built here), as for abs .. tanh. */
+                     FZ_OP_SIN = 21, FZ_OP_COS = 22, FZ_OP_LOG = 23 } fz_op;
 
 fz_expr* fz_placeholder(uint32_t i);                 /* _i          make_placeholder<i>() :78-82   */
 fz_expr* fz_delayed(uint32_t i, uint32_t n);         /* _i[_n]      delayed_placeholder   :84-85   */
@@ -123,7 +155,8 @@ fz_expr* fz_modulator(uint32_t k);                   /* the std::ref(x) terminal
 fz_expr* fz_arith(fz_op op, fz_expr* a, fz_expr* b); /* any C++ arithmetic, comparison or logical operator,
                                                         _default :769-772, or a graph function; b is ignored
                                                         (may be NULL) for FZ_OP_NEG, FZ_OP_NOT, FZ_OP_ABS,
-                                                        FZ_OP_SQRT, FZ_OP_EXP and FZ_OP_TANH           */
+                                                        FZ_OP_SQRT, FZ_OP_EXP, FZ_OP_TANH, FZ_OP_SIN,
+                                                        FZ_OP_COS and FZ_OP_LOG                           */
 fz_expr* fz_channel (fz_expr* a, fz_expr* b);        /* a , b       channel_operator   :90           */
 fz_expr* fz_parallel(fz_expr* a, fz_expr* b);        /* a | b       parallel_operator  :91           */
 fz_expr* fz_sequence(fz_expr* a, fz_expr* b);        /* a |= b      sequence_operator  :92           */
@@ -215,7 +248,9 @@ typedef enum fz_ir_kind {
    FZ_IR_LT = 15, FZ_IR_LE = 16, FZ_IR_GT = 17, FZ_IR_GE = 18, FZ_IR_EQ = 19, FZ_IR_NE = 20,
                       /* a (cmp) b ? 1.0f : 0.0f -- a float32 node (dtype 0) whose operands are compared in double when one of them is     */
    FZ_IR_ABS = 21, FZ_IR_SQRT = 22, FZ_IR_EXP = 23, FZ_IR_TANH = 24,   /* f(a), in a's type (see FZ_OP_ABS ..)                 */
-   FZ_IR_MIN = 25, FZ_IR_MAX = 26     /* std::min / std::max of a and b in their common type; never stage-packed (kinds >= ABSLT) */
+   FZ_IR_MIN = 25, FZ_IR_MAX = 26,    /* std::min / std::max of a and b in their common type; never stage-packed (kinds >= ABSLT) */
+   FZ_IR_SIN = 27, FZ_IR_COS = 28,    /* std::sin / std::cos of a, float32 only (see FZ_OP_SIN)                                   */
+   FZ_IR_LOG = 29                     /* std::log of a, in a's type; the three are never stage-packed or wave-split either          */
 } fz_ir_kind;
 
 typedef struct fz_ir_node {
@@ -469,6 +504,8 @@ int fz_program_tune_candidates(fz_program* p, uint64_t n_streams, uint32_t n_sam
  *   ADD  abar += g, bbar += g          SUB  abar += g, bbar -= g          NEG  abar -= g
  *   MUL  abar += g*b, bbar += g*a      DIV  q = g/b; abar += q, bbar -= q*v
  *   SQRT abar += g*(0.5/v)             EXP  abar += g*v                   TANH abar += g*(1 - v*v)
+ *   SIN  abar += g*cos(a)              COS  abar -= g*sin(a)              LOG  abar += g/a   -- cos(a) / sin(a): the library's own
+ *        functions (FZ_OP_COS / FZ_OP_SIN) on the operand's forward value; each contribution is formed, then added
  *   ABS  abar += g if a > 0, abar -= g if a < 0, nothing otherwise (a = +-0 or NaN)
  *   MIN  (b < a) ? bbar += g : abar += g      MAX  (a < b) ? bbar += g : abar += g   -- all of g to the operand std::min /
  *        std::max returned (their NaN and signed-zero rules decide which)
@@ -497,7 +534,7 @@ int fz_program_tune_candidates(fz_program* p, uint64_t n_streams, uint32_t n_sam
  *
  * Scope: fz_compile programs whose lowered graph is float32 throughout (no float64 literal, no complex wire), whose delay lines
  * all live in registers (max_delay <= 8: no LDS or HBM ring) and which read no modulator; node kinds INPUT, CONST, PARAM, DELAY,
- * ADD, SUB, MUL, DIV, NEG, LT .. NE, ABS, SQRT, EXP, TANH, MIN, MAX.  Anything else: FZ_E_UNSUPPORTED, fz_last_error() names why.
+ * ADD, SUB, MUL, DIV, NEG, LT .. NE, ABS, SQRT, EXP, TANH, MIN, MAX, SIN, COS, LOG.  Anything else: FZ_E_UNSUPPORTED, fz_last_error() names why.
  * Two frame layouts, one entry point each: fz_run_block_grad takes time-major frames, in / out_grad / in_grad as
  * [T][n_streams][wire]; fz_run_block_grad_stream_major takes stream-major buffers [n_streams][rows_total][wire] -- the layout of
  * fz_run_block_stream_major, and of a [batch, time] tensor -- and differentiates the window of rows [row0, row0 + n_samples).

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Times the graph-function workloads (zignal_amd.workloads: moog_ladder, soft_clip_cascade, envelope_follower) on the MI355X.
+"""Times the graph-function workloads (zignal_amd.workloads: moog_ladder, soft_clip_cascade, envelope_follower, pm_operator, wavefolder,
+log_compressor) on the MI355X.
 
 Not part of bench.py.  Each graph runs at 1 048 576 streams x 4096 samples on the library's default plan (no variant), with HIP events
 around each block after warm-up.  Printed per graph: ms per block (median of the timed blocks), GSamples/s, the bytes a block moves
@@ -25,7 +26,8 @@ import isa_stats  # noqa: E402
 from zignal_amd import flowz as F  # noqa: E402
 from zignal_amd import workloads as W  # noqa: E402
 
-GRAPHS = {"moog_ladder": W.moog_ladder, "soft_clip_cascade": W.soft_clip_cascade, "envelope_follower": W.envelope_follower}
+GRAPHS = {"moog_ladder": W.moog_ladder, "soft_clip_cascade": W.soft_clip_cascade, "envelope_follower": W.envelope_follower,
+          "pm_operator": W.pm_operator, "wavefolder": W.wavefolder, "log_compressor": W.log_compressor}
 HBM = 8e12
 
 

@@ -21,6 +21,7 @@ GRAPHS = {"cascade6": lambda: G.df1_cascade(6), "par4": G.par4_sum, "par4f": G.p
           "ring": lambda: G.seq(G.add(G.IN(1), G.mul(G.lit(0.5), G.DEL(1, 40))), G.fb(G.add(G.mul(G.lit(0.7), G.DEL(1, 23)), G.IN(2)))),
           "moog": G.moog_ladder, "softclip": G.soft_clip_cascade, "envelope": G.envelope_follower,
           "tanh": lambda: ("tanh", G.IN(1)), "exp": lambda: ("exp", G.IN(1)), "sqrt": lambda: ("sqrt", G.IN(1)), "min": lambda: ("min", G.IN(1), G.lit(0.5)),
+          "sin": lambda: ("sin", G.IN(1)), "cos": lambda: ("cos", G.IN(1)), "log": lambda: ("log", G.IN(1)),
           "wire": lambda: G.IN(1)}
 
 

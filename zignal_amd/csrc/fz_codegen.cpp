@@ -219,7 +219,11 @@ static const OpSpelling kOps[] = {
    {FZ_IR_EQ, "==", "fz_cmp", 2}, {FZ_IR_NE, "!=", "fz_cmp", 2},
    {FZ_IR_ABS, nullptr, "fz_abs", 1}, {FZ_IR_SQRT, nullptr, "fz_sqrt", 1}, {FZ_IR_EXP, nullptr, "fz_exp", 1}, {FZ_IR_TANH, nullptr, "fz_tanh", 1},
    {FZ_IR_MIN, nullptr, "fz_min", 2}, {FZ_IR_MAX, nullptr, "fz_max", 2},
+   {FZ_IR_SIN, nullptr, "fz_sin", 1}, {FZ_IR_COS, nullptr, "fz_cos", 1}, {FZ_IR_LOG, nullptr, "fz_log", 1},
 };
+
+// the graph functions are the kinds FZ_IR_ABS .. FZ_IR_LOG (FZ_IR_MAX is std::max, not the last of them)
+static constexpr uint32_t kFnFirst = FZ_IR_ABS, kFnLast = FZ_IR_LOG;
 
 static bool is_cmp(uint32_t kind) { return kind >= FZ_IR_LT && kind <= FZ_IR_NE; }
 
@@ -262,22 +266,64 @@ static void shift_line(std::ostringstream& o, uint32_t depth, const std::functio
 
 static std::string gen_body_skew(const Graph& g, const StageSplit& sp);
 
-// The graph functions (FZ_IR_ABS .. FZ_IR_MAX) for V and VD, written only into the text of graphs that use them: every other graph keeps
+// The graph functions (FZ_IR_ABS .. FZ_IR_LOG) for V and VD, written only into the text of graphs that use them: every other graph keeps
 // its kernel source byte for byte.  Branch-free per lane (both sides computed, the lane's one selected); exp and tanh are IEEE +, -, *,
 // correctly rounded / and exact power-of-two scaling through the exponent bits, no FMA (-ffp-contract=off), no hardware approximation and
 // no library call -- tests/fn_ref.py restates them operation for operation.  The polynomials run on V / VD themselves, so that two or four
 // streams per lane issue packed v_pk_mul_f32 / v_pk_add_f32; the comparisons and the exponent bits are per element (vector ternaries).
-static void emit_functions(std::ostringstream& o, const Graph& g)
+// adjoint: the text is for an adjoint kernel, whose rules for sin and cos call the other one of the two on the operand.
+static void emit_functions(std::ostringstream& o, const Graph& g, bool adjoint = false)
 {
-   bool has[FZ_IR_MAX + 1] = {};
+   bool has[kFnLast + 1] = {};
    for (const Node& nd : g.nodes)
-      if (nd.kind >= FZ_IR_ABS && nd.kind <= FZ_IR_MAX) has[nd.kind] = true;
+      if (nd.kind >= kFnFirst && nd.kind <= kFnLast) has[nd.kind] = true;
    if (has[FZ_IR_TANH]) has[FZ_IR_EXP] = true;
+   if (adjoint && (has[FZ_IR_SIN] || has[FZ_IR_COS])) has[FZ_IR_SIN] = has[FZ_IR_COS] = true;
    bool any = false;
-   for (uint32_t k = FZ_IR_ABS; k <= FZ_IR_MAX; ++k) any = any || has[k];
+   for (uint32_t k = kFnFirst; k <= kFnLast; ++k) any = any || has[k];
    if (!any) return;
    o << "#if FZ_P == 1\ntypedef int fz_vi;\ntypedef long long fz_vl;\n#else\n"
         "typedef int fz_vi __attribute__((ext_vector_type(FZ_P)));\ntypedef long long fz_vl __attribute__((ext_vector_type(FZ_P)));\n#endif\n";
+   if (has[FZ_IR_SIN] || has[FZ_IR_COS] || has[FZ_IR_LOG])   // value conversions per element (a C cast of a vector would be a bit cast)
+      o << "#if FZ_P == 1\n#define FZ_CVT(x, T) ((T)(x))\n#else\n#define FZ_CVT(x, T) __builtin_convertvector(x, T)\n#endif\n";
+   if (has[FZ_IR_SIN] || has[FZ_IR_COS]) {
+      // std::sin / std::cos of a float: the algorithm and the constants of fz_sincos_f32 (fz_aot_kernels.hip), restated for the streams of
+      // a lane; the double-precision core is shared by the two functions
+      static const char* const ps[] = {"0x1.952c77030ad4ap-49", "-0x1.ae7f3e733b81fp-41", "0x1.6124613a86d09p-33", "-0x1.ae64567f544e4p-26",
+                                       "0x1.71de3a556c734p-19", "-0x1.a01a01a01a01ap-13", "0x1.1111111111111p-7", "-0x1.5555555555555p-3"};
+      static const char* const pc[] = {"-0x1.6827863b97d97p-53", "0x1.ae7f3e733b81fp-45", "-0x1.93974a8c07c9dp-37", "0x1.1eed8eff8d898p-29", "-0x1.27e4fb7789f5cp-22",
+                                       "0x1.a01a01a01a01ap-16", "-0x1.6c16c16c16c17p-10", "0x1.5555555555555p-5", "-0x1.0000000000000p-1"};
+      o << "// s = sin r, c = cos r and the quadrant q = k & 3 of a = k pi/2 + r, in double; ok: |a| < 2^20 (else the core runs on 0)\n";
+      o << "__device__ __forceinline__ void fz_sincos_core(V a, VD& s, VD& c, fz_vl& q, fz_vi& ok)\n{\n";
+      o << "   ok = (__builtin_bit_cast(fz_vi, a) & (fz_vi)(0x7fffffff)) < (fz_vi)(0x49800000);   // |a| < 2^20; false for inf and NaN\n";
+      o << "   const V af = ok ? a : (V)(0);\n";
+      o << "   const VD x = FZ_CVT(af, VD);\n";
+      o << "   const VD t = x * (VD)(0x1.45f306dc9c883p-1);   // x * 2/pi\n";
+      o << "   const VD th = t + (t < (VD)(0) ? (VD)(-0.5) : (VD)(0.5));\n";
+      o << "   const fz_vi k = FZ_CVT(th, fz_vi);   // nearest integer (the conversion truncates)\n";
+      o << "   const VD kd = FZ_CVT(k, VD);\n";
+      o << "   VD r = x - kd * (VD)(0x1.921fb54400000p+0);   // pi/2, first 33 bits: the product is exact\n";
+      o << "   r = r - kd * (VD)(0x1.0b4611a600000p-34);\n";
+      o << "   r = r - kd * (VD)(0x1.3198a2e037073p-69);\n";
+      o << "   const VD z = r * r;\n";
+      o << "   VD ps = (VD)(" << ps[0] << ");\n";
+      for (size_t k = 1; k < std::size(ps); ++k) o << "   ps = (VD)(" << ps[k] << ") + z * ps;\n";
+      o << "   s = r + r * (z * ps);\n";
+      o << "   VD pc = (VD)(" << pc[0] << ");\n";
+      for (size_t k = 1; k < std::size(pc); ++k) o << "   pc = (VD)(" << pc[k] << ") + z * pc;\n";
+      o << "   c = (VD)(1) + z * pc;\n";
+      o << "   q = FZ_CVT(k, fz_vl) & (fz_vl)(3);\n}\n";
+      for (int cosine = 0; cosine < 2; ++cosine) {
+         if (!has[cosine ? FZ_IR_COS : FZ_IR_SIN]) continue;
+         o << "__device__ __forceinline__ V " << (cosine ? "fz_cos" : "fz_sin") << "(V a)\n{\n";
+         o << "   // quadrant 0..3: " << (cosine ? "c, -s, -c, s" : "s, c, -s, -c") << "; one rounding to float; |a| >= 2^20, inf, NaN: NaN\n";
+         o << "   VD s, c;\n   fz_vl q;\n   fz_vi ok;\n   fz_sincos_core(a, s, c, q, ok);\n";
+         o << "   const VD m = (q & (fz_vl)(1)) != (fz_vl)(0) ? " << (cosine ? "s : c" : "c : s") << ";\n";
+         o << "   const VD y = (" << (cosine ? "(q + (fz_vl)(1))" : "q") << " & (fz_vl)(2)) != (fz_vl)(0) ? -m : m;\n";
+         o << "   " << (cosine ? "const V yf = FZ_CVT(y, V);\n" : "V yf = FZ_CVT(y, V);\n   yf = a == (V)(0) ? a : yf;   // sin(+-0) = +-0 (r + r (z S) is +0 for r = -0)\n");
+         o << "   return ok ? yf : (V)(__builtin_nanf(\"\"));\n}\n";
+      }
+   }
    struct Ty {
       const char *T, *I, *sfx, *magic, *log2e, *ln2hi, *ln2lo, *xlo, *xhi, *xmax, *sw, *sat, *sign, *bias;
       int shift;
@@ -336,6 +382,45 @@ static void emit_functions(std::ostringstream& o, const Graph& g)
          o << "   " << T << " y = (p * __builtin_bit_cast(" << T << ", (k1 + " << t.bias << ") << " << t.shift << ")) * __builtin_bit_cast(" << T
            << ", (k2 + " << t.bias << ") << " << t.shift << ");\n";
          o << "   y = a > " << c << "(" << t.xmax << ") ? " << c << "(__builtin_huge_val" << t.sfx << "()) : y;\n";
+         o << "   return a != a ? a : y;\n}\n";
+      }
+      if (has[FZ_IR_LOG]) {
+         // the fdlibm scheme: a = m 2^e, m in [sqrt(1/2), sqrt 2), through the exponent bits (subnormals scaled first, exactly)
+         const bool dbl = &t == &tys[1];
+         const char* L = dbl ? "LL" : "";
+         const char *minn = dbl ? "0x0010000000000000" : "0x00800000", *scale = dbl ? "0x1p54" : "0x1p25f", *sbits = dbl ? "54" : "25",
+                    *off = dbl ? "0x00095f619980c433" : "0x004afb0d", *mant = dbl ? "0x000fffffffffffff" : "0x007fffff",
+                    *rh = dbl ? "0x3fe6a09e667f3bcd" : "0x3f3504f3";
+         const std::vector<const char*> lg = dbl ? std::vector<const char*>{"0x1.5555555555558p-1", "0x1.9999999995204p-2", "0x1.2492492e09d1ap-2", "0x1.c71c62c63e016p-3",
+                                                                         "0x1.7462bd8e53c17p-3", "0x1.39fd39474ad34p-3", "0x1.2b6686d1072f3p-3"} : std::vector<const char*>{"0x1.555556p-1f", "0x1.9999ecp-2f", "0x1.245c0ap-2f", "0x1.dddadep-3f"};
+         auto ic = [&](const char* v) { return "(" + I + ")(" + v + L + ")"; };
+         head("fz_log", false);
+         o << "   // f = m - 1, s = f / (2 + f), log m = f - (h - s (h + R(s^2))), h = f^2 / 2; + e ln2 in two parts (e ln2_hi exact)\n";
+         o << "   const auto sub = __builtin_bit_cast(" << I << ", a) < " << ic(minn) << ";   // subnormal (or zero, negative: overridden below)\n";
+         o << "   const " << T << " x = sub ? a * " << c << "(" << scale << ") : a;\n";
+         o << "   const " << I << " ix = __builtin_bit_cast(" << I << ", x) + " << ic(off) << ";\n";
+         o << "   const " << I << " e = ((ix >> " << t.shift << ") - " << ic(t.bias) << ") - (sub ? " << ic(sbits) << " : " << ic("0") << ");\n";
+         o << "   const " << T << " m = __builtin_bit_cast(" << T << ", (ix & " << ic(mant) << ") + " << ic(rh) << ");\n";
+         o << "   const " << T << " f = m - " << c << "(1);\n";
+         o << "   const " << T << " s = f / (" << c << "(2) + f);\n";
+         o << "   const " << T << " z = s * s;\n";
+         o << "   const " << T << " w = z * z;\n";
+         // R = z (L1 + w (L3 + ..)) + w (L2 + w (L4 + ..)): lg[] holds L1, L2, ..
+         for (int par = 0; par < 2; ++par) {
+            std::vector<const char*> cs;
+            for (size_t k = (size_t)par; k < lg.size(); k += 2) cs.push_back(lg[k]);
+            const char* nm = par ? "t1" : "t2";
+            o << "   " << T << " " << nm << " = " << c << "(" << cs.back() << ");\n";
+            for (size_t k = cs.size() - 1; k-- > 0;) o << "   " << nm << " = " << c << "(" << cs[k] << ") + w * " << nm << ";\n";
+         }
+         o << "   const " << T << " R = z * t2 + w * t1;\n";
+         o << "   const " << T << " h = (" << c << "(0.5) * f) * f;\n";
+         o << "   const " << T << " ef = FZ_CVT(e, " << T << ");\n";
+         o << "   const " << T << " u = s * (h + R) + ef * " << c << "(" << t.ln2lo << ");\n";
+         o << "   " << T << " y = ef * " << c << "(" << t.ln2hi << ") + (f - (h - u));\n";
+         o << "   y = a == " << c << "(__builtin_huge_val" << t.sfx << "()) ? a : y;\n";
+         o << "   y = a < " << c << "(0) ? " << c << "(__builtin_nan" << t.sfx << "(\"\")) : y;\n";
+         o << "   y = a == " << c << "(0) ? " << c << "(-__builtin_huge_val" << t.sfx << "()) : y;\n";
          o << "   return a != a ? a : y;\n}\n";
       }
       if (has[FZ_IR_TANH]) {
@@ -970,8 +1055,8 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
 }
 
 // the node kinds the adjoint kernel takes: inputs, coefficients, delayed reads and float arithmetic (INPUT .. NEG), the comparisons
-// and the graph functions (LT .. MAX) -- not the conversions, modulators, |a| < |b| and selections between them
-bool adjoint_takes(uint32_t kind) { return (kind >= FZ_IR_INPUT && kind <= FZ_IR_NEG) || (kind >= FZ_IR_LT && kind <= FZ_IR_MAX); }
+// and the graph functions (LT .. LOG) -- not the conversions, modulators, |a| < |b| and selections between them
+bool adjoint_takes(uint32_t kind) { return (kind >= FZ_IR_INPUT && kind <= FZ_IR_NEG) || (kind >= FZ_IR_LT && kind <= FZ_IR_LOG); }
 
 // struct fz_adj: fwd() -- the state after one step, from the state before it and the step's frame (the forward step() of gen_body for
 // one stream per lane, outputs left out) -- and bwd() -- the same step re-evaluated, then the adjoint statements in reverse node order.
@@ -985,7 +1070,7 @@ std::string gen_adjoint_body(const Graph& g)
    auto adj = [&](uint32_t id) { return "g" + std::to_string(id); };
    o << "// generated by libflowz_hip -- adjoint graph body: " << g.nodes.size() << " nodes, " << g.lines.size() << " delay lines, " << g.n_state
      << " state floats\n";
-   emit_functions(o, g);
+   emit_functions(o, g, true);
    auto row = [&](uint32_t src, uint32_t age) {          // state row of node src's value `age` samples ago (age >= 1)
       const Line& L = g.lines[(size_t)g.line_of_node[src]];
       return L.row0 + age - 1;
@@ -1070,6 +1155,9 @@ std::string gen_adjoint_body(const Graph& g)
          case FZ_IR_SQRT: plus(nd.a, gk + " * (0.5f / " + vk + ")"); break;
          case FZ_IR_EXP: plus(nd.a, gk + " * " + vk); break;
          case FZ_IR_TANH: plus(nd.a, gk + " * (1.0f - " + vk + " * " + vk + ")"); break;
+         case FZ_IR_SIN: plus(nd.a, gk + " * fz_cos(" + va + ")"); break;
+         case FZ_IR_COS: minus(nd.a, gk + " * fz_sin(" + va + ")"); break;
+         case FZ_IR_LOG: plus(nd.a, gk + " / " + va); break;
          case FZ_IR_ABS:
             o << "      " << adj(nd.a) << " = " << va << " > 0.f ? " << adj(nd.a) << " + " << gk << " : " << va << " < 0.f ? " << adj(nd.a) << " - " << gk
               << " : " << adj(nd.a) << ";\n";

@@ -216,7 +216,7 @@ std::string serialize_expr(const fz_expr* root)
          case EK::Modulator: std::snprintf(buf, sizeof buf, "M %u\n", e->i); break;
          case EK::Arith: std::snprintf(buf, sizeof buf, "A %d %lu %lu\n", (int)e->op, a, b); break;
          case EK::Neg: std::snprintf(buf, sizeof buf, "N %lu\n", a); break;
-         case EK::Fn1: std::snprintf(buf, sizeof buf, "G %d %lu\n", (int)e->op, a); break;   // abs, sqrt, exp, tanh (min / max: "A")
+         case EK::Fn1: std::snprintf(buf, sizeof buf, "G %d %lu\n", (int)e->op, a); break;   // abs, sqrt, exp, tanh, sin, cos, log (min / max: "A")
          case EK::Channel: std::snprintf(buf, sizeof buf, "C %lu %lu\n", a, b); break;
          case EK::Parallel: std::snprintf(buf, sizeof buf, "B %lu %lu\n", a, b); break;
          case EK::Sequence: std::snprintf(buf, sizeof buf, "S %lu %lu\n", a, b); break;
@@ -229,6 +229,9 @@ std::string serialize_expr(const fz_expr* root)
    }
    return out;
 }
+
+// the unary graph functions: FZ_OP_ABS .. FZ_OP_TANH and FZ_OP_SIN .. FZ_OP_LOG (min / max, between them, are binary)
+static bool is_fn1(int op) { return (op >= FZ_OP_ABS && op <= FZ_OP_TANH) || (op >= FZ_OP_SIN && op <= FZ_OP_LOG); }
 
 // the expression of a recipe (one reference, the caller's); nullptr + fz_last_error for text that is not one
 fz_expr* parse_expr(const std::string& text)
@@ -263,7 +266,7 @@ fz_expr* parse_expr(const std::string& text)
          case 'A': if (std::sscanf(s, "%d %lu %lu", &op, &a, &b) == 3 && ref(a) && ref(b)) e = fz_arith((fz_op)op, ref(a), ref(b)); break;
          case 'N': if (std::sscanf(s, "%lu", &a) == 1 && ref(a)) e = fz_arith(FZ_OP_NEG, ref(a), nullptr); break;
          case 'G':
-            if (std::sscanf(s, "%d %lu", &op, &a) == 2 && ref(a) && op >= FZ_OP_ABS && op <= FZ_OP_TANH) e = fz_arith((fz_op)op, ref(a), nullptr);
+            if (std::sscanf(s, "%d %lu", &op, &a) == 2 && ref(a) && is_fn1(op)) e = fz_arith((fz_op)op, ref(a), nullptr);
             break;
          case 'C': if (std::sscanf(s, "%lu %lu", &a, &b) == 2 && ref(a) && ref(b)) e = fz_channel(ref(a), ref(b)); break;
          case 'B': if (std::sscanf(s, "%lu %lu", &a, &b) == 2 && ref(a) && ref(b)) e = fz_parallel(ref(a), ref(b)); break;
@@ -431,8 +434,8 @@ fz_expr* fz_arith(fz_op op, fz_expr* a, fz_expr* b)
          Hold sum{check(fz_arith(FZ_OP_ADD, ta.e, tb.e))};
          return check(fz_arith(FZ_OP_NE, sum.e, zero.e));
       }
-      // the unary graph functions (std::fabs, std::sqrt, std::exp, std::tanh): a node of their own kind, like the negation
-      if (op >= FZ_OP_ABS && op <= FZ_OP_TANH) {
+      // the unary graph functions (std::fabs, std::sqrt, std::exp, std::tanh, std::sin, std::cos, std::log): a node of their own kind, like the negation
+      if (is_fn1(op)) {
          if (a->out_arity != 1) fail(FZ_E_GRAPH, "function operand must have exactly one output wire");
          auto* e = mk(EK::Fn1, a);
          e->op = op;

@@ -27,7 +27,7 @@ struct Error {
 
 // ---- expression tree (the EDSL surface, flowz.hpp:68-93) ---------------------------------------
 enum class EK : uint8_t { Placeholder, Delayed, Literal, Uniform, Param, Arith, Neg, Channel, Parallel, Sequence, Feedback, Modulator,
-                          Fn1 };   // Fn1: a unary graph function (op = FZ_OP_ABS .. FZ_OP_TANH); min / max are Arith nodes
+                          Fn1 };   // Fn1: a unary graph function (op = FZ_OP_ABS .. FZ_OP_TANH, FZ_OP_SIN .. FZ_OP_LOG); min / max are Arith nodes
 
 }  // namespace fz
 

@@ -140,7 +140,10 @@ struct Elab {
          }
          case EK::Fn1: {                                                // std::fabs / sqrt / exp / tanh: in the operand's type
             int a = one(e->a, ins);
-            if (imag_of.count(a)) fail(FZ_E_UNSUPPORTED, "abs, sqrt, exp and tanh of a std::complex wire are valid C++ but not built here");
+            if (imag_of.count(a))
+               fail(FZ_E_UNSUPPORTED, e->op >= FZ_OP_SIN ? "sin, cos and log of a std::complex wire are valid C++ but not built here"
+                                                         : "abs, sqrt, exp and tanh of a std::complex wire are valid C++ but not built here");
+            if (e->op >= FZ_OP_SIN) return {arith(FZ_IR_SIN + (uint32_t)(e->op - FZ_OP_SIN), a)};
             return {arith(FZ_IR_ABS + (uint32_t)(e->op - FZ_OP_ABS), a)};
          }
          case EK::Channel: {                                            // :765-768 same inputs to both
@@ -371,7 +374,7 @@ uint64_t bits_of64(double f)
 
 // VALU instructions per stream-sample of a node for the planner (Graph::op_weight): 1 for every operator; the graph functions as
 // tools/isa_stats.py (valu_per_step) counts them in the kernel of a one-node graph: one stream per lane, float (tanh 74, exp 40,
-// sqrt 17, min 2.7); double is not measured and weighs the same
+// sqrt 17, min 2.7, sin 67.7, cos 66.7, log 53.3); double is not measured and weighs the same
 uint32_t fn_weight(uint32_t kind, bool f64)
 {
    (void)f64;
@@ -381,6 +384,9 @@ uint32_t fn_weight(uint32_t kind, bool f64)
       case FZ_IR_SQRT: return 17;
       case FZ_IR_EXP: return 40;
       case FZ_IR_TANH: return 74;
+      case FZ_IR_SIN: return 68;
+      case FZ_IR_COS: return 67;
+      case FZ_IR_LOG: return 53;
       default: return 1;
    }
 }
@@ -513,7 +519,11 @@ Graph lower(const fz_expr* e, const LowerOptions& opt)
             r.f64 = raw[(size_t)r.a].f64 || raw[(size_t)r.b].f64;
             break;
          case FZ_IR_NEG: r.f64 = raw[(size_t)r.a].f64; break;
-         case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH: r.f64 = raw[(size_t)r.a].f64; break;
+         case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH: case FZ_IR_LOG: r.f64 = raw[(size_t)r.a].f64; break;
+         case FZ_IR_SIN: case FZ_IR_COS:
+            if (raw[(size_t)r.a].f64) fail(FZ_E_UNSUPPORTED, "sin and cos of a double operand are valid C++ but not built here (float32 operands only)");
+            r.f64 = false;
+            break;
          case FZ_IR_MIN: case FZ_IR_MAX: r.f64 = raw[(size_t)r.a].f64 || raw[(size_t)r.b].f64; break;
          case FZ_IR_ABSLT: r.f64 = raw[(size_t)r.a].f64 || raw[(size_t)r.b].f64; break;
          case FZ_IR_SELECT: r.f64 = raw[(size_t)r.b].f64 || raw[(size_t)r.n].f64; break;
@@ -575,7 +585,8 @@ Graph lower(const fz_expr* e, const LowerOptions& opt)
             case FZ_IR_PARAM: case FZ_IR_MOD: key = {r.kind, -1, -1, -1, r.n}; break;
             case FZ_IR_DELAY: key = {r.kind, rep[(size_t)r.a], -1, -1, r.n}; break;
             case FZ_IR_NEG: case FZ_IR_WIDEN: case FZ_IR_NARROW:
-            case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH: key = {r.kind, rep[(size_t)r.a], -1, -1, 0}; break;
+            case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH:
+            case FZ_IR_SIN: case FZ_IR_COS: case FZ_IR_LOG: key = {r.kind, rep[(size_t)r.a], -1, -1, 0}; break;
             case FZ_IR_SELECT: key = {r.kind, rep[(size_t)r.a], rep[(size_t)r.b], rep[(size_t)r.n], 0}; break;
             default: key = {r.kind, rep[(size_t)r.a], rep[(size_t)r.b], -1, 0}; break;
          }
@@ -610,7 +621,8 @@ Graph lower(const fz_expr* e, const LowerOptions& opt)
          case FZ_IR_MOD: n.a = r.n; g.n_mod = std::max(g.n_mod, r.n + 1); break;
          case FZ_IR_DELAY: n.a = nid(r.a); n.b = r.n; break;
          case FZ_IR_NEG: case FZ_IR_WIDEN: case FZ_IR_NARROW: n.a = nid(r.a); ++g.n_ops; break;
-         case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH: n.a = nid(r.a); ++g.n_ops; break;
+         case FZ_IR_ABS: case FZ_IR_SQRT: case FZ_IR_EXP: case FZ_IR_TANH:
+         case FZ_IR_SIN: case FZ_IR_COS: case FZ_IR_LOG: n.a = nid(r.a); ++g.n_ops; break;
          case FZ_IR_SELECT: n.a = nid(r.a); n.b = nid(r.b); n.c = nid((int)r.n); ++g.n_ops; break;
          default: n.a = nid(r.a); n.b = nid(r.b); ++g.n_ops; break;
       }

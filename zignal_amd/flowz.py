@@ -193,7 +193,7 @@ def seq(*xs) -> Expr:
     return r
 
 
-# ---- graph functions (include/flowz_hip.h, FZ_OP_ABS ..): std::fabs, std::sqrt, std::exp, std::tanh, std::min, std::max ---------
+# ---- graph functions (include/flowz_hip.h, FZ_OP_ABS ..): std::fabs, std::sqrt, std::exp, std::tanh, std::min, std::max, std::sin, std::cos, std::log
 def _fn1(op, a) -> Expr:
     a = as_expr(a)                      # (held: a temporary's handle would be released before fz_arith retains it)
     return Expr(C.lib.fz_arith(op, a._h, None))
@@ -224,6 +224,21 @@ def tanh(a) -> Expr:
     return _fn1(C.FZ_OP_TANH, a)
 
 
+def sin(a) -> Expr:
+    """std::sin of a float32 wire: correctly rounded but for arguments next to a rounding boundary, odd; |a| >= 2^20 gives NaN"""
+    return _fn1(C.FZ_OP_SIN, a)
+
+
+def cos(a) -> Expr:
+    """std::cos of a float32 wire: correctly rounded but for arguments next to a rounding boundary, even; |a| >= 2^20 gives NaN"""
+    return _fn1(C.FZ_OP_COS, a)
+
+
+def log(a) -> Expr:
+    """std::log: the library's algorithm, within 2 ulp; log(+-0) = -inf, a negative operand gives NaN"""
+    return _fn1(C.FZ_OP_LOG, a)
+
+
 def min(a, b) -> Expr:  # noqa: A001  (mirrors flowz::min)
     """std::min: (b < a) ? b : a, in the operands' common type; either side may be a scalar (a float literal)"""
     return _fn2(C.FZ_OP_MIN, a, b)
@@ -234,7 +249,8 @@ def max(a, b) -> Expr:  # noqa: A001  (mirrors flowz::max)
     return _fn2(C.FZ_OP_MAX, a, b)
 
 
-_FN1 = {"abs": C.FZ_OP_ABS, "sqrt": C.FZ_OP_SQRT, "exp": C.FZ_OP_EXP, "tanh": C.FZ_OP_TANH}
+_FN1 = {"abs": C.FZ_OP_ABS, "sqrt": C.FZ_OP_SQRT, "exp": C.FZ_OP_EXP, "tanh": C.FZ_OP_TANH,
+        "sin": C.FZ_OP_SIN, "cos": C.FZ_OP_COS, "log": C.FZ_OP_LOG}
 _FN2 = {"min": C.FZ_OP_MIN, "max": C.FZ_OP_MAX}
 
 

@@ -247,7 +247,7 @@ def complex_one_pole(c=(0.6, 0.7)):
 
 # ---- graph functions (abs, sqrt, exp, tanh, min, max): nonlinear filters.  Not BASELINE graphs: bench.py does not run them ----------
 def fn(name, *args):
-    """('abs'|'sqrt'|'exp'|'tanh', a) or ('min'|'max', a, b): std::fabs, std::sqrt, std::exp, std::tanh, std::min, std::max"""
+    """('abs'|'sqrt'|'exp'|'tanh'|'sin'|'cos'|'log', a) or ('min'|'max', a, b): std::fabs, std::sqrt, std::exp, std::tanh, std::min, std::max"""
     return (name, *args)
 
 
@@ -293,6 +293,39 @@ def envelope_follower(attack=ENV_ATTACK, release=ENV_RELEASE):
     e, r = DEL(1, 1), IN(2)
     d = sub(r, e)
     return seq(fn("abs", IN(1)), fb(fn("max", add(e, mul(lit(attack), d)), add(e, mul(lit(release), d)))))
+
+
+# ---- sin, cos, log: modulation operators and gain computers.  Not BASELINE graphs either -----------------------------------------
+PM_PI, PM_TWO_PI = F32(np.pi), F32(2.0 * np.pi)
+PM_INDEX = F32(2.5)
+
+
+def pm_operator(index=PM_INDEX):
+    """A phase-modulation operator: per-stream parameter 0 is the phase increment per sample (0 <= inc < 2 pi), accumulated in a
+    feedback and wrapped into [-pi, pi) with a comparison; the input modulates the phase:
+        p = ph' + inc;  ph = p - 2pi*(p >= pi);  y = sin(ph + index*x)     i.e.  ~(wrap(_1[_1] + inc)) |= sin(_1 + index*_2)"""
+    p = add(DEL(1, 1), param(0))
+    ph = sub(p, mul(lit(PM_TWO_PI), cmp("ge", p, lit(PM_PI))))
+    return seq(fb(ph), fn("sin", add(IN(1), mul(lit(index), IN(2)))))
+
+
+FOLD_POLE, FOLD_GAIN = F32(0.25), F32(4.0)
+
+
+def wavefolder(a=FOLD_POLE, g=FOLD_GAIN):
+    """A sine wavefolder behind a one-pole low-pass:  e = e' + a*(x - e');  y = sin(g*e)     i.e.  ~(_1[_1] + a*(_2 - _1[_1])) |= sin(g*_1)"""
+    e = DEL(1, 1)
+    return seq(fb(add(e, mul(lit(a), sub(IN(2), e)))), fn("sin", mul(lit(g), IN(1))))
+
+
+COMP_SLOPE, COMP_THRESHOLD, COMP_EPS = F32(0.75), F32(-1.5), F32(1e-6)
+
+
+def log_compressor(slope=COMP_SLOPE, threshold=COMP_THRESHOLD, eps=COMP_EPS, attack=ENV_ATTACK, release=ENV_RELEASE):
+    """A feed-forward compressor with its gain computer in the log domain (threshold in nepers): the envelope follower above, then
+        y = exp(min(0, slope*(threshold - log(env + eps)))) * x     i.e.  (envelope_follower, _1) |= exp(min(0, ..log(_1 + eps)..)) * _2"""
+    gain = fn("exp", fn("min", lit(0.0), mul(lit(slope), sub(lit(threshold), fn("log", add(IN(1), lit(eps)))))))
+    return seq(chan(envelope_follower(attack, release), IN(1)), mul(gain, IN(2)))
 
 
 # ---- synthetic inputs and per-stream coefficients (SURVEY 8d) -------------------------------------------
