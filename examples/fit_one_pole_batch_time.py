@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Example: fit per-stream one-pole coefficients to a batch of recordings held as [batch, time] tensors, with Adam.
 
-y[t] = a * y[t-1] + x[t], one coefficient `a` per recording.  The tensors stay stream-major from end to end:
-autograd.run(..., stream_major=True) runs the forward on them (run_block_stream_major) and back-propagates through the block with the
-stream-major adjoint kernel (run_block_grad_stream_major).  Nothing is transposed."""
+y[t] = a * y[t-1] + x[t], one coefficient `a` per recording.  The tensors stay stream-major from end to end, and a step is one
+launch: autograd.mse(..., stream_major=True) runs the stream-major adjoint kernel that forms y, the error against the target and
+dL/dy itself (run_block_loss_grad_stream_major).  Nothing is transposed, and neither y nor dL/dy is written to memory."""
 import os
 import sys
 
@@ -25,10 +25,9 @@ a = torch.full((1, batch), 0.5, device="cuda", requires_grad=True)
 opt = torch.optim.Adam([a], lr=0.05)
 for step in range(50):
     opt.zero_grad()
-    y, _ = AG.run(prog, x, None, a, stream_major=True)
-    loss = ((y - target) ** 2).mean()
+    loss = AG.mse(prog, x, target, None, a, stream_major=True)
     loss.backward()
     opt.step()
     if step % 10 == 0 or step == 49:
         print(f"step {step:2d}  loss {loss.item():.6f}  mean |a - a_true| {(a.detach() - a_true).abs().mean().item():.4f}")
-print("adjoint kernel:", prog.grad_kernel_symbol(stream_major=True))
+print("adjoint kernel:", prog.loss_grad_kernel_symbol(stream_major=True))

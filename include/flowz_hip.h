@@ -589,6 +589,58 @@ int fz_program_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint3
 long fz_program_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 
+/* fz_run_block_loss_grad -- the backward of one block where dL/dy is not given but FORMED IN THE KERNEL from a target, under a
+ * squared-error loss.  The adjoint kernel re-evaluates every step of the block anyway: it holds y when it needs dL/dy, so neither y
+ * nor dL/dy has to cross HBM.
+ *
+ * THE RULE (stated here once).  With y the float32 output of the forward step (the bits of fz_run_block) and k = grad_scale:
+ * rows t = T-1 down to 0; within a row the output slots j in ascending order:
+ *      e       = y[j] - target[t][j]        one rounding
+ *      ybar[j] = e * k                      one rounding
+ *      loss    = loss + e * e               the product rounded, then the sum; ONE accumulator per stream
+ * The accumulator starts from what the caller's loss[stream] holds: `loss` is ADDED TO, like param_grad, so blocks chain bitwise
+ * (the backward of block 2, then of block 1 on the same buffer, gives the bits of one block of 2T).  loss == NULL: not computed.
+ * ybar then enters rule 1 of the ORDER OF OPERATIONS above unchanged, and everything after it is fz_run_block_grad's text word for
+ * word: every gradient bit equals fz_run_block_grad given that ybar, the bits depend on the inputs only, no atomics, no FMA.
+ * The kernel knows no reduction: for the mean over everything pass k = 2 / (T * n_streams * n_out) and multiply the sum of the
+ * per-stream losses by 1 / (T * n_streams * n_out).
+ *
+ * fz_loss_grad_args is fz_grad_args with `target` (the layout of out) where out_grad was, grad_scale, `loss` and `out`: if out is not
+ * NULL, y is written there from the second sweep, with the bits of fz_run_block -- the only write the plain backward does not make.
+ * state_grad is accepted as before, so a caller can still walk blocks backwards.
+ * Scope: fz_program_grad_check's.  Workspace: fz_program_grad_workspace's.  Checks, before a device is needed, each naming its reason:
+ * the scope refusals of the backward; n_out == 0: FZ_E_INVALID (nothing to compare); then an empty block (n_streams == 0 or
+ * n_samples == 0): FZ_OK, nothing touched; target == NULL: FZ_E_INVALID; pointer alignment, overlap and the 2^30-streams rule as for
+ * fz_run_block_grad, with loss and out counted as outputs (they overlap nothing, target included).
+ * fz_run_block_loss_grad takes time-major frames; fz_run_block_loss_grad_stream_major stream-major buffers, windows and alignment
+ * exactly as fz_run_block_grad_stream_major: rows of in_grad and of out outside the window are never written.  The layout does not
+ * change a bit.  The inspection calls take (checkpoint_rows, layout) like their _grad_ twins; the kernels have symbols of their
+ * own, fz_adjoint_loss_kernel_c<C>b<lanes>_g<tag> and fz_adjoint_loss_sm_kernel_c<C>r<R>b<lanes>_g<tag>, with the C, the R and the LDS
+ * bytes of the plain adjoint kernels (the target travels in the patch part that carries dL/dy there, and y leaves through it). */
+typedef struct fz_loss_grad_args {
+   uint32_t struct_size;         /* sizeof(fz_loss_grad_args); a smaller or unknown size is FZ_E_INVALID   */
+   uint32_t checkpoint_rows;     /* as fz_grad_args                                                         */
+   const float* in;              /* [T][n_streams][n_in]    forward input of the block (NULL iff n_in == 0) */
+   const float* state;           /* [n_state][n_streams]    state BEFORE the block (read only)              */
+   const float* params;          /* [n_param][n_streams]                                                    */
+   const float* target;          /* [T][n_streams][n_out]   what y is compared with                         */
+   const float* state_grad;      /* [n_state][n_streams]    dL/d(state after the block); NULL = zero        */
+   float* in_grad;               /* [T][n_streams][n_in]    written;  NULL = not computed                   */
+   float* state0_grad;           /* [n_state][n_streams]    written;  NULL = not computed; may == state_grad */
+   float* param_grad;            /* [n_param][n_streams]    ADDED TO; NULL = not computed                   */
+   float* const_grad;            /* [n_const][n_streams]    ADDED TO; NULL = not computed                   */
+   float* loss;                  /* [n_streams]             sum of e * e, ADDED TO; NULL = not computed     */
+   float* out;                   /* [T][n_streams][n_out]   y, written; NULL = not written                  */
+   void*  workspace; uint64_t workspace_bytes;   /* device scratch of at least fz_program_grad_workspace bytes */
+   float  grad_scale;            /* k of the rule                                                           */
+} fz_loss_grad_args;
+int fz_run_block_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
+int fz_run_block_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                        uint32_t n_samples, void* hip_stream);
+int fz_program_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out);
+long fz_program_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+long fz_program_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+
 /* ------------------------------------------------------------------------------------------
  * 16-bit PCM frames.  fz_run_block_pcm16 is fz_run_block for a block whose frames are int16 on one side or on both: the caller
  * sends and receives 2 bytes per sample instead of 4, the conversions happen in the kernel.

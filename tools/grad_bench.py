@@ -16,7 +16,13 @@ beforehand).  Same process, legs interleaved: the time-major backward runs for a
 then every leg is timed --steps times in a forward and again in a backward pass over the list.  Printed per line: the median of
 each leg, the yardstick's spread (max - min over its own repeats: the noise), and the ratio to the time-major backward alone.
 
-usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare]
+--loss: one training step under a mean squared error, fused against the route before it, in both layouts.  fused: ONE launch of
+run_block_loss_grad (fz_run_block_loss_grad: y, the error and dL/dy formed in the adjoint kernel; every gradient and the per-stream
+loss).  route: the forward launch, torch's ((y - target) ** 2).mean() and its derivative 2 (y - target) / n, run_block_grad -- on the
+same buffers, same process, legs interleaved as for --layout compare (100 ms of the route first, then --steps launches per leg in a
+forward and again in a backward pass over the legs).  The table goes to stdout and to profiles/r10/loss_grad.txt.
+
+usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss]
 """
 import argparse
 import datetime
@@ -122,16 +128,90 @@ def compare(a, torch):
         torch.cuda.empty_cache()
 
 
+def loss_bench(a, torch):
+    """one step under a mean squared error: the fused launch against forward + torch MSE and derivative + backward, both layouts"""
+    import time
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+    props = torch.cuda.get_device_properties(0)
+    say(f"# command: tools/grad_bench.py --loss --steps {a.steps} --legs {a.legs}")
+    say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+    say(f"# fused = one run_block_loss_grad launch; route = run_block + torch ((y - target)**2).mean() and 2 (y - target) / n + run_block_grad;")
+    say(f"# HIP events, {a.steps} launches per leg and pass, a forward and a backward pass over the legs; spread = max - min of the route's own repeats")
+    say(f"{'graph':20s} {'layout':>12s} {'streams x T':>16s} {'route ms':>9s} {'spread':>7s} {'fused ms':>9s} {'fused/route':>11s} {'vgprs':>6s} {'lds':>6s}  loss kernel")
+    shapes = SHAPES["small"] + SHAPES["large"] if a.legs == "all" else SHAPES[a.legs]
+    for ns, T in shapes:
+        for sm in (False, True):
+            x = torch.empty((ns, T, 1) if sm else (T, ns, 1), dtype=torch.float32, device="cuda")
+            F.synth_fill(x, seed=W.SEED)
+            target = torch.empty_like(x)
+            F.synth_fill(target, seed=W.SEED + 1)
+            y, gy, gx = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+            n = float(ns) * T
+            for name, fn in GRAPHS.items():
+                prog = F.compile(F.from_sexpr(fn()))
+                pp = params_for(name, prog, ns, torch)
+                s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+                st = s0.clone()
+                fwd = prog.run_block_stream_major if sm else prog.run_block
+                bwd = prog.run_block_grad_stream_major if sm else prog.run_block_grad
+                kw = {"in_grad": gx} if sm else {}
+
+                def route():
+                    st.copy_(s0)
+                    fwd(x, state=st, params=pp, out=y)
+                    loss = ((y - target) ** 2).mean()
+                    torch.mul(y - target, 2.0 / n, out=gy)
+                    bwd(x, gy, s0, pp, **kw)
+                    return loss
+
+                def fused():
+                    f = prog.run_block_loss_grad_stream_major if sm else prog.run_block_loss_grad
+                    r = f(x, target, s0, pp, grad_scale=2.0 / n, want=("x", "state", "params", "consts", "loss"), **kw)
+                    return r["loss"].double().sum() / n
+                legs = {"route": route, "fused": fused}
+                vals = {k: float(f()) for k, f in legs.items()}        # JIT, allocator; and the two routes agree on the loss
+                assert abs(vals["route"] - vals["fused"]) <= 1e-3 * abs(vals["route"]), vals    # (a sanity check, not the test: float32 sums in two orders)
+                torch.cuda.synchronize()
+                t_end = time.time() + 0.1
+                while time.time() < t_end:                          # at least 100 ms of the yardstick before the first timing
+                    route()
+                    torch.cuda.synchronize()
+                got = {k: [] for k in legs}
+                for order in (list(legs), list(legs)[::-1]):
+                    for k in order:
+                        got[k] += samples(legs[k], a.steps, torch)
+                med = {k: float(np.median(v)) for k, v in got.items()}
+                res = prog.loss_grad_resources(stream_major=sm)
+                say(f"{name:20s} {'stream-major' if sm else 'time-major':>12s} {f'{ns} x {T}':>16s} {med['route']:9.3f} {max(got['route']) - min(got['route']):7.3f} "
+                    f"{med['fused']:9.3f} {med['fused'] / med['route']:11.3f} {res['vgprs'] + res['agprs']:6d} {res['lds_bytes']:6d}  "
+                    f"{prog.loss_grad_kernel_symbol(stream_major=sm)}")
+                say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
+                del pp, s0, st
+            del x, target, y, gy, gx
+            torch.cuda.empty_cache()
+    out = os.path.join(ROOT, "profiles", "r10", "loss_grad.txt")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--legs", choices=("small", "large", "all"), default="all")
     ap.add_argument("--layout", choices=("time-major", "stream-major", "compare"), default="time-major")
+    ap.add_argument("--loss", action="store_true", help="the fused squared-error backward against forward + torch MSE + backward, both layouts")
     a = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
+    if a.loss:
+        return loss_bench(a, torch)
     props = torch.cuda.get_device_properties(0)
     if a.layout == "compare":
         print(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")

@@ -2,6 +2,8 @@
 """Dev tool: JIT a graph variant (no GPU needed) and print instruction histogram + resources.
 
 usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par4|par4f|osc|df1|ring)
+       tools/isa_stats.py lossgrad [graph] [tm|sm]         the kernel of fz_run_block_loss_grad (sm: _stream_major) next to the plain
+                                                           adjoint kernel: registers, spills, LDS (graph: also cascade_params6)
 """
 import glob
 import os
@@ -22,7 +24,7 @@ GRAPHS = {"cascade6": lambda: G.df1_cascade(6), "par4": G.par4_sum, "par4f": G.p
           "moog": G.moog_ladder, "softclip": G.soft_clip_cascade, "envelope": G.envelope_follower,
           "tanh": lambda: ("tanh", G.IN(1)), "exp": lambda: ("exp", G.IN(1)), "sqrt": lambda: ("sqrt", G.IN(1)), "min": lambda: ("min", G.IN(1), G.lit(0.5)),
           "sin": lambda: ("sin", G.IN(1)), "cos": lambda: ("cos", G.IN(1)), "log": lambda: ("log", G.IN(1)),
-          "wire": lambda: G.IN(1)}
+          "wire": lambda: G.IN(1), "cascade_params6": lambda: G.df1_cascade_params(6)}
 
 
 def valu_count(expr, P, U=1, block=256, flags=0):
@@ -53,8 +55,19 @@ def valu_per_step(expr, P):
     return (valu_count(expr, P) - base) / copies
 
 
+def loss_grad_line(name, sm):
+    p = F.compile(F.from_sexpr(GRAPHS[name]()))
+    r, q = p.loss_grad_resources(stream_major=sm), p.grad_resources(stream_major=sm)
+    return (f"{name} {'stream' if sm else 'time'}-major {p.loss_grad_kernel_symbol(stream_major=sm)}: C {r['unroll']}, {r['vgprs'] + r['agprs']} VGPRs "
+            f"(plain adjoint {q['vgprs'] + q['agprs']}), {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills (plain {q['vgpr_spills']} / {q['sgpr_spills']}), "
+            f"{r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS")
+
+
 def main():
     a = sys.argv[1:]
+    if a and a[0] == "lossgrad":
+        print(loss_grad_line(a[1] if len(a) > 1 else "cascade_params6", len(a) > 2 and a[2] == "sm"))
+        return
     name = a[0] if a else "cascade6"
     P, U, B, FL = (int(a[i]) if len(a) > i else d for i, d in ((1, 2), (2, 8), (3, 256), (4, 0)))
     with tempfile.TemporaryDirectory() as td:

@@ -80,6 +80,14 @@ class GradArgs(ctypes.Structure):
                                                "const_grad", "workspace")] + [("workspace_bytes", ctypes.c_uint64)]
 
 
+class LossGradArgs(ctypes.Structure):
+    """fz_loss_grad_args (include/flowz_hip.h): the arguments of fz_run_block_loss_grad; struct_size first"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("checkpoint_rows", ctypes.c_uint32)] + \
+               [(n, ctypes.c_void_p) for n in ("in_", "state", "params", "target", "state_grad", "in_grad", "state0_grad", "param_grad",
+                                               "const_grad", "loss", "out", "workspace")] + \
+               [("workspace_bytes", ctypes.c_uint64), ("grad_scale", ctypes.c_float)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -165,6 +173,11 @@ def _load():
         "fz_program_grad_resources_for": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),
         "fz_program_grad_kernel_symbol_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_grad_source_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_run_block_loss_grad": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u64, u32, P]),
+        "fz_run_block_loss_grad_stream_major": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u64, u32, u32, u32, P]),
+        "fz_program_loss_grad_resources_for": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_loss_grad_kernel_symbol_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_loss_grad_source_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_pcm16_check": (ctypes.c_int, [P]),
         "fz_run_block_pcm16": (ctypes.c_int, [P, P, P, P, P, u64, u32, u32, u32, P]),
         "fz_program_pcm16_resources": (ctypes.c_int, [P, u32, u32, u64, ctypes.POINTER(KernelResources)]),

@@ -6,6 +6,10 @@ over consecutive blocks back-propagates through time across them (the state grad
 k-1).  Time-major frames [T, n_streams, n_in] (or [T, n_streams] for one input wire) on the GPU; there is no CPU path.
 run(..., stream_major=True) takes stream-major tensors instead, [n_streams, T, n_in] or [n_streams, T] -- a [batch, time] tensor as it
 lies: the forward is Program.run_block_stream_major, the backward Program.run_block_grad_stream_major, and nothing is transposed.
+
+mse(prog, x, target, ...) is the mean squared error of one block against a target as ONE launch (Program.run_block_loss_grad:
+the adjoint kernel forms y, the error and dL/dy itself), where run() followed by ((y - target) ** 2).mean() is a forward launch,
+several elementwise kernels and the backward launch.
 """
 from __future__ import annotations
 
@@ -82,3 +86,44 @@ def run(prog: Program, x, state=None, params=None, consts=None, stream_major=Fal
         if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
             raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
     return _Block.apply(prog, x, state, params, consts, bool(stream_major))
+
+
+class _Mse(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prog, x, target, state, params, consts, stream_major=False):
+        _apply_consts(prog, consts)
+        _, need_x, _, need_s, need_p, need_c = ctx.needs_input_grad[:6]
+        want = ["loss"] + [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
+        xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
+        n = xx.shape[0] * xx.shape[1] * prog.n_out                    # elements of y: the mean is over all of them
+        bwd = prog.run_block_loss_grad_stream_major if stream_major else prog.run_block_loss_grad
+        # the one launch: the loss and every gradient asked for, dL/dy = (y - target) * 2 / n formed in the kernel
+        r = bwd(xx, target.detach().contiguous(), state.detach() if state is not None else None,
+                params.detach() if params is not None else None, grad_scale=2.0 / n, want=want)
+        ctx.grads = (r["x"].reshape(x.shape) if need_x else None, r["state"] if need_s else None, r["params"] if need_p else None,
+                     # per-stream coefficient adjoints, summed over the streams in float64
+                     r["consts"][:prog.n_const].double().sum(1).to(consts.dtype).to(consts.device) if need_c else None)
+        return (r["loss"].double().sum() / n).to(torch.float32)       # per-stream sums of e * e, summed over the streams in float64
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        gx, gs, gp, gc = ctx.grads
+        scaled = lambda t: None if t is None else t * g.to(t.device)   # noqa: E731  (the upstream scalar)
+        return None, scaled(gx), None, scaled(gs), scaled(gp), scaled(gc), None
+
+
+def mse(prog: Program, x, target, state=None, params=None, consts=None, stream_major=False):
+    """The mean squared error ((y - target) ** 2).mean() of ONE block y = run(prog, x, state, params, consts)[0], as a scalar tensor,
+    differentiable in x, state, params and consts (not in target).  One launch, made in the forward (Program.run_block_loss_grad,
+    include/flowz_hip.h: fz_run_block_loss_grad): y and dL/dy never cross HBM, dL/dx is computed only if x requires a gradient, and
+    backward() applies the upstream scalar to the gradients that launch left.  x, state, params, consts and stream_major as for
+    run(); target is laid out like y.  It covers one block and does not return the state after it: chaining blocks stays with run()."""
+    if not prog.grad_supported():
+        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.grad_unsupported_reason())
+    if x.dim() == 2 and prog.n_in != 1:
+        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
+    if consts is not None:
+        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
+            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
+    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major))

@@ -27,6 +27,8 @@ extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
 extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a kernel text of its own
 extern const char* const kSkeletonAdjointSm; // fz_kernel_adjoint_sm.hip.inc: the same for stream-major buffers
+extern const char* const kSkeletonAdjointLoss;   // fz_kernel_adjoint_loss.hip.inc: the adjoint kernel that forms dL/dy from a target
+extern const char* const kSkeletonAdjointLossSm; // fz_kernel_adjoint_loss_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
@@ -37,6 +39,8 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string sm_pair = sm + kSkeletonBody_sm_pair, sm_long = sm + kSkeletonBody_sm_long, sm_short = sm + kSkeletonBody_sm_short,
                             ws = head + kSkeletonBody_wave_split, fr = head + kSkeletonBody_frames;
    static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm, pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
+   static const std::string adj_loss = kSkeletonAdjointLoss, adj_loss_sm = kSkeletonAdjointLossSm;
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_LOSS)) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_loss_sm : adj_loss;
    if (v.flags & FZ_VF_ADJOINT) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_sm : adj;
    if (v.flags & FZ_VF_PCM16) return (v.flags & FZ_VF_PCM16_SM) ? pcm_sm : pcm;
    if (v.flags & FZ_VF_STREAM_MAJOR) return !(v.flags & FZ_VF_SM_LONG) ? sm_short : v.P == 2 ? sm_pair : sm_long;
@@ -47,9 +51,10 @@ const std::string& skeleton_source(const Variant& v)
 // fz_block_kernel_p<streams/lane>u<unroll>b<block>[s<segments>]f<flags>
 std::string kernel_name(const Graph& g, const Variant& v)
 {
+   const std::string adj = (v.flags & FZ_VF_ADJOINT_LOSS) ? "fz_adjoint_loss" : "fz_adjoint";   // (the loss bit means something next to FZ_VF_ADJOINT only)
    if (v.flags & FZ_VF_ADJOINT_SM)
-      return "fz_adjoint_sm_kernel_c" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block);
-   if (v.flags & FZ_VF_ADJOINT) return "fz_adjoint_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
+      return adj + "_sm_kernel_c" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block);
+   if (v.flags & FZ_VF_ADJOINT) return adj + "_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
    if ((v.flags & FZ_VF_PCM16) && (v.flags & FZ_VF_PCM16_SM))   // (stream-major PCM: which side is int16, rows per chunk, lanes)
       return "fz_pcm16_sm_kernel_i" + std::to_string((v.flags & FZ_VF_PCM16_IN) ? 1 : 0) + "o" + std::to_string((v.flags & FZ_VF_PCM16_OUT) ? 1 : 0) + "u" +
              std::to_string(v.U) + "b" + std::to_string(v.block);
@@ -746,7 +751,7 @@ static std::string gen_body_waves(const Graph& g, uint32_t W)
 
 std::string gen_body(const Graph& g, const Variant& v)
 {
-   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_body(g);
+   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_body(g, (v.flags & FZ_VF_ADJOINT_LOSS) != 0);
    if (const uint32_t W = ws_parts(v.flags)) return gen_body_waves(g, W);
    if (v.flags & FZ_VF_STAGE_PACK) return gen_body_skew(g, g.split);
    return gen_body_frames(g, v);
@@ -1063,7 +1068,9 @@ bool adjoint_takes(uint32_t kind) { return (kind >= FZ_IR_INPUT && kind <= FZ_IR
 // The order of every sum is the one include/flowz_hip.h documents (fz_run_block_grad); tests/adjoint_ref.py restates it.  A node's
 // adjoint starts as -0.0f, the identity of IEEE addition: a first contribution is the contribution itself, bit for bit, and the
 // compiler folds the addition away.  Nodes no adjoint reaches (those that only feed comparisons) emit nothing at all.
-std::string gen_adjoint_body(const Graph& g)
+// loss (FZ_VF_ADJOINT_LOSS): out() as well -- the step's output values from (x, c, p, s), for the kernels that form dL/dy themselves;
+// without it the text is what it was before that variant existed, byte for byte.
+std::string gen_adjoint_body(const Graph& g, bool loss)
 {
    std::ostringstream o;
    auto val = [&](uint32_t id) { return "v" + std::to_string(id); };
@@ -1183,6 +1190,14 @@ std::string gen_adjoint_body(const Graph& g)
       o << "      xb[" << w << "] = " << e << ";\n";
    }
    o << "   }\n";
+   if (loss) {
+      o << "   // the step's output values, slot by slot: the bits fz_run_block writes\n";
+      o << "   __device__ __forceinline__ static void out(const float* x, const float* c, const float* p, const float* s, float* y)\n   {\n";
+      o << "      (void)x; (void)c; (void)p; (void)s; (void)y;\n";
+      values("      ");
+      for (size_t j = 0; j < g.outputs.size(); ++j) o << "      y[" << j << "] = " << val(g.outputs[j]) << ";\n";
+      o << "   }\n";
+   }
    o << "};\n";
    return o.str();
 }

@@ -2,7 +2,10 @@
 // their checkpoint stride, patch length and workspace, argument checks and the launch.  The kernel text is fz_kernel_adjoint.hip.inc
 // (time-major frames) or fz_kernel_adjoint_sm.hip.inc (stream-major buffers) plus gen_adjoint_body (fz_codegen.cpp); the code objects
 // go through the kernel cache as a Variant with FZ_VF_ADJOINT (and FZ_VF_ADJOINT_SM).
+// The backward under a squared-error loss (fz_run_block_loss_grad, fz_run_block_loss_grad_stream_major) is the same call with dL/dy
+// formed in the kernel from a target: FZ_VF_ADJOINT_LOSS on the Variant, fz_kernel_adjoint_loss.hip.inc / fz_kernel_adjoint_loss_sm.hip.inc.
 #include <algorithm>
+#include <cstddef>
 #include <cstring>
 #include <utility>
 #include <vector>
@@ -74,7 +77,8 @@ uint32_t grad_sm_max_patch_rows()
 // could adjoint_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
 bool adjoint_variant_fits(const Graph& g, const Variant& v)
 {
-   if (!(v.flags & FZ_VF_ADJOINT) || (v.flags & ~(FZ_VF_ADJOINT | FZ_VF_ADJOINT_SM)) || !grad_unsupported_reason(g).empty()) return false;
+   if (!(v.flags & FZ_VF_ADJOINT) || (v.flags & ~(FZ_VF_ADJOINT | FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_LOSS)) || !grad_unsupported_reason(g).empty()) return false;
+   if ((v.flags & FZ_VF_ADJOINT_LOSS) && g.n_out == 0) return false;                       // (a loss kernel compares outputs)
    if (v.block != kGradBlock || v.U == 0 || v.U > kGradMaxCheckpoint || (v.U & (v.U - 1))) return false;
    if (!(v.flags & FZ_VF_ADJOINT_SM)) return v.P == 1;
    return v.P >= 4 && !(v.P & (v.P - 1)) && v.P % v.U == 0 && v.P <= grad_sm_max_patch_rows() && sm_patch_bytes(g, v.P) <= kLdsBytes;
@@ -94,14 +98,15 @@ static void require_supported(const Graph& g)
    if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
 }
 
-static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool stream_major = false)
+static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool stream_major = false, bool loss = false)
 {
    require_supported(g);
    Variant v;
    v.P = 1;
    v.U = checkpoint_of(g, checkpoint_rows);
    v.block = kGradBlock;
-   v.flags = FZ_VF_ADJOINT | (stream_major ? FZ_VF_ADJOINT_SM : 0u);
+   v.flags = FZ_VF_ADJOINT | (stream_major ? FZ_VF_ADJOINT_SM : 0u) | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
+   if (loss && g.n_out == 0) fail(FZ_E_INVALID, "the graph has no output wires: a loss has nothing to compare");
    if (stream_major) v.P = grad_sm_patch_rows(g, v.U);      // (the patch rows travel in P: codegen puts them into FZ_R and the symbol)
    if (stream_major && sm_patch_bytes(g, v.P) > kLdsBytes)
       fail(FZ_E_UNSUPPORTED, "stream-major backward: a patch of " + std::to_string(v.U) + " checkpoint rows of " + std::to_string(g.n_in + g.n_out) +
@@ -147,19 +152,77 @@ struct AdjSmArgsHeader {
 };
 static_assert(sizeof(AdjSmArgsHeader) == sizeof(AdjArgsHeader) + 2 * 4, "AdjSmArgsHeader must match the head of the kernel's fz_adj_sm_args without padding");
 
+// kernarg image of `struct fz_adj_loss_args` (fz_kernel_adjoint_loss.hip.inc) up to the coefficient tail: it ends in one float, and
+// the first kAdjLossHeaderBytes of it are what the kernel's struct holds there; `struct fz_adj_loss_sm_args`
+// (fz_kernel_adjoint_loss_sm.hip.inc) has rows_total and row0 behind them
+struct AdjLossArgsHeader {
+   const float* in;
+   const float* state;
+   const float* params;
+   const float* target;
+   const float* state_grad;
+   float* in_grad;
+   float* state0_grad;
+   float* param_grad;
+   float* const_grad;
+   float* ckpt;
+   float* loss;
+   float* out;
+   unsigned long long n_streams;
+   unsigned int n_samples;
+   unsigned int n_chunks;
+   float grad_scale;
+};
+constexpr size_t kAdjLossHeaderBytes = offsetof(AdjLossArgsHeader, grad_scale) + sizeof(float);
+static_assert(kAdjLossHeaderBytes == 12 * 8 + 8 + 2 * 4 + 4, "AdjLossArgsHeader must match the head of the kernel's fz_adj_loss_args without padding");
+
 // the window of a stream-major launch: rows [row0, row0 + n_samples) of buffers [n_streams][rows_total][wire]; null: time-major frames
 struct SmWindow {
    uint32_t rows_total, row0;
 };
 
-static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm = nullptr)
+// the arguments of a backward, whichever struct they came in: fz_grad_args gives dL/dy (`ybar`), fz_loss_grad_args the target in its
+// place and what the squared-error rule needs (`loss_rule`)
+struct GradCall {
+   uint32_t checkpoint_rows;
+   const float *in, *state, *params, *ybar, *state_grad;
+   float *in_grad, *state0_grad, *param_grad, *const_grad;
+   void* workspace;
+   uint64_t workspace_bytes;
+   bool loss_rule;
+   float grad_scale;
+   float *loss, *out;
+};
+
+template <class Args>
+static const Args* checked_args(fz_program* p, const Args* a, const char* fn, const char* type)
 {
    if (!p) fail(FZ_E_INVALID, "null program");
-   if (!a) fail(FZ_E_INVALID, "fz_run_block_grad: null arguments");
-   if (a->struct_size != sizeof(fz_grad_args))
-      fail(FZ_E_INVALID, "fz_grad_args.struct_size is " + std::to_string(a->struct_size) + ", this library knows " + std::to_string(sizeof(fz_grad_args)));
+   if (!a) fail(FZ_E_INVALID, std::string(fn) + ": null arguments");
+   if (a->struct_size != sizeof(Args))
+      fail(FZ_E_INVALID, std::string(type) + ".struct_size is " + std::to_string(a->struct_size) + ", this library knows " + std::to_string(sizeof(Args)));
+   return a;
+}
+
+static GradCall call_of(fz_program* p, const fz_grad_args* a0)
+{
+   const fz_grad_args* a = checked_args(p, a0, "fz_run_block_grad", "fz_grad_args");
+   return GradCall{a->checkpoint_rows, a->in, a->state, a->params, a->out_grad, a->state_grad, a->in_grad, a->state0_grad, a->param_grad, a->const_grad,
+                   a->workspace, a->workspace_bytes, false, 0.f, nullptr, nullptr};
+}
+
+static GradCall call_of(fz_program* p, const fz_loss_grad_args* a0)
+{
+   const fz_loss_grad_args* a = checked_args(p, a0, "fz_run_block_loss_grad", "fz_loss_grad_args");
+   return GradCall{a->checkpoint_rows, a->in, a->state, a->params, a->target, a->state_grad, a->in_grad, a->state0_grad, a->param_grad, a->const_grad,
+                   a->workspace, a->workspace_bytes, true, a->grad_scale, a->loss, a->out};
+}
+
+static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm = nullptr)
+{
+   const GradCall* const a = &call;
    const Graph& g = p->g;
-   const Variant v = adjoint_variant(g, a->checkpoint_rows, sm != nullptr);
+   const Variant v = adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
    if (n_streams == 0 || n_samples == 0) return FZ_OK;     // an empty block: nothing to differentiate, nothing touched
    if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
    if (sm) {
@@ -176,7 +239,8 @@ static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, ui
    if (g.n_in && !a->in) fail(FZ_E_INVALID, "in is null but the graph has input wires");
    if (g.n_state && !a->state) fail(FZ_E_INVALID, "state is null but the graph has delay lines");
    if (g.n_param && !a->params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
-   if (g.n_out && !a->out_grad) fail(FZ_E_INVALID, "out_grad is null but the graph has output wires");
+   if (a->loss_rule && !a->ybar) fail(FZ_E_INVALID, "target is null: the loss compares the outputs with it");
+   if (g.n_out && !a->ybar) fail(FZ_E_INVALID, "out_grad is null but the graph has output wires");
    const uint64_t need = workspace_bytes(g, n_streams, n_samples, v.U);
    if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: fz_program_grad_workspace says " + std::to_string(need) + " bytes");
    if (need && a->workspace_bytes < need)
@@ -192,10 +256,11 @@ static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, ui
    // (only what the kernel touches: buffers of zero rows are never dereferenced)
    const std::vector<Buf> bufs = {
       {a->in, g.n_in ? fr * g.n_in : 0, "in", false},          {a->state, row * g.n_state, "state", false},
-      {a->params, row * g.n_param, "params", false},           {a->out_grad, g.n_out ? fr * g.n_out : 0, "out_grad", false},
+      {a->params, row * g.n_param, "params", false},           {a->ybar, g.n_out ? fr * g.n_out : 0, a->loss_rule ? "target" : "out_grad", false},
       {a->state_grad, row * g.n_state, "state_grad", false},   {a->in_grad, g.n_in ? fr * g.n_in : 0, "in_grad", true},
       {a->state0_grad, row * g.n_state, "state0_grad", true},  {a->param_grad, row * g.n_param, "param_grad", true},
       {a->const_grad, row * g.consts.size(), "const_grad", true}, {a->workspace, need, "workspace", true},
+      {a->loss, row, "loss", true},                            {a->out, g.n_out ? fr * g.n_out : 0, "out", true},
    };
    for (const Buf& b : bufs)
       if (b.ptr && (reinterpret_cast<uintptr_t>(b.ptr) & 15u)) fail(FZ_E_INVALID, std::string(b.name) + ": device pointers must be 16-byte aligned");
@@ -211,13 +276,21 @@ static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, ui
    void* fn = nullptr;
    (void)get_kernel(p, v, &fn);
    // (the size of the kernel's argument struct: 8-byte aligned -- a buffer of another size does not launch that struct)
-   const size_t hbytes = sm ? sizeof(AdjSmArgsHeader) : sizeof(AdjArgsHeader);
+   const size_t hbytes = a->loss_rule ? kAdjLossHeaderBytes + (sm ? 2 * sizeof(unsigned int) : 0) : sm ? sizeof(AdjSmArgsHeader) : sizeof(AdjArgsHeader);
    const size_t kbytes = (hbytes + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
    std::vector<char> kbuf(kbytes, 0);
-   const AdjArgsHeader h{a->in,      a->state,       a->params,     a->out_grad, a->state_grad, a->in_grad,
-                         a->state0_grad, a->param_grad, a->const_grad, static_cast<float*>(a->workspace), (unsigned long long)n_streams, n_samples,
-                         (unsigned int)((n_samples + (uint64_t)v.U - 1) / v.U)};
-   if (sm) {
+   const unsigned int n_chunks = (unsigned int)((n_samples + (uint64_t)v.U - 1) / v.U);
+   const AdjArgsHeader h{a->in,      a->state,       a->params,     a->ybar, a->state_grad, a->in_grad,
+                         a->state0_grad, a->param_grad, a->const_grad, static_cast<float*>(a->workspace), (unsigned long long)n_streams, n_samples, n_chunks};
+   if (a->loss_rule) {
+      const AdjLossArgsHeader hl{a->in, a->state, a->params, a->ybar, a->state_grad, a->in_grad, a->state0_grad, a->param_grad, a->const_grad,
+                                 static_cast<float*>(a->workspace), a->loss, a->out, (unsigned long long)n_streams, n_samples, n_chunks, a->grad_scale};
+      std::memcpy(kbuf.data(), &hl, kAdjLossHeaderBytes);
+      if (sm) {
+         const unsigned int win[2] = {sm->rows_total, sm->row0};
+         std::memcpy(kbuf.data() + kAdjLossHeaderBytes, win, sizeof win);
+      }
+   } else if (sm) {
       const AdjSmArgsHeader hs{h, sm->rows_total, sm->row0};
       std::memcpy(kbuf.data(), &hs, sizeof hs);
    } else
@@ -231,6 +304,13 @@ static int run_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, ui
    const unsigned grid = (unsigned)((n_streams + v.block - 1) / v.block);
    FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
    return FZ_OK;
+}
+
+// what an adjoint kernel needs (JITs it); `unroll` = its checkpoint stride
+static fz_kernel_resources resources_of(fz_program* p, const Variant& v)
+{
+   const auto k = get_kernel(p, v, nullptr);
+   return fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills, k->res.sgpr_spills, v.U};
 }
 
 // a string result of the inspection calls: the length, at most cap bytes written; an error code (negative) on failure
@@ -284,10 +364,7 @@ int fz_program_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint3
 {
    FZ_GUARD(
       if (!p || !out) fail(FZ_E_INVALID, "fz_program_grad_resources: bad arguments");
-      const Variant v = adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout));
-      const auto k = get_kernel(p, v, nullptr);
-      *out = fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills,
-                                 k->res.sgpr_spills, v.U};
+      *out = resources_of(p, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout)));
       return FZ_OK;)
 }
 
@@ -308,7 +385,7 @@ long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_
 
 int fz_run_block_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
-   FZ_GUARD(return run_grad(p, a, n_streams, n_samples, hip_stream);)
+   FZ_GUARD(return run_grad(p, call_of(p, a), n_streams, n_samples, hip_stream);)
 }
 
 int fz_run_block_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
@@ -316,7 +393,38 @@ int fz_run_block_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_
 {
    FZ_GUARD(
       const SmWindow w{rows_total, row0};
-      return run_grad(p, a, n_streams, n_samples, hip_stream, &w);)
+      return run_grad(p, call_of(p, a), n_streams, n_samples, hip_stream, &w);)
+}
+
+int fz_run_block_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
+{
+   FZ_GUARD(return run_grad(p, call_of(p, a), n_streams, n_samples, hip_stream);)
+}
+
+int fz_run_block_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                        uint32_t n_samples, void* hip_stream)
+{
+   FZ_GUARD(
+      const SmWindow w{rows_total, row0};
+      return run_grad(p, call_of(p, a), n_streams, n_samples, hip_stream, &w);)
+}
+
+int fz_program_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!p || !out) fail(FZ_E_INVALID, "fz_program_loss_grad_resources_for: bad arguments");
+      *out = resources_of(p, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true));
+      return FZ_OK;)
+}
+
+long fz_program_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true)); });
+}
+
+long fz_program_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true)); });
 }
 
 }  // extern "C"

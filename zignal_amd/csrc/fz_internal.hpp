@@ -185,6 +185,10 @@ constexpr uint32_t FZ_VF_ADJOINT = 1u << 27;
 // own; one of the reserved bits, so no caller's variant names it either.  Such a Variant carries the rows of its LDS patch in P
 // (fz_grad.cpp: grad_sm_patch_rows is their one home; the kernel itself runs one stream per lane).
 constexpr uint32_t FZ_VF_ADJOINT_SM = 1u << 18;
+// internal, with FZ_VF_ADJOINT (and optionally FZ_VF_ADJOINT_SM): the adjoint kernel that forms dL/dy itself, from a target and the
+// squared-error rule of fz_run_block_loss_grad (fz_kernel_adjoint_loss.hip.inc, fz_kernel_adjoint_loss_sm.hip.inc: texts and symbols
+// of their own); one more of the reserved bits.  P, U and block mean what they mean for the plain adjoint variant.
+constexpr uint32_t FZ_VF_ADJOINT_LOSS = 1u << 17;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte
 // accesses).  FZ_VF_ST_MERGE means for it what it means for the frame kernel.  Such a Variant shares the kernel cache and the manifests
@@ -240,7 +244,7 @@ const std::string& skeleton_source(const Variant& v);   // hand-written kernel t
 std::string full_source(const Graph& g, const Variant& v);
 // the adjoint kernel (a Variant with FZ_VF_ADJOINT): gen_config / gen_body / skeleton_source hand over to these for it
 std::string gen_adjoint_config(const Graph& g, const Variant& v);
-std::string gen_adjoint_body(const Graph& g);
+std::string gen_adjoint_body(const Graph& g, bool loss = false);   // loss: also out(), the step's output values (FZ_VF_ADJOINT_LOSS)
 // the node kinds gen_adjoint_body writes (fz_codegen.cpp); grad_unsupported_reason refuses a graph with any other
 bool adjoint_takes(uint32_t kind);
 // why the backward of a block does not support this graph ("" = it does): fz_grad.cpp

@@ -806,13 +806,53 @@ class Program:
         n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
         return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad))
 
-    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window):
-        """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers"""
+    # -- the backward under a squared-error loss (fz_run_block_loss_grad): dL/dy formed in the kernel from a target ------------------
+    LOSS_GRAD_WANT = GRAD_WANT + ("loss", "out")
+
+    def loss_grad_resources(self, checkpoint_rows: int = 0, stream_major: bool = False) -> dict:
+        """grad_resources() of the kernel of run_block_loss_grad (stream_major: of run_block_loss_grad_stream_major)"""
+        r = C.KernelResources()
+        C.check(C.lib.fz_program_loss_grad_resources_for(self._h, int(checkpoint_rows), int(bool(stream_major)), ctypes.byref(r)))
+        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+    def loss_grad_kernel_symbol(self, checkpoint_rows: int = 0, stream_major: bool = False) -> str:
+        buf = ctypes.create_string_buffer(160)
+        C.check(C.lib.fz_program_loss_grad_kernel_symbol_for(self._h, int(checkpoint_rows), int(bool(stream_major)), buf, 160))
+        return buf.value.decode()
+
+    def loss_grad_source(self, checkpoint_rows: int = 0, stream_major: bool = False) -> str:
+        n = C.check(C.lib.fz_program_loss_grad_source_for(self._h, int(checkpoint_rows), int(bool(stream_major)), None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        C.check(C.lib.fz_program_loss_grad_source_for(self._h, int(checkpoint_rows), int(bool(stream_major)), buf, n + 1))
+        return buf.value.decode()
+
+    def run_block_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
+                            checkpoint_rows: int = 0):
+        """run_block_grad with dL/dy formed in the kernel (fz_run_block_loss_grad): per row and output slot e = y - target, dL/dy = e *
+        grad_scale, loss[stream] += e * e -- one launch, neither y nor dL/dy crosses HBM.  target [T, n_streams, n_out].  want: as for
+        run_block_grad, plus "loss" ([n_streams], the per-stream sums of e * e) and "out" (y, like target: the bits of run_block).
+        accum: "params" / "consts" / "loss" tensors that are ADDED to.  Returns a dict."""
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), None))
+
+    def run_block_loss_grad_stream_major(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT,
+                                         accum=None, checkpoint_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None, in_grad=None,
+                                         out=None):
+        """run_block_loss_grad on stream-major buffers, windows as for run_block_grad_stream_major: x [n_streams, rows, n_in], target
+        [n_streams, rows, n_out].  in_grad / out: the tensors the window's rows of "x" / "out" are written to (otherwise new ones, zero
+        outside the window).  Not a bit differs from run_block_loss_grad on the transposed frames."""
+        n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), (float(grad_scale), out))
+
+    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None):
+        """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers; loss: None, or
+        (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad"""
         import torch
 
         _require(self.grad_supported(), self.grad_unsupported_reason())
         want = tuple(want)
-        _require(set(want) <= set(self.GRAD_WANT), f"want: a subset of {self.GRAD_WANT}")
+        allowed = self.GRAD_WANT if loss is None else self.LOSS_GRAD_WANT
+        _require(set(want) <= set(allowed), f"want: a subset of {allowed}")
+        _require(loss is None or self.n_out, "the graph has no output wires: a loss has nothing to compare")
         if x.dim() == 2 and self.n_in == 1:
             x = x.unsqueeze(-1)
         _check_frames(x, self.n_in)
@@ -829,7 +869,7 @@ class Program:
         dev = x.device
         if out_grad.dim() == 2 and self.n_out == 1:
             out_grad = out_grad.unsqueeze(-1)
-        _check_dev(out_grad, gshape, "out_grad")
+        _check_dev(out_grad, gshape, "out_grad" if loss is None else "target")
         if state is None:
             state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=dev)
         if self.n_state:
@@ -856,18 +896,30 @@ class Program:
                     out[key] = _check_dev(accum[key], (nrow, ns), f"accum[{key!r}]")
                 else:
                     out[key] = torch.zeros((_bi.max(nrow, 1), ns), dtype=torch.float32, device=dev)
+        if "loss" in want:
+            out["loss"] = _check_dev(accum["loss"], (ns,), "accum['loss']") if "loss" in accum else torch.zeros((ns,), dtype=torch.float32, device=dev)
+        if "out" in want:
+            if loss[1] is not None:
+                out["out"] = _check_dev(loss[1].unsqueeze(-1) if loss[1].dim() == 2 and self.n_out == 1 else loss[1], gshape, "out")
+            else:
+                out["out"] = torch.empty(gshape, dtype=torch.float32, device=dev) if window is None or (row0, T) == (0, rows) else \
+                    torch.zeros(gshape, dtype=torch.float32, device=dev)
         wsb = self.grad_workspace_bytes(ns, T, checkpoint_rows)
         ws = torch.empty((_bi.max(wsb, 16) + 3) // 4, dtype=torch.float32, device=dev)
 
         def ptr(t, rows=1):
             return t.data_ptr() if t is not None and rows else None
-        a = C.GradArgs()
-        a.struct_size = ctypes.sizeof(C.GradArgs)
+        a = C.GradArgs() if loss is None else C.LossGradArgs()
+        a.struct_size = ctypes.sizeof(a)
         a.checkpoint_rows = int(checkpoint_rows)
         a.in_ = ptr(x, self.n_in)
         a.state = ptr(state, self.n_state)
         a.params = ptr(params, self.n_param)
-        a.out_grad = ptr(out_grad, self.n_out)
+        if loss is None:
+            a.out_grad = ptr(out_grad, self.n_out)
+        else:
+            a.target, a.grad_scale = ptr(out_grad, self.n_out), loss[0]
+            a.loss, a.out = ptr(out.get("loss")), ptr(out.get("out"), self.n_out)
         a.state_grad = ptr(state_grad, self.n_state)
         a.in_grad = ptr(out.get("x"), self.n_in)
         a.state0_grad = ptr(out.get("state"), self.n_state)
@@ -876,10 +928,12 @@ class Program:
         a.workspace = ws.data_ptr()
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
+        hs = torch.cuda.current_stream().cuda_stream
         if window is None:
-            C.check(C.lib.fz_run_block_grad(self._h, ctypes.byref(a), int(ns), int(T), torch.cuda.current_stream().cuda_stream))
+            C.check((C.lib.fz_run_block_grad if loss is None else C.lib.fz_run_block_loss_grad)(self._h, ctypes.byref(a), int(ns), int(T), hs))
         else:
-            C.check(C.lib.fz_run_block_grad_stream_major(self._h, ctypes.byref(a), int(ns), int(rows), row0, T, torch.cuda.current_stream().cuda_stream))
+            fn = C.lib.fz_run_block_grad_stream_major if loss is None else C.lib.fz_run_block_loss_grad_stream_major
+            C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, T, hs))
         return out
 
 
