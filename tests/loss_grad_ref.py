@@ -9,11 +9,12 @@ import adjoint_ref as A
 F32 = np.float32
 
 
-def loss_grad(prog, x, target, k, state=None, params=None, state_grad=None, accum_params=None, accum_consts=None, accum_loss=None):
-    """dict x / state / params / consts / loss / out of fz_run_block_loss_grad's bits; time-major arrays, target [T, ns, n_out]"""
+def loss_grad(prog, x, target, k, state=None, params=None, state_grad=None, accum_params=None, accum_consts=None, accum_loss=None, ref=A):
+    """dict x / state / params / consts / loss / out of fz_run_block_loss_grad's bits; time-major arrays, target [T, ns, n_out].
+    ref: the module whose forward() and grad() restate the program -- tests/adjoint_ref_trig.py for one with sin, cos or log"""
     x, target = np.asarray(x, F32), np.asarray(target, F32)
     T, ns, _ = x.shape
-    y, _ = A.forward(prog, x, state, params)
+    y, _ = ref.forward(prog, x, state, params)
     with np.errstate(all="ignore"):
         e = y - target
         ybar = e * F32(k)
@@ -21,7 +22,7 @@ def loss_grad(prog, x, target, k, state=None, params=None, state_grad=None, accu
         for t in range(T - 1, -1, -1):
             for j in range(y.shape[2]):
                 loss = loss + e[t, :, j] * e[t, :, j]
-    r = A.grad(prog, x, ybar, state, params, state_grad, accum_params, accum_consts)
+    r = ref.grad(prog, x, ybar, state, params, state_grad, accum_params, accum_consts)
     r["loss"], r["out"] = loss, y
     return r
 

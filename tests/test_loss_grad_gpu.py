@@ -52,9 +52,10 @@ def draw(p, name, ns, T, seed):
     return x, s0, par, tg, sb, ap, ac, al
 
 
-def on_gpu(p, sm, x, s0, par, tg, sb, ap, ac, al, checkpoint_rows=0, want=KEYS, rows=None, row0=0):
+def on_gpu(p, sm, x, s0, par, tg, sb, ap, ac, al, checkpoint_rows=0, want=KEYS, rows=None, row0=0, in_grad=None, out=None):
     """one launch on time-major numpy inputs; sm: through stream-major buffers of `rows` rows with the block at row0, "x" and "out" come
-    back time-major (the window's rows), "x_buffer" / "out_buffer" are the whole buffers, SENTINEL outside the window"""
+    back time-major (the window's rows), "x_buffer" / "out_buffer" are the whole buffers, SENTINEL outside the window -- or in_grad / out,
+    the buffers consecutive windows fill; "target_sent" / "target_after": the target buffer as it went in and as the launch left it"""
     T, ns = x.shape[:2]
     accum = {k: dev(v) for k, v, n in (("params", ap, p.n_param), ("consts", ac, p.n_const), ("loss", al, 1)) if n and k in want}
     args = (dev(s0) if p.n_state else None, dev(par), dev(sb) if p.n_state else None)
@@ -63,17 +64,21 @@ def on_gpu(p, sm, x, s0, par, tg, sb, ap, ac, al, checkpoint_rows=0, want=KEYS, 
     else:
         rows = up4(row0 + T) if rows is None else rows
         full = lambda w: torch.full((ns, rows, w), float(SENTINEL), device="cuda")   # noqa: E731
-        r = p.run_block_loss_grad_stream_major(dev(to_sm(x, rows, row0, 7.0)), dev(to_sm(tg, rows, row0, 7.0)), *args, grad_scale=K, want=want,
+        sent = to_sm(tg, rows, row0, 7.0)
+        tgd = dev(sent)
+        r = p.run_block_loss_grad_stream_major(dev(to_sm(x, rows, row0, 7.0)), tgd, *args, grad_scale=K, want=want,
                                                accum=accum, checkpoint_rows=checkpoint_rows, row0=row0, n_samples=T,
-                                               in_grad=full(p.n_in) if "x" in want else None, out=full(p.n_out) if "out" in want else None)
+                                               in_grad=(full(p.n_in) if in_grad is None else in_grad) if "x" in want else None,
+                                               out=(full(p.n_out) if out is None else out) if "out" in want else None)
     torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in r.items()}
+    res = {k: v.cpu().numpy() for k, v in r.items()}
     if sm:
         for k in ("x", "out"):
-            if k in out:
-                out[k + "_buffer"] = out[k]
-                out[k] = np.ascontiguousarray(out[k][:, row0:row0 + T].transpose(1, 0, 2))
-    return out
+            if k in res:
+                res[k + "_buffer"] = res[k]
+                res[k] = np.ascontiguousarray(res[k][:, row0:row0 + T].transpose(1, 0, 2))
+        res["target_sent"], res["target_after"] = sent, tgd.cpu().numpy()
+    return res
 
 
 def check(p, got, want, what):
