@@ -641,6 +641,54 @@ int fz_program_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, 
 long fz_program_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 long fz_program_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 
+/* fz_run_recording_grad, fz_run_recording_loss_grad -- the backward of a whole RECORDING of T rows in bounded workspace.
+ *
+ * THE CONTRACT (stated here once).  Every output bit -- in_grad, state0_grad, param_grad, const_grad, loss, out -- is that of the
+ * one-launch call over the same T rows, fz_run_block_grad or fz_run_block_loss_grad (for FZ_GRAD_STREAM_MAJOR: their _stream_major
+ * siblings over the window [row0, row0 + n_samples) of rows_total), whatever block_rows is; state_out, if not NULL, receives the
+ * state after the last row with the bits of fz_run_block's state.  The arguments are those calls' (fz_grad_args / fz_loss_grad_args
+ * over T rows, accumulators ADDED TO, state0_grad may be state_grad), plus the layout, block_rows and state_out.
+ *
+ * How: two-level checkpointing.  One launch of a block-start-states kernel runs the recording forward and stores only the state
+ * before rows 0, B, 2B, ...; then the adjoint (or loss) kernel of the one-block calls is launched once per block, from the last
+ * block to the first: block k covers rows [k B, min((k + 1) B, T)) with state = the k-th stored state, state_grad = the state0_grad
+ * of the launch before it (in place) and the caller's accumulators throughout -- the chaining those calls document.  x is read
+ * once more than by the one-launch call; the workspace holds ceil(T / B) + ceil(B / C) row sets instead of ceil(T / C).
+ *
+ * B: block_rows, or for block_rows == 0 the B that minimises ceil(B / C) + ceil(T / B): sqrt(T * C) rounded up to a multiple of
+ * lcm(4, C), and B = T when that is not smaller than T.  A block_rows above T means one block of T rows.
+ * fz_program_recording_block_rows answers the B a call will use.
+ * WORKSPACE (the formula, stated here once): (ceil(T / B) + ceil(B / C)) * n_state * n_streams * 4 bytes, B as above, C the
+ * checkpoint stride of fz_program_grad_workspace; fz_program_recording_workspace answers it.  One caller-owned buffer: the
+ * block-start states [ceil(T / B)][n_state][n_streams] lie at its head, the workspace of the block launches behind them.
+ *
+ * Layout: FZ_GRAD_TIME_MAJOR -- frames [T][n_streams][wire], blocks are pointer offsets, so block_rows must be a multiple of 4 (the
+ * 16-byte pointer rule of every launch; FZ_E_INVALID otherwise), row0 must be 0 and rows_total 0 or n_samples.
+ * FZ_GRAD_STREAM_MAJOR -- buffers [n_streams][rows_total][wire], block k is the window row0 + k B, and every such window passes the
+ * checks of fz_run_block_grad_stream_major (with more than one block: block_rows * n_in and block_rows * n_out multiples of 4).
+ * The state and the workspace of a block launch are the library's own [row][n_streams] rows of the caller's workspace, touched in
+ * 4-byte accesses per lane like the checkpoint rows of any launch: the 16-byte rule is asked of the caller's pointers only.
+ * Checks, all before a device is needed: the refusals of fz_program_grad_check, unchanged; those of the one-launch call over the T
+ * rows (state_out counted as an output) with this call's workspace size; those of every block launch; n_samples < 2^31; with more
+ * than one block and delay lines, state0_grad must not be NULL (the blocks chain through it).  n_streams == 0 or n_samples == 0:
+ * FZ_OK, nothing is touched.  A graph without delay lines launches no states kernel; a graph without inputs reads no frames.
+ * Asynchronous on hip_stream like the one-block calls.
+ *
+ * The states kernel is a kernel text of its own per layout, fz_states_kernel_u<U>b<lanes>_g<tag> and
+ * fz_states_sm_kernel_u<U>r<R>b<lanes>_g<tag> (U rows per unrolled group; R rows of the LDS patch x moves through, x only:
+ * lds_bytes = 4 waves * 64 * (R * n_in + 4) * 4; none for a graph without input wires, and none for one without delay lines, whose
+ * kernel has nothing to store and is never launched); fz_program_states_* inspect it like their _grad_ twins. */
+int fz_program_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
+                                   uint32_t layout, uint64_t* bytes);
+int fz_program_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows);
+int fz_run_recording_grad(fz_program* p, const fz_grad_args* a, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                          uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream);
+int fz_run_recording_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                               uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream);
+int fz_program_states_resources(fz_program* p, uint32_t layout, fz_kernel_resources* out);
+long fz_program_states_kernel_symbol(fz_program* p, uint32_t layout, char* buf, size_t cap);
+long fz_program_states_source(fz_program* p, uint32_t layout, char* buf, size_t cap);
+
 /* ------------------------------------------------------------------------------------------
  * 16-bit PCM frames.  fz_run_block_pcm16 is fz_run_block for a block whose frames are int16 on one side or on both: the caller
  * sends and receives 2 bytes per sample instead of 4, the conversions happen in the kernel.

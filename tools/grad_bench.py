@@ -22,7 +22,14 @@ loss).  route: the forward launch, torch's ((y - target) ** 2).mean() and its de
 same buffers, same process, legs interleaved as for --layout compare (100 ms of the route first, then --steps launches per leg in a
 forward and again in a backward pass over the legs).  The table goes to stdout and to profiles/r10/loss_grad.txt.
 
-usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss]
+--recording: the squared-error backward of a whole RECORDING, run_recording_loss_grad (fz_run_recording_loss_grad: one block-start-states
+launch, then the loss kernel per block in reverse), against two alternatives on the same buffers, interleaved in one process as --loss
+does.  one: the one-launch run_block_loss_grad over all rows, where its workspace fits the board's free memory.  route: what a caller
+had before -- run_block per block into a scratch y (only to get the state before every block), then run_block_loss_grad per block from
+the last to the first, chained through state0_grad and the accumulators.  1 048 576 x 4096 and 65 536 x 16 384, both layouts; printed
+with each route's workspace bytes.  The table goes to stdout and to profiles/r11/recording.txt.
+
+usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording]
 """
 import argparse
 import datetime
@@ -199,6 +206,112 @@ def loss_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
+REC_SHAPES = {"large": [(1 << 20, 4096)], "small": [(65536, 16384)]}
+
+
+def recording_bench(a, torch):
+    """the backward of a whole recording under a mean squared error: the recording call, the one-launch call, and blocks chained by hand"""
+    import time
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+    props = torch.cuda.get_device_properties(0)
+    say(f"# command: tools/grad_bench.py --recording --steps {a.steps} --legs {a.legs}")
+    say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+    say("# rec = one run_recording_loss_grad call; one = one run_block_loss_grad launch over all rows (where its workspace fits);")
+    say("# route = run_block per block into a scratch y for the states, then run_block_loss_grad per block in reverse (same B as rec)")
+    say(f"# HIP events, {a.steps} calls per leg and pass, a forward and a backward pass over the legs; spread = max - min of a leg's own repeats")
+    say(f"{'graph':20s} {'layout':>12s} {'streams x T':>16s} {'B':>5s} {'route ms':>9s} {'spread':>7s} {'rec ms':>9s} {'spread':>7s} {'one ms':>9s} {'spread':>7s} "
+        f"{'rec/route':>9s} {'rec/one':>8s} {'ws rec MB':>10s} {'ws route MB':>11s} {'ws one MB':>10s}  states kernel")
+    shapes = REC_SHAPES["small"] + REC_SHAPES["large"] if a.legs == "all" else REC_SHAPES[a.legs]
+    want = ("x", "state", "params", "consts", "loss")
+    for ns, T in shapes:
+        for sm in (False, True):
+            x = torch.empty((ns, T, 1) if sm else (T, ns, 1), dtype=torch.float32, device="cuda")
+            F.synth_fill(x, seed=W.SEED)
+            target = torch.empty_like(x)
+            F.synth_fill(target, seed=W.SEED + 1)
+            gx = torch.empty_like(x)
+            n = float(ns) * T
+            for name, fn in GRAPHS.items():
+                prog = F.compile(F.from_sexpr(fn()))
+                pp = params_for(name, prog, ns, torch)
+                s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+                B = prog.recording_block_rows(T)
+                nb = (T + B - 1) // B
+                ws_rec, ws_one = prog.recording_workspace_bytes(ns, T, stream_major=sm), prog.grad_workspace_bytes(ns, T)
+                # the route keeps the state before every block itself, a scratch y of one block, and one block's checkpoints
+                ws_route = nb * prog.n_state * ns * 4 + B * ns * prog.n_out * 4 + prog.grad_workspace_bytes(ns, B)
+                ws = torch.empty(ws_rec // 4, dtype=torch.float32, device="cuda")
+                states = torch.empty((nb + 1, prog.n_state, ns), dtype=torch.float32, device="cuda")
+                y = torch.empty_like(x) if sm else torch.empty((B, ns, 1), dtype=torch.float32, device="cuda")
+                if sm:
+                    ws_route += (T - B) * ns * prog.n_out * 4     # (a stream-major window writes into a buffer of all rows)
+
+                def rec():
+                    r = prog.run_recording_loss_grad(x, target, s0, pp, grad_scale=2.0 / n, want=want, stream_major=sm, in_grad=gx if sm else None, workspace=ws)
+                    return r["loss"].double().sum() / n
+
+                def route():
+                    states[0].copy_(s0)
+                    for k in range(nb):
+                        rows = min(B, T - k * B)
+                        states[k + 1].copy_(states[k])
+                        if sm:
+                            prog.run_block_stream_major(x, state=states[k + 1], params=pp, out=y, row0=k * B, n_samples=rows)
+                        else:
+                            prog.run_block(x[k * B:k * B + rows], state=states[k + 1], params=pp, out=y[:rows])
+                    acc, sg = {}, None
+                    for k in range(nb - 1, -1, -1):
+                        rows = min(B, T - k * B)
+                        if sm:
+                            r = prog.run_block_loss_grad_stream_major(x, target, states[k], pp, state_grad=sg, grad_scale=2.0 / n, want=want, accum=acc,
+                                                                      row0=k * B, n_samples=rows, in_grad=gx)
+                        else:
+                            r = prog.run_block_loss_grad(x[k * B:k * B + rows], target[k * B:k * B + rows], states[k], pp, state_grad=sg, grad_scale=2.0 / n,
+                                                         want=want, accum=acc)
+                        # (the accumulators the next launch adds to: only those the graph has rows of)
+                        acc, sg = {k: r[k] for k, rows_k in (("params", prog.n_param), ("consts", prog.n_const), ("loss", 1)) if rows_k}, r["state"]
+                    return acc["loss"].double().sum() / n
+
+                def one():
+                    f = prog.run_block_loss_grad_stream_major if sm else prog.run_block_loss_grad
+                    r = f(x, target, s0, pp, grad_scale=2.0 / n, want=want, **({"in_grad": gx} if sm else {}))
+                    return r["loss"].double().sum() / n
+                legs = {"route": route, "rec": rec}
+                if ws_one + (4 << 30) < torch.cuda.mem_get_info()[0]:
+                    legs["one"] = one
+                vals = {k: float(f()) for k, f in legs.items()}        # JIT, allocator; and the legs agree on the loss
+                assert all(v == vals["rec"] for v in vals.values()), vals     # (bit for bit: the same per-stream sums)
+                torch.cuda.synchronize()
+                t_end = time.time() + 0.1
+                while time.time() < t_end:                          # at least 100 ms of the yardstick before the first timing
+                    route()
+                    torch.cuda.synchronize()
+                got = {k: [] for k in legs}
+                for order in (list(legs), list(legs)[::-1]):
+                    for k in order:
+                        got[k] += samples(legs[k], a.steps, torch)
+                med = {k: float(np.median(v)) for k, v in got.items()}
+                sp = {k: max(v) - min(v) for k, v in got.items()}
+                one_s = f"{med['one']:9.3f} {sp['one']:7.3f}" if "one" in med else f"{'-':>9s} {'-':>7s}"
+                ratio_one = f"{med['rec'] / med['one']:8.3f}" if "one" in med else f"{'-':>8s}"
+                say(f"{name:20s} {'stream-major' if sm else 'time-major':>12s} {f'{ns} x {T}':>16s} {B:5d} {med['route']:9.3f} {sp['route']:7.3f} "
+                    f"{med['rec']:9.3f} {sp['rec']:7.3f} {one_s} {med['rec'] / med['route']:9.3f} {ratio_one} {ws_rec / 2**20:10.1f} {ws_route / 2**20:11.1f} "
+                    f"{ws_one / 2**20:10.1f}  {prog.states_kernel_symbol(sm)}")
+                say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
+                del pp, s0, ws, states, y
+                torch.cuda.empty_cache()
+            del x, target, gx
+            torch.cuda.empty_cache()
+    out = os.path.join(ROOT, "profiles", "r11", "recording.txt")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
@@ -206,12 +319,15 @@ def main():
     ap.add_argument("--legs", choices=("small", "large", "all"), default="all")
     ap.add_argument("--layout", choices=("time-major", "stream-major", "compare"), default="time-major")
     ap.add_argument("--loss", action="store_true", help="the fused squared-error backward against forward + torch MSE + backward, both layouts")
+    ap.add_argument("--recording", action="store_true", help="the backward of a whole recording against the one-launch call and blocks chained by hand")
     a = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
     if a.loss:
         return loss_bench(a, torch)
+    if a.recording:
+        return recording_bench(a, torch)
     props = torch.cuda.get_device_properties(0)
     if a.layout == "compare":
         print(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")

@@ -4,6 +4,7 @@
 usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par4|par4f|osc|df1|ring)
        tools/isa_stats.py lossgrad [graph] [tm|sm]         the kernel of fz_run_block_loss_grad (sm: _stream_major) next to the plain
                                                            adjoint kernel: registers, spills, LDS (graph: also cascade_params6)
+       tools/isa_stats.py states [graph] [tm|sm]           the block-start-states kernel of fz_run_recording_grad: registers, spills, LDS
 """
 import glob
 import os
@@ -63,8 +64,18 @@ def loss_grad_line(name, sm):
             f"{r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS")
 
 
+def states_line(name, sm):
+    p = F.compile(F.from_sexpr(GRAPHS[name]()))
+    r = p.states_resources(sm)
+    return (f"{name} {'stream' if sm else 'time'}-major {p.states_kernel_symbol(sm)}: U {r['unroll']}, {r['vgprs'] + r['agprs']} VGPRs, "
+            f"{r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills, {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS")
+
+
 def main():
     a = sys.argv[1:]
+    if a and a[0] == "states":
+        print(states_line(a[1] if len(a) > 1 else "cascade_params6", len(a) > 2 and a[2] == "sm"))
+        return
     if a and a[0] == "lossgrad":
         print(loss_grad_line(a[1] if len(a) > 1 else "cascade_params6", len(a) > 2 and a[2] == "sm"))
         return

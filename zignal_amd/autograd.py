@@ -10,6 +10,10 @@ lies: the forward is Program.run_block_stream_major, the backward Program.run_bl
 mse(prog, x, target, ...) is the mean squared error of one block against a target as ONE launch (Program.run_block_loss_grad:
 the adjoint kernel forms y, the error and dL/dy itself), where run() followed by ((y - target) ** 2).mean() is a forward launch,
 several elementwise kernels and the backward launch.
+
+mse_recording(prog, x, target, ...) is the same loss over a whole recording of many blocks in bounded workspace
+(Program.run_recording_loss_grad: one forward launch that keeps the state before every block, then the loss kernel block by block
+from the last to the first), and also returns the state after the recording.
 """
 from __future__ import annotations
 
@@ -127,3 +131,45 @@ def mse(prog: Program, x, target, state=None, params=None, consts=None, stream_m
         if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
             raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
     return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major))
+
+
+class _MseRecording(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, prog, x, target, state, params, consts, block_rows=0, stream_major=False):
+        _apply_consts(prog, consts)
+        _, need_x, _, need_s, need_p, need_c = ctx.needs_input_grad[:6]
+        want = ["loss", "state_out"] + [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
+        xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
+        n = xx.shape[0] * xx.shape[1] * prog.n_out                    # elements of y: the mean is over all of them
+        r = prog.run_recording_loss_grad(xx, target.detach().contiguous(), state.detach() if state is not None else None,
+                                         params.detach() if params is not None else None, grad_scale=2.0 / n, want=want,
+                                         block_rows=int(block_rows), stream_major=bool(stream_major))
+        ctx.grads = (r["x"].reshape(x.shape) if need_x else None, r["state"] if need_s else None, r["params"] if need_p else None,
+                     # per-stream coefficient adjoints, summed over the streams in float64
+                     r["consts"][:prog.n_const].double().sum(1).to(consts.dtype).to(consts.device) if need_c else None)
+        ctx.mark_non_differentiable(r["state_out"])
+        return (r["loss"].double().sum() / n).to(torch.float32), r["state_out"]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gs):
+        gx, gs, gp, gc = ctx.grads
+        scaled = lambda t: None if t is None else t * g.to(t.device)   # noqa: E731  (the upstream scalar)
+        return None, scaled(gx), None, scaled(gs), scaled(gp), scaled(gc), None, None
+
+
+def mse_recording(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0, stream_major=False):
+    """mse() over a whole RECORDING: returns (loss, state_out).  loss is ((y - target) ** 2).mean() over all rows of x, differentiable as
+    mse() is; state_out is the state after the last row, detached, so the caller can continue the stream (pass it as `state` of the
+    next call).  The workspace is bounded (Program.recording_workspace_bytes: the state before every block of block_rows rows plus
+    one block's checkpoints; block_rows = 0 lets the library choose), where mse() over the same rows keeps a checkpoint every few rows
+    of the whole recording.  The gradients have the bits of mse()'s over the same rows.  Time-major frames need block_rows % 4 == 0."""
+    if not prog.grad_supported():
+        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.grad_unsupported_reason())
+    if x.dim() == 2 and prog.n_in != 1:
+        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
+    if consts is not None:
+        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
+            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
+    loss, state_out = _MseRecording.apply(prog, x, target, state, params, consts, int(block_rows), bool(stream_major))
+    return loss, state_out.detach()

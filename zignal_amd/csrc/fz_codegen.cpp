@@ -29,6 +29,8 @@ extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a ker
 extern const char* const kSkeletonAdjointSm; // fz_kernel_adjoint_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonAdjointLoss;   // fz_kernel_adjoint_loss.hip.inc: the adjoint kernel that forms dL/dy from a target
 extern const char* const kSkeletonAdjointLossSm; // fz_kernel_adjoint_loss_sm.hip.inc: the same for stream-major buffers
+extern const char* const kSkeletonStates;     // fz_kernel_states.hip.inc: the block-start states of a recording (the adjoint body's fwd alone)
+extern const char* const kSkeletonStatesSm;   // fz_kernel_states_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
@@ -40,6 +42,8 @@ const std::string& skeleton_source(const Variant& v)
                             ws = head + kSkeletonBody_wave_split, fr = head + kSkeletonBody_frames;
    static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm, pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
    static const std::string adj_loss = kSkeletonAdjointLoss, adj_loss_sm = kSkeletonAdjointLossSm;
+   static const std::string states = kSkeletonStates, states_sm = kSkeletonStatesSm;
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES)) return (v.flags & FZ_VF_ADJOINT_SM) ? states_sm : states;
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_LOSS)) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_loss_sm : adj_loss;
    if (v.flags & FZ_VF_ADJOINT) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_sm : adj;
    if (v.flags & FZ_VF_PCM16) return (v.flags & FZ_VF_PCM16_SM) ? pcm_sm : pcm;
@@ -51,6 +55,9 @@ const std::string& skeleton_source(const Variant& v)
 // fz_block_kernel_p<streams/lane>u<unroll>b<block>[s<segments>]f<flags>
 std::string kernel_name(const Graph& g, const Variant& v)
 {
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES))   // (the states bit means something next to FZ_VF_ADJOINT only)
+      return (v.flags & FZ_VF_ADJOINT_SM) ? "fz_states_sm_kernel_u" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block)
+                                          : "fz_states_kernel_u" + std::to_string(v.U) + "b" + std::to_string(v.block);
    const std::string adj = (v.flags & FZ_VF_ADJOINT_LOSS) ? "fz_adjoint_loss" : "fz_adjoint";   // (the loss bit means something next to FZ_VF_ADJOINT only)
    if (v.flags & FZ_VF_ADJOINT_SM)
       return adj + "_sm_kernel_c" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block);
@@ -1046,13 +1053,14 @@ std::string full_source(const Graph& g, const Variant& v)
 std::string gen_adjoint_config(const Graph& g, const Variant& v)
 {
    std::ostringstream o;
-   o << "// generated by libflowz_hip -- adjoint kernel configuration\n";
+   o << ((v.flags & FZ_VF_STATES) ? "// generated by libflowz_hip -- block-start-states kernel configuration\n" : "// generated by libflowz_hip -- adjoint kernel configuration\n");
    o << "#define FZ_NIN " << g.n_in << "\n";
    o << "#define FZ_NOUT " << g.n_out << "\n";
    o << "#define FZ_NCONST " << g.consts.size() << "\n";
    o << "#define FZ_NPARAM " << g.n_param << "\n";
    o << "#define FZ_NSTATE " << g.n_state << "\n";
-   o << "#define FZ_C " << v.U << "   // checkpoint rows: the chunk sweep 2 re-runs and walks backwards\n";
+   if (v.flags & FZ_VF_STATES) o << "#define FZ_U " << v.U << "   // rows per unrolled group of the forward recursion\n";
+   else o << "#define FZ_C " << v.U << "   // checkpoint rows: the chunk sweep 2 re-runs and walks backwards\n";
    if (v.flags & FZ_VF_ADJOINT_SM) o << "#define FZ_R " << v.P << "   // rows per LDS patch of the stream-major frames\n";
    o << "#define FZ_BLOCK " << v.block << "\n";
    o << "#define FZ_KERNEL " << kernel_symbol(g, v) << "\n";

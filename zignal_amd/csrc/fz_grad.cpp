@@ -4,6 +4,10 @@
 // go through the kernel cache as a Variant with FZ_VF_ADJOINT (and FZ_VF_ADJOINT_SM).
 // The backward under a squared-error loss (fz_run_block_loss_grad, fz_run_block_loss_grad_stream_major) is the same call with dL/dy
 // formed in the kernel from a target: FZ_VF_ADJOINT_LOSS on the Variant, fz_kernel_adjoint_loss.hip.inc / fz_kernel_adjoint_loss_sm.hip.inc.
+// The backward of a whole recording (fz_run_recording_grad, fz_run_recording_loss_grad) is two-level checkpointing over those: one
+// launch of the block-start-states kernel (FZ_VF_STATES; fz_kernel_states.hip.inc / fz_kernel_states_sm.hip.inc), then the launches
+// above block by block from the last to the first.
+#include <cmath>
 #include <algorithm>
 #include <cstddef>
 #include <cstring>
@@ -84,6 +88,46 @@ bool adjoint_variant_fits(const Graph& g, const Variant& v)
    return v.P >= 4 && !(v.P & (v.P - 1)) && v.P % v.U == 0 && v.P <= grad_sm_max_patch_rows() && sm_patch_bytes(g, v.P) <= kLdsBytes;
 }
 
+// The block-start-states kernel (FZ_VF_STATES): U, the rows of one unrolled group -- two groups of U * n_in frame registers are alive
+// (the group the recursion runs and the one requested for the next trip): 8 rows, halved while a group passes 16 floats.
+static uint32_t states_unroll(const Graph& g)
+{
+   uint32_t U = 8;
+   while (U > 1 && U * g.n_in > 16) U /= 2;
+   return U;
+}
+
+// Its stream-major text moves x through a wave-private LDS patch of R rows like sweep 1 of the stream-major adjoint kernel, but the
+// patch carries x only: a patch row is R * n_in + 4 floats.  R is a power of two >= 4 long enough that the run of one stream is a
+// whole 128-byte cache line (32 rows for one input wire: 9 KB per wave, 36 KB per workgroup); a multiple of U, which is at most 8
+// and at most 16 / n_in.
+static uint32_t states_sm_patch_bytes(const Graph& g, uint32_t R) { return g.n_in ? (R * g.n_in + 4u) * 4u * kGradBlock : 0u; }
+uint32_t states_sm_patch_rows(const Graph& g)
+{
+   uint32_t R = 4;
+   while (R * g.n_in < 32 && g.n_in) R *= 2;
+   return R;
+}
+
+static Variant states_variant_unchecked(const Graph& g, bool stream_major)
+{
+   Variant v;
+   v.P = stream_major ? states_sm_patch_rows(g) : 1;       // (the patch rows travel in P, as for the adjoint kernel)
+   v.U = stream_major ? std::min(states_unroll(g), v.P) : states_unroll(g);
+   v.block = kGradBlock;
+   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | (stream_major ? FZ_VF_ADJOINT_SM : 0u);
+   return v;
+}
+
+// could states_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
+bool states_variant_fits(const Graph& g, const Variant& v)
+{
+   if ((v.flags & ~FZ_VF_ADJOINT_SM) != (FZ_VF_ADJOINT | FZ_VF_STATES) || !grad_unsupported_reason(g).empty()) return false;
+   const bool sm = (v.flags & FZ_VF_ADJOINT_SM) != 0;
+   const Variant w = states_variant_unchecked(g, sm);
+   return v.P == w.P && v.U == w.U && v.block == w.block && (!sm || states_sm_patch_bytes(g, v.P) <= kLdsBytes);
+}
+
 static uint32_t checkpoint_of(const Graph& g, uint32_t checkpoint_rows)
 {
    if (checkpoint_rows == 0) return grad_default_checkpoint(g);
@@ -114,6 +158,16 @@ static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool st
    return v;
 }
 
+static Variant states_variant(const Graph& g, bool stream_major)
+{
+   require_supported(g);
+   const Variant v = states_variant_unchecked(g, stream_major);
+   if (stream_major && states_sm_patch_bytes(g, v.P) > kLdsBytes)
+      fail(FZ_E_UNSUPPORTED, "stream-major recording: a patch of " + std::to_string(v.P) + " rows of " + std::to_string(g.n_in) +
+                                " input wires does not fit the LDS of a workgroup");
+   return v;
+}
+
 static bool layout_is_stream_major(uint32_t layout)
 {
    if (layout != FZ_GRAD_TIME_MAJOR && layout != FZ_GRAD_STREAM_MAJOR) fail(FZ_E_INVALID, "layout must be FZ_GRAD_TIME_MAJOR or FZ_GRAD_STREAM_MAJOR");
@@ -125,6 +179,37 @@ static uint64_t workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t n_s
    const uint64_t chunks = ((uint64_t)n_samples + C - 1) / C;
    return chunks * g.n_state * n_streams * 4u;
 }
+
+// The rows per block of a recording of T rows (the one home of this rule; include/flowz_hip.h states it).  block_rows == 0: the B that
+// minimises the row sets kept, ceil(B / C) + ceil(T / B) -- sqrt(T * C) rounded up to a multiple of lcm(4, C) = max(4, C) (time-major
+// blocks are pointer offsets and keep the 16-byte alignment; checkpoint chunks stay whole), and B = T when that is not smaller.
+// A block_rows beyond T is one block of T rows.
+static uint32_t recording_block_rows(uint32_t T, uint32_t C, uint32_t block_rows)
+{
+   if (block_rows) return std::min(block_rows, T);
+   const uint64_t m = std::max<uint32_t>(4u, C);
+   uint64_t B = (uint64_t)std::ceil(std::sqrt((double)T * (double)C));
+   while (B * B < (uint64_t)T * C) ++B;                      // (whatever sqrt rounded: B is the least integer with B^2 >= T C)
+   B = (B + m - 1) / m * m;
+   return B < T ? (uint32_t)B : T;
+}
+
+// bytes of the block-start states, [ceil(T / B)][n_state][n_streams] floats: the head of a recording's workspace
+static uint64_t starts_bytes(const Graph& g, uint64_t n_streams, uint32_t T, uint32_t B) { return (((uint64_t)T + B - 1) / B) * g.n_state * n_streams * 4u; }
+
+// kernarg image of `struct fz_states_args` (fz_kernel_states.hip.inc) up to the coefficient tail; `struct fz_states_sm_args`
+// (fz_kernel_states_sm.hip.inc) has rows_total and row0 behind it
+struct StatesArgsHeader {
+   const float* in;
+   const float* state;
+   const float* params;
+   float* starts;
+   float* state_out;
+   unsigned long long n_streams;
+   unsigned int n_samples;
+   unsigned int block_rows;
+};
+static_assert(sizeof(StatesArgsHeader) == 5 * 8 + 8 + 2 * 4, "StatesArgsHeader must match the head of the kernel's fz_states_args without padding");
 
 // kernarg image of `struct fz_adj_args` (fz_kernel_adjoint.hip.inc) up to the coefficient tail
 struct AdjArgsHeader {
@@ -218,12 +303,24 @@ static GradCall call_of(fz_program* p, const fz_loss_grad_args* a0)
                    a->workspace, a->workspace_bytes, true, a->grad_scale, a->loss, a->out};
 }
 
-static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm = nullptr)
+// what a recording adds to the checks of a block: its own workspace size (and the call that answers it), and state_out as one more output
+struct RecordingCheck {
+   uint64_t need;
+   float* state_out;
+};
+
+// every argument check of a backward, before a device is needed; false: an empty block (FZ_OK, nothing to launch).  rec: the call is a
+// whole recording (fz_run_recording_grad), checked over its T rows.  own_rows: the call is a block launch of a recording, whose `state` and
+// `workspace` are the library's own rows of the caller's workspace -- [row][n_streams] rows at offsets of whole rows, read and written
+// per lane in 4-byte accesses like the checkpoint rows of any launch, so the 16-byte rule of the caller's pointers is not asked of them
+static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uint32_t n_samples, const SmWindow* sm, Variant* vout,
+                       const RecordingCheck* rec = nullptr, bool own_rows = false)
 {
    const GradCall* const a = &call;
    const Graph& g = p->g;
    const Variant v = adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
-   if (n_streams == 0 || n_samples == 0) return FZ_OK;     // an empty block: nothing to differentiate, nothing touched
+   *vout = v;
+   if (n_streams == 0 || n_samples == 0) return false;     // an empty block: nothing to differentiate, nothing touched
    if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
    if (sm) {
       if ((uint64_t)sm->row0 + n_samples > sm->rows_total)
@@ -241,10 +338,11 @@ static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uin
    if (g.n_param && !a->params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
    if (a->loss_rule && !a->ybar) fail(FZ_E_INVALID, "target is null: the loss compares the outputs with it");
    if (g.n_out && !a->ybar) fail(FZ_E_INVALID, "out_grad is null but the graph has output wires");
-   const uint64_t need = workspace_bytes(g, n_streams, n_samples, v.U);
-   if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: fz_program_grad_workspace says " + std::to_string(need) + " bytes");
+   const uint64_t need = rec ? rec->need : workspace_bytes(g, n_streams, n_samples, v.U);
+   const std::string ws_fn = rec ? "fz_program_recording_workspace" : "fz_program_grad_workspace";
+   if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: " + ws_fn + " says " + std::to_string(need) + " bytes");
    if (need && a->workspace_bytes < need)
-      fail(FZ_E_INVALID, "workspace_bytes " + std::to_string(a->workspace_bytes) + " is less than the " + std::to_string(need) + " bytes fz_program_grad_workspace asks for");
+      fail(FZ_E_INVALID, "workspace_bytes " + std::to_string(a->workspace_bytes) + " is less than the " + std::to_string(need) + " bytes " + ws_fn + " asks for");
    // (bytes of one wire's frames: a stream-major buffer is touched over its whole extent, n_streams * rows_total rows)
    const uint64_t fr = (uint64_t)(sm ? sm->rows_total : n_samples) * n_streams * 4u, row = n_streams * 4u;
    struct Buf {
@@ -252,18 +350,20 @@ static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uin
       uint64_t bytes;
       const char* name;
       bool out;
+      bool own = false;        // one of the library's own rows in a block launch of a recording: no 16-byte rule (see above)
    };
    // (only what the kernel touches: buffers of zero rows are never dereferenced)
-   const std::vector<Buf> bufs = {
-      {a->in, g.n_in ? fr * g.n_in : 0, "in", false},          {a->state, row * g.n_state, "state", false},
+   std::vector<Buf> bufs = {
+      {a->in, g.n_in ? fr * g.n_in : 0, "in", false},          {a->state, row * g.n_state, "state", false, own_rows},
       {a->params, row * g.n_param, "params", false},           {a->ybar, g.n_out ? fr * g.n_out : 0, a->loss_rule ? "target" : "out_grad", false},
       {a->state_grad, row * g.n_state, "state_grad", false},   {a->in_grad, g.n_in ? fr * g.n_in : 0, "in_grad", true},
       {a->state0_grad, row * g.n_state, "state0_grad", true},  {a->param_grad, row * g.n_param, "param_grad", true},
-      {a->const_grad, row * g.consts.size(), "const_grad", true}, {a->workspace, need, "workspace", true},
+      {a->const_grad, row * g.consts.size(), "const_grad", true}, {a->workspace, need, "workspace", true, own_rows},
       {a->loss, row, "loss", true},                            {a->out, g.n_out ? fr * g.n_out : 0, "out", true},
    };
+   if (rec) bufs.push_back({rec->state_out, row * g.n_state, "state_out", true});
    for (const Buf& b : bufs)
-      if (b.ptr && (reinterpret_cast<uintptr_t>(b.ptr) & 15u)) fail(FZ_E_INVALID, std::string(b.name) + ": device pointers must be 16-byte aligned");
+      if (b.ptr && !b.own && (reinterpret_cast<uintptr_t>(b.ptr) & 15u)) fail(FZ_E_INVALID, std::string(b.name) + ": device pointers must be 16-byte aligned");
    for (size_t i = 0; i < bufs.size(); ++i)
       for (size_t j = i + 1; j < bufs.size(); ++j) {
          const Buf &x = bufs[i], &y = bufs[j];
@@ -272,7 +372,14 @@ static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uin
          const uintptr_t x0 = reinterpret_cast<uintptr_t>(x.ptr), y0 = reinterpret_cast<uintptr_t>(y.ptr);
          if (x0 < y0 + y.bytes && y0 < x0 + x.bytes) fail(FZ_E_INVALID, std::string(x.name) + " and " + y.name + " overlap");
       }
-   require_device();
+   return true;
+}
+
+// the launch of a checked backward (a device is at hand)
+static void launch_grad(fz_program* p, const Variant& v, const GradCall& call, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm)
+{
+   const GradCall* const a = &call;
+   const Graph& g = p->g;
    void* fn = nullptr;
    (void)get_kernel(p, v, &fn);
    // (the size of the kernel's argument struct: 8-byte aligned -- a buffer of another size does not launch that struct)
@@ -303,6 +410,111 @@ static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uin
    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
    const unsigned grid = (unsigned)((n_streams + v.block - 1) / v.block);
    FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+}
+
+static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm = nullptr)
+{
+   Variant v;
+   if (!check_grad(p, call, n_streams, n_samples, sm, &v)) return FZ_OK;
+   require_device();
+   launch_grad(p, v, call, n_streams, n_samples, stream, sm);
+   return FZ_OK;
+}
+
+// One launch of the block-start-states kernel over the recording (checked by the caller; n_state > 0).
+static void launch_states(fz_program* p, const Variant& v, const GradCall& a, float* starts, float* state_out, uint64_t n_streams, uint32_t n_samples,
+                          uint32_t B, void* stream, const SmWindow* sm)
+{
+   const Graph& g = p->g;
+   void* fn = nullptr;
+   (void)get_kernel(p, v, &fn);
+   const size_t hbytes = sizeof(StatesArgsHeader) + (sm ? 2 * sizeof(unsigned int) : 0);
+   const size_t kbytes = (hbytes + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
+   std::vector<char> kbuf(kbytes, 0);
+   const StatesArgsHeader h{a.in, a.state, a.params, starts, state_out, (unsigned long long)n_streams, n_samples, B};
+   std::memcpy(kbuf.data(), &h, sizeof h);
+   if (sm) {
+      const unsigned int win[2] = {sm->rows_total, sm->row0};
+      std::memcpy(kbuf.data() + sizeof h, win, sizeof win);
+   }
+   {
+      std::lock_guard<std::mutex> lock(p->mu);
+      if (!g.consts.empty()) std::memcpy(kbuf.data() + hbytes, g.consts.data(), sizeof(float) * g.consts.size());
+   }
+   size_t size = kbytes;
+   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+   const unsigned grid = (unsigned)((n_streams + v.block - 1) / v.block);
+   FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+}
+
+static uint64_t recording_workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t T, uint32_t B, uint32_t C)
+{
+   return T ? starts_bytes(g, n_streams, T, B) + workspace_bytes(g, n_streams, B, C) : 0;
+}
+
+// The backward of a recording: the states kernel once, then the block launches from the last block to the first (the contract is in
+// include/flowz_hip.h).  Every check -- of the call over its T rows, then of every block launch as a direct call would be checked --
+// runs before a device is needed.
+static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
+                         uint32_t block_rows, float* state_out, void* stream)
+{
+   const Graph& g = p->g;
+   const bool stream_major = layout_is_stream_major(layout);
+   require_supported(g);                                   // (scope first: the refusals of fz_program_grad_check)
+   // (a graph without delay lines launches no states kernel: its LDS patch is not asked to fit)
+   const Variant sv = g.n_state ? states_variant(g, stream_major) : Variant{};
+   if (!stream_major && block_rows % 4)
+      fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
+   if (!stream_major && (row0 || (rows_total && rows_total != n_samples)))
+      fail(FZ_E_INVALID, "time-major frames have no window: row0 must be 0 and rows_total 0 or n_samples");
+   if (n_samples >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
+   const SmWindow whole{rows_total, row0};
+   const SmWindow* const sm = stream_major ? &whole : nullptr;
+   Variant v;
+   {
+      // (C is needed for the workspace the checks ask for; adjoint_variant validates checkpoint_rows and the loss's outputs)
+      const Variant v0 = adjoint_variant(g, call.checkpoint_rows, stream_major, call.loss_rule);
+      const uint32_t B0 = n_samples ? recording_block_rows(n_samples, v0.U, block_rows) : 0;
+      const RecordingCheck rec{recording_workspace_bytes(g, n_streams, n_samples, B0, v0.U), state_out};
+      if (!check_grad(p, call, n_streams, n_samples, sm, &v, &rec)) return FZ_OK;
+   }
+   const uint32_t B = recording_block_rows(n_samples, v.U, block_rows), nb = (uint32_t)(((uint64_t)n_samples + B - 1) / B);
+   if (nb > 1 && g.n_state && !call.state0_grad)
+      fail(FZ_E_INVALID, "state0_grad is null: the blocks of a recording chain through it (it may be state_grad)");
+   float* const starts = static_cast<float*>(call.workspace);
+   const uint64_t sbytes = starts_bytes(g, n_streams, n_samples, B), set = (uint64_t)g.n_state * n_streams;   // floats of one [n_state][n_streams]
+   // block k as a call of its own: rows [k B, min((k + 1) B, T)), state = starts[k], the state gradient chained in place
+   auto block_call = [&](uint32_t k, SmWindow* w, uint32_t* rows) {
+      GradCall b = call;
+      *rows = std::min<uint64_t>(B, (uint64_t)n_samples - (uint64_t)k * B);
+      const uint64_t off = (uint64_t)k * B * n_streams;     // frames in front of a time-major block, per wire
+      if (stream_major) *w = SmWindow{rows_total, row0 + k * B};
+      else {
+         if (b.in) b.in += off * g.n_in;
+         if (b.ybar) b.ybar += off * g.n_out;
+         if (b.in_grad) b.in_grad += off * g.n_in;
+         if (b.out) b.out += off * g.n_out;
+      }
+      if (g.n_state) b.state = starts + (uint64_t)k * set;
+      if (k + 1 < nb) b.state_grad = call.state0_grad;
+      b.workspace = static_cast<char*>(call.workspace) + sbytes;
+      b.workspace_bytes = call.workspace_bytes - sbytes;
+      return b;
+   };
+   for (uint32_t k = nb; k-- > 0;) {
+      SmWindow w{};
+      uint32_t rows = 0;
+      Variant vb;
+      (void)check_grad(p, block_call(k, &w, &rows), n_streams, rows, stream_major ? &w : nullptr, &vb, nullptr, true);
+   }
+   require_device();
+   if (g.n_state) launch_states(p, sv, call, starts, state_out, n_streams, n_samples, B, stream, sm);
+   for (uint32_t k = nb; k-- > 0;) {
+      SmWindow w{};
+      uint32_t rows = 0;
+      const GradCall b = block_call(k, &w, &rows);
+      launch_grad(p, v, b, n_streams, rows, stream, stream_major ? &w : nullptr);
+   }
    return FZ_OK;
 }
 
@@ -407,6 +619,59 @@ int fz_run_block_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* 
    FZ_GUARD(
       const SmWindow w{rows_total, row0};
       return run_grad(p, call_of(p, a), n_streams, n_samples, hip_stream, &w);)
+}
+
+int fz_program_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
+                                   uint32_t layout, uint64_t* bytes)
+{
+   FZ_GUARD(
+      if (!p || !bytes) fail(FZ_E_INVALID, "fz_program_recording_workspace: bad arguments");
+      require_supported(p->g);
+      if (!layout_is_stream_major(layout) && block_rows % 4) fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
+      if (n_rows >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
+      const uint32_t C = checkpoint_of(p->g, checkpoint_rows), B = n_rows ? recording_block_rows(n_rows, C, block_rows) : 0;
+      *bytes = recording_workspace_bytes(p->g, n_streams, n_rows, B, C);
+      return FZ_OK;)
+}
+
+int fz_program_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows)
+{
+   FZ_GUARD(
+      if (!p || !rows) fail(FZ_E_INVALID, "fz_program_recording_block_rows: bad arguments");
+      require_supported(p->g);
+      if (n_rows >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
+      *rows = n_rows ? recording_block_rows(n_rows, checkpoint_of(p->g, checkpoint_rows), block_rows) : 0;
+      return FZ_OK;)
+}
+
+int fz_run_recording_grad(fz_program* p, const fz_grad_args* a, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                          uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream)
+{
+   FZ_GUARD(return run_recording(p, call_of(p, a), layout, n_streams, rows_total, row0, n_samples, block_rows, state_out, hip_stream);)
+}
+
+int fz_run_recording_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                               uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream)
+{
+   FZ_GUARD(return run_recording(p, call_of(p, a), layout, n_streams, rows_total, row0, n_samples, block_rows, state_out, hip_stream);)
+}
+
+int fz_program_states_resources(fz_program* p, uint32_t layout, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!p || !out) fail(FZ_E_INVALID, "fz_program_states_resources: bad arguments");
+      *out = resources_of(p, states_variant(p->g, layout_is_stream_major(layout)));
+      return FZ_OK;)
+}
+
+long fz_program_states_kernel_symbol(fz_program* p, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, states_variant(p->g, layout_is_stream_major(layout))); });
+}
+
+long fz_program_states_source(fz_program* p, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, states_variant(p->g, layout_is_stream_major(layout))); });
 }
 
 int fz_program_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)

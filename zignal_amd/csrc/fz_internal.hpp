@@ -189,6 +189,11 @@ constexpr uint32_t FZ_VF_ADJOINT_SM = 1u << 18;
 // squared-error rule of fz_run_block_loss_grad (fz_kernel_adjoint_loss.hip.inc, fz_kernel_adjoint_loss_sm.hip.inc: texts and symbols
 // of their own); one more of the reserved bits.  P, U and block mean what they mean for the plain adjoint variant.
 constexpr uint32_t FZ_VF_ADJOINT_LOSS = 1u << 17;
+// internal, with FZ_VF_ADJOINT (and optionally FZ_VF_ADJOINT_SM): the BLOCK-START-STATES kernel of a recording (fz_grad.cpp:
+// fz_run_recording_grad; fz_kernel_states.hip.inc, fz_kernel_states_sm.hip.inc: texts and symbols of their own), the forward half of
+// the adjoint body alone; one more of the reserved bits.  Such a Variant is {P = 1 (stream-major: the rows of its LDS patch), U = the
+// rows of one unrolled group, block = lanes per workgroup}; fz_grad.cpp: states_variant is the one place that makes one.
+constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte
 // accesses).  FZ_VF_ST_MERGE means for it what it means for the frame kernel.  Such a Variant shares the kernel cache and the manifests
@@ -255,6 +260,9 @@ uint32_t grad_default_checkpoint(const Graph& g);
 uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C);
 uint32_t grad_sm_max_patch_rows();                                 // the longest patch any graph can have (one wire, the whole LDS)
 bool adjoint_variant_fits(const Graph& g, const Variant& v);       // an adjoint Variant the backward could have made for this graph
+// rows per LDS patch of the stream-major block-start-states kernel (x only), a multiple of 4 and of the unrolled group (fz_grad.cpp)
+uint32_t states_sm_patch_rows(const Graph& g);
+bool states_variant_fits(const Graph& g, const Variant& v);        // a states Variant (FZ_VF_STATES) fz_run_recording_grad could have made
 // 16-bit PCM frames (fz_pcm16.cpp): why the PCM kernel does not take this graph ("" = it does), and whether v is a Variant
 // fz_run_block_pcm16 could have made for it
 std::string pcm16_unsupported_reason(const Graph& g);

@@ -1,0 +1,160 @@
+// fz_states_sm_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the BLOCK-START STATES of a recording on STREAM-MAJOR
+// buffers (include/flowz_hip.h: fz_run_recording_grad with FZ_GRAD_STREAM_MAJOR).  What it computes and stores is
+// fz_kernel_states.hip.inc's -- the T rows forward with the generated fz_adj::fwd, one lane per stream; the state before rows 0, B,
+// 2B, ... of the window into starts[ceil(T / B)][n_state][n_streams], the state after the window's last row into state_out if that is
+// given, nothing else -- so the bits are the time-major kernel's.  What differs is how x arrives, and that is sweep 1 of
+// fz_kernel_adjoint_sm.hip.inc:
+//
+// in is [n_streams][rows_total][n_in], the recording the window of rows [row0, row0 + n_samples).  The 64 lanes of a wave fetch a
+// PATCH of [64 streams][FZ_R rows] as float4 pieces laid along the rows (consecutive lanes take consecutive pieces of one stream's
+// run), park them in a wave-private LDS patch, and every lane reads its own row back.  The patch carries x only: a patch row is
+// FZ_R * n_in floats + 4 of padding, 64 (FZ_R n_in + 4) 4 bytes per wave.  FZ_R is a multiple of FZ_U (the rows of one unrolled
+// group of the recursion) and of 4 (fz_grad.cpp: states_sm_patch_rows).  The fetch has no branches: a piece of a missing stream is
+// fetched from the wave's last stream, a piece behind the window's last float from the head of its run, and both are parked where
+// nobody reads them; at most FZ_AFLIGHT pieces are in flight per lane before they are parked.
+//
+// Masking, without a workgroup barrier (fz_wave_sync orders a wave's own LDS traffic; a wave past the last stream returns as a
+// whole): the last wave's missing streams shadow the wave's last stream and store nothing; a last patch shorter than FZ_R runs
+// the rows it has (a piece that straddles the window's last float is fetched whole: rows_total * n_in is a multiple of 4 floats, the
+// piece ends inside the stream's buffer).
+//
+// HBM bytes per stream-sample: 4 n_in + 4 n_state / B.
+//
+// Compiled by hiprtc with the build options of every other kernel: -ffp-contract=off, correctly rounded division and square root,
+// denormals kept.
+#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_U FZ_R FZ_BLOCK FZ_KERNEL
+
+#define FZ_P 1
+typedef float V;
+typedef double VD;
+#define FZ_A(n) ((n) > 0 ? (n) : 1)
+
+#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd }; fwd is all this kernel calls
+
+#if (FZ_R % 4) != 0 || (FZ_R % FZ_U) != 0 || (FZ_BLOCK % 64) != 0
+#error "stream-major states: the patch is a multiple of the unrolled group and of 4 rows, the workgroup whole waves"
+#endif
+#define FZ_AX (FZ_R * FZ_NIN)                 /* floats of x per patch row */
+#define FZ_AROW (FZ_AX + 4)                   /* padded patch row */
+#define FZ_API (FZ_AX / 4)                    /* float4 pieces per stream and patch */
+
+#define FZ_AFLIGHT 8                          /* float4 pieces a lane has in flight while a patch is fetched */
+
+typedef float fz_f4 __attribute__((ext_vector_type(4)));
+
+struct fz_states_sm_args {
+   const float* in;            // [n_streams][rows_total][n_in]
+   const float* state;         // [n_state][n_streams]   the state before the recording
+   const float* params;        // [n_param][n_streams]
+   float* starts;              // [ceil(T / B)][n_state][n_streams]   the state before rows 0, B, 2B, ... of the window
+   float* state_out;           // [n_state][n_streams]   the state after the window's last row; null: not written
+   unsigned long long n_streams;
+   unsigned int n_samples;     // T >= 1
+   unsigned int block_rows;    // B >= 1
+   unsigned int rows_total;
+   unsigned int row0;
+   float c[FZ_A(FZ_NCONST)];   // the program's uniform coefficients
+};
+
+__device__ __forceinline__ void fz_wave_sync()
+{
+   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+   __builtin_amdgcn_wave_barrier();
+   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Piece e = i * 64 + lane of the patch is piece e % PIECES of patch row e / PIECES: 4 floats at float 4 * (e % PIECES) of that
+// stream's run.  `rows` streams of the wave exist, `nval` floats of every run lie inside the window.  `g` is the first float of the
+// wave's first run, `gstride` the floats from one stream's run to the next.  No branches (see above).
+template <int PIECES>
+__device__ __forceinline__ void fz_states_fetch(float* part, const float* g, size_t gstride, unsigned rows, unsigned nval, unsigned lane)
+{
+   constexpr unsigned PP = PIECES > 0 ? PIECES : 1;
+#pragma unroll
+   for (int i = 0; i < PIECES; ++i) {
+      const unsigned e = (unsigned)i * 64u + lane, row = e / PP, q = e % PP;
+      const unsigned grow = row < rows ? row : rows - 1u, gq = q * 4u < nval ? q * 4u : 0u;
+      *reinterpret_cast<fz_f4*>(part + row * FZ_AROW + q * 4u) = *reinterpret_cast<const fz_f4*>(g + grow * gstride + gq);
+      if ((i + 1) % FZ_AFLIGHT == 0 && i + 1 < PIECES) asm volatile("" ::: "memory");   // (the parking rule)
+   }
+}
+
+extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_sm_args a)
+{
+#if FZ_NIN > 0
+   __shared__ __attribute__((aligned(16))) float fz_apatch[FZ_BLOCK / 64][64 * FZ_AROW];
+#endif
+   const size_t ns = a.n_streams;
+   const unsigned lane = threadIdx.x & 63u;
+   const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (wave-uniform: addresses built from it stay scalar)
+   const size_t s_base = (size_t)blockIdx.x * FZ_BLOCK + wave * 64u;                          // first stream of this wave
+   if (s_base >= ns) return;                                  // a wave past the last stream (no workgroup barriers below)
+   const unsigned rows_here = (unsigned)(ns - s_base < 64u ? ns - s_base : 64u);
+   const bool active = lane < rows_here;
+   const unsigned prow = active ? lane : rows_here - 1u;      // idle lanes shadow the wave's last stream, store nothing
+   const size_t s = s_base + prow;
+   const unsigned T = a.n_samples, B = a.block_rows;
+   const unsigned npatch = (T + (unsigned)FZ_R - 1u) / (unsigned)FZ_R;
+#if FZ_NIN > 0
+   float* const patch = fz_apatch[wave];
+   const float* const mine = patch + prow * FZ_AROW;
+   const size_t istride = (size_t)a.rows_total * FZ_NIN;
+   const float* const gin = a.in + s_base * istride + (size_t)a.row0 * FZ_NIN;   // the wave's first run: stream s_base, row row0
+#endif
+
+   float c[FZ_A(FZ_NCONST)], p[FZ_A(FZ_NPARAM)], st[FZ_A(FZ_NSTATE)];
+#pragma unroll
+   for (int k = 0; k < FZ_NCONST; ++k) c[k] = a.c[k];
+#pragma unroll
+   for (int k = 0; k < FZ_NPARAM; ++k) p[k] = a.params[(size_t)k * ns + s];
+   if (FZ_NCONST == 0) c[0] = 0.f;
+   if (FZ_NPARAM == 0) p[0] = 0.f;
+   st[0] = 0.f;
+#pragma unroll
+   for (int r = 0; r < FZ_NSTATE; ++r) st[r] = a.state[(size_t)r * ns + s];
+
+   unsigned tn = 0;                                           // the first row of the next block
+   float* sk = a.starts + s;                                  // its rows of `starts`
+   for (unsigned pk = 0; pk < npatch; ++pk) {
+      const unsigned r0 = pk * (unsigned)FZ_R, np = T - r0 < (unsigned)FZ_R ? T - r0 : (unsigned)FZ_R;   // rows of this patch (1 .. FZ_R)
+#if FZ_NIN > 0
+      fz_wave_sync();                                         // (the rows of the patch before are read)
+      fz_states_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+      fz_wave_sync();
+#endif
+      for (unsigned j0 = 0; j0 < np; j0 += FZ_U) {
+         float x[FZ_U][FZ_A(FZ_NIN)];
+#pragma unroll
+         for (int j = 0; j < FZ_U; ++j) {                     // (own-row reads inside the patch row: rows behind np hold parked pieces)
+            x[j][0] = 0.f;
+#if FZ_NIN > 0
+#pragma unroll
+            for (int w = 0; w < FZ_NIN; ++w) x[j][w] = mine[(j0 + j) * FZ_NIN + w];
+#endif
+         }
+#pragma unroll
+         for (int j = 0; j < FZ_U; ++j) {
+            const unsigned t = r0 + j0 + j;
+            if (j0 + j < np) {
+               if (t == tn) {                                 // (scalars both: no lane diverges)
+                  if (active) {
+#pragma unroll
+                     for (int r = 0; r < FZ_NSTATE; ++r) sk[(size_t)r * ns] = st[r];
+                  }
+                  sk += (size_t)FZ_NSTATE * ns;
+                  tn += B;
+               }
+               float sn[FZ_A(FZ_NSTATE)];
+               sn[0] = 0.f;
+               fz_adj::fwd(x[j], c, p, st, sn);
+#pragma unroll
+               for (int r = 0; r < FZ_NSTATE; ++r) st[r] = sn[r];
+            }
+         }
+      }
+   }
+   if (a.state_out && active) {
+#pragma unroll
+      for (int r = 0; r < FZ_NSTATE; ++r) a.state_out[(size_t)r * ns + s] = st[r];
+   }
+}

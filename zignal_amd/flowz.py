@@ -843,14 +843,72 @@ class Program:
         n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), (float(grad_scale), out))
 
-    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None):
+    # -- the backward of a whole recording (fz_run_recording_grad): two-level checkpointing over the calls above ---------------------
+    def recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
+        """the rows per block a recording of T rows is cut into (block_rows = 0: the library's choice; include/flowz_hip.h has the rule)"""
+        b = ctypes.c_uint32()
+        C.check(C.lib.fz_program_recording_block_rows(self._h, int(T), int(block_rows), int(checkpoint_rows), ctypes.byref(b)))
+        return int(b.value)
+
+    def recording_workspace_bytes(self, n_streams: int, T: int, block_rows: int = 0, checkpoint_rows: int = 0, stream_major: bool = False) -> int:
+        """workspace bytes of run_recording_grad / run_recording_loss_grad: the block-start states, then one block's checkpoints"""
+        b = ctypes.c_uint64()
+        C.check(C.lib.fz_program_recording_workspace(self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows), int(bool(stream_major)),
+                                                     ctypes.byref(b)))
+        return int(b.value)
+
+    def states_resources(self, stream_major: bool = False) -> dict:
+        """grad_resources() of the block-start-states kernel of a recording; 'unroll' = the rows of its unrolled group"""
+        r = C.KernelResources()
+        C.check(C.lib.fz_program_states_resources(self._h, int(bool(stream_major)), ctypes.byref(r)))
+        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+    def states_kernel_symbol(self, stream_major: bool = False) -> str:
+        buf = ctypes.create_string_buffer(160)
+        C.check(C.lib.fz_program_states_kernel_symbol(self._h, int(bool(stream_major)), buf, 160))
+        return buf.value.decode()
+
+    def states_source(self, stream_major: bool = False) -> str:
+        n = C.check(C.lib.fz_program_states_source(self._h, int(bool(stream_major)), None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        C.check(C.lib.fz_program_states_source(self._h, int(bool(stream_major)), buf, n + 1))
+        return buf.value.decode()
+
+    def run_recording_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0,
+                           block_rows: int = 0, stream_major: bool = False, row0: int = 0, n_samples: Optional[int] = None, in_grad=None,
+                           workspace=None):
+        """run_block_grad (stream_major: run_block_grad_stream_major, with its window and in_grad) over a whole recording in bounded
+        workspace (fz_run_recording_grad): the recording runs forward once keeping only the state before every block of block_rows rows
+        (0: the library's choice), then the blocks are differentiated from the last to the first.  Every bit is run_block_grad's over
+        the same rows.  want may also name "state_out": the state after the last row (the bits of run_block's).  workspace: a float32
+        tensor of at least recording_workspace_bytes to use (otherwise one is allocated).  Returns the dict of run_block_grad."""
+        window = None
+        if stream_major:
+            window = (int(row0), (x.shape[1] - int(row0)) if n_samples is None else int(n_samples), in_grad)
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, None, (int(block_rows), workspace))
+
+    def run_recording_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
+                                checkpoint_rows: int = 0, block_rows: int = 0, stream_major: bool = False, row0: int = 0,
+                                n_samples: Optional[int] = None, in_grad=None, out=None, workspace=None):
+        """run_block_loss_grad (stream_major: run_block_loss_grad_stream_major) over a whole recording, as run_recording_grad is to
+        run_block_grad: the same arguments, results and bits as the one-launch call over the same rows, plus "state_out" in want."""
+        window = None
+        if stream_major:
+            window = (int(row0), (x.shape[1] - int(row0)) if n_samples is None else int(n_samples), in_grad)
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, window, (float(grad_scale), out),
+                              (int(block_rows), workspace))
+
+    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None):
         """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers; loss: None, or
-        (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad"""
+        (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
+        (block_rows, workspace tensor or None) of the calls over a whole recording"""
         import torch
 
         _require(self.grad_supported(), self.grad_unsupported_reason())
         want = tuple(want)
         allowed = self.GRAD_WANT if loss is None else self.LOSS_GRAD_WANT
+        if recording is not None:
+            allowed = allowed + ("state_out",)
         _require(set(want) <= set(allowed), f"want: a subset of {allowed}")
         _require(loss is None or self.n_out, "the graph has no output wires: a loss has nothing to compare")
         if x.dim() == 2 and self.n_in == 1:
@@ -904,8 +962,20 @@ class Program:
             else:
                 out["out"] = torch.empty(gshape, dtype=torch.float32, device=dev) if window is None or (row0, T) == (0, rows) else \
                     torch.zeros(gshape, dtype=torch.float32, device=dev)
-        wsb = self.grad_workspace_bytes(ns, T, checkpoint_rows)
-        ws = torch.empty((_bi.max(wsb, 16) + 3) // 4, dtype=torch.float32, device=dev)
+        state0_grad = out.get("state")
+        if recording is None:
+            wsb = self.grad_workspace_bytes(ns, T, checkpoint_rows)
+        else:
+            wsb = self.recording_workspace_bytes(ns, T, recording[0], checkpoint_rows, window is not None)
+            if "state_out" in want:
+                out["state_out"] = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=dev)
+            if state0_grad is None and self.n_state:        # (the blocks chain through it, asked for or not)
+                state0_grad = torch.empty((self.n_state, ns), dtype=torch.float32, device=dev)
+        if recording is not None and recording[1] is not None:
+            ws = recording[1]
+            _require(ws.is_cuda and ws.dtype == torch.float32 and ws.is_contiguous(), "workspace: a contiguous float32 tensor on the GPU")
+        else:
+            ws = torch.empty((_bi.max(wsb, 16) + 3) // 4, dtype=torch.float32, device=dev)
 
         def ptr(t, rows=1):
             return t.data_ptr() if t is not None and rows else None
@@ -922,14 +992,19 @@ class Program:
             a.loss, a.out = ptr(out.get("loss")), ptr(out.get("out"), self.n_out)
         a.state_grad = ptr(state_grad, self.n_state)
         a.in_grad = ptr(out.get("x"), self.n_in)
-        a.state0_grad = ptr(out.get("state"), self.n_state)
+        a.state0_grad = ptr(state0_grad, self.n_state)
         a.param_grad = ptr(out.get("params"), self.n_param)
         a.const_grad = ptr(out.get("consts"), self.n_const)
         a.workspace = ws.data_ptr()
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
         hs = torch.cuda.current_stream().cuda_stream
-        if window is None:
+        if recording is not None:
+            fn = C.lib.fz_run_recording_grad if loss is None else C.lib.fz_run_recording_loss_grad
+            w = (int(rows), row0) if window is not None else (0, 0)
+            C.check(fn(self._h, ctypes.byref(a), int(window is not None), int(ns), w[0], w[1], int(T), recording[0],
+                       ptr(out.get("state_out"), self.n_state), hs))
+        elif window is None:
             C.check((C.lib.fz_run_block_grad if loss is None else C.lib.fz_run_block_loss_grad)(self._h, ctypes.byref(a), int(ns), int(T), hs))
         else:
             fn = C.lib.fz_run_block_grad_stream_major if loss is None else C.lib.fz_run_block_loss_grad_stream_major
