@@ -60,22 +60,22 @@ def rows_of(T):
     return up4(T + 9) + 4
 
 
-def launch(p, loss, sm, B, x, s0, par, tg, sb, ap, ac, al):
+def launch(p, loss, sm, B, x, s0, par, tg, sb, ap, ac, al, row0=ROW0, rows=None):
     """one call on time-major numpy inputs.  B None: the one-launch call; else the recording call with block_rows = B, its workspace
-    inside a larger sentinel-filled buffer.  sm: through stream-major buffers of rows_of(T) rows with the window at ROW0; "x" and "out"
-    come back time-major, "x_buffer" / "out_buffer" are the whole buffers.  "inputs_kept": in, target / dL/dy and state as the call left them
+    inside a larger sentinel-filled buffer.  sm: through stream-major buffers of `rows` rows (default rows_of(T)) with the window at
+    row0 (default ROW0); "x" and "out" come back time-major, "x_buffer" / "out_buffer" are the whole buffers.  "inputs_kept": in, target / dL/dy and state as the call left them
     equal what went in; "starts": the head of the workspace; "ws_kept": nothing outside the queried workspace bytes was written"""
     T, ns = x.shape[:2]
     want = keys_of(loss, B is not None)
     accum = {k: dev(v) for k, v, n in (("params", ap, p.n_param), ("consts", ac, p.n_const), ("loss", al, int(loss))) if n}
-    rows = rows_of(T)
-    xin, tin = (dev(to_sm(x, rows, ROW0, 7.0)), dev(to_sm(tg, rows, ROW0, 7.0))) if sm else (dev(x), dev(tg))
+    rows = rows_of(T) if rows is None else rows
+    xin, tin = (dev(to_sm(x, rows, row0, 7.0)), dev(to_sm(tg, rows, row0, 7.0))) if sm else (dev(x), dev(tg))
     sin = dev(s0) if p.n_state else None
     sent = [t.clone() for t in (xin, tin, sin) if t is not None]
     kw = dict(want=want, accum=accum)
     if sm:
         full = lambda w: torch.full((ns, rows, w), float(SENTINEL), device="cuda")   # noqa: E731
-        kw.update(row0=ROW0, n_samples=T, in_grad=full(p.n_in))
+        kw.update(row0=row0, n_samples=T, in_grad=full(p.n_in))
         if loss:
             kw["out"] = full(p.n_out)
     if loss:
@@ -96,7 +96,7 @@ def launch(p, loss, sm, B, x, s0, par, tg, sb, ap, ac, al):
         for k in ("x", "out"):
             if k in res:
                 res[k + "_buffer"] = res[k]
-                res[k] = np.ascontiguousarray(res[k][:, ROW0:ROW0 + T].transpose(1, 0, 2))
+                res[k] = np.ascontiguousarray(res[k][:, row0:row0 + T].transpose(1, 0, 2))
     # (bit for bit: the inputs of a cell with ties hold NaNs)
     res["inputs_kept"] = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(sent, [t for t in (xin, tin, sin) if t is not None]))
     if ws is not None:
@@ -122,9 +122,9 @@ def check(p, got, want, what, keys):
         assert same(g, w), f"{what}: {k} differs in {int((~((g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w)))).sum())} of {g.size}"
 
 
-def outside_keeps_sentinel(buf, T):
+def outside_keeps_sentinel(buf, T, row0=ROW0):
     keep = np.ones(buf.shape[1], bool)
-    keep[ROW0:ROW0 + T] = False
+    keep[row0:row0 + T] = False
     return bool(np.all(buf[:, keep].view(np.uint32) == SENTINEL.view(np.uint32)))
 
 
