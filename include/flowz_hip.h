@@ -589,6 +589,41 @@ int fz_program_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint3
 long fz_program_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 
+/* fz_run_block_ring_grad -- fz_run_block_grad for graphs with delay lines DEEPER THAN 8 SAMPLES (combs, echoes, plucked strings): a
+ * call family of its own, time-major frames, the plain backward (dL/dy given).  fz_grad_args is taken unchanged: fields, nullability,
+ * the accumulators that are added to, state0_grad == state_grad and every argument check mean what they mean for fz_run_block_grad,
+ * and every check runs before a device is needed.
+ *
+ * THE CONTRACT: the bits are those of the ORDER OF OPERATIONS of fz_run_block_grad, rules 1 - 4 as they stand, for a line of any
+ * depth (the adjoint state of a line of depth D has D rows; rule 2 moves them one up whatever D is).  They depend on the inputs
+ * alone -- not on the checkpoint stride, the lanes per workgroup or the stream count; no atomics, no FMA -- and the backward of
+ * block 2 followed by the backward of block 1 on the same accumulators (state0_grad of block 2 as state_grad of block 1) gives the
+ * bits of one block of 2T, also where a block is shorter than a line is deep.  tests/adjoint_ref.py restates the order for any depth.
+ *
+ * Scope: what fz_program_grad_check accepts, and graphs whose only objection there is float delay lines of depth 9 .. 256 (the lines
+ * the forward kernels keep as rings in LDS).  For a graph without such a line these calls ARE the fz_..._grad_ calls: the same
+ * kernel, symbol, workspace and bits.  Still refused, with the reasons of fz_program_grad_check: lines deeper than 256 samples (rings
+ * in HBM), typed programs, float64 nodes, complex wires, modulators.  Refused here alone: graphs whose deep lines hold more samples
+ * than the LDS of a workgroup has room for at 64 lanes (4 bytes per sample and lane, 163 840 bytes: 640 samples) -- the reason names
+ * the bytes.  Not built for such graphs: stream-major buffers, the fused loss, whole recordings (those calls keep refusing them).
+ *
+ * The kernel, fz_adjoint_ring_kernel_c<C>b<lanes per workgroup>_g<graph tag>: lines of depth <= 8 are kept as fz_run_block_grad keeps
+ * them (rows in registers, a checkpoint every C rows).  Of a deep line the forward sweep writes the source's value of every row into a
+ * tape in the workspace, which the backward sweep reads the delayed values from; the line's pending adjoints live in an LDS ring of D
+ * slots per lane.  Lanes per workgroup: the largest of 256 / 128 / 64 whose rings leave room for two workgroups in a compute unit's
+ * LDS, failing that the largest that fits one.  C: checkpoint_rows, or for 0 the library default -- 16, halved while
+ * C * (n_register_state + n_in + n_ring_reads) exceeds 64 (n_register_state: the state rows of the lines of depth <= 8, n_ring_reads:
+ * the distinct (deep line, delay) pairs the graph reads).
+ * Workspace: (ceil(n_samples / C) * n_register_state + n_samples * n_ring_lines) * n_streams * 4 bytes; fz_program_ring_grad_workspace
+ * answers it (for a graph without a deep line: what fz_program_grad_workspace answers). */
+int fz_program_ring_grad_check(const fz_program* p);
+int fz_program_ring_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_samples, uint32_t checkpoint_rows, uint64_t* bytes);
+/* registers, scratch and LDS bytes of the kernel (JITs it, no device needed); `unroll` = the checkpoint stride it uses */
+int fz_program_ring_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out);
+long fz_program_ring_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+long fz_program_ring_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+int fz_run_block_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
+
 /* fz_run_block_loss_grad -- the backward of one block where dL/dy is not given but FORMED IN THE KERNEL from a target, under a
  * squared-error loss.  The adjoint kernel re-evaluates every step of the block anyway: it holds y when it needs dL/dy, so neither y
  * nor dL/dy has to cross HBM.

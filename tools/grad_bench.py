@@ -29,7 +29,14 @@ had before -- run_block per block into a scratch y (only to get the state before
 the last to the first, chained through state0_grad and the accumulators.  1 048 576 x 4096 and 65 536 x 16 384, both layouts; printed
 with each route's workspace bytes.  The table goes to stdout and to profiles/r11/recording.txt.
 
-usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording]
+--rings: the forward / backward table for graphs with delay lines deeper than 8 samples, run_block against run_block_ring_grad
+(fz_run_block_ring_grad: the ring adjoint kernel) with every gradient and the default checkpoint stride -- workloads.lds_ring_comb (lines
+of 40 and 23 samples) and one deep single comb, ~(0.5 * _1[_256] + _2), at 1 048 576 x 1024 and 65 536 x 4096, time-major.  Same process,
+legs interleaved as --loss does (100 ms of the forward first, then --steps launches per leg in a forward and again in a backward pass:
+medians of 2 x --steps HIP-event timings per leg).  HBM traffic by the formula of DESIGN.md 9.6 (counted from the code, not measured) as a
+fraction of 8 TB/s.  There is no pass mark.  The table goes to stdout and to profiles/r12/ring_grad.txt.
+
+usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings]
 """
 import argparse
 import datetime
@@ -312,6 +319,75 @@ def recording_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
+RING_GRAPHS = {"lds_ring_comb": W.lds_ring_comb, "comb256": lambda: W.fb(W.add(W.mul(W.lit(0.5), W.DEL(1, 256)), W.IN(2)))}
+
+
+def rings_bench(a, torch):
+    """forward against the ring backward of graphs with delay lines in LDS, interleaved in one process"""
+    import time
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+    props = torch.cuda.get_device_properties(0)
+    say(f"# command: tools/grad_bench.py --rings --steps {a.steps} --legs {a.legs}")
+    say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+    say(f"# fwd = run_block (library default plan); bwd = run_block_ring_grad, every gradient, default checkpoint stride; time-major frames;")
+    say(f"# HIP events, {a.steps} launches per leg and pass, a forward and a backward pass over the legs; spread = max - min of the forward's own repeats;")
+    say("# bytes: fwd 4 (n_in + n_out), bwd 4 (3 n_in + n_out) + 8 n_register_state / C + 4 n_ring_lines + 4 n_ring_reads per stream-sample -- counted from the code")
+    say(f"{'graph':16s} {'streams x T':>16s} {'fwd ms':>9s} {'spread':>7s} {'bwd ms':>9s} {'bwd/fwd':>8s} {'fwd /8TB/s':>10s} {'bwd /8TB/s':>10s} {'C':>3s} {'vgprs':>6s} {'lds':>6s}  ring adjoint kernel")
+    shapes = SHAPES["large"] + SHAPES["small"] if a.legs == "all" else SHAPES[a.legs]
+    for ns, T in shapes:
+        x = torch.empty((T, ns, 1), dtype=torch.float32, device="cuda")
+        F.synth_fill(x, seed=W.SEED)
+        gy = torch.empty_like(x)
+        F.synth_fill(gy, seed=W.SEED + 1)
+        y = torch.empty_like(x)
+        for name, fn in RING_GRAPHS.items():
+            prog = F.compile(F.from_sexpr(fn()))
+            s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+            st = s0.clone()
+
+            def fwd():
+                st.copy_(s0)
+                prog.run_block(x, state=st, out=y)
+
+            def bwd():
+                prog.run_block_ring_grad(x, gy, s0, None, state_grad=s0)
+            legs = {"fwd": fwd, "bwd": bwd}
+            for f in legs.values():                            # JIT, allocator
+                f()
+            torch.cuda.synchronize()
+            t_end = time.time() + 0.1
+            while time.time() < t_end:                          # at least 100 ms of the yardstick before the first timing
+                fwd()
+                torch.cuda.synchronize()
+            got = {k: [] for k in legs}
+            for order in (list(legs), list(legs)[::-1]):
+                for k in order:
+                    got[k] += samples(legs[k], a.steps, torch)
+            med = {k: float(np.median(v)) for k, v in got.items()}
+            res = prog.ring_grad_resources()
+            C = res["unroll"]
+            depths = [d for _, d in prog.lines()]
+            n_reg, n_rl = sum(d for d in depths if d <= 8), sum(1 for d in depths if d > 8)
+            n_rr = len({(k, a_, b_) for k, a_, b_, _ in prog.ir() if k == "delay" and dict(prog.lines()).get(a_, 0) > 8})
+            fbytes = 4.0 * ns * T * (prog.n_in + prog.n_out)
+            bbytes = ns * T * (4.0 * (3 * prog.n_in + prog.n_out) + 8.0 * n_reg / C + 4.0 * n_rl + 4.0 * n_rr)
+            say(f"{name:16s} {f'{ns} x {T}':>16s} {med['fwd']:9.3f} {max(got['fwd']) - min(got['fwd']):7.3f} {med['bwd']:9.3f} {med['bwd'] / med['fwd']:8.2f} "
+                f"{fbytes / (med['fwd'] / 1e3) / HBM:10.3f} {bbytes / (med['bwd'] / 1e3) / HBM:10.3f} {C:3d} {res['vgprs'] + res['agprs']:6d} {res['lds_bytes']:6d}  "
+                f"{prog.ring_grad_kernel_symbol()}")
+            say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
+            del s0, st
+        del x, gy, y
+        torch.cuda.empty_cache()
+    out = os.path.join(ROOT, "profiles", "r12", "ring_grad.txt")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
@@ -320,6 +396,7 @@ def main():
     ap.add_argument("--layout", choices=("time-major", "stream-major", "compare"), default="time-major")
     ap.add_argument("--loss", action="store_true", help="the fused squared-error backward against forward + torch MSE + backward, both layouts")
     ap.add_argument("--recording", action="store_true", help="the backward of a whole recording against the one-launch call and blocks chained by hand")
+    ap.add_argument("--rings", action="store_true", help="forward against the ring backward of graphs with delay lines deeper than 8 samples")
     a = ap.parse_args()
     import torch
 
@@ -328,6 +405,8 @@ def main():
         return loss_bench(a, torch)
     if a.recording:
         return recording_bench(a, torch)
+    if a.rings:
+        return rings_bench(a, torch)
     props = torch.cuda.get_device_properties(0)
     if a.layout == "compare":
         print(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")

@@ -5,6 +5,9 @@ usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par
        tools/isa_stats.py lossgrad [graph] [tm|sm]         the kernel of fz_run_block_loss_grad (sm: _stream_major) next to the plain
                                                            adjoint kernel: registers, spills, LDS (graph: also cascade_params6)
        tools/isa_stats.py states [graph] [tm|sm]           the block-start-states kernel of fz_run_recording_grad: registers, spills, LDS
+       tools/isa_stats.py ringgrad [graph]                 the kernel of fz_run_block_ring_grad: registers, spills, scratch, LDS bytes, and
+                                                           its LDS (ds_*) and vector-memory instructions per row (graph: ldsring, comb256,
+                                                           or a name of tests/ring_grad_graphs.py)
 """
 import glob
 import os
@@ -25,7 +28,8 @@ GRAPHS = {"cascade6": lambda: G.df1_cascade(6), "par4": G.par4_sum, "par4f": G.p
           "moog": G.moog_ladder, "softclip": G.soft_clip_cascade, "envelope": G.envelope_follower,
           "tanh": lambda: ("tanh", G.IN(1)), "exp": lambda: ("exp", G.IN(1)), "sqrt": lambda: ("sqrt", G.IN(1)), "min": lambda: ("min", G.IN(1), G.lit(0.5)),
           "sin": lambda: ("sin", G.IN(1)), "cos": lambda: ("cos", G.IN(1)), "log": lambda: ("log", G.IN(1)),
-          "wire": lambda: G.IN(1), "cascade_params6": lambda: G.df1_cascade_params(6)}
+          "wire": lambda: G.IN(1), "cascade_params6": lambda: G.df1_cascade_params(6),
+          "comb256": lambda: G.fb(G.add(G.mul(G.lit(0.5), G.DEL(1, 256)), G.IN(2)))}
 
 
 def valu_count(expr, P, U=1, block=256, flags=0):
@@ -71,8 +75,47 @@ def states_line(name, sm):
             f"{r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills, {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS")
 
 
+def ring_grad_lines(name):
+    """the ring adjoint kernel at the default stride C, and its ds_* / vector-memory instructions per row of a chunk: the difference of
+    the kernels at C and C / 2 over C / 2 rows -- both sweeps unroll a chunk, everything outside the chunks cancels"""
+    import ring_grad_graphs as RG
+    build = RG.RINGS.get(name) or GRAPHS[name]
+    p = F.compile(F.from_sexpr(build()))
+    r = p.ring_grad_resources()
+    C = r["unroll"]
+
+    def counts(c):
+        with tempfile.TemporaryDirectory() as td:
+            os.environ["FLOWZ_HIP_CACHE"] = td
+            q = F.compile(F.from_sexpr(build()))
+            q.ring_grad_resources(c)
+            dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", glob.glob(td + "/*.hsaco")[0]], text=True)
+        ops = [ln.split()[0] for ln in dis.splitlines() if ln.split()]
+        vmem = [o for o in ops if o.startswith(("global_load", "global_store", "buffer_load", "buffer_store", "flat_load", "flat_store"))]
+        return {"ds_read": sum(o.startswith("ds_read") for o in ops), "ds_write": sum(o.startswith("ds_write") for o in ops),
+                "vmem_load": sum("load" in o for o in vmem), "vmem_store": sum("store" in o for o in vmem), "valu": sum(o.startswith("v_") for o in ops)}
+    old = os.environ.get("FLOWZ_HIP_CACHE")
+    try:
+        whole = counts(C)
+        half = counts(C // 2) if C > 1 else None
+    finally:
+        if old is None:
+            os.environ.pop("FLOWZ_HIP_CACHE", None)
+        else:
+            os.environ["FLOWZ_HIP_CACHE"] = old
+    out = [f"{name} {p.ring_grad_kernel_symbol()}: C {C}, {r['vgprs'] + r['agprs']} VGPRs, {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills, "
+           f"{r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS",
+           "  in the kernel: " + ", ".join(f"{v} {k}" for k, v in whole.items())]
+    if half:
+        out.append("  per row (both sweeps): " + ", ".join(f"{(whole[k] - half[k]) / (C - C // 2):.2f} {k}" for k in whole))
+    return out
+
+
 def main():
     a = sys.argv[1:]
+    if a and a[0] == "ringgrad":
+        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring")))
+        return
     if a and a[0] == "states":
         print(states_line(a[1] if len(a) > 1 else "cascade_params6", len(a) > 2 and a[2] == "sm"))
         return

@@ -182,6 +182,12 @@ def _load():
         "fz_program_recording_block_rows": (ctypes.c_int, [P, u32, u32, u32, ctypes.POINTER(u32)]),
         "fz_run_recording_grad": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u32, u64, u32, u32, u32, u32, P, P]),
         "fz_run_recording_loss_grad": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u32, u64, u32, u32, u32, u32, P, P]),
+        "fz_program_ring_grad_check": (ctypes.c_int, [P]),
+        "fz_program_ring_grad_workspace": (ctypes.c_int, [P, u64, u32, u32, ctypes.POINTER(u64)]),
+        "fz_program_ring_grad_resources": (ctypes.c_int, [P, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_ring_grad_kernel_symbol": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_ring_grad_source": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_run_block_ring_grad": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, P]),
         "fz_program_states_resources": (ctypes.c_int, [P, u32, ctypes.POINTER(KernelResources)]),
         "fz_program_states_kernel_symbol": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_states_source": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),

@@ -7,6 +7,9 @@ k-1).  Time-major frames [T, n_streams, n_in] (or [T, n_streams] for one input w
 run(..., stream_major=True) takes stream-major tensors instead, [n_streams, T, n_in] or [n_streams, T] -- a [batch, time] tensor as it
 lies: the forward is Program.run_block_stream_major, the backward Program.run_block_grad_stream_major, and nothing is transposed.
 
+run_rings(prog, x, state, params, consts) is run() for graphs with delay lines deeper than 8 samples (combs, echoes, plucked strings):
+time-major frames, the backward is Program.run_block_ring_grad (include/flowz_hip.h: fz_run_block_ring_grad).  run() keeps refusing them.
+
 mse(prog, x, target, ...) is the mean squared error of one block against a target as ONE launch (Program.run_block_loss_grad:
 the adjoint kernel forms y, the error and dL/dy itself), where run() followed by ((y - target) ** 2).mean() is a forward launch,
 several elementwise kernels and the backward launch.
@@ -33,8 +36,9 @@ def _apply_consts(prog: Program, consts):
 
 class _Block(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, prog, x, state, params, consts, stream_major=False):
+    def forward(ctx, prog, x, state, params, consts, stream_major=False, rings=False):
         _apply_consts(prog, consts)
+        ctx.rings = rings
         st = state.detach().clone() if state is not None else None    # (the caller's state is never advanced in place)
         fwd = prog.run_block_stream_major if stream_major else prog.run_block
         y, st = fwd(x.detach(), st, params.detach() if params is not None else None)
@@ -53,13 +57,13 @@ class _Block(torch.autograd.Function):
         _, need_x, need_s, need_p, need_c = ctx.needs_input_grad[:5]
         want = [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
         if not want:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
         if gy is None:
             gy = torch.zeros(tuple(xx.shape[:2]) + (prog.n_out,), dtype=torch.float32, device=x.device)
         sg = gs.contiguous() if gs is not None and prog.n_state else None
         _apply_consts(prog, ctx.consts)                               # (the constants of the forward launch)
-        bwd = prog.run_block_grad_stream_major if ctx.stream_major else prog.run_block_grad
+        bwd = prog.run_block_ring_grad if ctx.rings else prog.run_block_grad_stream_major if ctx.stream_major else prog.run_block_grad
         r = bwd(xx, gy.contiguous(), state.detach() if state is not None else None,
                 params.detach() if params is not None else None, state_grad=sg, want=want)
         gx = r["x"].reshape(ctx.x_shape) if need_x else None
@@ -69,7 +73,7 @@ class _Block(torch.autograd.Function):
         if need_c:
             # per-stream coefficient adjoints, summed over the streams in float64
             gc = r["consts"][:prog.n_const].double().sum(1).to(ctx.consts.dtype).to(ctx.consts.device)
-        return None, gx, gst, gp, gc, None
+        return None, gx, gst, gp, gc, None, None
 
 
 def run(prog: Program, x, state=None, params=None, consts=None, stream_major=False):
@@ -90,6 +94,23 @@ def run(prog: Program, x, state=None, params=None, consts=None, stream_major=Fal
         if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
             raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
     return _Block.apply(prog, x, state, params, consts, bool(stream_major))
+
+
+def run_rings(prog: Program, x, state=None, params=None, consts=None):
+    """run() for graphs with delay lines deeper than 8 samples -- and every graph run() takes --, time-major frames: returns (y [T,
+    n_streams, n_out], state after the block).  The forward is Program.run_block, the backward Program.run_block_ring_grad; x, state,
+    params and consts as for run(), the uniform-coefficient gradients summed over the streams in float64 as there.  Chaining it over
+    consecutive blocks back-propagates through time across them, whatever the blocks' lengths against the lines' depths."""
+    if not prog.ring_grad_supported():
+        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
+    if x.dim() == 2 and prog.n_in != 1:
+        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
+    if state is None:
+        state = torch.zeros((max(prog.n_state, 1), x.shape[1]), dtype=torch.float32, device=x.device)
+    if consts is not None:
+        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
+            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
+    return _Block.apply(prog, x, state, params, consts, False, True)
 
 
 class _Mse(torch.autograd.Function):

@@ -27,6 +27,7 @@ extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
 extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a kernel text of its own
 extern const char* const kSkeletonAdjointSm; // fz_kernel_adjoint_sm.hip.inc: the same for stream-major buffers
+extern const char* const kSkeletonAdjointRing;   // fz_kernel_adjoint_ring.hip.inc: the adjoint kernel of graphs with delay lines in LDS
 extern const char* const kSkeletonAdjointLoss;   // fz_kernel_adjoint_loss.hip.inc: the adjoint kernel that forms dL/dy from a target
 extern const char* const kSkeletonAdjointLossSm; // fz_kernel_adjoint_loss_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonStates;     // fz_kernel_states.hip.inc: the block-start states of a recording (the adjoint body's fwd alone)
@@ -43,6 +44,8 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm, pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
    static const std::string adj_loss = kSkeletonAdjointLoss, adj_loss_sm = kSkeletonAdjointLossSm;
    static const std::string states = kSkeletonStates, states_sm = kSkeletonStatesSm;
+   static const std::string adj_ring = kSkeletonAdjointRing;
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING)) return adj_ring;
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES)) return (v.flags & FZ_VF_ADJOINT_SM) ? states_sm : states;
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_LOSS)) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_loss_sm : adj_loss;
    if (v.flags & FZ_VF_ADJOINT) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_sm : adj;
@@ -58,6 +61,8 @@ std::string kernel_name(const Graph& g, const Variant& v)
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES))   // (the states bit means something next to FZ_VF_ADJOINT only)
       return (v.flags & FZ_VF_ADJOINT_SM) ? "fz_states_sm_kernel_u" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block)
                                           : "fz_states_kernel_u" + std::to_string(v.U) + "b" + std::to_string(v.block);
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING))   // (the ring bit means something next to FZ_VF_ADJOINT only)
+      return "fz_adjoint_ring_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
    const std::string adj = (v.flags & FZ_VF_ADJOINT_LOSS) ? "fz_adjoint_loss" : "fz_adjoint";   // (the loss bit means something next to FZ_VF_ADJOINT only)
    if (v.flags & FZ_VF_ADJOINT_SM)
       return adj + "_sm_kernel_c" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block);
@@ -758,7 +763,7 @@ static std::string gen_body_waves(const Graph& g, uint32_t W)
 
 std::string gen_body(const Graph& g, const Variant& v)
 {
-   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_body(g, (v.flags & FZ_VF_ADJOINT_LOSS) != 0);
+   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_body(g, (v.flags & FZ_VF_ADJOINT_LOSS) != 0, (v.flags & FZ_VF_ADJOINT_RING) != 0);
    if (const uint32_t W = ws_parts(v.flags)) return gen_body_waves(g, W);
    if (v.flags & FZ_VF_STAGE_PACK) return gen_body_skew(g, g.split);
    return gen_body_frames(g, v);
@@ -1059,6 +1064,24 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
    o << "#define FZ_NCONST " << g.consts.size() << "\n";
    o << "#define FZ_NPARAM " << g.n_param << "\n";
    o << "#define FZ_NSTATE " << g.n_state << "\n";
+   if (v.flags & FZ_VF_ADJOINT_RING) {
+      const RingLayout rl = ring_layout(g);
+      o << "#define FZ_NREG " << rl.n_reg() << "   // state rows of the lines in registers (depth <= " << kRegMaxDepth << ")\n";
+      o << "#define FZ_NRL " << rl.n_rl() << "   // ring lines: delay lines in LDS\n";
+      o << "#define FZ_NRR " << rl.n_rr() << "   // ring reads: distinct (ring line, delay) pairs\n";
+      o << "#define FZ_RING_SLOTS " << rl.slots << "   // LDS slots per lane: the sum of the ring lines' depths\n";
+      auto table = [&](const char* name, size_t n, const std::function<uint32_t(size_t)>& at, const char* what) {
+         o << "static __device__ constexpr unsigned " << name << "[" << std::max<size_t>(n, 1) << "] = {";
+         for (size_t i = 0; i < std::max<size_t>(n, 1); ++i) o << (i ? ", " : "") << (i < n ? at(i) : 0u) << "u";
+         o << "};   // " << what << "\n";
+      };
+      table("fz_reg_row", rl.n_reg(), [&](size_t i) { return rl.reg_row[i]; }, "per register row: the caller's state row");
+      table("fz_rl_row0", rl.n_rl(), [&](size_t i) { return g.lines[rl.rl_line[i]].row0; }, "per ring line: its first state row");
+      table("fz_rl_depth", rl.n_rl(), [&](size_t i) { return g.lines[rl.rl_line[i]].depth; }, "per ring line: its depth = its LDS slots");
+      table("fz_rl_slot0", rl.n_rl(), [&](size_t i) { return rl.rl_slot0[i]; }, "per ring line: its first LDS slot");
+      table("fz_rr_line", rl.n_rr(), [&](size_t i) { return rl.reads[i].first; }, "per ring read: its ring line");
+      table("fz_rr_delay", rl.n_rr(), [&](size_t i) { return rl.reads[i].second; }, "per ring read: its delay in samples");
+   }
    if (v.flags & FZ_VF_STATES) o << "#define FZ_U " << v.U << "   // rows per unrolled group of the forward recursion\n";
    else o << "#define FZ_C " << v.U << "   // checkpoint rows: the chunk sweep 2 re-runs and walks backwards\n";
    if (v.flags & FZ_VF_ADJOINT_SM) o << "#define FZ_R " << v.P << "   // rows per LDS patch of the stream-major frames\n";
@@ -1071,6 +1094,39 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
 // and the graph functions (LT .. LOG) -- not the conversions, modulators, |a| < |b| and selections between them
 bool adjoint_takes(uint32_t kind) { return (kind >= FZ_IR_INPUT && kind <= FZ_IR_NEG) || (kind >= FZ_IR_LT && kind <= FZ_IR_LOG); }
 
+// how the ring adjoint kernel lays a graph out (fz_internal.hpp: RingLayout)
+int RingLayout::read_index(uint32_t ring_line, uint32_t delay) const
+{
+   for (size_t i = 0; i < reads.size(); ++i)
+      if (reads[i].first == ring_line && reads[i].second == delay) return (int)i;
+   return -1;
+}
+
+RingLayout ring_layout(const Graph& g)
+{
+   RingLayout rl;
+   for (size_t l = 0; l < g.lines.size(); ++l) {
+      const Line& L = g.lines[l];
+      if (L.in_lds) {
+         rl.reg0.push_back(-1);
+         rl.ring_of_line.push_back((int)rl.rl_line.size());
+         rl.rl_line.push_back((uint32_t)l);
+         rl.rl_slot0.push_back(rl.slots);
+         rl.slots += L.depth;
+      } else {
+         rl.reg0.push_back((int)rl.reg_row.size());
+         rl.ring_of_line.push_back(-1);
+         for (uint32_t a = 0; a < L.depth; ++a) rl.reg_row.push_back(L.row0 + a);
+      }
+   }
+   for (const Node& nd : g.nodes) {
+      if (nd.kind != FZ_IR_DELAY) continue;
+      const int k = rl.ring_of_line[(size_t)g.line_of_node[nd.a]];
+      if (k >= 0 && rl.read_index((uint32_t)k, nd.b) < 0) rl.reads.emplace_back((uint32_t)k, nd.b);
+   }
+   return rl;
+}
+
 // struct fz_adj: fwd() -- the state after one step, from the state before it and the step's frame (the forward step() of gen_body for
 // one stream per lane, outputs left out) -- and bwd() -- the same step re-evaluated, then the adjoint statements in reverse node order.
 // The order of every sum is the one include/flowz_hip.h documents (fz_run_block_grad); tests/adjoint_ref.py restates it.  A node's
@@ -1078,9 +1134,25 @@ bool adjoint_takes(uint32_t kind) { return (kind >= FZ_IR_INPUT && kind <= FZ_IR
 // compiler folds the addition away.  Nodes no adjoint reaches (those that only feed comparisons) emit nothing at all.
 // loss (FZ_VF_ADJOINT_LOSS): out() as well -- the step's output values from (x, c, p, s), for the kernels that form dL/dy themselves;
 // without it the text is what it was before that variant existed, byte for byte.
-std::string gen_adjoint_body(const Graph& g, bool loss)
+// ring (FZ_VF_ADJOINT_RING, fz_kernel_adjoint_ring.hip.inc): the lines in LDS leave the register arrays -- s / sn / R hold the rows of
+// the other lines, compact (ring_layout) --; a delayed read of such a line is rv[read], fwd() hands the lines' source values out in
+// u[], and bwd() keeps their pending adjoints in the lane's LDS column `ring` (pt[line] = the row number modulo the line's depth):
+// rule 2 reads the row's slot and resets it to -0.0f, the pending adjoints the step's reads add into are loaded together behind that
+// (a read at the full depth finds the slot just reset), receive rule 3's additions in registers in its order and are stored once.
+// Without it -- every ring-free graph -- the text is byte for byte what it was.
+std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
 {
    std::ostringstream o;
+   const RingLayout rl = ring ? ring_layout(g) : RingLayout();
+   // ring mode: the ring line a line is (-1: a register line), the ring read a DELAY node is, the slot of a ring line `d` rows back
+   auto ring_line = [&](size_t line) { return ring ? rl.ring_of_line[line] : -1; };
+   auto read_of = [&](const Node& nd) { return rl.read_index((uint32_t)ring_line((size_t)g.line_of_node[nd.a]), nd.b); };
+   auto slot = [&](int k, uint32_t d) {
+      const uint32_t D = g.lines[rl.rl_line[(size_t)k]].depth, s0 = rl.rl_slot0[(size_t)k];
+      const std::string pt = "pt[" + std::to_string(k) + "]";
+      const std::string q = d == 0 || d == D ? pt : "(" + pt + " >= " + std::to_string(d) + "u ? " + pt + " - " + std::to_string(d) + "u : " + pt + " + " + std::to_string(D - d) + "u)";
+      return "ring[(size_t)(" + std::to_string(s0) + "u + " + q + ") * FZ_BLOCK]";
+   };
    auto val = [&](uint32_t id) { return "v" + std::to_string(id); };
    auto adj = [&](uint32_t id) { return "g" + std::to_string(id); };
    o << "// generated by libflowz_hip -- adjoint graph body: " << g.nodes.size() << " nodes, " << g.lines.size() << " delay lines, " << g.n_state
@@ -1088,6 +1160,7 @@ std::string gen_adjoint_body(const Graph& g, bool loss)
    emit_functions(o, g, true);
    auto row = [&](uint32_t src, uint32_t age) {          // state row of node src's value `age` samples ago (age >= 1)
       const Line& L = g.lines[(size_t)g.line_of_node[src]];
+      if (ring) return (uint32_t)rl.reg0[(size_t)g.line_of_node[src]] + age - 1;
       return L.row0 + age - 1;
    };
    auto values = [&](const char* indent) {
@@ -1099,7 +1172,10 @@ std::string gen_adjoint_body(const Graph& g, bool loss)
             case FZ_IR_INPUT: o << "x[" << nd.a << "]"; break;
             case FZ_IR_CONST: o << "c[" << nd.a << "]"; break;
             case FZ_IR_PARAM: o << "p[" << nd.a << "]"; break;
-            case FZ_IR_DELAY: o << "s[" << row(nd.a, nd.b) << "]"; break;
+            case FZ_IR_DELAY:
+               if (ring_line((size_t)g.line_of_node[nd.a]) >= 0) o << "rv[" << read_of(nd) << "]";
+               else o << "s[" << row(nd.a, nd.b) << "]";
+               break;
             default: o << op_expr(nd.kind, false, [&](uint32_t k, bool) { return val(operand(nd, k)); });
          }
          o << ";\n";
@@ -1107,19 +1183,39 @@ std::string gen_adjoint_body(const Graph& g, bool loss)
    };
    o << "struct fz_adj {\n";
    o << "   // the state after one step: row (row0 + j) of a line holds its source's value j + 1 samples ago\n";
-   o << "   __device__ __forceinline__ static void fwd(const float* x, const float* c, const float* p, const float* s, float* sn)\n   {\n";
-   o << "      (void)x; (void)c; (void)p; (void)s; (void)sn;\n";
+   if (ring) {
+      o << "   // (s / sn: the rows of the lines in registers, compact; rv: the step's ring-read values; u: the ring lines' source values)\n";
+      o << "   __device__ __forceinline__ static void fwd(const float* x, const float* c, const float* p, const float* s, const float* rv, float* sn,\n"
+           "                                              float* u)\n   {\n";
+      o << "      (void)x; (void)c; (void)p; (void)s; (void)rv; (void)sn; (void)u;\n";
+   } else {
+      o << "   __device__ __forceinline__ static void fwd(const float* x, const float* c, const float* p, const float* s, float* sn)\n   {\n";
+      o << "      (void)x; (void)c; (void)p; (void)s; (void)sn;\n";
+   }
    values("      ");
-   for (const Line& L : g.lines) {
-      o << "      sn[" << L.row0 << "] = " << val(L.src) << ";\n";
-      for (uint32_t a = 1; a < L.depth; ++a) o << "      sn[" << L.row0 + a << "] = s[" << L.row0 + a - 1 << "];\n";
+   for (size_t l = 0; l < g.lines.size(); ++l) {
+      const Line& L = g.lines[l];
+      if (ring_line(l) >= 0) {
+         o << "      u[" << ring_line(l) << "] = " << val(L.src) << ";\n";
+         continue;
+      }
+      const uint32_t r0 = ring ? (uint32_t)rl.reg0[l] : L.row0;
+      o << "      sn[" << r0 << "] = " << val(L.src) << ";\n";
+      for (uint32_t a = 1; a < L.depth; ++a) o << "      sn[" << r0 + a << "] = s[" << r0 + a - 1 << "];\n";
    }
    o << "   }\n";
    o << "   // one step backwards: yb = dL/dy of the step, R = the pending line adjoints (the state after the step on entry, before it on\n"
         "   // return), pb / cb += this step's parameter / coefficient adjoints, xb = dL/dx of the step\n";
-   o << "   __device__ __forceinline__ static void bwd(const float* x, const float* c, const float* p, const float* s, const float* yb, float* xb,\n"
-        "                                              float* R, float* pb, float* cb)\n   {\n";
-   o << "      (void)x; (void)c; (void)p; (void)s; (void)yb; (void)xb; (void)R; (void)pb; (void)cb;\n";
+   if (ring) {
+      o << "   // (ring: the lane's LDS column of the ring lines' pending adjoints; pt[line]: the row number modulo the line's depth)\n";
+      o << "   __device__ __forceinline__ static void bwd(const float* x, const float* c, const float* p, const float* s, const float* rv, const float* yb,\n"
+           "                                              float* xb, float* R, float* pb, float* cb, float* ring, const unsigned* pt)\n   {\n";
+      o << "      (void)x; (void)c; (void)p; (void)s; (void)rv; (void)yb; (void)xb; (void)R; (void)pb; (void)cb; (void)ring; (void)pt;\n";
+   } else {
+      o << "   __device__ __forceinline__ static void bwd(const float* x, const float* c, const float* p, const float* s, const float* yb, float* xb,\n"
+           "                                              float* R, float* pb, float* cb)\n   {\n";
+      o << "      (void)x; (void)c; (void)p; (void)s; (void)yb; (void)xb; (void)R; (void)pb; (void)cb;\n";
+   }
    values("      ");
    const size_t n = g.nodes.size();
    std::vector<char> has(n, 0);
@@ -1130,11 +1226,25 @@ std::string gen_adjoint_body(const Graph& g, bool loss)
       has[g.outputs[j]] = 1;
    }
    o << "      // 2. the pending line adjoint: row row0 of the state after the step is the line source's value; the other rows move one up\n";
-   for (const Line& L : g.lines) {
-      o << "      " << adj(L.src) << " = " << adj(L.src) << " + R[" << L.row0 << "];\n";
+   for (size_t l = 0; l < g.lines.size(); ++l) {
+      const Line& L = g.lines[l];
       has[L.src] = 1;
-      for (uint32_t a = 0; a + 1 < L.depth; ++a) o << "      R[" << L.row0 + a << "] = R[" << L.row0 + a + 1 << "];\n";
-      o << "      R[" << L.row0 + L.depth - 1 << "] = -0.0f;\n";
+      if (ring_line(l) >= 0) {                             // (the ring does not move: the row's slot is read and becomes the deepest row's)
+         o << "      " << adj(L.src) << " = " << adj(L.src) << " + " << slot(ring_line(l), 0) << ";\n";
+         o << "      " << slot(ring_line(l), 0) << " = -0.0f;\n";
+         continue;
+      }
+      const uint32_t r0 = ring ? (uint32_t)rl.reg0[l] : L.row0;
+      o << "      " << adj(L.src) << " = " << adj(L.src) << " + R[" << r0 << "];\n";
+      for (uint32_t a = 0; a + 1 < L.depth; ++a) o << "      R[" << r0 + a << "] = R[" << r0 + a + 1 << "];\n";
+      o << "      R[" << r0 + L.depth - 1 << "] = -0.0f;\n";
+   }
+   if (ring) {
+      o << "      // the pending adjoints the step's ring reads add into, loaded together (a read at the full depth: the slot just reset)\n";
+      for (size_t i = 0; i < rl.reads.size(); ++i) {
+         const uint32_t D = g.lines[rl.rl_line[rl.reads[i].first]].depth;
+         o << "      float q" << i << "r = " << (rl.reads[i].second == D ? std::string("-0.0f") : slot((int)rl.reads[i].first, rl.reads[i].second)) << ";\n";
+      }
    }
    o << "      // 3. consumers in decreasing node order\n";
    auto plus = [&](uint32_t to, const std::string& e) {
@@ -1154,6 +1264,10 @@ std::string gen_adjoint_body(const Graph& g, bool loss)
          case FZ_IR_CONST: o << "      cb[" << nd.a << "] = cb[" << nd.a << "] + " << gk << ";\n"; break;
          case FZ_IR_PARAM: o << "      pb[" << nd.a << "] = pb[" << nd.a << "] + " << gk << ";\n"; break;
          case FZ_IR_DELAY: {
+            if (ring_line((size_t)g.line_of_node[nd.a]) >= 0) {
+               o << "      q" << read_of(nd) << "r = q" << read_of(nd) << "r + " << gk << ";\n";
+               break;
+            }
             const uint32_t r = row(nd.a, nd.b);
             o << "      R[" << r << "] = R[" << r << "] + " << gk << ";\n";
             break;
@@ -1189,6 +1303,10 @@ std::string gen_adjoint_body(const Graph& g, bool loss)
          }
          default: break;                                   // comparisons: derivative zero, no arithmetic
       }
+   }
+   if (ring) {
+      o << "      // the ring reads' pending adjoints back into their slots, once each\n";
+      for (size_t i = 0; i < rl.reads.size(); ++i) o << "      " << slot((int)rl.reads[i].first, rl.reads[i].second) << " = q" << i << "r;\n";
    }
    o << "      // 4. the step's input adjoints (+0 for a wire no adjoint reaches)\n";
    for (uint32_t w = 0; w < g.n_in; ++w) {

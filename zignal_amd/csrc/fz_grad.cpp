@@ -7,6 +7,9 @@
 // The backward of a whole recording (fz_run_recording_grad, fz_run_recording_loss_grad) is two-level checkpointing over those: one
 // launch of the block-start-states kernel (FZ_VF_STATES; fz_kernel_states.hip.inc / fz_kernel_states_sm.hip.inc), then the launches
 // above block by block from the last to the first.
+// The backward of a block whose graph has delay lines in LDS (fz_run_block_ring_grad) is a call family of its own, time-major and plain:
+// FZ_VF_ADJOINT_RING on the Variant, fz_kernel_adjoint_ring.hip.inc, gen_adjoint_body in ring mode.  It shares the argument checks and
+// the launch with the calls above; for a graph without such a line it IS fz_run_block_grad.
 #include <cmath>
 #include <algorithm>
 #include <cstddef>
@@ -21,7 +24,7 @@ namespace fz {
 constexpr uint32_t kGradBlock = 256;          // lanes (= streams) per workgroup of the adjoint kernel
 constexpr uint32_t kGradMaxCheckpoint = 32;   // the chunk is unrolled: every step's state and frame stay in registers
 
-std::string grad_unsupported_reason(const Graph& g)
+std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds)
 {
    if (g.typed) return "typed programs (fz_compile_typed) are not supported by the backward";
    if (g.n_mod) return "sample-rate modulators (fz_modulator) are not supported by the backward";
@@ -29,10 +32,10 @@ std::string grad_unsupported_reason(const Graph& g)
       if (part) return "complex wires are not supported by the backward";
    for (const Line& L : g.lines) {
       if (L.far) return "delay lines deeper than 256 samples (rings in HBM) are not supported by the backward";
-      if (L.in_lds) return "delay lines deeper than 8 samples (rings in LDS) are not supported by the backward";
+      if (L.in_lds && !rings_in_lds) return "delay lines deeper than 8 samples (rings in LDS) are not supported by the backward";
       if (L.part || L.f64) return "complex or double delay lines are not supported by the backward";
    }
-   if (g.n_lds_slots || g.max_delay > kRegMaxDepth) return "delay lines deeper than 8 samples are not supported by the backward";
+   if (!rings_in_lds && (g.n_lds_slots || g.max_delay > kRegMaxDepth)) return "delay lines deeper than 8 samples are not supported by the backward";
    for (const Node& nd : g.nodes) {
       if (nd.f64) return "float64 nodes (a C++ double literal, fz_literal_f64) are not supported by the backward";
       if (nd.kind == FZ_IR_MOD) return "sample-rate modulators (fz_modulator) are not supported by the backward";
@@ -128,9 +131,41 @@ bool states_variant_fits(const Graph& g, const Variant& v)
    return v.P == w.P && v.U == w.U && v.block == w.block && (!sm || states_sm_patch_bytes(g, v.P) <= kLdsBytes);
 }
 
-static uint32_t checkpoint_of(const Graph& g, uint32_t checkpoint_rows)
+// ---- the ring backward (fz_run_block_ring_grad): its scope, checkpoint stride, workgroup and workspace, each at home here ---------------
+static bool has_ring_line(const Graph& g)
 {
-   if (checkpoint_rows == 0) return grad_default_checkpoint(g);
+   for (const Line& L : g.lines)
+      if (L.in_lds) return true;
+   return false;
+}
+
+// A chunk of the ring kernel's sweep 2 keeps C (n_register_state + n_in + n_ring_reads) floats in registers: the rule of
+// grad_default_checkpoint over what THIS kernel saves per row (for a graph without a ring line the two count the same).
+static uint32_t ring_default_checkpoint(const Graph& g)
+{
+   const RingLayout rl = ring_layout(g);
+   const uint32_t per_row = std::max<uint32_t>(rl.n_reg() + g.n_in + rl.n_rr(), 1);
+   uint32_t C = 16;
+   while (C > 1 && C * per_row > 64) C /= 2;
+   return C;
+}
+
+static uint64_t ring_lds_bytes(const RingLayout& rl, uint32_t block) { return (uint64_t)rl.slots * block * 4u; }
+
+// lanes per workgroup: the largest of 256 / 128 / 64 whose rings leave room for two workgroups in a CU's LDS; failing that the largest
+// that fits one workgroup; 0: not even 64 lanes fit
+static uint32_t ring_block(const RingLayout& rl)
+{
+   for (uint32_t b : {256u, 128u, 64u})
+      if (2 * ring_lds_bytes(rl, b) <= kLdsBytes) return b;
+   for (uint32_t b : {256u, 128u, 64u})
+      if (ring_lds_bytes(rl, b) <= kLdsBytes) return b;
+   return 0;
+}
+
+static uint32_t checkpoint_of(const Graph& g, uint32_t checkpoint_rows, bool ring = false)
+{
+   if (checkpoint_rows == 0) return ring ? ring_default_checkpoint(g) : grad_default_checkpoint(g);
    if (checkpoint_rows > kGradMaxCheckpoint || (checkpoint_rows & (checkpoint_rows - 1)))
       fail(FZ_E_INVALID, "checkpoint_rows must be 0 (library default) or a power of two <= 32");
    return checkpoint_rows;
@@ -158,6 +193,32 @@ static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool st
    return v;
 }
 
+// the Variant of the ring backward: for a graph without a ring line the plain adjoint Variant itself (same kernel, symbol, workspace, bits)
+static Variant ring_adjoint_variant(const Graph& g, uint32_t checkpoint_rows)
+{
+   const std::string why = grad_unsupported_reason(g, true);
+   if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
+   if (!has_ring_line(g)) return adjoint_variant(g, checkpoint_rows);
+   const RingLayout rl = ring_layout(g);
+   Variant v;
+   v.P = 1;
+   v.block = ring_block(rl);
+   if (!v.block)
+      fail(FZ_E_UNSUPPORTED, "the adjoint rings of the delay lines deeper than 8 samples, " + std::to_string(ring_lds_bytes(rl, 64)) + " bytes per 64 lanes (" +
+                                std::to_string(rl.slots) + " samples), do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup");
+   v.U = checkpoint_of(g, checkpoint_rows, true);
+   v.flags = FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING;
+   return v;
+}
+
+// could ring_adjoint_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
+bool ring_adjoint_variant_fits(const Graph& g, const Variant& v)
+{
+   if (v.flags != (FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING) || !grad_unsupported_reason(g, true).empty() || !has_ring_line(g)) return false;
+   if (v.P != 1 || v.U == 0 || v.U > kGradMaxCheckpoint || (v.U & (v.U - 1))) return false;
+   return v.block != 0 && v.block == ring_block(ring_layout(g));
+}
+
 static Variant states_variant(const Graph& g, bool stream_major)
 {
    require_supported(g);
@@ -178,6 +239,16 @@ static uint64_t workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t n_s
 {
    const uint64_t chunks = ((uint64_t)n_samples + C - 1) / C;
    return chunks * g.n_state * n_streams * 4u;
+}
+
+// the ring kernel's workspace: the register rows before every chunk, then the tape -- every row's ring-line source values
+// (include/flowz_hip.h: fz_program_ring_grad_workspace states it)
+static uint64_t ring_workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t n_samples, const Variant& v)
+{
+   if (!(v.flags & FZ_VF_ADJOINT_RING)) return workspace_bytes(g, n_streams, n_samples, v.U);
+   const RingLayout rl = ring_layout(g);
+   const uint64_t chunks = ((uint64_t)n_samples + v.U - 1) / v.U;
+   return (chunks * rl.n_reg() + (uint64_t)n_samples * rl.n_rl()) * n_streams * 4u;
 }
 
 // The rows per block of a recording of T rows (the one home of this rule; include/flowz_hip.h states it).  block_rows == 0: the B that
@@ -277,6 +348,7 @@ struct GradCall {
    bool loss_rule;
    float grad_scale;
    float *loss, *out;
+   bool ring = false;          // the call is fz_run_block_ring_grad: its scope, Variant and workspace
 };
 
 template <class Args>
@@ -318,7 +390,7 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
 {
    const GradCall* const a = &call;
    const Graph& g = p->g;
-   const Variant v = adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
+   const Variant v = a->ring ? ring_adjoint_variant(g, a->checkpoint_rows) : adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
    *vout = v;
    if (n_streams == 0 || n_samples == 0) return false;     // an empty block: nothing to differentiate, nothing touched
    if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
@@ -338,8 +410,8 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
    if (g.n_param && !a->params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
    if (a->loss_rule && !a->ybar) fail(FZ_E_INVALID, "target is null: the loss compares the outputs with it");
    if (g.n_out && !a->ybar) fail(FZ_E_INVALID, "out_grad is null but the graph has output wires");
-   const uint64_t need = rec ? rec->need : workspace_bytes(g, n_streams, n_samples, v.U);
-   const std::string ws_fn = rec ? "fz_program_recording_workspace" : "fz_program_grad_workspace";
+   const uint64_t need = rec ? rec->need : ring_workspace_bytes(g, n_streams, n_samples, v);
+   const std::string ws_fn = rec ? "fz_program_recording_workspace" : a->ring ? "fz_program_ring_grad_workspace" : "fz_program_grad_workspace";
    if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: " + ws_fn + " says " + std::to_string(need) + " bytes");
    if (need && a->workspace_bytes < need)
       fail(FZ_E_INVALID, "workspace_bytes " + std::to_string(a->workspace_bytes) + " is less than the " + std::to_string(need) + " bytes " + ws_fn + " asks for");
@@ -619,6 +691,48 @@ int fz_run_block_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* 
    FZ_GUARD(
       const SmWindow w{rows_total, row0};
       return run_grad(p, call_of(p, a), n_streams, n_samples, hip_stream, &w);)
+}
+
+int fz_program_ring_grad_check(const fz_program* p)
+{
+   FZ_GUARD(
+      if (!p) fail(FZ_E_INVALID, "null program");
+      (void)ring_adjoint_variant(p->g, 0);
+      return FZ_OK;)
+}
+
+int fz_program_ring_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_samples, uint32_t checkpoint_rows, uint64_t* bytes)
+{
+   FZ_GUARD(
+      if (!p || !bytes) fail(FZ_E_INVALID, "fz_program_ring_grad_workspace: bad arguments");
+      *bytes = ring_workspace_bytes(p->g, n_streams, n_samples, ring_adjoint_variant(p->g, checkpoint_rows));
+      return FZ_OK;)
+}
+
+int fz_program_ring_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_grad_resources: bad arguments");
+      *out = resources_of(p, ring_adjoint_variant(p->g, checkpoint_rows));
+      return FZ_OK;)
+}
+
+long fz_program_ring_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_adjoint_variant(p->g, checkpoint_rows)); });
+}
+
+long fz_program_ring_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_adjoint_variant(p->g, checkpoint_rows)); });
+}
+
+int fz_run_block_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
+{
+   FZ_GUARD(
+      GradCall call = call_of(p, a);
+      call.ring = true;
+      return run_grad(p, call, n_streams, n_samples, hip_stream);)
 }
 
 int fz_program_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,

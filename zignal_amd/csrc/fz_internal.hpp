@@ -194,6 +194,11 @@ constexpr uint32_t FZ_VF_ADJOINT_LOSS = 1u << 17;
 // the adjoint body alone; one more of the reserved bits.  Such a Variant is {P = 1 (stream-major: the rows of its LDS patch), U = the
 // rows of one unrolled group, block = lanes per workgroup}; fz_grad.cpp: states_variant is the one place that makes one.
 constexpr uint32_t FZ_VF_STATES = 1u << 16;
+// internal, with FZ_VF_ADJOINT alone: the adjoint kernel of a graph with delay lines in LDS (fz_grad.cpp: fz_run_block_ring_grad;
+// fz_kernel_adjoint_ring.hip.inc: a text and a symbol of its own, the pending adjoints of the deep lines in an LDS ring); the last of
+// the reserved bits 12 .. 14 that nothing used, so a forward variant naming it stays refused as reserved.  Such a Variant is {P = 1,
+// U = checkpoint rows, block = 256 / 128 / 64 lanes per workgroup}; fz_grad.cpp: ring_adjoint_variant is the one place that makes one.
+constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte
 // accesses).  FZ_VF_ST_MERGE means for it what it means for the frame kernel.  Such a Variant shares the kernel cache and the manifests
@@ -249,17 +254,38 @@ const std::string& skeleton_source(const Variant& v);   // hand-written kernel t
 std::string full_source(const Graph& g, const Variant& v);
 // the adjoint kernel (a Variant with FZ_VF_ADJOINT): gen_config / gen_body / skeleton_source hand over to these for it
 std::string gen_adjoint_config(const Graph& g, const Variant& v);
-std::string gen_adjoint_body(const Graph& g, bool loss = false);   // loss: also out(), the step's output values (FZ_VF_ADJOINT_LOSS)
+// loss: also out(), the step's output values (FZ_VF_ADJOINT_LOSS).  ring: the body of fz_kernel_adjoint_ring.hip.inc (FZ_VF_ADJOINT_RING):
+// register rows compact, the lines in LDS read through rv[] and their adjoints kept in an LDS ring; without it the text is unchanged
+std::string gen_adjoint_body(const Graph& g, bool loss = false, bool ring = false);
+// How the ring adjoint kernel lays a graph out (fz_codegen.cpp; the one home of these counts for fz_grad.cpp too): the lines of depth
+// <= 8 keep compact REGISTER rows, every `in_lds` line is a RING LINE with its slots in the lane's LDS column, and the distinct
+// (ring line, delay) pairs the graph reads are the RING READS, in node order.
+struct RingLayout {
+   std::vector<int> reg0;            // per line: its first compact register row, -1 for a ring line
+   std::vector<int> ring_of_line;    // per line: its ring line index, -1 for a register line
+   std::vector<uint32_t> reg_row;    // per compact register row: the caller's state row
+   std::vector<uint32_t> rl_line;    // per ring line: index into Graph::lines
+   std::vector<uint32_t> rl_slot0;   // per ring line: its first LDS slot
+   std::vector<std::pair<uint32_t, uint32_t>> reads;   // (ring line, delay)
+   uint32_t slots = 0;               // LDS slots per lane: the sum of the ring lines' depths
+   uint32_t n_reg() const { return (uint32_t)reg_row.size(); }
+   uint32_t n_rl() const { return (uint32_t)rl_line.size(); }
+   uint32_t n_rr() const { return (uint32_t)reads.size(); }
+   int read_index(uint32_t ring_line, uint32_t delay) const;   // -1: no such read
+};
+RingLayout ring_layout(const Graph& g);
 // the node kinds gen_adjoint_body writes (fz_codegen.cpp); grad_unsupported_reason refuses a graph with any other
 bool adjoint_takes(uint32_t kind);
 // why the backward of a block does not support this graph ("" = it does): fz_grad.cpp
-std::string grad_unsupported_reason(const Graph& g);
+// rings_in_lds: float delay lines in LDS (depth 9 .. 256) are no objection -- the scope of fz_run_block_ring_grad
+std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds = false);
 // the library's default checkpoint stride for the adjoint kernel of this graph (a power of two)
 uint32_t grad_default_checkpoint(const Graph& g);
 // rows per LDS patch of the stream-major adjoint kernel at checkpoint stride C: a multiple of C and of 4 (fz_grad.cpp)
 uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C);
 uint32_t grad_sm_max_patch_rows();                                 // the longest patch any graph can have (one wire, the whole LDS)
 bool adjoint_variant_fits(const Graph& g, const Variant& v);       // an adjoint Variant the backward could have made for this graph
+bool ring_adjoint_variant_fits(const Graph& g, const Variant& v);  // a ring adjoint Variant (FZ_VF_ADJOINT_RING) fz_run_block_ring_grad could have made
 // rows per LDS patch of the stream-major block-start-states kernel (x only), a multiple of 4 and of the unrolled group (fz_grad.cpp)
 uint32_t states_sm_patch_rows(const Graph& g);
 bool states_variant_fits(const Graph& g, const Variant& v);        // a states Variant (FZ_VF_STATES) fz_run_recording_grad could have made

@@ -806,6 +806,43 @@ class Program:
         n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
         return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad))
 
+    # -- the backward of a block with delay lines deeper than 8 samples (fz_run_block_ring_grad): a call family of its own --------------
+    def ring_grad_supported(self) -> bool:
+        """True when fz_run_block_ring_grad takes this program: what grad_supported() takes, and graphs with float delay lines of 9 ..
+        256 samples whose adjoint rings fit a workgroup's LDS (ring_grad_unsupported_reason() says why not)."""
+        return C.lib.fz_program_ring_grad_check(self._h) == C.FZ_OK
+
+    def ring_grad_unsupported_reason(self) -> str:
+        return "" if self.ring_grad_supported() else C.last_error()
+
+    def ring_grad_workspace_bytes(self, n_streams: int, T: int, checkpoint_rows: int = 0) -> int:
+        b = ctypes.c_uint64()
+        C.check(C.lib.fz_program_ring_grad_workspace(self._h, int(n_streams), int(T), int(checkpoint_rows), ctypes.byref(b)))
+        return int(b.value)
+
+    def ring_grad_resources(self, c: int = 0) -> dict:
+        """grad_resources() of the kernel of run_block_ring_grad at checkpoint stride c (0: the library default); 'lds_bytes' = the
+        adjoint rings of one workgroup"""
+        r = C.KernelResources()
+        C.check(C.lib.fz_program_ring_grad_resources(self._h, int(c), ctypes.byref(r)))
+        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+    def ring_grad_kernel_symbol(self, c: int = 0) -> str:
+        buf = ctypes.create_string_buffer(160)
+        C.check(C.lib.fz_program_ring_grad_kernel_symbol(self._h, int(c), buf, 160))
+        return buf.value.decode()
+
+    def ring_grad_source(self, c: int = 0) -> str:
+        n = C.check(C.lib.fz_program_ring_grad_source(self._h, int(c), None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        C.check(C.lib.fz_program_ring_grad_source(self._h, int(c), buf, n + 1))
+        return buf.value.decode()
+
+    def run_block_ring_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0):
+        """run_block_grad for graphs with delay lines deeper than 8 samples (fz_run_block_ring_grad): the same arguments, the same
+        result dict, the same order of every sum; time-major frames only.  For a graph run_block_grad takes it is run_block_grad."""
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None, ring=True)
+
     # -- the backward under a squared-error loss (fz_run_block_loss_grad): dL/dy formed in the kernel from a target ------------------
     LOSS_GRAD_WANT = GRAD_WANT + ("loss", "out")
 
@@ -898,13 +935,17 @@ class Program:
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, window, (float(grad_scale), out),
                               (int(block_rows), workspace))
 
-    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None):
+    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None, ring=False):
         """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers; loss: None, or
         (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
-        (block_rows, workspace tensor or None) of the calls over a whole recording"""
+        (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is run_block_ring_grad (one
+        time-major block, dL/dy given)"""
         import torch
 
-        _require(self.grad_supported(), self.grad_unsupported_reason())
+        if ring:
+            _require(self.ring_grad_supported(), self.ring_grad_unsupported_reason())
+        else:
+            _require(self.grad_supported(), self.grad_unsupported_reason())
         want = tuple(want)
         allowed = self.GRAD_WANT if loss is None else self.LOSS_GRAD_WANT
         if recording is not None:
@@ -964,7 +1005,7 @@ class Program:
                     torch.zeros(gshape, dtype=torch.float32, device=dev)
         state0_grad = out.get("state")
         if recording is None:
-            wsb = self.grad_workspace_bytes(ns, T, checkpoint_rows)
+            wsb = (self.ring_grad_workspace_bytes if ring else self.grad_workspace_bytes)(ns, T, checkpoint_rows)
         else:
             wsb = self.recording_workspace_bytes(ns, T, recording[0], checkpoint_rows, window is not None)
             if "state_out" in want:
@@ -1005,7 +1046,8 @@ class Program:
             C.check(fn(self._h, ctypes.byref(a), int(window is not None), int(ns), w[0], w[1], int(T), recording[0],
                        ptr(out.get("state_out"), self.n_state), hs))
         elif window is None:
-            C.check((C.lib.fz_run_block_grad if loss is None else C.lib.fz_run_block_loss_grad)(self._h, ctypes.byref(a), int(ns), int(T), hs))
+            fn = C.lib.fz_run_block_ring_grad if ring else C.lib.fz_run_block_grad if loss is None else C.lib.fz_run_block_loss_grad
+            C.check(fn(self._h, ctypes.byref(a), int(ns), int(T), hs))
         else:
             fn = C.lib.fz_run_block_grad_stream_major if loss is None else C.lib.fz_run_block_loss_grad_stream_major
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, T, hs))
