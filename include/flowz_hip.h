@@ -605,7 +605,8 @@ long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_
  * kernel, symbol, workspace and bits.  Still refused, with the reasons of fz_program_grad_check: lines deeper than 256 samples (rings
  * in HBM), typed programs, float64 nodes, complex wires, modulators.  Refused here alone: graphs whose deep lines hold more samples
  * than the LDS of a workgroup has room for at 64 lanes (4 bytes per sample and lane, 163 840 bytes: 640 samples) -- the reason names
- * the bytes.  Not built for such graphs: stream-major buffers, the fused loss, whole recordings (those calls keep refusing them).
+ * the bytes.  Not built for such graphs: stream-major buffers, whole recordings (those calls keep refusing them).  The fused loss is
+ * fz_run_block_ring_loss_grad, below fz_run_block_loss_grad.
  *
  * The kernel, fz_adjoint_ring_kernel_c<C>b<lanes per workgroup>_g<graph tag>: lines of depth <= 8 are kept as fz_run_block_grad keeps
  * them (rows in registers, a checkpoint every C rows).  Of a deep line the forward sweep writes the source's value of every row into a
@@ -675,6 +676,27 @@ int fz_run_block_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* 
 int fz_program_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out);
 long fz_program_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 long fz_program_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+
+/* fz_run_block_ring_loss_grad -- fz_run_block_loss_grad for graphs with delay lines DEEPER THAN 8 SAMPLES: the member of the
+ * fz_run_block_ring_grad family that forms dL/dy in the kernel.  fz_loss_grad_args is taken unchanged; time-major frames only.
+ *
+ * THE CONTRACT needs no rule of its own.  THE RULE of fz_run_block_loss_grad applies as written there (e, ybar = e * k, loss += e * e;
+ * rows T-1 down to 0, output slots ascending, one rounding per operation, one accumulator per stream that is ADDED TO); ybar then
+ * enters rules 1 - 4 of the ORDER OF OPERATIONS as fz_run_block_ring_grad states them for a line of any depth.  Hence every gradient
+ * bit equals fz_run_block_ring_grad given that ybar, `out` has the bits of fz_run_block, the bits do not depend on the checkpoint
+ * stride, the lanes per workgroup or the stream count, and two blocks chain bitwise through state0_grad, param_grad, const_grad and
+ * loss, also where a block is shorter than a line is deep.
+ *
+ * Scope: fz_program_ring_grad_check's.  Checkpoint stride, lanes per workgroup and workspace: those of fz_run_block_ring_grad
+ * (fz_program_ring_grad_workspace answers the bytes; the target is read where dL/dy was).  Checks: those of fz_run_block_loss_grad, in
+ * its order, before a device is needed; a short workspace names fz_program_ring_grad_workspace.  For a graph without a deep line these
+ * calls ARE the time-major fz_..._loss_grad_ calls: the same kernel, symbol, workspace and bits.  The kernel for a graph with one,
+ * fz_adjoint_ring_loss_kernel_c<C>b<lanes per workgroup>_g<graph tag>, is a text of its own with the LDS bytes of the plain ring
+ * kernel.  fz_run_block_loss_grad, its stream-major twin and the recording calls keep refusing graphs with a deep line. */
+int fz_program_ring_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out);
+long fz_program_ring_loss_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+long fz_program_ring_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
 
 /* fz_run_recording_grad, fz_run_recording_loss_grad -- the backward of a whole RECORDING of T rows in bounded workspace.
  *

@@ -36,6 +36,12 @@ legs interleaved as --loss does (100 ms of the forward first, then --steps launc
 medians of 2 x --steps HIP-event timings per leg).  HBM traffic by the formula of DESIGN.md 9.6 (counted from the code, not measured) as a
 fraction of 8 TB/s.  There is no pass mark.  The table goes to stdout and to profiles/r12/ring_grad.txt.
 
+--rings --loss: one training step under a mean squared error for those graphs and shapes, fused against the route a caller had before
+it.  fused: ONE launch of run_block_ring_loss_grad (fz_run_block_ring_loss_grad: every gradient and the per-stream loss).  route:
+run_block, torch's ((y - target) ** 2).mean() and 2 (y - target) / n, run_block_ring_grad.  Same buffers, same process, legs interleaved
+and timed as --loss does; the two legs must agree on the loss.  The pass mark is fused no slower than the route, the margin the route's own
+spread in that run.  The table goes to stdout and to profiles/r13/ring_loss_grad.txt.
+
 usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings]
 """
 import argparse
@@ -388,6 +394,75 @@ def rings_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
+def rings_loss_bench(a, torch):
+    """one step under a mean squared error for graphs with delay lines in LDS: the fused launch against forward + torch MSE and
+    derivative + ring backward, interleaved in one process"""
+    import time
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+    props = torch.cuda.get_device_properties(0)
+    say(f"# command: tools/grad_bench.py --rings --loss --steps {a.steps} --legs {a.legs}")
+    say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+    say("# fused = one run_block_ring_loss_grad launch; route = run_block + torch ((y - target)**2).mean() and 2 (y - target) / n + run_block_ring_grad;")
+    say(f"# time-major frames; HIP events, {a.steps} launches per leg and pass, a forward and a backward pass over the legs; spread = max - min of the route's own repeats;")
+    say("# pass = fused median <= route median + spread")
+    say(f"{'graph':16s} {'streams x T':>16s} {'route ms':>9s} {'spread':>7s} {'fused ms':>9s} {'fused/route':>11s} {'pass':>5s} {'C':>3s} {'vgprs':>6s} {'sgpr spills':>11s} {'lds':>6s}  ring loss kernel")
+    shapes = SHAPES["large"] + SHAPES["small"] if a.legs == "all" else SHAPES[a.legs]
+    for ns, T in shapes:
+        x = torch.empty((T, ns, 1), dtype=torch.float32, device="cuda")
+        F.synth_fill(x, seed=W.SEED)
+        target = torch.empty_like(x)
+        F.synth_fill(target, seed=W.SEED + 1)
+        y, gy = torch.empty_like(x), torch.empty_like(x)
+        n = float(ns) * T
+        for name, fn in RING_GRAPHS.items():
+            prog = F.compile(F.from_sexpr(fn()))
+            s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+            st = s0.clone()
+
+            def route():
+                st.copy_(s0)
+                prog.run_block(x, state=st, out=y)
+                loss = ((y - target) ** 2).mean()
+                torch.mul(y - target, 2.0 / n, out=gy)
+                prog.run_block_ring_grad(x, gy, s0, None)
+                return loss
+
+            def fused():
+                r = prog.run_block_ring_loss_grad(x, target, s0, None, grad_scale=2.0 / n, want=("x", "state", "params", "consts", "loss"))
+                return r["loss"].double().sum() / n
+            legs = {"route": route, "fused": fused}
+            vals = {k: float(f()) for k, f in legs.items()}        # JIT, allocator; and the two legs agree on the loss
+            assert abs(vals["route"] - vals["fused"]) <= 1e-3 * abs(vals["route"]), vals    # (a sanity check, not the test: float32 sums in two orders)
+            torch.cuda.synchronize()
+            t_end = time.time() + 0.1
+            while time.time() < t_end:                          # at least 100 ms of the yardstick before the first timing
+                route()
+                torch.cuda.synchronize()
+            got = {k: [] for k in legs}
+            for order in (list(legs), list(legs)[::-1]):
+                for k in order:
+                    got[k] += samples(legs[k], a.steps, torch)
+            med = {k: float(np.median(v)) for k, v in got.items()}
+            spread = max(got["route"]) - min(got["route"])
+            res = prog.ring_loss_grad_resources()
+            say(f"{name:16s} {f'{ns} x {T}':>16s} {med['route']:9.3f} {spread:7.3f} {med['fused']:9.3f} {med['fused'] / med['route']:11.3f} "
+                f"{'yes' if med['fused'] <= med['route'] + spread else 'NO':>5s} {res['unroll']:3d} {res['vgprs'] + res['agprs']:6d} {res['sgpr_spills']:11d} "
+                f"{res['lds_bytes']:6d}  {prog.ring_loss_grad_kernel_symbol()}")
+            say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
+            say(f"#   loss: route {vals['route']:.9g}, fused {vals['fused']:.9g}")
+            del s0, st
+        del x, target, y, gy
+        torch.cuda.empty_cache()
+    out = os.path.join(ROOT, "profiles", "r13", "ring_loss_grad.txt")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
@@ -396,11 +471,13 @@ def main():
     ap.add_argument("--layout", choices=("time-major", "stream-major", "compare"), default="time-major")
     ap.add_argument("--loss", action="store_true", help="the fused squared-error backward against forward + torch MSE + backward, both layouts")
     ap.add_argument("--recording", action="store_true", help="the backward of a whole recording against the one-launch call and blocks chained by hand")
-    ap.add_argument("--rings", action="store_true", help="forward against the ring backward of graphs with delay lines deeper than 8 samples")
+    ap.add_argument("--rings", action="store_true", help="forward against the ring backward of graphs with delay lines deeper than 8 samples; with --loss: their fused squared-error backward against the route")
     a = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
+    if a.rings and a.loss:
+        return rings_loss_bench(a, torch)
     if a.loss:
         return loss_bench(a, torch)
     if a.recording:

@@ -8,6 +8,8 @@ usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par
        tools/isa_stats.py ringgrad [graph]                 the kernel of fz_run_block_ring_grad: registers, spills, scratch, LDS bytes, and
                                                            its LDS (ds_*) and vector-memory instructions per row (graph: ldsring, comb256,
                                                            or a name of tests/ring_grad_graphs.py)
+       tools/isa_stats.py ringlossgrad [graph]             the same line for the kernel of fz_run_block_ring_loss_grad, next to the plain
+                                                           ring kernel's figures (graph: also a name of tests/ring_loss_graphs.py)
 """
 import glob
 import os
@@ -75,20 +77,22 @@ def states_line(name, sm):
             f"{r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills, {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS")
 
 
-def ring_grad_lines(name):
+def ring_grad_lines(name, loss=False):
     """the ring adjoint kernel at the default stride C, and its ds_* / vector-memory instructions per row of a chunk: the difference of
-    the kernels at C and C / 2 over C / 2 rows -- both sweeps unroll a chunk, everything outside the chunks cancels"""
-    import ring_grad_graphs as RG
-    build = RG.RINGS.get(name) or GRAPHS[name]
+    the kernels at C and C / 2 over C / 2 rows -- both sweeps unroll a chunk, everything outside the chunks cancels.
+    loss: the kernel of fz_run_block_ring_loss_grad, with the plain ring kernel's registers and spills next to its own"""
+    import ring_loss_graphs as RL
+    build = RL.GRAPHS.get(name) or GRAPHS[name]
     p = F.compile(F.from_sexpr(build()))
-    r = p.ring_grad_resources()
+    resources = (lambda q, c=0: q.ring_loss_grad_resources(c)) if loss else (lambda q, c=0: q.ring_grad_resources(c))
+    r = resources(p)
     C = r["unroll"]
 
     def counts(c):
         with tempfile.TemporaryDirectory() as td:
             os.environ["FLOWZ_HIP_CACHE"] = td
             q = F.compile(F.from_sexpr(build()))
-            q.ring_grad_resources(c)
+            resources(q, c)
             dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", glob.glob(td + "/*.hsaco")[0]], text=True)
         ops = [ln.split()[0] for ln in dis.splitlines() if ln.split()]
         vmem = [o for o in ops if o.startswith(("global_load", "global_store", "buffer_load", "buffer_store", "flat_load", "flat_store"))]
@@ -103,8 +107,10 @@ def ring_grad_lines(name):
             os.environ.pop("FLOWZ_HIP_CACHE", None)
         else:
             os.environ["FLOWZ_HIP_CACHE"] = old
-    out = [f"{name} {p.ring_grad_kernel_symbol()}: C {C}, {r['vgprs'] + r['agprs']} VGPRs, {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills, "
-           f"{r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS",
+    plain = p.ring_grad_resources() if loss else None
+    out = [f"{name} {p.ring_loss_grad_kernel_symbol() if loss else p.ring_grad_kernel_symbol()}: C {C}, {r['vgprs'] + r['agprs']} VGPRs"
+           + (f" (plain ring {plain['vgprs'] + plain['agprs']})" if loss else "") + f", {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills"
+           + (f" (plain ring {plain['vgpr_spills']} / {plain['sgpr_spills']})" if loss else "") + f", {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS",
            "  in the kernel: " + ", ".join(f"{v} {k}" for k, v in whole.items())]
     if half:
         out.append("  per row (both sweeps): " + ", ".join(f"{(whole[k] - half[k]) / (C - C // 2):.2f} {k}" for k in whole))
@@ -115,6 +121,9 @@ def main():
     a = sys.argv[1:]
     if a and a[0] == "ringgrad":
         print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring")))
+        return
+    if a and a[0] == "ringlossgrad":
+        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring", loss=True)))
         return
     if a and a[0] == "states":
         print(states_line(a[1] if len(a) > 1 else "cascade_params6", len(a) > 2 and a[2] == "sm"))

@@ -14,6 +14,9 @@ mse(prog, x, target, ...) is the mean squared error of one block against a targe
 the adjoint kernel forms y, the error and dL/dy itself), where run() followed by ((y - target) ** 2).mean() is a forward launch,
 several elementwise kernels and the backward launch.
 
+mse_rings(prog, x, target, ...) is mse() for every graph run_rings() takes, time-major (Program.run_block_ring_loss_grad: the ring
+adjoint kernel with the loss formed in it); mse() keeps refusing graphs with delay lines deeper than 8 samples.
+
 mse_recording(prog, x, target, ...) is the same loss over a whole recording of many blocks in bounded workspace
 (Program.run_recording_loss_grad: one forward launch that keeps the state before every block, then the loss kernel block by block
 from the last to the first), and also returns the state after the recording.
@@ -115,13 +118,13 @@ def run_rings(prog: Program, x, state=None, params=None, consts=None):
 
 class _Mse(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, prog, x, target, state, params, consts, stream_major=False):
+    def forward(ctx, prog, x, target, state, params, consts, stream_major=False, rings=False):
         _apply_consts(prog, consts)
         _, need_x, _, need_s, need_p, need_c = ctx.needs_input_grad[:6]
         want = ["loss"] + [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
         xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
         n = xx.shape[0] * xx.shape[1] * prog.n_out                    # elements of y: the mean is over all of them
-        bwd = prog.run_block_loss_grad_stream_major if stream_major else prog.run_block_loss_grad
+        bwd = prog.run_block_ring_loss_grad if rings else prog.run_block_loss_grad_stream_major if stream_major else prog.run_block_loss_grad
         # the one launch: the loss and every gradient asked for, dL/dy = (y - target) * 2 / n formed in the kernel
         r = bwd(xx, target.detach().contiguous(), state.detach() if state is not None else None,
                 params.detach() if params is not None else None, grad_scale=2.0 / n, want=want)
@@ -135,7 +138,7 @@ class _Mse(torch.autograd.Function):
     def backward(ctx, g):
         gx, gs, gp, gc = ctx.grads
         scaled = lambda t: None if t is None else t * g.to(t.device)   # noqa: E731  (the upstream scalar)
-        return None, scaled(gx), None, scaled(gs), scaled(gp), scaled(gc), None
+        return None, scaled(gx), None, scaled(gs), scaled(gp), scaled(gc), None, None
 
 
 def mse(prog: Program, x, target, state=None, params=None, consts=None, stream_major=False):
@@ -151,7 +154,21 @@ def mse(prog: Program, x, target, state=None, params=None, consts=None, stream_m
     if consts is not None:
         if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
             raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major))
+    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), False)
+
+
+def mse_rings(prog: Program, x, target, state=None, params=None, consts=None):
+    """mse() for graphs with delay lines deeper than 8 samples -- and every graph mse() takes --, time-major frames: the scalar
+    ((y - target) ** 2).mean() of one block, differentiable in x, state, params and consts.  One launch, made in the forward
+    (Program.run_block_ring_loss_grad, include/flowz_hip.h: fz_run_block_ring_loss_grad); backward() applies the upstream scalar."""
+    if not prog.ring_grad_supported():
+        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
+    if x.dim() == 2 and prog.n_in != 1:
+        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
+    if consts is not None:
+        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
+            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
+    return _Mse.apply(prog, x, target, state, params, consts, False, True)
 
 
 class _MseRecording(torch.autograd.Function):

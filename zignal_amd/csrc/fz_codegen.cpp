@@ -28,6 +28,7 @@ extern const char* const kSkeletonBody_frames;
 extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a kernel text of its own
 extern const char* const kSkeletonAdjointSm; // fz_kernel_adjoint_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonAdjointRing;   // fz_kernel_adjoint_ring.hip.inc: the adjoint kernel of graphs with delay lines in LDS
+extern const char* const kSkeletonAdjointRingLoss;   // fz_kernel_adjoint_ring_loss.hip.inc: the same with dL/dy formed from a target
 extern const char* const kSkeletonAdjointLoss;   // fz_kernel_adjoint_loss.hip.inc: the adjoint kernel that forms dL/dy from a target
 extern const char* const kSkeletonAdjointLossSm; // fz_kernel_adjoint_loss_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonStates;     // fz_kernel_states.hip.inc: the block-start states of a recording (the adjoint body's fwd alone)
@@ -44,7 +45,9 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm, pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
    static const std::string adj_loss = kSkeletonAdjointLoss, adj_loss_sm = kSkeletonAdjointLossSm;
    static const std::string states = kSkeletonStates, states_sm = kSkeletonStatesSm;
-   static const std::string adj_ring = kSkeletonAdjointRing;
+   static const std::string adj_ring = kSkeletonAdjointRing, adj_ring_loss = kSkeletonAdjointRingLoss;
+   // (ring + loss before ring and before loss: the three-bit combination is a text of its own)
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_LOSS)) return adj_ring_loss;
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING)) return adj_ring;
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES)) return (v.flags & FZ_VF_ADJOINT_SM) ? states_sm : states;
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_LOSS)) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_loss_sm : adj_loss;
@@ -61,6 +64,8 @@ std::string kernel_name(const Graph& g, const Variant& v)
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES))   // (the states bit means something next to FZ_VF_ADJOINT only)
       return (v.flags & FZ_VF_ADJOINT_SM) ? "fz_states_sm_kernel_u" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block)
                                           : "fz_states_kernel_u" + std::to_string(v.U) + "b" + std::to_string(v.block);
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_LOSS))   // (ring + loss: before either alone)
+      return "fz_adjoint_ring_loss_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING))   // (the ring bit means something next to FZ_VF_ADJOINT only)
       return "fz_adjoint_ring_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
    const std::string adj = (v.flags & FZ_VF_ADJOINT_LOSS) ? "fz_adjoint_loss" : "fz_adjoint";   // (the loss bit means something next to FZ_VF_ADJOINT only)
@@ -1140,6 +1145,7 @@ RingLayout ring_layout(const Graph& g)
 // rule 2 reads the row's slot and resets it to -0.0f, the pending adjoints the step's reads add into are loaded together behind that
 // (a read at the full depth finds the slot just reset), receive rule 3's additions in registers in its order and are stored once.
 // Without it -- every ring-free graph -- the text is byte for byte what it was.
+// loss and ring (fz_kernel_adjoint_ring_loss.hip.inc): out() takes rv as well -- a delayed read of a ring line is rv[read] there too.
 std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
 {
    std::ostringstream o;
@@ -1318,8 +1324,14 @@ std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
    o << "   }\n";
    if (loss) {
       o << "   // the step's output values, slot by slot: the bits fz_run_block writes\n";
-      o << "   __device__ __forceinline__ static void out(const float* x, const float* c, const float* p, const float* s, float* y)\n   {\n";
-      o << "      (void)x; (void)c; (void)p; (void)s; (void)y;\n";
+      if (ring) {
+         o << "   // (s: the rows of the lines in registers, compact; rv: the step's ring-read values)\n";
+         o << "   __device__ __forceinline__ static void out(const float* x, const float* c, const float* p, const float* s, const float* rv, float* y)\n   {\n";
+         o << "      (void)x; (void)c; (void)p; (void)s; (void)rv; (void)y;\n";
+      } else {
+         o << "   __device__ __forceinline__ static void out(const float* x, const float* c, const float* p, const float* s, float* y)\n   {\n";
+         o << "      (void)x; (void)c; (void)p; (void)s; (void)y;\n";
+      }
       values("      ");
       for (size_t j = 0; j < g.outputs.size(); ++j) o << "      y[" << j << "] = " << val(g.outputs[j]) << ";\n";
       o << "   }\n";

@@ -9,7 +9,9 @@
 // above block by block from the last to the first.
 // The backward of a block whose graph has delay lines in LDS (fz_run_block_ring_grad) is a call family of its own, time-major and plain:
 // FZ_VF_ADJOINT_RING on the Variant, fz_kernel_adjoint_ring.hip.inc, gen_adjoint_body in ring mode.  It shares the argument checks and
-// the launch with the calls above; for a graph without such a line it IS fz_run_block_grad.
+// the launch with the calls above; for a graph without such a line it IS fz_run_block_grad.  Under the squared-error loss
+// (fz_run_block_ring_loss_grad) it is that family's call with FZ_VF_ADJOINT_LOSS next to the ring bit: fz_kernel_adjoint_ring_loss.hip.inc,
+// the ring kernel's C, block and workspace; for a graph without such a line it IS fz_run_block_loss_grad.
 #include <cmath>
 #include <algorithm>
 #include <cstddef>
@@ -194,11 +196,12 @@ static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool st
 }
 
 // the Variant of the ring backward: for a graph without a ring line the plain adjoint Variant itself (same kernel, symbol, workspace, bits)
-static Variant ring_adjoint_variant(const Graph& g, uint32_t checkpoint_rows)
+// loss: the kernel forms dL/dy itself (FZ_VF_ADJOINT_LOSS next to the ring bit); C, block and workspace do not change with it
+static Variant ring_adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool loss = false)
 {
    const std::string why = grad_unsupported_reason(g, true);
    if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
-   if (!has_ring_line(g)) return adjoint_variant(g, checkpoint_rows);
+   if (!has_ring_line(g)) return adjoint_variant(g, checkpoint_rows, false, loss);
    const RingLayout rl = ring_layout(g);
    Variant v;
    v.P = 1;
@@ -207,14 +210,16 @@ static Variant ring_adjoint_variant(const Graph& g, uint32_t checkpoint_rows)
       fail(FZ_E_UNSUPPORTED, "the adjoint rings of the delay lines deeper than 8 samples, " + std::to_string(ring_lds_bytes(rl, 64)) + " bytes per 64 lanes (" +
                                 std::to_string(rl.slots) + " samples), do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup");
    v.U = checkpoint_of(g, checkpoint_rows, true);
-   v.flags = FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING;
+   v.flags = FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
+   if (loss && g.n_out == 0) fail(FZ_E_INVALID, "the graph has no output wires: a loss has nothing to compare");
    return v;
 }
 
 // could ring_adjoint_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
 bool ring_adjoint_variant_fits(const Graph& g, const Variant& v)
 {
-   if (v.flags != (FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING) || !grad_unsupported_reason(g, true).empty() || !has_ring_line(g)) return false;
+   if ((v.flags & ~FZ_VF_ADJOINT_LOSS) != (FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING) || !grad_unsupported_reason(g, true).empty() || !has_ring_line(g)) return false;
+   if ((v.flags & FZ_VF_ADJOINT_LOSS) && g.n_out == 0) return false;                       // (a loss kernel compares outputs)
    if (v.P != 1 || v.U == 0 || v.U > kGradMaxCheckpoint || (v.U & (v.U - 1))) return false;
    return v.block != 0 && v.block == ring_block(ring_layout(g));
 }
@@ -348,7 +353,7 @@ struct GradCall {
    bool loss_rule;
    float grad_scale;
    float *loss, *out;
-   bool ring = false;          // the call is fz_run_block_ring_grad: its scope, Variant and workspace
+   bool ring = false;          // the call is fz_run_block_ring_grad or fz_run_block_ring_loss_grad: its scope, Variant and workspace
 };
 
 template <class Args>
@@ -390,7 +395,7 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
 {
    const GradCall* const a = &call;
    const Graph& g = p->g;
-   const Variant v = a->ring ? ring_adjoint_variant(g, a->checkpoint_rows) : adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
+   const Variant v = a->ring ? ring_adjoint_variant(g, a->checkpoint_rows, a->loss_rule) : adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
    *vout = v;
    if (n_streams == 0 || n_samples == 0) return false;     // an empty block: nothing to differentiate, nothing touched
    if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
@@ -728,6 +733,32 @@ long fz_program_ring_grad_source(fz_program* p, uint32_t checkpoint_rows, char* 
 }
 
 int fz_run_block_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
+{
+   FZ_GUARD(
+      GradCall call = call_of(p, a);
+      call.ring = true;
+      return run_grad(p, call, n_streams, n_samples, hip_stream);)
+}
+
+int fz_program_ring_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_loss_grad_resources: bad arguments");
+      *out = resources_of(p, ring_adjoint_variant(p->g, checkpoint_rows, true));
+      return FZ_OK;)
+}
+
+long fz_program_ring_loss_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_adjoint_variant(p->g, checkpoint_rows, true)); });
+}
+
+long fz_program_ring_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_adjoint_variant(p->g, checkpoint_rows, true)); });
+}
+
+int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
    FZ_GUARD(
       GradCall call = call_of(p, a);

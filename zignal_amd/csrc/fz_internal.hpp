@@ -198,6 +198,8 @@ constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // fz_kernel_adjoint_ring.hip.inc: a text and a symbol of its own, the pending adjoints of the deep lines in an LDS ring); the last of
 // the reserved bits 12 .. 14 that nothing used, so a forward variant naming it stays refused as reserved.  Such a Variant is {P = 1,
 // U = checkpoint rows, block = 256 / 128 / 64 lanes per workgroup}; fz_grad.cpp: ring_adjoint_variant is the one place that makes one.
+// With FZ_VF_ADJOINT_LOSS next to it (and never FZ_VF_ADJOINT_SM): the ring kernel that forms dL/dy itself (fz_run_block_ring_loss_grad;
+// fz_kernel_adjoint_ring_loss.hip.inc: one more text and symbol of its own), the same P, U and block.
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte
@@ -255,7 +257,8 @@ std::string full_source(const Graph& g, const Variant& v);
 // the adjoint kernel (a Variant with FZ_VF_ADJOINT): gen_config / gen_body / skeleton_source hand over to these for it
 std::string gen_adjoint_config(const Graph& g, const Variant& v);
 // loss: also out(), the step's output values (FZ_VF_ADJOINT_LOSS).  ring: the body of fz_kernel_adjoint_ring.hip.inc (FZ_VF_ADJOINT_RING):
-// register rows compact, the lines in LDS read through rv[] and their adjoints kept in an LDS ring; without it the text is unchanged
+// register rows compact, the lines in LDS read through rv[] and their adjoints kept in an LDS ring; without it the text is unchanged.
+// Both: out() takes rv[] too (fz_kernel_adjoint_ring_loss.hip.inc)
 std::string gen_adjoint_body(const Graph& g, bool loss = false, bool ring = false);
 // How the ring adjoint kernel lays a graph out (fz_codegen.cpp; the one home of these counts for fz_grad.cpp too): the lines of depth
 // <= 8 keep compact REGISTER rows, every `in_lds` line is a RING LINE with its slots in the lane's LDS column, and the distinct
@@ -285,7 +288,7 @@ uint32_t grad_default_checkpoint(const Graph& g);
 uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C);
 uint32_t grad_sm_max_patch_rows();                                 // the longest patch any graph can have (one wire, the whole LDS)
 bool adjoint_variant_fits(const Graph& g, const Variant& v);       // an adjoint Variant the backward could have made for this graph
-bool ring_adjoint_variant_fits(const Graph& g, const Variant& v);  // a ring adjoint Variant (FZ_VF_ADJOINT_RING) fz_run_block_ring_grad could have made
+bool ring_adjoint_variant_fits(const Graph& g, const Variant& v);  // a ring adjoint Variant (FZ_VF_ADJOINT_RING, with or without FZ_VF_ADJOINT_LOSS) fz_run_block_ring_grad / _ring_loss_grad could have made
 // rows per LDS patch of the stream-major block-start-states kernel (x only), a multiple of 4 and of the unrolled group (fz_grad.cpp)
 uint32_t states_sm_patch_rows(const Graph& g);
 bool states_variant_fits(const Graph& g, const Variant& v);        // a states Variant (FZ_VF_STATES) fz_run_recording_grad could have made

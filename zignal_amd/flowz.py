@@ -880,6 +880,31 @@ class Program:
         n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), (float(grad_scale), out))
 
+    # -- the squared-error backward of a block with delay lines deeper than 8 samples (fz_run_block_ring_loss_grad) -------------------
+    def ring_loss_grad_resources(self, c: int = 0) -> dict:
+        """ring_grad_resources() of the kernel of run_block_ring_loss_grad at checkpoint stride c (0: the library default)"""
+        r = C.KernelResources()
+        C.check(C.lib.fz_program_ring_loss_grad_resources(self._h, int(c), ctypes.byref(r)))
+        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+    def ring_loss_grad_kernel_symbol(self, c: int = 0) -> str:
+        buf = ctypes.create_string_buffer(160)
+        C.check(C.lib.fz_program_ring_loss_grad_kernel_symbol(self._h, int(c), buf, 160))
+        return buf.value.decode()
+
+    def ring_loss_grad_source(self, c: int = 0) -> str:
+        n = C.check(C.lib.fz_program_ring_loss_grad_source(self._h, int(c), None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        C.check(C.lib.fz_program_ring_loss_grad_source(self._h, int(c), buf, n + 1))
+        return buf.value.decode()
+
+    def run_block_ring_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
+                                 checkpoint_rows: int = 0):
+        """run_block_loss_grad for graphs with delay lines deeper than 8 samples (fz_run_block_ring_loss_grad): the same arguments, the
+        same result dict, the rule of run_block_loss_grad and then the order of run_block_ring_grad; time-major frames only, the
+        workspace of run_block_ring_grad.  For a graph run_block_loss_grad takes it is run_block_loss_grad."""
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), None), ring=True)
+
     # -- the backward of a whole recording (fz_run_recording_grad): two-level checkpointing over the calls above ---------------------
     def recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
         """the rows per block a recording of T rows is cut into (block_rows = 0: the library's choice; include/flowz_hip.h has the rule)"""
@@ -938,8 +963,8 @@ class Program:
     def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None, ring=False):
         """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers; loss: None, or
         (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
-        (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is run_block_ring_grad (one
-        time-major block, dL/dy given)"""
+        (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is run_block_ring_grad, or with
+        loss run_block_ring_loss_grad (one time-major block)"""
         import torch
 
         if ring:
@@ -1046,7 +1071,10 @@ class Program:
             C.check(fn(self._h, ctypes.byref(a), int(window is not None), int(ns), w[0], w[1], int(T), recording[0],
                        ptr(out.get("state_out"), self.n_state), hs))
         elif window is None:
-            fn = C.lib.fz_run_block_ring_grad if ring else C.lib.fz_run_block_grad if loss is None else C.lib.fz_run_block_loss_grad
+            if ring:
+                fn = C.lib.fz_run_block_ring_grad if loss is None else C.lib.fz_run_block_ring_loss_grad
+            else:
+                fn = C.lib.fz_run_block_grad if loss is None else C.lib.fz_run_block_loss_grad
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(T), hs))
         else:
             fn = C.lib.fz_run_block_grad_stream_major if loss is None else C.lib.fz_run_block_loss_grad_stream_major
