@@ -746,6 +746,51 @@ int fz_program_states_resources(fz_program* p, uint32_t layout, fz_kernel_resour
 long fz_program_states_kernel_symbol(fz_program* p, uint32_t layout, char* buf, size_t cap);
 long fz_program_states_source(fz_program* p, uint32_t layout, char* buf, size_t cap);
 
+/* fz_run_recording_ring_grad, fz_run_recording_ring_loss_grad -- the backward of a whole recording of a graph with delay lines deeper
+ * than 8 samples, in bounded workspace: to fz_run_block_ring_grad / fz_run_block_ring_loss_grad what fz_run_recording_grad /
+ * fz_run_recording_loss_grad are to the one-block calls, time-major frames only (as the ring family is).
+ *
+ * The contract is the one stated above, read with the ring calls as the one-launch calls: every output bit -- in_grad, state0_grad,
+ * param_grad, const_grad, loss, out -- is that of fz_run_block_ring_grad / fz_run_block_ring_loss_grad over the same T rows, whatever
+ * block_rows is; state_out, if not NULL, receives the state after row T-1 with the bits of fz_run_block's state.  fz_grad_args and
+ * fz_loss_grad_args are taken unchanged, the accumulators are ADDED TO, state0_grad may be state_grad.  No new arithmetic rule: two
+ * ring blocks chain bitwise, also where a block is shorter than a line is deep (fz_run_block_ring_grad says so).
+ *
+ * Scope: that of fz_program_ring_grad_check.  For a graph without a deep line these calls ARE the FZ_GRAD_TIME_MAJOR
+ * fz_run_recording_grad / fz_run_recording_loss_grad: the same states kernel, B, workspace and bits.  fz_run_recording_*,
+ * fz_program_recording_workspace and fz_program_states_* keep refusing graphs with deep lines.
+ *
+ * How: one launch of the RING STATES kernel writes starts[ceil(T / B)][n_state][n_streams] at the head of the workspace (and state_out);
+ * then the ring adjoint or ring loss kernel is launched, unchanged, per block from the last to the first, with state = starts[k] and
+ * state_grad = the state0_grad of the launch before it.  The states kernel keeps each deep line as a value ring in LDS (the ring
+ * kernel's sweep 1 without the tape) and reads a line's D values back out of LDS in the caller's row order at every block start.
+ *
+ * B: block_rows, capped at T; for block_rows == 0 the least B with B^2 (n_register_state + C n_ring_lines) >= T n_state C -- the
+ * continuous minimiser of ceil(T / B) n_state + ceil(B / C) n_register_state + B n_ring_lines, the rows kept per stream -- rounded up
+ * to a multiple of max(4, C), and B = T when that is not smaller than T (n_register_state: the state floats of the lines of depth
+ * <= 8; C: the ring kernel's checkpoint stride).  Without a deep line this is the rule above.  fz_program_ring_recording_block_rows
+ * answers the B a call will use.
+ * WORKSPACE: ceil(T / B) * n_state * n_streams * 4 bytes plus fz_program_ring_grad_workspace(n_streams, B, C);
+ * fz_program_ring_recording_workspace answers it.
+ *
+ * Checks, all before a device is needed and in this order: the refusals of fz_program_ring_grad_check; block_rows a multiple of 4;
+ * n_samples < 2^31; those of the one-launch ring call over the T rows (state_out counted as an output) with this call's workspace
+ * size; those of every block launch; with more than one block, state0_grad not NULL.  n_streams == 0 or n_samples == 0: FZ_OK,
+ * nothing is touched.  Asynchronous on hip_stream.
+ *
+ * The ring states kernel is a kernel text of its own, fz_states_ring_kernel_u<U>b<lanes>_g<tag> (U rows per unrolled group; the
+ * lanes and lds_bytes of the ring adjoint kernel); fz_program_ring_states_* inspect it like fz_program_states_*. */
+int fz_program_ring_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows);
+int fz_program_ring_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
+                                        uint64_t* bytes);
+int fz_run_recording_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows, float* state_out,
+                               void* hip_stream);
+int fz_run_recording_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows,
+                                    float* state_out, void* hip_stream);
+int fz_program_ring_states_resources(fz_program* p, fz_kernel_resources* out);
+long fz_program_ring_states_kernel_symbol(fz_program* p, char* buf, size_t cap);
+long fz_program_ring_states_source(fz_program* p, char* buf, size_t cap);
+
 /* ------------------------------------------------------------------------------------------
  * 16-bit PCM frames.  fz_run_block_pcm16 is fz_run_block for a block whose frames are int16 on one side or on both: the caller
  * sends and receives 2 bytes per sample instead of 4, the conversions happen in the kernel.

@@ -42,6 +42,14 @@ run_block, torch's ((y - target) ** 2).mean() and 2 (y - target) / n, run_block_
 and timed as --loss does; the two legs must agree on the loss.  The pass mark is fused no slower than the route, the margin the route's own
 spread in that run.  The table goes to stdout and to profiles/r13/ring_loss_grad.txt.
 
+--rings --recording: the squared-error backward of a whole recording of those graphs, run_recording_ring_loss_grad
+(fz_run_recording_ring_loss_grad: one ring states launch, then the ring loss kernel per block in reverse), against two alternatives on the
+same buffers, interleaved in one process and timed as --recording does.  one: the one-launch run_block_ring_loss_grad over all rows, where
+its workspace fits the board's free memory.  route: what a caller had before -- run_block per block into a scratch y (only to get the
+state before every block), then run_block_ring_loss_grad per block from the last to the first, with the same B.  65 536 x 16 384 and
+1 048 576 x 4096, time-major; the three legs must agree on the loss bit for bit.  The mark is rec no slower than the route, the margin the
+route's own spread in that run; a line that misses it says so.  The table goes to stdout and to profiles/r14/ring_recording.txt.
+
 usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings]
 """
 import argparse
@@ -463,6 +471,98 @@ def rings_loss_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
+def rings_recording_bench(a, torch):
+    """the squared-error backward of a whole recording of graphs with delay lines in LDS: the recording call, the one-launch call, and
+    blocks chained by hand"""
+    import time
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+    props = torch.cuda.get_device_properties(0)
+    say(f"# command: tools/grad_bench.py --rings --recording --steps {a.steps} --legs {a.legs}")
+    say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+    say("# rec = one run_recording_ring_loss_grad call; one = one run_block_ring_loss_grad launch over all rows (where its workspace fits);")
+    say("# route = run_block per block into a scratch y for the states, then run_block_ring_loss_grad per block in reverse (same B as rec); time-major frames")
+    say(f"# HIP events, {a.steps} calls per leg and pass, a forward and a backward pass over the legs; spread = max - min of a leg's own repeats;")
+    say("# mark = rec median <= route median + the route's spread")
+    say(f"{'graph':16s} {'streams x T':>16s} {'B':>5s} {'route ms':>9s} {'spread':>7s} {'rec ms':>9s} {'spread':>7s} {'one ms':>9s} {'spread':>7s} "
+        f"{'rec/route':>9s} {'rec/one':>8s} {'mark':>5s} {'ws rec MB':>10s} {'ws route MB':>11s} {'ws one MB':>10s}  ring states kernel")
+    shapes = REC_SHAPES["small"] + REC_SHAPES["large"] if a.legs == "all" else REC_SHAPES[a.legs]
+    want = ("x", "state", "params", "consts", "loss")
+    for ns, T in shapes:
+        x = torch.empty((T, ns, 1), dtype=torch.float32, device="cuda")
+        F.synth_fill(x, seed=W.SEED)
+        target = torch.empty_like(x)
+        F.synth_fill(target, seed=W.SEED + 1)
+        n = float(ns) * T
+        for name, fn in RING_GRAPHS.items():
+            prog = F.compile(F.from_sexpr(fn()))
+            s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+            B = prog.ring_recording_block_rows(T)
+            nb = (T + B - 1) // B
+            ws_rec, ws_one = prog.ring_recording_workspace_bytes(ns, T), prog.ring_grad_workspace_bytes(ns, T)
+            # the route keeps the state before every block itself, a scratch y of one block, and one block's ring workspace
+            ws_route = nb * prog.n_state * ns * 4 + B * ns * prog.n_out * 4 + prog.ring_grad_workspace_bytes(ns, B)
+            ws = torch.empty(ws_rec // 4, dtype=torch.float32, device="cuda")
+            states = torch.empty((nb + 1, prog.n_state, ns), dtype=torch.float32, device="cuda")
+            y = torch.empty((B, ns, 1), dtype=torch.float32, device="cuda")
+
+            def rec():
+                r = prog.run_recording_ring_loss_grad(x, target, s0, None, grad_scale=2.0 / n, want=want, workspace=ws)
+                return r["loss"].double().sum() / n
+
+            def route():
+                states[0].copy_(s0)
+                for k in range(nb):
+                    rows = min(B, T - k * B)
+                    states[k + 1].copy_(states[k])
+                    prog.run_block(x[k * B:k * B + rows], state=states[k + 1], out=y[:rows])
+                acc, sg = {}, None
+                for k in range(nb - 1, -1, -1):
+                    rows = min(B, T - k * B)
+                    r = prog.run_block_ring_loss_grad(x[k * B:k * B + rows], target[k * B:k * B + rows], states[k], None, state_grad=sg, grad_scale=2.0 / n,
+                                                      want=want, accum=acc)
+                    # (the accumulators the next launch adds to: only those the graph has rows of)
+                    acc, sg = {k: r[k] for k, rows_k in (("params", prog.n_param), ("consts", prog.n_const), ("loss", 1)) if rows_k}, r["state"]
+                return acc["loss"].double().sum() / n
+
+            def one():
+                r = prog.run_block_ring_loss_grad(x, target, s0, None, grad_scale=2.0 / n, want=want)
+                return r["loss"].double().sum() / n
+            legs = {"route": route, "rec": rec}
+            if ws_one + (4 << 30) < torch.cuda.mem_get_info()[0]:
+                legs["one"] = one
+            vals = {k: float(f()) for k, f in legs.items()}        # JIT, allocator; and the legs agree on the loss
+            assert all(v == vals["rec"] for v in vals.values()), vals     # (bit for bit: the same per-stream sums)
+            torch.cuda.synchronize()
+            t_end = time.time() + 0.1
+            while time.time() < t_end:                          # at least 100 ms of the yardstick before the first timing
+                route()
+                torch.cuda.synchronize()
+            got = {k: [] for k in legs}
+            for order in (list(legs), list(legs)[::-1]):
+                for k in order:
+                    got[k] += samples(legs[k], a.steps, torch)
+            med = {k: float(np.median(v)) for k, v in got.items()}
+            sp = {k: max(v) - min(v) for k, v in got.items()}
+            one_s = f"{med['one']:9.3f} {sp['one']:7.3f}" if "one" in med else f"{'-':>9s} {'-':>7s}"
+            ratio_one = f"{med['rec'] / med['one']:8.3f}" if "one" in med else f"{'-':>8s}"
+            say(f"{name:16s} {f'{ns} x {T}':>16s} {B:5d} {med['route']:9.3f} {sp['route']:7.3f} {med['rec']:9.3f} {sp['rec']:7.3f} {one_s} "
+                f"{med['rec'] / med['route']:9.3f} {ratio_one} {'yes' if med['rec'] <= med['route'] + sp['route'] else 'NO':>5s} {ws_rec / 2**20:10.1f} "
+                f"{ws_route / 2**20:11.1f} {ws_one / 2**20:10.1f}  {prog.ring_states_kernel_symbol()}")
+            say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
+            del s0, ws, states, y
+            torch.cuda.empty_cache()
+        del x, target
+        torch.cuda.empty_cache()
+    out = os.path.join(ROOT, "profiles", "r14", "ring_recording.txt")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
@@ -471,11 +571,13 @@ def main():
     ap.add_argument("--layout", choices=("time-major", "stream-major", "compare"), default="time-major")
     ap.add_argument("--loss", action="store_true", help="the fused squared-error backward against forward + torch MSE + backward, both layouts")
     ap.add_argument("--recording", action="store_true", help="the backward of a whole recording against the one-launch call and blocks chained by hand")
-    ap.add_argument("--rings", action="store_true", help="forward against the ring backward of graphs with delay lines deeper than 8 samples; with --loss: their fused squared-error backward against the route")
+    ap.add_argument("--rings", action="store_true", help="forward against the ring backward of graphs with delay lines deeper than 8 samples; with --loss: their fused squared-error backward against the route; with --recording: the backward of a whole recording of them")
     a = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
+    if a.rings and a.recording:
+        return rings_recording_bench(a, torch)
     if a.rings and a.loss:
         return rings_loss_bench(a, torch)
     if a.loss:

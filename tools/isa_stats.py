@@ -10,6 +10,9 @@ usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par
                                                            or a name of tests/ring_grad_graphs.py)
        tools/isa_stats.py ringlossgrad [graph]             the same line for the kernel of fz_run_block_ring_loss_grad, next to the plain
                                                            ring kernel's figures (graph: also a name of tests/ring_loss_graphs.py)
+       tools/isa_stats.py ringstates [graph]               the block-start-states kernel of fz_run_recording_ring_grad next to the ring
+                                                           adjoint kernel: registers, spills, scratch, LDS bytes, and the ds_* and
+                                                           vector-memory instructions in the kernel (graph: as for ringlossgrad)
 """
 import glob
 import os
@@ -117,8 +120,40 @@ def ring_grad_lines(name, loss=False):
     return out
 
 
+def ring_states_lines(name):
+    """the ring states kernel: its resources next to the ring adjoint kernel's, and the instructions of its text -- the unrolled group of
+    U rows (U ring-read sets, U ds_write per ring line, the next group's U x loads) plus the two state dumps (block start, state_out)"""
+    import ring_loss_graphs as RL
+    build = RL.GRAPHS.get(name) or GRAPHS[name]
+    p = F.compile(F.from_sexpr(build()))
+    r, ring = p.ring_states_resources(), p.ring_grad_resources()
+    old = os.environ.get("FLOWZ_HIP_CACHE")
+    try:
+        with tempfile.TemporaryDirectory() as td:
+            os.environ["FLOWZ_HIP_CACHE"] = td
+            F.compile(F.from_sexpr(build())).ring_states_resources()
+            dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", glob.glob(td + "/*.hsaco")[0]], text=True)
+    finally:
+        if old is None:
+            os.environ.pop("FLOWZ_HIP_CACHE", None)
+        else:
+            os.environ["FLOWZ_HIP_CACHE"] = old
+    ops = [ln.split()[0] for ln in dis.splitlines() if ln.split()]
+    vmem = [o for o in ops if o.startswith(("global_load", "global_store", "buffer_load", "buffer_store", "flat_load", "flat_store"))]
+    n = {"ds_read": sum(o.startswith("ds_read") for o in ops), "ds_write": sum(o.startswith("ds_write") for o in ops),
+         "vmem_load": sum("load" in o for o in vmem), "vmem_store": sum("store" in o for o in vmem), "valu": sum(o.startswith("v_") for o in ops),
+         "s_barrier": ops.count("s_barrier"), "atomic": sum("atomic" in o for o in ops)}
+    return [f"{name} {p.ring_states_kernel_symbol()}: U {r['unroll']}, {r['vgprs'] + r['agprs']} VGPRs (ring adjoint {ring['vgprs'] + ring['agprs']}), "
+            f"{r['sgprs']} SGPRs, {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills (ring adjoint {ring['vgpr_spills']} / {ring['sgpr_spills']}), "
+            f"{r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS (ring adjoint {ring['lds_bytes']})",
+            "  in the kernel: " + ", ".join(f"{v} {k}" for k, v in n.items())]
+
+
 def main():
     a = sys.argv[1:]
+    if a and a[0] == "ringstates":
+        print("\n".join(ring_states_lines(a[1] if len(a) > 1 else "ldsring")))
+        return
     if a and a[0] == "ringgrad":
         print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring")))
         return

@@ -195,6 +195,13 @@ def _load():
         "fz_program_states_resources": (ctypes.c_int, [P, u32, ctypes.POINTER(KernelResources)]),
         "fz_program_states_kernel_symbol": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_states_source": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_ring_recording_block_rows": (ctypes.c_int, [P, u32, u32, u32, ctypes.POINTER(u32)]),
+        "fz_program_ring_recording_workspace": (ctypes.c_int, [P, u64, u32, u32, u32, ctypes.POINTER(u64)]),
+        "fz_run_recording_ring_grad": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, u32, P, P]),
+        "fz_run_recording_ring_loss_grad": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u64, u32, u32, P, P]),
+        "fz_program_ring_states_resources": (ctypes.c_int, [P, ctypes.POINTER(KernelResources)]),
+        "fz_program_ring_states_kernel_symbol": (ctypes.c_long, [P, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_ring_states_source": (ctypes.c_long, [P, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_pcm16_check": (ctypes.c_int, [P]),
         "fz_run_block_pcm16": (ctypes.c_int, [P, P, P, P, P, u64, u32, u32, u32, P]),
         "fz_program_pcm16_resources": (ctypes.c_int, [P, u32, u32, u64, ctypes.POINTER(KernelResources)]),

@@ -20,6 +20,10 @@ adjoint kernel with the loss formed in it); mse() keeps refusing graphs with del
 mse_recording(prog, x, target, ...) is the same loss over a whole recording of many blocks in bounded workspace
 (Program.run_recording_loss_grad: one forward launch that keeps the state before every block, then the loss kernel block by block
 from the last to the first), and also returns the state after the recording.
+
+mse_recording_rings(prog, x, target, ...) is mse_recording() for every graph run_rings() takes, time-major
+(Program.run_recording_ring_loss_grad: the ring states kernel, then the ring loss kernel block by block); mse_recording() keeps refusing
+graphs with delay lines deeper than 8 samples.
 """
 from __future__ import annotations
 
@@ -173,15 +177,16 @@ def mse_rings(prog: Program, x, target, state=None, params=None, consts=None):
 
 class _MseRecording(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, prog, x, target, state, params, consts, block_rows=0, stream_major=False):
+    def forward(ctx, prog, x, target, state, params, consts, block_rows=0, stream_major=False, rings=False):
         _apply_consts(prog, consts)
         _, need_x, _, need_s, need_p, need_c = ctx.needs_input_grad[:6]
         want = ["loss", "state_out"] + [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
         xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
         n = xx.shape[0] * xx.shape[1] * prog.n_out                    # elements of y: the mean is over all of them
-        r = prog.run_recording_loss_grad(xx, target.detach().contiguous(), state.detach() if state is not None else None,
-                                         params.detach() if params is not None else None, grad_scale=2.0 / n, want=want,
-                                         block_rows=int(block_rows), stream_major=bool(stream_major))
+        kw = {} if rings else {"stream_major": bool(stream_major)}
+        r = (prog.run_recording_ring_loss_grad if rings else prog.run_recording_loss_grad)(
+            xx, target.detach().contiguous(), state.detach() if state is not None else None,
+            params.detach() if params is not None else None, grad_scale=2.0 / n, want=want, block_rows=int(block_rows), **kw)
         ctx.grads = (r["x"].reshape(x.shape) if need_x else None, r["state"] if need_s else None, r["params"] if need_p else None,
                      # per-stream coefficient adjoints, summed over the streams in float64
                      r["consts"][:prog.n_const].double().sum(1).to(consts.dtype).to(consts.device) if need_c else None)
@@ -193,7 +198,7 @@ class _MseRecording(torch.autograd.Function):
     def backward(ctx, g, _gs):
         gx, gs, gp, gc = ctx.grads
         scaled = lambda t: None if t is None else t * g.to(t.device)   # noqa: E731  (the upstream scalar)
-        return None, scaled(gx), None, scaled(gs), scaled(gp), scaled(gc), None, None
+        return None, scaled(gx), None, scaled(gs), scaled(gp), scaled(gc), None, None, None
 
 
 def mse_recording(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0, stream_major=False):
@@ -210,4 +215,20 @@ def mse_recording(prog: Program, x, target, state=None, params=None, consts=None
         if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
             raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
     loss, state_out = _MseRecording.apply(prog, x, target, state, params, consts, int(block_rows), bool(stream_major))
+    return loss, state_out.detach()
+
+
+def mse_recording_rings(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0):
+    """mse_recording() for graphs with delay lines deeper than 8 samples -- and every graph mse_recording() takes --, time-major frames:
+    returns (loss, state_out) over a whole recording in bounded workspace (Program.ring_recording_workspace_bytes: the state before every
+    block plus one block's checkpoints and tape; block_rows = 0 lets the library choose, otherwise a multiple of 4).  The gradients
+    have the bits of mse_rings()'s over the same rows (include/flowz_hip.h: fz_run_recording_ring_loss_grad)."""
+    if not prog.ring_grad_supported():
+        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
+    if x.dim() == 2 and prog.n_in != 1:
+        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
+    if consts is not None:
+        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
+            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
+    loss, state_out = _MseRecording.apply(prog, x, target, state, params, consts, int(block_rows), False, True)
     return loss, state_out.detach()

@@ -33,6 +33,7 @@ extern const char* const kSkeletonAdjointLoss;   // fz_kernel_adjoint_loss.hip.i
 extern const char* const kSkeletonAdjointLossSm; // fz_kernel_adjoint_loss_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonStates;     // fz_kernel_states.hip.inc: the block-start states of a recording (the adjoint body's fwd alone)
 extern const char* const kSkeletonStatesSm;   // fz_kernel_states_sm.hip.inc: the same for stream-major buffers
+extern const char* const kSkeletonStatesRing; // fz_kernel_states_ring.hip.inc: the same for graphs with delay lines in LDS (the ring body's fwd alone)
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
@@ -45,7 +46,9 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm, pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
    static const std::string adj_loss = kSkeletonAdjointLoss, adj_loss_sm = kSkeletonAdjointLossSm;
    static const std::string states = kSkeletonStates, states_sm = kSkeletonStatesSm;
-   static const std::string adj_ring = kSkeletonAdjointRing, adj_ring_loss = kSkeletonAdjointRingLoss;
+   static const std::string adj_ring = kSkeletonAdjointRing, adj_ring_loss = kSkeletonAdjointRingLoss, states_ring = kSkeletonStatesRing;
+   // (states + ring: the block-start-states kernel of a ring recording, before either bit alone)
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_RING)) return states_ring;
    // (ring + loss before ring and before loss: the three-bit combination is a text of its own)
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_LOSS)) return adj_ring_loss;
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING)) return adj_ring;
@@ -61,6 +64,8 @@ const std::string& skeleton_source(const Variant& v)
 // fz_block_kernel_p<streams/lane>u<unroll>b<block>[s<segments>]f<flags>
 std::string kernel_name(const Graph& g, const Variant& v)
 {
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_RING))   // (states + ring: before either alone)
+      return "fz_states_ring_kernel_u" + std::to_string(v.U) + "b" + std::to_string(v.block);
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES))   // (the states bit means something next to FZ_VF_ADJOINT only)
       return (v.flags & FZ_VF_ADJOINT_SM) ? "fz_states_sm_kernel_u" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block)
                                           : "fz_states_kernel_u" + std::to_string(v.U) + "b" + std::to_string(v.block);

@@ -12,6 +12,10 @@
 // the launch with the calls above; for a graph without such a line it IS fz_run_block_grad.  Under the squared-error loss
 // (fz_run_block_ring_loss_grad) it is that family's call with FZ_VF_ADJOINT_LOSS next to the ring bit: fz_kernel_adjoint_ring_loss.hip.inc,
 // the ring kernel's C, block and workspace; for a graph without such a line it IS fz_run_block_loss_grad.
+// The backward of a whole recording of such a graph (fz_run_recording_ring_grad, fz_run_recording_ring_loss_grad) is run_recording with
+// the ring family's pieces: the ring states kernel (FZ_VF_STATES next to the ring bit; fz_kernel_states_ring.hip.inc), the ring
+// launches per block, a block length and a workspace that count the tape; for a graph without such a line it IS the time-major
+// fz_run_recording_grad / fz_run_recording_loss_grad.
 #include <cmath>
 #include <algorithm>
 #include <cstddef>
@@ -234,6 +238,27 @@ static Variant states_variant(const Graph& g, bool stream_major)
    return v;
 }
 
+// the Variant of the block-start-states kernel of a ring recording: the scope and the workgroup of the ring backward (its value rings
+// are that kernel's LDS bytes), the unrolled group of the states kernel; for a graph without a ring line the time-major states Variant itself
+static Variant ring_states_variant(const Graph& g)
+{
+   const Variant a = ring_adjoint_variant(g, 0);
+   if (!(a.flags & FZ_VF_ADJOINT_RING)) return states_variant(g, false);
+   Variant v;
+   v.P = 1;
+   v.U = states_unroll(g);
+   v.block = a.block;
+   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | FZ_VF_ADJOINT_RING;
+   return v;
+}
+
+// could ring_states_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
+bool ring_states_variant_fits(const Graph& g, const Variant& v)
+{
+   if (v.flags != (FZ_VF_ADJOINT | FZ_VF_STATES | FZ_VF_ADJOINT_RING) || !grad_unsupported_reason(g, true).empty() || !has_ring_line(g)) return false;
+   return v.P == 1 && v.U == states_unroll(g) && v.block != 0 && v.block == ring_block(ring_layout(g));
+}
+
 static bool layout_is_stream_major(uint32_t layout)
 {
    if (layout != FZ_GRAD_TIME_MAJOR && layout != FZ_GRAD_STREAM_MAJOR) fail(FZ_E_INVALID, "layout must be FZ_GRAD_TIME_MAJOR or FZ_GRAD_STREAM_MAJOR");
@@ -266,6 +291,23 @@ static uint32_t recording_block_rows(uint32_t T, uint32_t C, uint32_t block_rows
    const uint64_t m = std::max<uint32_t>(4u, C);
    uint64_t B = (uint64_t)std::ceil(std::sqrt((double)T * (double)C));
    while (B * B < (uint64_t)T * C) ++B;                      // (whatever sqrt rounded: B is the least integer with B^2 >= T C)
+   B = (B + m - 1) / m * m;
+   return B < T ? (uint32_t)B : T;
+}
+
+// The rows per block of a recording of a ring graph (the one home of this rule; include/flowz_hip.h states it).  The row sets kept are
+// ceil(T / B) n_state of starts, ceil(B / C) n_register_state of checkpoints and B n_ring_lines of tape; block_rows == 0 starts from
+// the continuous minimiser of their sum, the least B with B^2 (n_register_state + C n_ring_lines) >= T n_state C, rounded up like
+// recording_block_rows.  Without a ring line the rule IS recording_block_rows.
+static uint32_t ring_recording_block_rows(const Graph& g, uint32_t T, uint32_t C, uint32_t block_rows)
+{
+   const RingLayout rl = ring_layout(g);
+   if (!rl.n_rl()) return recording_block_rows(T, C, block_rows);
+   if (block_rows) return std::min(block_rows, T);
+   const uint64_t m = std::max<uint32_t>(4u, C), den = (uint64_t)rl.n_reg() + (uint64_t)C * rl.n_rl(), num = (uint64_t)T * g.n_state * C;
+   uint64_t B = (uint64_t)std::ceil(std::sqrt((double)num / (double)den));
+   while (B && (B - 1) * (B - 1) * den >= num) --B;          // (whatever sqrt rounded: B is the least integer with B^2 den >= num)
+   while (B * B * den < num) ++B;
    B = (B + m - 1) / m * m;
    return B < T ? (uint32_t)B : T;
 }
@@ -353,7 +395,7 @@ struct GradCall {
    bool loss_rule;
    float grad_scale;
    float *loss, *out;
-   bool ring = false;          // the call is fz_run_block_ring_grad or fz_run_block_ring_loss_grad: its scope, Variant and workspace
+   bool ring = false;          // the call is of the ring family (fz_run_block_ring_*, fz_run_recording_ring_*): its scope, Variant and workspace
 };
 
 template <class Args>
@@ -416,7 +458,7 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
    if (a->loss_rule && !a->ybar) fail(FZ_E_INVALID, "target is null: the loss compares the outputs with it");
    if (g.n_out && !a->ybar) fail(FZ_E_INVALID, "out_grad is null but the graph has output wires");
    const uint64_t need = rec ? rec->need : ring_workspace_bytes(g, n_streams, n_samples, v);
-   const std::string ws_fn = rec ? "fz_program_recording_workspace" : a->ring ? "fz_program_ring_grad_workspace" : "fz_program_grad_workspace";
+   const std::string ws_fn = rec ? (a->ring ? "fz_program_ring_recording_workspace" : "fz_program_recording_workspace") : a->ring ? "fz_program_ring_grad_workspace" : "fz_program_grad_workspace";
    if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: " + ws_fn + " says " + std::to_string(need) + " bytes");
    if (need && a->workspace_bytes < need)
       fail(FZ_E_INVALID, "workspace_bytes " + std::to_string(a->workspace_bytes) + " is less than the " + std::to_string(need) + " bytes " + ws_fn + " asks for");
@@ -529,17 +571,27 @@ static uint64_t recording_workspace_bytes(const Graph& g, uint64_t n_streams, ui
    return T ? starts_bytes(g, n_streams, T, B) + workspace_bytes(g, n_streams, B, C) : 0;
 }
 
+// the workspace of a ring recording (the one home of this rule): the block-start states, then one block's ring workspace -- v is the
+// block launches' Variant; for a graph without a ring line this is recording_workspace_bytes
+static uint64_t ring_recording_workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t T, uint32_t B, const Variant& v)
+{
+   return T ? starts_bytes(g, n_streams, T, B) + ring_workspace_bytes(g, n_streams, B, v) : 0;
+}
+
 // The backward of a recording: the states kernel once, then the block launches from the last block to the first (the contract is in
 // include/flowz_hip.h).  Every check -- of the call over its T rows, then of every block launch as a direct call would be checked --
-// runs before a device is needed.
+// runs before a device is needed.  call.ring: the recording of the ring family (time-major) -- the scope, the states kernel, B and
+// the workspace are that family's, the rest is shared.
 static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
                          uint32_t block_rows, float* state_out, void* stream)
 {
    const Graph& g = p->g;
    const bool stream_major = layout_is_stream_major(layout);
-   require_supported(g);                                   // (scope first: the refusals of fz_program_grad_check)
+   if (call.ring) (void)ring_adjoint_variant(g, 0);        // (scope first: the refusals of fz_program_ring_grad_check)
+   else require_supported(g);                              // (... of fz_program_grad_check)
    // (a graph without delay lines launches no states kernel: its LDS patch is not asked to fit)
-   const Variant sv = g.n_state ? states_variant(g, stream_major) : Variant{};
+   const Variant sv = !g.n_state ? Variant{} : call.ring ? ring_states_variant(g) : states_variant(g, stream_major);
+   auto rows_per_block = [&](uint32_t C) { return call.ring ? ring_recording_block_rows(g, n_samples, C, block_rows) : recording_block_rows(n_samples, C, block_rows); };
    if (!stream_major && block_rows % 4)
       fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
    if (!stream_major && (row0 || (rows_total && rows_total != n_samples)))
@@ -550,12 +602,12 @@ static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, u
    Variant v;
    {
       // (C is needed for the workspace the checks ask for; adjoint_variant validates checkpoint_rows and the loss's outputs)
-      const Variant v0 = adjoint_variant(g, call.checkpoint_rows, stream_major, call.loss_rule);
-      const uint32_t B0 = n_samples ? recording_block_rows(n_samples, v0.U, block_rows) : 0;
-      const RecordingCheck rec{recording_workspace_bytes(g, n_streams, n_samples, B0, v0.U), state_out};
+      const Variant v0 = call.ring ? ring_adjoint_variant(g, call.checkpoint_rows, call.loss_rule) : adjoint_variant(g, call.checkpoint_rows, stream_major, call.loss_rule);
+      const uint32_t B0 = n_samples ? rows_per_block(v0.U) : 0;
+      const RecordingCheck rec{call.ring ? ring_recording_workspace_bytes(g, n_streams, n_samples, B0, v0) : recording_workspace_bytes(g, n_streams, n_samples, B0, v0.U), state_out};
       if (!check_grad(p, call, n_streams, n_samples, sm, &v, &rec)) return FZ_OK;
    }
-   const uint32_t B = recording_block_rows(n_samples, v.U, block_rows), nb = (uint32_t)(((uint64_t)n_samples + B - 1) / B);
+   const uint32_t B = rows_per_block(v.U), nb = (uint32_t)(((uint64_t)n_samples + B - 1) / B);
    if (nb > 1 && g.n_state && !call.state0_grad)
       fail(FZ_E_INVALID, "state0_grad is null: the blocks of a recording chain through it (it may be state_grad)");
    float* const starts = static_cast<float*>(call.workspace);
@@ -764,6 +816,65 @@ int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint6
       GradCall call = call_of(p, a);
       call.ring = true;
       return run_grad(p, call, n_streams, n_samples, hip_stream);)
+}
+
+int fz_program_ring_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows)
+{
+   FZ_GUARD(
+      if (!p || !rows) fail(FZ_E_INVALID, "fz_program_ring_recording_block_rows: bad arguments");
+      const Variant v = ring_adjoint_variant(p->g, checkpoint_rows);
+      if (n_rows >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
+      *rows = n_rows ? ring_recording_block_rows(p->g, n_rows, v.U, block_rows) : 0;
+      return FZ_OK;)
+}
+
+int fz_program_ring_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
+                                        uint64_t* bytes)
+{
+   FZ_GUARD(
+      if (!p || !bytes) fail(FZ_E_INVALID, "fz_program_ring_recording_workspace: bad arguments");
+      const Variant v = ring_adjoint_variant(p->g, checkpoint_rows);
+      if (block_rows % 4) fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
+      if (n_rows >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
+      const uint32_t B = n_rows ? ring_recording_block_rows(p->g, n_rows, v.U, block_rows) : 0;
+      *bytes = ring_recording_workspace_bytes(p->g, n_streams, n_rows, B, v);
+      return FZ_OK;)
+}
+
+int fz_run_recording_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows, float* state_out,
+                               void* hip_stream)
+{
+   FZ_GUARD(
+      GradCall call = call_of(p, a);
+      call.ring = true;
+      return run_recording(p, call, FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
+}
+
+int fz_run_recording_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows,
+                                    float* state_out, void* hip_stream)
+{
+   FZ_GUARD(
+      GradCall call = call_of(p, a);
+      call.ring = true;
+      return run_recording(p, call, FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
+}
+
+int fz_program_ring_states_resources(fz_program* p, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_states_resources: bad arguments");
+      *out = resources_of(p, ring_states_variant(p->g));
+      return FZ_OK;)
+}
+
+long fz_program_ring_states_kernel_symbol(fz_program* p, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_states_variant(p->g)); });
+}
+
+long fz_program_ring_states_source(fz_program* p, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_states_variant(p->g)); });
 }
 
 int fz_program_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,

@@ -200,6 +200,9 @@ constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // U = checkpoint rows, block = 256 / 128 / 64 lanes per workgroup}; fz_grad.cpp: ring_adjoint_variant is the one place that makes one.
 // With FZ_VF_ADJOINT_LOSS next to it (and never FZ_VF_ADJOINT_SM): the ring kernel that forms dL/dy itself (fz_run_block_ring_loss_grad;
 // fz_kernel_adjoint_ring_loss.hip.inc: one more text and symbol of its own), the same P, U and block.
+// With FZ_VF_STATES next to it (and neither FZ_VF_ADJOINT_LOSS nor FZ_VF_ADJOINT_SM): the block-start-states kernel of a ring recording
+// (fz_run_recording_ring_grad; fz_kernel_states_ring.hip.inc: a text and a symbol of its own), {P = 1, U = the rows of one unrolled
+// group, block = the ring adjoint kernel's}; fz_grad.cpp: ring_states_variant is the one place that makes one.
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte
@@ -292,6 +295,7 @@ bool ring_adjoint_variant_fits(const Graph& g, const Variant& v);  // a ring adj
 // rows per LDS patch of the stream-major block-start-states kernel (x only), a multiple of 4 and of the unrolled group (fz_grad.cpp)
 uint32_t states_sm_patch_rows(const Graph& g);
 bool states_variant_fits(const Graph& g, const Variant& v);        // a states Variant (FZ_VF_STATES) fz_run_recording_grad could have made
+bool ring_states_variant_fits(const Graph& g, const Variant& v);   // a ring states Variant (FZ_VF_STATES | FZ_VF_ADJOINT_RING) fz_run_recording_ring_grad could have made
 // 16-bit PCM frames (fz_pcm16.cpp): why the PCM kernel does not take this graph ("" = it does), and whether v is a Variant
 // fz_run_block_pcm16 could have made for it
 std::string pcm16_unsupported_reason(const Graph& g);

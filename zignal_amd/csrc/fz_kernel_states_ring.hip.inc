@@ -1,0 +1,145 @@
+// fz_states_ring_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the BLOCK-START STATES of a recording whose graph has delay
+// lines deeper than 8 samples (include/flowz_hip.h: fz_run_recording_ring_grad).  The skeleton of fz_kernel_states.hip.inc with sweep 1
+// of fz_kernel_adjoint_ring.hip.inc as its step: one lane owns one stream (wave64; the workgroups of the last wave are masked by the
+// stream count), the generated fz_adj::fwd in ring mode (fz_codegen.cpp: gen_adjoint_body) is the step, so the state bits are the forward
+// kernels' and that sweep's.  It stores the state before rows 0, B, 2B, ... into starts[ceil(T / B)][n_state][n_streams], one coalesced
+// row per state float, and the state after row T-1 into state_out if that is given.  It writes nothing else: no output frames, no
+// checkpoints, no tape.
+//
+// Lines of depth <= 8 are register rows, COMPACT as in the ring adjoint kernel (register row r is the caller's state row fz_reg_row[r]).
+// A ring line l with source node u keeps a value ring in the lane's LDS column: slot q mod D holds u[q], filled from the caller's `state`
+// (slot D - 1 - j holds u[-1-j], the state row row0 + j); pos[l], a scalar, is the row number modulo D.  Per row: the ring reads, then
+// fz_adj::fwd, then one ds_write_b32 per line.  A lane touches only its own column: no barriers, no atomics.
+// Where a row starts a block (a comparison of two scalars: the row, the next block's first row) the register rows go to their caller
+// rows and every ring line is read out of LDS in the caller's order, row0 + j = ring[(pos - 1 - j) mod D], one coalesced store per
+// row: D LDS reads and D stores per line and block, D / B per row -- the price of a start.
+//
+// The rows go in groups of FZ_U, and the x rows of the NEXT group are requested before the recursion of the current group runs (two
+// groups of FZ_U * n_in registers); occupancy hides what is left.  Rows behind the last are fetched from row T-1 and not used.
+//
+// LDS: ring[slot][lane], FZ_RING_SLOTS x FZ_BLOCK floats -- the ring adjoint kernel's bytes, so the same workgroups per CU.
+// HBM bytes per stream-sample: 4 n_in + 4 n_state / B.
+//
+// Compiled by hiprtc with the build options of every other kernel: -ffp-contract=off (no FMA: one rounding per operation), correctly
+// rounded division and square root, denormals kept.
+#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_NREG FZ_NRL FZ_NRR FZ_RING_SLOTS FZ_U FZ_BLOCK
+                               // FZ_KERNEL and the tables fz_reg_row, fz_rl_row0 / fz_rl_depth / fz_rl_slot0, fz_rr_line / fz_rr_delay
+
+#define FZ_P 1
+typedef float V;
+typedef double VD;
+#define FZ_A(n) ((n) > 0 ? (n) : 1)
+
+#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd } in ring mode; fwd is all this kernel calls
+
+struct fz_states_ring_args {   // the layout of fz_states_args (fz_kernel_states.hip.inc): one host-side image serves both
+   const float* in;            // [T][n_streams][n_in]
+   const float* state;         // [n_state][n_streams]   the state before the recording (register and ring lines' rows)
+   const float* params;        // [n_param][n_streams]
+   float* starts;              // [ceil(T / B)][n_state][n_streams]   the state before rows 0, B, 2B, ...
+   float* state_out;           // [n_state][n_streams]   the state after row T-1; null: not written
+   unsigned long long n_streams;
+   unsigned int n_samples;     // T >= 1
+   unsigned int block_rows;    // B >= 1
+   float c[FZ_A(FZ_NCONST)];   // the program's uniform coefficients
+};
+
+// the whole state in the caller's rows: the register rows, then every ring line read back from its value ring, youngest value first
+static __device__ __forceinline__ void fz_dump_state(float* dst, size_t ns, const float* st, const float* ring, const unsigned* pos)
+{
+#pragma unroll
+   for (int r = 0; r < FZ_NREG; ++r) dst[(size_t)fz_reg_row[r] * ns] = st[r];
+#pragma unroll
+   for (int l = 0; l < FZ_NRL; ++l) {
+      const unsigned D = fz_rl_depth[l];
+      unsigned slot = pos[l];                              // (the slot of u[t]: the row before it is u[t-1], the state row row0)
+#pragma unroll 4
+      for (unsigned j = 0; j < D; ++j) {
+         slot = slot ? slot - 1u : D - 1u;
+         dst[(size_t)(fz_rl_row0[l] + j) * ns] = ring[(size_t)(fz_rl_slot0[l] + slot) * FZ_BLOCK];
+      }
+   }
+}
+
+extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_ring_args a)
+{
+   __shared__ float fz_ring[FZ_RING_SLOTS * FZ_BLOCK];
+   const size_t ns = a.n_streams;
+   const size_t s = (size_t)blockIdx.x * FZ_BLOCK + threadIdx.x;
+   if (s >= ns) return;                                  // the masked tail of the last wave (no barriers below)
+   float* const ring = fz_ring + threadIdx.x;            // the lane's column: slot q of line l is ring[(fz_rl_slot0[l] + q) * FZ_BLOCK]
+   const unsigned T = a.n_samples, B = a.block_rows;
+   float c[FZ_A(FZ_NCONST)], p[FZ_A(FZ_NPARAM)], st[FZ_A(FZ_NREG)];
+   unsigned pos[FZ_NRL];                                 // the row number modulo each ring line's depth (uniform over the wave)
+#pragma unroll
+   for (int k = 0; k < FZ_NCONST; ++k) c[k] = a.c[k];
+#pragma unroll
+   for (int k = 0; k < FZ_NPARAM; ++k) p[k] = a.params[(size_t)k * ns + s];
+   if (FZ_NCONST == 0) c[0] = 0.f;
+   if (FZ_NPARAM == 0) p[0] = 0.f;
+   st[0] = 0.f;
+#pragma unroll
+   for (int r = 0; r < FZ_NREG; ++r) st[r] = a.state[(size_t)fz_reg_row[r] * ns + s];
+#pragma unroll
+   for (int l = 0; l < FZ_NRL; ++l) {                    // the value rings: slot D - 1 - j holds u[-1-j], the caller's state row row0 + j
+      const unsigned D = fz_rl_depth[l];
+#pragma unroll 4
+      for (unsigned j = 0; j < D; ++j) ring[(size_t)(fz_rl_slot0[l] + D - 1u - j) * FZ_BLOCK] = a.state[(size_t)(fz_rl_row0[l] + j) * ns + s];
+      pos[l] = 0u;
+   }
+
+   float xa[FZ_U][FZ_A(FZ_NIN)], xb[FZ_U][FZ_A(FZ_NIN)];
+#pragma unroll
+   for (int j = 0; j < FZ_U; ++j) {
+      xa[j][0] = xb[j][0] = 0.f;
+      const size_t t = (unsigned)j < T ? (size_t)j : (size_t)T - 1;
+#pragma unroll
+      for (int w = 0; w < FZ_NIN; ++w) xa[j][w] = a.in[(t * ns + s) * FZ_NIN + w];
+   }
+   unsigned tn = 0;                                      // the first row of the next block
+   float* sk = a.starts + s;                             // its rows of `starts`
+   for (unsigned t0 = 0; t0 < T; t0 += FZ_U) {
+      // the next group's rows: requested here, used one trip on
+#pragma unroll
+      for (int j = 0; j < FZ_U; ++j) {
+         const unsigned tj = t0 + FZ_U + j;
+         const size_t t = tj < T ? (size_t)tj : (size_t)T - 1;
+#pragma unroll
+         for (int w = 0; w < FZ_NIN; ++w) xb[j][w] = a.in[(t * ns + s) * FZ_NIN + w];
+      }
+#pragma unroll
+      for (int j = 0; j < FZ_U; ++j) {
+         const unsigned t = t0 + j;
+         if (t < T) {
+            if (t == tn) {                               // (scalars both: no lane diverges)
+               fz_dump_state(sk, ns, st, ring, pos);
+               sk += (size_t)FZ_NSTATE * ns;
+               tn += B;
+            }
+            float rv[FZ_A(FZ_NRR)], sn[FZ_A(FZ_NREG)], u[FZ_NRL];
+            rv[0] = 0.f;
+            sn[0] = 0.f;
+#pragma unroll
+            for (int q = 0; q < FZ_NRR; ++q) {
+               const unsigned l = fz_rr_line[q], d = fz_rr_delay[q], D = fz_rl_depth[l];
+               const unsigned slot = pos[l] >= d ? pos[l] - d : pos[l] + D - d;
+               rv[q] = ring[(size_t)(fz_rl_slot0[l] + slot) * FZ_BLOCK];
+            }
+            fz_adj::fwd(xa[j], c, p, st, rv, sn, u);
+#pragma unroll
+            for (int l = 0; l < FZ_NRL; ++l) {
+               ring[(size_t)(fz_rl_slot0[l] + pos[l]) * FZ_BLOCK] = u[l];
+               pos[l] = pos[l] + 1u == fz_rl_depth[l] ? 0u : pos[l] + 1u;
+            }
+#pragma unroll
+            for (int r = 0; r < FZ_NREG; ++r) st[r] = sn[r];
+         }
+      }
+#pragma unroll
+      for (int j = 0; j < FZ_U; ++j) {
+#pragma unroll
+         for (int w = 0; w < FZ_NIN; ++w) xa[j][w] = xb[j][w];
+      }
+   }
+   if (a.state_out) fz_dump_state(a.state_out + s, ns, st, ring, pos);
+}

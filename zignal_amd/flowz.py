@@ -960,11 +960,62 @@ class Program:
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, window, (float(grad_scale), out),
                               (int(block_rows), workspace))
 
+    # -- the backward of a whole recording with delay lines deeper than 8 samples (fz_run_recording_ring_grad) -----------------------
+    def ring_recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
+        """the rows per block run_recording_ring_grad cuts a recording of T rows into (block_rows = 0: the library's choice, which
+        counts the tape of the deep lines; include/flowz_hip.h has the rule)"""
+        b = ctypes.c_uint32()
+        C.check(C.lib.fz_program_ring_recording_block_rows(self._h, int(T), int(block_rows), int(checkpoint_rows), ctypes.byref(b)))
+        return int(b.value)
+
+    def ring_recording_workspace_bytes(self, n_streams: int, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
+        """workspace bytes of run_recording_ring_grad / run_recording_ring_loss_grad: the block-start states, then one block's ring workspace"""
+        b = ctypes.c_uint64()
+        C.check(C.lib.fz_program_ring_recording_workspace(self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows), ctypes.byref(b)))
+        return int(b.value)
+
+    def ring_states_resources(self) -> dict:
+        """grad_resources() of the block-start-states kernel of a ring recording; 'unroll' = the rows of its unrolled group, 'lds_bytes' =
+        the value rings of one workgroup (the ring adjoint kernel's bytes)"""
+        r = C.KernelResources()
+        C.check(C.lib.fz_program_ring_states_resources(self._h, ctypes.byref(r)))
+        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+    def ring_states_kernel_symbol(self) -> str:
+        buf = ctypes.create_string_buffer(160)
+        C.check(C.lib.fz_program_ring_states_kernel_symbol(self._h, buf, 160))
+        return buf.value.decode()
+
+    def ring_states_source(self) -> str:
+        n = C.check(C.lib.fz_program_ring_states_source(self._h, None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        C.check(C.lib.fz_program_ring_states_source(self._h, buf, n + 1))
+        return buf.value.decode()
+
+    def run_recording_ring_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0,
+                                block_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None, in_grad=None, workspace=None):
+        """run_block_ring_grad over a whole recording in bounded workspace (fz_run_recording_ring_grad), as run_recording_grad is to
+        run_block_grad: every bit is run_block_ring_grad's over the same rows, "state_out" may be named in want.  Time-major frames
+        only: row0 must be 0, n_samples None or T, in_grad None.  For a graph run_recording_grad takes it is run_recording_grad."""
+        _require(int(row0) == 0 and (n_samples is None or int(n_samples) == x.shape[0]) and in_grad is None,
+                 "run_recording_ring_grad takes time-major frames: no window (row0, n_samples, in_grad)")
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None, None, (int(block_rows), workspace), ring=True)
+
+    def run_recording_ring_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT,
+                                     accum=None, checkpoint_rows: int = 0, block_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None,
+                                     in_grad=None, out=None, workspace=None):
+        """run_block_ring_loss_grad over a whole recording (fz_run_recording_ring_loss_grad): the arguments, results and bits of the
+        one-launch call over the same rows, plus "state_out" in want.  Time-major frames only, as run_recording_ring_grad."""
+        _require(int(row0) == 0 and (n_samples is None or int(n_samples) == x.shape[0]) and in_grad is None,
+                 "run_recording_ring_loss_grad takes time-major frames: no window (row0, n_samples, in_grad)")
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), out),
+                              (int(block_rows), workspace), ring=True)
+
     def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None, ring=False):
         """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers; loss: None, or
         (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
-        (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is run_block_ring_grad, or with
-        loss run_block_ring_loss_grad (one time-major block)"""
+        (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is of the ring family (time-major):
+        run_block_ring_grad / run_block_ring_loss_grad, or with recording run_recording_ring_grad / run_recording_ring_loss_grad"""
         import torch
 
         if ring:
@@ -1032,7 +1083,8 @@ class Program:
         if recording is None:
             wsb = (self.ring_grad_workspace_bytes if ring else self.grad_workspace_bytes)(ns, T, checkpoint_rows)
         else:
-            wsb = self.recording_workspace_bytes(ns, T, recording[0], checkpoint_rows, window is not None)
+            wsb = self.ring_recording_workspace_bytes(ns, T, recording[0], checkpoint_rows) if ring else \
+                self.recording_workspace_bytes(ns, T, recording[0], checkpoint_rows, window is not None)
             if "state_out" in want:
                 out["state_out"] = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=dev)
             if state0_grad is None and self.n_state:        # (the blocks chain through it, asked for or not)
@@ -1065,7 +1117,10 @@ class Program:
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
         hs = torch.cuda.current_stream().cuda_stream
-        if recording is not None:
+        if recording is not None and ring:
+            fn = C.lib.fz_run_recording_ring_grad if loss is None else C.lib.fz_run_recording_ring_loss_grad
+            C.check(fn(self._h, ctypes.byref(a), int(ns), int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
+        elif recording is not None:
             fn = C.lib.fz_run_recording_grad if loss is None else C.lib.fz_run_recording_loss_grad
             w = (int(rows), row0) if window is not None else (0, 0)
             C.check(fn(self._h, ctypes.byref(a), int(window is not None), int(ns), w[0], w[1], int(T), recording[0],
