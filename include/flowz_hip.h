@@ -605,7 +605,8 @@ long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_
  * kernel, symbol, workspace and bits.  Still refused, with the reasons of fz_program_grad_check: lines deeper than 256 samples (rings
  * in HBM), typed programs, float64 nodes, complex wires, modulators.  Refused here alone: graphs whose deep lines hold more samples
  * than the LDS of a workgroup has room for at 64 lanes (4 bytes per sample and lane, 163 840 bytes: 640 samples) -- the reason names
- * the bytes.  Not built for such graphs: stream-major buffers, whole recordings (those calls keep refusing them).  The fused loss is
+ * the bytes.  fz_run_block_grad, its stream-major twin and the plain recording calls keep refusing such graphs: stream-major buffers
+ * are fz_run_block_ring_grad_stream_major, whole recordings fz_run_recording_ring_grad (time-major).  The fused loss is
  * fz_run_block_ring_loss_grad, below fz_run_block_loss_grad.
  *
  * The kernel, fz_adjoint_ring_kernel_c<C>b<lanes per workgroup>_g<graph tag>: lines of depth <= 8 are kept as fz_run_block_grad keeps
@@ -697,6 +698,39 @@ int fz_program_ring_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows,
 long fz_program_ring_loss_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
 long fz_program_ring_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
 int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
+
+/* fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major -- the two one-launch calls of the
+ * fz_run_block_ring_grad family on STREAM-MAJOR buffers.  The args structs are taken unchanged.
+ *
+ * THE CONTRACT, by reference: the bits of fz_run_block_ring_grad (of fz_run_block_ring_loss_grad) on the transposed buffers -- the
+ * layout does not change a bit -- and windows and alignment exactly as fz_run_block_grad_stream_major
+ * (fz_run_block_loss_grad_stream_major): buffers [n_streams][rows_total][wire], the block is rows [row0, row0 + n_samples),
+ * rows_total * n_in, rows_total * n_out, row0 * n_in and row0 * n_out multiples of 4 floats, rows of in_grad and of out outside the
+ * window never written.  State, coefficient, accumulator rows and the workspace keep their [row][n_streams] layout.
+ *
+ * Scope: fz_program_ring_grad_check's.  Checkpoint stride and workspace: those of fz_run_block_ring_grad (fz_program_ring_grad_workspace
+ * answers the bytes, unchanged).  Checks: those of fz_run_block_grad_stream_major / fz_run_block_loss_grad_stream_major, in their order,
+ * before a device is needed; a short workspace names fz_program_ring_grad_workspace.  For a graph without a deep line these calls ARE
+ * fz_run_block_grad_stream_major / fz_run_block_loss_grad_stream_major: the same kernel, symbol, workspace and bits.
+ *
+ * The kernels for a graph with a deep line, fz_adjoint_ring_sm_kernel_c<C>r<R>b<lanes>_g<tag> and
+ * fz_adjoint_ring_loss_sm_kernel_c<C>r<R>b<lanes>_g<tag>, keep the rings AND the frame patches of R rows in LDS:
+ * 4 * lanes * (ring samples + R * (n_in + n_out) + 4) bytes per workgroup.  Lanes and R are chosen together: R from the patch length
+ * of fz_run_block_grad_stream_major halved down to max(4, C), lanes from 256 / 128 / 64; the first pair, in that order, that leaves
+ * room for two workgroups in a compute unit's LDS, failing that the first that fits one.  Refused here alone (FZ_E_UNSUPPORTED): a
+ * graph whose rings plus the shortest patch do not fit a workgroup at 64 lanes -- the reason names the bytes; a smaller
+ * checkpoint_rows shortens the patch.  Not built: stream-major recordings of such graphs.
+ * The inspection calls take (checkpoint_rows, layout) like their _grad_ twins. */
+int fz_run_block_ring_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                        uint32_t n_samples, void* hip_stream);
+int fz_run_block_ring_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                             uint32_t n_samples, void* hip_stream);
+int fz_program_ring_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out);
+long fz_program_ring_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+long fz_program_ring_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+int fz_program_ring_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out);
+long fz_program_ring_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+long fz_program_ring_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 
 /* fz_run_recording_grad, fz_run_recording_loss_grad -- the backward of a whole RECORDING of T rows in bounded workspace.
  *

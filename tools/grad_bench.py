@@ -50,7 +50,16 @@ state before every block), then run_block_ring_loss_grad per block from the last
 1 048 576 x 4096, time-major; the three legs must agree on the loss bit for bit.  The mark is rec no slower than the route, the margin the
 route's own spread in that run; a line that misses it says so.  The table goes to stdout and to profiles/r14/ring_recording.txt.
 
+--rings --layout compare [--loss]: the ring backward on stream-major buffers, run_block_ring_grad_stream_major
+(fz_run_block_ring_grad_stream_major; with --loss run_block_ring_loss_grad_stream_major), against the route a caller with stream-major
+buffers had before it: fz_transpose_frames of x and of dL/dy (or the target) to time-major, the time-major ring call, fz_transpose_frames
+of dL/dx back (every frame buffer allocated beforehand).  Those graphs and shapes; same buffers, same process, legs interleaved (100 ms of
+the route first, then --steps launches per leg in a forward and again in a backward pass: medians of 2 x --steps HIP-event timings).  The
+two legs must agree bit for bit -- dL/dx, the state gradient, the loss -- before a time is printed.  There is no pass mark: a line slower
+than the route says so.  The table goes to stdout and to profiles/r15/ring_stream_major.txt (the --loss table is appended to it).
+
 usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings]
+       (--rings takes --layout compare, alone or with --loss)
 """
 import argparse
 import datetime
@@ -402,6 +411,87 @@ def rings_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
+def rings_compare_bench(a, torch):
+    """the ring backward on stream-major buffers (plain, or with a.loss under the squared-error loss) against transpose + the time-major
+    ring call + transpose, interleaved in one process; the two legs agree bit for bit before a time is printed"""
+    import time
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+    props = torch.cuda.get_device_properties(0)
+    loss = bool(a.loss)
+    call = "run_block_ring_loss_grad" if loss else "run_block_ring_grad"
+    say(f"# command: tools/grad_bench.py --rings --layout compare{' --loss' if loss else ''} --steps {a.steps} --legs {a.legs}")
+    say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+    say(f"# sm = one {call}_stream_major launch on [n_streams, T] buffers; route = fz_transpose_frames of x and of {'the target' if loss else 'dL/dy'}, {call}, fz_transpose_frames of dL/dx back;")
+    say(f"# every gradient, default checkpoint stride; HIP events, {a.steps} launches per leg and pass, a forward and a")
+    say("# backward pass over the legs; spread = max - min of the route's own repeats; the legs agree bit for bit (dL/dx, the state gradient" + (", the loss" if loss else "") + ") before a time is printed")
+    say(f"{'graph':16s} {'streams x T':>16s} {'route ms':>9s} {'spread':>7s} {'sm ms':>9s} {'sm/route':>9s} {'slower':>6s} {'C':>3s} {'R':>3s} {'lanes':>5s} {'vgprs':>6s} {'sgpr spills':>11s} {'lds':>6s}  stream-major ring kernel")
+    shapes = SHAPES["large"] + SHAPES["small"] if a.legs == "all" else SHAPES[a.legs]
+    for ns, T in shapes:
+        x_sm = torch.empty((ns, T, 1), dtype=torch.float32, device="cuda")
+        F.synth_fill(x_sm, seed=W.SEED)
+        yt_sm = torch.empty_like(x_sm)                         # dL/dy, or the target
+        F.synth_fill(yt_sm, seed=W.SEED + 1)
+        gx_sm, gx_back = torch.empty_like(x_sm), torch.empty_like(x_sm)
+        x_tm, yt_tm = (torch.empty((T, ns, 1), dtype=torch.float32, device="cuda") for _ in range(2))
+        n = float(ns) * T
+        want = ("x", "state", "params", "consts") + (("loss",) if loss else ())
+        for name, fn in RING_GRAPHS.items():
+            prog = F.compile(F.from_sexpr(fn()))
+            s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+
+            def route():
+                F.frames_from_stream_major(x_sm, 0, out=x_tm)
+                F.frames_from_stream_major(yt_sm, 0, out=yt_tm)
+                if loss:
+                    r = prog.run_block_ring_loss_grad(x_tm, yt_tm, s0, None, state_grad=s0, grad_scale=2.0 / n, want=want)
+                else:
+                    r = prog.run_block_ring_grad(x_tm, yt_tm, s0, None, state_grad=s0)
+                F.frames_to_stream_major(r["x"], out=gx_back)
+                return r
+
+            def sm():
+                if loss:
+                    return prog.run_block_ring_loss_grad_stream_major(x_sm, yt_sm, s0, None, state_grad=s0, grad_scale=2.0 / n, want=want, in_grad=gx_sm)
+                return prog.run_block_ring_grad_stream_major(x_sm, yt_sm, s0, None, state_grad=s0, in_grad=gx_sm)
+            legs = {"route": route, "sm": sm}
+            first = {k: f() for k, f in legs.items()}           # JIT, allocator; and the legs agree bit for bit
+            torch.cuda.synchronize()
+            same = lambda u, v: torch.equal(u.view(torch.int32), v.view(torch.int32))   # noqa: E731
+            assert same(gx_sm, gx_back), f"{name} {ns} x {T}: dL/dx of the two legs differs"
+            for key in ("state",) + (("loss",) if loss else ()):
+                assert same(first["sm"][key], first["route"][key]), f"{name} {ns} x {T}: {key} of the two legs differs"
+            del first
+            t_end = time.time() + 0.1
+            while time.time() < t_end:                          # at least 100 ms of the yardstick before the first timing
+                route()
+                torch.cuda.synchronize()
+            got = {k: [] for k in legs}
+            for order in (list(legs), list(legs)[::-1]):
+                for k in order:
+                    got[k] += samples(legs[k], a.steps, torch)
+            med = {k: float(np.median(v)) for k, v in got.items()}
+            spread = max(got["route"]) - min(got["route"])
+            res = (prog.ring_loss_grad_resources if loss else prog.ring_grad_resources)(0, stream_major=True)
+            sym = (prog.ring_loss_grad_kernel_symbol if loss else prog.ring_grad_kernel_symbol)(0, stream_major=True)
+            R, lanes = int(sym.split("_g")[0].split("r")[-1].split("b")[0]), int(sym.split("_g")[0].split("b")[-1])
+            say(f"{name:16s} {f'{ns} x {T}':>16s} {med['route']:9.3f} {spread:7.3f} {med['sm']:9.3f} {med['sm'] / med['route']:9.3f} "
+                f"{'YES' if med['sm'] > med['route'] + spread else 'no':>6s} {res['unroll']:3d} {R:3d} {lanes:5d} {res['vgprs'] + res['agprs']:6d} "
+                f"{res['sgpr_spills']:11d} {res['lds_bytes']:6d}  {sym}")
+            say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
+            del s0
+            torch.cuda.empty_cache()
+        del x_sm, yt_sm, gx_sm, gx_back, x_tm, yt_tm
+        torch.cuda.empty_cache()
+    out = os.path.join(ROOT, "profiles", "r15", "ring_stream_major.txt")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a" if loss and os.path.exists(out) else "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def rings_loss_bench(a, torch):
     """one step under a mean squared error for graphs with delay lines in LDS: the fused launch against forward + torch MSE and
     derivative + ring backward, interleaved in one process"""
@@ -578,6 +668,8 @@ def main():
     torch.cuda.set_device(0)
     if a.rings and a.recording:
         return rings_recording_bench(a, torch)
+    if a.rings and a.layout == "compare":
+        return rings_compare_bench(a, torch)
     if a.rings and a.loss:
         return rings_loss_bench(a, torch)
     if a.loss:

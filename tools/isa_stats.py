@@ -5,10 +5,13 @@ usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par
        tools/isa_stats.py lossgrad [graph] [tm|sm]         the kernel of fz_run_block_loss_grad (sm: _stream_major) next to the plain
                                                            adjoint kernel: registers, spills, LDS (graph: also cascade_params6)
        tools/isa_stats.py states [graph] [tm|sm]           the block-start-states kernel of fz_run_recording_grad: registers, spills, LDS
-       tools/isa_stats.py ringgrad [graph]                 the kernel of fz_run_block_ring_grad: registers, spills, scratch, LDS bytes, and
+       tools/isa_stats.py ringgrad [graph] [--layout stream-major]
+                                                           the kernel of fz_run_block_ring_grad: registers, spills, scratch, LDS bytes, and
                                                            its LDS (ds_*) and vector-memory instructions per row (graph: ldsring, comb256,
-                                                           or a name of tests/ring_grad_graphs.py)
-       tools/isa_stats.py ringlossgrad [graph]             the same line for the kernel of fz_run_block_ring_loss_grad, next to the plain
+                                                           or a name of tests/ring_grad_graphs.py); --layout stream-major: the kernel of
+                                                           fz_run_block_ring_grad_stream_major, with its patch rows R and lanes
+       tools/isa_stats.py ringlossgrad [graph] [--layout stream-major]
+                                                           the same line for the kernel of fz_run_block_ring_loss_grad, next to the plain
                                                            ring kernel's figures (graph: also a name of tests/ring_loss_graphs.py)
        tools/isa_stats.py ringstates [graph]               the block-start-states kernel of fz_run_recording_ring_grad next to the ring
                                                            adjoint kernel: registers, spills, scratch, LDS bytes, and the ds_* and
@@ -80,14 +83,16 @@ def states_line(name, sm):
             f"{r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills, {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS")
 
 
-def ring_grad_lines(name, loss=False):
+def ring_grad_lines(name, loss=False, sm=False):
     """the ring adjoint kernel at the default stride C, and its ds_* / vector-memory instructions per row of a chunk: the difference of
     the kernels at C and C / 2 over C / 2 rows -- both sweeps unroll a chunk, everything outside the chunks cancels.
-    loss: the kernel of fz_run_block_ring_loss_grad, with the plain ring kernel's registers and spills next to its own"""
+    loss: the kernel of fz_run_block_ring_loss_grad, with the plain ring kernel's registers and spills next to its own.
+    sm: the kernels for stream-major buffers (their per-row ds_* include the row's frames read from and written to the LDS patch; the
+    patch fetch and flush are outside the chunks and cancel)"""
     import ring_loss_graphs as RL
     build = RL.GRAPHS.get(name) or GRAPHS[name]
     p = F.compile(F.from_sexpr(build()))
-    resources = (lambda q, c=0: q.ring_loss_grad_resources(c)) if loss else (lambda q, c=0: q.ring_grad_resources(c))
+    resources = (lambda q, c=0: q.ring_loss_grad_resources(c, stream_major=sm)) if loss else (lambda q, c=0: q.ring_grad_resources(c, stream_major=sm))
     r = resources(p)
     C = r["unroll"]
 
@@ -110,8 +115,9 @@ def ring_grad_lines(name, loss=False):
             os.environ.pop("FLOWZ_HIP_CACHE", None)
         else:
             os.environ["FLOWZ_HIP_CACHE"] = old
-    plain = p.ring_grad_resources() if loss else None
-    out = [f"{name} {p.ring_loss_grad_kernel_symbol() if loss else p.ring_grad_kernel_symbol()}: C {C}, {r['vgprs'] + r['agprs']} VGPRs"
+    plain = p.ring_grad_resources(0, stream_major=sm) if loss else None
+    sym = p.ring_loss_grad_kernel_symbol(0, stream_major=sm) if loss else p.ring_grad_kernel_symbol(0, stream_major=sm)
+    out = [f"{name} {sym}: C {C}, {r['vgprs'] + r['agprs']} VGPRs"
            + (f" (plain ring {plain['vgprs'] + plain['agprs']})" if loss else "") + f", {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills"
            + (f" (plain ring {plain['vgpr_spills']} / {plain['sgpr_spills']})" if loss else "") + f", {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS",
            "  in the kernel: " + ", ".join(f"{v} {k}" for k, v in whole.items())]
@@ -151,14 +157,21 @@ def ring_states_lines(name):
 
 def main():
     a = sys.argv[1:]
+    sm = False
+    if "--layout" in a:
+        i = a.index("--layout")
+        if a[i + 1:i + 2] not in (["stream-major"], ["time-major"]):
+            sys.exit("--layout time-major | stream-major")
+        sm = a[i + 1] == "stream-major"
+        del a[i:i + 2]
     if a and a[0] == "ringstates":
         print("\n".join(ring_states_lines(a[1] if len(a) > 1 else "ldsring")))
         return
     if a and a[0] == "ringgrad":
-        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring")))
+        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring", sm=sm)))
         return
     if a and a[0] == "ringlossgrad":
-        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring", loss=True)))
+        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring", loss=True, sm=sm)))
         return
     if a and a[0] == "states":
         print(states_line(a[1] if len(a) > 1 else "cascade_params6", len(a) > 2 and a[2] == "sm"))

@@ -9,6 +9,8 @@ lies: the forward is Program.run_block_stream_major, the backward Program.run_bl
 
 run_rings(prog, x, state, params, consts) is run() for graphs with delay lines deeper than 8 samples (combs, echoes, plucked strings):
 time-major frames, the backward is Program.run_block_ring_grad (include/flowz_hip.h: fz_run_block_ring_grad).  run() keeps refusing them.
+run_rings(..., stream_major=True) takes the stream-major tensors of run(..., stream_major=True): the forward is
+Program.run_block_stream_major, the backward Program.run_block_ring_grad_stream_major, and nothing is transposed.
 
 mse(prog, x, target, ...) is the mean squared error of one block against a target as ONE launch (Program.run_block_loss_grad:
 the adjoint kernel forms y, the error and dL/dy itself), where run() followed by ((y - target) ** 2).mean() is a forward launch,
@@ -16,6 +18,7 @@ several elementwise kernels and the backward launch.
 
 mse_rings(prog, x, target, ...) is mse() for every graph run_rings() takes, time-major (Program.run_block_ring_loss_grad: the ring
 adjoint kernel with the loss formed in it); mse() keeps refusing graphs with delay lines deeper than 8 samples.
+mse_rings(..., stream_major=True) is the same on stream-major tensors (Program.run_block_ring_loss_grad_stream_major).
 
 mse_recording(prog, x, target, ...) is the same loss over a whole recording of many blocks in bounded workspace
 (Program.run_recording_loss_grad: one forward launch that keeps the state before every block, then the loss kernel block by block
@@ -70,7 +73,10 @@ class _Block(torch.autograd.Function):
             gy = torch.zeros(tuple(xx.shape[:2]) + (prog.n_out,), dtype=torch.float32, device=x.device)
         sg = gs.contiguous() if gs is not None and prog.n_state else None
         _apply_consts(prog, ctx.consts)                               # (the constants of the forward launch)
-        bwd = prog.run_block_ring_grad if ctx.rings else prog.run_block_grad_stream_major if ctx.stream_major else prog.run_block_grad
+        if ctx.rings:
+            bwd = prog.run_block_ring_grad_stream_major if ctx.stream_major else prog.run_block_ring_grad
+        else:
+            bwd = prog.run_block_grad_stream_major if ctx.stream_major else prog.run_block_grad
         r = bwd(xx, gy.contiguous(), state.detach() if state is not None else None,
                 params.detach() if params is not None else None, state_grad=sg, want=want)
         gx = r["x"].reshape(ctx.x_shape) if need_x else None
@@ -103,21 +109,23 @@ def run(prog: Program, x, state=None, params=None, consts=None, stream_major=Fal
     return _Block.apply(prog, x, state, params, consts, bool(stream_major))
 
 
-def run_rings(prog: Program, x, state=None, params=None, consts=None):
+def run_rings(prog: Program, x, state=None, params=None, consts=None, stream_major=False):
     """run() for graphs with delay lines deeper than 8 samples -- and every graph run() takes --, time-major frames: returns (y [T,
     n_streams, n_out], state after the block).  The forward is Program.run_block, the backward Program.run_block_ring_grad; x, state,
     params and consts as for run(), the uniform-coefficient gradients summed over the streams in float64 as there.  Chaining it over
-    consecutive blocks back-propagates through time across them, whatever the blocks' lengths against the lines' depths."""
+    consecutive blocks back-propagates through time across them, whatever the blocks' lengths against the lines' depths.
+    stream_major: the tensor shapes of run(..., stream_major=True) -- x [n_streams, T, n_in], or [n_streams, T] for one input wire --;
+    the forward is Program.run_block_stream_major, the backward Program.run_block_ring_grad_stream_major."""
     if not prog.ring_grad_supported():
         raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
     if x.dim() == 2 and prog.n_in != 1:
         raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
     if state is None:
-        state = torch.zeros((max(prog.n_state, 1), x.shape[1]), dtype=torch.float32, device=x.device)
+        state = torch.zeros((max(prog.n_state, 1), x.shape[0 if stream_major else 1]), dtype=torch.float32, device=x.device)
     if consts is not None:
         if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
             raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    return _Block.apply(prog, x, state, params, consts, False, True)
+    return _Block.apply(prog, x, state, params, consts, bool(stream_major), True)
 
 
 class _Mse(torch.autograd.Function):
@@ -128,7 +136,10 @@ class _Mse(torch.autograd.Function):
         want = ["loss"] + [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
         xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
         n = xx.shape[0] * xx.shape[1] * prog.n_out                    # elements of y: the mean is over all of them
-        bwd = prog.run_block_ring_loss_grad if rings else prog.run_block_loss_grad_stream_major if stream_major else prog.run_block_loss_grad
+        if rings:
+            bwd = prog.run_block_ring_loss_grad_stream_major if stream_major else prog.run_block_ring_loss_grad
+        else:
+            bwd = prog.run_block_loss_grad_stream_major if stream_major else prog.run_block_loss_grad
         # the one launch: the loss and every gradient asked for, dL/dy = (y - target) * 2 / n formed in the kernel
         r = bwd(xx, target.detach().contiguous(), state.detach() if state is not None else None,
                 params.detach() if params is not None else None, grad_scale=2.0 / n, want=want)
@@ -161,10 +172,12 @@ def mse(prog: Program, x, target, state=None, params=None, consts=None, stream_m
     return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), False)
 
 
-def mse_rings(prog: Program, x, target, state=None, params=None, consts=None):
+def mse_rings(prog: Program, x, target, state=None, params=None, consts=None, stream_major=False):
     """mse() for graphs with delay lines deeper than 8 samples -- and every graph mse() takes --, time-major frames: the scalar
     ((y - target) ** 2).mean() of one block, differentiable in x, state, params and consts.  One launch, made in the forward
-    (Program.run_block_ring_loss_grad, include/flowz_hip.h: fz_run_block_ring_loss_grad); backward() applies the upstream scalar."""
+    (Program.run_block_ring_loss_grad, include/flowz_hip.h: fz_run_block_ring_loss_grad); backward() applies the upstream scalar.
+    stream_major: the tensor shapes of mse(..., stream_major=True), a [batch, time] tensor as it lies for one wire
+    (Program.run_block_ring_loss_grad_stream_major)."""
     if not prog.ring_grad_supported():
         raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
     if x.dim() == 2 and prog.n_in != 1:
@@ -172,7 +185,7 @@ def mse_rings(prog: Program, x, target, state=None, params=None, consts=None):
     if consts is not None:
         if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
             raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    return _Mse.apply(prog, x, target, state, params, consts, False, True)
+    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), True)
 
 
 class _MseRecording(torch.autograd.Function):

@@ -29,6 +29,8 @@ extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a ker
 extern const char* const kSkeletonAdjointSm; // fz_kernel_adjoint_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonAdjointRing;   // fz_kernel_adjoint_ring.hip.inc: the adjoint kernel of graphs with delay lines in LDS
 extern const char* const kSkeletonAdjointRingLoss;   // fz_kernel_adjoint_ring_loss.hip.inc: the same with dL/dy formed from a target
+extern const char* const kSkeletonAdjointRingSm;     // fz_kernel_adjoint_ring_sm.hip.inc: the ring adjoint kernel for stream-major buffers
+extern const char* const kSkeletonAdjointRingLossSm; // fz_kernel_adjoint_ring_loss_sm.hip.inc: the same with dL/dy formed from a target
 extern const char* const kSkeletonAdjointLoss;   // fz_kernel_adjoint_loss.hip.inc: the adjoint kernel that forms dL/dy from a target
 extern const char* const kSkeletonAdjointLossSm; // fz_kernel_adjoint_loss_sm.hip.inc: the same for stream-major buffers
 extern const char* const kSkeletonStates;     // fz_kernel_states.hip.inc: the block-start states of a recording (the adjoint body's fwd alone)
@@ -47,8 +49,11 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string adj_loss = kSkeletonAdjointLoss, adj_loss_sm = kSkeletonAdjointLossSm;
    static const std::string states = kSkeletonStates, states_sm = kSkeletonStatesSm;
    static const std::string adj_ring = kSkeletonAdjointRing, adj_ring_loss = kSkeletonAdjointRingLoss, states_ring = kSkeletonStatesRing;
+   static const std::string adj_ring_sm = kSkeletonAdjointRingSm, adj_ring_loss_sm = kSkeletonAdjointRingLossSm;
    // (states + ring: the block-start-states kernel of a ring recording, before either bit alone)
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_RING)) return states_ring;
+   // (ring + stream-major, with or without the loss: texts of their own, before the two-bit cases)
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_SM)) return (v.flags & FZ_VF_ADJOINT_LOSS) ? adj_ring_loss_sm : adj_ring_sm;
    // (ring + loss before ring and before loss: the three-bit combination is a text of its own)
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_LOSS)) return adj_ring_loss;
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING)) return adj_ring;
@@ -69,6 +74,9 @@ std::string kernel_name(const Graph& g, const Variant& v)
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES))   // (the states bit means something next to FZ_VF_ADJOINT only)
       return (v.flags & FZ_VF_ADJOINT_SM) ? "fz_states_sm_kernel_u" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block)
                                           : "fz_states_kernel_u" + std::to_string(v.U) + "b" + std::to_string(v.block);
+   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_SM))   // (ring + stream-major, with or without the loss: before the two-bit cases)
+      return std::string((v.flags & FZ_VF_ADJOINT_LOSS) ? "fz_adjoint_ring_loss_sm_kernel_c" : "fz_adjoint_ring_sm_kernel_c") + std::to_string(v.U) + "r" + std::to_string(v.P) +
+             "b" + std::to_string(v.block);
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_LOSS))   // (ring + loss: before either alone)
       return "fz_adjoint_ring_loss_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
    if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING))   // (the ring bit means something next to FZ_VF_ADJOINT only)

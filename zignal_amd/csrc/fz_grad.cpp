@@ -12,6 +12,10 @@
 // the launch with the calls above; for a graph without such a line it IS fz_run_block_grad.  Under the squared-error loss
 // (fz_run_block_ring_loss_grad) it is that family's call with FZ_VF_ADJOINT_LOSS next to the ring bit: fz_kernel_adjoint_ring_loss.hip.inc,
 // the ring kernel's C, block and workspace; for a graph without such a line it IS fz_run_block_loss_grad.
+// On stream-major buffers (fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major) the ring backward is
+// FZ_VF_ADJOINT_SM next to the ring bit: fz_kernel_adjoint_ring_sm.hip.inc / fz_kernel_adjoint_ring_loss_sm.hip.inc, the ring kernel's C
+// and workspace, a workgroup and a patch length chosen together (ring_sm_geometry); for a graph without such a line it IS
+// fz_run_block_grad_stream_major / fz_run_block_loss_grad_stream_major.
 // The backward of a whole recording of such a graph (fz_run_recording_ring_grad, fz_run_recording_ring_loss_grad) is run_recording with
 // the ring family's pieces: the ring states kernel (FZ_VF_STATES next to the ring bit; fz_kernel_states_ring.hip.inc), the ring
 // launches per block, a block length and a workspace that count the tape; for a graph without such a line it IS the time-major
@@ -228,6 +232,70 @@ bool ring_adjoint_variant_fits(const Graph& g, const Variant& v)
    return v.block != 0 && v.block == ring_block(ring_layout(g));
 }
 
+// ---- the ring backward on stream-major buffers: rings and patches share the LDS of a workgroup ----------------------------------------
+// A workgroup of `block` lanes holds ring[slots][block] and block / 64 patches of [64][R (n_in + n_out) + 4] floats
+// (fz_kernel_adjoint_ring_sm.hip.inc): 4 block (slots + R (n_in + n_out) + 4) bytes.
+static uint64_t ring_sm_lds_bytes(const Graph& g, const RingLayout& rl, uint32_t block, uint32_t R)
+{
+   return 4ull * block * ((uint64_t)rl.slots + (uint64_t)R * (g.n_in + g.n_out) + 4u);
+}
+
+struct RingSmGeometry {
+   uint32_t block = 0, R = 0;   // block == 0: nothing fits
+};
+
+// The one home of the rule that chooses the workgroup and the patch length together.  R runs over R0 = grad_sm_patch_rows(g, C),
+// R0 / 2, ... down to Rmin = max(4, C) (powers of two: multiples of 4 and of C); per R the block over 256, 128, 64.  The first pair
+// that fits the LDS twice (two workgroups per CU) wins; failing that the first that fits once.  The rule prefers a long run per
+// stream (a whole cache line) over lanes per workgroup: static, not measured against the alternative.
+static RingSmGeometry ring_sm_geometry(const Graph& g, const RingLayout& rl, uint32_t C)
+{
+   const uint32_t R0 = grad_sm_patch_rows(g, C), Rmin = std::max<uint32_t>(4u, C);
+   for (uint64_t times : {2u, 1u})
+      for (uint32_t R = R0; R >= Rmin; R /= 2)
+         for (uint32_t b : {256u, 128u, 64u})
+            if (times * ring_sm_lds_bytes(g, rl, b, R) <= kLdsBytes) return RingSmGeometry{b, R};
+   return RingSmGeometry{};
+}
+
+// the Variant of the ring backward on stream-major buffers: for a graph without a ring line the stream-major adjoint Variant itself
+// (same kernel, symbol, workspace, bits); with one, the ring kernel's C and {P = R, block} of ring_sm_geometry
+static Variant ring_sm_adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool loss = false)
+{
+   const std::string why = grad_unsupported_reason(g, true);
+   if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
+   if (!has_ring_line(g)) return adjoint_variant(g, checkpoint_rows, true, loss);
+   const RingLayout rl = ring_layout(g);
+   if (!ring_block(rl)) (void)ring_adjoint_variant(g, checkpoint_rows, loss);   // (the refusal of fz_program_ring_grad_check, in its words)
+   Variant v;
+   v.U = checkpoint_of(g, checkpoint_rows, true);
+   v.flags = FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
+   if (loss && g.n_out == 0) fail(FZ_E_INVALID, "the graph has no output wires: a loss has nothing to compare");
+   const RingSmGeometry geo = ring_sm_geometry(g, rl, v.U);
+   if (!geo.block) {
+      const uint32_t Rmin = std::max<uint32_t>(4u, v.U);
+      fail(FZ_E_UNSUPPORTED, "stream-major ring backward: the rings of the delay lines deeper than 8 samples (" + std::to_string(rl.slots) + " samples) plus a patch of " +
+                                std::to_string(Rmin) + " rows of " + std::to_string(g.n_in + g.n_out) + " wires, " + std::to_string(ring_sm_lds_bytes(g, rl, 64, Rmin)) +
+                                " bytes per 64 lanes, do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup: a smaller checkpoint_rows shortens the patch");
+   }
+   v.P = geo.R;                                             // (the patch rows travel in P: codegen puts them into FZ_R and the symbol)
+   v.block = geo.block;
+   return v;
+}
+
+// could ring_sm_adjoint_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it
+// builds)  Exactly what the rule makes for this graph and C: block, R and the flag set.
+bool ring_sm_adjoint_variant_fits(const Graph& g, const Variant& v)
+{
+   if ((v.flags & ~FZ_VF_ADJOINT_LOSS) != (FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM) || !grad_unsupported_reason(g, true).empty() || !has_ring_line(g)) return false;
+   if ((v.flags & FZ_VF_ADJOINT_LOSS) && g.n_out == 0) return false;                       // (a loss kernel compares outputs)
+   if (v.U == 0 || v.U > kGradMaxCheckpoint || (v.U & (v.U - 1))) return false;
+   const RingLayout rl = ring_layout(g);
+   if (!ring_block(rl)) return false;
+   const RingSmGeometry geo = ring_sm_geometry(g, rl, v.U);
+   return geo.block != 0 && v.block == geo.block && v.P == geo.R;
+}
+
 static Variant states_variant(const Graph& g, bool stream_major)
 {
    require_supported(g);
@@ -437,7 +505,8 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
 {
    const GradCall* const a = &call;
    const Graph& g = p->g;
-   const Variant v = a->ring ? ring_adjoint_variant(g, a->checkpoint_rows, a->loss_rule) : adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
+   const Variant v = a->ring ? (sm ? ring_sm_adjoint_variant(g, a->checkpoint_rows, a->loss_rule) : ring_adjoint_variant(g, a->checkpoint_rows, a->loss_rule))
+                             : adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
    *vout = v;
    if (n_streams == 0 || n_samples == 0) return false;     // an empty block: nothing to differentiate, nothing touched
    if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
@@ -790,6 +859,67 @@ int fz_run_block_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_stre
       GradCall call = call_of(p, a);
       call.ring = true;
       return run_grad(p, call, n_streams, n_samples, hip_stream);)
+}
+
+static Variant ring_variant_for(const Graph& g, uint32_t checkpoint_rows, uint32_t layout, bool loss)
+{
+   return layout_is_stream_major(layout) ? ring_sm_adjoint_variant(g, checkpoint_rows, loss) : ring_adjoint_variant(g, checkpoint_rows, loss);
+}
+
+int fz_program_ring_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_grad_resources_for: bad arguments");
+      *out = resources_of(p, ring_variant_for(p->g, checkpoint_rows, layout, false));
+      return FZ_OK;)
+}
+
+long fz_program_ring_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_variant_for(p->g, checkpoint_rows, layout, false)); });
+}
+
+long fz_program_ring_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_variant_for(p->g, checkpoint_rows, layout, false)); });
+}
+
+int fz_program_ring_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
+{
+   FZ_GUARD(
+      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_loss_grad_resources_for: bad arguments");
+      *out = resources_of(p, ring_variant_for(p->g, checkpoint_rows, layout, true));
+      return FZ_OK;)
+}
+
+long fz_program_ring_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_variant_for(p->g, checkpoint_rows, layout, true)); });
+}
+
+long fz_program_ring_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_variant_for(p->g, checkpoint_rows, layout, true)); });
+}
+
+int fz_run_block_ring_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
+                                        void* hip_stream)
+{
+   FZ_GUARD(
+      GradCall call = call_of(p, a);
+      call.ring = true;
+      const SmWindow w{rows_total, row0};
+      return run_grad(p, call, n_streams, n_samples, hip_stream, &w);)
+}
+
+int fz_run_block_ring_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                             uint32_t n_samples, void* hip_stream)
+{
+   FZ_GUARD(
+      GradCall call = call_of(p, a);
+      call.ring = true;
+      const SmWindow w{rows_total, row0};
+      return run_grad(p, call, n_streams, n_samples, hip_stream, &w);)
 }
 
 int fz_program_ring_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)

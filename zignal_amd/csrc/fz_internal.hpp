@@ -194,13 +194,18 @@ constexpr uint32_t FZ_VF_ADJOINT_LOSS = 1u << 17;
 // the adjoint body alone; one more of the reserved bits.  Such a Variant is {P = 1 (stream-major: the rows of its LDS patch), U = the
 // rows of one unrolled group, block = lanes per workgroup}; fz_grad.cpp: states_variant is the one place that makes one.
 constexpr uint32_t FZ_VF_STATES = 1u << 16;
-// internal, with FZ_VF_ADJOINT alone: the adjoint kernel of a graph with delay lines in LDS (fz_grad.cpp: fz_run_block_ring_grad;
+// internal, with FZ_VF_ADJOINT: the adjoint kernel of a graph with delay lines in LDS (fz_grad.cpp: fz_run_block_ring_grad;
 // fz_kernel_adjoint_ring.hip.inc: a text and a symbol of its own, the pending adjoints of the deep lines in an LDS ring); the last of
 // the reserved bits 12 .. 14 that nothing used, so a forward variant naming it stays refused as reserved.  Such a Variant is {P = 1,
 // U = checkpoint rows, block = 256 / 128 / 64 lanes per workgroup}; fz_grad.cpp: ring_adjoint_variant is the one place that makes one.
-// With FZ_VF_ADJOINT_LOSS next to it (and never FZ_VF_ADJOINT_SM): the ring kernel that forms dL/dy itself (fz_run_block_ring_loss_grad;
+// With FZ_VF_ADJOINT_LOSS next to it: the ring kernel that forms dL/dy itself (fz_run_block_ring_loss_grad;
 // fz_kernel_adjoint_ring_loss.hip.inc: one more text and symbol of its own), the same P, U and block.
-// With FZ_VF_STATES next to it (and neither FZ_VF_ADJOINT_LOSS nor FZ_VF_ADJOINT_SM): the block-start-states kernel of a ring recording
+// With FZ_VF_ADJOINT_SM next to it (with or without FZ_VF_ADJOINT_LOSS): the ring kernels for STREAM-MAJOR buffers
+// (fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major; fz_kernel_adjoint_ring_sm.hip.inc,
+// fz_kernel_adjoint_ring_loss_sm.hip.inc: texts and symbols of their own), {P = rows of the LDS patch, U = the ring kernel's checkpoint
+// rows, block = 256 / 128 / 64}: rings and patches share the workgroup's LDS, so fz_grad.cpp: ring_sm_geometry chooses P and block
+// together and ring_sm_adjoint_variant is the one place that makes one.
+// With FZ_VF_STATES next to it (and neither FZ_VF_ADJOINT_LOSS nor FZ_VF_ADJOINT_SM: stream-major ring recordings are not built): the block-start-states kernel of a ring recording
 // (fz_run_recording_ring_grad; fz_kernel_states_ring.hip.inc: a text and a symbol of its own), {P = 1, U = the rows of one unrolled
 // group, block = the ring adjoint kernel's}; fz_grad.cpp: ring_states_variant is the one place that makes one.
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
@@ -291,6 +296,7 @@ uint32_t grad_default_checkpoint(const Graph& g);
 uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C);
 uint32_t grad_sm_max_patch_rows();                                 // the longest patch any graph can have (one wire, the whole LDS)
 bool adjoint_variant_fits(const Graph& g, const Variant& v);       // an adjoint Variant the backward could have made for this graph
+bool ring_sm_adjoint_variant_fits(const Graph& g, const Variant& v);   // a stream-major ring adjoint Variant (FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, with or without FZ_VF_ADJOINT_LOSS): exactly the block and patch rows fz_run_block_ring_grad_stream_major makes
 bool ring_adjoint_variant_fits(const Graph& g, const Variant& v);  // a ring adjoint Variant (FZ_VF_ADJOINT_RING, with or without FZ_VF_ADJOINT_LOSS) fz_run_block_ring_grad / _ring_loss_grad could have made
 // rows per LDS patch of the stream-major block-start-states kernel (x only), a multiple of 4 and of the unrolled group (fz_grad.cpp)
 uint32_t states_sm_patch_rows(const Graph& g);

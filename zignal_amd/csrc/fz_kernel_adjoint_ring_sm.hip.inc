@@ -1,0 +1,329 @@
+// fz_adjoint_ring_sm_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the ADJOINT of one block whose graph has delay lines
+// deeper than 8 samples, on STREAM-MAJOR buffers (include/flowz_hip.h: fz_run_block_ring_grad_stream_major).  The algorithm, the
+// generated body (fz_codegen.cpp: gen_adjoint_body in ring mode: struct fz_adj { fwd, bwd }) and the order of every operation are
+// those of fz_kernel_adjoint_ring.hip.inc -- one lane per stream, sweep 1 with its value rings in LDS, the checkpoints of the register
+// rows and the tape, sweep 2 with the adjoint rings in the same LDS -- so the bits are the time-major ring kernel's.  How the frames
+// move is fz_kernel_adjoint_sm.hip.inc's: the 64 lanes of a wave fetch a PATCH of [64 streams][FZ_R rows] as float4 pieces laid along
+// the rows, park them in a wave-private LDS patch and every lane reads its own row back; dL/dx overwrites x in place and leaves as
+// float4 pieces when the patch's chunks are done.
+//
+// Where the two do not simply paste together:
+//   * sweep 1 runs EVERY row of the block, the last chunk too (the stream-major kernel stops before it): the tape needs the last
+//     chunk's u[t] for reads at delays shorter than a chunk;
+//   * idle lanes of the last wave shadow the wave's last stream (its patch row, its state, its checkpoint and tape rows) but own the
+//     ring column of their threadIdx.x; they store nothing -- no tape, no checkpoints, no outputs -- and nothing depends on what they
+//     read back (rows another lane wrote, without a fence); every address they form is in bounds.  A wave past the last stream
+//     returns whole.  No workgroup barrier, no atomic: fz_wave_sync orders a wave's own patch traffic, a lane's ring column is its own;
+//   * LDS is ONE static array: ring[slot][lane], FZ_RING_SLOTS x FZ_BLOCK floats, then the patches [FZ_BLOCK / 64][64 * FZ_AROW]
+//     (FZ_BLOCK is whole waves: they start on a 256-byte boundary).  4 FZ_BLOCK (FZ_RING_SLOTS + FZ_R (n_in + n_out) + 4) bytes:
+//     fz_grad.cpp: ring_sm_geometry chooses FZ_BLOCK and FZ_R together;
+//   * rows [row][n_streams] touched once per launch go through a row stride held per lane (nsv / nse), as in the stream-major kernel;
+//   * sweep 2 requests a chunk's ring reads together before the re-run: tape row t - d, or the caller's state for t < d; x and dL/dy
+//     come from the patch.
+// Masking of a short last patch and a short last chunk: fz_kernel_adjoint_sm.hip.inc's -- no row of in_grad outside the window is written.
+//
+// Workspace: [ceil(T / FZ_C)][FZ_NREG][n_streams] checkpoints, then the tape [T][FZ_NRL][n_streams] (fz_program_ring_grad_workspace);
+// tape loads and stores are one coalesced row each.
+// HBM bytes per stream-sample: 4 (2 n_in + n_out + n_in) + 8 FZ_NREG / FZ_C + 4 FZ_NRL + 4 FZ_NRR, as the time-major ring kernel.
+//
+// Compiled by hiprtc with the build options of every other kernel: -ffp-contract=off, correctly rounded division and square root,
+// denormals kept.
+#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_NREG FZ_NRL FZ_NRR FZ_RING_SLOTS FZ_C FZ_R FZ_BLOCK
+                               // FZ_KERNEL and the tables fz_reg_row, fz_rl_row0 / fz_rl_depth / fz_rl_slot0, fz_rr_line / fz_rr_delay
+
+#define FZ_P 1
+typedef float V;
+typedef double VD;
+#define FZ_A(n) ((n) > 0 ? (n) : 1)
+
+#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd }
+
+#if (FZ_R % 4) != 0 || (FZ_R % FZ_C) != 0 || (FZ_BLOCK % 64) != 0
+#error "stream-major ring adjoint: the patch is a multiple of the checkpoint stride and of 4 rows, the workgroup whole waves"
+#endif
+#define FZ_AX (FZ_R * FZ_NIN)                 /* floats of x (then of dL/dx) per patch row */
+#define FZ_AY (FZ_R * FZ_NOUT)                /* floats of dL/dy per patch row, behind them */
+#define FZ_AROW (FZ_AX + FZ_AY + 4)           /* padded patch row */
+#define FZ_API (FZ_AX / 4)                    /* float4 pieces per stream and patch */
+#define FZ_APO (FZ_AY / 4)
+
+#define FZ_AFLIGHT 8                          /* float4 pieces a lane has in flight while a patch part is fetched */
+
+typedef float fz_f4 __attribute__((ext_vector_type(4)));
+
+struct fz_adj_ring_sm_args {   // the layout of fz_adj_sm_args (fz_kernel_adjoint_sm.hip.inc): one host-side image serves both
+   const float* in;            // [n_streams][rows_total][n_in]
+   const float* state;         // [n_state][n_streams]   the state before the block (register and ring lines' rows)
+   const float* params;        // [n_param][n_streams]
+   const float* out_grad;      // [n_streams][rows_total][n_out]
+   const float* state_grad;    // [n_state][n_streams]   dL/d(state after the block); null: zero
+   float* in_grad;             // [n_streams][rows_total][n_in]   rows of the window written; null: not computed
+   float* state0_grad;         // [n_state][n_streams]   written; null: not computed (may be state_grad)
+   float* param_grad;          // [n_param][n_streams]   added to; null: not computed
+   float* const_grad;          // [n_const][n_streams]   added to; null: not computed
+   float* ckpt;                // [n_chunks][FZ_NREG][n_streams] checkpoints, then [T][FZ_NRL][n_streams] the tape
+   unsigned long long n_streams;
+   unsigned int n_samples;
+   unsigned int n_chunks;      // ceil(n_samples / FZ_C)
+   unsigned int rows_total;
+   unsigned int row0;
+   float c[FZ_A(FZ_NCONST)];   // the program's uniform coefficients
+};
+
+__device__ __forceinline__ void fz_wave_sync()
+{
+   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+   __builtin_amdgcn_wave_barrier();
+   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Piece e = i * 64 + lane of a patch part is piece e % PIECES of patch row e / PIECES: 4 floats at float 4 * (e % PIECES) of that
+// stream's run.  `rows` streams of the wave exist, `nval` floats of every run lie inside the window.
+// global -> patch: `g` the first float of the wave's first run, `gstride` floats from one stream's run to the next.  No branches (a
+// branch per piece of the unrolled loop keeps an exec mask per piece alive in scalar registers): a piece of a missing stream is fetched
+// from the wave's last stream, a piece behind the window's last float from the head of its run, and parked where nobody reads it.
+template <int PIECES>
+__device__ __forceinline__ void fz_adj_fetch(float* part, const float* g, size_t gstride, unsigned rows, unsigned nval, unsigned lane)
+{
+   constexpr unsigned PP = PIECES > 0 ? PIECES : 1;
+#pragma unroll
+   for (int i = 0; i < PIECES; ++i) {
+      const unsigned e = (unsigned)i * 64u + lane, row = e / PP, q = e % PP;
+      const unsigned grow = row < rows ? row : rows - 1u, gq = q * 4u < nval ? q * 4u : 0u;
+      *reinterpret_cast<fz_f4*>(part + row * FZ_AROW + q * 4u) = *reinterpret_cast<const fz_f4*>(g + grow * gstride + gq);
+      // at most FZ_AFLIGHT pieces in flight: the pieces before are parked before the next are fetched
+      if ((i + 1) % FZ_AFLIGHT == 0 && i + 1 < PIECES) asm volatile("" ::: "memory");
+   }
+}
+
+// patch -> global: the whole pieces inside the window as float4; the floats of the piece that straddles the window's last float (at
+// most three) leave one by one, every lane handing over those of its own row
+template <int PIECES>
+__device__ __forceinline__ void fz_adj_flush(const float* part, float* g, size_t gstride, unsigned rows, unsigned nval, unsigned lane)
+{
+   constexpr unsigned PP = PIECES > 0 ? PIECES : 1;
+#pragma unroll
+   for (int i = 0; i < PIECES; ++i) {
+      const unsigned e = (unsigned)i * 64u + lane, row = e / PP, q = e % PP;
+      if (row < rows && q * 4u + 4u <= nval) *reinterpret_cast<fz_f4*>(g + row * gstride + q * 4u) = *reinterpret_cast<const fz_f4*>(part + row * FZ_AROW + q * 4u);
+   }
+   const unsigned whole = nval & ~3u;
+   if (PIECES > 0 && whole != nval && lane < rows) {
+      for (unsigned j = whole; j < nval; ++j) g[lane * gstride + j] = part[lane * FZ_AROW + j];
+   }
+}
+
+extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_args a)
+{
+   // ring[slot][lane], then the waves' patches (FZ_RING_SLOTS * FZ_BLOCK floats are whole multiples of 256 bytes)
+   __shared__ __attribute__((aligned(16))) float fz_ring[FZ_RING_SLOTS * FZ_BLOCK + (FZ_BLOCK / 64) * 64 * FZ_AROW];
+   const size_t ns = a.n_streams;
+   const unsigned lane = threadIdx.x & 63u;
+   const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (wave-uniform: addresses built from it stay scalar)
+   const size_t s_base = (size_t)blockIdx.x * FZ_BLOCK + wave * 64u;                          // first stream of this wave
+   if (s_base >= ns) return;                                  // a wave past the last stream (no workgroup barriers below)
+   const unsigned rows_here = (unsigned)(ns - s_base < 64u ? ns - s_base : 64u);
+   const bool active = lane < rows_here;
+   const unsigned prow = active ? lane : rows_here - 1u;      // idle lanes shadow the wave's last stream, store nothing
+   const size_t s = s_base + prow;
+   float* const ring = fz_ring + threadIdx.x;                 // the lane's OWN column (an idle lane's too): slot q of line l is ring[(fz_rl_slot0[l] + q) * FZ_BLOCK]
+   const unsigned T = a.n_samples, nck = a.n_chunks;
+   const unsigned npatch = (T + (unsigned)FZ_R - 1u) / (unsigned)FZ_R;
+   float* const patch = fz_ring + FZ_RING_SLOTS * FZ_BLOCK + wave * (64u * FZ_AROW);
+   float* const mine = patch + prow * FZ_AROW;
+   float* const tape = a.ckpt + (size_t)nck * FZ_NREG * ns + s;
+   // the wave's first run of each buffer: stream s_base, row row0
+   const size_t istride = (size_t)a.rows_total * FZ_NIN, ostride = (size_t)a.rows_total * FZ_NOUT;
+   const float* const gin = FZ_NIN ? a.in + s_base * istride + (size_t)a.row0 * FZ_NIN : nullptr;
+   const float* const gyb = FZ_NOUT ? a.out_grad + s_base * ostride + (size_t)a.row0 * FZ_NOUT : nullptr;
+   float* const gxb = FZ_NIN && a.in_grad ? a.in_grad + s_base * istride + (size_t)a.row0 * FZ_NIN : nullptr;
+
+   // (rows [row][n_streams] that are touched once per launch go through a row stride held per lane: as a scalar, every multiple of it
+   //  -- one per parameter and accumulator row -- would stay in scalar registers from here to the epilogue)
+   size_t nsv = ns;
+   asm volatile("" : "+v"(nsv));
+   float c[FZ_A(FZ_NCONST)], p[FZ_A(FZ_NPARAM)];
+#pragma unroll
+   for (int k = 0; k < FZ_NCONST; ++k) c[k] = a.c[k];
+#pragma unroll
+   for (int k = 0; k < FZ_NPARAM; ++k) p[k] = a.params[(size_t)k * nsv + s];
+   if (FZ_NCONST == 0) c[0] = 0.f;
+   if (FZ_NPARAM == 0) p[0] = 0.f;
+
+   // ---- sweep 1: forward over EVERY row of the block; the register rows before every chunk and every row's ring-line values into the workspace
+   {
+      float st[FZ_A(FZ_NREG)];
+      unsigned pos[FZ_NRL];                                // the row number modulo each ring line's depth (uniform over the wave)
+      st[0] = 0.f;
+#pragma unroll
+      for (int r = 0; r < FZ_NREG; ++r) st[r] = a.state[(size_t)fz_reg_row[r] * nsv + s];
+#pragma unroll
+      for (int l = 0; l < FZ_NRL; ++l) {                   // the value rings: slot D - 1 - j holds u[-1-j], the caller's state row row0 + j
+         const unsigned D = fz_rl_depth[l];
+#pragma unroll 4
+         for (unsigned j = 0; j < D; ++j) ring[(size_t)(fz_rl_slot0[l] + D - 1u - j) * FZ_BLOCK] = a.state[(size_t)(fz_rl_row0[l] + j) * nsv + s];
+         pos[l] = 0u;
+      }
+      for (unsigned pk = 0; pk < npatch; ++pk) {
+         const unsigned r0 = pk * (unsigned)FZ_R, np = T - r0 < (unsigned)FZ_R ? T - r0 : (unsigned)FZ_R;   // rows of this patch (1 .. FZ_R)
+         fz_wave_sync();                                     // (the rows of the patch before are read)
+         fz_adj_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+         fz_wave_sync();
+         const unsigned nk = (np + (unsigned)FZ_C - 1u) / (unsigned)FZ_C;
+         for (unsigned kk = 0; kk < nk; ++kk) {
+            const unsigned k = pk * (unsigned)(FZ_R / FZ_C) + kk;
+            const unsigned t0 = k * (unsigned)FZ_C;
+            const unsigned n = T - t0 < (unsigned)FZ_C ? T - t0 : (unsigned)FZ_C;   // rows of this chunk (1 .. FZ_C)
+            if (active) {
+               float* ck = a.ckpt + (size_t)k * FZ_NREG * ns + s;
+#pragma unroll
+               for (int r = 0; r < FZ_NREG; ++r) ck[(size_t)r * ns] = st[r];
+            }
+            const float* xr = mine + kk * (unsigned)(FZ_C * FZ_NIN);
+#pragma unroll
+            for (int j = 0; j < FZ_C; ++j)
+               if ((unsigned)j < n) {
+                  float x[FZ_A(FZ_NIN)], rv[FZ_A(FZ_NRR)], sn[FZ_A(FZ_NREG)], u[FZ_NRL];
+                  x[0] = 0.f;
+                  rv[0] = 0.f;
+                  sn[0] = 0.f;
+#pragma unroll
+                  for (int w = 0; w < FZ_NIN; ++w) x[w] = xr[j * FZ_NIN + w];
+#pragma unroll
+                  for (int q = 0; q < FZ_NRR; ++q) {
+                     const unsigned l = fz_rr_line[q], d = fz_rr_delay[q], D = fz_rl_depth[l];
+                     const unsigned slot = pos[l] >= d ? pos[l] - d : pos[l] + D - d;
+                     rv[q] = ring[(size_t)(fz_rl_slot0[l] + slot) * FZ_BLOCK];
+                  }
+                  fz_adj::fwd(x, c, p, st, rv, sn, u);
+#pragma unroll
+                  for (int l = 0; l < FZ_NRL; ++l) {
+                     ring[(size_t)(fz_rl_slot0[l] + pos[l]) * FZ_BLOCK] = u[l];
+                     if (active) tape[((size_t)(t0 + j) * FZ_NRL + l) * ns] = u[l];
+                     pos[l] = pos[l] + 1u == fz_rl_depth[l] ? 0u : pos[l] + 1u;
+                  }
+#pragma unroll
+                  for (int r = 0; r < FZ_NREG; ++r) st[r] = sn[r];
+               }
+         }
+      }
+   }
+
+   // ---- sweep 2: patches from the last to the first, the chunks of a patch from its last to its first
+   float R[FZ_A(FZ_NREG)], pb[FZ_A(FZ_NPARAM)], cb[FZ_A(FZ_NCONST)];
+   R[0] = pb[0] = cb[0] = 0.f;
+#pragma unroll
+   for (int r = 0; r < FZ_NREG; ++r) R[r] = a.state_grad ? a.state_grad[(size_t)fz_reg_row[r] * nsv + s] : 0.f;
+#pragma unroll
+   for (int k = 0; k < FZ_NPARAM; ++k) pb[k] = a.param_grad ? a.param_grad[(size_t)k * nsv + s] : 0.f;
+#pragma unroll
+   for (int k = 0; k < FZ_NCONST; ++k) cb[k] = a.const_grad ? a.const_grad[(size_t)k * nsv + s] : 0.f;
+#pragma unroll
+   for (int l = 0; l < FZ_NRL; ++l) {                      // the adjoint rings: the slot of u[T-1-j] holds state_grad[row0 + j], or +0.0f
+      const unsigned D = fz_rl_depth[l], top = (T - 1u) % D;
+#pragma unroll 4
+      for (unsigned j = 0; j < D; ++j) {
+         const unsigned slot = top >= j ? top - j : top + D - j;
+         ring[(size_t)(fz_rl_slot0[l] + slot) * FZ_BLOCK] = a.state_grad ? a.state_grad[(size_t)(fz_rl_row0[l] + j) * nsv + s] : 0.f;
+      }
+   }
+   for (unsigned pk = npatch; pk-- > 0;) {
+      const unsigned r0 = pk * (unsigned)FZ_R, np = T - r0 < (unsigned)FZ_R ? T - r0 : (unsigned)FZ_R;
+      fz_wave_sync();                                        // (the patch before has left for in_grad)
+      fz_adj_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+      fz_adj_fetch<FZ_APO>(patch + FZ_AX, gyb + (size_t)r0 * FZ_NOUT, ostride, rows_here, np * FZ_NOUT, lane);
+      fz_wave_sync();
+      const unsigned nk = (np + (unsigned)FZ_C - 1u) / (unsigned)FZ_C;
+      for (unsigned kk = nk; kk-- > 0;) {
+         const unsigned k = pk * (unsigned)(FZ_R / FZ_C) + kk;
+         const unsigned t0 = k * (unsigned)FZ_C;
+         const unsigned n = T - t0 < (unsigned)FZ_C ? T - t0 : (unsigned)FZ_C;   // rows of this chunk (1 .. FZ_C)
+         float S[FZ_C][FZ_A(FZ_NREG)], X[FZ_C][FZ_A(FZ_NIN)], RV[FZ_C][FZ_A(FZ_NRR)];
+         const float* ck = a.ckpt + (size_t)k * FZ_NREG * ns + s;
+         float* const xr = mine + kk * (unsigned)(FZ_C * FZ_NIN);                 // the chunk's x rows, then its dL/dx rows
+         const float* const yr = mine + FZ_AX + kk * (unsigned)(FZ_C * FZ_NOUT);  // its dL/dy rows
+#pragma unroll
+         for (int j = 0; j < FZ_C; ++j) {
+            S[j][0] = 0.f;
+            X[j][0] = 0.f;
+            RV[j][0] = 0.f;
+         }
+#pragma unroll
+         for (int r = 0; r < FZ_NREG; ++r) S[0][r] = ck[(size_t)r * ns];
+         // every ring read of the chunk, requested together: tape row t - d, or the caller's state for t < d; the frames from the patch
+#pragma unroll
+         for (int j = 0; j < FZ_C; ++j)
+            if ((unsigned)j < n) {
+#pragma unroll
+               for (int q = 0; q < FZ_NRR; ++q) {
+                  const unsigned l = fz_rr_line[q], d = fz_rr_delay[q];
+                  const unsigned t = t0 + (unsigned)j;
+                  RV[j][q] = t >= d ? tape[((size_t)(t - d) * FZ_NRL + l) * ns] : a.state[(size_t)(fz_rl_row0[l] + d - 1u - t) * ns + s];
+               }
+#pragma unroll
+               for (int w = 0; w < FZ_NIN; ++w) X[j][w] = xr[j * FZ_NIN + w];
+            }
+#pragma unroll
+         for (int j = 0; j + 1 < FZ_C; ++j)
+            if ((unsigned)j + 1u < n) {
+               float u[FZ_NRL];
+               fz_adj::fwd(X[j], c, p, S[j], RV[j], S[j + 1], u);
+            }
+         // the saved states, frames and ring values are opaque from here on: the compiler must not keep the re-run's node values alive
+         // for the backward walk instead of re-evaluating them from these
+#pragma unroll
+         for (int j = 0; j < FZ_C; ++j) {
+#pragma unroll
+            for (int r = 0; r < FZ_A(FZ_NREG); ++r) asm volatile("" : "+v"(S[j][r]));
+#pragma unroll
+            for (int w = 0; w < FZ_A(FZ_NIN); ++w) asm volatile("" : "+v"(X[j][w]));
+#pragma unroll
+            for (int q = 0; q < FZ_A(FZ_NRR); ++q) asm volatile("" : "+v"(RV[j][q]));
+         }
+         unsigned base[FZ_NRL];
+#pragma unroll
+         for (int l = 0; l < FZ_NRL; ++l) base[l] = t0 % fz_rl_depth[l];
+#pragma unroll
+         for (int j = FZ_C - 1; j >= 0; --j)
+            if ((unsigned)j < n) {
+               float yb[FZ_A(FZ_NOUT)], xb[FZ_A(FZ_NIN)];
+               unsigned pt[FZ_NRL];
+               yb[0] = 0.f;
+#pragma unroll
+               for (int l = 0; l < FZ_NRL; ++l) pt[l] = (base[l] + (unsigned)j) % fz_rl_depth[l];
+#pragma unroll
+               for (int w = 0; w < FZ_NOUT; ++w) yb[w] = yr[j * FZ_NOUT + w];
+               fz_adj::bwd(X[j], c, p, S[j], RV[j], yb, xb, R, pb, cb, ring, pt);
+               if (gxb && active) {                          // (the row's x is in X[j]: its dL/dx takes its place)
+#pragma unroll
+                  for (int w = 0; w < FZ_NIN; ++w) xr[j * FZ_NIN + w] = xb[w];
+               }
+            }
+      }
+      if (gxb) {
+         fz_wave_sync();
+         fz_adj_flush<FZ_API>(patch, gxb + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+      }
+   }
+   if (!active) return;
+   size_t nse = ns;
+   asm volatile("" : "+v"(nse));
+   if (a.state0_grad) {
+#pragma unroll
+      for (int r = 0; r < FZ_NREG; ++r) a.state0_grad[(size_t)fz_reg_row[r] * nse + s] = R[r];
+#pragma unroll
+      for (int l = 0; l < FZ_NRL; ++l) {                   // after row 0 the slot of u[-1-j] is D - 1 - j
+         const unsigned D = fz_rl_depth[l];
+#pragma unroll 4
+         for (unsigned j = 0; j < D; ++j) a.state0_grad[(size_t)(fz_rl_row0[l] + j) * nse + s] = ring[(size_t)(fz_rl_slot0[l] + D - 1u - j) * FZ_BLOCK];
+      }
+   }
+   if (a.param_grad) {
+#pragma unroll
+      for (int k = 0; k < FZ_NPARAM; ++k) a.param_grad[(size_t)k * nse + s] = pb[k];
+   }
+   if (a.const_grad) {
+#pragma unroll
+      for (int k = 0; k < FZ_NCONST; ++k) a.const_grad[(size_t)k * nse + s] = cb[k];
+   }
+}

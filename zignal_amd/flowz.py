@@ -820,28 +820,36 @@ class Program:
         C.check(C.lib.fz_program_ring_grad_workspace(self._h, int(n_streams), int(T), int(checkpoint_rows), ctypes.byref(b)))
         return int(b.value)
 
-    def ring_grad_resources(self, c: int = 0) -> dict:
+    def ring_grad_resources(self, c: int = 0, stream_major: bool = False) -> dict:
         """grad_resources() of the kernel of run_block_ring_grad at checkpoint stride c (0: the library default); 'lds_bytes' = the
-        adjoint rings of one workgroup"""
+        adjoint rings of one workgroup.  stream_major: the kernel of run_block_ring_grad_stream_major ('lds_bytes': rings and patches)"""
         r = C.KernelResources()
-        C.check(C.lib.fz_program_ring_grad_resources(self._h, int(c), ctypes.byref(r)))
+        C.check(C.lib.fz_program_ring_grad_resources_for(self._h, int(c), int(bool(stream_major)), ctypes.byref(r)))
         return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
 
-    def ring_grad_kernel_symbol(self, c: int = 0) -> str:
+    def ring_grad_kernel_symbol(self, c: int = 0, stream_major: bool = False) -> str:
         buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_ring_grad_kernel_symbol(self._h, int(c), buf, 160))
+        C.check(C.lib.fz_program_ring_grad_kernel_symbol_for(self._h, int(c), int(bool(stream_major)), buf, 160))
         return buf.value.decode()
 
-    def ring_grad_source(self, c: int = 0) -> str:
-        n = C.check(C.lib.fz_program_ring_grad_source(self._h, int(c), None, 0))
+    def ring_grad_source(self, c: int = 0, stream_major: bool = False) -> str:
+        n = C.check(C.lib.fz_program_ring_grad_source_for(self._h, int(c), int(bool(stream_major)), None, 0))
         buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_ring_grad_source(self._h, int(c), buf, n + 1))
+        C.check(C.lib.fz_program_ring_grad_source_for(self._h, int(c), int(bool(stream_major)), buf, n + 1))
         return buf.value.decode()
 
     def run_block_ring_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0):
         """run_block_grad for graphs with delay lines deeper than 8 samples (fz_run_block_ring_grad): the same arguments, the same
         result dict, the same order of every sum; time-major frames only.  For a graph run_block_grad takes it is run_block_grad."""
         return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None, ring=True)
+
+    def run_block_ring_grad_stream_major(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None,
+                                         checkpoint_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None, in_grad=None):
+        """run_block_ring_grad on stream-major buffers (fz_run_block_ring_grad_stream_major): the arguments, windows and result dict of
+        run_block_grad_stream_major; not a bit differs from run_block_ring_grad on the transposed frames.  For a graph
+        run_block_grad_stream_major takes it is run_block_grad_stream_major."""
+        n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), ring=True)
 
     # -- the backward under a squared-error loss (fz_run_block_loss_grad): dL/dy formed in the kernel from a target ------------------
     LOSS_GRAD_WANT = GRAD_WANT + ("loss", "out")
@@ -881,21 +889,22 @@ class Program:
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), (float(grad_scale), out))
 
     # -- the squared-error backward of a block with delay lines deeper than 8 samples (fz_run_block_ring_loss_grad) -------------------
-    def ring_loss_grad_resources(self, c: int = 0) -> dict:
-        """ring_grad_resources() of the kernel of run_block_ring_loss_grad at checkpoint stride c (0: the library default)"""
+    def ring_loss_grad_resources(self, c: int = 0, stream_major: bool = False) -> dict:
+        """ring_grad_resources() of the kernel of run_block_ring_loss_grad at checkpoint stride c (0: the library default);
+        stream_major: of run_block_ring_loss_grad_stream_major"""
         r = C.KernelResources()
-        C.check(C.lib.fz_program_ring_loss_grad_resources(self._h, int(c), ctypes.byref(r)))
+        C.check(C.lib.fz_program_ring_loss_grad_resources_for(self._h, int(c), int(bool(stream_major)), ctypes.byref(r)))
         return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
 
-    def ring_loss_grad_kernel_symbol(self, c: int = 0) -> str:
+    def ring_loss_grad_kernel_symbol(self, c: int = 0, stream_major: bool = False) -> str:
         buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_ring_loss_grad_kernel_symbol(self._h, int(c), buf, 160))
+        C.check(C.lib.fz_program_ring_loss_grad_kernel_symbol_for(self._h, int(c), int(bool(stream_major)), buf, 160))
         return buf.value.decode()
 
-    def ring_loss_grad_source(self, c: int = 0) -> str:
-        n = C.check(C.lib.fz_program_ring_loss_grad_source(self._h, int(c), None, 0))
+    def ring_loss_grad_source(self, c: int = 0, stream_major: bool = False) -> str:
+        n = C.check(C.lib.fz_program_ring_loss_grad_source_for(self._h, int(c), int(bool(stream_major)), None, 0))
         buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_ring_loss_grad_source(self._h, int(c), buf, n + 1))
+        C.check(C.lib.fz_program_ring_loss_grad_source_for(self._h, int(c), int(bool(stream_major)), buf, n + 1))
         return buf.value.decode()
 
     def run_block_ring_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
@@ -904,6 +913,16 @@ class Program:
         same result dict, the rule of run_block_loss_grad and then the order of run_block_ring_grad; time-major frames only, the
         workspace of run_block_ring_grad.  For a graph run_block_loss_grad takes it is run_block_loss_grad."""
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), None), ring=True)
+
+    def run_block_ring_loss_grad_stream_major(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0,
+                                              want=LOSS_GRAD_WANT, accum=None, checkpoint_rows: int = 0, row0: int = 0,
+                                              n_samples: Optional[int] = None, in_grad=None, out=None):
+        """run_block_ring_loss_grad on stream-major buffers (fz_run_block_ring_loss_grad_stream_major): the arguments, windows and
+        result dict of run_block_loss_grad_stream_major; not a bit differs from run_block_ring_loss_grad on the transposed frames.  For
+        a graph run_block_loss_grad_stream_major takes it is run_block_loss_grad_stream_major."""
+        n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), (float(grad_scale), out),
+                              ring=True)
 
     # -- the backward of a whole recording (fz_run_recording_grad): two-level checkpointing over the calls above ---------------------
     def recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
@@ -1014,8 +1033,9 @@ class Program:
     def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None, ring=False):
         """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers; loss: None, or
         (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
-        (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is of the ring family (time-major):
-        run_block_ring_grad / run_block_ring_loss_grad, or with recording run_recording_ring_grad / run_recording_ring_loss_grad"""
+        (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is of the ring family:
+        run_block_ring_grad / run_block_ring_loss_grad and their _stream_major twins, or with recording (time-major) run_recording_ring_grad /
+        run_recording_ring_loss_grad"""
         import torch
 
         if ring:
@@ -1132,7 +1152,10 @@ class Program:
                 fn = C.lib.fz_run_block_grad if loss is None else C.lib.fz_run_block_loss_grad
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(T), hs))
         else:
-            fn = C.lib.fz_run_block_grad_stream_major if loss is None else C.lib.fz_run_block_loss_grad_stream_major
+            if ring:
+                fn = C.lib.fz_run_block_ring_grad_stream_major if loss is None else C.lib.fz_run_block_ring_loss_grad_stream_major
+            else:
+                fn = C.lib.fz_run_block_grad_stream_major if loss is None else C.lib.fz_run_block_loss_grad_stream_major
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, T, hs))
         return out
 
