@@ -1,10 +1,9 @@
 """Graphs, rules and cases of the ring recording tests (fz_run_recording_ring_grad, fz_run_recording_ring_loss_grad): the ten graphs of
 tests/ring_loss_graphs.py with what the block rule counts of each; the block rule and the workspace formula restated; the (streams,
 rows, block_rows) triples both test files share, their draws and the restatement's answers (tests/recording_ref.py chaining
-tests/adjoint_ref.py / tests/loss_grad_ref.py block by block), computed once; the kernel sources the parent pins hold; and the kernels
+tests/adjoint_ref.py / tests/loss_grad_ref.py block by block), computed once; and the kernels
 the GPU tests launch (tests/golden/ring_recording_kernels.fzm.gz)."""
 import gzip
-import hashlib
 import math
 import os
 import subprocess
@@ -22,7 +21,6 @@ import ring_loss_graphs as RL
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 MANIFEST = os.path.join(HERE, "golden", "ring_recording_kernels.fzm.gz")
-PINS = os.path.join(HERE, "golden", "ring_recording_parent_pins.json")
 K = RL.K
 
 GRAPHS = RL.GRAPHS
@@ -130,29 +128,6 @@ def want(name, ns, T, B, loss, c=0):
                 a.setflags(write=False)
         _wants[key] = r
     return _wants[key]
-
-
-# ---- every other kernel text: tests/golden/ring_recording_parent_pins.json -------------------------------------------------------------
-def _h(s):
-    return [len(s.encode()), hashlib.sha256(s.encode()).hexdigest()]
-
-
-def kernel_pins():
-    """length and sha256 of the whole source of every adjoint, loss, states, ring and ring loss kernel of the test graphs, with the library
-    that is imported.  The committed file was written by this function from the parent commit, in a checkout of its own:
-        PYTHONPATH=<parent checkout>:tests python -c "import json, ring_recording_graphs as R; print(json.dumps(R.kernel_pins(), indent=1, sort_keys=True))" """
-    import grad_graphs as GG
-    from zignal_amd import flowz as F
-    pins = {"ring": {}, "ring_loss": {}, "plain": {}}
-    for name in sorted(GRAPHS):
-        p = prog(name)
-        pins["ring"][name] = [_h(p.ring_grad_source(c)) for c in (0, 1)]
-        pins["ring_loss"][name] = [_h(p.ring_loss_grad_source(c)) for c in (0, 1)]
-    for name in sorted(GG.SUPPORTED):
-        p = F.compile(F.from_sexpr(GG.SUPPORTED[name]()))
-        pins["plain"][name] = {"adjoint": [_h(p.grad_source(0, sm)) for sm in (False, True)], "loss": [_h(p.loss_grad_source(0, sm)) for sm in (False, True)],
-                               "states": [_h(p.states_source(sm)) for sm in (False, True)]}
-    return pins
 
 
 # ---- the kernels the GPU tests launch: tests/golden/ring_recording_kernels.fzm.gz ------------------------------------------------------

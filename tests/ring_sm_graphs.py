@@ -3,7 +3,6 @@ fz_run_block_ring_loss_grad_stream_major): the graphs are those of tests/ring_gr
 that chooses the workgroup and the patch length together, restated; the graph whose rings plus the shortest patch fit no workgroup;
 the transposition helpers; and the kernels the GPU tests launch (tests/golden/ring_sm_kernels.fzm.gz)."""
 import gzip
-import hashlib
 import os
 import re
 import subprocess
@@ -19,7 +18,6 @@ from graphs import DEL, add
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 MANIFEST = os.path.join(HERE, "golden", "ring_sm_kernels.fzm.gz")
-PINS = os.path.join(HERE, "golden", "ring_sm_parent_pins.json")
 LDS_BYTES = 163840                                                # per CU and the most one workgroup may declare (gfx950)
 
 RINGS = RG.RINGS                                                  # the eight graphs of the plain backward
@@ -110,31 +108,6 @@ def to_sm(a, rows=None, row0=0, fill=0.0):
 def from_sm(a, T, row0=0):
     """the window's rows of a stream-major buffer, time-major"""
     return np.ascontiguousarray(a[:, row0:row0 + T].transpose(1, 0, 2))
-
-
-# ---- every other kernel text: tests/golden/ring_sm_parent_pins.json ------------------------------------------------------------------------
-def _h(s):
-    return [len(s.encode()), hashlib.sha256(s.encode()).hexdigest()]
-
-
-def kernel_pins():
-    """length and sha256 of the whole source of every adjoint, loss, states, ring, ring loss and ring states kernel of the test graphs, in
-    both layouts where they exist, with the library that is imported -- through the calls the parent commit has.  The committed file was
-    written by this function from the parent commit, in a checkout of its own:
-        PYTHONPATH=<parent checkout>:tests python -c "import json, ring_sm_graphs as R; print(json.dumps(R.kernel_pins(), indent=1, sort_keys=True))" """
-    import grad_graphs as GG
-    from zignal_amd import flowz as F
-    pins = {"ring": {}, "ring_loss": {}, "ring_states": {}, "plain": {}}
-    for name in sorted(GRAPHS):
-        p = prog(name)
-        pins["ring"][name] = [_h(p.ring_grad_source(c)) for c in STRIDES]
-        pins["ring_loss"][name] = [_h(p.ring_loss_grad_source(c)) for c in STRIDES]
-        pins["ring_states"][name] = _h(p.ring_states_source())
-    for name in sorted(GG.SUPPORTED):
-        p = F.compile(F.from_sexpr(GG.SUPPORTED[name]()))
-        pins["plain"][name] = {"adjoint": [_h(p.grad_source(0, sm)) for sm in (False, True)], "loss": [_h(p.loss_grad_source(0, sm)) for sm in (False, True)],
-                               "states": [_h(p.states_source(sm)) for sm in (False, True)]}
-    return pins
 
 
 # ---- the kernels the GPU tests launch: tests/golden/ring_sm_kernels.fzm.gz ---------------------------------------------------------------

@@ -178,7 +178,8 @@ def test_the_plain_adjoint_kernels_are_untouched_by_the_loss_variant(tmp_path):
     for sm in (False, True):
         p.loss_grad_resources(stream_major=sm)
         src = p.loss_grad_source(stream_major=sm)
-        assert "fz_adj_loss" in src and "static void out(" in src and "static void out(" not in p.grad_source(0, sm)
+        assert "#define FZ_LOSS 1 " in src and "static void out(" in src
+        assert "#define FZ_LOSS 0 " in p.grad_source(0, sm) and "static void out(" not in p.grad_source(0, sm)
     assert before == snap() == never
 
 

@@ -5,7 +5,6 @@ against float64 autograd."""
 import ctypes
 import glob
 import gzip
-import hashlib
 import json
 import os
 import re
@@ -273,19 +272,17 @@ def test_ring_kernel_has_no_fma(name, tmp_path, monkeypatch):
 
 @pytest.mark.parametrize("name", ["df1_cascade6", "moog_ladder", "rules"])
 def test_the_other_adjoint_kernels_have_the_parents_texts(name):
-    """tests/golden/ring_grad_parent_pins.json: length and sha256 of the whole source of the adjoint, loss and states kernels in both
-    layouts, recorded from the commit before the ring kernel -- a kernel's source is its cache and manifest key.  The time-major
-    adjoint pin is also the one test_grad_stream_major_host.py holds (tests/golden/adjoint_time_major_pins.json)."""
-    pin = json.load(open(os.path.join(HERE, "golden", "ring_grad_parent_pins.json")))[name]
+    """tests/golden/adjoint_code_pins.json: the code of the adjoint, loss and states kernels in both layouts, recorded from the parent of
+    the commit that folded the loss kernels into their siblings; test_adjoint_code_pins_host.py holds what the library builds now to
+    them.  Here: the pins name this graph's kernels by the symbols the library gives them, and for a graph without a ring line the ring
+    kernel IS the adjoint kernel."""
+    pins = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
     p = F.compile(F.from_sexpr(GG.SUPPORTED[name]()))
-    h = lambda s: [len(s.encode()), hashlib.sha256(s.encode()).hexdigest()]   # noqa: E731
-    assert [h(p.grad_source(0, sm)) for sm in (False, True)] == pin["adjoint"]
-    assert [h(p.loss_grad_source(0, sm)) for sm in (False, True)] == pin["loss"]
-    assert [h(p.states_source(sm)) for sm in (False, True)] == pin["states"]
-    assert h(p.ring_grad_source()) == pin["adjoint"][0]
-    old = os.path.join(HERE, "golden", "adjoint_time_major_pins.json")
-    if name in json.load(open(old)):
-        assert json.load(open(old))[name]["source_sha256"] == pin["adjoint"][0][1]
+    for sm, layout in ((False, "tm"), (True, "sm")):
+        assert pins[f"adjoint/{layout}/{name}"]["symbol"] == p.grad_kernel_symbol(0, sm)
+        assert pins[f"loss/{layout}/{name}"]["symbol"] == p.loss_grad_kernel_symbol(0, sm)
+        assert pins[f"states/{layout}/{name}"]["symbol"] == p.states_kernel_symbol(sm)
+    assert p.ring_grad_source() == p.grad_source() and p.ring_grad_kernel_symbol() == p.grad_kernel_symbol()
 
 
 def test_the_ring_kernel_has_a_text_of_its_own():
@@ -294,6 +291,7 @@ def test_the_ring_kernel_has_a_text_of_its_own():
     assert "fz_adj_ring_args" in src and "FZ_RING_SLOTS" in src and "__shared__" in src and "__syncthreads" not in src
     plain = F.compile(F.from_sexpr(GG.SUPPORTED["df1_cascade6"]())).grad_source()
     assert "fz_adj_ring_args" not in plain and "FZ_RING_SLOTS" not in plain and "ring" not in plain.split("// ==== fz_block_kernel.hip.inc ====")[0]
+    assert "#define FZ_LOSS 0 " in src and "#define FZ_LOSS 0 " in plain and "static void out(" not in src + plain
     assert "fz_adj" not in p.source()
 
 

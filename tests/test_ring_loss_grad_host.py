@@ -1,10 +1,9 @@
 """The ring backward under a squared-error loss without a GPU (fz_run_block_ring_loss_grad: fz_run_block_loss_grad for graphs with delay
 lines deeper than 8 samples): its scope and the refusals that stay, the calls it IS for a graph without such a line, the argument checks
-of fz_run_block_loss_grad, the kernel's resources and instructions (JIT for gfx950), every other kernel text unchanged, the kernel
+of fz_run_block_loss_grad, the kernel's resources and instructions (JIT for gfx950), the code pins' names for every other kernel, the kernel
 manifest of the GPU tests, and tests/loss_grad_ref.py on the ring graphs against float64 autograd of the mean squared error."""
 import ctypes
 import glob
-import hashlib
 import json
 import os
 import re
@@ -57,7 +56,7 @@ def test_the_ten_graphs_are_taken(name):
     for c in (0, 1, 4):
         assert p.ring_loss_grad_kernel_symbol(c) == p.ring_grad_kernel_symbol(c).replace("fz_adjoint_ring_", "fz_adjoint_ring_loss_", 1)
     src = p.ring_loss_grad_source()
-    assert "fz_adj_ring_loss_args" in src and "const float* rv, float* y)" in src and "__syncthreads" not in src
+    assert "#define FZ_LOSS 1 " in src and "#define FZ_LOSS 0 " in p.ring_grad_source() and "fz_adj_ring_args" in src and "const float* rv, float* y)" in src and "__syncthreads" not in src
     assert "static void out(" not in p.ring_grad_source()
     # an empty block is FZ_OK with nothing touched
     for ns, T in ((0, 100), (100, 0), (0, 0)):
@@ -254,32 +253,38 @@ def test_ring_loss_kernel_has_no_fma(name, tmp_path, monkeypatch):
     assert "s_barrier" not in every and not [o for o in every if "atomic" in o]
 
 
-# ---- every existing kernel text is the parent's --------------------------------------------------------------------------------------
-PINS = json.load(open(os.path.join(HERE, "golden", "ring_loss_parent_pins.json")))
-_h = lambda s: [len(s.encode()), hashlib.sha256(s.encode()).hexdigest()]   # noqa: E731
+# ---- every existing kernel's code is the parent's: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py --------------
+PINS = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
 
 
 def test_the_pins_cover_every_graph():
-    assert sorted(PINS["ring"]) == sorted(RG.RINGS) and sorted(PINS["plain"]) == sorted(GG.SUPPORTED)
+    for kind in ("ring", "ring_loss"):
+        assert sorted(k.split("/")[3] for k in PINS if k.startswith(kind + "/tm/c0/")) == sorted(RL.GRAPHS) and set(RG.RINGS) <= set(RL.GRAPHS)
+    for kind in ("adjoint", "loss", "states"):
+        assert sorted(k.split("/")[2] for k in PINS if k.startswith(kind + "/tm/")) == sorted(GG.SUPPORTED)
 
 
 @pytest.mark.parametrize("name", sorted(RG.RINGS))
 def test_the_ring_kernel_has_the_parents_text(name):
-    """tests/golden/ring_loss_parent_pins.json: length and sha256 of whole kernel sources, recorded from the commit before the ring loss
-    kernel in a checkout of its own -- a kernel's source is its cache and manifest key"""
+    """the pins name the ring kernel the library makes, at the default stride and at C = 1, and the ring loss kernel is not the ring kernel:
+    other instructions, other metadata (that both are the parent's code: test_adjoint_code_pins_host.py)"""
     p = RL.prog(name)
-    assert [_h(p.ring_grad_source(c)) for c in (0, 1)] == PINS["ring"][name]
-    assert [_h(p.ring_loss_grad_source(c)) for c in (0, 1)] != PINS["ring"][name]
+    for c in (0, 1):
+        ring, loss = PINS[f"ring/tm/c{c}/{name}"], PINS[f"ring_loss/tm/c{c}/{name}"]
+        assert ring["symbol"] == p.ring_grad_kernel_symbol(c) and loss["symbol"] == p.ring_loss_grad_kernel_symbol(c)
+        assert loss[".text"] != ring[".text"] and loss[".note"] != ring[".note"]
+        assert p.ring_loss_grad_source(c) != p.ring_grad_source(c)
 
 
 @pytest.mark.parametrize("name", sorted(GG.SUPPORTED))
 def test_the_adjoint_loss_and_states_kernels_have_the_parents_texts(name):
-    pin = PINS["plain"][name]
+    """the pins name this graph's kernels, and for a graph without a ring line the ring loss kernel IS the loss kernel"""
     p = F.compile(F.from_sexpr(GG.SUPPORTED[name]()))
-    assert [_h(p.grad_source(0, sm)) for sm in (False, True)] == pin["adjoint"]
-    assert [_h(p.loss_grad_source(0, sm)) for sm in (False, True)] == pin["loss"]
-    assert [_h(p.states_source(sm)) for sm in (False, True)] == pin["states"]
-    assert _h(p.ring_loss_grad_source()) == pin["loss"][0]
+    for sm, layout in ((False, "tm"), (True, "sm")):
+        assert PINS[f"adjoint/{layout}/{name}"]["symbol"] == p.grad_kernel_symbol(0, sm)
+        assert PINS[f"loss/{layout}/{name}"]["symbol"] == p.loss_grad_kernel_symbol(0, sm)
+        assert PINS[f"states/{layout}/{name}"]["symbol"] == p.states_kernel_symbol(sm)
+    assert p.ring_loss_grad_source() == p.loss_grad_source()
 
 
 # ---- the kernel manifest of the GPU tests ------------------------------------------------------------------------------------------

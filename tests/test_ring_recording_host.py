@@ -1,7 +1,7 @@
 """The backward of a whole recording with deep delay lines without a GPU (fz_run_recording_ring_grad, fz_run_recording_ring_loss_grad):
 the scope and the refusals that stay, the calls they ARE for a graph without a deep line, the block rule and the workspace formula
 against their restatements, every argument check with its reason, the ring states kernel's JIT for gfx950 (a symbol of its own, no
-scratch, no VGPR spills, the ring adjoint kernel's LDS, no FMA, no barrier, no atomic), every other kernel text unchanged, the kernel
+scratch, no VGPR spills, the ring adjoint kernel's LDS, no FMA, no barrier, no atomic), the code pins' names for every other kernel, the kernel
 manifest of the GPU tests, and tests/recording_ref.py on the ring graphs -- the block-by-block restatement the GPU test holds the calls
 to -- against the single restated call, bit for bit, with inputs that tell a wrong chain from the right one."""
 import ctypes
@@ -368,26 +368,26 @@ def test_ring_states_kernel_has_no_fma_no_barrier_no_atomic(name, tmp_path, monk
     assert "s_barrier" not in every and not [o for o in every if "atomic" in o]
 
 
-# ---- every other kernel text is the parent's -------------------------------------------------------------------------------------------
-PINS = json.load(open(R.PINS))
+# ---- every other kernel's code is the parent's: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py ---------------
+PINS = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
 
 
 def test_the_pins_cover_every_graph():
-    assert sorted(PINS["ring"]) == sorted(PINS["ring_loss"]) == NAMES and sorted(PINS["plain"]) == sorted(GG.SUPPORTED)
+    for kind in ("ring/tm/c0/", "ring/tm/c1/", "ring_loss/tm/c0/", "ring_loss/tm/c1/", "ring_states/tm/"):
+        assert sorted(k[len(kind):] for k in PINS if k.startswith(kind)) == NAMES, kind
+    assert sorted(k.split("/")[2] for k in PINS if k.startswith("states/tm/")) == sorted(GG.SUPPORTED)
 
 
 def test_every_other_kernel_has_the_parents_text():
-    """tests/golden/ring_recording_parent_pins.json: length and sha256 of whole kernel sources, recorded from the commit before the ring
-    states kernel in a checkout of its own -- a kernel's source is its cache and manifest key"""
-    now = R.kernel_pins()
-    for kind in ("ring", "ring_loss"):
-        for name in NAMES:
-            assert now[kind][name] == PINS[kind][name], (kind, name)
-    for name in sorted(GG.SUPPORTED):
-        assert now["plain"][name] == PINS["plain"][name], name
-    pinned = {tuple(h) for kind in ("ring", "ring_loss") for v in PINS[kind].values() for h in v}
-    for name in NAMES:                                            # and the new kernel's text is none of them
-        assert tuple(R._h(R.prog(name).ring_states_source())) not in pinned
+    """the pins name the kernels the library makes, and the ring states kernel's instructions are none of the ring adjoint kernels' (that
+    all of them are the parent's code: test_adjoint_code_pins_host.py)"""
+    pinned = {PINS[f"{kind}/tm/c{c}/{name}"][".text"] for kind in ("ring", "ring_loss") for c in (0, 1) for name in NAMES}
+    for name in NAMES:
+        p = R.prog(name)
+        assert PINS[f"ring_states/tm/{name}"]["symbol"] == p.ring_states_kernel_symbol() and PINS[f"ring_states/tm/{name}"][".text"] not in pinned
+        for c in (0, 1):
+            assert PINS[f"ring/tm/c{c}/{name}"]["symbol"] == p.ring_grad_kernel_symbol(c)
+            assert PINS[f"ring_loss/tm/c{c}/{name}"]["symbol"] == p.ring_loss_grad_kernel_symbol(c)
 
 
 # ---- the kernel manifest of the GPU tests ----------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 fz_run_block_ring_loss_grad_stream_major): its scope and the refusals that stay, the calls it IS for a graph without a deep line, the
 rule that chooses the workgroup and the patch length together (restated in tests/ring_sm_graphs.py), the refusal when rings plus the
 shortest patch fit no workgroup, the argument checks of the stream-major siblings, the kernels' resources and instructions (JIT for
-gfx950), every other kernel text unchanged, the kernel manifest of the GPU tests, and the restatement on transposed arrays."""
+gfx950), the code pins' names for every other kernel, the kernel manifest of the GPU tests, and the restatement on transposed arrays."""
 import ctypes
 import glob
 import json
@@ -68,7 +68,7 @@ def test_the_graphs_are_taken(name):
         sym = symbol(0, stream_major=True)
         assert re.fullmatch(r"fz_adjoint_ring_%ssm_kernel_c(1|2|4|8|16)r(4|8|16|32|64)b(256|128|64)_g%s" % ("loss_" if loss else "", tag), sym), sym
         src = (p.ring_loss_grad_source if loss else p.ring_grad_source)(0, stream_major=True)
-        assert ("fz_adj_ring_loss_sm_args" if loss else "fz_adj_ring_sm_args") in src and "#define FZ_R " in src and "#define FZ_RING_SLOTS " in src
+        assert "fz_adj_ring_sm_args" in src and "#define FZ_LOSS %d " % loss in src and "#define FZ_R " in src and "#define FZ_RING_SLOTS " in src
         assert "__syncthreads" not in src and "atomic" not in src.split("extern \"C\"")[1]
         assert ("static void out(" in src) == loss
         for ns, T in ((0, 100), (100, 0), (0, 0)):                # an empty block is FZ_OK with nothing touched
@@ -340,30 +340,31 @@ def test_the_kernels_have_no_fma_no_barrier_and_no_atomic(name, loss, c, tmp_pat
     assert "s_barrier" not in every and not [o for o in every if "atomic" in o]
 
 
-# ---- every existing kernel text is the parent's --------------------------------------------------------------------------------------
-PINS = json.load(open(RS.PINS))
+# ---- every existing kernel's code is the parent's: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py -------------
+PINS = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
 
 
 def test_the_pins_cover_every_graph():
-    assert sorted(PINS["ring"]) == sorted(PINS["ring_loss"]) == sorted(PINS["ring_states"]) == sorted(RS.GRAPHS)
-    assert sorted(PINS["plain"]) == sorted(GG.SUPPORTED)
+    for kind in ("ring", "ring_loss"):
+        for layout in ("tm", "sm"):
+            for c in RS.STRIDES:
+                assert sorted(k.split("/")[3] for k in PINS if k.startswith(f"{kind}/{layout}/c{c}/")) == sorted(RS.GRAPHS), (kind, layout, c)
+    assert sorted(k.split("/")[2] for k in PINS if k.startswith("ring_states/tm/")) == sorted(RS.GRAPHS)
+    for kind in ("adjoint", "loss", "states"):
+        for layout in ("tm", "sm"):
+            assert sorted(k.split("/")[2] for k in PINS if k.startswith(f"{kind}/{layout}/")) == sorted(GG.SUPPORTED), (kind, layout)
 
 
 def test_every_other_kernel_has_the_parents_text():
-    """tests/golden/ring_sm_parent_pins.json: length and sha256 of whole kernel sources, recorded from the commit before the stream-major
-    ring kernels in a checkout of its own -- a kernel's source is its cache and manifest key"""
-    now = RS.kernel_pins()
-    for kind in ("ring", "ring_loss", "ring_states"):
-        for name in sorted(RS.GRAPHS):
-            assert now[kind][name] == PINS[kind][name], (kind, name)
-    for name in sorted(GG.SUPPORTED):
-        assert now["plain"][name] == PINS["plain"][name], name
-    pinned = {tuple(h) for kind in ("ring", "ring_loss") for v in PINS[kind].values() for h in v}
-    for name in sorted(RS.GRAPHS):                                # and the new kernels' texts are none of them
+    """the pins name the kernels the library makes in both layouts, and the stream-major ring kernels' instructions are none of the
+    time-major ones' (that all of them are the parent's code: test_adjoint_code_pins_host.py)"""
+    pinned = {v[".text"] for k, v in PINS.items() if k.startswith(("ring/tm/", "ring_loss/tm/"))}
+    for name in sorted(RS.GRAPHS):
         p = RS.prog(name)
         for c in RS.STRIDES:
-            assert tuple(RS._h(p.ring_grad_source(c, stream_major=True))) not in pinned
-            assert tuple(RS._h(p.ring_loss_grad_source(c, stream_major=True))) not in pinned
+            for kind, symbol in (("ring", p.ring_grad_kernel_symbol), ("ring_loss", p.ring_loss_grad_kernel_symbol)):
+                assert PINS[f"{kind}/tm/c{c}/{name}"]["symbol"] == symbol(c) and PINS[f"{kind}/sm/c{c}/{name}"]["symbol"] == symbol(c, stream_major=True)
+                assert PINS[f"{kind}/sm/c{c}/{name}"][".text"] not in pinned
 
 
 # ---- the kernel manifest of the GPU tests ------------------------------------------------------------------------------------------

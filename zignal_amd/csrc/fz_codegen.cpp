@@ -25,19 +25,40 @@ extern const char* const kSkeletonBody_sm_long;
 extern const char* const kSkeletonBody_sm_short;
 extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
-extern const char* const kSkeletonAdjoint;   // fz_kernel_adjoint.hip.inc: a kernel text of its own
-extern const char* const kSkeletonAdjointSm; // fz_kernel_adjoint_sm.hip.inc: the same for stream-major buffers
-extern const char* const kSkeletonAdjointRing;   // fz_kernel_adjoint_ring.hip.inc: the adjoint kernel of graphs with delay lines in LDS
-extern const char* const kSkeletonAdjointRingLoss;   // fz_kernel_adjoint_ring_loss.hip.inc: the same with dL/dy formed from a target
-extern const char* const kSkeletonAdjointRingSm;     // fz_kernel_adjoint_ring_sm.hip.inc: the ring adjoint kernel for stream-major buffers
-extern const char* const kSkeletonAdjointRingLossSm; // fz_kernel_adjoint_ring_loss_sm.hip.inc: the same with dL/dy formed from a target
-extern const char* const kSkeletonAdjointLoss;   // fz_kernel_adjoint_loss.hip.inc: the adjoint kernel that forms dL/dy from a target
-extern const char* const kSkeletonAdjointLossSm; // fz_kernel_adjoint_loss_sm.hip.inc: the same for stream-major buffers
-extern const char* const kSkeletonStates;     // fz_kernel_states.hip.inc: the block-start states of a recording (the adjoint body's fwd alone)
-extern const char* const kSkeletonStatesSm;   // fz_kernel_states_sm.hip.inc: the same for stream-major buffers
-extern const char* const kSkeletonStatesRing; // fz_kernel_states_ring.hip.inc: the same for graphs with delay lines in LDS (the ring body's fwd alone)
+extern const char* const kSkeletonAdjoint;       // fz_kernel_adjoint.hip.inc: a kernel text of its own, like the six below
+extern const char* const kSkeletonAdjointSm;
+extern const char* const kSkeletonAdjointRing;
+extern const char* const kSkeletonAdjointRingSm;
+extern const char* const kSkeletonStates;
+extern const char* const kSkeletonStatesSm;
+extern const char* const kSkeletonStatesRing;
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
+
+// The adjoint family (fz_grad.cpp), layout x rings plus the states kernels: one row per combination of the family bits next to
+// FZ_VF_ADJOINT, found by exact match.  The loss selects no row: it is FZ_LOSS in the configuration of the row's text and "_loss" in the
+// symbol, fz_<head>[_loss]<tail>_kernel_<c|u><U>[r<P>]b<block>.
+struct AdjointRow {
+   uint32_t bits;               // of FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM
+   const char *head, *tail;     // of the symbol's stem
+   std::string text;            // the hand-written kernel
+   bool patch_rows;             // the symbol carries r<P>: the rows of the LDS patch of the stream-major frames
+};
+static const AdjointRow& adjoint_row(const Variant& v)
+{
+   static const AdjointRow rows[] = {
+      {0, "fz_adjoint", "", kSkeletonAdjoint, false},
+      {FZ_VF_ADJOINT_SM, "fz_adjoint", "_sm", kSkeletonAdjointSm, true},
+      {FZ_VF_ADJOINT_RING, "fz_adjoint_ring", "", kSkeletonAdjointRing, false},
+      {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_adjoint_ring", "_sm", kSkeletonAdjointRingSm, true},
+      {FZ_VF_STATES, "fz_states", "", kSkeletonStates, false},
+      {FZ_VF_STATES | FZ_VF_ADJOINT_SM, "fz_states", "_sm", kSkeletonStatesSm, true},
+      {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStatesRing, false},
+   };
+   for (const AdjointRow& r : rows)
+      if (r.bits == (v.flags & (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM)) && !((v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_LOSS))) return r;
+   fail(FZ_E_INVALID, "internal: no kernel of the adjoint family has the flags " + std::to_string(v.flags));
+}
 
 // the hand-written text of a variant's kernel: the common head + the ONE body its flags (stream-major: and its streams per lane) select
 const std::string& skeleton_source(const Variant& v)
@@ -45,21 +66,8 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string head = kSkeletonHead, sm = head + kSkeletonBody_sm_common;
    static const std::string sm_pair = sm + kSkeletonBody_sm_pair, sm_long = sm + kSkeletonBody_sm_long, sm_short = sm + kSkeletonBody_sm_short,
                             ws = head + kSkeletonBody_wave_split, fr = head + kSkeletonBody_frames;
-   static const std::string adj = kSkeletonAdjoint, adj_sm = kSkeletonAdjointSm, pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
-   static const std::string adj_loss = kSkeletonAdjointLoss, adj_loss_sm = kSkeletonAdjointLossSm;
-   static const std::string states = kSkeletonStates, states_sm = kSkeletonStatesSm;
-   static const std::string adj_ring = kSkeletonAdjointRing, adj_ring_loss = kSkeletonAdjointRingLoss, states_ring = kSkeletonStatesRing;
-   static const std::string adj_ring_sm = kSkeletonAdjointRingSm, adj_ring_loss_sm = kSkeletonAdjointRingLossSm;
-   // (states + ring: the block-start-states kernel of a ring recording, before either bit alone)
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_RING)) return states_ring;
-   // (ring + stream-major, with or without the loss: texts of their own, before the two-bit cases)
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_SM)) return (v.flags & FZ_VF_ADJOINT_LOSS) ? adj_ring_loss_sm : adj_ring_sm;
-   // (ring + loss before ring and before loss: the three-bit combination is a text of its own)
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_LOSS)) return adj_ring_loss;
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING)) return adj_ring;
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES)) return (v.flags & FZ_VF_ADJOINT_SM) ? states_sm : states;
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_LOSS)) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_loss_sm : adj_loss;
-   if (v.flags & FZ_VF_ADJOINT) return (v.flags & FZ_VF_ADJOINT_SM) ? adj_sm : adj;
+   static const std::string pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
+   if (v.flags & FZ_VF_ADJOINT) return adjoint_row(v).text;
    if (v.flags & FZ_VF_PCM16) return (v.flags & FZ_VF_PCM16_SM) ? pcm_sm : pcm;
    if (v.flags & FZ_VF_STREAM_MAJOR) return !(v.flags & FZ_VF_SM_LONG) ? sm_short : v.P == 2 ? sm_pair : sm_long;
    return ws_parts(v.flags) ? ws : fr;
@@ -69,22 +77,11 @@ const std::string& skeleton_source(const Variant& v)
 // fz_block_kernel_p<streams/lane>u<unroll>b<block>[s<segments>]f<flags>
 std::string kernel_name(const Graph& g, const Variant& v)
 {
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_RING))   // (states + ring: before either alone)
-      return "fz_states_ring_kernel_u" + std::to_string(v.U) + "b" + std::to_string(v.block);
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES))   // (the states bit means something next to FZ_VF_ADJOINT only)
-      return (v.flags & FZ_VF_ADJOINT_SM) ? "fz_states_sm_kernel_u" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block)
-                                          : "fz_states_kernel_u" + std::to_string(v.U) + "b" + std::to_string(v.block);
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_SM))   // (ring + stream-major, with or without the loss: before the two-bit cases)
-      return std::string((v.flags & FZ_VF_ADJOINT_LOSS) ? "fz_adjoint_ring_loss_sm_kernel_c" : "fz_adjoint_ring_sm_kernel_c") + std::to_string(v.U) + "r" + std::to_string(v.P) +
-             "b" + std::to_string(v.block);
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_LOSS))   // (ring + loss: before either alone)
-      return "fz_adjoint_ring_loss_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
-   if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING))   // (the ring bit means something next to FZ_VF_ADJOINT only)
-      return "fz_adjoint_ring_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
-   const std::string adj = (v.flags & FZ_VF_ADJOINT_LOSS) ? "fz_adjoint_loss" : "fz_adjoint";   // (the loss bit means something next to FZ_VF_ADJOINT only)
-   if (v.flags & FZ_VF_ADJOINT_SM)
-      return adj + "_sm_kernel_c" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block);
-   if (v.flags & FZ_VF_ADJOINT) return adj + "_kernel_c" + std::to_string(v.U) + "b" + std::to_string(v.block);
+   if (v.flags & FZ_VF_ADJOINT) {   // (the family bits mean something next to FZ_VF_ADJOINT only)
+      const AdjointRow& r = adjoint_row(v);
+      return std::string(r.head) + ((v.flags & FZ_VF_ADJOINT_LOSS) ? "_loss" : "") + r.tail + "_kernel_" + ((v.flags & FZ_VF_STATES) ? "u" : "c") + std::to_string(v.U) +
+             (r.patch_rows ? "r" + std::to_string(v.P) : "") + "b" + std::to_string(v.block);
+   }
    if ((v.flags & FZ_VF_PCM16) && (v.flags & FZ_VF_PCM16_SM))   // (stream-major PCM: which side is int16, rows per chunk, lanes)
       return "fz_pcm16_sm_kernel_i" + std::to_string((v.flags & FZ_VF_PCM16_IN) ? 1 : 0) + "o" + std::to_string((v.flags & FZ_VF_PCM16_OUT) ? 1 : 0) + "u" +
              std::to_string(v.U) + "b" + std::to_string(v.block);
@@ -1102,6 +1099,7 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
    }
    if (v.flags & FZ_VF_STATES) o << "#define FZ_U " << v.U << "   // rows per unrolled group of the forward recursion\n";
    else o << "#define FZ_C " << v.U << "   // checkpoint rows: the chunk sweep 2 re-runs and walks backwards\n";
+   if (!(v.flags & FZ_VF_STATES)) o << "#define FZ_LOSS " << ((v.flags & FZ_VF_ADJOINT_LOSS) ? 1 : 0) << "   // 1: dL/dy is formed in the kernel, from a target (the squared-error loss)\n";
    if (v.flags & FZ_VF_ADJOINT_SM) o << "#define FZ_R " << v.P << "   // rows per LDS patch of the stream-major frames\n";
    o << "#define FZ_BLOCK " << v.block << "\n";
    o << "#define FZ_KERNEL " << kernel_symbol(g, v) << "\n";
@@ -1158,7 +1156,7 @@ RingLayout ring_layout(const Graph& g)
 // rule 2 reads the row's slot and resets it to -0.0f, the pending adjoints the step's reads add into are loaded together behind that
 // (a read at the full depth finds the slot just reset), receive rule 3's additions in registers in its order and are stored once.
 // Without it -- every ring-free graph -- the text is byte for byte what it was.
-// loss and ring (fz_kernel_adjoint_ring_loss.hip.inc): out() takes rv as well -- a delayed read of a ring line is rv[read] there too.
+// loss and ring (fz_kernel_adjoint_ring.hip.inc with FZ_LOSS): out() takes rv as well -- a delayed read of a ring line is rv[read] there too.
 std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
 {
    std::ostringstream o;

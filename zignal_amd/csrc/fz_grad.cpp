@@ -1,25 +1,19 @@
-// The backward of a block (include/flowz_hip.h: fz_run_block_grad, fz_run_block_grad_stream_major): what the adjoint kernels support,
-// their checkpoint stride, patch length and workspace, argument checks and the launch.  The kernel text is fz_kernel_adjoint.hip.inc
-// (time-major frames) or fz_kernel_adjoint_sm.hip.inc (stream-major buffers) plus gen_adjoint_body (fz_codegen.cpp); the code objects
-// go through the kernel cache as a Variant with FZ_VF_ADJOINT (and FZ_VF_ADJOINT_SM).
-// The backward under a squared-error loss (fz_run_block_loss_grad, fz_run_block_loss_grad_stream_major) is the same call with dL/dy
-// formed in the kernel from a target: FZ_VF_ADJOINT_LOSS on the Variant, fz_kernel_adjoint_loss.hip.inc / fz_kernel_adjoint_loss_sm.hip.inc.
-// The backward of a whole recording (fz_run_recording_grad, fz_run_recording_loss_grad) is two-level checkpointing over those: one
-// launch of the block-start-states kernel (FZ_VF_STATES; fz_kernel_states.hip.inc / fz_kernel_states_sm.hip.inc), then the launches
-// above block by block from the last to the first.
-// The backward of a block whose graph has delay lines in LDS (fz_run_block_ring_grad) is a call family of its own, time-major and plain:
-// FZ_VF_ADJOINT_RING on the Variant, fz_kernel_adjoint_ring.hip.inc, gen_adjoint_body in ring mode.  It shares the argument checks and
-// the launch with the calls above; for a graph without such a line it IS fz_run_block_grad.  Under the squared-error loss
-// (fz_run_block_ring_loss_grad) it is that family's call with FZ_VF_ADJOINT_LOSS next to the ring bit: fz_kernel_adjoint_ring_loss.hip.inc,
-// the ring kernel's C, block and workspace; for a graph without such a line it IS fz_run_block_loss_grad.
-// On stream-major buffers (fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major) the ring backward is
-// FZ_VF_ADJOINT_SM next to the ring bit: fz_kernel_adjoint_ring_sm.hip.inc / fz_kernel_adjoint_ring_loss_sm.hip.inc, the ring kernel's C
-// and workspace, a workgroup and a patch length chosen together (ring_sm_geometry); for a graph without such a line it IS
-// fz_run_block_grad_stream_major / fz_run_block_loss_grad_stream_major.
-// The backward of a whole recording of such a graph (fz_run_recording_ring_grad, fz_run_recording_ring_loss_grad) is run_recording with
-// the ring family's pieces: the ring states kernel (FZ_VF_STATES next to the ring bit; fz_kernel_states_ring.hip.inc), the ring
-// launches per block, a block length and a workspace that count the tape; for a graph without such a line it IS the time-major
-// fz_run_recording_grad / fz_run_recording_loss_grad.
+// The backward (include/flowz_hip.h): what the adjoint kernels support, their checkpoint stride, workgroup, patch length and workspace,
+// the argument checks and the launch.  One family of kernels, each a Variant with FZ_VF_ADJOINT that goes through the kernel cache
+// (fz_codegen.cpp: the family's table, gen_adjoint_config, gen_adjoint_body):
+//
+//                                                     time-major frames                 stream-major buffers (FZ_VF_ADJOINT_SM)
+//   fz_run_block_grad[_stream_major]                  fz_kernel_adjoint.hip.inc         fz_kernel_adjoint_sm.hip.inc
+//   fz_run_block_ring_grad[_stream_major]             fz_kernel_adjoint_ring.hip.inc    fz_kernel_adjoint_ring_sm.hip.inc
+//     (delay lines in LDS: FZ_VF_ADJOINT_RING)
+//   fz_run_recording_grad: the block-start states     fz_kernel_states.hip.inc          fz_kernel_states_sm.hip.inc
+//     (FZ_VF_STATES)
+//   fz_run_recording_ring_grad: the same              fz_kernel_states_ring.hip.inc     not built
+//
+// Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the four adjoint kernels forms dL/dy itself, from a
+// target: the same text with FZ_LOSS, the same C, workgroup and workspace.  The ring calls share the checks and the launch with the
+// others; for a graph without a ring line each IS its plain sibling (same Variant, kernel, symbol, workspace, bits).  The backward of a
+// recording is two-level checkpointing: one launch of the states kernel, then the block launches above from the last block to the first.
 #include <cmath>
 #include <algorithm>
 #include <cstddef>
@@ -54,13 +48,15 @@ std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds)
    return "";
 }
 
-// The chunk of sweep 2 keeps C steps of state and frame in registers, (n_state + n_in) * C floats, next to one step's node values
-// and the accumulators: at most 64 saved floats, 16 rows at most.  Measured: no graph of tests/test_grad_host.py spills; random graphs
+// The chunk of sweep 2 keeps C rows of saved floats in registers next to one step's node values and the accumulators: at most 64 saved
+// floats, 16 rows at most.  A row saves its state and frame, n_state + n_in floats; in the ring kernels its register state rows, frame and
+// ring reads (for a graph without a ring line the two count the same).  Measured: no graph of tests/test_grad_host.py spills; random graphs
 // (tests/grad_fuzz_cells.py) do spill SGPRs into VGPR lanes -- one-state graphs at C = 16 as well as 72-state ones at C = 1, with two
 // coefficients as with twenty, so counting n_const here removes nothing -- and none uses scratch: correct, slower.
-uint32_t grad_default_checkpoint(const Graph& g)
+static uint32_t grad_default_checkpoint(const Graph& g, bool ring)
 {
-   const uint32_t per_row = std::max<uint32_t>(g.n_state + g.n_in, 1);
+   const RingLayout rl = ring ? ring_layout(g) : RingLayout{};
+   const uint32_t per_row = std::max<uint32_t>(ring ? rl.n_reg() + g.n_in + rl.n_rr() : g.n_state + g.n_in, 1);
    uint32_t C = 16;
    while (C > 1 && C * per_row > 64) C /= 2;
    return C;
@@ -73,32 +69,13 @@ uint32_t grad_default_checkpoint(const Graph& g)
 // two) and of 4.  A 1-in / 1-out graph: R = 32, 17 KB per wave, 68 KB per workgroup.
 constexpr uint32_t kLdsBytes = 160u * 1024u;   // per CU and the most one workgroup may declare (gfx950)
 static uint32_t sm_patch_bytes(const Graph& g, uint32_t R) { return (R * (g.n_in + g.n_out) + 4u) * 4u * kGradBlock; }
-uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C)
+static uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C)
 {
    const uint32_t wide = std::max<uint32_t>(std::max(g.n_in, g.n_out), 1), narrow = std::max<uint32_t>(g.n_in && g.n_out ? std::min(g.n_in, g.n_out) : wide, 1);
    uint32_t R = 4;
    while (R * wide < 32) R *= 2;
    while (R * narrow < 32 && sm_patch_bytes(g, 2 * R) <= kLdsBytes / 2) R *= 2;
    return std::max(R, C);
-}
-
-// the longest patch any graph can have: the largest power of two R whose patch of ONE wire in all, (R + 4) floats per lane, fits
-// the LDS of a workgroup (128 on gfx950)
-uint32_t grad_sm_max_patch_rows()
-{
-   uint32_t R = 4;
-   while ((2u * R * 1u + 4u) * 4u * kGradBlock <= kLdsBytes) R *= 2;   // (does the next power of two still fit?)
-   return R;
-}
-
-// could adjoint_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
-bool adjoint_variant_fits(const Graph& g, const Variant& v)
-{
-   if (!(v.flags & FZ_VF_ADJOINT) || (v.flags & ~(FZ_VF_ADJOINT | FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_LOSS)) || !grad_unsupported_reason(g).empty()) return false;
-   if ((v.flags & FZ_VF_ADJOINT_LOSS) && g.n_out == 0) return false;                       // (a loss kernel compares outputs)
-   if (v.block != kGradBlock || v.U == 0 || v.U > kGradMaxCheckpoint || (v.U & (v.U - 1))) return false;
-   if (!(v.flags & FZ_VF_ADJOINT_SM)) return v.P == 1;
-   return v.P >= 4 && !(v.P & (v.P - 1)) && v.P % v.U == 0 && v.P <= grad_sm_max_patch_rows() && sm_patch_bytes(g, v.P) <= kLdsBytes;
 }
 
 // The block-start-states kernel (FZ_VF_STATES): U, the rows of one unrolled group -- two groups of U * n_in frame registers are alive
@@ -115,30 +92,11 @@ static uint32_t states_unroll(const Graph& g)
 // whole 128-byte cache line (32 rows for one input wire: 9 KB per wave, 36 KB per workgroup); a multiple of U, which is at most 8
 // and at most 16 / n_in.
 static uint32_t states_sm_patch_bytes(const Graph& g, uint32_t R) { return g.n_in ? (R * g.n_in + 4u) * 4u * kGradBlock : 0u; }
-uint32_t states_sm_patch_rows(const Graph& g)
+static uint32_t states_sm_patch_rows(const Graph& g)
 {
    uint32_t R = 4;
    while (R * g.n_in < 32 && g.n_in) R *= 2;
    return R;
-}
-
-static Variant states_variant_unchecked(const Graph& g, bool stream_major)
-{
-   Variant v;
-   v.P = stream_major ? states_sm_patch_rows(g) : 1;       // (the patch rows travel in P, as for the adjoint kernel)
-   v.U = stream_major ? std::min(states_unroll(g), v.P) : states_unroll(g);
-   v.block = kGradBlock;
-   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | (stream_major ? FZ_VF_ADJOINT_SM : 0u);
-   return v;
-}
-
-// could states_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
-bool states_variant_fits(const Graph& g, const Variant& v)
-{
-   if ((v.flags & ~FZ_VF_ADJOINT_SM) != (FZ_VF_ADJOINT | FZ_VF_STATES) || !grad_unsupported_reason(g).empty()) return false;
-   const bool sm = (v.flags & FZ_VF_ADJOINT_SM) != 0;
-   const Variant w = states_variant_unchecked(g, sm);
-   return v.P == w.P && v.U == w.U && v.block == w.block && (!sm || states_sm_patch_bytes(g, v.P) <= kLdsBytes);
 }
 
 // ---- the ring backward (fz_run_block_ring_grad): its scope, checkpoint stride, workgroup and workspace, each at home here ---------------
@@ -147,17 +105,6 @@ static bool has_ring_line(const Graph& g)
    for (const Line& L : g.lines)
       if (L.in_lds) return true;
    return false;
-}
-
-// A chunk of the ring kernel's sweep 2 keeps C (n_register_state + n_in + n_ring_reads) floats in registers: the rule of
-// grad_default_checkpoint over what THIS kernel saves per row (for a graph without a ring line the two count the same).
-static uint32_t ring_default_checkpoint(const Graph& g)
-{
-   const RingLayout rl = ring_layout(g);
-   const uint32_t per_row = std::max<uint32_t>(rl.n_reg() + g.n_in + rl.n_rr(), 1);
-   uint32_t C = 16;
-   while (C > 1 && C * per_row > 64) C /= 2;
-   return C;
 }
 
 static uint64_t ring_lds_bytes(const RingLayout& rl, uint32_t block) { return (uint64_t)rl.slots * block * 4u; }
@@ -175,16 +122,23 @@ static uint32_t ring_block(const RingLayout& rl)
 
 static uint32_t checkpoint_of(const Graph& g, uint32_t checkpoint_rows, bool ring = false)
 {
-   if (checkpoint_rows == 0) return ring ? ring_default_checkpoint(g) : grad_default_checkpoint(g);
+   if (checkpoint_rows == 0) return grad_default_checkpoint(g, ring);
    if (checkpoint_rows > kGradMaxCheckpoint || (checkpoint_rows & (checkpoint_rows - 1)))
       fail(FZ_E_INVALID, "checkpoint_rows must be 0 (library default) or a power of two <= 32");
    return checkpoint_rows;
 }
 
-static void require_supported(const Graph& g)
+static void require_supported(const Graph& g, bool rings_in_lds = false)
 {
-   const std::string why = grad_unsupported_reason(g);
+   const std::string why = grad_unsupported_reason(g, rings_in_lds);
    if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
+}
+
+// the flag set of an adjoint Variant: the one place that refuses a loss on a graph without outputs
+static uint32_t adjoint_flags(const Graph& g, uint32_t family_bits, bool loss)
+{
+   if (loss && g.n_out == 0) fail(FZ_E_INVALID, "the graph has no output wires: a loss has nothing to compare");
+   return FZ_VF_ADJOINT | family_bits | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
 }
 
 static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool stream_major = false, bool loss = false)
@@ -194,8 +148,7 @@ static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool st
    v.P = 1;
    v.U = checkpoint_of(g, checkpoint_rows);
    v.block = kGradBlock;
-   v.flags = FZ_VF_ADJOINT | (stream_major ? FZ_VF_ADJOINT_SM : 0u) | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
-   if (loss && g.n_out == 0) fail(FZ_E_INVALID, "the graph has no output wires: a loss has nothing to compare");
+   v.flags = adjoint_flags(g, stream_major ? FZ_VF_ADJOINT_SM : 0u, loss);
    if (stream_major) v.P = grad_sm_patch_rows(g, v.U);      // (the patch rows travel in P: codegen puts them into FZ_R and the symbol)
    if (stream_major && sm_patch_bytes(g, v.P) > kLdsBytes)
       fail(FZ_E_UNSUPPORTED, "stream-major backward: a patch of " + std::to_string(v.U) + " checkpoint rows of " + std::to_string(g.n_in + g.n_out) +
@@ -207,8 +160,7 @@ static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool st
 // loss: the kernel forms dL/dy itself (FZ_VF_ADJOINT_LOSS next to the ring bit); C, block and workspace do not change with it
 static Variant ring_adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool loss = false)
 {
-   const std::string why = grad_unsupported_reason(g, true);
-   if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
+   require_supported(g, true);
    if (!has_ring_line(g)) return adjoint_variant(g, checkpoint_rows, false, loss);
    const RingLayout rl = ring_layout(g);
    Variant v;
@@ -218,18 +170,8 @@ static Variant ring_adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bo
       fail(FZ_E_UNSUPPORTED, "the adjoint rings of the delay lines deeper than 8 samples, " + std::to_string(ring_lds_bytes(rl, 64)) + " bytes per 64 lanes (" +
                                 std::to_string(rl.slots) + " samples), do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup");
    v.U = checkpoint_of(g, checkpoint_rows, true);
-   v.flags = FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
-   if (loss && g.n_out == 0) fail(FZ_E_INVALID, "the graph has no output wires: a loss has nothing to compare");
+   v.flags = adjoint_flags(g, FZ_VF_ADJOINT_RING, loss);
    return v;
-}
-
-// could ring_adjoint_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
-bool ring_adjoint_variant_fits(const Graph& g, const Variant& v)
-{
-   if ((v.flags & ~FZ_VF_ADJOINT_LOSS) != (FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING) || !grad_unsupported_reason(g, true).empty() || !has_ring_line(g)) return false;
-   if ((v.flags & FZ_VF_ADJOINT_LOSS) && g.n_out == 0) return false;                       // (a loss kernel compares outputs)
-   if (v.P != 1 || v.U == 0 || v.U > kGradMaxCheckpoint || (v.U & (v.U - 1))) return false;
-   return v.block != 0 && v.block == ring_block(ring_layout(g));
 }
 
 // ---- the ring backward on stream-major buffers: rings and patches share the LDS of a workgroup ----------------------------------------
@@ -262,15 +204,13 @@ static RingSmGeometry ring_sm_geometry(const Graph& g, const RingLayout& rl, uin
 // (same kernel, symbol, workspace, bits); with one, the ring kernel's C and {P = R, block} of ring_sm_geometry
 static Variant ring_sm_adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool loss = false)
 {
-   const std::string why = grad_unsupported_reason(g, true);
-   if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
+   require_supported(g, true);
    if (!has_ring_line(g)) return adjoint_variant(g, checkpoint_rows, true, loss);
    const RingLayout rl = ring_layout(g);
    if (!ring_block(rl)) (void)ring_adjoint_variant(g, checkpoint_rows, loss);   // (the refusal of fz_program_ring_grad_check, in its words)
    Variant v;
    v.U = checkpoint_of(g, checkpoint_rows, true);
-   v.flags = FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
-   if (loss && g.n_out == 0) fail(FZ_E_INVALID, "the graph has no output wires: a loss has nothing to compare");
+   v.flags = adjoint_flags(g, FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, loss);
    const RingSmGeometry geo = ring_sm_geometry(g, rl, v.U);
    if (!geo.block) {
       const uint32_t Rmin = std::max<uint32_t>(4u, v.U);
@@ -283,23 +223,21 @@ static Variant ring_sm_adjoint_variant(const Graph& g, uint32_t checkpoint_rows,
    return v;
 }
 
-// could ring_sm_adjoint_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it
-// builds)  Exactly what the rule makes for this graph and C: block, R and the flag set.
-bool ring_sm_adjoint_variant_fits(const Graph& g, const Variant& v)
+// the Variant of a block's backward, whichever call asks
+static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring, bool stream_major, bool loss)
 {
-   if ((v.flags & ~FZ_VF_ADJOINT_LOSS) != (FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM) || !grad_unsupported_reason(g, true).empty() || !has_ring_line(g)) return false;
-   if ((v.flags & FZ_VF_ADJOINT_LOSS) && g.n_out == 0) return false;                       // (a loss kernel compares outputs)
-   if (v.U == 0 || v.U > kGradMaxCheckpoint || (v.U & (v.U - 1))) return false;
-   const RingLayout rl = ring_layout(g);
-   if (!ring_block(rl)) return false;
-   const RingSmGeometry geo = ring_sm_geometry(g, rl, v.U);
-   return geo.block != 0 && v.block == geo.block && v.P == geo.R;
+   if (!ring) return adjoint_variant(g, checkpoint_rows, stream_major, loss);
+   return stream_major ? ring_sm_adjoint_variant(g, checkpoint_rows, loss) : ring_adjoint_variant(g, checkpoint_rows, loss);
 }
 
 static Variant states_variant(const Graph& g, bool stream_major)
 {
    require_supported(g);
-   const Variant v = states_variant_unchecked(g, stream_major);
+   Variant v;
+   v.P = stream_major ? states_sm_patch_rows(g) : 1;       // (the patch rows travel in P, as for the adjoint kernel)
+   v.U = stream_major ? std::min(states_unroll(g), v.P) : states_unroll(g);
+   v.block = kGradBlock;
+   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | (stream_major ? FZ_VF_ADJOINT_SM : 0u);
    if (stream_major && states_sm_patch_bytes(g, v.P) > kLdsBytes)
       fail(FZ_E_UNSUPPORTED, "stream-major recording: a patch of " + std::to_string(v.P) + " rows of " + std::to_string(g.n_in) +
                                 " input wires does not fit the LDS of a workgroup");
@@ -320,11 +258,19 @@ static Variant ring_states_variant(const Graph& g)
    return v;
 }
 
-// could ring_states_variant have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
-bool ring_states_variant_fits(const Graph& g, const Variant& v)
+// Could the backward have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
+// The family bits name the maker; v fits when that maker, asked for v's own stride, makes exactly v.  So nothing fits that no maker
+// makes: another bit, U = 0 (the maker answers with the default stride), a ring bit on a graph without a ring line (the ring makers
+// hand over to the plain ones), the loss or ring + stream-major next to FZ_VF_STATES.
+bool grad_variant_fits(const Graph& g, const Variant& v)
 {
-   if (v.flags != (FZ_VF_ADJOINT | FZ_VF_STATES | FZ_VF_ADJOINT_RING) || !grad_unsupported_reason(g, true).empty() || !has_ring_line(g)) return false;
-   return v.P == 1 && v.U == states_unroll(g) && v.block != 0 && v.block == ring_block(ring_layout(g));
+   const bool ring = v.flags & FZ_VF_ADJOINT_RING, sm = v.flags & FZ_VF_ADJOINT_SM, loss = v.flags & FZ_VF_ADJOINT_LOSS;
+   try {
+      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss) : ring ? ring_states_variant(g) : states_variant(g, sm);
+      return w.P == v.P && w.U == v.U && w.block == v.block && w.flags == v.flags;
+   } catch (const Error&) {
+      return false;                                         // (a graph, a stride or a patch the call refuses)
+   }
 }
 
 static bool layout_is_stream_major(uint32_t layout)
@@ -383,8 +329,8 @@ static uint32_t ring_recording_block_rows(const Graph& g, uint32_t T, uint32_t C
 // bytes of the block-start states, [ceil(T / B)][n_state][n_streams] floats: the head of a recording's workspace
 static uint64_t starts_bytes(const Graph& g, uint64_t n_streams, uint32_t T, uint32_t B) { return (((uint64_t)T + B - 1) / B) * g.n_state * n_streams * 4u; }
 
-// kernarg image of `struct fz_states_args` (fz_kernel_states.hip.inc) up to the coefficient tail; `struct fz_states_sm_args`
-// (fz_kernel_states_sm.hip.inc) has rows_total and row0 behind it
+// kernarg image of `struct fz_states_args` (fz_kernel_states.hip.inc) up to the coefficient tail; the stream-major text has the
+// window (SmWindow) behind it
 struct StatesArgsHeader {
    const float* in;
    const float* state;
@@ -397,7 +343,8 @@ struct StatesArgsHeader {
 };
 static_assert(sizeof(StatesArgsHeader) == 5 * 8 + 8 + 2 * 4, "StatesArgsHeader must match the head of the kernel's fz_states_args without padding");
 
-// kernarg image of `struct fz_adj_args` (fz_kernel_adjoint.hip.inc) up to the coefficient tail
+// kernarg image of `struct fz_adj_args` without FZ_LOSS (fz_kernel_adjoint.hip.inc; the ring text has the same layout) up to the
+// coefficient tail; the stream-major texts have the window (SmWindow) behind it
 struct AdjArgsHeader {
    const float* in;
    const float* state;
@@ -415,17 +362,8 @@ struct AdjArgsHeader {
 };
 static_assert(sizeof(AdjArgsHeader) == 10 * 8 + 8 + 2 * 4, "AdjArgsHeader must match the head of the kernel's fz_adj_args without padding");
 
-// kernarg image of `struct fz_adj_sm_args` (fz_kernel_adjoint_sm.hip.inc) up to the coefficient tail
-struct AdjSmArgsHeader {
-   AdjArgsHeader tm;
-   unsigned int rows_total;
-   unsigned int row0;
-};
-static_assert(sizeof(AdjSmArgsHeader) == sizeof(AdjArgsHeader) + 2 * 4, "AdjSmArgsHeader must match the head of the kernel's fz_adj_sm_args without padding");
-
-// kernarg image of `struct fz_adj_loss_args` (fz_kernel_adjoint_loss.hip.inc) up to the coefficient tail: it ends in one float, and
-// the first kAdjLossHeaderBytes of it are what the kernel's struct holds there; `struct fz_adj_loss_sm_args`
-// (fz_kernel_adjoint_loss_sm.hip.inc) has rows_total and row0 behind them
+// the same with FZ_LOSS: it ends in one float, and the first kAdjLossHeaderBytes of it are what the kernel's struct holds there; the
+// stream-major texts have the window behind them
 struct AdjLossArgsHeader {
    const float* in;
    const float* state;
@@ -445,12 +383,13 @@ struct AdjLossArgsHeader {
    float grad_scale;
 };
 constexpr size_t kAdjLossHeaderBytes = offsetof(AdjLossArgsHeader, grad_scale) + sizeof(float);
-static_assert(kAdjLossHeaderBytes == 12 * 8 + 8 + 2 * 4 + 4, "AdjLossArgsHeader must match the head of the kernel's fz_adj_loss_args without padding");
+static_assert(kAdjLossHeaderBytes == 12 * 8 + 8 + 2 * 4 + 4, "AdjLossArgsHeader must match the head of the kernel's fz_adj_args under FZ_LOSS without padding");
 
 // the window of a stream-major launch: rows [row0, row0 + n_samples) of buffers [n_streams][rows_total][wire]; null: time-major frames
 struct SmWindow {
    uint32_t rows_total, row0;
 };
+static_assert(sizeof(SmWindow) == 2 * sizeof(unsigned int), "SmWindow is the kernels' rows_total and row0");
 
 // the arguments of a backward, whichever struct they came in: fz_grad_args gives dL/dy (`ybar`), fz_loss_grad_args the target in its
 // place and what the squared-error rule needs (`loss_rule`)
@@ -505,8 +444,7 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
 {
    const GradCall* const a = &call;
    const Graph& g = p->g;
-   const Variant v = a->ring ? (sm ? ring_sm_adjoint_variant(g, a->checkpoint_rows, a->loss_rule) : ring_adjoint_variant(g, a->checkpoint_rows, a->loss_rule))
-                             : adjoint_variant(g, a->checkpoint_rows, sm != nullptr, a->loss_rule);
+   const Variant v = block_variant(g, a->checkpoint_rows, a->ring, sm != nullptr, a->loss_rule);
    *vout = v;
    if (n_streams == 0 || n_samples == 0) return false;     // an empty block: nothing to differentiate, nothing touched
    if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
@@ -563,33 +501,18 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
    return true;
 }
 
-// the launch of a checked backward (a device is at hand)
-static void launch_grad(fz_program* p, const Variant& v, const GradCall& call, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm)
+// The launch of a kernel of the family (a device is at hand).  Its argument struct is the header image, the window of a stream-major launch
+// behind it, then the coefficient tail (read under p->mu); its size is 8-byte aligned -- a buffer of another size does not launch it.
+static void launch_family(fz_program* p, const Variant& v, const void* header, size_t header_bytes, const SmWindow* sm, uint64_t n_streams, void* stream)
 {
-   const GradCall* const a = &call;
    const Graph& g = p->g;
    void* fn = nullptr;
    (void)get_kernel(p, v, &fn);
-   // (the size of the kernel's argument struct: 8-byte aligned -- a buffer of another size does not launch that struct)
-   const size_t hbytes = a->loss_rule ? kAdjLossHeaderBytes + (sm ? 2 * sizeof(unsigned int) : 0) : sm ? sizeof(AdjSmArgsHeader) : sizeof(AdjArgsHeader);
+   const size_t hbytes = header_bytes + (sm ? sizeof *sm : 0);
    const size_t kbytes = (hbytes + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
    std::vector<char> kbuf(kbytes, 0);
-   const unsigned int n_chunks = (unsigned int)((n_samples + (uint64_t)v.U - 1) / v.U);
-   const AdjArgsHeader h{a->in,      a->state,       a->params,     a->ybar, a->state_grad, a->in_grad,
-                         a->state0_grad, a->param_grad, a->const_grad, static_cast<float*>(a->workspace), (unsigned long long)n_streams, n_samples, n_chunks};
-   if (a->loss_rule) {
-      const AdjLossArgsHeader hl{a->in, a->state, a->params, a->ybar, a->state_grad, a->in_grad, a->state0_grad, a->param_grad, a->const_grad,
-                                 static_cast<float*>(a->workspace), a->loss, a->out, (unsigned long long)n_streams, n_samples, n_chunks, a->grad_scale};
-      std::memcpy(kbuf.data(), &hl, kAdjLossHeaderBytes);
-      if (sm) {
-         const unsigned int win[2] = {sm->rows_total, sm->row0};
-         std::memcpy(kbuf.data() + kAdjLossHeaderBytes, win, sizeof win);
-      }
-   } else if (sm) {
-      const AdjSmArgsHeader hs{h, sm->rows_total, sm->row0};
-      std::memcpy(kbuf.data(), &hs, sizeof hs);
-   } else
-      std::memcpy(kbuf.data(), &h, sizeof h);
+   std::memcpy(kbuf.data(), header, header_bytes);
+   if (sm) std::memcpy(kbuf.data() + header_bytes, sm, sizeof *sm);
    {
       std::lock_guard<std::mutex> lock(p->mu);
       if (!g.consts.empty()) std::memcpy(kbuf.data() + hbytes, g.consts.data(), sizeof(float) * g.consts.size());
@@ -598,6 +521,22 @@ static void launch_grad(fz_program* p, const Variant& v, const GradCall& call, u
    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
    const unsigned grid = (unsigned)((n_streams + v.block - 1) / v.block);
    FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+}
+
+// the launch of a checked backward
+static void launch_grad(fz_program* p, const Variant& v, const GradCall& a, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm)
+{
+   float* const ws = static_cast<float*>(a.workspace);
+   const unsigned int n_chunks = (unsigned int)((n_samples + (uint64_t)v.U - 1) / v.U);
+   if (a.loss_rule) {
+      const AdjLossArgsHeader h{a.in, a.state, a.params, a.ybar, a.state_grad, a.in_grad, a.state0_grad, a.param_grad, a.const_grad, ws,
+                                a.loss, a.out, (unsigned long long)n_streams, n_samples, n_chunks, a.grad_scale};
+      launch_family(p, v, &h, kAdjLossHeaderBytes, sm, n_streams, stream);
+   } else {
+      const AdjArgsHeader h{a.in, a.state, a.params, a.ybar, a.state_grad, a.in_grad, a.state0_grad, a.param_grad, a.const_grad, ws,
+                            (unsigned long long)n_streams, n_samples, n_chunks};
+      launch_family(p, v, &h, sizeof h, sm, n_streams, stream);
+   }
 }
 
 static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uint32_t n_samples, void* stream, const SmWindow* sm = nullptr)
@@ -613,26 +552,8 @@ static int run_grad(fz_program* p, const GradCall& call, uint64_t n_streams, uin
 static void launch_states(fz_program* p, const Variant& v, const GradCall& a, float* starts, float* state_out, uint64_t n_streams, uint32_t n_samples,
                           uint32_t B, void* stream, const SmWindow* sm)
 {
-   const Graph& g = p->g;
-   void* fn = nullptr;
-   (void)get_kernel(p, v, &fn);
-   const size_t hbytes = sizeof(StatesArgsHeader) + (sm ? 2 * sizeof(unsigned int) : 0);
-   const size_t kbytes = (hbytes + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
-   std::vector<char> kbuf(kbytes, 0);
    const StatesArgsHeader h{a.in, a.state, a.params, starts, state_out, (unsigned long long)n_streams, n_samples, B};
-   std::memcpy(kbuf.data(), &h, sizeof h);
-   if (sm) {
-      const unsigned int win[2] = {sm->rows_total, sm->row0};
-      std::memcpy(kbuf.data() + sizeof h, win, sizeof win);
-   }
-   {
-      std::lock_guard<std::mutex> lock(p->mu);
-      if (!g.consts.empty()) std::memcpy(kbuf.data() + hbytes, g.consts.data(), sizeof(float) * g.consts.size());
-   }
-   size_t size = kbytes;
-   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-   const unsigned grid = (unsigned)((n_streams + v.block - 1) / v.block);
-   FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+   launch_family(p, v, &h, sizeof h, sm, n_streams, stream);
 }
 
 static uint64_t recording_workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t T, uint32_t B, uint32_t C)
@@ -671,7 +592,7 @@ static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, u
    Variant v;
    {
       // (C is needed for the workspace the checks ask for; adjoint_variant validates checkpoint_rows and the loss's outputs)
-      const Variant v0 = call.ring ? ring_adjoint_variant(g, call.checkpoint_rows, call.loss_rule) : adjoint_variant(g, call.checkpoint_rows, stream_major, call.loss_rule);
+      const Variant v0 = block_variant(g, call.checkpoint_rows, call.ring, stream_major, call.loss_rule);
       const uint32_t B0 = n_samples ? rows_per_block(v0.U) : 0;
       const RecordingCheck rec{call.ring ? ring_recording_workspace_bytes(g, n_streams, n_samples, B0, v0) : recording_workspace_bytes(g, n_streams, n_samples, B0, v0.U), state_out};
       if (!check_grad(p, call, n_streams, n_samples, sm, &v, &rec)) return FZ_OK;
@@ -742,6 +663,28 @@ static long grad_string(fz_program* p, char* buf, size_t cap, Fn make)
    }
 }
 
+// the inspection calls of a kernel of the family, given the maker of its Variant: resources (`fn` names the call in the refusal), symbol, source
+template <class Maker>
+static int grad_resources(fz_program* p, fz_kernel_resources* out, const char* fn, Maker make)
+{
+   FZ_GUARD(
+      if (!p || !out) fail(FZ_E_INVALID, std::string(fn) + ": bad arguments");
+      *out = resources_of(p, make());
+      return FZ_OK;)
+}
+
+template <class Maker>
+static long grad_symbol(fz_program* p, char* buf, size_t cap, Maker make)
+{
+   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, make()); });
+}
+
+template <class Maker>
+static long grad_source(fz_program* p, char* buf, size_t cap, Maker make)
+{
+   return grad_string(p, buf, cap, [&] { return full_source(p->g, make()); });
+}
+
 }  // namespace fz
 
 using namespace fz;
@@ -772,10 +715,7 @@ int fz_program_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel
 
 int fz_program_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
 {
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, "fz_program_grad_resources: bad arguments");
-      *out = resources_of(p, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout)));
-      return FZ_OK;)
+   return grad_resources(p, out, "fz_program_grad_resources", [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout)); });
 }
 
 long fz_program_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
@@ -785,12 +725,12 @@ long fz_program_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char
 
 long fz_program_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout))); });
+   return grad_symbol(p, buf, cap, [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout)); });
 }
 
 long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout))); });
+   return grad_source(p, buf, cap, [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout)); });
 }
 
 int fz_run_block_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
@@ -837,20 +777,17 @@ int fz_program_ring_grad_workspace(const fz_program* p, uint64_t n_streams, uint
 
 int fz_program_ring_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
 {
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_grad_resources: bad arguments");
-      *out = resources_of(p, ring_adjoint_variant(p->g, checkpoint_rows));
-      return FZ_OK;)
+   return grad_resources(p, out, "fz_program_ring_grad_resources", [&] { return ring_adjoint_variant(p->g, checkpoint_rows); });
 }
 
 long fz_program_ring_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_adjoint_variant(p->g, checkpoint_rows)); });
+   return grad_symbol(p, buf, cap, [&] { return ring_adjoint_variant(p->g, checkpoint_rows); });
 }
 
 long fz_program_ring_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_adjoint_variant(p->g, checkpoint_rows)); });
+   return grad_source(p, buf, cap, [&] { return ring_adjoint_variant(p->g, checkpoint_rows); });
 }
 
 int fz_run_block_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
@@ -861,45 +798,34 @@ int fz_run_block_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_stre
       return run_grad(p, call, n_streams, n_samples, hip_stream);)
 }
 
-static Variant ring_variant_for(const Graph& g, uint32_t checkpoint_rows, uint32_t layout, bool loss)
-{
-   return layout_is_stream_major(layout) ? ring_sm_adjoint_variant(g, checkpoint_rows, loss) : ring_adjoint_variant(g, checkpoint_rows, loss);
-}
-
 int fz_program_ring_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
 {
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_grad_resources_for: bad arguments");
-      *out = resources_of(p, ring_variant_for(p->g, checkpoint_rows, layout, false));
-      return FZ_OK;)
+   return grad_resources(p, out, "fz_program_ring_grad_resources_for", [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), false); });
 }
 
 long fz_program_ring_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_variant_for(p->g, checkpoint_rows, layout, false)); });
+   return grad_symbol(p, buf, cap, [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), false); });
 }
 
 long fz_program_ring_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_variant_for(p->g, checkpoint_rows, layout, false)); });
+   return grad_source(p, buf, cap, [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), false); });
 }
 
 int fz_program_ring_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
 {
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_loss_grad_resources_for: bad arguments");
-      *out = resources_of(p, ring_variant_for(p->g, checkpoint_rows, layout, true));
-      return FZ_OK;)
+   return grad_resources(p, out, "fz_program_ring_loss_grad_resources_for", [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), true); });
 }
 
 long fz_program_ring_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_variant_for(p->g, checkpoint_rows, layout, true)); });
+   return grad_symbol(p, buf, cap, [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), true); });
 }
 
 long fz_program_ring_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_variant_for(p->g, checkpoint_rows, layout, true)); });
+   return grad_source(p, buf, cap, [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), true); });
 }
 
 int fz_run_block_ring_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
@@ -924,20 +850,17 @@ int fz_run_block_ring_loss_grad_stream_major(fz_program* p, const fz_loss_grad_a
 
 int fz_program_ring_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
 {
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_loss_grad_resources: bad arguments");
-      *out = resources_of(p, ring_adjoint_variant(p->g, checkpoint_rows, true));
-      return FZ_OK;)
+   return grad_resources(p, out, "fz_program_ring_loss_grad_resources", [&] { return ring_adjoint_variant(p->g, checkpoint_rows, true); });
 }
 
 long fz_program_ring_loss_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_adjoint_variant(p->g, checkpoint_rows, true)); });
+   return grad_symbol(p, buf, cap, [&] { return ring_adjoint_variant(p->g, checkpoint_rows, true); });
 }
 
 long fz_program_ring_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_adjoint_variant(p->g, checkpoint_rows, true)); });
+   return grad_source(p, buf, cap, [&] { return ring_adjoint_variant(p->g, checkpoint_rows, true); });
 }
 
 int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
@@ -991,20 +914,17 @@ int fz_run_recording_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, u
 
 int fz_program_ring_states_resources(fz_program* p, fz_kernel_resources* out)
 {
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, "fz_program_ring_states_resources: bad arguments");
-      *out = resources_of(p, ring_states_variant(p->g));
-      return FZ_OK;)
+   return grad_resources(p, out, "fz_program_ring_states_resources", [&] { return ring_states_variant(p->g); });
 }
 
 long fz_program_ring_states_kernel_symbol(fz_program* p, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, ring_states_variant(p->g)); });
+   return grad_symbol(p, buf, cap, [&] { return ring_states_variant(p->g); });
 }
 
 long fz_program_ring_states_source(fz_program* p, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, ring_states_variant(p->g)); });
+   return grad_source(p, buf, cap, [&] { return ring_states_variant(p->g); });
 }
 
 int fz_program_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
@@ -1044,38 +964,32 @@ int fz_run_recording_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint32
 
 int fz_program_states_resources(fz_program* p, uint32_t layout, fz_kernel_resources* out)
 {
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, "fz_program_states_resources: bad arguments");
-      *out = resources_of(p, states_variant(p->g, layout_is_stream_major(layout)));
-      return FZ_OK;)
+   return grad_resources(p, out, "fz_program_states_resources", [&] { return states_variant(p->g, layout_is_stream_major(layout)); });
 }
 
 long fz_program_states_kernel_symbol(fz_program* p, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, states_variant(p->g, layout_is_stream_major(layout))); });
+   return grad_symbol(p, buf, cap, [&] { return states_variant(p->g, layout_is_stream_major(layout)); });
 }
 
 long fz_program_states_source(fz_program* p, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, states_variant(p->g, layout_is_stream_major(layout))); });
+   return grad_source(p, buf, cap, [&] { return states_variant(p->g, layout_is_stream_major(layout)); });
 }
 
 int fz_program_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
 {
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, "fz_program_loss_grad_resources_for: bad arguments");
-      *out = resources_of(p, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true));
-      return FZ_OK;)
+   return grad_resources(p, out, "fz_program_loss_grad_resources_for", [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true); });
 }
 
 long fz_program_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true)); });
+   return grad_symbol(p, buf, cap, [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true); });
 }
 
 long fz_program_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true)); });
+   return grad_source(p, buf, cap, [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true); });
 }
 
 }  // extern "C"

@@ -186,8 +186,8 @@ constexpr uint32_t FZ_VF_ADJOINT = 1u << 27;
 // (fz_grad.cpp: grad_sm_patch_rows is their one home; the kernel itself runs one stream per lane).
 constexpr uint32_t FZ_VF_ADJOINT_SM = 1u << 18;
 // internal, with FZ_VF_ADJOINT (and optionally FZ_VF_ADJOINT_SM): the adjoint kernel that forms dL/dy itself, from a target and the
-// squared-error rule of fz_run_block_loss_grad (fz_kernel_adjoint_loss.hip.inc, fz_kernel_adjoint_loss_sm.hip.inc: texts and symbols
-// of their own); one more of the reserved bits.  P, U and block mean what they mean for the plain adjoint variant.
+// squared-error rule of fz_run_block_loss_grad (the plain kernel's text with FZ_LOSS, a symbol of its own); one more of the reserved
+// bits.  P, U and block mean what they mean for the plain adjoint variant.
 constexpr uint32_t FZ_VF_ADJOINT_LOSS = 1u << 17;
 // internal, with FZ_VF_ADJOINT (and optionally FZ_VF_ADJOINT_SM): the BLOCK-START-STATES kernel of a recording (fz_grad.cpp:
 // fz_run_recording_grad; fz_kernel_states.hip.inc, fz_kernel_states_sm.hip.inc: texts and symbols of their own), the forward half of
@@ -198,11 +198,11 @@ constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // fz_kernel_adjoint_ring.hip.inc: a text and a symbol of its own, the pending adjoints of the deep lines in an LDS ring); the last of
 // the reserved bits 12 .. 14 that nothing used, so a forward variant naming it stays refused as reserved.  Such a Variant is {P = 1,
 // U = checkpoint rows, block = 256 / 128 / 64 lanes per workgroup}; fz_grad.cpp: ring_adjoint_variant is the one place that makes one.
-// With FZ_VF_ADJOINT_LOSS next to it: the ring kernel that forms dL/dy itself (fz_run_block_ring_loss_grad;
-// fz_kernel_adjoint_ring_loss.hip.inc: one more text and symbol of its own), the same P, U and block.
+// With FZ_VF_ADJOINT_LOSS next to it: the ring kernel that forms dL/dy itself (fz_run_block_ring_loss_grad: the ring kernel's text
+// with FZ_LOSS, one more symbol), the same P, U and block.
 // With FZ_VF_ADJOINT_SM next to it (with or without FZ_VF_ADJOINT_LOSS): the ring kernels for STREAM-MAJOR buffers
-// (fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major; fz_kernel_adjoint_ring_sm.hip.inc,
-// fz_kernel_adjoint_ring_loss_sm.hip.inc: texts and symbols of their own), {P = rows of the LDS patch, U = the ring kernel's checkpoint
+// (fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major; fz_kernel_adjoint_ring_sm.hip.inc: a text of
+// its own, a symbol each), {P = rows of the LDS patch, U = the ring kernel's checkpoint
 // rows, block = 256 / 128 / 64}: rings and patches share the workgroup's LDS, so fz_grad.cpp: ring_sm_geometry chooses P and block
 // together and ring_sm_adjoint_variant is the one place that makes one.
 // With FZ_VF_STATES next to it (and neither FZ_VF_ADJOINT_LOSS nor FZ_VF_ADJOINT_SM: stream-major ring recordings are not built): the block-start-states kernel of a ring recording
@@ -266,7 +266,7 @@ std::string full_source(const Graph& g, const Variant& v);
 std::string gen_adjoint_config(const Graph& g, const Variant& v);
 // loss: also out(), the step's output values (FZ_VF_ADJOINT_LOSS).  ring: the body of fz_kernel_adjoint_ring.hip.inc (FZ_VF_ADJOINT_RING):
 // register rows compact, the lines in LDS read through rv[] and their adjoints kept in an LDS ring; without it the text is unchanged.
-// Both: out() takes rv[] too (fz_kernel_adjoint_ring_loss.hip.inc)
+// Both: out() takes rv[] too (fz_kernel_adjoint_ring.hip.inc with FZ_LOSS)
 std::string gen_adjoint_body(const Graph& g, bool loss = false, bool ring = false);
 // How the ring adjoint kernel lays a graph out (fz_codegen.cpp; the one home of these counts for fz_grad.cpp too): the lines of depth
 // <= 8 keep compact REGISTER rows, every `in_lds` line is a RING LINE with its slots in the lane's LDS column, and the distinct
@@ -290,18 +290,9 @@ bool adjoint_takes(uint32_t kind);
 // why the backward of a block does not support this graph ("" = it does): fz_grad.cpp
 // rings_in_lds: float delay lines in LDS (depth 9 .. 256) are no objection -- the scope of fz_run_block_ring_grad
 std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds = false);
-// the library's default checkpoint stride for the adjoint kernel of this graph (a power of two)
-uint32_t grad_default_checkpoint(const Graph& g);
-// rows per LDS patch of the stream-major adjoint kernel at checkpoint stride C: a multiple of C and of 4 (fz_grad.cpp)
-uint32_t grad_sm_patch_rows(const Graph& g, uint32_t C);
-uint32_t grad_sm_max_patch_rows();                                 // the longest patch any graph can have (one wire, the whole LDS)
-bool adjoint_variant_fits(const Graph& g, const Variant& v);       // an adjoint Variant the backward could have made for this graph
-bool ring_sm_adjoint_variant_fits(const Graph& g, const Variant& v);   // a stream-major ring adjoint Variant (FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, with or without FZ_VF_ADJOINT_LOSS): exactly the block and patch rows fz_run_block_ring_grad_stream_major makes
-bool ring_adjoint_variant_fits(const Graph& g, const Variant& v);  // a ring adjoint Variant (FZ_VF_ADJOINT_RING, with or without FZ_VF_ADJOINT_LOSS) fz_run_block_ring_grad / _ring_loss_grad could have made
-// rows per LDS patch of the stream-major block-start-states kernel (x only), a multiple of 4 and of the unrolled group (fz_grad.cpp)
-uint32_t states_sm_patch_rows(const Graph& g);
-bool states_variant_fits(const Graph& g, const Variant& v);        // a states Variant (FZ_VF_STATES) fz_run_recording_grad could have made
-bool ring_states_variant_fits(const Graph& g, const Variant& v);   // a ring states Variant (FZ_VF_STATES | FZ_VF_ADJOINT_RING) fz_run_recording_ring_grad could have made
+// could the backward have made this Variant of the adjoint family (FZ_VF_ADJOINT and the family bits next to it) for this graph?
+// The flag set names the call; v fits when that call, asked for v's stride, makes exactly v: fz_grad.cpp
+bool grad_variant_fits(const Graph& g, const Variant& v);
 // 16-bit PCM frames (fz_pcm16.cpp): why the PCM kernel does not take this graph ("" = it does), and whether v is a Variant
 // fz_run_block_pcm16 could have made for it
 std::string pcm16_unsupported_reason(const Graph& g);

@@ -1,6 +1,7 @@
-// fz_adjoint_ring_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the ADJOINT of one block whose graph has delay lines deeper
-// than 8 samples (include/flowz_hip.h: fz_run_block_ring_grad).  A sibling of fz_kernel_adjoint.hip.inc: the same two sweeps, the same
-// order of every sum; what differs is where a deep line ("ring line": float, depth D in 9 .. 256) lives.
+// fz_adjoint_ring_kernel / fz_adjoint_ring_loss_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the ADJOINT of one block whose
+// graph has delay lines deeper than 8 samples (include/flowz_hip.h: fz_run_block_ring_grad), and with FZ_LOSS the same UNDER A
+// SQUARED-ERROR LOSS (fz_run_block_ring_loss_grad): dL/dy formed in the kernel instead of read.  A sibling of fz_kernel_adjoint.hip.inc:
+// the same two sweeps, the same order of every sum; what differs is where a deep line ("ring line": float, depth D in 9 .. 256) lives.
 //
 // One lane owns one stream for the whole block (wave64; the workgroups of the last wave are masked by the stream count).  A lane touches
 // only its own LDS column, so there are no barriers and no atomics.
@@ -8,7 +9,9 @@
 //   fwd(x, c, p, s, rv, sn, u)                     the REGISTER state rows after one step and the ring lines' source values u[line],
 //                                                  from the register rows before it, the step's frame and its ring-read values rv[read];
 //   bwd(x, c, p, s, rv, yb, xb, R, pb, cb, ring, pt)   that step re-evaluated, then its adjoint statements in reverse node order;
-//                                                  ring = the lane's LDS column, pt[line] = the row number modulo the line's depth.
+//                                                  ring = the lane's LDS column, pt[line] = the row number modulo the line's depth;
+//   out(x, c, p, s, rv, y)                         FZ_LOSS only: the step's output values (a delayed read of a ring line is rv[...], not
+//                                                  a state row).
 // Lines of depth <= 8 are what they are in fz_kernel_adjoint.hip.inc: state rows in registers (here COMPACT: register row r is the
 // caller's state row fz_reg_row[r]), a checkpoint every FZ_C rows, the chunk re-run and walked backwards.
 //
@@ -24,12 +27,21 @@
 // LDS: ring[slot][lane], FZ_RING_SLOTS (the sum of the depths) x FZ_BLOCK floats; the lanes' dwords lie side by side and the slot is
 // uniform over the wave: ds_read_b32 / ds_write_b32 without bank conflicts.
 //
-// Workspace: [ceil(T / FZ_C)][FZ_NREG][n_streams] checkpoints, then the tape [T][FZ_NRL][n_streams].
-// HBM bytes per stream-sample: 4 (2 n_in + n_out + n_in) + 8 FZ_NREG / FZ_C + 4 FZ_NRL (the tape written) + 4 FZ_NRR (read back).
+// FZ_LOSS: walking row t, sweep 2 holds the row's frame X[j], the register state rows S[j] and the ring-read values RV[j], so the row's
+// outputs y are a few VALU instructions away.  Where the plain kernel reads a dL/dy row, the loss kernel reads the TARGET row and applies
+// the rule of the header, per output slot w in ascending order:  e = y[w] - target[t][w];  ybar[w] = e * grad_scale;  loss = loss + e * e
+// (each operation rounded once, no FMA).  ybar then enters bwd() as the dL/dy row does, so every gradient bit is fz_run_block_ring_grad's
+// for that ybar.  The loss accumulator is one register per lane for the whole block, next to pb / cb: it starts from the caller's
+// loss[stream] and runs over the rows T-1 .. 0 as they do, so blocks chain bitwise.  y leaves for `out` on the way if asked (the bits
+// of fz_run_block).  The loss adds no LDS.
+//
+// Workspace: [ceil(T / FZ_C)][FZ_NREG][n_streams] checkpoints, then the tape [T][FZ_NRL][n_streams] (fz_program_ring_grad_workspace).
+// HBM bytes per stream-sample: 4 (2 n_in + n_out + n_in) + 8 FZ_NREG / FZ_C + 4 FZ_NRL (the tape written) + 4 FZ_NRR (read back; the
+// target read where dL/dy was), + 4 n_out when `out` is asked for.
 //
 // Compiled by hiprtc with the build options of the forward kernels: -ffp-contract=off (no FMA: one rounding per operation),
 // correctly rounded division and square root, denormals kept.
-#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_NREG FZ_NRL FZ_NRR FZ_RING_SLOTS FZ_C FZ_BLOCK
+#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_NREG FZ_NRL FZ_NRR FZ_RING_SLOTS FZ_C FZ_LOSS FZ_BLOCK
                                // FZ_KERNEL and the tables fz_reg_row, fz_rl_row0 / fz_rl_depth / fz_rl_slot0, fz_rr_line / fz_rr_delay
 
 #define FZ_P 1
@@ -37,22 +49,33 @@ typedef float V;
 typedef double VD;
 #define FZ_A(n) ((n) > 0 ? (n) : 1)
 
-#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd }
+#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd; FZ_LOSS: out }
 
 struct fz_adj_ring_args {      // the layout of fz_adj_args (fz_kernel_adjoint.hip.inc): one host-side image serves both
    const float* in;            // [T][n_streams][n_in]
    const float* state;         // [n_state][n_streams]   the state before the block (register and ring lines' rows)
    const float* params;        // [n_param][n_streams]
+#if FZ_LOSS
+   const float* target;        // [T][n_streams][n_out]  what y is compared with
+#else
    const float* out_grad;      // [T][n_streams][n_out]
+#endif
    const float* state_grad;    // [n_state][n_streams]   dL/d(state after the block); null: zero
    float* in_grad;             // [T][n_streams][n_in]   written; null: not computed
    float* state0_grad;         // [n_state][n_streams]   written; null: not computed (may be state_grad)
    float* param_grad;          // [n_param][n_streams]   added to; null: not computed
    float* const_grad;          // [n_const][n_streams]   added to; null: not computed
    float* ckpt;                // [n_chunks][FZ_NREG][n_streams] checkpoints, then [T][FZ_NRL][n_streams] the tape
+#if FZ_LOSS
+   float* loss;                // [n_streams]            the sum of e * e, added to; null: not computed
+   float* out;                 // [T][n_streams][n_out]  y, written; null: not written
+#endif
    unsigned long long n_streams;
    unsigned int n_samples;
    unsigned int n_chunks;      // ceil(n_samples / FZ_C)
+#if FZ_LOSS
+   float grad_scale;           // ybar = (y - target) * grad_scale
+#endif
    float c[FZ_A(FZ_NCONST)];   // the program's uniform coefficients
 };
 
@@ -136,6 +159,10 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_arg
    for (int k = 0; k < FZ_NPARAM; ++k) pb[k] = a.param_grad ? a.param_grad[(size_t)k * ns + s] : 0.f;
 #pragma unroll
    for (int k = 0; k < FZ_NCONST; ++k) cb[k] = a.const_grad ? a.const_grad[(size_t)k * ns + s] : 0.f;
+#if FZ_LOSS
+   float ls = a.loss ? a.loss[s] : 0.f;                  // the stream's loss accumulator, in a register for the whole block
+   const float gk = a.grad_scale;
+#endif
 #pragma unroll
    for (int l = 0; l < FZ_NRL; ++l) {                      // the adjoint rings: the slot of u[T-1-j] holds state_grad[row0 + j], or +0.0f
       const unsigned D = fz_rl_depth[l], top = (T - 1u) % D;
@@ -200,13 +227,31 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_arg
             yb[0] = 0.f;
 #pragma unroll
             for (int l = 0; l < FZ_NRL; ++l) pt[l] = (base[l] + (unsigned)j) % fz_rl_depth[l];
+#if FZ_LOSS
+            float y[FZ_A(FZ_NOUT)];
+            y[0] = 0.f;
+            fz_adj::out(X[j], c, p, S[j], RV[j], y);
+#pragma unroll
+            for (int w = 0; w < FZ_NOUT; ++w) {            // the rule: slots in ascending order, one rounding per operation
+               const float e = y[w] - a.target[(t * ns + s) * FZ_NOUT + w];
+               yb[w] = e * gk;
+               ls = ls + e * e;
+            }
+#else
 #pragma unroll
             for (int w = 0; w < FZ_NOUT; ++w) yb[w] = a.out_grad[(t * ns + s) * FZ_NOUT + w];
+#endif
             fz_adj::bwd(X[j], c, p, S[j], RV[j], yb, xb, R, pb, cb, ring, pt);
             if (a.in_grad) {
 #pragma unroll
                for (int w = 0; w < FZ_NIN; ++w) a.in_grad[(t * ns + s) * FZ_NIN + w] = xb[w];
             }
+#if FZ_LOSS
+            if (a.out) {                                    // (behind bwd(), like dL/dx: a store in front of it cost 60 and more registers)
+#pragma unroll
+               for (int w = 0; w < FZ_NOUT; ++w) a.out[(t * ns + s) * FZ_NOUT + w] = y[w];
+            }
+#endif
          }
    }
    if (a.state0_grad) {
@@ -227,4 +272,7 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_arg
 #pragma unroll
       for (int k = 0; k < FZ_NCONST; ++k) a.const_grad[(size_t)k * ns + s] = cb[k];
    }
+#if FZ_LOSS
+   if (a.loss) a.loss[s] = ls;
+#endif
 }

@@ -1,11 +1,14 @@
-// fz_adjoint_ring_sm_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the ADJOINT of one block whose graph has delay lines
-// deeper than 8 samples, on STREAM-MAJOR buffers (include/flowz_hip.h: fz_run_block_ring_grad_stream_major).  The algorithm, the
-// generated body (fz_codegen.cpp: gen_adjoint_body in ring mode: struct fz_adj { fwd, bwd }) and the order of every operation are
-// those of fz_kernel_adjoint_ring.hip.inc -- one lane per stream, sweep 1 with its value rings in LDS, the checkpoints of the register
-// rows and the tape, sweep 2 with the adjoint rings in the same LDS -- so the bits are the time-major ring kernel's.  How the frames
+// fz_adjoint_ring_sm_kernel / fz_adjoint_ring_loss_sm_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the ADJOINT of one block
+// whose graph has delay lines deeper than 8 samples, on STREAM-MAJOR buffers (include/flowz_hip.h: fz_run_block_ring_grad_stream_major),
+// and with FZ_LOSS the same UNDER A SQUARED-ERROR LOSS (fz_run_block_ring_loss_grad_stream_major).  The algorithm, the generated body
+// (fz_codegen.cpp: gen_adjoint_body in ring mode: struct fz_adj { fwd, bwd; FZ_LOSS: out }), the rule of the loss and the order of
+// every operation are those of fz_kernel_adjoint_ring.hip.inc -- one lane per stream, sweep 1 with its value rings in LDS, the
+// checkpoints of the register rows and the tape, sweep 2 with the adjoint rings in the same LDS -- so the bits are the time-major
+// ring kernel's.  How the frames
 // move is fz_kernel_adjoint_sm.hip.inc's: the 64 lanes of a wave fetch a PATCH of [64 streams][FZ_R rows] as float4 pieces laid along
 // the rows, park them in a wave-private LDS patch and every lane reads its own row back; dL/dx overwrites x in place and leaves as
-// float4 pieces when the patch's chunks are done.
+// float4 pieces when the patch's chunks are done.  FZ_LOSS moves the frames as it does there: the part of the patch behind x carries
+// the TARGET rows where it carried dL/dy, and if `out` is asked for, y overwrites the row's target in place and leaves like dL/dx.
 //
 // Where the two do not simply paste together:
 //   * sweep 1 runs EVERY row of the block, the last chunk too (the stream-major kernel stops before it): the tape needs the last
@@ -20,15 +23,17 @@
 //   * rows [row][n_streams] touched once per launch go through a row stride held per lane (nsv / nse), as in the stream-major kernel;
 //   * sweep 2 requests a chunk's ring reads together before the re-run: tape row t - d, or the caller's state for t < d; x and dL/dy
 //     come from the patch.
-// Masking of a short last patch and a short last chunk: fz_kernel_adjoint_sm.hip.inc's -- no row of in_grad outside the window is written.
+// Masking of a short last patch and a short last chunk: fz_kernel_adjoint_sm.hip.inc's -- no row of in_grad (FZ_LOSS: or of
+// out) outside the window is written.
 //
 // Workspace: [ceil(T / FZ_C)][FZ_NREG][n_streams] checkpoints, then the tape [T][FZ_NRL][n_streams] (fz_program_ring_grad_workspace);
 // tape loads and stores are one coalesced row each.
-// HBM bytes per stream-sample: 4 (2 n_in + n_out + n_in) + 8 FZ_NREG / FZ_C + 4 FZ_NRL + 4 FZ_NRR, as the time-major ring kernel.
+// HBM bytes per stream-sample: 4 (2 n_in + n_out + n_in) + 8 FZ_NREG / FZ_C + 4 FZ_NRL + 4 FZ_NRR, as the time-major ring kernel
+// (+ 4 n_out when `out` is asked for).
 //
 // Compiled by hiprtc with the build options of every other kernel: -ffp-contract=off, correctly rounded division and square root,
 // denormals kept.
-#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_NREG FZ_NRL FZ_NRR FZ_RING_SLOTS FZ_C FZ_R FZ_BLOCK
+#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_NREG FZ_NRL FZ_NRR FZ_RING_SLOTS FZ_C FZ_R FZ_LOSS FZ_BLOCK
                                // FZ_KERNEL and the tables fz_reg_row, fz_rl_row0 / fz_rl_depth / fz_rl_slot0, fz_rr_line / fz_rr_delay
 
 #define FZ_P 1
@@ -36,82 +41,48 @@ typedef float V;
 typedef double VD;
 #define FZ_A(n) ((n) > 0 ? (n) : 1)
 
-#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd }
+#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd; FZ_LOSS: out }
 
 #if (FZ_R % 4) != 0 || (FZ_R % FZ_C) != 0 || (FZ_BLOCK % 64) != 0
 #error "stream-major ring adjoint: the patch is a multiple of the checkpoint stride and of 4 rows, the workgroup whole waves"
 #endif
 #define FZ_AX (FZ_R * FZ_NIN)                 /* floats of x (then of dL/dx) per patch row */
-#define FZ_AY (FZ_R * FZ_NOUT)                /* floats of dL/dy per patch row, behind them */
+#define FZ_AY (FZ_R * FZ_NOUT)                /* floats of dL/dy (FZ_LOSS: of the target, then of y) per patch row, behind them */
 #define FZ_AROW (FZ_AX + FZ_AY + 4)           /* padded patch row */
 #define FZ_API (FZ_AX / 4)                    /* float4 pieces per stream and patch */
 #define FZ_APO (FZ_AY / 4)
 
-#define FZ_AFLIGHT 8                          /* float4 pieces a lane has in flight while a patch part is fetched */
-
-typedef float fz_f4 __attribute__((ext_vector_type(4)));
+//@splice fz_kernel_adjoint_patch.hip.inc
 
 struct fz_adj_ring_sm_args {   // the layout of fz_adj_sm_args (fz_kernel_adjoint_sm.hip.inc): one host-side image serves both
    const float* in;            // [n_streams][rows_total][n_in]
    const float* state;         // [n_state][n_streams]   the state before the block (register and ring lines' rows)
    const float* params;        // [n_param][n_streams]
+#if FZ_LOSS
+   const float* target;        // [n_streams][rows_total][n_out]  what y is compared with
+#else
    const float* out_grad;      // [n_streams][rows_total][n_out]
+#endif
    const float* state_grad;    // [n_state][n_streams]   dL/d(state after the block); null: zero
    float* in_grad;             // [n_streams][rows_total][n_in]   rows of the window written; null: not computed
    float* state0_grad;         // [n_state][n_streams]   written; null: not computed (may be state_grad)
    float* param_grad;          // [n_param][n_streams]   added to; null: not computed
    float* const_grad;          // [n_const][n_streams]   added to; null: not computed
    float* ckpt;                // [n_chunks][FZ_NREG][n_streams] checkpoints, then [T][FZ_NRL][n_streams] the tape
+#if FZ_LOSS
+   float* loss;                // [n_streams]            the sum of e * e, added to; null: not computed
+   float* out;                 // [n_streams][rows_total][n_out]  y, rows of the window written; null: not written
+#endif
    unsigned long long n_streams;
    unsigned int n_samples;
    unsigned int n_chunks;      // ceil(n_samples / FZ_C)
+#if FZ_LOSS
+   float grad_scale;           // ybar = (y - target) * grad_scale
+#endif
    unsigned int rows_total;
    unsigned int row0;
    float c[FZ_A(FZ_NCONST)];   // the program's uniform coefficients
 };
-
-__device__ __forceinline__ void fz_wave_sync()
-{
-   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-   __builtin_amdgcn_wave_barrier();
-   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Piece e = i * 64 + lane of a patch part is piece e % PIECES of patch row e / PIECES: 4 floats at float 4 * (e % PIECES) of that
-// stream's run.  `rows` streams of the wave exist, `nval` floats of every run lie inside the window.
-// global -> patch: `g` the first float of the wave's first run, `gstride` floats from one stream's run to the next.  No branches (a
-// branch per piece of the unrolled loop keeps an exec mask per piece alive in scalar registers): a piece of a missing stream is fetched
-// from the wave's last stream, a piece behind the window's last float from the head of its run, and parked where nobody reads it.
-template <int PIECES>
-__device__ __forceinline__ void fz_adj_fetch(float* part, const float* g, size_t gstride, unsigned rows, unsigned nval, unsigned lane)
-{
-   constexpr unsigned PP = PIECES > 0 ? PIECES : 1;
-#pragma unroll
-   for (int i = 0; i < PIECES; ++i) {
-      const unsigned e = (unsigned)i * 64u + lane, row = e / PP, q = e % PP;
-      const unsigned grow = row < rows ? row : rows - 1u, gq = q * 4u < nval ? q * 4u : 0u;
-      *reinterpret_cast<fz_f4*>(part + row * FZ_AROW + q * 4u) = *reinterpret_cast<const fz_f4*>(g + grow * gstride + gq);
-      // at most FZ_AFLIGHT pieces in flight: the pieces before are parked before the next are fetched
-      if ((i + 1) % FZ_AFLIGHT == 0 && i + 1 < PIECES) asm volatile("" ::: "memory");
-   }
-}
-
-// patch -> global: the whole pieces inside the window as float4; the floats of the piece that straddles the window's last float (at
-// most three) leave one by one, every lane handing over those of its own row
-template <int PIECES>
-__device__ __forceinline__ void fz_adj_flush(const float* part, float* g, size_t gstride, unsigned rows, unsigned nval, unsigned lane)
-{
-   constexpr unsigned PP = PIECES > 0 ? PIECES : 1;
-#pragma unroll
-   for (int i = 0; i < PIECES; ++i) {
-      const unsigned e = (unsigned)i * 64u + lane, row = e / PP, q = e % PP;
-      if (row < rows && q * 4u + 4u <= nval) *reinterpret_cast<fz_f4*>(g + row * gstride + q * 4u) = *reinterpret_cast<const fz_f4*>(part + row * FZ_AROW + q * 4u);
-   }
-   const unsigned whole = nval & ~3u;
-   if (PIECES > 0 && whole != nval && lane < rows) {
-      for (unsigned j = whole; j < nval; ++j) g[lane * gstride + j] = part[lane * FZ_AROW + j];
-   }
-}
 
 extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_args a)
 {
@@ -135,7 +106,12 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_
    // the wave's first run of each buffer: stream s_base, row row0
    const size_t istride = (size_t)a.rows_total * FZ_NIN, ostride = (size_t)a.rows_total * FZ_NOUT;
    const float* const gin = FZ_NIN ? a.in + s_base * istride + (size_t)a.row0 * FZ_NIN : nullptr;
+#if FZ_LOSS
+   const float* const gyb = FZ_NOUT ? a.target + s_base * ostride + (size_t)a.row0 * FZ_NOUT : nullptr;
+   float* const gyo = FZ_NOUT && a.out ? a.out + s_base * ostride + (size_t)a.row0 * FZ_NOUT : nullptr;
+#else
    const float* const gyb = FZ_NOUT ? a.out_grad + s_base * ostride + (size_t)a.row0 * FZ_NOUT : nullptr;
+#endif
    float* const gxb = FZ_NIN && a.in_grad ? a.in_grad + s_base * istride + (size_t)a.row0 * FZ_NIN : nullptr;
 
    // (rows [row][n_streams] that are touched once per launch go through a row stride held per lane: as a scalar, every multiple of it
@@ -167,7 +143,7 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_
       for (unsigned pk = 0; pk < npatch; ++pk) {
          const unsigned r0 = pk * (unsigned)FZ_R, np = T - r0 < (unsigned)FZ_R ? T - r0 : (unsigned)FZ_R;   // rows of this patch (1 .. FZ_R)
          fz_wave_sync();                                     // (the rows of the patch before are read)
-         fz_adj_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+         fz_patch_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
          fz_wave_sync();
          const unsigned nk = (np + (unsigned)FZ_C - 1u) / (unsigned)FZ_C;
          for (unsigned kk = 0; kk < nk; ++kk) {
@@ -218,6 +194,10 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_
    for (int k = 0; k < FZ_NPARAM; ++k) pb[k] = a.param_grad ? a.param_grad[(size_t)k * nsv + s] : 0.f;
 #pragma unroll
    for (int k = 0; k < FZ_NCONST; ++k) cb[k] = a.const_grad ? a.const_grad[(size_t)k * nsv + s] : 0.f;
+#if FZ_LOSS
+   float ls = a.loss ? a.loss[s] : 0.f;                      // the stream's loss accumulator, in a register for the whole block
+   const float gk = a.grad_scale;
+#endif
 #pragma unroll
    for (int l = 0; l < FZ_NRL; ++l) {                      // the adjoint rings: the slot of u[T-1-j] holds state_grad[row0 + j], or +0.0f
       const unsigned D = fz_rl_depth[l], top = (T - 1u) % D;
@@ -229,9 +209,9 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_
    }
    for (unsigned pk = npatch; pk-- > 0;) {
       const unsigned r0 = pk * (unsigned)FZ_R, np = T - r0 < (unsigned)FZ_R ? T - r0 : (unsigned)FZ_R;
-      fz_wave_sync();                                        // (the patch before has left for in_grad)
-      fz_adj_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
-      fz_adj_fetch<FZ_APO>(patch + FZ_AX, gyb + (size_t)r0 * FZ_NOUT, ostride, rows_here, np * FZ_NOUT, lane);
+      fz_wave_sync();                                        // (the patch before has left for in_grad and out)
+      fz_patch_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+      fz_patch_fetch<FZ_APO>(patch + FZ_AX, gyb + (size_t)r0 * FZ_NOUT, ostride, rows_here, np * FZ_NOUT, lane);
       fz_wave_sync();
       const unsigned nk = (np + (unsigned)FZ_C - 1u) / (unsigned)FZ_C;
       for (unsigned kk = nk; kk-- > 0;) {
@@ -241,7 +221,7 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_
          float S[FZ_C][FZ_A(FZ_NREG)], X[FZ_C][FZ_A(FZ_NIN)], RV[FZ_C][FZ_A(FZ_NRR)];
          const float* ck = a.ckpt + (size_t)k * FZ_NREG * ns + s;
          float* const xr = mine + kk * (unsigned)(FZ_C * FZ_NIN);                 // the chunk's x rows, then its dL/dx rows
-         const float* const yr = mine + FZ_AX + kk * (unsigned)(FZ_C * FZ_NOUT);  // its dL/dy rows
+         float* const yr = mine + FZ_AX + kk * (unsigned)(FZ_C * FZ_NOUT);        // its dL/dy rows (FZ_LOSS: its target rows, then its y rows)
 #pragma unroll
          for (int j = 0; j < FZ_C; ++j) {
             S[j][0] = 0.f;
@@ -291,8 +271,24 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_
                yb[0] = 0.f;
 #pragma unroll
                for (int l = 0; l < FZ_NRL; ++l) pt[l] = (base[l] + (unsigned)j) % fz_rl_depth[l];
+#if FZ_LOSS
+               float y[FZ_A(FZ_NOUT)];
+               y[0] = 0.f;
+               fz_adj::out(X[j], c, p, S[j], RV[j], y);
+#pragma unroll
+               for (int w = 0; w < FZ_NOUT; ++w) {         // the rule: slots in ascending order, one rounding per operation
+                  const float e = y[w] - yr[j * FZ_NOUT + w];
+                  yb[w] = e * gk;
+                  ls = ls + e * e;
+               }
+               if (gyo && active) {                          // (the row's target is read: its y takes its place)
+#pragma unroll
+                  for (int w = 0; w < FZ_NOUT; ++w) yr[j * FZ_NOUT + w] = y[w];
+               }
+#else
 #pragma unroll
                for (int w = 0; w < FZ_NOUT; ++w) yb[w] = yr[j * FZ_NOUT + w];
+#endif
                fz_adj::bwd(X[j], c, p, S[j], RV[j], yb, xb, R, pb, cb, ring, pt);
                if (gxb && active) {                          // (the row's x is in X[j]: its dL/dx takes its place)
 #pragma unroll
@@ -300,10 +296,16 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_
                }
             }
       }
+#if FZ_LOSS
+      if (gxb || gyo) fz_wave_sync();
+      if (gxb) fz_patch_flush<FZ_API>(patch, gxb + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+      if (gyo) fz_patch_flush<FZ_APO>(patch + FZ_AX, gyo + (size_t)r0 * FZ_NOUT, ostride, rows_here, np * FZ_NOUT, lane);
+#else
       if (gxb) {
          fz_wave_sync();
-         fz_adj_flush<FZ_API>(patch, gxb + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+         fz_patch_flush<FZ_API>(patch, gxb + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
       }
+#endif
    }
    if (!active) return;
    size_t nse = ns;
@@ -326,4 +328,7 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_adj_ring_sm_
 #pragma unroll
       for (int k = 0; k < FZ_NCONST; ++k) a.const_grad[(size_t)k * nse + s] = cb[k];
    }
+#if FZ_LOSS
+   if (a.loss) a.loss[s] = ls;
+#endif
 }

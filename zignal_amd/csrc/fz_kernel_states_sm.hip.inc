@@ -38,9 +38,7 @@ typedef double VD;
 #define FZ_AROW (FZ_AX + 4)                   /* padded patch row */
 #define FZ_API (FZ_AX / 4)                    /* float4 pieces per stream and patch */
 
-#define FZ_AFLIGHT 8                          /* float4 pieces a lane has in flight while a patch is fetched */
-
-typedef float fz_f4 __attribute__((ext_vector_type(4)));
+//@splice fz_kernel_adjoint_patch.hip.inc   (the fetch is all this kernel uses of it)
 
 struct fz_states_sm_args {
    const float* in;            // [n_streams][rows_total][n_in]
@@ -55,29 +53,6 @@ struct fz_states_sm_args {
    unsigned int row0;
    float c[FZ_A(FZ_NCONST)];   // the program's uniform coefficients
 };
-
-__device__ __forceinline__ void fz_wave_sync()
-{
-   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-   __builtin_amdgcn_wave_barrier();
-   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Piece e = i * 64 + lane of the patch is piece e % PIECES of patch row e / PIECES: 4 floats at float 4 * (e % PIECES) of that
-// stream's run.  `rows` streams of the wave exist, `nval` floats of every run lie inside the window.  `g` is the first float of the
-// wave's first run, `gstride` the floats from one stream's run to the next.  No branches (see above).
-template <int PIECES>
-__device__ __forceinline__ void fz_states_fetch(float* part, const float* g, size_t gstride, unsigned rows, unsigned nval, unsigned lane)
-{
-   constexpr unsigned PP = PIECES > 0 ? PIECES : 1;
-#pragma unroll
-   for (int i = 0; i < PIECES; ++i) {
-      const unsigned e = (unsigned)i * 64u + lane, row = e / PP, q = e % PP;
-      const unsigned grow = row < rows ? row : rows - 1u, gq = q * 4u < nval ? q * 4u : 0u;
-      *reinterpret_cast<fz_f4*>(part + row * FZ_AROW + q * 4u) = *reinterpret_cast<const fz_f4*>(g + grow * gstride + gq);
-      if ((i + 1) % FZ_AFLIGHT == 0 && i + 1 < PIECES) asm volatile("" ::: "memory");   // (the parking rule)
-   }
-}
 
 extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_sm_args a)
 {
@@ -119,7 +94,7 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_sm_ar
       const unsigned r0 = pk * (unsigned)FZ_R, np = T - r0 < (unsigned)FZ_R ? T - r0 : (unsigned)FZ_R;   // rows of this patch (1 .. FZ_R)
 #if FZ_NIN > 0
       fz_wave_sync();                                         // (the rows of the patch before are read)
-      fz_states_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
+      fz_patch_fetch<FZ_API>(patch, gin + (size_t)r0 * FZ_NIN, istride, rows_here, np * FZ_NIN, lane);
       fz_wave_sync();
 #endif
       for (unsigned j0 = 0; j0 < np; j0 += FZ_U) {

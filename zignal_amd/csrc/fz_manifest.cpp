@@ -42,15 +42,10 @@ void manifest_record(const fz_program* p, const Variant& v)
    ::close(fd);
 }
 
-// What a record's variant must satisfy before anything is generated from it: a forward kernel runs 1, 2 or 4 streams per lane.  An adjoint
-// variant has rules of its own and one home for them, fz_grad.cpp: adjoint_variant_fits -- asked below, once the record's graph is compiled;
-// a block-start-states variant (FZ_VF_STATES next to FZ_VF_ADJOINT) is asked of fz_grad.cpp: states_variant_fits in the same place,
-// a ring adjoint variant (FZ_VF_ADJOINT_RING next to it, with or without FZ_VF_ADJOINT_LOSS) of fz_grad.cpp: ring_adjoint_variant_fits;
-// a ring states variant (FZ_VF_STATES and FZ_VF_ADJOINT_RING next to it) of fz_grad.cpp: ring_states_variant_fits;
-// a stream-major ring adjoint variant (FZ_VF_ADJOINT_RING and FZ_VF_ADJOINT_SM next to it, no FZ_VF_STATES) of fz_grad.cpp:
-// ring_sm_adjoint_variant_fits, asked before the two-bit cases;
-// a PCM variant passes the forward rule and then fz_pcm16.cpp: pcm16_variant_fits, or pcm16_sm_variant_fits where it names the kernel for
-// stream-major buffers.
+// What a record's variant must satisfy before anything is generated from it: a forward kernel runs 1, 2 or 4 streams per lane.  A
+// variant of the adjoint family has rules of its own and one home for them, fz_grad.cpp: grad_variant_fits -- asked below, once the
+// record's graph is compiled; a PCM variant passes the forward rule and then fz_pcm16.cpp: pcm16_variant_fits, or pcm16_sm_variant_fits
+// where it names the kernel for stream-major buffers.
 static bool variant_is_sane(const Variant& v)
 {
    if (v.flags & FZ_VF_ADJOINT) return true;
@@ -107,20 +102,7 @@ int manifest_build(const std::string& path, unsigned n_workers, uint32_t counts[
       }
       programs.emplace_back(p);
       for (const Variant& v : kv.second) {
-         if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_RING)) {   // (the states kernel of a ring recording: its block, its U, a graph with a ring line the ring backward takes)
-            if (ring_states_variant_fits(p->g, v)) items.push_back(Item{p, v});
-            else ++counts[3];
-         }
-         else if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && (v.flags & FZ_VF_ADJOINT_SM) && !(v.flags & FZ_VF_STATES)) {   // (the ring backward's on stream-major buffers: exactly the block and patch rows its rule makes for this graph and C)
-            if (ring_sm_adjoint_variant_fits(p->g, v)) items.push_back(Item{p, v});
-            else ++counts[3];
-         }
-         else if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_STATES) && !states_variant_fits(p->g, v)) ++counts[3];   // (no variant fz_run_recording_grad makes: U, the patch rows in P, other bits)
-         else if ((v.flags & FZ_VF_ADJOINT) && (v.flags & FZ_VF_ADJOINT_RING) && !(v.flags & FZ_VF_STATES)) {   // (the ring backward's, plain or under the loss: its block, its C, a graph with a ring -- and outputs for the loss)
-            if (ring_adjoint_variant_fits(p->g, v)) items.push_back(Item{p, v});
-            else ++counts[3];
-         }
-         else if ((v.flags & FZ_VF_ADJOINT) && !(v.flags & FZ_VF_STATES) && !adjoint_variant_fits(p->g, v)) ++counts[3];   // (no variant the backward makes: C, the patch rows in P, a patch this graph's frames do not fit, a graph it refuses)
+         if ((v.flags & FZ_VF_ADJOINT) && !grad_variant_fits(p->g, v)) ++counts[3];   // (no variant a backward makes for this graph: its flag set, stride, workgroup, patch rows)
          else if ((v.flags & FZ_VF_PCM16) && !((v.flags & FZ_VF_PCM16_SM) ? pcm16_sm_variant_fits(p->g, v) : pcm16_variant_fits(p->g, v))) ++counts[3];   // (no variant fz_run_block_pcm16 makes, or a graph it refuses)
          else items.push_back(Item{p, v});
       }
