@@ -190,9 +190,9 @@ def draw_params(p, ns, rng):
 
 
 def inputs(cell, ns, T, seed):
-    """test_grad_gpu.make_inputs for a cell: x, state, params, dL/dy, dL/d(state after), the two accumulators -- none of them zero; cells
+    """grad_harness.make_inputs for a cell: x, state, params, dL/dy, dL/d(state after), the two accumulators -- none of them zero; cells
     with ABS / MIN / MAX / comparisons get the ties and specials (+-0, NaN, +-inf, equal operands) in every third stream"""
-    from test_grad_gpu import make_inputs
+    from grad_harness import make_inputs
     p = prog(cell)
     return make_inputs(p, cell, ns, T, seed, ties=has_ties(p), draw_params=draw_params, special_every=SPECIAL_EVERY)
 

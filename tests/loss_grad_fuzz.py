@@ -49,7 +49,7 @@ def draw(cell, ns, T, seed):
 
 def draw_trig(p, ns, T, seed):
     """test_trig_log_gpu.grad_inputs' draws and a loss accumulator"""
-    from test_grad_gpu import make_inputs
+    from grad_harness import make_inputs
     d = make_inputs(p, "trig", ns, T, seed, ties=False, draw_params=lambda p_, n, rng: rng.uniform(0.01, 0.5, (p_.n_param, n)).astype(F32))
     return d + (np.random.default_rng(seed + 1).standard_normal(ns).astype(F32),)
 

@@ -25,6 +25,7 @@ import adjoint_ref as A
 import adjoint_ref_trig as AT
 import grad_fuzz_cells as GC
 import trig_cells as TC
+from grad_harness import up4
 from graphs import DEL, IN, add, chan, lit, mul
 from zignal_amd import flowz as F
 
@@ -140,10 +141,6 @@ def load_pins():
         return json.load(f)
 
 
-def up4(n):
-    return (n + 3) // 4 * 4
-
-
 # ---- shapes -------------------------------------------------------------------------------------------------------------------------
 def shapes(name):
     """[(ns, T, B)], at most eight, from the graph's own strides():
@@ -184,9 +181,9 @@ def chain_triple(name):
 
 # ---- inputs -------------------------------------------------------------------------------------------------------------------------
 def draw(name, ns, T, seed):
-    """x, state, params, target (also dL/dy), dL/d(state after) and three accumulators, none of them zero: test_grad_gpu.make_inputs as
+    """x, state, params, target (also dL/dy), dL/d(state after) and three accumulators, none of them zero: grad_harness.make_inputs as
     test_recording_grad_gpu.draw calls it for a cell"""
-    from test_grad_gpu import make_inputs
+    from grad_harness import make_inputs
     p = prog(name)
     x, s0, par, tg, sb, ap, ac = make_inputs(p, name, ns, T, seed, draw_params=GC.draw_params, ties=GC.has_ties(p), special_every=GC.SPECIAL_EVERY)
     al = np.random.default_rng(seed + 1).standard_normal(ns).astype(F32)

@@ -13,6 +13,7 @@ import numpy as np
 
 import ring_grad_graphs as RG
 import ring_loss_graphs as RL
+from grad_harness import from_sm, to_sm, up4  # noqa: F401  (the transposition, under the names the users of this module know)
 from graphs import DEL, add
 
 F32 = np.float32
@@ -89,25 +90,6 @@ def symbol_geometry(sym):
     m = SYMBOL.match(sym)
     assert m, sym
     return int(m.group(2)), int(m.group(3)), int(m.group(4))
-
-
-# ---- transposition ---------------------------------------------------------------------------------------------------------------------
-def up4(n):
-    return (n + 3) // 4 * 4
-
-
-def to_sm(a, rows=None, row0=0, fill=0.0):
-    """time-major [T][ns][w] -> stream-major [ns][rows][w] with the block at rows [row0, row0 + T), `fill` around it"""
-    T, ns, w = a.shape
-    rows = up4(row0 + T) if rows is None else rows
-    out = np.full((ns, rows, w), fill, F32)
-    out[:, row0:row0 + T] = a.transpose(1, 0, 2)
-    return out
-
-
-def from_sm(a, T, row0=0):
-    """the window's rows of a stream-major buffer, time-major"""
-    return np.ascontiguousarray(a[:, row0:row0 + T].transpose(1, 0, 2))
 
 
 # ---- the kernels the GPU tests launch: tests/golden/ring_sm_kernels.fzm.gz ---------------------------------------------------------------

@@ -6,8 +6,8 @@ import pytest
 
 import adjoint_ref as A
 import grad_fuzz_cells as GC
-from test_grad_gpu import check, on_gpu, same
-from test_grad_stream_major_gpu import on_gpu_sm, outside_keeps_sentinel, up4
+import grad_harness as H
+from grad_harness import gpu_flowz, grid, on_gpu, on_gpu_sm, outside_keeps_sentinel, same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -17,17 +17,11 @@ N_CHUNKS = 8                                       # about six cells per test
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
+    return gpu_flowz()
 
 
-def grid(p, n):
-    """the next row count whose frames of both widths lie on the float4 grid (rows_total and row0 of a stream-major window)"""
-    while (n * p.n_in) % 4 or (n * p.n_out) % 4:
-        n += 1
-    return n
+def check(p, got, want, what):
+    H.check(p, got, want, what, H.GRAD_KEYS)
 
 
 def refused(F, p):

@@ -7,20 +7,18 @@ import pytest
 
 import adjoint_ref as A
 import grad_graphs as GG
+import grad_harness as H
+from grad_harness import F32, dev, gpu_flowz, make_inputs, on_gpu, same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-KEYS = ("x", "state", "params", "consts")
+KEYS = H.GRAD_KEYS
 
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
+    return gpu_flowz()
 
 
 _progs = {}
@@ -36,78 +34,8 @@ def stride(p):
     return int(p.grad_kernel_symbol().split("_c")[1].split("b")[0])
 
 
-def same(a, b):
-    """bit for bit, a NaN of any payload equal to a NaN"""
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    if a.shape != b.shape:
-        return False
-    eq = a.view(np.uint32) == b.view(np.uint32)
-    return bool(np.all(eq | (np.isnan(a) & np.isnan(b))))
-
-
-def make_inputs(p, name, ns, T, seed, ties=None, draw_params=None, special_every=1):
-    """x, state, params, dL/dy, dL/d(state after) and the two accumulators, none of them zero.  ties (default: by name): the ties and
-    specials below mixed into x -- special_every = k: only into every k-th stream, the others stay finite (behind a feedback a NaN
-    never leaves its stream); draw_params(p, ns, rng): the per-stream coefficients of a graph that is none of the named ones"""
-    rng = np.random.default_rng(seed)
-    x = (rng.standard_normal((T, ns, p.n_in)) * 0.5).astype(F32)
-    if name == "div_sqrt_exp":
-        x = np.abs(x)
-    if name in ("rules", "envelope_follower", "clipped_biquad") if ties is None else ties:
-        # ties of MIN / MAX (equal values, +0 against -0), +-0 under ABS, NaN and inf through the comparisons
-        special = np.array([0.0, -0.0, 1.0, 0.5, np.nan, np.inf, -np.inf, 0.75], F32)
-        m = rng.random(x.shape) < 0.2
-        m[:, np.arange(ns) % special_every != 0] = False
-        x[m] = special[rng.integers(0, special.size, int(m.sum()))]
-        if p.n_in >= 2:
-            tie = rng.random((T, ns)) < 0.2
-            x[:, :, 1][tie] = x[:, :, 0][tie]
-    s0 = (rng.standard_normal((p.n_state, ns)) * 0.1).astype(F32)
-    par = None
-    if p.n_param:
-        if draw_params is not None:
-            par = draw_params(p, ns, rng)
-        elif name == "moog_ladder":
-            par = rng.uniform(0.05, 0.5, (1, ns)).astype(F32)
-        elif name == "osc_chain6":
-            import graphs as G
-            par = np.asarray(G.osc_chain_params(G.SEED, np.arange(ns)), F32)
-        else:
-            import graphs as G
-            par = np.empty((p.n_param, ns), F32)
-            for j in range(p.n_param // 5):
-                par[5 * j:5 * j + 5] = np.asarray(G.STABLE, F32)[:, None] * rng.uniform(0.9, 1.0, (5, ns)).astype(F32)
-    yb = rng.standard_normal((T, ns, p.n_out)).astype(F32)
-    sb = rng.standard_normal((p.n_state, ns)).astype(F32)
-    ap = rng.standard_normal((p.n_param, ns)).astype(F32)
-    ac = rng.standard_normal((p.n_const, ns)).astype(F32)
-    return x, s0, par, yb, sb, ap, ac
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda() if a is not None else None
-
-
-def on_gpu(p, x, s0, par, yb, sb, ap, ac, checkpoint_rows=0, want=KEYS):
-    accum = {}
-    if p.n_param and "params" in want:
-        accum["params"] = dev(ap)
-    if p.n_const and "consts" in want:
-        accum["consts"] = dev(ac)
-    r = p.run_block_grad(dev(x), dev(yb), dev(s0) if p.n_state else None, dev(par), dev(sb) if p.n_state else None, want=want,
-                         accum=accum, checkpoint_rows=checkpoint_rows)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
 def check(p, got, want, what):
-    for k in KEYS:
-        if k not in got:
-            continue
-        rows = {"x": None, "state": p.n_state, "params": p.n_param, "consts": p.n_const}[k]
-        g = got[k] if rows is None else got[k][:rows]
-        w = want[k] if rows is None else want[k][:rows]
-        assert same(g, w), f"{what}: {k} differs in {int((~((g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w)))).sum())} of {g.size}"
+    H.check(p, got, want, what, KEYS)
 
 
 @pytest.mark.parametrize("name", sorted(GG.SUPPORTED))

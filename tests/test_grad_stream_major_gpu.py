@@ -5,26 +5,23 @@ checkpoint strides, subsets, repeatability, and autograd.run(..., stream_major=T
 import ctypes
 import re
 
-import numpy as np
 import pytest
 
 import adjoint_ref as A
 import grad_graphs as GG
-from test_grad_gpu import KEYS, F32, check, dev, make_inputs, same
-from test_grad_gpu import on_gpu as on_gpu_time_major
+import grad_harness as H
+from grad_harness import SENTINEL, dev, gpu_flowz, make_inputs, on_gpu_sm, outside_keeps_sentinel, same, to_sm, up4
+from grad_harness import on_gpu as on_gpu_time_major
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-SENTINEL = np.float32(-1234.5)
+KEYS = H.GRAD_KEYS
 
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
+    return gpu_flowz()
 
 
 _progs = {}
@@ -42,45 +39,8 @@ def strides(p, checkpoint_rows=0):
     return int(m.group(1)), int(m.group(2))
 
 
-def up4(n):
-    return (n + 3) // 4 * 4
-
-
-def to_sm(a, rows, row0=0, fill=0.0):
-    """time-major [T][ns][w] -> stream-major [ns][rows][w] with the block at rows [row0, row0 + T), `fill` around it"""
-    T, ns, w = a.shape
-    out = np.full((ns, rows, w), fill, F32)
-    out[:, row0:row0 + T] = a.transpose(1, 0, 2)
-    return out
-
-
-def on_gpu_sm(p, x, s0, par, yb, sb, ap, ac, checkpoint_rows=0, want=KEYS, rows=None, row0=0, in_grad=None, pad=7.0):
-    """the stream-major backward of time-major numpy inputs; "x" comes back time-major (the window's rows), "x_buffer" is the whole
-    in_grad buffer.  Rows outside the window hold `pad` in x and dL/dy: they must not matter."""
-    T = x.shape[0]
-    rows = up4(row0 + T) if rows is None else rows
-    accum = {}
-    if p.n_param and "params" in want:
-        accum["params"] = dev(ap)
-    if p.n_const and "consts" in want:
-        accum["consts"] = dev(ac)
-    if in_grad is None and "x" in want:
-        in_grad = torch.full((x.shape[1], rows, p.n_in), float(SENTINEL), device="cuda")
-    r = p.run_block_grad_stream_major(dev(to_sm(x, rows, row0, pad)), dev(to_sm(yb, rows, row0, pad)), dev(s0) if p.n_state else None, dev(par),
-                                      dev(sb) if p.n_state else None, want=want, accum=accum, checkpoint_rows=checkpoint_rows, row0=row0,
-                                      n_samples=T, in_grad=in_grad if "x" in want else None)
-    torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in r.items()}
-    if "x" in out:
-        out["x_buffer"] = out["x"]
-        out["x"] = np.ascontiguousarray(out["x_buffer"][:, row0:row0 + T].transpose(1, 0, 2))
-    return out
-
-
-def outside_keeps_sentinel(buf, row0, T):
-    keep = np.ones(buf.shape[1], bool)
-    keep[row0:row0 + T] = False
-    return bool(np.all(buf[:, keep].view(np.uint32) == SENTINEL.view(np.uint32)))
+def check(p, got, want, what):
+    H.check(p, got, want, what, KEYS)
 
 
 @pytest.mark.parametrize("name", sorted(GG.SUPPORTED))

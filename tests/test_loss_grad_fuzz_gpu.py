@@ -14,12 +14,11 @@ import adjoint_ref_trig as AT
 import grad_fuzz_cells as GC
 import loss_grad_fuzz as LF
 import loss_grad_ref as LR
-import test_grad_gpu as TG
+import grad_harness as H
 import trig_cells as TC
-from test_grad_fuzz_gpu import grid
-from test_grad_gpu import F32, dev, same
-from test_grad_stream_major_gpu import SENTINEL, on_gpu_sm, to_sm
-from test_loss_grad_gpu import K, KEYS, check, on_gpu, outside_keeps_sentinel
+from grad_harness import F32, K, SENTINEL, dev, gpu_flowz, grid, on_gpu_sm, outside_keeps_sentinel, same, to_sm
+from grad_harness import on_gpu as on_gpu_plain
+from grad_harness import on_gpu_loss as on_gpu
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -30,10 +29,14 @@ assert K == LF.K
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
+    return gpu_flowz()
+
+
+KEYS = H.LOSS_KEYS
+
+
+def check(p, got, want, what, keys=KEYS):
+    H.check(p, got, want, what, keys)
 
 
 def refused(F, p):
@@ -95,12 +98,12 @@ def test_the_gradients_are_the_plain_adjoint_kernels_given_the_same_out_grad(F, 
             ybar = ((y - tg) * F32(K)).astype(F32)
         tm = on_gpu(p, False, *d)
         assert same(tm["out"], y), f"{cell}: the restated y is not the kernel's"
-        TG.check(p, tm, TG.on_gpu(p, x, s0, par, ybar, sb, ap, ac), f"{cell} time-major, loss kernel against plain kernel")
+        check(p, tm, on_gpu_plain(p, x, s0, par, ybar, sb, ap, ac), f"{cell} time-major, loss kernel against plain kernel", H.GRAD_KEYS)
         if r is None:
             assert refused(F, p)
             continue
         rows = grid(p, T)
-        TG.check(p, on_gpu(p, True, *d, rows=rows), on_gpu_sm(p, x, s0, par, ybar, sb, ap, ac, rows=rows), f"{cell} stream-major, loss kernel against plain kernel")
+        check(p, on_gpu(p, True, *d, rows=rows), on_gpu_sm(p, x, s0, par, ybar, sb, ap, ac, rows=rows), f"{cell} stream-major, loss kernel against plain kernel", H.GRAD_KEYS)
 
 
 # ---- c. two blocks chain like one ---------------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ import grad_fuzz_cells as GC
 import loss_grad_fuzz as LF
 import loss_grad_ref as LR
 import trig_cells as TC
-from test_grad_gpu import same
+from grad_harness import same
 from test_grad_host import inputs as smooth_inputs
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F

@@ -10,23 +10,20 @@ import pytest
 import adjoint_ref as A
 import grad_graphs as GG
 import loss_grad_ref as LR
-from test_grad_gpu import F32, dev, make_inputs, same
-from test_grad_stream_major_gpu import SENTINEL, to_sm, up4
+import grad_harness as H
+from grad_harness import F32, K, SENTINEL, dev, gpu_flowz, make_inputs, outside_keeps_sentinel, same, to_sm, up4
+from grad_harness import on_gpu_loss as on_gpu
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 GRAPHS = ["df1_cascade_params6", "moog_ladder", "rules", "par4_sum", "div_sqrt_exp"]
-KEYS = ("x", "state", "params", "consts", "loss", "out")
-K = 0.37                                                          # grad_scale: no power of two, so e * k rounds
+KEYS = H.LOSS_KEYS
 
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
+    return gpu_flowz()
 
 
 _progs = {}
@@ -52,48 +49,8 @@ def draw(p, name, ns, T, seed):
     return x, s0, par, tg, sb, ap, ac, al
 
 
-def on_gpu(p, sm, x, s0, par, tg, sb, ap, ac, al, checkpoint_rows=0, want=KEYS, rows=None, row0=0, in_grad=None, out=None):
-    """one launch on time-major numpy inputs; sm: through stream-major buffers of `rows` rows with the block at row0, "x" and "out" come
-    back time-major (the window's rows), "x_buffer" / "out_buffer" are the whole buffers, SENTINEL outside the window -- or in_grad / out,
-    the buffers consecutive windows fill; "target_sent" / "target_after": the target buffer as it went in and as the launch left it"""
-    T, ns = x.shape[:2]
-    accum = {k: dev(v) for k, v, n in (("params", ap, p.n_param), ("consts", ac, p.n_const), ("loss", al, 1)) if n and k in want}
-    args = (dev(s0) if p.n_state else None, dev(par), dev(sb) if p.n_state else None)
-    if not sm:
-        r = p.run_block_loss_grad(dev(x), dev(tg), *args, grad_scale=K, want=want, accum=accum, checkpoint_rows=checkpoint_rows)
-    else:
-        rows = up4(row0 + T) if rows is None else rows
-        full = lambda w: torch.full((ns, rows, w), float(SENTINEL), device="cuda")   # noqa: E731
-        sent = to_sm(tg, rows, row0, 7.0)
-        tgd = dev(sent)
-        r = p.run_block_loss_grad_stream_major(dev(to_sm(x, rows, row0, 7.0)), tgd, *args, grad_scale=K, want=want,
-                                               accum=accum, checkpoint_rows=checkpoint_rows, row0=row0, n_samples=T,
-                                               in_grad=(full(p.n_in) if in_grad is None else in_grad) if "x" in want else None,
-                                               out=(full(p.n_out) if out is None else out) if "out" in want else None)
-    torch.cuda.synchronize()
-    res = {k: v.cpu().numpy() for k, v in r.items()}
-    if sm:
-        for k in ("x", "out"):
-            if k in res:
-                res[k + "_buffer"] = res[k]
-                res[k] = np.ascontiguousarray(res[k][:, row0:row0 + T].transpose(1, 0, 2))
-        res["target_sent"], res["target_after"] = sent, tgd.cpu().numpy()
-    return res
-
-
 def check(p, got, want, what):
-    rows = {"state": p.n_state, "params": p.n_param, "consts": p.n_const}
-    for k in KEYS:
-        if k not in got:
-            continue
-        g, w = (got[k][:rows[k]], want[k][:rows[k]]) if k in rows else (got[k], want[k])
-        assert same(g, w), f"{what}: {k} differs in {int((~((g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w)))).sum())} of {g.size}"
-
-
-def outside_keeps_sentinel(buf, row0, T):
-    keep = np.ones(buf.shape[1], bool)
-    keep[row0:row0 + T] = False
-    return bool(np.all(buf[:, keep].view(np.uint32) == SENTINEL.view(np.uint32)))
+    H.check(p, got, want, what, KEYS)
 
 
 @pytest.mark.parametrize("name", GRAPHS)

@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 
 import recording_fuzz as RF
-from test_grad_gpu import dev, same
-from test_recording_grad_gpu import check, keys_of, launch, outside_keeps_sentinel
+import grad_harness as H
+from grad_harness import ROW0, dev, gpu_flowz, keys_of, outside_keeps_sentinel, same
+from grad_harness import on_gpu_recording as launch
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,11 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
+    return gpu_flowz()
+
+
+def check(p, got, want, what, keys):
+    H.check(p, got, want, what, keys, require=True)
 
 
 def run_blocks_state(p, x, s0, par):
@@ -37,7 +39,7 @@ def run_blocks_state(p, x, s0, par):
 
 def hold(p, name, loss, d, B, sms, what, row0=None, rows=None, forward=False):
     """one draw through the recording call in the layouts `sms`, held to everything the module's docstring lists.  row0 / rows: the
-    stream-major window and buffer rows (default: test_recording_grad_gpu's)"""
+    stream-major window and buffer rows (default: grad_harness.on_gpu_recording's)"""
     x, s0, par, tg, sb, ap, ac, al = d
     T = x.shape[0]
     assert all(np.all(a != 0) for a in (sb, ap, ac, al) if a.size), what + ": an accumulator is zero"
@@ -59,9 +61,9 @@ def hold(p, name, loss, d, B, sms, what, row0=None, rows=None, forward=False):
         assert g["inputs_kept"], lay + ": in, target or state were written"
         assert g["ws_kept"], lay + ": the workspace was written beyond the queried size"
         if sm:
-            r0 = {} if row0 is None else dict(row0=row0)
-            assert outside_keeps_sentinel(g["x_buffer"], T, **r0), lay + ": rows of in_grad outside the window were written"
-            assert not loss or outside_keeps_sentinel(g["out_buffer"], T, **r0), lay + ": rows of out outside the window were written"
+            r0 = ROW0 if row0 is None else row0
+            assert outside_keeps_sentinel(g["x_buffer"], r0, T), lay + ": rows of in_grad outside the window were written"
+            assert not loss or outside_keeps_sentinel(g["out_buffer"], r0, T), lay + ": rows of out outside the window were written"
     if len(got) == 2:
         check(p, got[True], got[False], what + ": the two layouts", keys_of(loss, True))
         assert same(got[True]["starts"], got[False]["starts"]), what + ": the block-start states of the two layouts"

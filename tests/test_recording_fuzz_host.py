@@ -14,7 +14,7 @@ import pytest
 
 import grad_fuzz_cells as GC
 import recording_fuzz as RF
-from test_grad_gpu import same
+from grad_harness import same
 from test_recording_grad_host import FakeBufs
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F

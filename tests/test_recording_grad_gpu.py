@@ -17,26 +17,21 @@ import adjoint_ref as A
 import grad_fuzz_cells as GC
 import loss_grad_ref as LR
 import recording_ref as RR
-from test_grad_gpu import F32, dev, make_inputs, same
-from test_grad_stream_major_gpu import SENTINEL, to_sm, up4
+import grad_harness as H
+from grad_harness import F32, K, ROW0, dev, gpu_flowz, keys_of, make_inputs, outside_keeps_sentinel, rows_of, same, to_sm
+from grad_harness import on_gpu_recording as launch
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 NAMES = RR.GPU_GRAPHS + RR.GPU_CELLS
-KEYS = ("x", "state", "params", "consts", "loss", "out")
-K = 0.37                                                          # grad_scale: no power of two, so e * k rounds
-ROW0 = 8
 MSE_TOL = 1e-6                                                    # the bound of test_loss_grad_gpu.test_mse_equals_run_then_torch_mse
 SHAPES = RR.GPU_SHAPES
 
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
+    return gpu_flowz()
 
 
 _progs = {}
@@ -56,76 +51,9 @@ def draw(p, name, ns, T, seed):
     return x, s0, par, tg, sb, ap, ac, al
 
 
-def rows_of(T):
-    return up4(T + 9) + 4
-
-
-def launch(p, loss, sm, B, x, s0, par, tg, sb, ap, ac, al, row0=ROW0, rows=None):
-    """one call on time-major numpy inputs.  B None: the one-launch call; else the recording call with block_rows = B, its workspace
-    inside a larger sentinel-filled buffer.  sm: through stream-major buffers of `rows` rows (default rows_of(T)) with the window at
-    row0 (default ROW0); "x" and "out" come back time-major, "x_buffer" / "out_buffer" are the whole buffers.  "inputs_kept": in, target / dL/dy and state as the call left them
-    equal what went in; "starts": the head of the workspace; "ws_kept": nothing outside the queried workspace bytes was written"""
-    T, ns = x.shape[:2]
-    want = keys_of(loss, B is not None)
-    accum = {k: dev(v) for k, v, n in (("params", ap, p.n_param), ("consts", ac, p.n_const), ("loss", al, int(loss))) if n}
-    rows = rows_of(T) if rows is None else rows
-    xin, tin = (dev(to_sm(x, rows, row0, 7.0)), dev(to_sm(tg, rows, row0, 7.0))) if sm else (dev(x), dev(tg))
-    sin = dev(s0) if p.n_state else None
-    sent = [t.clone() for t in (xin, tin, sin) if t is not None]
-    kw = dict(want=want, accum=accum)
-    if sm:
-        full = lambda w: torch.full((ns, rows, w), float(SENTINEL), device="cuda")   # noqa: E731
-        kw.update(row0=row0, n_samples=T, in_grad=full(p.n_in))
-        if loss:
-            kw["out"] = full(p.n_out)
-    if loss:
-        kw["grad_scale"] = K
-    ws = None
-    if B is not None:
-        n = p.recording_workspace_bytes(ns, T, B, stream_major=sm) // 4
-        ws = torch.full((n + 128,), float(SENTINEL), device="cuda")
-        kw.update(block_rows=B, stream_major=sm, workspace=ws[64:64 + max(n, 4)])
-        fn = p.run_recording_loss_grad if loss else p.run_recording_grad
-    else:
-        fn = {(False, False): p.run_block_grad, (False, True): p.run_block_grad_stream_major, (True, False): p.run_block_loss_grad,
-              (True, True): p.run_block_loss_grad_stream_major}[(loss, sm)]
-    r = fn(xin, tin, sin, dev(par), dev(sb) if p.n_state else None, **kw)
-    torch.cuda.synchronize()
-    res = {k: v.cpu().numpy() for k, v in r.items()}
-    if sm:
-        for k in ("x", "out"):
-            if k in res:
-                res[k + "_buffer"] = res[k]
-                res[k] = np.ascontiguousarray(res[k][:, row0:row0 + T].transpose(1, 0, 2))
-    # (bit for bit: the inputs of a cell with ties hold NaNs)
-    res["inputs_kept"] = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(sent, [t for t in (xin, tin, sin) if t is not None]))
-    if ws is not None:
-        w = ws.cpu().numpy()
-        nb = -(-T // p.recording_block_rows(T, B))                 # (B = 0: the library's choice)
-        res["starts"] = w[64:64 + nb * p.n_state * ns].reshape(nb, p.n_state, ns)
-        keep = np.concatenate([w[:64], w[64 + n:]]) if n else w
-        res["ws_kept"] = bool(np.all(keep.view(np.uint32) == SENTINEL.view(np.uint32)))
-    return res
-
-
-def keys_of(loss, state_out=False):
-    """the results a call returns: every gradient, "loss" and "out" of a loss call, "state_out" of a recording call or the restatement"""
-    return tuple(k for k in KEYS if loss or k not in ("loss", "out")) + (("state_out",) if state_out else ())
-
-
 def check(p, got, want, what, keys):
     """every key of `keys` is there on both sides (a result that went missing fails, it does not pass unseen) and equal bit for bit"""
-    rows = {"state": p.n_state, "params": p.n_param, "consts": p.n_const, "state_out": p.n_state}
-    for k in keys:
-        assert k in got and k in want, f"{what}: {k} is missing ({sorted(got)} against {sorted(want)})"
-        g, w = (got[k][:rows[k]], want[k][:rows[k]]) if k in rows else (got[k], want[k])
-        assert same(g, w), f"{what}: {k} differs in {int((~((g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w)))).sum())} of {g.size}"
-
-
-def outside_keeps_sentinel(buf, T, row0=ROW0):
-    keep = np.ones(buf.shape[1], bool)
-    keep[row0:row0 + T] = False
-    return bool(np.all(buf[:, keep].view(np.uint32) == SENTINEL.view(np.uint32)))
+    H.check(p, got, want, what, keys, require=True)
 
 
 def forward_state(p, x, s0, par, rows):
@@ -161,8 +89,8 @@ def test_a_recording_is_the_one_launch_call_bitwise_in_both_layouts(F, name, los
             assert g["inputs_kept"], lay + ": in, target or state were written"
             assert g["ws_kept"], lay + ": the workspace was written beyond the queried size"
             if sm:
-                assert outside_keeps_sentinel(g["x_buffer"], T), lay + ": rows of in_grad outside the window were written"
-                assert not loss or outside_keeps_sentinel(g["out_buffer"], T), lay + ": rows of out outside the window were written"
+                assert outside_keeps_sentinel(g["x_buffer"], ROW0, T), lay + ": rows of in_grad outside the window were written"
+                assert not loss or outside_keeps_sentinel(g["out_buffer"], ROW0, T), lay + ": rows of out outside the window were written"
         one_sm = launch(p, loss, True, None, *d)                  # (the stream-major one-launch call on the same window)
         check(p, got[True], one_sm, what + " stream-major against its one-launch call", keys_of(loss))
         check(p, got[True], got[False], what + ": the two layouts", keys_of(loss, True))

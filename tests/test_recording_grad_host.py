@@ -17,7 +17,7 @@ import grad_fuzz_cells as GC
 import grad_graphs as GG
 import loss_grad_ref as LR
 import recording_ref as RR
-from test_grad_gpu import make_inputs, same
+from grad_harness import make_inputs, same
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 

@@ -5,30 +5,25 @@ blocks of which the first is shorter than the line, the inputs and the workspace
 
 Every launch goes through the C ABI with a workspace of exactly the queried bytes inside a larger buffer of sentinels, and checks
 afterwards that the sentinels and every input kept their bits."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import adjoint_ref as A
 import grad_graphs as GG
+import grad_harness as H
 import ring_grad_graphs as RG
+from grad_harness import F32, OUT, dev, gpu_flowz, make_inputs, same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-KEYS = ("x", "state", "params", "consts")
-OUT = {"x": "in_grad", "state": "state0_grad", "params": "param_grad", "consts": "const_grad"}
-SENTINEL = np.float32(-1234.5)
+KEYS = H.GRAD_KEYS
+OUT = {key: OUT[key] for key in KEYS}
 
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
+    return gpu_flowz()
 
 
 _progs, _cases = {}, {}
@@ -58,58 +53,13 @@ def stride(p):
     return int(p.ring_grad_kernel_symbol().split("_c")[1].split("b")[0])
 
 
-def same(a, b):
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, F32, order="C")).cuda() if a is not None else None     # (a copy: the cases are read-only)
-
-
-def launch(p, inputs, checkpoint_rows=0, state_grad=True, alias=False, leave_out=(), fn="fz_run_block_ring_grad"):
-    """one call through the C ABI: dict of the outputs asked for (numpy).  The accumulators start from ap / ac.  alias: state0_grad is
-    the state_grad buffer.  Afterwards: the inputs kept their bits, outputs left out and the workspace's surroundings their sentinels."""
-    from zignal_amd import _capi as CA
-    x, s0, par, yb, sb, ap, ac = inputs
-    T, ns, _ = x.shape
-    ins = {"in_": dev(x), "state": dev(s0), "params": dev(par), "out_grad": dev(yb), "state_grad": dev(sb) if state_grad else None}
-    before = {k: v.clone() for k, v in ins.items() if v is not None}
-    outs = {"in_grad": torch.full((T, ns, max(p.n_in, 1)), SENTINEL, device="cuda"),
-            "state0_grad": ins["state_grad"] if alias else torch.full((max(p.n_state, 1), ns), SENTINEL, device="cuda"),
-            "param_grad": dev(ap) if p.n_param else torch.full((1, ns), SENTINEL, device="cuda"),
-            "const_grad": dev(ac) if p.n_const else torch.full((1, ns), SENTINEL, device="cuda")}
-    rows = {"in_grad": p.n_in, "state0_grad": p.n_state, "param_grad": p.n_param, "const_grad": p.n_const}
-    untouched = {k: v.clone() for k, v in outs.items()}
-    wsb = p.ring_grad_workspace_bytes(ns, T, checkpoint_rows) if fn == "fz_run_block_ring_grad" else p.grad_workspace_bytes(ns, T, checkpoint_rows)
-    pad = 64                                                   # floats of sentinel on either side (the head stays 16-byte aligned)
-    ws = torch.full((pad + (wsb + 3) // 4 + pad,), SENTINEL, device="cuda")
-    a = CA.GradArgs()
-    a.struct_size = ctypes.sizeof(CA.GradArgs)
-    a.checkpoint_rows = checkpoint_rows
-    for k, t in ins.items():
-        setattr(a, k, t.data_ptr() if t is not None and t.numel() else None)
-    for k, t in outs.items():
-        setattr(a, k, t.data_ptr() if rows[k] and k not in leave_out else None)
-    a.workspace, a.workspace_bytes = ws.data_ptr() + 4 * pad, wsb
-    CA.check(getattr(CA.lib, fn)(p._h, ctypes.byref(a), ns, T, torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    for k, t in before.items():
-        if not (alias and k == "state_grad"):
-            assert torch.equal(ins[k].view(torch.int32), t.view(torch.int32)), f"input {k} was written"
-    assert bool((ws[:pad] == SENTINEL).all()) and bool((ws[pad + (wsb + 3) // 4:] == SENTINEL).all()), "the workspace's surroundings were written"
-    for k in leave_out:
-        if not (alias and k == "state0_grad"):
-            assert torch.equal(outs[k], untouched[k]), f"{k} was left out and written"
-    return {key: outs[b].cpu().numpy() for key, b in OUT.items() if rows[b] and b not in leave_out}
+def launch(p, inputs, checkpoint_rows=0, state_grad=True, alias=False, leave_out=(), ring=True):
+    """one call of fz_run_block_ring_grad (ring=False: fz_run_block_grad) through grad_harness.launch"""
+    return H.launch(p, inputs, ring=ring, c=checkpoint_rows, state_grad=state_grad, alias=alias, leave_out=leave_out)
 
 
 def check(p, got, want, what, keys=KEYS):
-    for k in keys:
-        if k not in got:
-            continue
-        g, w = got[k], want[k][:got[k].shape[0]] if k != "x" else want[k]
-        assert same(g, w), f"{what}: {k} differs in {int((g.view(np.uint32) != np.asarray(w, F32).view(np.uint32)).sum())} of {g.size}"
+    H.check(p, got, want, what, keys)
 
 
 def shapes(p, name):
@@ -185,10 +135,9 @@ def test_two_blocks_chain_like_one(F, name):
 
 @pytest.mark.parametrize("name", ["df1_cascade6", "moog_ladder", "rules"])
 def test_for_a_graph_without_a_ring_it_is_run_block_grad(F, name):
-    import test_grad_gpu as TG
     p = prog(F, name)
-    inputs = TG.make_inputs(p, name, 257, 37, 3)
-    ring, plain = launch(p, inputs), launch(p, inputs, fn="fz_run_block_grad")
+    inputs = make_inputs(p, name, 257, 37, 3)
+    ring, plain = launch(p, inputs), launch(p, inputs, ring=False)
     assert set(ring) == set(plain)
     for k in ring:
         assert same(ring[k], plain[k]), k

@@ -6,109 +6,34 @@ chained blocks of which the first is shorter than the line, non-finite targets, 
 
 Every launch of launch() goes through the C ABI with a workspace of exactly the queried bytes and every output inside a larger buffer of
 sentinels, and checks afterwards that the sentinels, the inputs and the target kept their bits."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import adjoint_ref as A
+import grad_harness as H
 import ring_grad_graphs as RG
 import ring_loss_graphs as RL
+from grad_harness import F32, OUT, dev, gpu_flowz, make_inputs, same
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
 K = RL.K
-KEYS = ("x", "state", "params", "consts", "loss", "out")
-OUT = {"x": "in_grad", "state": "state0_grad", "params": "param_grad", "consts": "const_grad", "loss": "loss", "out": "out"}
-SENTINEL = np.float32(-1234.5)
-PAD = 64                                                          # floats of sentinel on either side (the middle stays 16-byte aligned)
+KEYS = H.LOSS_KEYS
 
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
-
-
-def same(a, b):
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, F32, order="C")).cuda() if a is not None else None     # (a copy: the cases are read-only)
-
-
-class Guarded:
-    """a device buffer of `shape` floats between two runs of PAD sentinels; init: what the middle starts from (None: sentinels too)"""
-
-    def __init__(self, shape, init=None):
-        self.n = int(np.prod(shape))
-        self.buf = torch.full((2 * PAD + self.n,), float(SENTINEL), device="cuda")
-        self.mid = self.buf[PAD:PAD + self.n].view(*shape)
-        if init is not None:
-            self.mid.copy_(dev(init).view(*shape))
-        self.before = self.buf.clone()
-
-    def guards_kept(self):
-        return bool((self.buf[:PAD] == SENTINEL).all()) and bool((self.buf[PAD + self.n:] == SENTINEL).all())
-
-    def untouched(self):
-        return torch.equal(self.buf.view(torch.int32), self.before.view(torch.int32))
+    return gpu_flowz()
 
 
 def launch(p, d, checkpoint_rows=0, state_grad=True, alias=False, leave_out=(), k=K):
-    """one call through the C ABI on the draw d: dict of the outputs asked for (numpy).  param_grad, const_grad and loss start from ap / ac
-    / al.  alias: state0_grad is the state_grad buffer.  Afterwards: the inputs and the target kept their bits, the guards around every
-    output and the workspace their sentinels, and outputs left out were not written at all."""
-    from zignal_amd import _capi as CA
-    x, s0, par, tg, sb, ap, ac, al = d
-    T, ns, _ = x.shape
-    ins = {"in_": dev(x), "state": dev(s0), "params": dev(par), "target": dev(tg), "state_grad": dev(sb) if state_grad else None}
-    before = {key: v.clone() for key, v in ins.items() if v is not None}
-    rows = {"in_grad": p.n_in, "state0_grad": p.n_state, "param_grad": p.n_param, "const_grad": p.n_const, "loss": 1, "out": p.n_out}
-    outs = {"in_grad": Guarded((T, ns, max(p.n_in, 1))), "state0_grad": Guarded((max(p.n_state, 1), ns)),
-            "param_grad": Guarded((max(p.n_param, 1), ns), ap if p.n_param else None),
-            "const_grad": Guarded((max(p.n_const, 1), ns), ac if p.n_const else None),
-            "loss": Guarded((ns,), al), "out": Guarded((T, ns, max(p.n_out, 1)))}
-    wsb = p.ring_grad_workspace_bytes(ns, T, checkpoint_rows)
-    ws = Guarded(((wsb + 3) // 4,))
-    a = CA.LossGradArgs()
-    a.struct_size, a.checkpoint_rows, a.grad_scale = ctypes.sizeof(CA.LossGradArgs), checkpoint_rows, k
-    for key, t in ins.items():
-        setattr(a, key, t.data_ptr() if t is not None and t.numel() else None)
-    for key, g in outs.items():
-        setattr(a, key, g.mid.data_ptr() if rows[key] and key not in leave_out else None)
-    if alias:
-        a.state0_grad = ins["state_grad"].data_ptr()
-    a.workspace, a.workspace_bytes = ws.mid.data_ptr(), wsb
-    CA.check(CA.lib.fz_run_block_ring_loss_grad(p._h, ctypes.byref(a), ns, T, torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    for key, t in before.items():
-        if not (alias and key == "state_grad"):
-            assert torch.equal(ins[key].view(torch.int32), t.view(torch.int32)), f"input {key} was written"
-    assert ws.guards_kept(), "the workspace's surroundings were written"
-    for key, g in outs.items():
-        assert g.guards_kept(), f"the surroundings of {key} were written"
-        if key in leave_out or not rows[key] or (alias and key == "state0_grad"):
-            assert g.untouched(), f"{key} was left out and written"
-    got = {key: outs[b].mid.cpu().numpy() for key, b in OUT.items() if rows[b] and b not in leave_out and not (alias and b == "state0_grad")}
-    if alias and "state0_grad" not in leave_out:
-        got["state"] = ins["state_grad"].cpu().numpy()
-    return got
+    """one call of fz_run_block_ring_loss_grad through grad_harness.launch"""
+    return H.launch(p, d, ring=True, loss=True, c=checkpoint_rows, state_grad=state_grad, alias=alias, leave_out=leave_out, k=k)
 
 
 def check(p, got, want, what, keys=KEYS):
-    rows = {"state": p.n_state, "params": p.n_param, "consts": p.n_const}
-    for key in keys:
-        if key not in got:
-            continue
-        g, w = (got[key][:rows[key]], np.asarray(want[key])[:rows[key]]) if key in rows else (got[key], np.asarray(want[key]))
-        assert same(g, w), f"{what}: {key} differs in {int((~((g.view(np.uint32) == np.asarray(w, F32).view(np.uint32)) | (np.isnan(g) & np.isnan(w)))).sum())} of {g.size}"
+    H.check(p, got, want, what, keys)
 
 
 @pytest.mark.parametrize("c", [0, 1])
@@ -246,10 +171,9 @@ def test_run_block_ring_loss_grad_returns_the_dict_of_run_block_loss_grad(F):
 
 def test_for_a_graph_without_a_ring_it_is_run_block_loss_grad(F):
     import grad_graphs as GG
-    import test_grad_gpu as TG
     name = "moog_ladder"
     p = F.compile(F.from_sexpr(GG.SUPPORTED[name]()))
-    x, s0, par, tg, sb, ap, ac = TG.make_inputs(p, name, 257, 37, 3)
+    x, s0, par, tg, sb, ap, ac = make_inputs(p, name, 257, 37, 3)
     run = lambda fn: fn(dev(x), dev(tg), dev(s0), dev(par), dev(sb), grad_scale=K, accum={"params": dev(ap), "consts": dev(ac)})   # noqa: E731
     ring, plain = run(p.run_block_ring_loss_grad), run(p.run_block_loss_grad)
     torch.cuda.synchronize()

@@ -21,6 +21,7 @@ import loss_grad_ref as LR
 import recording_ref as RR
 import ring_grad_graphs as RG
 import ring_recording_graphs as R
+from grad_harness import same
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
@@ -33,11 +34,6 @@ NEW_EXPORTS = ("fz_program_ring_recording_block_rows", "fz_program_ring_recordin
                "fz_run_recording_ring_loss_grad", "fz_program_ring_states_resources", "fz_program_ring_states_kernel_symbol",
                "fz_program_ring_states_source")
 NAMES = sorted(R.GRAPHS)
-
-
-def same(a, b):
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
 
 
 def empty_args(loss):

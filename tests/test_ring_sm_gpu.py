@@ -8,45 +8,27 @@ every output left out in turn, accumulators, repeatability, and autograd.run_rin
 Every launch of launch() goes through the C ABI with a workspace of exactly the queried bytes and every output inside a larger buffer
 of sentinels; in_grad and out are whole [n_streams][rows_total][wire] buffers of sentinels of which only the window may change.
 Afterwards the sentinels and every input kept their bits."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import adjoint_ref as A
+import grad_harness as H
 import ring_grad_graphs as RG
 import ring_loss_graphs as RL
 import ring_sm_graphs as RS
-from ring_sm_graphs import from_sm, to_sm, up4
+from grad_harness import F32, OUT, dev, gpu_flowz, outside_keeps_sentinel, same, to_sm, up4
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
 K = RL.K
-KEYS = ("x", "state", "params", "consts")
-LOSS_KEYS = KEYS + ("loss", "out")
-OUT = {"x": "in_grad", "state": "state0_grad", "params": "param_grad", "consts": "const_grad", "loss": "loss", "out": "out"}
-SENTINEL = np.float32(-1234.5)
-PAD = 64                                                          # floats of sentinel on either side (the middle stays 16-byte aligned)
-FILL = 7.0                                                        # what x, dL/dy and the target hold outside the window: it must not matter
+KEYS = H.GRAD_KEYS
+LOSS_KEYS = H.LOSS_KEYS
 
 
 @pytest.fixture(scope="module")
 def F():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from zignal_amd import flowz
-    return flowz
-
-
-def same(a, b):
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    return a.shape == b.shape and bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))))
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, F32, order="C")).cuda() if a is not None else None     # (a copy: the cases are read-only)
+    return gpu_flowz()
 
 
 _plain = {}
@@ -75,94 +57,11 @@ def geometry(p, loss=False, c=0):
     return RS.symbol_geometry((p.ring_loss_grad_kernel_symbol if loss else p.ring_grad_kernel_symbol)(c, stream_major=True))
 
 
-class Guarded:
-    """a device buffer of `shape` floats between two runs of PAD sentinels; init: what the middle starts from (None: sentinels too)"""
-
-    def __init__(self, shape, init=None):
-        self.n = int(np.prod(shape))
-        self.buf = torch.full((2 * PAD + self.n,), float(SENTINEL), device="cuda")
-        self.mid = self.buf[PAD:PAD + self.n].view(*shape)
-        if init is not None:
-            self.mid.copy_(dev(init).view(*shape))
-        self.before = self.buf.clone()
-
-    def guards_kept(self):
-        return bool((self.buf[:PAD] == SENTINEL).all()) and bool((self.buf[PAD + self.n:] == SENTINEL).all())
-
-    def untouched(self):
-        return torch.equal(self.buf.view(torch.int32), self.before.view(torch.int32))
-
-
-def outside_keeps_sentinel(buf, row0, T):
-    keep = np.ones(buf.shape[1], bool)
-    keep[row0:row0 + T] = False
-    return bool(np.all(buf[:, keep].view(np.uint32) == SENTINEL.view(np.uint32)))
-
-
 def launch(p, d, loss, c=0, rows=None, row0=0, state_grad=True, alias=False, leave_out=(), frames=None, k=K):
-    """one call through the C ABI on the time-major draw d, transposed into stream-major buffers of `rows` rows with the block at
-    [row0, row0 + T): dict of the outputs asked for (numpy; "x" and "out" are the window's rows, time-major).  d is (x, s0, par, dL/dy,
-    sb, ap, ac) or, under the loss, (x, s0, par, target, sb, ap, ac, al).  frames: a dict that keeps the in_grad / out buffers from one
-    launch to the next (consecutive windows fill one buffer)."""
-    from zignal_amd import _capi as CA
-    x, s0, par, yt, sb, ap, ac = d[:7]
-    T, ns, _ = x.shape
-    rows = up4(row0 + T) if rows is None else rows
-    second = "target" if loss else "out_grad"
-    ins = {"in_": dev(to_sm(x, rows, row0, FILL)), "state": dev(s0), "params": dev(par), second: dev(to_sm(yt, rows, row0, FILL)),
-           "state_grad": dev(sb) if state_grad else None}
-    before = {key: v.clone() for key, v in ins.items() if v is not None}
-    n = {"in_grad": p.n_in, "state0_grad": p.n_state, "param_grad": p.n_param, "const_grad": p.n_const, "loss": 1, "out": p.n_out}
-    frames = {} if frames is None else frames
-    frames.setdefault("in_grad", Guarded((ns, rows, max(p.n_in, 1))))
-    outs = {"in_grad": frames["in_grad"], "state0_grad": Guarded((max(p.n_state, 1), ns)),
-            "param_grad": Guarded((max(p.n_param, 1), ns), ap if p.n_param else None),
-            "const_grad": Guarded((max(p.n_const, 1), ns), ac if p.n_const else None)}
-    if loss:
-        frames.setdefault("out", Guarded((ns, rows, max(p.n_out, 1))))
-        outs.update(loss=Guarded((ns,), d[7]), out=frames["out"])
-    for g in outs.values():
-        g.before = g.buf.clone()
-    wsb = p.ring_grad_workspace_bytes(ns, T, c)
-    ws = Guarded(((wsb + 3) // 4,))
-    a = CA.LossGradArgs() if loss else CA.GradArgs()
-    a.struct_size, a.checkpoint_rows = ctypes.sizeof(a), c
-    if loss:
-        a.grad_scale = k
-    for key, t in ins.items():
-        setattr(a, key, t.data_ptr() if t is not None and t.numel() else None)
-    for key, g in outs.items():
-        setattr(a, key, g.mid.data_ptr() if n[key] and key not in leave_out else None)
-    if alias:
-        a.state0_grad = ins["state_grad"].data_ptr()
-    a.workspace, a.workspace_bytes = ws.mid.data_ptr(), wsb
-    fn = CA.lib.fz_run_block_ring_loss_grad_stream_major if loss else CA.lib.fz_run_block_ring_grad_stream_major
-    CA.check(fn(p._h, ctypes.byref(a), ns, rows, row0, T, torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    for key, t in before.items():
-        if not (alias and key == "state_grad"):
-            assert torch.equal(ins[key].view(torch.int32), t.view(torch.int32)), f"input {key} was written"
-    assert ws.guards_kept(), "the workspace's surroundings were written"
-    for key, g in outs.items():
-        assert g.guards_kept(), f"the surroundings of {key} were written"
-        if key in leave_out or not n[key] or (alias and key == "state0_grad"):
-            assert g.untouched(), f"{key} was left out and written"
-    got = {}
-    for key, b in OUT.items():
-        if b not in outs or not n[b] or b in leave_out or (alias and b == "state0_grad"):
-            continue
-        h = outs[b].mid.cpu().numpy()
-        if b in ("in_grad", "out"):
-            before_rows = outs[b].before[PAD:PAD + outs[b].n].view(*h.shape).cpu().numpy()
-            keep = np.ones(rows, bool)
-            keep[row0:row0 + T] = False
-            assert same(h[:, keep], before_rows[:, keep]), f"rows of {b} outside [{row0}, {row0 + T}) were written"
-            got[key + "_buffer"] = h
-            h = from_sm(h, T, row0)
-        got[key] = h
-    if alias and "state0_grad" not in leave_out:
-        got["state"] = ins["state_grad"].cpu().numpy()
-    return got
+    """one call of fz_run_block_ring_grad_stream_major / fz_run_block_ring_loss_grad_stream_major through grad_harness.launch: the
+    time-major draw d in stream-major buffers of `rows` rows with the block at [row0, row0 + T)"""
+    return H.launch(p, d, ring=True, loss=loss, window=(rows, row0), c=c, state_grad=state_grad, alias=alias, leave_out=leave_out, k=k,
+                    frames=frames)
 
 
 def time_major(p, d, loss, c=0, state_grad=True, k=K):
@@ -180,12 +79,7 @@ def time_major(p, d, loss, c=0, state_grad=True, k=K):
 
 
 def check(p, got, want, what, keys=LOSS_KEYS):
-    n = {"state": p.n_state, "params": p.n_param, "consts": p.n_const}
-    for key in keys:
-        if key not in got or key not in want:
-            continue
-        g, w = (got[key][:n[key]], np.asarray(want[key])[:n[key]]) if key in n else (got[key], np.asarray(want[key]))
-        assert same(g, w), f"{what}: {key} differs in {int((~((g.view(np.uint32) == np.asarray(w, F32).view(np.uint32)) | (np.isnan(g) & np.isnan(w)))).sum())} of {g.size}"
+    H.check(p, got, want, what, keys)
 
 
 def present(p, loss):

@@ -6,8 +6,10 @@ import pytest
 
 import adjoint_ref_trig as AT
 import fn_ref as R
+import grad_harness as H
 import pcm16_ref as PR
 import trig_cells as TC
+from grad_harness import dev, make_inputs, on_gpu, on_gpu_sm
 from test_graph_functions_bodies_gpu import run
 from test_graph_functions_gpu import ndiff
 
@@ -97,16 +99,17 @@ def test_pcm16_stream_major_window_wavefolder(F):
 
 
 # ---- backward ------------------------------------------------------------------------------------------------------------------
+def check(p, got, want, what):
+    H.check(p, got, want, what, H.GRAD_KEYS)
+
+
 def grad_inputs(p, ns, T, seed):
-    from test_grad_gpu import make_inputs
     return make_inputs(p, "trig", ns, T, seed, ties=False, draw_params=lambda p_, n, rng: rng.uniform(0.01, 0.5, (p_.n_param, n)).astype(F32))
 
 
 @pytest.mark.parametrize("name", TC.GRAD_GRAPHS)
 @pytest.mark.parametrize("C", [0, 4])
 def test_both_adjoint_kernels_match_the_restatement_and_each_other(F, name, C):
-    from test_grad_gpu import check, on_gpu
-    from test_grad_stream_major_gpu import on_gpu_sm
     p = TC.graph(name)
     ns, T = 130, 37
     x, s0, par, yb, sb, ap, ac = grad_inputs(p, ns, T, 21)
@@ -122,7 +125,6 @@ def test_both_adjoint_kernels_match_the_restatement_and_each_other(F, name, C):
 
 @pytest.mark.parametrize("name", TC.GRAD_GRAPHS)
 def test_two_chained_blocks_give_one_block_of_2T(F, name):
-    from test_grad_gpu import check, dev, on_gpu
     p = TC.graph(name)
     ns, T = 130, 37
     x, s0, par, yb, sb, ap, ac = grad_inputs(p, ns, 2 * T, 23)

@@ -213,7 +213,7 @@ def test_float_sine_and_cosine_equal_the_c_checker():
 # ---- backward ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", sorted(GG.SUPPORTED))
 def test_extended_restatement_gives_the_bits_of_adjoint_ref_on_graphs_without_the_new_kinds(name):
-    from test_grad_gpu import make_inputs, same
+    from grad_harness import make_inputs, same
     p = F.compile(F.from_sexpr(GG.SUPPORTED[name]()))
     x, s0, par, yb, sb, ap, ac = make_inputs(p, name, 5, 7, 31)
     a, b = A.grad(p, x, yb, s0, par, sb, ap, ac), AT.grad(p, x, yb, s0, par, sb, ap, ac)

@@ -44,6 +44,42 @@ def _apply_consts(prog: Program, consts):
         prog.set_const(k, v)
 
 
+def _front_door(prog: Program, x, consts, rings):
+    """the checks every public function starts with, in this order: the graph is supported, 2-D frames have one input wire, consts fit"""
+    if rings:
+        if not prog.ring_grad_supported():
+            raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
+    elif not prog.grad_supported():
+        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.grad_unsupported_reason())
+    if x.dim() == 2 and prog.n_in != 1:
+        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
+    if consts is not None:
+        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
+            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
+
+
+def _backward_call(prog: Program, rings, stream_major, loss=False, recording=False):
+    """the bound Program method of one corner of the backward family"""
+    name = ("run_recording_" if recording else "run_block_") + ("ring_" if rings else "") + ("loss_grad" if loss else "grad")
+    return getattr(prog, name + ("_stream_major" if stream_major and not recording else ""))
+
+
+_WANT = ("x", "state", "params", "consts")
+
+
+def _want(needs):
+    """the gradients to ask the launch for, from needs_input_grad of (x, state, params, consts)"""
+    return [k for k, n in zip(_WANT, needs) if n]
+
+
+def _grads(prog: Program, r, needs, x_shape, consts):
+    """(dx, dstate, dparams, dconsts) from the dict a launch returned, None where not needed"""
+    need_x, need_s, need_p, need_c = needs
+    return (r["x"].reshape(x_shape) if need_x else None, r["state"] if need_s else None, r["params"] if need_p else None,
+            # per-stream coefficient adjoints, summed over the streams in float64
+            r["consts"][:prog.n_const].double().sum(1).to(consts.dtype).to(consts.device) if need_c else None)
+
+
 class _Block(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prog, x, state, params, consts, stream_major=False, rings=False):
@@ -64,8 +100,8 @@ class _Block(torch.autograd.Function):
     def backward(ctx, gy, gs):
         prog = ctx.prog
         x, state, params = ctx.saved_tensors
-        _, need_x, need_s, need_p, need_c = ctx.needs_input_grad[:5]
-        want = [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
+        needs = ctx.needs_input_grad[1:5]
+        want = _want(needs)
         if not want:
             return None, None, None, None, None, None, None
         xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
@@ -73,20 +109,17 @@ class _Block(torch.autograd.Function):
             gy = torch.zeros(tuple(xx.shape[:2]) + (prog.n_out,), dtype=torch.float32, device=x.device)
         sg = gs.contiguous() if gs is not None and prog.n_state else None
         _apply_consts(prog, ctx.consts)                               # (the constants of the forward launch)
-        if ctx.rings:
-            bwd = prog.run_block_ring_grad_stream_major if ctx.stream_major else prog.run_block_ring_grad
-        else:
-            bwd = prog.run_block_grad_stream_major if ctx.stream_major else prog.run_block_grad
-        r = bwd(xx, gy.contiguous(), state.detach() if state is not None else None,
-                params.detach() if params is not None else None, state_grad=sg, want=want)
-        gx = r["x"].reshape(ctx.x_shape) if need_x else None
-        gst = r["state"] if need_s else None
-        gp = r["params"] if need_p else None
-        gc = None
-        if need_c:
-            # per-stream coefficient adjoints, summed over the streams in float64
-            gc = r["consts"][:prog.n_const].double().sum(1).to(ctx.consts.dtype).to(ctx.consts.device)
-        return None, gx, gst, gp, gc, None, None
+        r = _backward_call(prog, ctx.rings, ctx.stream_major)(
+            xx, gy.contiguous(), state.detach() if state is not None else None,
+            params.detach() if params is not None else None, state_grad=sg, want=want)
+        return (None,) + _grads(prog, r, needs, ctx.x_shape, ctx.consts) + (None, None)
+
+
+def _run(prog, x, state, params, consts, stream_major, rings):
+    _front_door(prog, x, consts, rings)
+    if state is None:
+        state = torch.zeros((max(prog.n_state, 1), x.shape[0 if stream_major else 1]), dtype=torch.float32, device=x.device)
+    return _Block.apply(prog, x, state, params, consts, bool(stream_major), rings)
 
 
 def run(prog: Program, x, state=None, params=None, consts=None, stream_major=False):
@@ -95,18 +128,7 @@ def run(prog: Program, x, state=None, params=None, consts=None, stream_major=Fal
     state: the state before the block (None: zeros; never modified), params: [n_param, n_streams] per-stream coefficients,
     consts: an optional CPU float32 tensor [n_const] of uniform coefficient slots (Program.consts() order), applied with
     set_const before the forward launch and again before the backward one (None: the program's current values, constant)."""
-    if not prog.grad_supported():
-        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.grad_unsupported_reason())
-    if x.dim() == 2:
-        if prog.n_in != 1:
-            raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
-    ns = x.shape[0 if stream_major else 1]
-    if state is None:
-        state = torch.zeros((max(prog.n_state, 1), ns), dtype=torch.float32, device=x.device)
-    if consts is not None:
-        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
-            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    return _Block.apply(prog, x, state, params, consts, bool(stream_major))
+    return _run(prog, x, state, params, consts, stream_major, False)
 
 
 def run_rings(prog: Program, x, state=None, params=None, consts=None, stream_major=False):
@@ -116,44 +138,40 @@ def run_rings(prog: Program, x, state=None, params=None, consts=None, stream_maj
     consecutive blocks back-propagates through time across them, whatever the blocks' lengths against the lines' depths.
     stream_major: the tensor shapes of run(..., stream_major=True) -- x [n_streams, T, n_in], or [n_streams, T] for one input wire --;
     the forward is Program.run_block_stream_major, the backward Program.run_block_ring_grad_stream_major."""
-    if not prog.ring_grad_supported():
-        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
-    if x.dim() == 2 and prog.n_in != 1:
-        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
-    if state is None:
-        state = torch.zeros((max(prog.n_state, 1), x.shape[0 if stream_major else 1]), dtype=torch.float32, device=x.device)
-    if consts is not None:
-        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
-            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    return _Block.apply(prog, x, state, params, consts, bool(stream_major), True)
+    return _run(prog, x, state, params, consts, stream_major, True)
 
 
 class _Mse(torch.autograd.Function):
+    """the loss of one block, or (block_rows not None) of a whole recording, which also returns the state after it"""
+
     @staticmethod
-    def forward(ctx, prog, x, target, state, params, consts, stream_major=False, rings=False):
+    def forward(ctx, prog, x, target, state, params, consts, stream_major, rings, block_rows):
         _apply_consts(prog, consts)
-        _, need_x, _, need_s, need_p, need_c = ctx.needs_input_grad[:6]
-        want = ["loss"] + [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
+        recording = block_rows is not None
+        needs = (ctx.needs_input_grad[1],) + tuple(ctx.needs_input_grad[3:6])
+        want = ["loss"] + (["state_out"] if recording else []) + _want(needs)
         xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
         n = xx.shape[0] * xx.shape[1] * prog.n_out                    # elements of y: the mean is over all of them
-        if rings:
-            bwd = prog.run_block_ring_loss_grad_stream_major if stream_major else prog.run_block_ring_loss_grad
-        else:
-            bwd = prog.run_block_loss_grad_stream_major if stream_major else prog.run_block_loss_grad
-        # the one launch: the loss and every gradient asked for, dL/dy = (y - target) * 2 / n formed in the kernel
-        r = bwd(xx, target.detach().contiguous(), state.detach() if state is not None else None,
-                params.detach() if params is not None else None, grad_scale=2.0 / n, want=want)
-        ctx.grads = (r["x"].reshape(x.shape) if need_x else None, r["state"] if need_s else None, r["params"] if need_p else None,
-                     # per-stream coefficient adjoints, summed over the streams in float64
-                     r["consts"][:prog.n_const].double().sum(1).to(consts.dtype).to(consts.device) if need_c else None)
-        return (r["loss"].double().sum() / n).to(torch.float32)       # per-stream sums of e * e, summed over the streams in float64
+        kw = {}
+        if recording:
+            kw = {"block_rows": int(block_rows)} if rings else {"block_rows": int(block_rows), "stream_major": bool(stream_major)}
+        # the one call: the loss and every gradient asked for, dL/dy = (y - target) * 2 / n formed in the kernel
+        r = _backward_call(prog, rings, stream_major, True, recording)(
+            xx, target.detach().contiguous(), state.detach() if state is not None else None,
+            params.detach() if params is not None else None, grad_scale=2.0 / n, want=want, **kw)
+        ctx.grads = _grads(prog, r, needs, x.shape, consts)
+        loss = (r["loss"].double().sum() / n).to(torch.float32)       # per-stream sums of e * e, summed over the streams in float64
+        if not recording:
+            return loss
+        ctx.mark_non_differentiable(r["state_out"])
+        return loss, r["state_out"]
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g):
-        gx, gs, gp, gc = ctx.grads
-        scaled = lambda t: None if t is None else t * g.to(t.device)   # noqa: E731  (the upstream scalar)
-        return None, scaled(gx), None, scaled(gs), scaled(gp), scaled(gc), None, None
+    def backward(ctx, g, _gs=None):
+        scaled = lambda t: None if t is None else t * g.to(t.device)   # noqa: E731  (the upstream scalar on what the forward launch left)
+        gx, gs, gp, gc = map(scaled, ctx.grads)
+        return None, gx, None, gs, gp, gc, None, None, None
 
 
 def mse(prog: Program, x, target, state=None, params=None, consts=None, stream_major=False):
@@ -162,14 +180,8 @@ def mse(prog: Program, x, target, state=None, params=None, consts=None, stream_m
     include/flowz_hip.h: fz_run_block_loss_grad): y and dL/dy never cross HBM, dL/dx is computed only if x requires a gradient, and
     backward() applies the upstream scalar to the gradients that launch left.  x, state, params, consts and stream_major as for
     run(); target is laid out like y.  It covers one block and does not return the state after it: chaining blocks stays with run()."""
-    if not prog.grad_supported():
-        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.grad_unsupported_reason())
-    if x.dim() == 2 and prog.n_in != 1:
-        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
-    if consts is not None:
-        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
-            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), False)
+    _front_door(prog, x, consts, False)
+    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), False, None)
 
 
 def mse_rings(prog: Program, x, target, state=None, params=None, consts=None, stream_major=False):
@@ -178,40 +190,8 @@ def mse_rings(prog: Program, x, target, state=None, params=None, consts=None, st
     (Program.run_block_ring_loss_grad, include/flowz_hip.h: fz_run_block_ring_loss_grad); backward() applies the upstream scalar.
     stream_major: the tensor shapes of mse(..., stream_major=True), a [batch, time] tensor as it lies for one wire
     (Program.run_block_ring_loss_grad_stream_major)."""
-    if not prog.ring_grad_supported():
-        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
-    if x.dim() == 2 and prog.n_in != 1:
-        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
-    if consts is not None:
-        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
-            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), True)
-
-
-class _MseRecording(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, prog, x, target, state, params, consts, block_rows=0, stream_major=False, rings=False):
-        _apply_consts(prog, consts)
-        _, need_x, _, need_s, need_p, need_c = ctx.needs_input_grad[:6]
-        want = ["loss", "state_out"] + [k for k, n in (("x", need_x), ("state", need_s), ("params", need_p), ("consts", need_c)) if n]
-        xx = x.detach() if x.dim() == 3 else x.detach().unsqueeze(-1)
-        n = xx.shape[0] * xx.shape[1] * prog.n_out                    # elements of y: the mean is over all of them
-        kw = {} if rings else {"stream_major": bool(stream_major)}
-        r = (prog.run_recording_ring_loss_grad if rings else prog.run_recording_loss_grad)(
-            xx, target.detach().contiguous(), state.detach() if state is not None else None,
-            params.detach() if params is not None else None, grad_scale=2.0 / n, want=want, block_rows=int(block_rows), **kw)
-        ctx.grads = (r["x"].reshape(x.shape) if need_x else None, r["state"] if need_s else None, r["params"] if need_p else None,
-                     # per-stream coefficient adjoints, summed over the streams in float64
-                     r["consts"][:prog.n_const].double().sum(1).to(consts.dtype).to(consts.device) if need_c else None)
-        ctx.mark_non_differentiable(r["state_out"])
-        return (r["loss"].double().sum() / n).to(torch.float32), r["state_out"]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g, _gs):
-        gx, gs, gp, gc = ctx.grads
-        scaled = lambda t: None if t is None else t * g.to(t.device)   # noqa: E731  (the upstream scalar)
-        return None, scaled(gx), None, scaled(gs), scaled(gp), scaled(gc), None, None, None
+    _front_door(prog, x, consts, True)
+    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), True, None)
 
 
 def mse_recording(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0, stream_major=False):
@@ -220,14 +200,8 @@ def mse_recording(prog: Program, x, target, state=None, params=None, consts=None
     next call).  The workspace is bounded (Program.recording_workspace_bytes: the state before every block of block_rows rows plus
     one block's checkpoints; block_rows = 0 lets the library choose), where mse() over the same rows keeps a checkpoint every few rows
     of the whole recording.  The gradients have the bits of mse()'s over the same rows.  Time-major frames need block_rows % 4 == 0."""
-    if not prog.grad_supported():
-        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.grad_unsupported_reason())
-    if x.dim() == 2 and prog.n_in != 1:
-        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
-    if consts is not None:
-        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
-            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    loss, state_out = _MseRecording.apply(prog, x, target, state, params, consts, int(block_rows), bool(stream_major))
+    _front_door(prog, x, consts, False)
+    loss, state_out = _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), False, int(block_rows))
     return loss, state_out.detach()
 
 
@@ -236,12 +210,6 @@ def mse_recording_rings(prog: Program, x, target, state=None, params=None, const
     returns (loss, state_out) over a whole recording in bounded workspace (Program.ring_recording_workspace_bytes: the state before every
     block plus one block's checkpoints and tape; block_rows = 0 lets the library choose, otherwise a multiple of 4).  The gradients
     have the bits of mse_rings()'s over the same rows (include/flowz_hip.h: fz_run_recording_ring_loss_grad)."""
-    if not prog.ring_grad_supported():
-        raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
-    if x.dim() == 2 and prog.n_in != 1:
-        raise FlowzError(C.FZ_E_INVALID, f"x: two-dimensional frames are for one input wire, the graph has {prog.n_in}")
-    if consts is not None:
-        if consts.device.type != "cpu" or consts.dtype != torch.float32 or tuple(consts.shape) != (prog.n_const,):
-            raise FlowzError(C.FZ_E_INVALID, f"consts: a CPU float32 tensor of shape ({prog.n_const},)")
-    loss, state_out = _MseRecording.apply(prog, x, target, state, params, consts, int(block_rows), False, True)
+    _front_door(prog, x, consts, True)
+    loss, state_out = _Mse.apply(prog, x, target, state, params, consts, False, True, int(block_rows))
     return loss, state_out.detach()

@@ -320,6 +320,61 @@ def _check_frames(x, last, what="x"):
     return x
 
 
+# ---- marshalling: each takes the C function and its leading arguments, and appends the out-parameter(s) the idiom ends in ----------
+def _resources(fn, *args) -> dict:
+    """fz_kernel_resources out-parameter -> dict of its fields"""
+    r = C.KernelResources()
+    C.check(fn(*args, ctypes.byref(r)))
+    return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+
+
+def _name(fn, *args, size: int = 160) -> str:
+    """(char* buf, size) of a fixed-size name"""
+    buf = ctypes.create_string_buffer(size)
+    C.check(fn(*args, buf, size))
+    return buf.value.decode()
+
+
+def _text(fn, *args) -> str:
+    """(char* buf, size) of a text of any length: asked for the length first, then for the text"""
+    n = C.check(fn(*args, None, 0))
+    buf = ctypes.create_string_buffer(n + 1)
+    C.check(fn(*args, buf, n + 1))
+    return buf.value.decode()
+
+
+def _out(ctype, fn, *args) -> int:
+    """an integer out-parameter of type ctype (ctypes.c_uint32 / ctypes.c_uint64)"""
+    v = ctype()
+    C.check(fn(*args, ctypes.byref(v)))
+    return int(v.value)
+
+
+def _window(x, row0, n_samples, in_grad):
+    """the window of a stream-major front door as Program._run_grad takes it: (row0, rows of the block, in_grad); n_samples None: to the
+    last row of x"""
+    return int(row0), (x.shape[1] - int(row0)) if n_samples is None else int(n_samples), in_grad
+
+
+# the C entry point of Program._run_grad by (ring, loss, stream-major window, recording); the ring recordings are time-major only
+_GRAD_ENTRY = {
+    (False, False, False, False): "fz_run_block_grad",
+    (False, True, False, False): "fz_run_block_loss_grad",
+    (False, False, True, False): "fz_run_block_grad_stream_major",
+    (False, True, True, False): "fz_run_block_loss_grad_stream_major",
+    (True, False, False, False): "fz_run_block_ring_grad",
+    (True, True, False, False): "fz_run_block_ring_loss_grad",
+    (True, False, True, False): "fz_run_block_ring_grad_stream_major",
+    (True, True, True, False): "fz_run_block_ring_loss_grad_stream_major",
+    (False, False, False, True): "fz_run_recording_grad",
+    (False, True, False, True): "fz_run_recording_loss_grad",
+    (False, False, True, True): "fz_run_recording_grad",
+    (False, True, True, True): "fz_run_recording_loss_grad",
+    (True, False, False, True): "fz_run_recording_ring_grad",
+    (True, True, False, True): "fz_run_recording_ring_loss_grad",
+}
+
+
 class Program:
     """compile() result: lowered graph + its fused gfx950 kernels (flowz.hpp:1233-1249)."""
 
@@ -457,31 +512,22 @@ class Program:
         """Name of the kernel variant that a launch of this shape runs (kernel_symbol: the symbol profilers show).  tile_streams: the frame layout (0 = plain
         time-major rows, as for run_block on a 3-D tensor); stream-major frames: FZ_VF_STREAM_MAJOR in the variant's flags."""
         vp = ctypes.byref(variant) if variant is not None else None
-        buf = ctypes.create_string_buffer(128)
-        C.check(C.lib.fz_program_kernel_name(self._h, vp, int(n_streams), int(n_samples), int(tile_streams), buf, 128))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_kernel_name, self._h, vp, int(n_streams), int(n_samples), int(tile_streams), size=128)
 
     def kernel_symbol(self, variant: Optional[Variant] = None, n_streams: int = 0, n_samples: int = 0, tile_streams: int = 0) -> str:
         """kernel_name + "_g<graph tag>": the symbol in the code object, what rocprofv3 --kernel-trace --stats lists."""
         vp = ctypes.byref(variant) if variant is not None else None
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_kernel_symbol(self._h, vp, int(n_streams), int(n_samples), int(tile_streams), buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_kernel_symbol, self._h, vp, int(n_streams), int(n_samples), int(tile_streams))
 
     def kernel_code_id(self, variant: Optional[Variant] = None, n_streams: int = 0, n_samples: int = 0, tile_streams: int = 0) -> str:
         """16 hex digits naming the CODE of that kernel (hash of generated source + build options + compiler): the code object's file name
         in the kernel cache.  Needs no GPU and builds nothing."""
         vp = ctypes.byref(variant) if variant is not None else None
-        buf = ctypes.create_string_buffer(32)
-        C.check(C.lib.fz_program_kernel_code_id(self._h, vp, int(n_streams), int(n_samples), int(tile_streams), buf, 32))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_kernel_code_id, self._h, vp, int(n_streams), int(n_samples), int(tile_streams), size=32)
 
     def source(self, variant: Optional[Variant] = None) -> str:
         vp = ctypes.byref(variant) if variant is not None else None
-        n = C.check(C.lib.fz_program_source(self._h, vp, None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_source(self._h, vp, buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_source, self._h, vp)
 
     def plan(self, n_streams: int, tile_streams: int = 0) -> Variant:
         """The variant a launch of this shape WITHOUT a variant would use on the current device: tuned in this process,
@@ -512,9 +558,7 @@ class Program:
         """registers / LDS / scratch bytes per lane of a variant's kernel (JITs it; needs no GPU).  as_launched: with the
         unroll lowered until nothing spills, as run_block does ('unroll' = what runs); False: the variant exactly as given."""
         vp = ctypes.byref(variant) if variant is not None else None
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_kernel_resources(self._h, vp, int(n_streams), int(n_samples), int(tile_streams), int(as_launched), ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_kernel_resources, self._h, vp, int(n_streams), int(n_samples), int(tile_streams), int(as_launched))
 
     # -- the hot path ----------------------------------------------------------------------
     def run_block_ptr(self, in_ptr, out_ptr, state_ptr, params_ptr, n_streams, n_samples,
@@ -636,24 +680,14 @@ class Program:
     def pcm16_resources(self, in_dtype="int16", out_dtype="int16", n_streams: int = 0) -> dict:
         """registers / scratch bytes of the PCM kernel a block of these frame types and this stream count (0: 2^20) runs (JITs it; needs
         no GPU); 'unroll' = rows per chunk"""
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_pcm16_resources(self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"),
-                                                 int(n_streams), ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_pcm16_resources, self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"), int(n_streams))
 
     def pcm16_kernel_symbol(self, in_dtype="int16", out_dtype="int16", n_streams: int = 0) -> str:
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_pcm16_kernel_symbol(self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"),
-                                                     int(n_streams), buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_pcm16_kernel_symbol, self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"), int(n_streams))
 
     def pcm16_source(self, in_dtype="int16", out_dtype="int16", n_streams: int = 0) -> str:
         """the PCM kernel's whole source: generated configuration and body, the common head, the PCM frame walk"""
-        it, ot = self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype")
-        n = C.check(C.lib.fz_program_pcm16_source(self._h, it, ot, int(n_streams), None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_pcm16_source(self._h, it, ot, int(n_streams), buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_pcm16_source, self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"), int(n_streams))
 
     def run_block_pcm16(self, x, state=None, params=None, out=None, out_dtype=None):
         """run_block with 16-bit PCM frames on one side or on both: x is a CUDA int16 or float32 tensor [T, n_streams, n_in] (or
@@ -694,24 +728,14 @@ class Program:
     def pcm16_stream_major_resources(self, in_dtype="int16", out_dtype="int16") -> dict:
         """registers / scratch / LDS bytes of the kernel a stream-major PCM block of these frame types runs (JITs it; needs no GPU);
         'unroll' = rows per chunk"""
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_pcm16_stream_major_resources(self._h, self._frame_type(in_dtype, "in_dtype"),
-                                                              self._frame_type(out_dtype, "out_dtype"), ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_pcm16_stream_major_resources, self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"))
 
     def pcm16_stream_major_kernel_symbol(self, in_dtype="int16", out_dtype="int16") -> str:
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_pcm16_stream_major_kernel_symbol(self._h, self._frame_type(in_dtype, "in_dtype"),
-                                                                  self._frame_type(out_dtype, "out_dtype"), buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_pcm16_stream_major_kernel_symbol, self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"))
 
     def pcm16_stream_major_source(self, in_dtype="int16", out_dtype="int16") -> str:
         """that kernel's whole source: generated configuration and body, the common head, the stream-major PCM walk"""
-        it, ot = self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype")
-        n = C.check(C.lib.fz_program_pcm16_stream_major_source(self._h, it, ot, None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_pcm16_stream_major_source(self._h, it, ot, buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_pcm16_stream_major_source, self._h, self._frame_type(in_dtype, "in_dtype"), self._frame_type(out_dtype, "out_dtype"))
 
     def run_block_pcm16_stream_major(self, x, state=None, params=None, out=None, out_dtype=None, row0=0, n_samples=None):
         """run_block_stream_major with 16-bit PCM frames on one side or on both: x is a CUDA int16 or float32 tensor
@@ -764,28 +788,19 @@ class Program:
         return "" if self.grad_supported() else C.last_error()
 
     def grad_workspace_bytes(self, n_streams: int, T: int, checkpoint_rows: int = 0) -> int:
-        b = ctypes.c_uint64()
-        C.check(C.lib.fz_program_grad_workspace(self._h, int(n_streams), int(T), int(checkpoint_rows), ctypes.byref(b)))
-        return int(b.value)
+        return _out(ctypes.c_uint64, C.lib.fz_program_grad_workspace, self._h, int(n_streams), int(T), int(checkpoint_rows))
 
     def grad_resources(self, checkpoint_rows: int = 0, stream_major: bool = False) -> dict:
         """registers / scratch / LDS bytes of the adjoint kernel (JITs it; needs no GPU); 'unroll' = the checkpoint stride it uses.
         stream_major: the kernel of run_block_grad_stream_major"""
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_grad_resources_for(self._h, int(checkpoint_rows), int(bool(stream_major)), ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_grad_resources_for, self._h, int(checkpoint_rows), int(bool(stream_major)))
 
     def grad_kernel_symbol(self, checkpoint_rows: int = 0, stream_major: bool = False) -> str:
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_grad_kernel_symbol_for(self._h, int(checkpoint_rows), int(bool(stream_major)), buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_grad_kernel_symbol_for, self._h, int(checkpoint_rows), int(bool(stream_major)))
 
     def grad_source(self, checkpoint_rows: int = 0, stream_major: bool = False) -> str:
         """the adjoint kernel's whole source: generated configuration and body, then the hand-written skeleton"""
-        n = C.check(C.lib.fz_program_grad_source_for(self._h, int(checkpoint_rows), int(bool(stream_major)), None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_grad_source_for(self._h, int(checkpoint_rows), int(bool(stream_major)), buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_grad_source_for, self._h, int(checkpoint_rows), int(bool(stream_major)))
 
     def run_block_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0):
         """Reverse-mode gradients of the block run_block(x, state, params) computes (time-major frames; run_block_grad_stream_major takes [n_streams, rows, wire]): out_grad = dL/dy
@@ -803,8 +818,7 @@ class Program:
         row).  No layout pass (fz_run_block_grad_stream_major), and not a bit differs from run_block_grad on the transposed frames.
         Returns the same dict, "x" laid out like x: only the rows of the window are written.  in_grad: the tensor to write them to
         (returned as "x"), so that consecutive windows fill one tensor; otherwise a new one, zero outside the window."""
-        n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
-        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad))
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad))
 
     # -- the backward of a block with delay lines deeper than 8 samples (fz_run_block_ring_grad): a call family of its own --------------
     def ring_grad_supported(self) -> bool:
@@ -816,27 +830,18 @@ class Program:
         return "" if self.ring_grad_supported() else C.last_error()
 
     def ring_grad_workspace_bytes(self, n_streams: int, T: int, checkpoint_rows: int = 0) -> int:
-        b = ctypes.c_uint64()
-        C.check(C.lib.fz_program_ring_grad_workspace(self._h, int(n_streams), int(T), int(checkpoint_rows), ctypes.byref(b)))
-        return int(b.value)
+        return _out(ctypes.c_uint64, C.lib.fz_program_ring_grad_workspace, self._h, int(n_streams), int(T), int(checkpoint_rows))
 
     def ring_grad_resources(self, c: int = 0, stream_major: bool = False) -> dict:
         """grad_resources() of the kernel of run_block_ring_grad at checkpoint stride c (0: the library default); 'lds_bytes' = the
         adjoint rings of one workgroup.  stream_major: the kernel of run_block_ring_grad_stream_major ('lds_bytes': rings and patches)"""
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_ring_grad_resources_for(self._h, int(c), int(bool(stream_major)), ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_ring_grad_resources_for, self._h, int(c), int(bool(stream_major)))
 
     def ring_grad_kernel_symbol(self, c: int = 0, stream_major: bool = False) -> str:
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_ring_grad_kernel_symbol_for(self._h, int(c), int(bool(stream_major)), buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_ring_grad_kernel_symbol_for, self._h, int(c), int(bool(stream_major)))
 
     def ring_grad_source(self, c: int = 0, stream_major: bool = False) -> str:
-        n = C.check(C.lib.fz_program_ring_grad_source_for(self._h, int(c), int(bool(stream_major)), None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_ring_grad_source_for(self._h, int(c), int(bool(stream_major)), buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_ring_grad_source_for, self._h, int(c), int(bool(stream_major)))
 
     def run_block_ring_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0):
         """run_block_grad for graphs with delay lines deeper than 8 samples (fz_run_block_ring_grad): the same arguments, the same
@@ -848,28 +853,20 @@ class Program:
         """run_block_ring_grad on stream-major buffers (fz_run_block_ring_grad_stream_major): the arguments, windows and result dict of
         run_block_grad_stream_major; not a bit differs from run_block_ring_grad on the transposed frames.  For a graph
         run_block_grad_stream_major takes it is run_block_grad_stream_major."""
-        n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
-        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), ring=True)
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad), ring=True)
 
     # -- the backward under a squared-error loss (fz_run_block_loss_grad): dL/dy formed in the kernel from a target ------------------
     LOSS_GRAD_WANT = GRAD_WANT + ("loss", "out")
 
     def loss_grad_resources(self, checkpoint_rows: int = 0, stream_major: bool = False) -> dict:
         """grad_resources() of the kernel of run_block_loss_grad (stream_major: of run_block_loss_grad_stream_major)"""
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_loss_grad_resources_for(self._h, int(checkpoint_rows), int(bool(stream_major)), ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_loss_grad_resources_for, self._h, int(checkpoint_rows), int(bool(stream_major)))
 
     def loss_grad_kernel_symbol(self, checkpoint_rows: int = 0, stream_major: bool = False) -> str:
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_loss_grad_kernel_symbol_for(self._h, int(checkpoint_rows), int(bool(stream_major)), buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_loss_grad_kernel_symbol_for, self._h, int(checkpoint_rows), int(bool(stream_major)))
 
     def loss_grad_source(self, checkpoint_rows: int = 0, stream_major: bool = False) -> str:
-        n = C.check(C.lib.fz_program_loss_grad_source_for(self._h, int(checkpoint_rows), int(bool(stream_major)), None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_loss_grad_source_for(self._h, int(checkpoint_rows), int(bool(stream_major)), buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_loss_grad_source_for, self._h, int(checkpoint_rows), int(bool(stream_major)))
 
     def run_block_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
                             checkpoint_rows: int = 0):
@@ -885,27 +882,19 @@ class Program:
         """run_block_loss_grad on stream-major buffers, windows as for run_block_grad_stream_major: x [n_streams, rows, n_in], target
         [n_streams, rows, n_out].  in_grad / out: the tensors the window's rows of "x" / "out" are written to (otherwise new ones, zero
         outside the window).  Not a bit differs from run_block_loss_grad on the transposed frames."""
-        n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
-        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), (float(grad_scale), out))
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad), (float(grad_scale), out))
 
     # -- the squared-error backward of a block with delay lines deeper than 8 samples (fz_run_block_ring_loss_grad) -------------------
     def ring_loss_grad_resources(self, c: int = 0, stream_major: bool = False) -> dict:
         """ring_grad_resources() of the kernel of run_block_ring_loss_grad at checkpoint stride c (0: the library default);
         stream_major: of run_block_ring_loss_grad_stream_major"""
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_ring_loss_grad_resources_for(self._h, int(c), int(bool(stream_major)), ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_ring_loss_grad_resources_for, self._h, int(c), int(bool(stream_major)))
 
     def ring_loss_grad_kernel_symbol(self, c: int = 0, stream_major: bool = False) -> str:
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_ring_loss_grad_kernel_symbol_for(self._h, int(c), int(bool(stream_major)), buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_ring_loss_grad_kernel_symbol_for, self._h, int(c), int(bool(stream_major)))
 
     def ring_loss_grad_source(self, c: int = 0, stream_major: bool = False) -> str:
-        n = C.check(C.lib.fz_program_ring_loss_grad_source_for(self._h, int(c), int(bool(stream_major)), None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_ring_loss_grad_source_for(self._h, int(c), int(bool(stream_major)), buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_ring_loss_grad_source_for, self._h, int(c), int(bool(stream_major)))
 
     def run_block_ring_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
                                  checkpoint_rows: int = 0):
@@ -920,40 +909,27 @@ class Program:
         """run_block_ring_loss_grad on stream-major buffers (fz_run_block_ring_loss_grad_stream_major): the arguments, windows and
         result dict of run_block_loss_grad_stream_major; not a bit differs from run_block_ring_loss_grad on the transposed frames.  For
         a graph run_block_loss_grad_stream_major takes it is run_block_loss_grad_stream_major."""
-        n = (x.shape[1] - int(row0)) if n_samples is None else int(n_samples)
-        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, (int(row0), n, in_grad), (float(grad_scale), out),
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad), (float(grad_scale), out),
                               ring=True)
 
     # -- the backward of a whole recording (fz_run_recording_grad): two-level checkpointing over the calls above ---------------------
     def recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
         """the rows per block a recording of T rows is cut into (block_rows = 0: the library's choice; include/flowz_hip.h has the rule)"""
-        b = ctypes.c_uint32()
-        C.check(C.lib.fz_program_recording_block_rows(self._h, int(T), int(block_rows), int(checkpoint_rows), ctypes.byref(b)))
-        return int(b.value)
+        return _out(ctypes.c_uint32, C.lib.fz_program_recording_block_rows, self._h, int(T), int(block_rows), int(checkpoint_rows))
 
     def recording_workspace_bytes(self, n_streams: int, T: int, block_rows: int = 0, checkpoint_rows: int = 0, stream_major: bool = False) -> int:
         """workspace bytes of run_recording_grad / run_recording_loss_grad: the block-start states, then one block's checkpoints"""
-        b = ctypes.c_uint64()
-        C.check(C.lib.fz_program_recording_workspace(self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows), int(bool(stream_major)),
-                                                     ctypes.byref(b)))
-        return int(b.value)
+        return _out(ctypes.c_uint64, C.lib.fz_program_recording_workspace, self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows), int(bool(stream_major)))
 
     def states_resources(self, stream_major: bool = False) -> dict:
         """grad_resources() of the block-start-states kernel of a recording; 'unroll' = the rows of its unrolled group"""
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_states_resources(self._h, int(bool(stream_major)), ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_states_resources, self._h, int(bool(stream_major)))
 
     def states_kernel_symbol(self, stream_major: bool = False) -> str:
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_states_kernel_symbol(self._h, int(bool(stream_major)), buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_states_kernel_symbol, self._h, int(bool(stream_major)))
 
     def states_source(self, stream_major: bool = False) -> str:
-        n = C.check(C.lib.fz_program_states_source(self._h, int(bool(stream_major)), None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_states_source(self._h, int(bool(stream_major)), buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_states_source, self._h, int(bool(stream_major)))
 
     def run_recording_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0,
                            block_rows: int = 0, stream_major: bool = False, row0: int = 0, n_samples: Optional[int] = None, in_grad=None,
@@ -963,9 +939,7 @@ class Program:
         (0: the library's choice), then the blocks are differentiated from the last to the first.  Every bit is run_block_grad's over
         the same rows.  want may also name "state_out": the state after the last row (the bits of run_block's).  workspace: a float32
         tensor of at least recording_workspace_bytes to use (otherwise one is allocated).  Returns the dict of run_block_grad."""
-        window = None
-        if stream_major:
-            window = (int(row0), (x.shape[1] - int(row0)) if n_samples is None else int(n_samples), in_grad)
+        window = _window(x, row0, n_samples, in_grad) if stream_major else None
         return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, None, (int(block_rows), workspace))
 
     def run_recording_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
@@ -973,9 +947,7 @@ class Program:
                                 n_samples: Optional[int] = None, in_grad=None, out=None, workspace=None):
         """run_block_loss_grad (stream_major: run_block_loss_grad_stream_major) over a whole recording, as run_recording_grad is to
         run_block_grad: the same arguments, results and bits as the one-launch call over the same rows, plus "state_out" in want."""
-        window = None
-        if stream_major:
-            window = (int(row0), (x.shape[1] - int(row0)) if n_samples is None else int(n_samples), in_grad)
+        window = _window(x, row0, n_samples, in_grad) if stream_major else None
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, window, (float(grad_scale), out),
                               (int(block_rows), workspace))
 
@@ -983,33 +955,22 @@ class Program:
     def ring_recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
         """the rows per block run_recording_ring_grad cuts a recording of T rows into (block_rows = 0: the library's choice, which
         counts the tape of the deep lines; include/flowz_hip.h has the rule)"""
-        b = ctypes.c_uint32()
-        C.check(C.lib.fz_program_ring_recording_block_rows(self._h, int(T), int(block_rows), int(checkpoint_rows), ctypes.byref(b)))
-        return int(b.value)
+        return _out(ctypes.c_uint32, C.lib.fz_program_ring_recording_block_rows, self._h, int(T), int(block_rows), int(checkpoint_rows))
 
     def ring_recording_workspace_bytes(self, n_streams: int, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
         """workspace bytes of run_recording_ring_grad / run_recording_ring_loss_grad: the block-start states, then one block's ring workspace"""
-        b = ctypes.c_uint64()
-        C.check(C.lib.fz_program_ring_recording_workspace(self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows), ctypes.byref(b)))
-        return int(b.value)
+        return _out(ctypes.c_uint64, C.lib.fz_program_ring_recording_workspace, self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows))
 
     def ring_states_resources(self) -> dict:
         """grad_resources() of the block-start-states kernel of a ring recording; 'unroll' = the rows of its unrolled group, 'lds_bytes' =
         the value rings of one workgroup (the ring adjoint kernel's bytes)"""
-        r = C.KernelResources()
-        C.check(C.lib.fz_program_ring_states_resources(self._h, ctypes.byref(r)))
-        return {n: getattr(r, n) for n, _ in C.KernelResources._fields_}
+        return _resources(C.lib.fz_program_ring_states_resources, self._h)
 
     def ring_states_kernel_symbol(self) -> str:
-        buf = ctypes.create_string_buffer(160)
-        C.check(C.lib.fz_program_ring_states_kernel_symbol(self._h, buf, 160))
-        return buf.value.decode()
+        return _name(C.lib.fz_program_ring_states_kernel_symbol, self._h)
 
     def ring_states_source(self) -> str:
-        n = C.check(C.lib.fz_program_ring_states_source(self._h, None, 0))
-        buf = ctypes.create_string_buffer(n + 1)
-        C.check(C.lib.fz_program_ring_states_source(self._h, buf, n + 1))
-        return buf.value.decode()
+        return _text(C.lib.fz_program_ring_states_source, self._h)
 
     def run_recording_ring_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0,
                                 block_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None, in_grad=None, workspace=None):
@@ -1137,25 +1098,16 @@ class Program:
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
         hs = torch.cuda.current_stream().cuda_stream
-        if recording is not None and ring:
-            fn = C.lib.fz_run_recording_ring_grad if loss is None else C.lib.fz_run_recording_ring_loss_grad
+        fn = getattr(C.lib, _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
+        if recording is not None and ring:                            # ring recording
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
-        elif recording is not None:
-            fn = C.lib.fz_run_recording_grad if loss is None else C.lib.fz_run_recording_loss_grad
+        elif recording is not None:                                   # recording, either layout
             w = (int(rows), row0) if window is not None else (0, 0)
             C.check(fn(self._h, ctypes.byref(a), int(window is not None), int(ns), w[0], w[1], int(T), recording[0],
                        ptr(out.get("state_out"), self.n_state), hs))
-        elif window is None:
-            if ring:
-                fn = C.lib.fz_run_block_ring_grad if loss is None else C.lib.fz_run_block_ring_loss_grad
-            else:
-                fn = C.lib.fz_run_block_grad if loss is None else C.lib.fz_run_block_loss_grad
+        elif window is None:                                          # block
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(T), hs))
-        else:
-            if ring:
-                fn = C.lib.fz_run_block_ring_grad_stream_major if loss is None else C.lib.fz_run_block_ring_loss_grad_stream_major
-            else:
-                fn = C.lib.fz_run_block_grad_stream_major if loss is None else C.lib.fz_run_block_loss_grad_stream_major
+        else:                                                         # block window
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, T, hs))
         return out
 
