@@ -23,6 +23,79 @@ struct fz_bank {
    hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_run[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
 };
 
+// ---- the pipeline of the host-frames paths (bank_process_host, bank_process_host_stream_major below) ---------------------------------
+static void drain_pipeline(fz_bank* b)
+{
+   for (hipStream_t st : {b->s_h2d, b->s_run, b->s_d2h})
+      if (st) (void)hipStreamSynchronize(st);
+}
+
+// the three streams and six events of the pipelined host paths (created on first use, destroyed with the bank)
+static void ensure_pipeline(fz_bank* b)
+{
+   if (b->s_h2d) return;
+   FZ_HIP(hipStreamCreateWithFlags(&b->s_h2d, hipStreamNonBlocking));
+   FZ_HIP(hipStreamCreateWithFlags(&b->s_run, hipStreamNonBlocking));
+   FZ_HIP(hipStreamCreateWithFlags(&b->s_d2h, hipStreamNonBlocking));
+   for (int i = 0; i < 2; ++i) {
+      FZ_HIP(hipEventCreateWithFlags(&b->ev_in[i], hipEventDisableTiming));
+      FZ_HIP(hipEventCreateWithFlags(&b->ev_run[i], hipEventDisableTiming));
+      FZ_HIP(hipEventCreateWithFlags(&b->ev_out[i], hipEventDisableTiming));
+   }
+}
+
+// bytes per direction and pipeline slot of a time chunk: 32 MiB (developer switch FLOWZ_HIP_HOST_CHUNK_BYTES, read at every call:
+// another size, so that a test reaches the pipelines' second and third chunk with kilobytes instead of 64 MiB)
+static size_t host_chunk_bytes()
+{
+   if (const char* e = std::getenv("FLOWZ_HIP_HOST_CHUNK_BYTES"))
+      if (const unsigned long long n = std::strtoull(e, nullptr, 10)) return (size_t)n;
+   return 32u << 20;
+}
+
+// The pipeline of both host-frames paths: a block cut along TIME into chunks of chunk_t rows that flow through three stages on three HIP
+// streams -- H2D of chunk k+1, the kernel of chunk k and D2H of chunk k-1 overlap; the recurrence only orders the kernels, which run
+// back to back on one stream.  The chunks alternate between two slots of the bank's staging buffers: upload(slot, t0, nt) enqueues the
+// copy of rows [t0, t0 + nt) into a slot on s_h2d (has_input: the graph has input wires at all), run(slot, t0, nt) launches on s_run
+// and returns a code, download(slot, t0, nt) enqueues the copy out on s_d2h.  With pinned host memory (hipHostMalloc / hipHostRegister /
+// torch pin_memory) both PCIe directions run concurrently; pageable memory still works, HIP then stages the copies itself.
+template <class Upload, class Run, class Download>
+static int run_pipeline(fz_bank* b, uint32_t n_samples, uint32_t chunk_t, bool has_input, Upload upload, Run run, Download download)
+{
+   ensure_pipeline(b);
+   FZ_HIP(hipDeviceSynchronize());                          // the bank's state may still be in use on other streams
+   uint32_t k = 0;
+   for (uint32_t t0 = 0; t0 < n_samples; t0 += chunk_t, ++k) {
+      const uint32_t nt = std::min(chunk_t, n_samples - t0);
+      const int slot = (int)(k & 1u);
+      if (has_input) {
+         if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_h2d, b->ev_run[slot], 0));        // kernel k-2 has consumed this slot
+         upload(slot, t0, nt);
+         FZ_HIP(hipEventRecord(b->ev_in[slot], b->s_h2d));
+         FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_in[slot], 0));
+      }
+      if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_out[slot], 0));            // D2H k-2 has drained this slot
+      int rc = FZ_OK;
+      try {
+         rc = run(slot, t0, nt);
+      } catch (...) {                                       // chunks already in flight still write into the caller's memory
+         drain_pipeline(b);
+         throw;
+      }
+      if (rc != FZ_OK) {
+         drain_pipeline(b);
+         return rc;
+      }
+      FZ_HIP(hipEventRecord(b->ev_run[slot], b->s_run));
+      FZ_HIP(hipStreamWaitEvent(b->s_d2h, b->ev_run[slot], 0));
+      download(slot, t0, nt);
+      FZ_HIP(hipEventRecord(b->ev_out[slot], b->s_d2h));
+   }
+   FZ_HIP(hipStreamSynchronize(b->s_d2h));
+   FZ_HIP(hipStreamSynchronize(b->s_run));
+   return FZ_OK;
+}
+
 extern "C" {
 
 // ---- fz_bank -------------------------------------------------------------------------------------------------
@@ -192,19 +265,8 @@ static void ensure_stage(fz_bank* b, size_t ib, size_t ob)
    }
 }
 
-static void drain_pipeline(fz_bank* b)
-{
-   for (hipStream_t st : {b->s_h2d, b->s_run, b->s_d2h})
-      if (st) (void)hipStreamSynchronize(st);
-}
-
 // Host frames in, host frames out.  Short blocks (the per-sample call protocol) take one synchronous
-// H2D / kernel / D2H round trip.  Long blocks are cut along TIME into chunks that flow through a
-// three-stage pipeline on three HIP streams -- H2D of chunk k+1, the kernel of chunk k and D2H of chunk
-// k-1 overlap (time-major frames: a time chunk is contiguous; the recurrence only orders the kernels,
-// which run back to back on one stream).  With pinned host memory (hipHostMalloc / hipHostRegister /
-// torch pin_memory) both PCIe directions run concurrently; pageable memory still works, HIP then
-// stages the copies itself.
+// H2D / kernel / D2H round trip.  Long blocks go through run_pipeline (time-major frames: a time chunk is contiguous).
 // (frames: float32 in and out, float32 in and float64 out, or int16 in and out -- fz_bank_process_host_pcm16)
 enum class HostFrames { F32, OutF64, Pcm16 };
 static int bank_process_host(fz_bank* b, const void* in_host, void* out_host, uint32_t n_samples, HostFrames frames)
@@ -226,10 +288,10 @@ static int bank_process_host(fz_bank* b, const void* in_host, void* out_host, ui
          return fz::launch(b->prog, g.n_in ? din : nullptr, dout, g.n_state ? b->state : nullptr, b->params, b->n_streams, nt, uv, stream,
                            0, 0, 0, t0);                       // (sample-rate modulators: this chunk starts at sample t0)
       };
-      constexpr size_t kChunkBytes = 32u << 20;            // per direction and pipeline slot
+      const size_t chunk_bytes = host_chunk_bytes();
       const size_t row = std::max(irow, orow);
-      uint32_t chunk_t = (uint32_t)std::max<size_t>(1, kChunkBytes / std::max<size_t>(row, 1));
-      if ((size_t)n_samples * row <= 2 * kChunkBytes || chunk_t >= n_samples) {                    // one round trip
+      uint32_t chunk_t = (uint32_t)std::max<size_t>(1, chunk_bytes / std::max<size_t>(row, 1));
+      if ((size_t)n_samples * row <= 2 * chunk_bytes || chunk_t >= n_samples) {                    // one round trip
          ensure_stage(b, irow * n_samples, orow * n_samples);
          if (irow) FZ_HIP(hipMemcpy(b->stage_in, in_host, irow * n_samples, hipMemcpyHostToDevice));
          int rc = run(b->stage_in, b->stage_out, n_samples, nullptr, 0);
@@ -241,51 +303,15 @@ static int bank_process_host(fz_bank* b, const void* in_host, void* out_host, ui
       // the second pipeline slot must start 16-byte aligned whatever n_streams and chunk_t are
       const size_t islot = (irow * chunk_t + 255) & ~size_t(255), oslot = (orow * chunk_t + 255) & ~size_t(255);
       ensure_stage(b, 2 * islot, 2 * oslot);
-      if (!b->s_h2d) {
-         FZ_HIP(hipStreamCreateWithFlags(&b->s_h2d, hipStreamNonBlocking));
-         FZ_HIP(hipStreamCreateWithFlags(&b->s_run, hipStreamNonBlocking));
-         FZ_HIP(hipStreamCreateWithFlags(&b->s_d2h, hipStreamNonBlocking));
-         for (int i = 0; i < 2; ++i) {
-            FZ_HIP(hipEventCreateWithFlags(&b->ev_in[i], hipEventDisableTiming));
-            FZ_HIP(hipEventCreateWithFlags(&b->ev_run[i], hipEventDisableTiming));
-            FZ_HIP(hipEventCreateWithFlags(&b->ev_out[i], hipEventDisableTiming));
-         }
-      }
-      FZ_HIP(hipDeviceSynchronize());                       // the bank's state may still be in use on other streams
       const char* hin = reinterpret_cast<const char*>(in_host);
       char* hout = reinterpret_cast<char*>(out_host);
-      uint32_t k = 0;
-      for (uint32_t t0 = 0; t0 < n_samples; t0 += chunk_t, ++k) {
-         const uint32_t nt = std::min(chunk_t, n_samples - t0);
-         const int slot = (int)(k & 1u);
-         float* din = reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_in) + (size_t)slot * islot);
-         float* dout = reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_out) + (size_t)slot * oslot);
-         if (irow) {
-            if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_h2d, b->ev_run[slot], 0));        // kernel k-2 has consumed this slot
-            FZ_HIP(hipMemcpyAsync(din, hin + (size_t)t0 * irow, irow * nt, hipMemcpyHostToDevice, b->s_h2d));
-            FZ_HIP(hipEventRecord(b->ev_in[slot], b->s_h2d));
-            FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_in[slot], 0));
-         }
-         if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_out[slot], 0));            // D2H k-2 has drained this slot
-         int rc = FZ_OK;
-         try {
-            rc = run(din, dout, nt, b->s_run, t0);
-         } catch (...) {                                    // chunks already in flight still write into the caller's memory
-            drain_pipeline(b);
-            throw;
-         }
-         if (rc != FZ_OK) {
-            drain_pipeline(b);
-            return rc;
-         }
-         FZ_HIP(hipEventRecord(b->ev_run[slot], b->s_run));
-         FZ_HIP(hipStreamWaitEvent(b->s_d2h, b->ev_run[slot], 0));
-         FZ_HIP(hipMemcpyAsync(hout + (size_t)t0 * orow, dout, orow * nt, hipMemcpyDeviceToHost, b->s_d2h));
-         FZ_HIP(hipEventRecord(b->ev_out[slot], b->s_d2h));
-      }
-      FZ_HIP(hipStreamSynchronize(b->s_d2h));
-      FZ_HIP(hipStreamSynchronize(b->s_run));
-      return FZ_OK;)
+      auto din = [&](int slot) { return reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_in) + (size_t)slot * islot); };
+      auto dout = [&](int slot) { return reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_out) + (size_t)slot * oslot); };
+      return run_pipeline(
+         b, n_samples, chunk_t, irow != 0,
+         [&](int slot, uint32_t t0, uint32_t nt) { FZ_HIP(hipMemcpyAsync(din(slot), hin + (size_t)t0 * irow, irow * nt, hipMemcpyHostToDevice, b->s_h2d)); },
+         [&](int slot, uint32_t t0, uint32_t nt) { return run(din(slot), dout(slot), nt, b->s_run, t0); },
+         [&](int slot, uint32_t t0, uint32_t nt) { FZ_HIP(hipMemcpyAsync(hout + (size_t)t0 * orow, dout(slot), orow * nt, hipMemcpyDeviceToHost, b->s_d2h)); });)
 }
 
 int fz_bank_process_host(fz_bank* b, const float* in_host, float* out_host, uint32_t n_samples)
@@ -296,7 +322,7 @@ int fz_bank_process_host(fz_bank* b, const float* in_host, float* out_host, uint
 // Host buffers in the reference's own calling convention: one contiguous sample buffer per stream
 // ([n_streams][n_samples][wires]).  Time chunks travel as 2-D copies (one row per stream) into compact
 // device patches [n_streams][chunk][wires], run through the stream-major kernel and travel back; the
-// same three-stream pipeline as the frame path.
+// same pipeline as the frame path.
 // (pcm: int16 samples on both sides through int16 staging and the stream-major PCM kernel -- fz_bank_process_host_pcm16_stream_major;
 //  chunks of whole 32 rows keep every device patch on the 16-byte grid of that kernel's pieces)
 static int bank_process_host_stream_major(fz_bank* b, const void* in_host, void* out_host, uint32_t n_samples, bool pcm)
@@ -308,69 +334,33 @@ static int bank_process_host_stream_major(fz_bank* b, const void* in_host, void*
       const Graph& g = b->prog->g;
       if (g.n_in && !in_host) fail(FZ_E_INVALID, "in_host is null but the graph has input wires");
       const uint32_t nw = std::max<uint32_t>(std::max(g.n_in, g.n_out), 1);
-      // (developer switch FLOWZ_HIP_HOST_CHUNK_BYTES: another chunk size, so that a test reaches the pipeline's second and third chunk
-      //  with kilobytes instead of 64 MiB)
-      size_t kChunkBytes = 32u << 20;
-      if (const char* e = std::getenv("FLOWZ_HIP_HOST_CHUNK_BYTES"))
-         if (const unsigned long long n = std::strtoull(e, nullptr, 10)) kChunkBytes = (size_t)n;
-      uint32_t chunk_t = (uint32_t)std::max<size_t>(32, kChunkBytes / ((size_t)b->n_streams * nw * es) / 32 * 32);
+      uint32_t chunk_t = (uint32_t)std::max<size_t>(32, host_chunk_bytes() / ((size_t)b->n_streams * nw * es) / 32 * 32);
       chunk_t = std::min(chunk_t, (n_samples + 31u) / 32u * 32u);
       const size_t ipitch = (size_t)chunk_t * g.n_in * es, opitch = (size_t)chunk_t * g.n_out * es;     // device rows
       const size_t hip = (size_t)n_samples * g.n_in * es, hop = (size_t)n_samples * g.n_out * es;       // host rows
       ensure_stage(b, 2 * ipitch * b->n_streams, 2 * opitch * b->n_streams);
-      if (!b->s_h2d) {
-         FZ_HIP(hipStreamCreateWithFlags(&b->s_h2d, hipStreamNonBlocking));
-         FZ_HIP(hipStreamCreateWithFlags(&b->s_run, hipStreamNonBlocking));
-         FZ_HIP(hipStreamCreateWithFlags(&b->s_d2h, hipStreamNonBlocking));
-         for (int i = 0; i < 2; ++i) {
-            FZ_HIP(hipEventCreateWithFlags(&b->ev_in[i], hipEventDisableTiming));
-            FZ_HIP(hipEventCreateWithFlags(&b->ev_run[i], hipEventDisableTiming));
-            FZ_HIP(hipEventCreateWithFlags(&b->ev_out[i], hipEventDisableTiming));
-         }
-      }
-      FZ_HIP(hipDeviceSynchronize());
       const fz_variant sm{0, 0, 0, FZ_VF_STREAM_MAJOR};
       const char* hin = reinterpret_cast<const char*>(in_host);
       char* hout = reinterpret_cast<char*>(out_host);
-      uint32_t k = 0;
-      for (uint32_t t0 = 0; t0 < n_samples; t0 += chunk_t, ++k) {
-         const uint32_t nt = std::min(chunk_t, n_samples - t0);
-         const int slot = (int)(k & 1u);
-         float* din = reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_in) + (size_t)slot * ipitch * b->n_streams);
-         float* dout = reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_out) + (size_t)slot * opitch * b->n_streams);
-         if (g.n_in) {
-            if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_h2d, b->ev_run[slot], 0));
-            FZ_HIP(hipMemcpy2DAsync(din, ipitch, hin + (size_t)t0 * g.n_in * es, hip, (size_t)nt * g.n_in * es, b->n_streams,
+      auto din = [&](int slot) { return reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_in) + (size_t)slot * ipitch * b->n_streams); };
+      auto dout = [&](int slot) { return reinterpret_cast<float*>(reinterpret_cast<char*>(b->stage_out) + (size_t)slot * opitch * b->n_streams); };
+      return run_pipeline(
+         b, n_samples, chunk_t, g.n_in != 0,
+         [&](int slot, uint32_t t0, uint32_t nt) {
+            FZ_HIP(hipMemcpy2DAsync(din(slot), ipitch, hin + (size_t)t0 * g.n_in * es, hip, (size_t)nt * g.n_in * es, b->n_streams,
                                     hipMemcpyHostToDevice, b->s_h2d));
-            FZ_HIP(hipEventRecord(b->ev_in[slot], b->s_h2d));
-            FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_in[slot], 0));
-         }
-         if (k >= 2) FZ_HIP(hipStreamWaitEvent(b->s_run, b->ev_out[slot], 0));
-         int rc = FZ_OK;
-         try {
+         },
+         [&](int slot, uint32_t t0, uint32_t nt) {
             if (pcm)
-               rc = fz::launch_pcm16_sm(b->prog, g.n_in ? din : nullptr, g.n_out ? dout : nullptr, g.n_state ? b->state : nullptr, b->params,
-                                        b->n_streams, chunk_t, 0, nt, FZ_FRAMES_I16, FZ_FRAMES_I16, b->s_run);
-            else
-               rc = fz::launch(b->prog, g.n_in ? din : nullptr, dout, g.n_state ? b->state : nullptr, b->params, b->n_streams, nt, &sm,
-                               b->s_run, 0, chunk_t, 0, t0);
-         } catch (...) {
-            drain_pipeline(b);
-            throw;
-         }
-         if (rc != FZ_OK) {
-            drain_pipeline(b);
-            return rc;
-         }
-         FZ_HIP(hipEventRecord(b->ev_run[slot], b->s_run));
-         FZ_HIP(hipStreamWaitEvent(b->s_d2h, b->ev_run[slot], 0));
-         FZ_HIP(hipMemcpy2DAsync(hout + (size_t)t0 * g.n_out * es, hop, dout, opitch, (size_t)nt * g.n_out * es, b->n_streams,
-                                 hipMemcpyDeviceToHost, b->s_d2h));
-         FZ_HIP(hipEventRecord(b->ev_out[slot], b->s_d2h));
-      }
-      FZ_HIP(hipStreamSynchronize(b->s_d2h));
-      FZ_HIP(hipStreamSynchronize(b->s_run));
-      return FZ_OK;)
+               return fz::launch_pcm16_sm(b->prog, g.n_in ? din(slot) : nullptr, g.n_out ? dout(slot) : nullptr, g.n_state ? b->state : nullptr, b->params,
+                                          b->n_streams, chunk_t, 0, nt, FZ_FRAMES_I16, FZ_FRAMES_I16, b->s_run);
+            return fz::launch(b->prog, g.n_in ? din(slot) : nullptr, dout(slot), g.n_state ? b->state : nullptr, b->params, b->n_streams, nt, &sm,
+                              b->s_run, 0, chunk_t, 0, t0);
+         },
+         [&](int slot, uint32_t t0, uint32_t nt) {
+            FZ_HIP(hipMemcpy2DAsync(hout + (size_t)t0 * g.n_out * es, hop, dout(slot), opitch, (size_t)nt * g.n_out * es, b->n_streams,
+                                    hipMemcpyDeviceToHost, b->s_d2h));
+         });)
 }
 
 int fz_bank_process_host_stream_major(fz_bank* b, const float* in_host, float* out_host, uint32_t n_samples)

@@ -1,17 +1,11 @@
 // extern "C" entry points of libflowz_hip that are pure host work: compile(), IR inspection,
 // kernel build (hiprtc needs no GPU), and the fz_run_block wrapper.
 #include <cmath>
-#include <cstring>
 #include <memory>
 
 #include "fz_internal.hpp"
 
 using namespace fz;
-
-#define FZ_GUARD(...)                                                           \
-   try { __VA_ARGS__ }                                                                 \
-   catch (const fz::Error& er) { fz::set_error(er.msg); return er.code; }       \
-   catch (const std::exception& ex) { fz::set_error(ex.what()); return FZ_E_INVALID; }
 
 // a program the SHIPPED reference would evaluate differently: the compile succeeds -- this library routes per the
 // reference's own arity table -- and says so: fz_info.differs_from_reference, and this note in fz_last_error()
@@ -21,24 +15,6 @@ static void note_divergence(const Graph& g)
       set_error("note: a feedback in this graph keeps " + std::to_string(g.ref_divergent) + " external input(s) for its promise part next to a future part that "
                 "reads external inputs too: the reference's shipped binary_feedback hands the future part the wrong wires there (flowz.hpp:1045-1050, "
                 "std::min(0, ...)); this library routes per the arity table (flowz.hpp:162-246), so its results differ from the reference's closure");
-}
-
-// a string result: its length, and as much of it as fits `cap` (NUL-terminated) in `buf`; an error: its code, the message in fz_last_error
-template <class Text>
-static long string_result(char* buf, size_t cap, Text text)
-{
-   try {
-      const std::string s = text();
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
 }
 
 // the kernel a launch of that shape runs (a shape left 0: 2^20 streams / samples), as `of` names it
@@ -267,10 +243,7 @@ int fz_program_kernel_resources(fz_program* p, const fz_variant* v, uint64_t n_s
 {
    FZ_GUARD(
       if (!p || !out || !n_streams || !n_samples) fail(FZ_E_INVALID, "fz_program_kernel_resources: bad arguments");
-      const Variant rv = plan_launch(p, v, n_streams, n_samples, tile_streams, 0, as_launched != 0, false).main;
-      const auto k = get_kernel(p, rv, nullptr);
-      *out = fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills,
-                                 k->res.sgpr_spills, rv.U};
+      *out = resources_of(p, plan_launch(p, v, n_streams, n_samples, tile_streams, 0, as_launched != 0, false).main);
       return FZ_OK;)
 }
 

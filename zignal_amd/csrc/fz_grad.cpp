@@ -17,7 +17,6 @@
 #include <cmath>
 #include <algorithm>
 #include <cstddef>
-#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -385,11 +384,7 @@ struct AdjLossArgsHeader {
 constexpr size_t kAdjLossHeaderBytes = offsetof(AdjLossArgsHeader, grad_scale) + sizeof(float);
 static_assert(kAdjLossHeaderBytes == 12 * 8 + 8 + 2 * 4 + 4, "AdjLossArgsHeader must match the head of the kernel's fz_adj_args under FZ_LOSS without padding");
 
-// the window of a stream-major launch: rows [row0, row0 + n_samples) of buffers [n_streams][rows_total][wire]; null: time-major frames
-struct SmWindow {
-   uint32_t rows_total, row0;
-};
-static_assert(sizeof(SmWindow) == 2 * sizeof(unsigned int), "SmWindow is the kernels' rows_total and row0");
+// (the window of a stream-major launch, SmWindow: fz_kernargs.hpp; a null one below: time-major frames)
 
 // the arguments of a backward, whichever struct they came in: fz_grad_args gives dL/dy (`ybar`), fz_loss_grad_args the target in its
 // place and what the squared-error rule needs (`loss_rule`)
@@ -429,6 +424,15 @@ static GradCall call_of(fz_program* p, const fz_loss_grad_args* a0)
                    a->workspace, a->workspace_bytes, true, a->grad_scale, a->loss, a->out};
 }
 
+// the same for a call of the ring family
+template <class Args>
+static GradCall ring_call_of(fz_program* p, const Args* a)
+{
+   GradCall call = call_of(p, a);
+   call.ring = true;
+   return call;
+}
+
 // what a recording adds to the checks of a block: its own workspace size (and the call that answers it), and state_out as one more output
 struct RecordingCheck {
    uint64_t need;
@@ -446,24 +450,21 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
    const Graph& g = p->g;
    const Variant v = block_variant(g, a->checkpoint_rows, a->ring, sm != nullptr, a->loss_rule);
    *vout = v;
-   if (n_streams == 0 || n_samples == 0) return false;     // an empty block: nothing to differentiate, nothing touched
-   if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
+   if (!block_has_work(n_streams, n_samples)) return false;   // an empty block: nothing to differentiate, nothing touched
    if (sm) {
-      if ((uint64_t)sm->row0 + n_samples > sm->rows_total)
-         fail(FZ_E_INVALID, "the window [row0, row0 + n_samples) = [" + std::to_string(sm->row0) + ", " + std::to_string((uint64_t)sm->row0 + n_samples) +
-                               ") reaches beyond rows_total = " + std::to_string(sm->rows_total));
-      // (the forward stream-major rule: every stream's buffer and the window's first row on the 16-byte grid of the float4 pieces)
-      if (((uint64_t)sm->rows_total * g.n_in) % 4 || ((uint64_t)sm->rows_total * g.n_out) % 4)
+      check_window(sm->rows_total, sm->row0, n_samples);
+      // (the forward stream-major rule, in the words the backward has for it: the buffers' rule first, then the window's)
+      if (!on_piece_grid(sm->rows_total, g.n_in) || !on_piece_grid(sm->rows_total, g.n_out))
          fail(FZ_E_INVALID, "stream-major buffers: rows_total * n_in and rows_total * n_out must be multiples of 4 floats");
-      if (((uint64_t)sm->row0 * g.n_in) % 4 || ((uint64_t)sm->row0 * g.n_out) % 4)
+      if (!on_piece_grid(sm->row0, g.n_in) || !on_piece_grid(sm->row0, g.n_out))
          fail(FZ_E_INVALID, "stream-major buffers: row0 * n_in and row0 * n_out must be multiples of 4 floats");
    }
-   if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams");
-   if (g.n_in && !a->in) fail(FZ_E_INVALID, "in is null but the graph has input wires");
-   if (g.n_state && !a->state) fail(FZ_E_INVALID, "state is null but the graph has delay lines");
-   if (g.n_param && !a->params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
+   check_stream_count(n_streams);
+   require_pointer(a->in, g.n_in, "in", "input wires");
+   require_pointer(a->state, g.n_state, "state", "delay lines");
+   require_pointer(a->params, g.n_param, "params", "per-stream coefficients");
    if (a->loss_rule && !a->ybar) fail(FZ_E_INVALID, "target is null: the loss compares the outputs with it");
-   if (g.n_out && !a->ybar) fail(FZ_E_INVALID, "out_grad is null but the graph has output wires");
+   require_pointer(a->ybar, g.n_out, "out_grad", "output wires");
    const uint64_t need = rec ? rec->need : ring_workspace_bytes(g, n_streams, n_samples, v);
    const std::string ws_fn = rec ? (a->ring ? "fz_program_ring_recording_workspace" : "fz_program_recording_workspace") : a->ring ? "fz_program_ring_grad_workspace" : "fz_program_grad_workspace";
    if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: " + ws_fn + " says " + std::to_string(need) + " bytes");
@@ -489,7 +490,7 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
    };
    if (rec) bufs.push_back({rec->state_out, row * g.n_state, "state_out", true});
    for (const Buf& b : bufs)
-      if (b.ptr && !b.own && (reinterpret_cast<uintptr_t>(b.ptr) & 15u)) fail(FZ_E_INVALID, std::string(b.name) + ": device pointers must be 16-byte aligned");
+      if (!b.own) check_aligned16({{b.ptr, b.name}});
    for (size_t i = 0; i < bufs.size(); ++i)
       for (size_t j = i + 1; j < bufs.size(); ++j) {
          const Buf &x = bufs[i], &y = bufs[j];
@@ -502,25 +503,16 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
 }
 
 // The launch of a kernel of the family (a device is at hand).  Its argument struct is the header image, the window of a stream-major launch
-// behind it, then the coefficient tail (read under p->mu); its size is 8-byte aligned -- a buffer of another size does not launch it.
+// behind it, then the coefficient tail.
 static void launch_family(fz_program* p, const Variant& v, const void* header, size_t header_bytes, const SmWindow* sm, uint64_t n_streams, void* stream)
 {
-   const Graph& g = p->g;
    void* fn = nullptr;
    (void)get_kernel(p, v, &fn);
-   const size_t hbytes = header_bytes + (sm ? sizeof *sm : 0);
-   const size_t kbytes = (hbytes + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
-   std::vector<char> kbuf(kbytes, 0);
-   std::memcpy(kbuf.data(), header, header_bytes);
-   if (sm) std::memcpy(kbuf.data() + header_bytes, sm, sizeof *sm);
-   {
-      std::lock_guard<std::mutex> lock(p->mu);
-      if (!g.consts.empty()) std::memcpy(kbuf.data() + hbytes, g.consts.data(), sizeof(float) * g.consts.size());
-   }
-   size_t size = kbytes;
-   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-   const unsigned grid = (unsigned)((n_streams + v.block - 1) / v.block);
-   FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+   KernArgs ka(header_bytes, sm != nullptr, p->g.consts.size());
+   ka.set_header(header);
+   if (sm) ka.set_window(*sm);
+   copy_coefficients(ka, p);
+   launch_kernel(fn, (unsigned)((n_streams + v.block - 1) / v.block), v.block, stream, ka);
 }
 
 // the launch of a checked backward
@@ -637,33 +629,8 @@ static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, u
    return FZ_OK;
 }
 
-// what an adjoint kernel needs (JITs it); `unroll` = its checkpoint stride
-static fz_kernel_resources resources_of(fz_program* p, const Variant& v)
-{
-   const auto k = get_kernel(p, v, nullptr);
-   return fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills, k->res.sgpr_spills, v.U};
-}
-
-// a string result of the inspection calls: the length, at most cap bytes written; an error code (negative) on failure
-template <class Fn>
-static long grad_string(fz_program* p, char* buf, size_t cap, Fn make)
-{
-   try {
-      if (!p) fail(FZ_E_INVALID, "null program");
-      const std::string s = make();
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
-}
-
-// the inspection calls of a kernel of the family, given the maker of its Variant: resources (`fn` names the call in the refusal), symbol, source
+// the inspection calls of a kernel of the family, given the maker of its Variant: resources (`fn` names the call in the refusal; `unroll`
+// = the checkpoint stride), symbol, source
 template <class Maker>
 static int grad_resources(fz_program* p, fz_kernel_resources* out, const char* fn, Maker make)
 {
@@ -676,13 +643,19 @@ static int grad_resources(fz_program* p, fz_kernel_resources* out, const char* f
 template <class Maker>
 static long grad_symbol(fz_program* p, char* buf, size_t cap, Maker make)
 {
-   return grad_string(p, buf, cap, [&] { return kernel_symbol(p->g, make()); });
+   return string_result(buf, cap, [&] {
+      if (!p) fail(FZ_E_INVALID, "null program");
+      return kernel_symbol(p->g, make());
+   });
 }
 
 template <class Maker>
 static long grad_source(fz_program* p, char* buf, size_t cap, Maker make)
 {
-   return grad_string(p, buf, cap, [&] { return full_source(p->g, make()); });
+   return string_result(buf, cap, [&] {
+      if (!p) fail(FZ_E_INVALID, "null program");
+      return full_source(p->g, make());
+   });
 }
 
 }  // namespace fz
@@ -792,10 +765,7 @@ long fz_program_ring_grad_source(fz_program* p, uint32_t checkpoint_rows, char* 
 
 int fz_run_block_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
-   FZ_GUARD(
-      GradCall call = call_of(p, a);
-      call.ring = true;
-      return run_grad(p, call, n_streams, n_samples, hip_stream);)
+   FZ_GUARD(return run_grad(p, ring_call_of(p, a), n_streams, n_samples, hip_stream);)
 }
 
 int fz_program_ring_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
@@ -832,20 +802,16 @@ int fz_run_block_ring_grad_stream_major(fz_program* p, const fz_grad_args* a, ui
                                         void* hip_stream)
 {
    FZ_GUARD(
-      GradCall call = call_of(p, a);
-      call.ring = true;
       const SmWindow w{rows_total, row0};
-      return run_grad(p, call, n_streams, n_samples, hip_stream, &w);)
+      return run_grad(p, ring_call_of(p, a), n_streams, n_samples, hip_stream, &w);)
 }
 
 int fz_run_block_ring_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
                                              uint32_t n_samples, void* hip_stream)
 {
    FZ_GUARD(
-      GradCall call = call_of(p, a);
-      call.ring = true;
       const SmWindow w{rows_total, row0};
-      return run_grad(p, call, n_streams, n_samples, hip_stream, &w);)
+      return run_grad(p, ring_call_of(p, a), n_streams, n_samples, hip_stream, &w);)
 }
 
 int fz_program_ring_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
@@ -865,10 +831,7 @@ long fz_program_ring_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, c
 
 int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
-   FZ_GUARD(
-      GradCall call = call_of(p, a);
-      call.ring = true;
-      return run_grad(p, call, n_streams, n_samples, hip_stream);)
+   FZ_GUARD(return run_grad(p, ring_call_of(p, a), n_streams, n_samples, hip_stream);)
 }
 
 int fz_program_ring_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows)
@@ -897,19 +860,13 @@ int fz_program_ring_recording_workspace(const fz_program* p, uint64_t n_streams,
 int fz_run_recording_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows, float* state_out,
                                void* hip_stream)
 {
-   FZ_GUARD(
-      GradCall call = call_of(p, a);
-      call.ring = true;
-      return run_recording(p, call, FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
+   FZ_GUARD(return run_recording(p, ring_call_of(p, a), FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
 }
 
 int fz_run_recording_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows,
                                     float* state_out, void* hip_stream)
 {
-   FZ_GUARD(
-      GradCall call = call_of(p, a);
-      call.ring = true;
-      return run_recording(p, call, FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
+   FZ_GUARD(return run_recording(p, ring_call_of(p, a), FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
 }
 
 int fz_program_ring_states_resources(fz_program* p, fz_kernel_resources* out)

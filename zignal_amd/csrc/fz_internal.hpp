@@ -1,9 +1,12 @@
 // Internal structures of libflowz_hip: expression trees, the lowered per-sample DAG, programs.
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
+#include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -24,6 +27,73 @@ struct Error {
    std::string msg;
 };
 [[noreturn]] void fail(int code, const std::string& msg);
+
+// the body of an extern "C" entry point that returns a code: what it throws becomes the code, the message goes to fz_last_error
+#define FZ_GUARD(...)                                                           \
+   try { __VA_ARGS__ }                                                                 \
+   catch (const fz::Error& er) { fz::set_error(er.msg); return er.code; }       \
+   catch (const std::exception& ex) { fz::set_error(ex.what()); return FZ_E_INVALID; }
+
+// a string result of an inspection call: its length, and as much of it as fits `cap` (NUL-terminated) in `buf`; an error: its code
+// (negative), the message in fz_last_error
+template <class Text>
+long string_result(char* buf, size_t cap, Text text)
+{
+   try {
+      const std::string s = text();
+      if (buf && cap) {
+         const size_t n = std::min(cap - 1, s.size());
+         std::memcpy(buf, s.data(), n);
+         buf[n] = 0;
+      }
+      return (long)s.size();
+   } catch (const Error& er) {
+      set_error(er.msg);
+      return er.code;
+   }
+}
+
+// ---- argument rules of the launches: each written once, all of them checked before a device is needed ----------
+// an empty block is nothing to do (false: FZ_OK, nothing touched)
+inline bool block_has_work(uint64_t n_streams, uint32_t n_samples)
+{
+   if (n_streams == 0 || n_samples == 0) return false;
+   if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
+   return true;
+}
+// (state and coefficient rows go through one-row buffer descriptors: 32-bit byte offsets and sizes, n_streams * 4 < 2^32)
+inline void check_stream_count(uint64_t n_streams) { if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams"); }
+// a pointer the graph needs: "<name> is null but the graph has <what>"
+inline void require_pointer(const void* q, bool needed, const char* name, const char* what) { if (needed && !q) fail(FZ_E_INVALID, std::string(name) + " is null but the graph has " + what); }
+// device pointers are 16-byte aligned (a null one is); a name goes in front of the refusal
+struct NamedPointer {
+   const void* ptr;
+   const char* name = nullptr;
+};
+inline void check_aligned16(std::initializer_list<NamedPointer> ptrs)
+{
+   for (const NamedPointer& q : ptrs)
+      if (reinterpret_cast<uintptr_t>(q.ptr) & 15u)
+         fail(FZ_E_INVALID, (q.name ? std::string(q.name) + ": " : std::string()) + "device pointers must be 16-byte aligned");
+}
+// the window [row0, row0 + n_samples) lies inside the rows_total rows of the buffers
+inline void check_window(uint32_t rows_total, uint32_t row0, uint32_t n_samples)
+{
+   if ((uint64_t)row0 + n_samples > rows_total)
+      fail(FZ_E_INVALID, "the window [row0, row0 + n_samples) = [" + std::to_string(row0) + ", " + std::to_string((uint64_t)row0 + n_samples) +
+                            ") reaches beyond rows_total = " + std::to_string(rows_total));
+}
+// The piece grid of stream-major rows: every stream's buffer (rows_total x wires samples) and the window's first row (row0 x wires)
+// start on the 16-byte pieces the kernels move -- 4 floats or 8 int16 samples.  on_piece_grid is the rule, check_piece_grid one
+// side's refusal in words that name the side.
+inline uint32_t piece_samples(bool i16) { return i16 ? 8u : 4u; }
+inline bool on_piece_grid(uint32_t rows, uint32_t wires, bool i16 = false) { return ((uint64_t)rows * wires) % piece_samples(i16) == 0; }
+inline void check_piece_grid(const char* side, uint32_t wires, uint32_t rows_total, uint32_t row0, bool i16)
+{
+   if (!on_piece_grid(rows_total, wires, i16) || !on_piece_grid(row0, wires, i16))
+      fail(FZ_E_INVALID, std::string(side) + ": rows_total x wires and row0 x wires must be multiples of " + std::to_string(piece_samples(i16)) + " on " +
+                            (i16 ? "an int16" : "a float32") + " side (16-byte pieces)");
+}
 
 // ---- expression tree (the EDSL surface, flowz.hpp:68-93) ---------------------------------------
 enum class EK : uint8_t { Placeholder, Delayed, Literal, Uniform, Param, Arith, Neg, Channel, Parallel, Sequence, Feedback, Modulator,
@@ -397,6 +467,12 @@ LaunchPlan plan_launch(fz_program* p, const fz_variant* uv, uint64_t n_streams, 
 // builds (or fetches from the caches) the kernel of variant v; fn_out != null: also load it on the
 // current device and return its hipFunction_t; build_in_own_process: a missing kernel is compiled by a process of its own (fz_rtc.cpp)
 std::shared_ptr<Kernel> get_kernel(fz_program* p, const Variant& v, void** fn_out, bool build_in_own_process = false);
+// what the kernel of variant v needs, as the inspection calls answer (builds or fetches it); `unroll` = v.U
+inline fz_kernel_resources resources_of(fz_program* p, const Variant& v)
+{
+   const KernelResources r = get_kernel(p, v, nullptr)->res;
+   return fz_kernel_resources{r.vgprs, r.agprs, r.sgprs, r.scratch_bytes, r.lds_bytes, r.vgpr_spills, r.sgpr_spills, v.U};
+}
 // the variant that runs: `v` with its unroll lowered until the kernel keeps its values in registers (no scratch memory): fz_plan.cpp
 Variant settle_variant(fz_program* p, Variant v);
 int launch(fz_program* p, const float* in, float* out, float* state, const float* params,

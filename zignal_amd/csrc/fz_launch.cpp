@@ -2,7 +2,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <map>
 #include <mutex>
 #include <optional>
@@ -139,35 +138,44 @@ static SideStream& side_stream(fz_program* p)
 
 static_assert(sizeof(ArgsHeader) % 8 == 0 && sizeof(ArgsHeader) == 6 * 8 + 8 + 10 * 4, "ArgsHeader must match the head of the kernel's fz_args without padding");
 
+void copy_coefficients(KernArgs& ka, fz_program* p)
+{
+   std::lock_guard<std::mutex> lock(p->mu);
+   ka.copy_tails(p->g.consts.data(), p->g.consts64.data());
+}
+
+void launch_kernel(void* fn, unsigned grid, unsigned threads, void* stream, KernArgs& ka)
+{
+   size_t size = ka.size();
+   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, ka.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+   FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, threads, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+}
+
 int launch(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
            uint32_t n_samples, const fz_variant* uv, void* stream, uint32_t tile_streams, uint32_t rows_total, uint32_t row0,
            uint32_t mod_row0)
 {
    if (rows_total == 0) rows_total = n_samples;             // the block is the whole buffer
-   if ((uint64_t)row0 + n_samples > rows_total) fail(FZ_E_INVALID, "row0 + n_samples exceeds rows_total");
+   check_window(rows_total, row0, n_samples);
    const bool stream_major = uv_flag(uv, FZ_VF_STREAM_MAJOR);
    if (stream_major) {
       if (tile_streams) fail(FZ_E_INVALID, "stream-major frames are not tiled");
       if ((uint64_t)rows_total * std::max(p->g.n_in, p->g.n_out) >= ((uv->flags & FZ_VF_SM_LONG) && uv->streams_per_lane == 2 ? (1ull << 23) : (1ull << 24)))
          fail(FZ_E_UNSUPPORTED, "stream-major frames: more than 2^24 floats per stream buffer (2^23 with two streams per lane; the rows of a wave are addressed through one 4 GiB descriptor): use a window");
-      if (((uint64_t)rows_total * p->g.n_in) % 4 || ((uint64_t)row0 * p->g.n_in) % 4 || ((uint64_t)rows_total * p->g.n_out) % 4 ||
-          ((uint64_t)row0 * p->g.n_out) % 4)
-         fail(FZ_E_INVALID, "stream-major frames: rows_total and row0 times the wires per frame must be multiples of 4 floats");
+      check_piece_grid("in", p->g.n_in, rows_total, row0, false);
+      check_piece_grid("out", p->g.n_out, rows_total, row0, false);
    }
    const Graph& g = p->g;
-   if (n_streams == 0 || n_samples == 0) return FZ_OK;      // an empty block: nothing to evaluate, state unchanged
-   if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
+   if (!block_has_work(n_streams, n_samples)) return FZ_OK;   // an empty block: nothing to evaluate, state unchanged
    if (!out) fail(FZ_E_INVALID, "out is null");
-   if (g.n_in && !in) fail(FZ_E_INVALID, "in is null but the graph has input wires");
-   if (g.n_state && !state) fail(FZ_E_INVALID, "state is null but the graph has delay lines");
-   if (g.n_param && !params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
-   auto mis = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) != 0; };
-   if (mis(in) || mis(out) || mis(state) || mis(params)) fail(FZ_E_INVALID, "device pointers must be 16-byte aligned");
+   require_pointer(in, g.n_in, "in", "input wires");
+   require_pointer(state, g.n_state, "state", "delay lines");
+   require_pointer(params, g.n_param, "params", "per-stream coefficients");
+   check_aligned16({{in}, {out}, {state}, {params}});
    if (tile_streams == 0 || tile_streams >= n_streams) tile_streams = 0;    // one tile == plain time-major
    const uint64_t row_streams = tile_streams ? tile_streams : n_streams;
    if (!stream_major && !chunk_below_4gib(g, row_streams, uv_flag(uv, FZ_VF_OUT_F64), 1)) fail(FZ_E_UNSUPPORTED, "row longer than 4 GiB: shard or tile the streams");
-   // (state and coefficient rows go through one-row buffer descriptors: 32-bit byte offsets and sizes, n_streams * 4 < 2^32)
-   if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams");
+   check_stream_count(n_streams);
    if (tile_streams && n_streams % tile_streams) fail(FZ_E_INVALID, "n_streams must be a multiple of tile_streams");
    require_device();
    const std::optional<fz_variant> planned = uv ? std::nullopt : launch_plan_of_shape(p, in, out, state, params, n_streams, n_samples, tile_streams,
@@ -195,18 +203,9 @@ int launch(fz_program* p, const float* in, float* out, float* state, const float
       if ((uint64_t)mod_row0 + row0 + n_samples > mod_stride) fail(FZ_E_INVALID, "fz_program_set_modulation: stride is shorter than the rows of this launch");
       mod_dev += mod_row0;
    }
-   // kernarg image of `struct fz_args` (8-byte aligned: pad the coefficient tail)
-   // (built on the stack for ordinary graphs: no allocation on the launch path)
-   const size_t off64 = (sizeof(ArgsHeader) + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
-   const size_t kbytes = off64 + sizeof(double) * std::max<size_t>(g.consts64.size(), 1);
-   alignas(8) char small[1024];
-   std::vector<char> big;
-   char* const kbuf = kbytes <= sizeof small ? small : (big.resize(kbytes), big.data());
-   {
-      std::lock_guard<std::mutex> lock(p->mu);
-      if (!g.consts.empty()) std::memcpy(kbuf + sizeof(ArgsHeader), g.consts.data(), sizeof(float) * g.consts.size());
-      if (!g.consts64.empty()) std::memcpy(kbuf + off64, g.consts64.data(), sizeof(double) * g.consts64.size());
-   }
+   // kernarg image of `struct fz_args`: the tails once, the header per launch
+   KernArgs ka(sizeof(ArgsHeader), false, g.consts.size(), g.consts64.size());
+   copy_coefficients(ka, p);
    static const bool debug = std::getenv("FLOWZ_HIP_DEBUG") != nullptr;
 
    // One kernel variant over the streams [first, first + count) of the block (the pointers and the row pitch stay the block's:
@@ -245,15 +244,13 @@ int launch(fz_program* p, const float* in, float* out, float* state, const float
             h.sync = sync_counters(p, sync_bytes, stream);
             FZ_HIP(hipMemsetAsync(h.sync, 0, sync_bytes, (hipStream_t)stream));
          }
-         std::memcpy(kbuf, &h, sizeof h);
-         size_t size = kbytes;
-         void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-         FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, threads, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+         ka.set_header(&h);
+         launch_kernel(fn, grid, threads, stream, ka);
       }
       if (debug) {
          FZ_HIP(hipStreamSynchronize((hipStream_t)stream));
          std::fprintf(stderr, "[flowz_hip] launched streams [%llu, %llu) of %llu: %u lap(s) grid=%u block=%u P=%u U=%u flags=%u n_samples=%u kernarg=%zu B vgprs=%u scratch=%u B/lane\n",
-                      (unsigned long long)first, (unsigned long long)(first + count), (unsigned long long)n_streams, laps, grid, w.block, w.P, w.U, w.flags, n_samples, kbytes,
+                      (unsigned long long)first, (unsigned long long)(first + count), (unsigned long long)n_streams, laps, grid, w.block, w.P, w.U, w.flags, n_samples, ka.size(),
                       k->res.vgprs + k->res.agprs, k->res.scratch_bytes);
       }
    };

@@ -5,8 +5,6 @@
 // The same for stream-major buffers (fz_run_block_pcm16_stream_major): fz_kernel_pcm16_sm.hip.inc behind the same head and body, a
 // Variant with FZ_VF_PCM16 | FZ_VF_PCM16_SM whose U carries the rows of a chunk (pcm16_sm_chunk_rows is their one home).
 #include <algorithm>
-#include <cstring>
-#include <vector>
 
 #include "fz_runtime.hpp"
 
@@ -50,6 +48,17 @@ static void check_types(uint32_t in_type, uint32_t out_type)
 }
 
 static uint32_t bytes_of(uint32_t type) { return type == FZ_FRAMES_I16 ? 2u : 4u; }
+
+// In place: every lane reads a row's slice (stream-major: every piece and every row) before it writes the same bytes -- int16 on both
+// sides, as many wires out as in, in == out.  Any other overlap of the two buffers' extents is refused.
+static void check_in_place_or_apart(const Graph& g, const void* in, uint64_t ibytes, uint32_t in_type, const void* out, uint64_t obytes, uint32_t out_type)
+{
+   if (!in || !out || !ibytes || !obytes) return;
+   const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+   const bool in_place = i0 == o0 && in_type == FZ_FRAMES_I16 && out_type == FZ_FRAMES_I16 && g.n_in == g.n_out;
+   if (!in_place && i0 < o0 + obytes && o0 < i0 + ibytes)
+      fail(FZ_E_INVALID, "in and out overlap: in place only with int16 frames on both sides, as many output wires as input wires and in == out");
+}
 
 // The plan: ONE choice per (graph width, int16 rows on / off the dword grid).
 //   up to two wires a side, on the grid    four streams per lane: a wire's int16 slice is a b64 access, its floats a b128
@@ -108,48 +117,29 @@ int launch_pcm16(fz_program* p, const void* in, void* out, float* state, const f
    const Graph& g = p->g;
    require_supported(g);
    check_types(in_type, out_type);
-   if (n_streams == 0 || n_samples == 0) return FZ_OK;      // an empty block: nothing to evaluate, state unchanged
-   if (n_samples == 0xFFFFFFFFu) fail(FZ_E_INVALID, "n_samples must be below 2^32 - 1");
-   if (g.n_out && !out) fail(FZ_E_INVALID, "out is null but the graph has output wires");
-   if (g.n_in && !in) fail(FZ_E_INVALID, "in is null but the graph has input wires");
-   if (g.n_state && !state) fail(FZ_E_INVALID, "state is null but the graph has delay lines");
-   if (g.n_param && !params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
-   auto mis = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) != 0; };
-   if (mis(in) || mis(out) || mis(state) || mis(params)) fail(FZ_E_INVALID, "device pointers must be 16-byte aligned");
+   if (!block_has_work(n_streams, n_samples)) return FZ_OK;   // an empty block: nothing to evaluate, state unchanged
+   require_pointer(out, g.n_out, "out", "output wires");
+   require_pointer(in, g.n_in, "in", "input wires");
+   require_pointer(state, g.n_state, "state", "delay lines");
+   require_pointer(params, g.n_param, "params", "per-stream coefficients");
+   check_aligned16({{in}, {out}, {state}, {params}});
    // a row through one descriptor, and the last lane's byte offset (its four streams may reach past the row) in 32 bits
    const uint64_t irow = n_streams * g.n_in * bytes_of(in_type), orow = n_streams * g.n_out * bytes_of(out_type);
    const uint64_t lane_streams = (n_streams + 3) / 4 * 4;
    if (lane_streams * std::max<uint64_t>((uint64_t)g.n_in * bytes_of(in_type), (uint64_t)g.n_out * bytes_of(out_type)) >= (1ull << 32))
       fail(FZ_E_UNSUPPORTED, "row longer than 4 GiB: shard the streams");
-   if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams");
-   // in place: every lane reads a row's slice before it writes the same bytes -- int16 on both sides, as many wires out as in
-   const uint64_t ibytes = irow * n_samples, obytes = orow * n_samples;
-   if (in && out && ibytes && obytes) {
-      const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-      const bool in_place = i0 == o0 && in_type == FZ_FRAMES_I16 && out_type == FZ_FRAMES_I16 && g.n_in == g.n_out;
-      if (!in_place && i0 < o0 + obytes && o0 < i0 + ibytes)
-         fail(FZ_E_INVALID, "in and out overlap: in place only with int16 frames on both sides, as many output wires as input wires and in == out");
-   }
+   check_stream_count(n_streams);
+   check_in_place_or_apart(g, in, irow * n_samples, in_type, out, orow * n_samples, out_type);
    require_device();
    const Variant v = settle_variant(p, pcm16_plan(g, in_type, out_type, n_streams));
    void* fn = nullptr;
    (void)get_kernel(p, v, &fn);
-   const size_t kbytes = (sizeof(PcmArgsHeader) + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
-   alignas(8) char small[1024];
-   std::vector<char> big;
-   char* const kbuf = kbytes <= sizeof small ? small : (big.resize(kbytes), big.data());
-   std::memset(kbuf, 0, kbytes);
    const unsigned groups = (unsigned)((n_streams + v.P - 1) / v.P);
    const PcmArgsHeader h{in, out, state, params, (unsigned long long)n_streams, n_samples, groups};
-   std::memcpy(kbuf, &h, sizeof h);
-   {
-      std::lock_guard<std::mutex> lock(p->mu);
-      if (!g.consts.empty()) std::memcpy(kbuf + sizeof h, g.consts.data(), sizeof(float) * g.consts.size());
-   }
-   size_t size = kbytes;
-   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-   const unsigned grid = (groups + v.block - 1) / v.block;
-   FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+   KernArgs ka(sizeof h, false, g.consts.size());
+   ka.set_header(&h);
+   copy_coefficients(ka, p);
+   launch_kernel(fn, (groups + v.block - 1) / v.block, v.block, stream, ka);
    return FZ_OK;
 }
 
@@ -238,70 +228,30 @@ int launch_pcm16_sm(fz_program* p, const void* in, void* out, float* state, cons
    const Graph& g = p->g;
    require_supported(g);
    check_types(in_type, out_type);
-   if (n_streams == 0 || n_samples == 0) return FZ_OK;      // an empty block: nothing to evaluate, nothing touched
-   if ((uint64_t)row0 + n_samples > rows_total) fail(FZ_E_INVALID, "the window [row0, row0 + n_samples) reaches past rows_total");
-   // the 16-byte grid of the pieces: every stream's buffer and the window's first row start on it
-   auto on_grid = [&](const char* side, uint32_t wires, uint32_t type) {
-      const uint64_t m = type == FZ_FRAMES_I16 ? 8u : 4u;
-      if (((uint64_t)rows_total * wires) % m || ((uint64_t)row0 * wires) % m)
-         fail(FZ_E_INVALID, std::string(side) + ": rows_total x wires and row0 x wires must be multiples of " + std::to_string(m) + " on " +
-                               (type == FZ_FRAMES_I16 ? "an int16" : "a float32") + " side (16-byte pieces)");
-   };
-   on_grid("in", g.n_in, in_type);
-   on_grid("out", g.n_out, out_type);
-   if ((g.n_in != 0) != (in != nullptr)) fail(FZ_E_INVALID, g.n_in ? "in is null but the graph has input wires" : "in must be null: the graph has no input wires");
-   if ((g.n_out != 0) != (out != nullptr)) fail(FZ_E_INVALID, g.n_out ? "out is null but the graph has output wires" : "out must be null: the graph has no output wires");
-   if (g.n_state && !state) fail(FZ_E_INVALID, "state is null but the graph has delay lines");
-   if (g.n_param && !params) fail(FZ_E_INVALID, "params is null but the graph has per-stream coefficients");
-   auto mis = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) != 0; };
-   if (mis(in) || mis(out) || mis(state) || mis(params)) fail(FZ_E_INVALID, "device pointers must be 16-byte aligned");
-   // in place: every piece and every row is read before the same bytes are written -- int16 on both sides, as many wires out as in
-   const uint64_t ibytes = n_streams * rows_total * g.n_in * bytes_of(in_type), obytes = n_streams * rows_total * g.n_out * bytes_of(out_type);
-   if (in && out && ibytes && obytes) {
-      const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-      const bool in_place = i0 == o0 && in_type == FZ_FRAMES_I16 && out_type == FZ_FRAMES_I16 && g.n_in == g.n_out;
-      if (!in_place && i0 < o0 + obytes && o0 < i0 + ibytes)
-         fail(FZ_E_INVALID, "in and out overlap: in place only with int16 frames on both sides, as many output wires as input wires and in == out");
-   }
-   if (n_streams >= (1ull << 30)) fail(FZ_E_UNSUPPORTED, "2^30 streams or more per launch: shard the streams");
+   if (!block_has_work(n_streams, n_samples)) return FZ_OK;   // an empty block: nothing to evaluate, nothing touched
+   check_window(rows_total, row0, n_samples);
+   check_piece_grid("in", g.n_in, rows_total, row0, in_type == FZ_FRAMES_I16);
+   check_piece_grid("out", g.n_out, rows_total, row0, out_type == FZ_FRAMES_I16);
+   // (this kernel takes a pointer iff its side has wires)
+   if (!g.n_in && in) fail(FZ_E_INVALID, "in must be null: the graph has no input wires");
+   require_pointer(in, g.n_in, "in", "input wires");
+   if (!g.n_out && out) fail(FZ_E_INVALID, "out must be null: the graph has no output wires");
+   require_pointer(out, g.n_out, "out", "output wires");
+   require_pointer(state, g.n_state, "state", "delay lines");
+   require_pointer(params, g.n_param, "params", "per-stream coefficients");
+   check_aligned16({{in}, {out}, {state}, {params}});
+   check_in_place_or_apart(g, in, n_streams * rows_total * g.n_in * bytes_of(in_type), in_type, out, n_streams * rows_total * g.n_out * bytes_of(out_type), out_type);
+   check_stream_count(n_streams);
    require_device();
    const Variant v = pcm16_sm_settle(p, pcm16_sm_plan(g, in_type, out_type));
    void* fn = nullptr;
    (void)get_kernel(p, v, &fn);
-   const size_t kbytes = (sizeof(PcmSmArgsHeader) + sizeof(float) * std::max<size_t>(g.consts.size(), 1) + 7) & ~size_t(7);
-   alignas(8) char small[1024];
-   std::vector<char> big;
-   char* const kbuf = kbytes <= sizeof small ? small : (big.resize(kbytes), big.data());
-   std::memset(kbuf, 0, kbytes);
    const PcmSmArgsHeader h{in, out, state, params, (unsigned long long)n_streams, n_samples, rows_total, row0, 0u};
-   std::memcpy(kbuf, &h, sizeof h);
-   {
-      std::lock_guard<std::mutex> lock(p->mu);
-      if (!g.consts.empty()) std::memcpy(kbuf + sizeof h, g.consts.data(), sizeof(float) * g.consts.size());
-   }
-   size_t size = kbytes;
-   void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, kbuf, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-   const unsigned grid = (unsigned)((n_streams + 63u) / 64u);           // one wave of 64 streams per workgroup
-   FZ_HIP(hipModuleLaunchKernel((hipFunction_t)fn, grid, 1, 1, v.block, 1, 1, 0, (hipStream_t)stream, nullptr, extra));
+   KernArgs ka(sizeof h, false, g.consts.size());
+   ka.set_header(&h);
+   copy_coefficients(ka, p);
+   launch_kernel(fn, (unsigned)((n_streams + 63u) / 64u), v.block, stream, ka);   // one wave of 64 streams per workgroup
    return FZ_OK;
-}
-
-// a string result of the inspection calls: the length, at most cap bytes written; an error code (negative) on failure
-template <class Fn>
-static long pcm16_string(char* buf, size_t cap, Fn make)
-{
-   try {
-      const std::string s = make();
-      if (buf && cap) {
-         const size_t n = std::min(cap - 1, s.size());
-         std::memcpy(buf, s.data(), n);
-         buf[n] = 0;
-      }
-      return (long)s.size();
-   } catch (const fz::Error& er) {
-      set_error(er.msg);
-      return er.code;
-   }
 }
 
 }  // namespace fz
@@ -328,27 +278,18 @@ int fz_program_pcm16_resources(fz_program* p, uint32_t in_type, uint32_t out_typ
 {
    FZ_GUARD(
       if (!out) fail(FZ_E_INVALID, "fz_program_pcm16_resources: bad arguments");
-      const Variant v = pcm16_variant(p, in_type, out_type, n_streams);
-      const auto k = get_kernel(p, v, nullptr);
-      *out = fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills,
-                                 k->res.sgpr_spills, v.U};
+      *out = resources_of(p, pcm16_variant(p, in_type, out_type, n_streams));
       return FZ_OK;)
 }
 
 long fz_program_pcm16_kernel_symbol(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, char* buf, size_t cap)
 {
-   return pcm16_string(buf, cap, [&] {
-      const Variant v = pcm16_variant(p, in_type, out_type, n_streams);
-      return kernel_symbol(p->g, v);
-   });
+   return string_result(buf, cap, [&] { const Variant v = pcm16_variant(p, in_type, out_type, n_streams); return kernel_symbol(p->g, v); });
 }
 
 long fz_program_pcm16_source(fz_program* p, uint32_t in_type, uint32_t out_type, uint64_t n_streams, char* buf, size_t cap)
 {
-   return pcm16_string(buf, cap, [&] {
-      const Variant v = pcm16_variant(p, in_type, out_type, n_streams);
-      return full_source(p->g, v);
-   });
+   return string_result(buf, cap, [&] { const Variant v = pcm16_variant(p, in_type, out_type, n_streams); return full_source(p->g, v); });
 }
 
 int fz_run_block_pcm16_stream_major(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams,
@@ -361,27 +302,18 @@ int fz_program_pcm16_stream_major_resources(fz_program* p, uint32_t in_type, uin
 {
    FZ_GUARD(
       if (!out) fail(FZ_E_INVALID, "fz_program_pcm16_stream_major_resources: bad arguments");
-      const Variant v = pcm16_sm_variant(p, in_type, out_type);
-      const auto k = get_kernel(p, v, nullptr);
-      *out = fz_kernel_resources{k->res.vgprs, k->res.agprs, k->res.sgprs, k->res.scratch_bytes, k->res.lds_bytes, k->res.vgpr_spills,
-                                 k->res.sgpr_spills, v.U};
+      *out = resources_of(p, pcm16_sm_variant(p, in_type, out_type));
       return FZ_OK;)
 }
 
 long fz_program_pcm16_stream_major_kernel_symbol(fz_program* p, uint32_t in_type, uint32_t out_type, char* buf, size_t cap)
 {
-   return pcm16_string(buf, cap, [&] {
-      const Variant v = pcm16_sm_variant(p, in_type, out_type);
-      return kernel_symbol(p->g, v);
-   });
+   return string_result(buf, cap, [&] { const Variant v = pcm16_sm_variant(p, in_type, out_type); return kernel_symbol(p->g, v); });
 }
 
 long fz_program_pcm16_stream_major_source(fz_program* p, uint32_t in_type, uint32_t out_type, char* buf, size_t cap)
 {
-   return pcm16_string(buf, cap, [&] {
-      const Variant v = pcm16_sm_variant(p, in_type, out_type);
-      return full_source(p->g, v);
-   });
+   return string_result(buf, cap, [&] { const Variant v = pcm16_sm_variant(p, in_type, out_type); return full_source(p->g, v); });
 }
 
 }  // extern "C"

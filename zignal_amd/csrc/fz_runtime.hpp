@@ -4,7 +4,7 @@
 //   fz_manifest.cpp      kernel manifests: record what a process resolves, replay it into the kernel cache
 //   fz_plan.cpp          variant resolution: the library's static choice per layout and kernel body
 //   fz_tune.cpp          measured plans: tune candidates, fz_program_tune, persistence per board
-//   fz_launch.cpp        the launch of the fused block kernel
+//   fz_launch.cpp        the launch of the fused block kernel; the one hipModuleLaunchKernel (its image: fz_kernargs.hpp)
 //   fz_bank.cpp          device-resident closure state (fz_bank) and the host-frames pipelines
 //   fz_aot_kernels.hip   the AOT utility kernels (synthetic fill, copy probe, RBJ coefficients, layout adapter)
 #pragma once
@@ -14,6 +14,7 @@
 #include <string>
 
 #include "fz_internal.hpp"
+#include "fz_kernargs.hpp"
 
 namespace fz {
 
@@ -24,11 +25,6 @@ namespace fz {
          fail(FZ_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));                     \
    } while (0)
 
-#define FZ_GUARD(...)                                                           \
-   try { __VA_ARGS__ }                                                                 \
-   catch (const fz::Error& er) { fz::set_error(er.msg); return er.code; }       \
-   catch (const std::exception& ex) { fz::set_error(ex.what()); return FZ_E_INVALID; }
-
 void require_device();                       // FZ_E_NO_DEVICE: there is no CPU fallback in the product path
 std::string cache_dir();                     // where code objects and plans.txt live ("" = nowhere)
 std::string library_dir();                   // where libflowz_hip.so and fz_rtc_worker are installed
@@ -38,6 +34,10 @@ const std::string& compiler_identity();      // the hiprtc that builds for this 
 std::vector<const char*> build_options(const Graph& g, const Variant& v);
 std::vector<char> compile_kernel(const Graph& g, const Variant& v, bool in_own_process);
 void manifest_record(const fz_program* p, const Variant& v);   // fz_manifest.cpp: FLOWZ_HIP_MANIFEST
+// fz_launch.cpp: the coefficient tails of p's graph into a kernarg image made for their counts, read under p->mu; and the one
+// hipModuleLaunchKernel of the library -- fn (hipFunction_t) on `grid` workgroups of `threads` lanes, the image as its arguments
+void copy_coefficients(KernArgs& ka, fz_program* p);
+void launch_kernel(void* fn, unsigned grid, unsigned threads, void* stream, KernArgs& ka);
 
 inline uint64_t fnv1a_bytes(const char* d, size_t n, uint64_t h = 1469598103934665603ull)
 {
