@@ -606,7 +606,7 @@ long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_
  * in HBM), typed programs, float64 nodes, complex wires, modulators.  Refused here alone: graphs whose deep lines hold more samples
  * than the LDS of a workgroup has room for at 64 lanes (4 bytes per sample and lane, 163 840 bytes: 640 samples) -- the reason names
  * the bytes.  fz_run_block_grad, its stream-major twin and the plain recording calls keep refusing such graphs: stream-major buffers
- * are fz_run_block_ring_grad_stream_major, whole recordings fz_run_recording_ring_grad (time-major).  The fused loss is
+ * are fz_run_block_ring_grad_stream_major, whole recordings fz_run_recording_ring_grad[_stream_major].  The fused loss is
  * fz_run_block_ring_loss_grad, below fz_run_block_loss_grad.
  *
  * The kernel, fz_adjoint_ring_kernel_c<C>b<lanes per workgroup>_g<graph tag>: lines of depth <= 8 are kept as fz_run_block_grad keeps
@@ -782,7 +782,7 @@ long fz_program_states_source(fz_program* p, uint32_t layout, char* buf, size_t 
 
 /* fz_run_recording_ring_grad, fz_run_recording_ring_loss_grad -- the backward of a whole recording of a graph with delay lines deeper
  * than 8 samples, in bounded workspace: to fz_run_block_ring_grad / fz_run_block_ring_loss_grad what fz_run_recording_grad /
- * fz_run_recording_loss_grad are to the one-block calls, time-major frames only (as the ring family is).
+ * fz_run_recording_loss_grad are to the one-block calls, on time-major frames (stream-major buffers: their _stream_major siblings, below).
  *
  * The contract is the one stated above, read with the ring calls as the one-launch calls: every output bit -- in_grad, state0_grad,
  * param_grad, const_grad, loss, out -- is that of fz_run_block_ring_grad / fz_run_block_ring_loss_grad over the same T rows, whatever
@@ -824,6 +824,50 @@ int fz_run_recording_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, u
 int fz_program_ring_states_resources(fz_program* p, fz_kernel_resources* out);
 long fz_program_ring_states_kernel_symbol(fz_program* p, char* buf, size_t cap);
 long fz_program_ring_states_source(fz_program* p, char* buf, size_t cap);
+
+/* fz_run_recording_ring_grad_stream_major, fz_run_recording_ring_loss_grad_stream_major -- the same on STREAM-MAJOR buffers
+ * [n_streams][rows_total][wire], the recording the window of rows [row0, row0 + n_samples): a batch of recordings lying as
+ * [batch, time] is taken as it lies, without a transposed copy of the frames.
+ *
+ * THE CONTRACT IS A REFERENCE.  Every output bit -- in_grad, state0_grad, param_grad, const_grad, loss, out -- is that of
+ * fz_run_recording_ring_grad / fz_run_recording_ring_loss_grad on the transposed buffers (and so that of the one-launch
+ * fz_run_block_ring_grad_stream_major / fz_run_block_ring_loss_grad_stream_major over the same window), whatever block_rows is.
+ * Windows, alignment and the rows outside the window, which are never written, are those of fz_run_recording_grad with
+ * FZ_GRAD_STREAM_MAJOR: block k is the window row0 + k B, and every such window passes the checks of
+ * fz_run_block_ring_grad_stream_major (rows_total, row0 and, with more than one block, block_rows times n_in and n_out multiples of
+ * 4 floats).  state_out, if not NULL, receives the state after the window's last row with the bits of fz_run_block's state.
+ * fz_grad_args and fz_loss_grad_args are taken unchanged.
+ *
+ * B and the workspace: fz_program_ring_recording_block_rows and fz_program_ring_recording_workspace answer both layouts -- C, the
+ * tape, the checkpoints and the block-start states do not depend on the layout (the workspace query asks for a block_rows that is a
+ * multiple of 4 in either layout).
+ *
+ * Scope: that of fz_program_ring_grad_check, plus the LDS refusals of the two stream-major kernels, whose rings share the
+ * workgroup's LDS with the patches the frames move through: a graph whose block kernel fz_run_block_ring_grad_stream_major refuses
+ * at the default stride is refused here with that reason and taken at a checkpoint_rows that fits.  For a graph without a deep line
+ * these calls ARE fz_run_recording_grad / fz_run_recording_loss_grad with FZ_GRAD_STREAM_MAJOR: the same states kernel, B, workspace
+ * and bits.  fz_run_recording_grad with FZ_GRAD_STREAM_MAJOR keeps refusing graphs with deep lines, and the time-major
+ * fz_run_recording_ring_* keep having no window.
+ *
+ * Checks, all before a device is needed and in this order: the refusals of fz_program_ring_grad_check; the states kernel's LDS;
+ * n_samples < 2^31; the block kernel's LDS; those of the one-launch stream-major ring call over the window (state_out counted as an
+ * output) with this call's workspace size -- a short workspace names fz_program_ring_recording_workspace; with more than one block,
+ * state0_grad not NULL; those of every block launch.  n_streams == 0 or n_samples == 0: FZ_OK, nothing is touched.  Asynchronous on
+ * hip_stream.
+ *
+ * The states kernel is a kernel text of its own, fz_states_ring_sm_kernel_u<U>r<R>b<lanes>_g<tag>: U rows per unrolled group as for
+ * every states kernel; x moves through a wave-private LDS patch of R rows next to the value rings, lds_bytes =
+ * 4 * lanes * (ring samples + R * n_in + 4) (no patch for a graph without input wires).  R runs over twice the R of
+ * fz_states_sm_kernel, halved down to max(4, U); per R the lanes over 256 / 128 / 64; the first pair that fits a compute unit's LDS
+ * twice wins, failing that the first that fits once, otherwise FZ_E_UNSUPPORTED naming the bytes.  The _for calls inspect the ring
+ * states kernel of a layout (FZ_GRAD_TIME_MAJOR: fz_program_ring_states_*). */
+int fz_run_recording_ring_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                            uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream);
+int fz_run_recording_ring_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                                 uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream);
+int fz_program_ring_states_resources_for(fz_program* p, uint32_t layout, fz_kernel_resources* out);
+long fz_program_ring_states_kernel_symbol_for(fz_program* p, uint32_t layout, char* buf, size_t cap);
+long fz_program_ring_states_source_for(fz_program* p, uint32_t layout, char* buf, size_t cap);
 
 /* ------------------------------------------------------------------------------------------
  * 16-bit PCM frames.  fz_run_block_pcm16 is fz_run_block for a block whose frames are int16 on one side or on both: the caller

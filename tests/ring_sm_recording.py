@@ -1,0 +1,216 @@
+"""Geometry, cases, launcher and kernels of the stream-major ring recording tests (fz_run_recording_ring_grad_stream_major,
+fz_run_recording_ring_loss_grad_stream_major): the graphs, triples, draws and restated answers are those of
+tests/ring_recording_graphs.py; the rule that chooses the states kernel's workgroup and patch length together, restated; the windows
+and the patch-boundary cases; ONE launch() through the C ABI with the after-checks of grad_harness.launch (whose ENTRY table has no
+row for these calls); and the kernels the GPU tests launch (tests/golden/ring_sm_recording_kernels.fzm.gz)."""
+import ctypes
+import gzip
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+import grad_harness as H
+import ring_recording_graphs as R
+import ring_sm_graphs as RS
+
+F32 = np.float32
+HERE = os.path.dirname(os.path.abspath(__file__))
+MANIFEST = os.path.join(HERE, "golden", "ring_sm_recording_kernels.fzm.gz")
+LDS_BYTES = RS.LDS_BYTES
+K = R.K
+GRAPHS = R.GRAPHS
+DEEPEST = R.DEEPEST
+prog = R.prog
+ENTRY = {False: "fz_run_recording_ring_grad_stream_major", True: "fz_run_recording_ring_loss_grad_stream_major"}
+BOUNDARY_GRAPHS = ("lds_ring_comb", "tap256", "biquad_comb17")    # the graphs run with block starts around a patch boundary
+STRIDES = (0, 1)                                                  # checkpoint_rows the tests ask for
+
+
+# ---- the geometry rule, restated (zignal_amd/csrc/fz_grad.cpp: states_unroll, states_sm_patch_rows, ring_states_sm_geometry) ----------
+def states_unroll(p):
+    """U: 8 rows per unrolled group, halved while a group's frames pass 16 floats"""
+    U = 8
+    while U > 1 and U * p.n_in > 16:
+        U //= 2
+    return U
+
+
+def states_patch_rows(p):
+    """the patch rows of the plain stream-major states kernel: the power of two >= 4 whose run of one stream is a cache line"""
+    R_ = 4
+    while p.n_in and R_ * p.n_in < 32:
+        R_ *= 2
+    return R_
+
+
+def lds_bytes(p, block, R_, slots=None):
+    """rings and an x-only patch: 4 block (slots + R n_in + 4); a graph without input wires declares no patch"""
+    slots = RS.ring_slots(p) if slots is None else slots
+    return 4 * block * (slots + (R_ * p.n_in + 4 if p.n_in else 0))
+
+
+def geometry(p):
+    """(U, R, block) of the stream-major ring states kernel, or (U, Rmin, 0) when nothing fits: R from R0 = twice the plain states
+    kernel's, halved down to Rmin = max(4, U); per R the block over 256, 128, 64; the first pair that fits the LDS twice, failing that
+    the first that fits once"""
+    U, slots = states_unroll(p), RS.ring_slots(p)
+    R0, Rmin = 2 * states_patch_rows(p), max(4, U)
+    for times in (2, 1):
+        R_ = R0
+        while R_ >= Rmin:
+            for block in (256, 128, 64):
+                if times * lds_bytes(p, block, R_, slots) <= LDS_BYTES:
+                    return U, R_, block
+            R_ //= 2
+    return U, Rmin, 0
+
+
+SYMBOL = re.compile(r"fz_states_ring_sm_kernel_u(\d+)r(\d+)b(\d+)_g([0-9a-f]{8})")
+
+
+def symbol_geometry(sym):
+    """(U, R, block) the kernel's symbol names"""
+    m = SYMBOL.fullmatch(sym)
+    assert m, sym
+    return int(m.group(1)), int(m.group(2)), int(m.group(3))
+
+
+# ---- shapes ------------------------------------------------------------------------------------------------------------------------------
+def windows(T):
+    """(rows_total, row0) of the two windows of a recording of T rows: the whole buffer, and four rows in with rows behind it"""
+    return [(H.up4(T), 0), (H.up4(4 + T) + 4, 4)]
+
+
+def boundary_cases(name):
+    """(streams, rows, block_rows) that put block starts on, before and after a patch boundary: T in R - 1, R, R + 1, 2 R + 3 (R the states
+    kernel's patch rows) at 65 streams with blocks of 4 rows and the default"""
+    R_ = geometry(prog(name))[1]
+    return [(65, T, B) for T in (R_ - 1, R_, R_ + 1, 2 * R_ + 3) for B in (4, 0)]
+
+
+def cases(name):
+    """((streams, rows, block_rows), checkpoint_rows) of every bitwise case of a graph"""
+    out = [(t, 0) for t in R.triples(name)] + [(R.below_depth(name), 1)]
+    if name in BOUNDARY_GRAPHS:
+        out += [(t, 0) for t in boundary_cases(name)]
+    return out
+
+
+def forward_shape(name):
+    """(streams, rows) of the run_block_stream_major launch state_out is compared with, and of autograd: rows on the float4 grid"""
+    return 65, H.up4(DEEPEST[name] + 5)
+
+
+# ---- one launch through the C ABI ------------------------------------------------------------------------------------------------------
+def launch(p, d, B, loss, window=None, c=0, state_grad=True, alias=False, leave_out=()):
+    """One call of fz_run_recording_ring_grad_stream_major / fz_run_recording_ring_loss_grad_stream_major on the time-major draw d of
+    ring_recording_graphs.case, in blocks of B rows (0: the library's choice): dict of the outputs asked for (numpy), "x" and "out" as
+    the window's rows, time-major ("x_buffer" / "out_buffer": the whole buffers), plus "state_out" and "starts" (the head of the
+    workspace).  window: (rows_total, row0), default windows(T)[0]; FILL lies around the window in x, dL/dy and the target.
+    param_grad, const_grad and loss start from the draw's accumulators.  c: checkpoint_rows.  alias: state0_grad is the state_grad
+    buffer.  leave_out: C names of outputs passed as null.
+    Afterwards, as grad_harness.launch: every input kept its bits (state_grad excepted when aliased); the workspace is exactly the
+    queried bytes and its surroundings and those of every output kept their sentinels; an output that is left out, has zero rows or is
+    aliased away was not written at all; the rows of in_grad / out outside the window hold what they held before the launch."""
+    import torch
+    from zignal_amd import _capi as CA
+    x, s0, par, yb, tg, sb, ap, ac, al = d
+    T, ns, _ = x.shape
+    rows, row0 = windows(T)[0] if window is None else window
+    frame = lambda a: H.dev(H.to_sm(a, rows, row0, H.FILL))       # noqa: E731
+    fshape = lambda w: (ns, rows, max(w, 1))                      # noqa: E731
+    ins = {"in_": frame(x), "state": H.dev(s0), "params": H.dev(par), "target" if loss else "out_grad": frame(tg if loss else yb),
+           "state_grad": H.dev(sb) if state_grad else None}
+    before = {key: v.clone() for key, v in ins.items() if v is not None}
+    n = {"in_grad": p.n_in, "state0_grad": p.n_state, "param_grad": p.n_param, "const_grad": p.n_const, "loss": 1, "out": p.n_out,
+         "state_out": p.n_state}
+    outs = {"in_grad": H.Guarded(fshape(p.n_in)), "state0_grad": H.Guarded((max(p.n_state, 1), ns)),
+            "param_grad": H.Guarded((max(p.n_param, 1), ns), ap if p.n_param else None),
+            "const_grad": H.Guarded((max(p.n_const, 1), ns), ac if p.n_const else None)}
+    if loss:
+        outs.update(loss=H.Guarded((ns,), al), out=H.Guarded(fshape(p.n_out)))
+    outs["state_out"] = H.Guarded((max(p.n_state, 1), ns))
+    wsb = p.ring_recording_workspace_bytes(ns, T, B, c)
+    assert wsb % 4 == 0
+    ws = H.Guarded(((wsb + 3) // 4,))
+    a = CA.LossGradArgs() if loss else CA.GradArgs()
+    a.struct_size, a.checkpoint_rows = ctypes.sizeof(a), c
+    if loss:
+        a.grad_scale = K
+    for key, t in ins.items():
+        setattr(a, key, t.data_ptr() if t is not None and t.numel() else None)
+    for key, g in outs.items():
+        if key != "state_out":
+            setattr(a, key, g.mid.data_ptr() if n[key] and key not in leave_out else None)
+    if alias:
+        a.state0_grad = ins["state_grad"].data_ptr()
+    a.workspace, a.workspace_bytes = ws.mid.data_ptr(), wsb
+    so = outs["state_out"].mid.data_ptr() if "state_out" not in leave_out else None
+    CA.check(getattr(CA.lib, ENTRY[bool(loss)])(p._h, ctypes.byref(a), ns, rows, row0, T, B, so, torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    for key, t in before.items():
+        if not (alias and key == "state_grad"):
+            assert torch.equal(ins[key].view(torch.int32), t.view(torch.int32)), f"input {key} was written"
+    assert ws.guards_kept(), "the workspace's surroundings were written"
+    gone = {key for key in outs if key in leave_out or not n[key] or (alias and key == "state0_grad")}
+    for key, g in outs.items():
+        assert g.guards_kept(), f"the surroundings of {key} were written"
+        if key in gone:
+            assert g.untouched(), f"{key} was left out and written"
+    got = {}
+    for key, b in H.OUT.items():
+        if b not in outs or b in gone:
+            continue
+        h = outs[b].mid.cpu().numpy()
+        if b in ("in_grad", "out"):
+            assert H.outside_keeps_sentinel(h, row0, T), f"rows of {b} outside [{row0}, {row0 + T}) were written"
+            got[key + "_buffer"] = h
+            h = H.from_sm(h, T, row0)
+        got[key] = h
+    if alias and "state0_grad" not in leave_out:
+        got["state"] = ins["state_grad"].cpu().numpy()
+    if "state_out" not in leave_out:
+        got["state_out"] = outs["state_out"].mid.cpu().numpy()
+    nb = -(-T // p.ring_recording_block_rows(T, B, c))
+    got["starts"] = ws.mid[:nb * p.n_state * ns].view(nb, p.n_state, ns).cpu().numpy()
+    return got
+
+
+# ---- the kernels the GPU tests launch: tests/golden/ring_sm_recording_kernels.fzm.gz ---------------------------------------------------
+def resolve():
+    """what a recording process calls (FLOWZ_HIP_MANIFEST set): the stream-major ring states kernels, the stream-major ring and ring loss
+    kernels at the strides used, the time-major kernels compared with, and the stream-major forward kernels state_out is compared with"""
+    from zignal_amd import flowz as F
+    for n in sorted(GRAPHS):
+        p = prog(n)
+        p.ring_states_resources(stream_major=True)
+        p.ring_states_resources()
+        for c in STRIDES:
+            for sm in (True, False):
+                p.ring_grad_resources(c, stream_major=sm)
+                p.ring_loss_grad_resources(c, stream_major=sm)
+        ns, rows = forward_shape(n)
+        p.build(F.make_variant(0, 0, 0, F.C.FZ_VF_STREAM_MAJOR), ns, rows)
+
+
+def record():
+    """record the manifest with the library as it is; needs no GPU.  By hand: PYTHONPATH=. python tests/ring_sm_recording.py"""
+    from zignal_amd import flowz as F
+    code = "import sys\nsys.path[:0] = [%r, %r]\nimport ring_sm_recording as S\nS.resolve()\n" % (os.path.dirname(HERE), HERE)
+    with tempfile.TemporaryDirectory() as td:
+        raw = os.path.join(td, "manifest.fzm")
+        subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, FLOWZ_HIP_MANIFEST=raw))
+        with open(raw, "rb") as f, open(MANIFEST, "wb") as out:
+            out.write(gzip.compress(f.read(), 9, mtime=0))
+    return F.manifest_build(MANIFEST)
+
+
+manifest_variants = R.RL.manifest_variants
+
+
+if __name__ == "__main__":
+    print("kernel manifest:", record())

@@ -58,8 +58,18 @@ the route first, then --steps launches per leg in a forward and again in a backw
 two legs must agree bit for bit -- dL/dx, the state gradient, the loss -- before a time is printed.  There is no pass mark: a line slower
 than the route says so.  The table goes to stdout and to profiles/r15/ring_stream_major.txt (the --loss table is appended to it).
 
+--rings --recording --layout stream-major|compare [--loss]: the backward of a whole recording of those graphs on stream-major buffers,
+run_recording_ring_grad_stream_major (fz_run_recording_ring_grad_stream_major; with --loss run_recording_ring_loss_grad_stream_major).
+stream-major: that call alone.  compare: against the route a caller with [batch, time] buffers had before it -- fz_transpose_frames of x
+and of dL/dy (or the target) to time-major, the time-major ring recording, fz_transpose_frames of dL/dx back (every frame buffer and both
+workspaces allocated beforehand).  65 536 x 16 384 and 1 048 576 x 4096; same buffers, same process, legs interleaved (100 ms of the route
+first, then --steps calls per leg in a forward and again in a backward pass: medians of 2 x --steps HIP-event timings, ten at the default).
+The two legs must agree bit for bit -- dL/dx, the state gradient, the loss -- before a time is printed.  There is no pass mark: a line slower
+than the route beyond the route's own spread says so.  The table goes to stdout and to profiles/r16/ring_sm_recording.txt (the --loss table
+is appended to it).
+
 usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings]
-       (--rings takes --layout compare, alone or with --loss)
+       (--rings takes --layout compare, alone or with --loss; --rings --recording takes --layout stream-major|compare, alone or with --loss)
 """
 import argparse
 import datetime
@@ -653,6 +663,96 @@ def rings_recording_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
+def rings_recording_sm_bench(a, torch):
+    """the backward of a whole recording of graphs with delay lines in LDS on stream-major buffers (plain, or with a.loss under the
+    squared-error loss), alone (--layout stream-major) or against transpose + the time-major ring recording + transpose (--layout
+    compare), interleaved in one process; the two legs agree bit for bit before a time is printed"""
+    import time
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+    props = torch.cuda.get_device_properties(0)
+    loss, both = bool(a.loss), a.layout == "compare"
+    call = "run_recording_ring_loss_grad" if loss else "run_recording_ring_grad"
+    say(f"# command: tools/grad_bench.py --rings --recording --layout {a.layout}{' --loss' if loss else ''} --steps {a.steps} --legs {a.legs}")
+    say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+    say(f"# sm = one {call}_stream_major call on [n_streams, T] buffers; route = fz_transpose_frames of x and of {'the target' if loss else 'dL/dy'}, {call}, fz_transpose_frames of dL/dx back;")
+    say(f"# every gradient, default checkpoint stride and B; HIP events, {a.steps} calls per leg and pass, a forward and a backward pass over the legs;")
+    say("# spread = max - min of the route's own repeats; the legs agree bit for bit (dL/dx, the state gradient" + (", the loss" if loss else "") + ") before a time is printed;")
+    say("# slower = sm median > route median + the route's spread")
+    say(f"{'graph':16s} {'streams x T':>16s} {'B':>5s} {'route ms':>9s} {'spread':>7s} {'sm ms':>9s} {'sm/route':>9s} {'slower':>6s} {'ws MB':>9s} {'U':>3s} {'R':>3s} {'lanes':>5s} {'vgprs':>6s} "
+        f"{'sgpr spills':>11s} {'lds':>6s}  stream-major ring states kernel")
+    shapes = REC_SHAPES["small"] + REC_SHAPES["large"] if a.legs == "all" else REC_SHAPES[a.legs]
+    for ns, T in shapes:
+        x_sm = torch.empty((ns, T, 1), dtype=torch.float32, device="cuda")
+        F.synth_fill(x_sm, seed=W.SEED)
+        yt_sm = torch.empty_like(x_sm)                         # dL/dy, or the target
+        F.synth_fill(yt_sm, seed=W.SEED + 1)
+        gx_sm = torch.empty_like(x_sm)
+        if both:
+            gx_back = torch.empty_like(x_sm)
+            x_tm, yt_tm = (torch.empty((T, ns, 1), dtype=torch.float32, device="cuda") for _ in range(2))
+        n = float(ns) * T
+        want = ("x", "state", "params", "consts") + (("loss",) if loss else ())
+        for name, fn in RING_GRAPHS.items():
+            prog = F.compile(F.from_sexpr(fn()))
+            s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+            B, ws_bytes = prog.ring_recording_block_rows(T), prog.ring_recording_workspace_bytes(ns, T)
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device="cuda")
+            kw = dict(grad_scale=2.0 / n) if loss else {}
+
+            def route():
+                F.frames_from_stream_major(x_sm, 0, out=x_tm)
+                F.frames_from_stream_major(yt_sm, 0, out=yt_tm)
+                r = getattr(prog, call)(x_tm, yt_tm, s0, None, state_grad=s0, want=want, workspace=ws, **kw)
+                F.frames_to_stream_major(r["x"], out=gx_back)
+                return r
+
+            def sm():
+                return getattr(prog, call + "_stream_major")(x_sm, yt_sm, s0, None, state_grad=s0, want=want, in_grad=gx_sm, workspace=ws, **kw)
+            legs = {"route": route, "sm": sm} if both else {"sm": sm}
+            first = {k: f() for k, f in legs.items()}           # JIT, allocator; and the legs agree bit for bit
+            torch.cuda.synchronize()
+            if both:
+                same = lambda u, v: torch.equal(u.view(torch.int32), v.view(torch.int32))   # noqa: E731
+                assert same(gx_sm, gx_back), f"{name} {ns} x {T}: dL/dx of the two legs differs"
+                for key in ("state",) + (("loss",) if loss else ()):
+                    assert same(first["sm"][key], first["route"][key]), f"{name} {ns} x {T}: {key} of the two legs differs"
+            del first
+            yard = legs["route" if both else "sm"]
+            t_end = time.time() + 0.1
+            while time.time() < t_end:                          # at least 100 ms of the yardstick before the first timing
+                yard()
+                torch.cuda.synchronize()
+            got = {k: [] for k in legs}
+            for order in (list(legs), list(legs)[::-1]):
+                for k in order:
+                    got[k] += samples(legs[k], a.steps, torch)
+            med = {k: float(np.median(v)) for k, v in got.items()}
+            res, sym = prog.ring_states_resources(stream_major=True), prog.ring_states_kernel_symbol(stream_major=True)
+            R, lanes = int(sym.split("_g")[0].split("r")[-1].split("b")[0]), int(sym.split("_g")[0].split("b")[-1])
+            if both:
+                spread = max(got["route"]) - min(got["route"])
+                vs = f"{med['route']:9.3f} {spread:7.3f} {med['sm']:9.3f} {med['sm'] / med['route']:9.3f} {'YES' if med['sm'] > med['route'] + spread else 'no':>6s}"
+            else:
+                vs = f"{'-':>9s} {'-':>7s} {med['sm']:9.3f} {'-':>9s} {'-':>6s}"
+            say(f"{name:16s} {f'{ns} x {T}':>16s} {B:5d} {vs} {ws_bytes / 2**20:9.1f} {res['unroll']:3d} {R:3d} {lanes:5d} {res['vgprs'] + res['agprs']:6d} "
+                f"{res['sgpr_spills']:11d} {res['lds_bytes']:6d}  {sym}")
+            say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
+            del s0, ws
+            torch.cuda.empty_cache()
+        del x_sm, yt_sm, gx_sm
+        if both:
+            del gx_back, x_tm, yt_tm
+        torch.cuda.empty_cache()
+    out = os.path.join(ROOT, "profiles", "r16", "ring_sm_recording.txt")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a" if loss and os.path.exists(out) else "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=2)
@@ -666,6 +766,8 @@ def main():
     import torch
 
     torch.cuda.set_device(0)
+    if a.rings and a.recording and a.layout != "time-major":
+        return rings_recording_sm_bench(a, torch)
     if a.rings and a.recording:
         return rings_recording_bench(a, torch)
     if a.rings and a.layout == "compare":

@@ -13,9 +13,12 @@ usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par
        tools/isa_stats.py ringlossgrad [graph] [--layout stream-major]
                                                            the same line for the kernel of fz_run_block_ring_loss_grad, next to the plain
                                                            ring kernel's figures (graph: also a name of tests/ring_loss_graphs.py)
-       tools/isa_stats.py ringstates [graph]               the block-start-states kernel of fz_run_recording_ring_grad next to the ring
+       tools/isa_stats.py ringstates [graph] [--layout stream-major]
+                                                           the block-start-states kernel of fz_run_recording_ring_grad next to the ring
                                                            adjoint kernel: registers, spills, scratch, LDS bytes, and the ds_* and
-                                                           vector-memory instructions in the kernel (graph: as for ringlossgrad)
+                                                           vector-memory instructions in the kernel (graph: as for ringlossgrad, or `all`:
+                                                           the ten of tests/ring_loss_graphs.py); --layout stream-major: the kernel of
+                                                           fz_run_recording_ring_grad_stream_major, with its patch rows R and lanes
 """
 import glob
 import os
@@ -126,18 +129,20 @@ def ring_grad_lines(name, loss=False, sm=False):
     return out
 
 
-def ring_states_lines(name):
+def ring_states_lines(name, sm=False):
     """the ring states kernel: its resources next to the ring adjoint kernel's, and the instructions of its text -- the unrolled group of
-    U rows (U ring-read sets, U ds_write per ring line, the next group's U x loads) plus the two state dumps (block start, state_out)"""
+    U rows (U ring-read sets, U ds_write per ring line, the next group's U x loads) plus the two state dumps (block start, state_out).
+    sm: the kernel for stream-major buffers (its ds_* include the patch: the fetched pieces parked, the group's own-row reads; its
+    vector-memory loads are the patch fetch, the state and the coefficients)"""
     import ring_loss_graphs as RL
     build = RL.GRAPHS.get(name) or GRAPHS[name]
     p = F.compile(F.from_sexpr(build()))
-    r, ring = p.ring_states_resources(), p.ring_grad_resources()
+    r, ring = p.ring_states_resources(stream_major=sm), p.ring_grad_resources(0, stream_major=sm)
     old = os.environ.get("FLOWZ_HIP_CACHE")
     try:
         with tempfile.TemporaryDirectory() as td:
             os.environ["FLOWZ_HIP_CACHE"] = td
-            F.compile(F.from_sexpr(build())).ring_states_resources()
+            F.compile(F.from_sexpr(build())).ring_states_resources(stream_major=sm)
             dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", glob.glob(td + "/*.hsaco")[0]], text=True)
     finally:
         if old is None:
@@ -149,7 +154,9 @@ def ring_states_lines(name):
     n = {"ds_read": sum(o.startswith("ds_read") for o in ops), "ds_write": sum(o.startswith("ds_write") for o in ops),
          "vmem_load": sum("load" in o for o in vmem), "vmem_store": sum("store" in o for o in vmem), "valu": sum(o.startswith("v_") for o in ops),
          "s_barrier": ops.count("s_barrier"), "atomic": sum("atomic" in o for o in ops)}
-    return [f"{name} {p.ring_states_kernel_symbol()}: U {r['unroll']}, {r['vgprs'] + r['agprs']} VGPRs (ring adjoint {ring['vgprs'] + ring['agprs']}), "
+    sym = p.ring_states_kernel_symbol(stream_major=sm)
+    geo = f"R {sym.split('_g')[0].split('r')[-1].split('b')[0]}, {sym.split('_g')[0].split('b')[-1]} lanes, " if sm else ""
+    return [f"{name} {sym}: U {r['unroll']}, {geo}{r['vgprs'] + r['agprs']} VGPRs (ring adjoint {ring['vgprs'] + ring['agprs']}), "
             f"{r['sgprs']} SGPRs, {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills (ring adjoint {ring['vgpr_spills']} / {ring['sgpr_spills']}), "
             f"{r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS (ring adjoint {ring['lds_bytes']})",
             "  in the kernel: " + ", ".join(f"{v} {k}" for k, v in n.items())]
@@ -165,7 +172,12 @@ def main():
         sm = a[i + 1] == "stream-major"
         del a[i:i + 2]
     if a and a[0] == "ringstates":
-        print("\n".join(ring_states_lines(a[1] if len(a) > 1 else "ldsring")))
+        names = [a[1] if len(a) > 1 else "ldsring"]
+        if names == ["all"]:
+            import ring_loss_graphs as RL
+            names = sorted(RL.GRAPHS)
+        for n in names:
+            print("\n".join(ring_states_lines(n, sm)))
         return
     if a and a[0] == "ringgrad":
         print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring", sm=sm)))

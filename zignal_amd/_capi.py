@@ -210,6 +210,11 @@ def _load():
         "fz_program_ring_states_resources": (ctypes.c_int, [P, ctypes.POINTER(KernelResources)]),
         "fz_program_ring_states_kernel_symbol": (ctypes.c_long, [P, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_ring_states_source": (ctypes.c_long, [P, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_run_recording_ring_grad_stream_major": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, u32, u32, u32, P, P]),
+        "fz_run_recording_ring_loss_grad_stream_major": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u64, u32, u32, u32, u32, P, P]),
+        "fz_program_ring_states_resources_for": (ctypes.c_int, [P, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_ring_states_kernel_symbol_for": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_ring_states_source_for": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_pcm16_check": (ctypes.c_int, [P]),
         "fz_run_block_pcm16": (ctypes.c_int, [P, P, P, P, P, u64, u32, u32, u32, P]),
         "fz_program_pcm16_resources": (ctypes.c_int, [P, u32, u32, u64, ctypes.POINTER(KernelResources)]),

@@ -27,6 +27,8 @@ from the last to the first), and also returns the state after the recording.
 mse_recording_rings(prog, x, target, ...) is mse_recording() for every graph run_rings() takes, time-major
 (Program.run_recording_ring_loss_grad: the ring states kernel, then the ring loss kernel block by block); mse_recording() keeps refusing
 graphs with delay lines deeper than 8 samples.
+mse_recording_rings(..., stream_major=True) is the same on stream-major tensors (Program.run_recording_ring_loss_grad_stream_major):
+a batch of recordings lying as [batch, time] is fitted in bounded workspace without a transposed copy.
 """
 from __future__ import annotations
 
@@ -61,7 +63,8 @@ def _front_door(prog: Program, x, consts, rings):
 def _backward_call(prog: Program, rings, stream_major, loss=False, recording=False):
     """the bound Program method of one corner of the backward family"""
     name = ("run_recording_" if recording else "run_block_") + ("ring_" if rings else "") + ("loss_grad" if loss else "grad")
-    return getattr(prog, name + ("_stream_major" if stream_major and not recording else ""))
+    # (the plain recording calls take the layout as a keyword; every other stream-major corner is a method of its own)
+    return getattr(prog, name + ("_stream_major" if stream_major and (rings or not recording) else ""))
 
 
 _WANT = ("x", "state", "params", "consts")
@@ -205,11 +208,13 @@ def mse_recording(prog: Program, x, target, state=None, params=None, consts=None
     return loss, state_out.detach()
 
 
-def mse_recording_rings(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0):
+def mse_recording_rings(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0, stream_major=False):
     """mse_recording() for graphs with delay lines deeper than 8 samples -- and every graph mse_recording() takes --, time-major frames:
     returns (loss, state_out) over a whole recording in bounded workspace (Program.ring_recording_workspace_bytes: the state before every
     block plus one block's checkpoints and tape; block_rows = 0 lets the library choose, otherwise a multiple of 4).  The gradients
-    have the bits of mse_rings()'s over the same rows (include/flowz_hip.h: fz_run_recording_ring_loss_grad)."""
+    have the bits of mse_rings()'s over the same rows (include/flowz_hip.h: fz_run_recording_ring_loss_grad).
+    stream_major: the tensor shapes of mse_recording(..., stream_major=True), a [batch, time] tensor as it lies for one wire
+    (Program.run_recording_ring_loss_grad_stream_major); block_rows times n_in and n_out are then multiples of 4."""
     _front_door(prog, x, consts, True)
-    loss, state_out = _Mse.apply(prog, x, target, state, params, consts, False, True, int(block_rows))
+    loss, state_out = _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), True, int(block_rows))
     return loss, state_out.detach()

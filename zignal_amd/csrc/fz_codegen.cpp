@@ -25,13 +25,14 @@ extern const char* const kSkeletonBody_sm_long;
 extern const char* const kSkeletonBody_sm_short;
 extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
-extern const char* const kSkeletonAdjoint;       // fz_kernel_adjoint.hip.inc: a kernel text of its own, like the six below
+extern const char* const kSkeletonAdjoint;       // fz_kernel_adjoint.hip.inc: a kernel text of its own, like the seven below
 extern const char* const kSkeletonAdjointSm;
 extern const char* const kSkeletonAdjointRing;
 extern const char* const kSkeletonAdjointRingSm;
 extern const char* const kSkeletonStates;
 extern const char* const kSkeletonStatesSm;
 extern const char* const kSkeletonStatesRing;
+extern const char* const kSkeletonStatesRingSm;
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
@@ -54,6 +55,7 @@ static const AdjointRow& adjoint_row(const Variant& v)
       {FZ_VF_STATES, "fz_states", "", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_SM, "fz_states", "_sm", kSkeletonStatesSm, true},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStatesRing, false},
+      {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_states", "_ring_sm", kSkeletonStatesRingSm, true},
    };
    for (const AdjointRow& r : rows)
       if (r.bits == (v.flags & (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM)) && !((v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_LOSS))) return r;

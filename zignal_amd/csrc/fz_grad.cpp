@@ -8,7 +8,8 @@
 //     (delay lines in LDS: FZ_VF_ADJOINT_RING)
 //   fz_run_recording_grad: the block-start states     fz_kernel_states.hip.inc          fz_kernel_states_sm.hip.inc
 //     (FZ_VF_STATES)
-//   fz_run_recording_ring_grad: the same              fz_kernel_states_ring.hip.inc     not built
+//   fz_run_recording_ring_grad[_stream_major]:        fz_kernel_states_ring.hip.inc     fz_kernel_states_ring_sm.hip.inc
+//     the same
 //
 // Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the four adjoint kernels forms dL/dy itself, from a
 // target: the same text with FZ_LOSS, the same C, workgroup and workspace.  The ring calls share the checks and the launch with the
@@ -257,15 +258,69 @@ static Variant ring_states_variant(const Graph& g)
    return v;
 }
 
+// ---- the same on stream-major buffers: rings and an x-only patch share the LDS of a workgroup ------------------------------------------
+// A workgroup of `block` lanes holds ring[slots][block] and block / 64 patches of [64][R n_in + 4] floats
+// (fz_kernel_states_ring_sm.hip.inc): 4 block (slots + R n_in + 4) bytes; a graph without input wires declares no patch.
+static uint64_t ring_states_sm_lds_bytes(const Graph& g, const RingLayout& rl, uint32_t block, uint32_t R)
+{
+   return 4ull * block * ((uint64_t)rl.slots + (g.n_in ? (uint64_t)R * g.n_in + 4u : 0u));
+}
+
+// The one home of the rule that chooses its workgroup and patch length together, ring_sm_geometry's shape: R runs over
+// R0 = 2 * states_sm_patch_rows(g), R0 / 2, ... down to Rmin = max(4, U) (powers of two: multiples of 4 and of U); per R the block over
+// 256, 128, 64.  The first pair that fits the LDS twice wins; failing that the first that fits once.  R0 is twice the plain states
+// kernel's -- one stream's run is two cache lines, the 256-byte in-run of the forward stream-major long-run bodies: where the rings
+// bound the workgroup anyway the longer run costs no occupancy.  Static, not measured against R0 = states_sm_patch_rows(g).
+static RingSmGeometry ring_states_sm_geometry(const Graph& g, const RingLayout& rl, uint32_t U)
+{
+   const uint32_t R0 = 2 * states_sm_patch_rows(g), Rmin = std::max<uint32_t>(4u, U);
+   for (uint64_t times : {2u, 1u})
+      for (uint32_t R = R0; R >= Rmin; R /= 2)
+         for (uint32_t b : {256u, 128u, 64u})
+            if (times * ring_states_sm_lds_bytes(g, rl, b, R) <= kLdsBytes) return RingSmGeometry{b, R};
+   return RingSmGeometry{};
+}
+
+// the Variant of the block-start-states kernel of a ring recording on stream-major buffers: the scope of the ring backward, the
+// unrolled group of the states kernel, {P = R, block} of ring_states_sm_geometry; for a graph without a ring line the stream-major
+// states Variant itself
+static Variant ring_states_sm_variant(const Graph& g)
+{
+   require_supported(g, true);
+   if (!has_ring_line(g)) return states_variant(g, true);
+   const RingLayout rl = ring_layout(g);
+   if (!ring_block(rl)) (void)ring_adjoint_variant(g, 0);  // (the refusal of fz_program_ring_grad_check, in its words)
+   Variant v;
+   v.U = states_unroll(g);
+   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM;
+   const RingSmGeometry geo = ring_states_sm_geometry(g, rl, v.U);
+   if (!geo.block) {
+      const uint32_t Rmin = std::max<uint32_t>(4u, v.U);
+      fail(FZ_E_UNSUPPORTED, "stream-major ring recording: the rings of the delay lines deeper than 8 samples (" + std::to_string(rl.slots) + " samples) plus a patch of " +
+                                std::to_string(Rmin) + " rows of " + std::to_string(g.n_in) + " input wires, " + std::to_string(ring_states_sm_lds_bytes(g, rl, 64, Rmin)) +
+                                " bytes per 64 lanes, do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup");
+   }
+   v.P = geo.R;                                             // (the patch rows travel in P: codegen puts them into FZ_R and the symbol)
+   v.block = geo.block;
+   return v;
+}
+
+// the Variant of a recording's states kernel, whichever call asks
+static Variant recording_states_variant(const Graph& g, bool ring, bool stream_major)
+{
+   if (!ring) return states_variant(g, stream_major);
+   return stream_major ? ring_states_sm_variant(g) : ring_states_variant(g);
+}
+
 // Could the backward have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
 // The family bits name the maker; v fits when that maker, asked for v's own stride, makes exactly v.  So nothing fits that no maker
 // makes: another bit, U = 0 (the maker answers with the default stride), a ring bit on a graph without a ring line (the ring makers
-// hand over to the plain ones), the loss or ring + stream-major next to FZ_VF_STATES.
+// hand over to the plain ones), the loss next to FZ_VF_STATES.
 bool grad_variant_fits(const Graph& g, const Variant& v)
 {
    const bool ring = v.flags & FZ_VF_ADJOINT_RING, sm = v.flags & FZ_VF_ADJOINT_SM, loss = v.flags & FZ_VF_ADJOINT_LOSS;
    try {
-      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss) : ring ? ring_states_variant(g) : states_variant(g, sm);
+      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss) : recording_states_variant(g, ring, sm);
       return w.P == v.P && w.U == v.U && w.block == v.block && w.flags == v.flags;
    } catch (const Error&) {
       return false;                                         // (a graph, a stride or a patch the call refuses)
@@ -562,8 +617,8 @@ static uint64_t ring_recording_workspace_bytes(const Graph& g, uint64_t n_stream
 
 // The backward of a recording: the states kernel once, then the block launches from the last block to the first (the contract is in
 // include/flowz_hip.h).  Every check -- of the call over its T rows, then of every block launch as a direct call would be checked --
-// runs before a device is needed.  call.ring: the recording of the ring family (time-major) -- the scope, the states kernel, B and
-// the workspace are that family's, the rest is shared.
+// runs before a device is needed.  call.ring: the recording of the ring family, in either layout -- the scope, the states kernel, B
+// and the workspace are that family's, the rest is shared.
 static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
                          uint32_t block_rows, float* state_out, void* stream)
 {
@@ -572,7 +627,7 @@ static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, u
    if (call.ring) (void)ring_adjoint_variant(g, 0);        // (scope first: the refusals of fz_program_ring_grad_check)
    else require_supported(g);                              // (... of fz_program_grad_check)
    // (a graph without delay lines launches no states kernel: its LDS patch is not asked to fit)
-   const Variant sv = !g.n_state ? Variant{} : call.ring ? ring_states_variant(g) : states_variant(g, stream_major);
+   const Variant sv = !g.n_state ? Variant{} : recording_states_variant(g, call.ring, stream_major);
    auto rows_per_block = [&](uint32_t C) { return call.ring ? ring_recording_block_rows(g, n_samples, C, block_rows) : recording_block_rows(n_samples, C, block_rows); };
    if (!stream_major && block_rows % 4)
       fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
@@ -869,6 +924,18 @@ int fz_run_recording_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, u
    FZ_GUARD(return run_recording(p, ring_call_of(p, a), FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
 }
 
+int fz_run_recording_ring_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                            uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream)
+{
+   FZ_GUARD(return run_recording(p, ring_call_of(p, a), FZ_GRAD_STREAM_MAJOR, n_streams, rows_total, row0, n_samples, block_rows, state_out, hip_stream);)
+}
+
+int fz_run_recording_ring_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                                 uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream)
+{
+   FZ_GUARD(return run_recording(p, ring_call_of(p, a), FZ_GRAD_STREAM_MAJOR, n_streams, rows_total, row0, n_samples, block_rows, state_out, hip_stream);)
+}
+
 int fz_program_ring_states_resources(fz_program* p, fz_kernel_resources* out)
 {
    return grad_resources(p, out, "fz_program_ring_states_resources", [&] { return ring_states_variant(p->g); });
@@ -882,6 +949,21 @@ long fz_program_ring_states_kernel_symbol(fz_program* p, char* buf, size_t cap)
 long fz_program_ring_states_source(fz_program* p, char* buf, size_t cap)
 {
    return grad_source(p, buf, cap, [&] { return ring_states_variant(p->g); });
+}
+
+int fz_program_ring_states_resources_for(fz_program* p, uint32_t layout, fz_kernel_resources* out)
+{
+   return grad_resources(p, out, "fz_program_ring_states_resources_for", [&] { return recording_states_variant(p->g, true, layout_is_stream_major(layout)); });
+}
+
+long fz_program_ring_states_kernel_symbol_for(fz_program* p, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_symbol(p, buf, cap, [&] { return recording_states_variant(p->g, true, layout_is_stream_major(layout)); });
+}
+
+long fz_program_ring_states_source_for(fz_program* p, uint32_t layout, char* buf, size_t cap)
+{
+   return grad_source(p, buf, cap, [&] { return recording_states_variant(p->g, true, layout_is_stream_major(layout)); });
 }
 
 int fz_program_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,

@@ -275,9 +275,13 @@ constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // its own, a symbol each), {P = rows of the LDS patch, U = the ring kernel's checkpoint
 // rows, block = 256 / 128 / 64}: rings and patches share the workgroup's LDS, so fz_grad.cpp: ring_sm_geometry chooses P and block
 // together and ring_sm_adjoint_variant is the one place that makes one.
-// With FZ_VF_STATES next to it (and neither FZ_VF_ADJOINT_LOSS nor FZ_VF_ADJOINT_SM: stream-major ring recordings are not built): the block-start-states kernel of a ring recording
+// With FZ_VF_STATES next to it (never FZ_VF_ADJOINT_LOSS): the block-start-states kernel of a ring recording
 // (fz_run_recording_ring_grad; fz_kernel_states_ring.hip.inc: a text and a symbol of its own), {P = 1, U = the rows of one unrolled
 // group, block = the ring adjoint kernel's}; fz_grad.cpp: ring_states_variant is the one place that makes one.
+// With FZ_VF_STATES and FZ_VF_ADJOINT_SM next to it: the same for STREAM-MAJOR buffers (fz_run_recording_ring_grad_stream_major;
+// fz_kernel_states_ring_sm.hip.inc: a text and a symbol of its own), {P = rows of the x-only LDS patch, U = the rows of one unrolled
+// group, block = 256 / 128 / 64}: fz_grad.cpp: ring_states_sm_geometry chooses P and block together and ring_states_sm_variant is the
+// one place that makes one.
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte

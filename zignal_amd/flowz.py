@@ -356,7 +356,7 @@ def _window(x, row0, n_samples, in_grad):
     return int(row0), (x.shape[1] - int(row0)) if n_samples is None else int(n_samples), in_grad
 
 
-# the C entry point of Program._run_grad by (ring, loss, stream-major window, recording); the ring recordings are time-major only
+# the C entry point of Program._run_grad by (ring, loss, stream-major window, recording)
 _GRAD_ENTRY = {
     (False, False, False, False): "fz_run_block_grad",
     (False, True, False, False): "fz_run_block_loss_grad",
@@ -372,6 +372,8 @@ _GRAD_ENTRY = {
     (False, True, True, True): "fz_run_recording_loss_grad",
     (True, False, False, True): "fz_run_recording_ring_grad",
     (True, True, False, True): "fz_run_recording_ring_loss_grad",
+    (True, False, True, True): "fz_run_recording_ring_grad_stream_major",
+    (True, True, True, True): "fz_run_recording_ring_loss_grad_stream_major",
 }
 
 
@@ -961,22 +963,23 @@ class Program:
         """workspace bytes of run_recording_ring_grad / run_recording_ring_loss_grad: the block-start states, then one block's ring workspace"""
         return _out(ctypes.c_uint64, C.lib.fz_program_ring_recording_workspace, self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows))
 
-    def ring_states_resources(self) -> dict:
+    def ring_states_resources(self, stream_major: bool = False) -> dict:
         """grad_resources() of the block-start-states kernel of a ring recording; 'unroll' = the rows of its unrolled group, 'lds_bytes' =
-        the value rings of one workgroup (the ring adjoint kernel's bytes)"""
-        return _resources(C.lib.fz_program_ring_states_resources, self._h)
+        the value rings of one workgroup (the ring adjoint kernel's bytes).  stream_major: the kernel of
+        run_recording_ring_grad_stream_major ('lds_bytes': rings and the x-only patches)"""
+        return _resources(C.lib.fz_program_ring_states_resources_for, self._h, int(bool(stream_major)))
 
-    def ring_states_kernel_symbol(self) -> str:
-        return _name(C.lib.fz_program_ring_states_kernel_symbol, self._h)
+    def ring_states_kernel_symbol(self, stream_major: bool = False) -> str:
+        return _name(C.lib.fz_program_ring_states_kernel_symbol_for, self._h, int(bool(stream_major)))
 
-    def ring_states_source(self) -> str:
-        return _text(C.lib.fz_program_ring_states_source, self._h)
+    def ring_states_source(self, stream_major: bool = False) -> str:
+        return _text(C.lib.fz_program_ring_states_source_for, self._h, int(bool(stream_major)))
 
     def run_recording_ring_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0,
                                 block_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None, in_grad=None, workspace=None):
         """run_block_ring_grad over a whole recording in bounded workspace (fz_run_recording_ring_grad), as run_recording_grad is to
         run_block_grad: every bit is run_block_ring_grad's over the same rows, "state_out" may be named in want.  Time-major frames
-        only: row0 must be 0, n_samples None or T, in_grad None.  For a graph run_recording_grad takes it is run_recording_grad."""
+        (stream-major buffers: run_recording_ring_grad_stream_major): row0 must be 0, n_samples None or T, in_grad None.  For a graph run_recording_grad takes it is run_recording_grad."""
         _require(int(row0) == 0 and (n_samples is None or int(n_samples) == x.shape[0]) and in_grad is None,
                  "run_recording_ring_grad takes time-major frames: no window (row0, n_samples, in_grad)")
         return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None, None, (int(block_rows), workspace), ring=True)
@@ -991,12 +994,32 @@ class Program:
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), out),
                               (int(block_rows), workspace), ring=True)
 
+    def run_recording_ring_grad_stream_major(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None,
+                                             checkpoint_rows: int = 0, block_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None,
+                                             in_grad=None, workspace=None):
+        """run_recording_ring_grad on stream-major buffers (fz_run_recording_ring_grad_stream_major): x [n_streams, rows, n_in] (or
+        [n_streams, rows] for one input wire: a [batch, time] tensor as it lies), the windows, in_grad and result dict of
+        run_recording_grad(stream_major=True), the workspace of run_recording_ring_grad.  Not a bit differs from run_recording_ring_grad
+        on the transposed frames, nor from run_block_ring_grad_stream_major over the same window.  For a graph run_recording_grad takes
+        it is run_recording_grad(stream_major=True)."""
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad), None,
+                              (int(block_rows), workspace), ring=True)
+
+    def run_recording_ring_loss_grad_stream_major(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0,
+                                                  want=LOSS_GRAD_WANT, accum=None, checkpoint_rows: int = 0, block_rows: int = 0, row0: int = 0,
+                                                  n_samples: Optional[int] = None, in_grad=None, out=None, workspace=None):
+        """run_recording_ring_loss_grad on stream-major buffers (fz_run_recording_ring_loss_grad_stream_major): the arguments, windows
+        and result dict of run_recording_loss_grad(stream_major=True); not a bit differs from run_recording_ring_loss_grad on the
+        transposed frames."""
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad),
+                              (float(grad_scale), out), (int(block_rows), workspace), ring=True)
+
     def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None, ring=False):
         """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers; loss: None, or
         (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
         (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is of the ring family:
-        run_block_ring_grad / run_block_ring_loss_grad and their _stream_major twins, or with recording (time-major) run_recording_ring_grad /
-        run_recording_ring_loss_grad"""
+        run_block_ring_grad / run_block_ring_loss_grad, or with recording run_recording_ring_grad / run_recording_ring_loss_grad, and their
+        _stream_major twins"""
         import torch
 
         if ring:
@@ -1099,7 +1122,9 @@ class Program:
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
         hs = torch.cuda.current_stream().cuda_stream
         fn = getattr(C.lib, _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
-        if recording is not None and ring:                            # ring recording
+        if recording is not None and ring and window is not None:     # ring recording window
+            C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
+        elif recording is not None and ring:                          # ring recording
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
         elif recording is not None:                                   # recording, either layout
             w = (int(rows), row0) if window is not None else (0, 0)
