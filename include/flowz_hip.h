@@ -812,7 +812,7 @@ long fz_program_states_source(fz_program* p, uint32_t layout, char* buf, size_t 
  * size; those of every block launch; with more than one block, state0_grad not NULL.  n_streams == 0 or n_samples == 0: FZ_OK,
  * nothing is touched.  Asynchronous on hip_stream.
  *
- * The ring states kernel is a kernel text of its own, fz_states_ring_kernel_u<U>b<lanes>_g<tag> (U rows per unrolled group; the
+ * The ring states kernel is a kernel of its own, fz_states_ring_kernel_u<U>b<lanes>_g<tag> (U rows per unrolled group; the
  * lanes and lds_bytes of the ring adjoint kernel); fz_program_ring_states_* inspect it like fz_program_states_*. */
 int fz_program_ring_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows);
 int fz_program_ring_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
@@ -855,7 +855,7 @@ long fz_program_ring_states_source(fz_program* p, char* buf, size_t cap);
  * state0_grad not NULL; those of every block launch.  n_streams == 0 or n_samples == 0: FZ_OK, nothing is touched.  Asynchronous on
  * hip_stream.
  *
- * The states kernel is a kernel text of its own, fz_states_ring_sm_kernel_u<U>r<R>b<lanes>_g<tag>: U rows per unrolled group as for
+ * The states kernel is a kernel of its own, fz_states_ring_sm_kernel_u<U>r<R>b<lanes>_g<tag>: U rows per unrolled group as for
  * every states kernel; x moves through a wave-private LDS patch of R rows next to the value rings, lds_bytes =
  * 4 * lanes * (ring samples + R * n_in + 4) (no patch for a graph without input wires).  R runs over twice the R of
  * fz_states_sm_kernel, halved down to max(4, U); per R the lanes over 256 / 128 / 64; the first pair that fits a compute unit's LDS

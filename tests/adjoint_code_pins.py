@@ -6,11 +6,14 @@ on the compiler, like the code ids of tests/golden/graph_pins.json.
 The kernels: for every graph of grad_graphs.SUPPORTED the adjoint, loss and states kernel in both layouts at the default stride; for every
 ring graph (ring_sm_graphs.GRAPHS, which holds those of ring_grad_graphs, ring_loss_graphs and ring_recording_graphs) at every stride of
 ring_sm_graphs.STRIDES the ring and ring loss kernel in both layouts -- where the geometry rule refuses, the pin is the refusal's text --
-and the ring states kernel.
+and the ring states kernel in both layouts.
 
 The committed file was written by pins() from the parent commit of the change that folded the loss kernels into their siblings, in a
 checkout of its own:
-    PYTHONPATH=<parent checkout>:tests python tests/adjoint_code_pins.py > tests/golden/adjoint_code_pins.json"""
+    PYTHONPATH=<parent checkout>:tests python tests/adjoint_code_pins.py > tests/golden/adjoint_code_pins.json
+The ring_states/sm/* entries are younger than that kernel: they were written the same way from the parent commit of the change that
+folded the four block-start-states texts into one per layout (the commit that added the stream-major ring states kernel), with the
+requests() of this file; the 214 entries the file held before came out of that tree byte for byte as they stood."""
 import hashlib
 import json
 import os
@@ -66,6 +69,7 @@ def requests():
             out.append((f"states/{layout}/{name}", GG.SUPPORTED[name](), "states_kernel_symbol", (sm,)))
     for name in sorted(RS.GRAPHS):
         out.append((f"ring_states/tm/{name}", RS.GRAPHS[name](), "ring_states_kernel_symbol", ()))
+        out.append((f"ring_states/sm/{name}", RS.GRAPHS[name](), "ring_states_kernel_symbol", (True,)))
         for c in RS.STRIDES:
             for sm in (False, True):
                 layout = "sm" if sm else "tm"

@@ -30,7 +30,7 @@ BOUNDARY_GRAPHS = ("lds_ring_comb", "tap256", "biquad_comb17")    # the graphs r
 STRIDES = (0, 1)                                                  # checkpoint_rows the tests ask for
 
 
-# ---- the geometry rule, restated (zignal_amd/csrc/fz_grad.cpp: states_unroll, states_sm_patch_rows, ring_states_sm_geometry) ----------
+# ---- the geometry rule, restated (zignal_amd/csrc/fz_grad.cpp: states_unroll, states_sm_patch_rows, ring_sm_geometry for states_variant)
 def states_unroll(p):
     """U: 8 rows per unrolled group, halved while a group's frames pass 16 floats"""
     U = 8
@@ -77,6 +77,40 @@ def symbol_geometry(sym):
     m = SYMBOL.fullmatch(sym)
     assert m, sym
     return int(m.group(1)), int(m.group(2)), int(m.group(3))
+
+
+# ---- the states kernels' text: one per layout, the ring a switch (zignal_amd/csrc/fz_kernel_states{,_sm}.hip.inc) ------------------------
+HAND_WRITTEN = "// ==== fz_block_kernel.hip.inc ====\n"
+
+
+def hand_written(src):
+    """the hand-written part of a kernel's source: what follows the generated configuration and body"""
+    return src.split(HAND_WRITTEN)[1]
+
+
+def compiled_text(src):
+    """the hand-written part of a states kernel's source as the FZ_RING of its configuration compiles it: the other side of every
+    `#if FZ_RING` and the comments set aside (conditionals on anything else stay as they stand)"""
+    ring = int(re.search(r"^#define FZ_RING ([01]) ", src, re.M).group(1))
+    out, open_ifs = [], []                                        # per open #if: None, or for `#if FZ_RING` whether its side here compiles
+    for ln in hand_written(src).split("\n"):
+        word = ln.split()[0] if ln.strip() else ""
+        if word in ("#if", "#ifdef", "#ifndef"):
+            open_ifs.append(bool(ring) if re.fullmatch(r"#if FZ_RING\s*", ln) else None)
+            switch = open_ifs[-1] is not None                     # the line is one of the switch's own: never kept
+        elif word in ("#else", "#elif"):
+            switch = open_ifs[-1] is not None
+            assert not (switch and word == "#elif"), ln
+            if switch:
+                open_ifs[-1] = not open_ifs[-1]
+        elif word == "#endif":
+            switch = open_ifs.pop() is not None
+        else:
+            switch = False
+        if not switch and all(side is not False for side in open_ifs):
+            out.append(ln)
+    assert not open_ifs
+    return re.sub(r"//.*|/\*.*?\*/", "", "\n".join(out))
 
 
 # ---- shapes ------------------------------------------------------------------------------------------------------------------------------

@@ -37,7 +37,7 @@ def test_the_pins_cover_every_graph_kernel_layout_and_stride():
         for kind in ("adjoint", "loss", "states"):
             assert {f"{kind}/tm/{name}", f"{kind}/sm/{name}"} <= set(WANT)
     for name in RS.GRAPHS:
-        assert f"ring_states/tm/{name}" in WANT
+        assert {f"ring_states/tm/{name}", f"ring_states/sm/{name}"} <= set(WANT)
         for c in RS.STRIDES:
             assert {f"{kind}/{layout}/c{c}/{name}" for kind in ("ring", "ring_loss") for layout in ("tm", "sm")} <= set(WANT)
     for label, pin in WANT.items():

@@ -21,6 +21,7 @@ import loss_grad_ref as LR
 import recording_ref as RR
 import ring_grad_graphs as RG
 import ring_recording_graphs as R
+import ring_sm_recording as S
 from grad_harness import same
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
@@ -68,7 +69,10 @@ def test_the_ten_graphs_are_taken(name):
     ring = re.fullmatch(r"fz_adjoint_ring_kernel_c\d+b(\d+)_g([0-9a-f]{8})", p.ring_grad_kernel_symbol())
     assert (m.group(2), m.group(3)) == (ring.group(1), ring.group(2))     # the ring adjoint kernel's lanes and graph tag
     src = p.ring_states_source()
-    assert sym in src and "fz_states_ring_args" in src and "fz_adj::fwd(xa[j], c, p, st, rv, sn, u)" in src and f"#define FZ_U {m.group(1)} " in src
+    text = S.compiled_text(src)                                   # (the ring side of the one time-major states text)
+    assert sym in src and "#define FZ_RING 1 " in src and "fz_states_args" in text and f"#define FZ_U {m.group(1)} " in src
+    assert "fz_adj::fwd(xa[j], c, p, st, rv, sn, u)" in text and "fz_adj::fwd(xa[j], c, p, st, sn)" not in text
+    assert "fz_dump_state(sk, ns, st, ring, pos)" in text and "__shared__ float fz_ring[FZ_RING_SLOTS * FZ_BLOCK];" in text
     assert "__syncthreads" not in src and "atomic" not in src.split("// ==== fz_block_kernel.hip.inc ====")[1].split("#include")[1]
     for loss in (False, True):
         for ns, T in ((0, 100), (100, 0), (0, 0)):                # an empty recording is FZ_OK with nothing touched

@@ -3,7 +3,7 @@
 stay, the calls they ARE for a graph without a deep line, the rule that chooses the states kernel's workgroup and patch length together
 (restated in tests/ring_sm_recording.py) with the figures derived by hand, the kernel's resources and instructions (JIT for gfx950: no
 scratch, no VGPR spill, no FMA, no barrier, no atomic), every argument check with its reason, the kernel manifest of the GPU tests,
-the code pins' names for every other kernel, and the restatement on transposed arrays."""
+the code pins' names for every kernel, and the restatement on transposed arrays."""
 import ctypes
 import glob
 import json
@@ -79,13 +79,35 @@ def test_the_ten_graphs_are_taken(name):
     U, R_, block = S.symbol_geometry(sym)
     assert sym.split("_g")[1] == p.ring_grad_kernel_symbol().split("_g")[1]          # the ring adjoint kernel's graph tag
     src = p.ring_states_source(stream_major=True)
-    assert sym in src and "fz_states_ring_sm_args" in src and "fz_adj::fwd(x[j], c, p, st, rv, sn, u)" in src
+    text = S.compiled_text(src)                                   # (the ring side of the one stream-major states text)
+    assert sym in src and "#define FZ_RING 1 " in src and "fz_states_sm_args" in text
+    assert "fz_adj::fwd(x[j], c, p, st, rv, sn, u)" in text and "fz_adj::fwd(x[j], c, p, st, sn)" not in text and "fz_apatch" not in text
+    assert "if (active) fz_dump_state(sk, ns, st, ring, pos);" in text and "float fz_ring[FZ_RING_SLOTS * FZ_BLOCK" in text
     assert f"#define FZ_U {U} " in src and f"#define FZ_R {R_} " in src and f"#define FZ_BLOCK {block}\n" in src and "#define FZ_RING_SLOTS " in src
     assert "fz_patch_fetch<FZ_API>(patch, " in src and "\n//@splice" not in src
     assert "__syncthreads" not in src and "atomic" not in src.split("extern \"C\"")[1] and "xb[" not in src.split("extern \"C\"")[1]
     for loss in (False, True):
         for ns, T in ((0, 100), (100, 0), (0, 0)):                # an empty recording is FZ_OK with nothing touched
             assert run_fn(loss)(p._h, ctypes.byref(empty_args(loss)), ns, 100, 0, T, 0, None, None) == C.FZ_OK, C.last_error()
+
+
+@pytest.mark.parametrize("sm", (False, True))
+def test_each_layout_has_one_states_text_and_the_ring_is_a_switch(sm):
+    """the hand-written part of a plain graph's states source and of a ring graph's ring states source is the same string, every
+    `//@splice` line replaced; FZ_RING of the configuration chooses: the plain kernel compiles nothing of the rings"""
+    plain = F.compile(F.from_sexpr(GG.SUPPORTED["df1_cascade6"]())).states_source(sm)
+    ring = S.prog("biquad_comb17").ring_states_source(stream_major=sm)
+    assert plain.count(S.HAND_WRITTEN) == 1 and ring.count(S.HAND_WRITTEN) == 1
+    assert S.hand_written(plain) == S.hand_written(ring) and not re.search(r"(?m)^//@splice", S.hand_written(plain))
+    assert "#define FZ_RING 0 " in plain and "#define FZ_RING 1 " in ring
+    assert plain.split(S.HAND_WRITTEN)[0] != ring.split(S.HAND_WRITTEN)[0]
+    text = S.compiled_text(plain)
+    for word in ("fz_ring", "FZ_RING_SLOTS", "fz_dump_state(", "fz_reg_row", "pos[", "rv["):
+        assert word not in text, word
+    assert f"fz_adj::fwd({'x' if sm else 'xa'}[j], c, p, st, sn)" in text and "#define FZ_NREG FZ_NSTATE" in text
+    assert "fz_ring" in S.compiled_text(ring) and "#define FZ_NREG FZ_NSTATE" not in S.compiled_text(ring)
+    # a graph without a ring line asked through the ring calls IS the plain kernel: the same source, switch and all
+    assert F.compile(F.from_sexpr(GG.SUPPORTED["df1_cascade6"]())).ring_states_source(stream_major=sm) == plain
 
 
 def test_rings_that_fit_no_workgroup_keep_the_refusal_of_the_ring_check():
@@ -384,11 +406,11 @@ def test_argument_checks_fail_one_by_one_with_their_reason(name, loss):
         assert b.run(b.args(), B=37) == C.FZ_E_NO_DEVICE, C.last_error()
 
 
-# ---- every other kernel's name is the parent's: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py ------------
+# ---- every kernel's name is the pinned one: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py -----------------
 PINS = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
 
 
-def test_the_pinned_names_are_still_produced_and_the_new_text_is_none_of_them():
+def test_the_pinned_names_are_still_produced():
     pinned = {v[".text"] for v in PINS.values()}
     for name in NAMES:
         p = S.prog(name)
@@ -396,7 +418,7 @@ def test_the_pinned_names_are_still_produced_and_the_new_text_is_none_of_them():
         for c in (0, 1, 4):
             for kind, symbol in (("ring", p.ring_grad_kernel_symbol), ("ring_loss", p.ring_loss_grad_kernel_symbol)):
                 assert PINS[f"{kind}/tm/c{c}/{name}"]["symbol"] == symbol(c) and PINS[f"{kind}/sm/c{c}/{name}"]["symbol"] == symbol(c, stream_major=True)
-        assert p.ring_states_kernel_symbol(stream_major=True) not in {v["symbol"] for v in PINS.values()}
+        assert PINS[f"ring_states/sm/{name}"]["symbol"] == p.ring_states_kernel_symbol(stream_major=True)
     for name in sorted(GG.SUPPORTED):
         p = F.compile(F.from_sexpr(GG.SUPPORTED[name]()))
         for key, sm in (("tm", False), ("sm", True)):

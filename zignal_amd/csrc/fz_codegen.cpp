@@ -25,20 +25,19 @@ extern const char* const kSkeletonBody_sm_long;
 extern const char* const kSkeletonBody_sm_short;
 extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
-extern const char* const kSkeletonAdjoint;       // fz_kernel_adjoint.hip.inc: a kernel text of its own, like the seven below
+extern const char* const kSkeletonAdjoint;       // fz_kernel_adjoint.hip.inc: a kernel text of its own, like the five below
 extern const char* const kSkeletonAdjointSm;
 extern const char* const kSkeletonAdjointRing;
 extern const char* const kSkeletonAdjointRingSm;
-extern const char* const kSkeletonStates;
-extern const char* const kSkeletonStatesSm;
-extern const char* const kSkeletonStatesRing;
-extern const char* const kSkeletonStatesRingSm;
+extern const char* const kSkeletonStates;        // fz_kernel_states.hip.inc: plain and, with FZ_RING, ring
+extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: the same
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
 // The adjoint family (fz_grad.cpp), layout x rings plus the states kernels: one row per combination of the family bits next to
-// FZ_VF_ADJOINT, found by exact match.  The loss selects no row: it is FZ_LOSS in the configuration of the row's text and "_loss" in the
-// symbol, fz_<head>[_loss]<tail>_kernel_<c|u><U>[r<P>]b<block>.
+// FZ_VF_ADJOINT, found by exact match: a row per symbol stem.  The loss selects no row: it is FZ_LOSS in the configuration of the row's
+// text and "_loss" in the symbol, fz_<head>[_loss]<tail>_kernel_<c|u><U>[r<P>]b<block>.  The states rows' text is chosen by the layout
+// alone: the ring is FZ_RING in its configuration.
 struct AdjointRow {
    uint32_t bits;               // of FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM
    const char *head, *tail;     // of the symbol's stem
@@ -54,8 +53,8 @@ static const AdjointRow& adjoint_row(const Variant& v)
       {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_adjoint_ring", "_sm", kSkeletonAdjointRingSm, true},
       {FZ_VF_STATES, "fz_states", "", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_SM, "fz_states", "_sm", kSkeletonStatesSm, true},
-      {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStatesRing, false},
-      {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_states", "_ring_sm", kSkeletonStatesRingSm, true},
+      {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStates, false},
+      {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_states", "_ring_sm", kSkeletonStatesSm, true},
    };
    for (const AdjointRow& r : rows)
       if (r.bits == (v.flags & (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM)) && !((v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_LOSS))) return r;
@@ -1099,7 +1098,10 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
       table("fz_rr_line", rl.n_rr(), [&](size_t i) { return rl.reads[i].first; }, "per ring read: its ring line");
       table("fz_rr_delay", rl.n_rr(), [&](size_t i) { return rl.reads[i].second; }, "per ring read: its delay in samples");
    }
-   if (v.flags & FZ_VF_STATES) o << "#define FZ_U " << v.U << "   // rows per unrolled group of the forward recursion\n";
+   if (v.flags & FZ_VF_STATES) {
+      o << "#define FZ_RING " << ((v.flags & FZ_VF_ADJOINT_RING) ? 1 : 0) << "   // 1: the delay lines deeper than " << kRegMaxDepth << " samples keep value rings in LDS\n";
+      o << "#define FZ_U " << v.U << "   // rows per unrolled group of the forward recursion\n";
+   }
    else o << "#define FZ_C " << v.U << "   // checkpoint rows: the chunk sweep 2 re-runs and walks backwards\n";
    if (!(v.flags & FZ_VF_STATES)) o << "#define FZ_LOSS " << ((v.flags & FZ_VF_ADJOINT_LOSS) ? 1 : 0) << "   // 1: dL/dy is formed in the kernel, from a target (the squared-error loss)\n";
    if (v.flags & FZ_VF_ADJOINT_SM) o << "#define FZ_R " << v.P << "   // rows per LDS patch of the stream-major frames\n";

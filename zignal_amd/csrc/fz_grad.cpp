@@ -8,8 +8,8 @@
 //     (delay lines in LDS: FZ_VF_ADJOINT_RING)
 //   fz_run_recording_grad: the block-start states     fz_kernel_states.hip.inc          fz_kernel_states_sm.hip.inc
 //     (FZ_VF_STATES)
-//   fz_run_recording_ring_grad[_stream_major]:        fz_kernel_states_ring.hip.inc     fz_kernel_states_ring_sm.hip.inc
-//     the same
+//   fz_run_recording_ring_grad[_stream_major]:        the same text with FZ_RING        the same text with FZ_RING
+//     the same (FZ_VF_STATES | FZ_VF_ADJOINT_RING)
 //
 // Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the four adjoint kernels forms dL/dy itself, from a
 // target: the same text with FZ_LOSS, the same C, workgroup and workspace.  The ring calls share the checks and the launch with the
@@ -99,25 +99,30 @@ static uint32_t states_sm_patch_rows(const Graph& g)
    return R;
 }
 
-// ---- the ring backward (fz_run_block_ring_grad): its scope, checkpoint stride, workgroup and workspace, each at home here ---------------
-static bool has_ring_line(const Graph& g)
-{
-   for (const Line& L : g.lines)
-      if (L.in_lds) return true;
-   return false;
-}
+// ---- the ring kernels' LDS: value rings (or pending adjoints) alone on time-major frames, rings and patches on stream-major buffers -----
+// The LDS floats of one lane: `slots` of rings (the sum of the ring lines' depths) and, on stream-major buffers, its row of a wave's
+// patch: R rows of `wires` floats and `pad` of padding.  A workgroup of `block` lanes holds ring[slots][block] and block / 64 patches
+// of [64][R wires + pad] floats: 4 block (slots + R wires + pad) bytes.
+struct LaneLds {
+   uint32_t slots = 0, wires = 0, pad = 0;
+   uint64_t bytes(uint32_t block, uint32_t R) const { return 4ull * block * ((uint64_t)slots + (uint64_t)R * wires + pad); }
+};
 
-static uint64_t ring_lds_bytes(const RingLayout& rl, uint32_t block) { return (uint64_t)rl.slots * block * 4u; }
+struct RingSmGeometry {
+   uint32_t block = 0, R = 0;   // block == 0: nothing fits
+};
 
-// lanes per workgroup: the largest of 256 / 128 / 64 whose rings leave room for two workgroups in a CU's LDS; failing that the largest
-// that fits one workgroup; 0: not even 64 lanes fit
-static uint32_t ring_block(const RingLayout& rl)
+// The one home of the rule that chooses the workgroup and the patch length together.  R runs over R0, R0 / 2, ... down to Rmin (powers
+// of two); per R the block over 256, 128, 64.  The first pair that fits the LDS twice (two workgroups per CU) wins; failing that the
+// first that fits once.  The rule prefers a long run per stream (a whole cache line) over lanes per workgroup: static, not measured
+// against the alternative.  Time-major frames have no patch: R0 = Rmin = 1, and the rule is the largest block whose rings fit.
+static RingSmGeometry ring_sm_geometry(const LaneLds& lane, uint32_t R0, uint32_t Rmin)
 {
-   for (uint32_t b : {256u, 128u, 64u})
-      if (2 * ring_lds_bytes(rl, b) <= kLdsBytes) return b;
-   for (uint32_t b : {256u, 128u, 64u})
-      if (ring_lds_bytes(rl, b) <= kLdsBytes) return b;
-   return 0;
+   for (uint64_t times : {2u, 1u})
+      for (uint32_t R = R0; R >= Rmin; R /= 2)
+         for (uint32_t b : {256u, 128u, 64u})
+            if (times * lane.bytes(b, R) <= kLdsBytes) return RingSmGeometry{b, R};
+   return RingSmGeometry{};
 }
 
 static uint32_t checkpoint_of(const Graph& g, uint32_t checkpoint_rows, bool ring = false)
@@ -134,6 +139,18 @@ static void require_supported(const Graph& g, bool rings_in_lds = false)
    if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
 }
 
+// The scope of a call, before anything else is asked of it.  ring: the call is of the ring family -- the ring scope and the ring-fit
+// refusal in fz_program_ring_grad_check's words, whichever kernel and layout the call goes on to ask for.
+static void require_scope(const Graph& g, bool ring)
+{
+   require_supported(g, ring);
+   if (!ring) return;
+   const LaneLds rings{ring_layout(g).slots};
+   if (!ring_sm_geometry(rings, 1, 1).block)
+      fail(FZ_E_UNSUPPORTED, "the adjoint rings of the delay lines deeper than 8 samples, " + std::to_string(rings.bytes(64, 1)) + " bytes per 64 lanes (" +
+                                std::to_string(rings.slots) + " samples), do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup");
+}
+
 // the flag set of an adjoint Variant: the one place that refuses a loss on a graph without outputs
 static uint32_t adjoint_flags(const Graph& g, uint32_t family_bits, bool loss)
 {
@@ -141,186 +158,86 @@ static uint32_t adjoint_flags(const Graph& g, uint32_t family_bits, bool loss)
    return FZ_VF_ADJOINT | family_bits | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
 }
 
-static Variant adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool stream_major = false, bool loss = false)
-{
-   require_supported(g);
-   Variant v;
-   v.P = 1;
-   v.U = checkpoint_of(g, checkpoint_rows);
-   v.block = kGradBlock;
-   v.flags = adjoint_flags(g, stream_major ? FZ_VF_ADJOINT_SM : 0u, loss);
-   if (stream_major) v.P = grad_sm_patch_rows(g, v.U);      // (the patch rows travel in P: codegen puts them into FZ_R and the symbol)
-   if (stream_major && sm_patch_bytes(g, v.P) > kLdsBytes)
-      fail(FZ_E_UNSUPPORTED, "stream-major backward: a patch of " + std::to_string(v.U) + " checkpoint rows of " + std::to_string(g.n_in + g.n_out) +
-                                " wires does not fit the LDS of a workgroup: choose smaller checkpoint_rows");
-   return v;
-}
+static uint32_t family_bits(bool ring, bool stream_major) { return (ring ? FZ_VF_ADJOINT_RING : 0u) | (stream_major ? FZ_VF_ADJOINT_SM : 0u); }
 
-// the Variant of the ring backward: for a graph without a ring line the plain adjoint Variant itself (same kernel, symbol, workspace, bits)
-// loss: the kernel forms dL/dy itself (FZ_VF_ADJOINT_LOSS next to the ring bit); C, block and workspace do not change with it
-static Variant ring_adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool loss = false)
-{
-   require_supported(g, true);
-   if (!has_ring_line(g)) return adjoint_variant(g, checkpoint_rows, false, loss);
-   const RingLayout rl = ring_layout(g);
-   Variant v;
-   v.P = 1;
-   v.block = ring_block(rl);
-   if (!v.block)
-      fail(FZ_E_UNSUPPORTED, "the adjoint rings of the delay lines deeper than 8 samples, " + std::to_string(ring_lds_bytes(rl, 64)) + " bytes per 64 lanes (" +
-                                std::to_string(rl.slots) + " samples), do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup");
-   v.U = checkpoint_of(g, checkpoint_rows, true);
-   v.flags = adjoint_flags(g, FZ_VF_ADJOINT_RING, loss);
-   return v;
-}
-
-// ---- the ring backward on stream-major buffers: rings and patches share the LDS of a workgroup ----------------------------------------
-// A workgroup of `block` lanes holds ring[slots][block] and block / 64 patches of [64][R (n_in + n_out) + 4] floats
-// (fz_kernel_adjoint_ring_sm.hip.inc): 4 block (slots + R (n_in + n_out) + 4) bytes.
-static uint64_t ring_sm_lds_bytes(const Graph& g, const RingLayout& rl, uint32_t block, uint32_t R)
-{
-   return 4ull * block * ((uint64_t)rl.slots + (uint64_t)R * (g.n_in + g.n_out) + 4u);
-}
-
-struct RingSmGeometry {
-   uint32_t block = 0, R = 0;   // block == 0: nothing fits
-};
-
-// The one home of the rule that chooses the workgroup and the patch length together.  R runs over R0 = grad_sm_patch_rows(g, C),
-// R0 / 2, ... down to Rmin = max(4, C) (powers of two: multiples of 4 and of C); per R the block over 256, 128, 64.  The first pair
-// that fits the LDS twice (two workgroups per CU) wins; failing that the first that fits once.  The rule prefers a long run per
-// stream (a whole cache line) over lanes per workgroup: static, not measured against the alternative.
-static RingSmGeometry ring_sm_geometry(const Graph& g, const RingLayout& rl, uint32_t C)
-{
-   const uint32_t R0 = grad_sm_patch_rows(g, C), Rmin = std::max<uint32_t>(4u, C);
-   for (uint64_t times : {2u, 1u})
-      for (uint32_t R = R0; R >= Rmin; R /= 2)
-         for (uint32_t b : {256u, 128u, 64u})
-            if (times * ring_sm_lds_bytes(g, rl, b, R) <= kLdsBytes) return RingSmGeometry{b, R};
-   return RingSmGeometry{};
-}
-
-// the Variant of the ring backward on stream-major buffers: for a graph without a ring line the stream-major adjoint Variant itself
-// (same kernel, symbol, workspace, bits); with one, the ring kernel's C and {P = R, block} of ring_sm_geometry
-static Variant ring_sm_adjoint_variant(const Graph& g, uint32_t checkpoint_rows, bool loss = false)
-{
-   require_supported(g, true);
-   if (!has_ring_line(g)) return adjoint_variant(g, checkpoint_rows, true, loss);
-   const RingLayout rl = ring_layout(g);
-   if (!ring_block(rl)) (void)ring_adjoint_variant(g, checkpoint_rows, loss);   // (the refusal of fz_program_ring_grad_check, in its words)
-   Variant v;
-   v.U = checkpoint_of(g, checkpoint_rows, true);
-   v.flags = adjoint_flags(g, FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, loss);
-   const RingSmGeometry geo = ring_sm_geometry(g, rl, v.U);
-   if (!geo.block) {
-      const uint32_t Rmin = std::max<uint32_t>(4u, v.U);
-      fail(FZ_E_UNSUPPORTED, "stream-major ring backward: the rings of the delay lines deeper than 8 samples (" + std::to_string(rl.slots) + " samples) plus a patch of " +
-                                std::to_string(Rmin) + " rows of " + std::to_string(g.n_in + g.n_out) + " wires, " + std::to_string(ring_sm_lds_bytes(g, rl, 64, Rmin)) +
-                                " bytes per 64 lanes, do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup: a smaller checkpoint_rows shortens the patch");
-   }
-   v.P = geo.R;                                             // (the patch rows travel in P: codegen puts them into FZ_R and the symbol)
-   v.block = geo.block;
-   return v;
-}
-
-// the Variant of a block's backward, whichever call asks
+// The Variant of a block's backward, whichever call asks: {P = 1 (stream-major: the patch rows R -- codegen puts them into FZ_R and the
+// symbol), U = C, block}.  ring: the call is of the ring family; for a graph without a ring line its Variant is the plain one itself
+// (same kernel, symbol, workspace, bits).  With a ring line the ring kernel's C, and on stream-major buffers R and the block are chosen
+// together: R0 = grad_sm_patch_rows(g, C), Rmin = max(4, C) (multiples of 4 and of C); its patch keeps its padding whatever the wires.
+// loss: the kernel forms dL/dy itself (FZ_VF_ADJOINT_LOSS next to the family bits); C, block and workspace do not change with it.
 static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring, bool stream_major, bool loss)
 {
-   if (!ring) return adjoint_variant(g, checkpoint_rows, stream_major, loss);
-   return stream_major ? ring_sm_adjoint_variant(g, checkpoint_rows, loss) : ring_adjoint_variant(g, checkpoint_rows, loss);
-}
-
-static Variant states_variant(const Graph& g, bool stream_major)
-{
-   require_supported(g);
+   require_scope(g, ring);
+   const uint32_t slots = ring ? ring_layout(g).slots : 0u, wires = g.n_in + g.n_out;
    Variant v;
-   v.P = stream_major ? states_sm_patch_rows(g) : 1;       // (the patch rows travel in P, as for the adjoint kernel)
-   v.U = stream_major ? std::min(states_unroll(g), v.P) : states_unroll(g);
+   v.P = 1;
+   v.U = checkpoint_of(g, checkpoint_rows, slots != 0);
    v.block = kGradBlock;
-   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | (stream_major ? FZ_VF_ADJOINT_SM : 0u);
-   if (stream_major && states_sm_patch_bytes(g, v.P) > kLdsBytes)
-      fail(FZ_E_UNSUPPORTED, "stream-major recording: a patch of " + std::to_string(v.P) + " rows of " + std::to_string(g.n_in) +
-                                " input wires does not fit the LDS of a workgroup");
+   v.flags = adjoint_flags(g, family_bits(slots != 0, stream_major), loss);
+   if (slots) {
+      const LaneLds lane{slots, stream_major ? wires : 0u, stream_major ? 4u : 0u};
+      const uint32_t Rmin = stream_major ? std::max<uint32_t>(4u, v.U) : 1u;
+      const RingSmGeometry geo = ring_sm_geometry(lane, stream_major ? grad_sm_patch_rows(g, v.U) : 1u, Rmin);
+      if (!geo.block)                                       // (stream-major only: rings alone fit, require_scope has asked)
+         fail(FZ_E_UNSUPPORTED, "stream-major ring backward: the rings of the delay lines deeper than 8 samples (" + std::to_string(slots) + " samples) plus a patch of " +
+                                   std::to_string(Rmin) + " rows of " + std::to_string(wires) + " wires, " + std::to_string(lane.bytes(64, Rmin)) +
+                                   " bytes per 64 lanes, do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup: a smaller checkpoint_rows shortens the patch");
+      v.P = geo.R;
+      v.block = geo.block;
+   } else if (stream_major) {
+      v.P = grad_sm_patch_rows(g, v.U);
+      if (sm_patch_bytes(g, v.P) > kLdsBytes)
+         fail(FZ_E_UNSUPPORTED, "stream-major backward: a patch of " + std::to_string(v.U) + " checkpoint rows of " + std::to_string(wires) +
+                                   " wires does not fit the LDS of a workgroup: choose smaller checkpoint_rows");
+   }
    return v;
 }
 
-// the Variant of the block-start-states kernel of a ring recording: the scope and the workgroup of the ring backward (its value rings
-// are that kernel's LDS bytes), the unrolled group of the states kernel; for a graph without a ring line the time-major states Variant itself
-static Variant ring_states_variant(const Graph& g)
+// The Variant of a recording's block-start-states kernel, whichever call asks: {P = 1 (stream-major: the rows R of the x-only patch),
+// U = the rows of one unrolled group, block}.  ring: as for block_variant -- the scope of the ring backward; without a ring line the
+// plain states Variant itself.  With one the value rings are the ring adjoint kernel's LDS bytes, so on time-major frames its
+// workgroup; on stream-major buffers R and the block are chosen together: R0 = 2 * states_sm_patch_rows(g), Rmin = max(4, U) (multiples
+// of 4 and of U); a graph without input wires declares no patch.  R0 is twice the plain states kernel's -- one stream's run is two
+// cache lines, the 256-byte in-run of the forward stream-major long-run bodies: where the rings bound the workgroup anyway the longer
+// run costs no occupancy.  Static, not measured against R0 = states_sm_patch_rows(g).
+static Variant states_variant(const Graph& g, bool ring, bool stream_major)
 {
-   const Variant a = ring_adjoint_variant(g, 0);
-   if (!(a.flags & FZ_VF_ADJOINT_RING)) return states_variant(g, false);
+   require_scope(g, ring);
+   const uint32_t slots = ring ? ring_layout(g).slots : 0u;
    Variant v;
    v.P = 1;
    v.U = states_unroll(g);
-   v.block = a.block;
-   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | FZ_VF_ADJOINT_RING;
-   return v;
-}
-
-// ---- the same on stream-major buffers: rings and an x-only patch share the LDS of a workgroup ------------------------------------------
-// A workgroup of `block` lanes holds ring[slots][block] and block / 64 patches of [64][R n_in + 4] floats
-// (fz_kernel_states_ring_sm.hip.inc): 4 block (slots + R n_in + 4) bytes; a graph without input wires declares no patch.
-static uint64_t ring_states_sm_lds_bytes(const Graph& g, const RingLayout& rl, uint32_t block, uint32_t R)
-{
-   return 4ull * block * ((uint64_t)rl.slots + (g.n_in ? (uint64_t)R * g.n_in + 4u : 0u));
-}
-
-// The one home of the rule that chooses its workgroup and patch length together, ring_sm_geometry's shape: R runs over
-// R0 = 2 * states_sm_patch_rows(g), R0 / 2, ... down to Rmin = max(4, U) (powers of two: multiples of 4 and of U); per R the block over
-// 256, 128, 64.  The first pair that fits the LDS twice wins; failing that the first that fits once.  R0 is twice the plain states
-// kernel's -- one stream's run is two cache lines, the 256-byte in-run of the forward stream-major long-run bodies: where the rings
-// bound the workgroup anyway the longer run costs no occupancy.  Static, not measured against R0 = states_sm_patch_rows(g).
-static RingSmGeometry ring_states_sm_geometry(const Graph& g, const RingLayout& rl, uint32_t U)
-{
-   const uint32_t R0 = 2 * states_sm_patch_rows(g), Rmin = std::max<uint32_t>(4u, U);
-   for (uint64_t times : {2u, 1u})
-      for (uint32_t R = R0; R >= Rmin; R /= 2)
-         for (uint32_t b : {256u, 128u, 64u})
-            if (times * ring_states_sm_lds_bytes(g, rl, b, R) <= kLdsBytes) return RingSmGeometry{b, R};
-   return RingSmGeometry{};
-}
-
-// the Variant of the block-start-states kernel of a ring recording on stream-major buffers: the scope of the ring backward, the
-// unrolled group of the states kernel, {P = R, block} of ring_states_sm_geometry; for a graph without a ring line the stream-major
-// states Variant itself
-static Variant ring_states_sm_variant(const Graph& g)
-{
-   require_supported(g, true);
-   if (!has_ring_line(g)) return states_variant(g, true);
-   const RingLayout rl = ring_layout(g);
-   if (!ring_block(rl)) (void)ring_adjoint_variant(g, 0);  // (the refusal of fz_program_ring_grad_check, in its words)
-   Variant v;
-   v.U = states_unroll(g);
-   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM;
-   const RingSmGeometry geo = ring_states_sm_geometry(g, rl, v.U);
-   if (!geo.block) {
-      const uint32_t Rmin = std::max<uint32_t>(4u, v.U);
-      fail(FZ_E_UNSUPPORTED, "stream-major ring recording: the rings of the delay lines deeper than 8 samples (" + std::to_string(rl.slots) + " samples) plus a patch of " +
-                                std::to_string(Rmin) + " rows of " + std::to_string(g.n_in) + " input wires, " + std::to_string(ring_states_sm_lds_bytes(g, rl, 64, Rmin)) +
-                                " bytes per 64 lanes, do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup");
+   v.block = kGradBlock;
+   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | family_bits(slots != 0, stream_major);
+   if (slots) {
+      const LaneLds lane{slots, stream_major ? g.n_in : 0u, stream_major && g.n_in ? 4u : 0u};
+      const uint32_t Rmin = stream_major ? std::max<uint32_t>(4u, v.U) : 1u;
+      const RingSmGeometry geo = ring_sm_geometry(lane, stream_major ? 2 * states_sm_patch_rows(g) : 1u, Rmin);
+      if (!geo.block)                                       // (stream-major only, as above)
+         fail(FZ_E_UNSUPPORTED, "stream-major ring recording: the rings of the delay lines deeper than 8 samples (" + std::to_string(slots) + " samples) plus a patch of " +
+                                   std::to_string(Rmin) + " rows of " + std::to_string(g.n_in) + " input wires, " + std::to_string(lane.bytes(64, Rmin)) +
+                                   " bytes per 64 lanes, do not fit the " + std::to_string(kLdsBytes) + " bytes of LDS of a workgroup");
+      v.P = geo.R;
+      v.block = geo.block;
+   } else if (stream_major) {
+      v.P = states_sm_patch_rows(g);                        // (a multiple of U, or shorter than it: then it is the group)
+      v.U = std::min(v.U, v.P);
+      if (states_sm_patch_bytes(g, v.P) > kLdsBytes)
+         fail(FZ_E_UNSUPPORTED, "stream-major recording: a patch of " + std::to_string(v.P) + " rows of " + std::to_string(g.n_in) +
+                                   " input wires does not fit the LDS of a workgroup");
    }
-   v.P = geo.R;                                             // (the patch rows travel in P: codegen puts them into FZ_R and the symbol)
-   v.block = geo.block;
    return v;
-}
-
-// the Variant of a recording's states kernel, whichever call asks
-static Variant recording_states_variant(const Graph& g, bool ring, bool stream_major)
-{
-   if (!ring) return states_variant(g, stream_major);
-   return stream_major ? ring_states_sm_variant(g) : ring_states_variant(g);
 }
 
 // Could the backward have made v for this graph?  (kernel manifests are data from elsewhere: fz_manifest.cpp asks before it builds)
-// The family bits name the maker; v fits when that maker, asked for v's own stride, makes exactly v.  So nothing fits that no maker
-// makes: another bit, U = 0 (the maker answers with the default stride), a ring bit on a graph without a ring line (the ring makers
-// hand over to the plain ones), the loss next to FZ_VF_STATES.
+// The family bits name the maker and its arguments; v fits when that maker, asked for v's own stride, makes exactly v.  So nothing
+// fits that no maker makes: another bit, U = 0 (the maker answers with the default stride), a ring bit on a graph without a ring line
+// (the makers answer with the plain Variant), the loss next to FZ_VF_STATES.
 bool grad_variant_fits(const Graph& g, const Variant& v)
 {
    const bool ring = v.flags & FZ_VF_ADJOINT_RING, sm = v.flags & FZ_VF_ADJOINT_SM, loss = v.flags & FZ_VF_ADJOINT_LOSS;
    try {
-      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss) : recording_states_variant(g, ring, sm);
+      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss) : states_variant(g, ring, sm);
       return w.P == v.P && w.U == v.U && w.block == v.block && w.flags == v.flags;
    } catch (const Error&) {
       return false;                                         // (a graph, a stride or a patch the call refuses)
@@ -624,10 +541,9 @@ static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, u
 {
    const Graph& g = p->g;
    const bool stream_major = layout_is_stream_major(layout);
-   if (call.ring) (void)ring_adjoint_variant(g, 0);        // (scope first: the refusals of fz_program_ring_grad_check)
-   else require_supported(g);                              // (... of fz_program_grad_check)
+   require_scope(g, call.ring);                            // (scope first: the refusals of fz_program_grad_check, fz_program_ring_grad_check)
    // (a graph without delay lines launches no states kernel: its LDS patch is not asked to fit)
-   const Variant sv = !g.n_state ? Variant{} : recording_states_variant(g, call.ring, stream_major);
+   const Variant sv = !g.n_state ? Variant{} : states_variant(g, call.ring, stream_major);
    auto rows_per_block = [&](uint32_t C) { return call.ring ? ring_recording_block_rows(g, n_samples, C, block_rows) : recording_block_rows(n_samples, C, block_rows); };
    if (!stream_major && block_rows % 4)
       fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
@@ -638,7 +554,7 @@ static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, u
    const SmWindow* const sm = stream_major ? &whole : nullptr;
    Variant v;
    {
-      // (C is needed for the workspace the checks ask for; adjoint_variant validates checkpoint_rows and the loss's outputs)
+      // (C is needed for the workspace the checks ask for; block_variant validates checkpoint_rows and the loss's outputs)
       const Variant v0 = block_variant(g, call.checkpoint_rows, call.ring, stream_major, call.loss_rule);
       const uint32_t B0 = n_samples ? rows_per_block(v0.U) : 0;
       const RecordingCheck rec{call.ring ? ring_recording_workspace_bytes(g, n_streams, n_samples, B0, v0) : recording_workspace_bytes(g, n_streams, n_samples, B0, v0.U), state_out};
@@ -736,29 +652,49 @@ int fz_program_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t 
       return FZ_OK;)
 }
 
+// The inspection calls of one kernel of the family -- fz_program_<stem>_resources<suf>, fz_program_<stem>_kernel_symbol<suf> and
+// fz_program_<stem>_source<suf> (include/flowz_hip.h declares each) -- from one statement of its Variant.  `who` names the resources
+// call in its refusal; ARGS is what the calls take between the program and their results, every argument with its comma.
+#define FZ_ARG_C uint32_t checkpoint_rows,
+#define FZ_ARG_LAYOUT uint32_t layout,
+#define FZ_SM layout_is_stream_major(layout)
+#define FZ_INSPECTION(stem, suf, who, ARGS, VARIANT)                                                                         \
+   int fz_program_##stem##_resources##suf(fz_program* p, ARGS fz_kernel_resources* out)                                      \
+   {                                                                                                                         \
+      return grad_resources(p, out, who, [&] { return VARIANT; });                                                           \
+   }                                                                                                                         \
+   long fz_program_##stem##_kernel_symbol##suf(fz_program* p, ARGS char* buf, size_t cap)                                    \
+   {                                                                                                                         \
+      return grad_symbol(p, buf, cap, [&] { return VARIANT; });                                                              \
+   }                                                                                                                         \
+   long fz_program_##stem##_source##suf(fz_program* p, ARGS char* buf, size_t cap)                                           \
+   {                                                                                                                         \
+      return grad_source(p, buf, cap, [&] { return VARIANT; });                                                              \
+   }
+
+// (block_variant(g, C, ring, stream-major, loss) and states_variant(g, ring, stream-major) are the two makers)
+FZ_INSPECTION(grad, _for, "fz_program_grad_resources", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, false, FZ_SM, false))
+FZ_INSPECTION(loss_grad, _for, "fz_program_loss_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, false, FZ_SM, true))
+FZ_INSPECTION(ring_grad, , "fz_program_ring_grad_resources", FZ_ARG_C, block_variant(p->g, checkpoint_rows, true, false, false))
+FZ_INSPECTION(ring_grad, _for, "fz_program_ring_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, true, FZ_SM, false))
+FZ_INSPECTION(ring_loss_grad, , "fz_program_ring_loss_grad_resources", FZ_ARG_C, block_variant(p->g, checkpoint_rows, true, false, true))
+FZ_INSPECTION(ring_loss_grad, _for, "fz_program_ring_loss_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, true, FZ_SM, true))
+FZ_INSPECTION(states, , "fz_program_states_resources", FZ_ARG_LAYOUT, states_variant(p->g, false, FZ_SM))
+FZ_INSPECTION(ring_states, , "fz_program_ring_states_resources", , states_variant(p->g, true, false))
+FZ_INSPECTION(ring_states, _for, "fz_program_ring_states_resources_for", FZ_ARG_LAYOUT, states_variant(p->g, true, FZ_SM))
+#undef FZ_INSPECTION
+#undef FZ_SM
+#undef FZ_ARG_LAYOUT
+#undef FZ_ARG_C
+
 int fz_program_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
 {
    return fz_program_grad_resources_for(p, checkpoint_rows, FZ_GRAD_TIME_MAJOR, out);
 }
 
-int fz_program_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_grad_resources", [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout)); });
-}
-
 long fz_program_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
 {
    return fz_program_grad_kernel_symbol_for(p, checkpoint_rows, FZ_GRAD_TIME_MAJOR, buf, cap);
-}
-
-long fz_program_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout)); });
-}
-
-long fz_program_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout)); });
 }
 
 int fz_run_block_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
@@ -791,7 +727,7 @@ int fz_program_ring_grad_check(const fz_program* p)
 {
    FZ_GUARD(
       if (!p) fail(FZ_E_INVALID, "null program");
-      (void)ring_adjoint_variant(p->g, 0);
+      require_scope(p->g, true);
       return FZ_OK;)
 }
 
@@ -799,58 +735,13 @@ int fz_program_ring_grad_workspace(const fz_program* p, uint64_t n_streams, uint
 {
    FZ_GUARD(
       if (!p || !bytes) fail(FZ_E_INVALID, "fz_program_ring_grad_workspace: bad arguments");
-      *bytes = ring_workspace_bytes(p->g, n_streams, n_samples, ring_adjoint_variant(p->g, checkpoint_rows));
+      *bytes = ring_workspace_bytes(p->g, n_streams, n_samples, block_variant(p->g, checkpoint_rows, true, false, false));
       return FZ_OK;)
-}
-
-int fz_program_ring_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_ring_grad_resources", [&] { return ring_adjoint_variant(p->g, checkpoint_rows); });
-}
-
-long fz_program_ring_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return ring_adjoint_variant(p->g, checkpoint_rows); });
-}
-
-long fz_program_ring_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return ring_adjoint_variant(p->g, checkpoint_rows); });
 }
 
 int fz_run_block_ring_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
    FZ_GUARD(return run_grad(p, ring_call_of(p, a), n_streams, n_samples, hip_stream);)
-}
-
-int fz_program_ring_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_ring_grad_resources_for", [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), false); });
-}
-
-long fz_program_ring_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), false); });
-}
-
-long fz_program_ring_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), false); });
-}
-
-int fz_program_ring_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_ring_loss_grad_resources_for", [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), true); });
-}
-
-long fz_program_ring_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), true); });
-}
-
-long fz_program_ring_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return block_variant(p->g, checkpoint_rows, true, layout_is_stream_major(layout), true); });
 }
 
 int fz_run_block_ring_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
@@ -869,21 +760,6 @@ int fz_run_block_ring_loss_grad_stream_major(fz_program* p, const fz_loss_grad_a
       return run_grad(p, ring_call_of(p, a), n_streams, n_samples, hip_stream, &w);)
 }
 
-int fz_program_ring_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_ring_loss_grad_resources", [&] { return ring_adjoint_variant(p->g, checkpoint_rows, true); });
-}
-
-long fz_program_ring_loss_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return ring_adjoint_variant(p->g, checkpoint_rows, true); });
-}
-
-long fz_program_ring_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return ring_adjoint_variant(p->g, checkpoint_rows, true); });
-}
-
 int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
    FZ_GUARD(return run_grad(p, ring_call_of(p, a), n_streams, n_samples, hip_stream);)
@@ -893,7 +769,7 @@ int fz_program_ring_recording_block_rows(const fz_program* p, uint32_t n_rows, u
 {
    FZ_GUARD(
       if (!p || !rows) fail(FZ_E_INVALID, "fz_program_ring_recording_block_rows: bad arguments");
-      const Variant v = ring_adjoint_variant(p->g, checkpoint_rows);
+      const Variant v = block_variant(p->g, checkpoint_rows, true, false, false);
       if (n_rows >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
       *rows = n_rows ? ring_recording_block_rows(p->g, n_rows, v.U, block_rows) : 0;
       return FZ_OK;)
@@ -904,7 +780,7 @@ int fz_program_ring_recording_workspace(const fz_program* p, uint64_t n_streams,
 {
    FZ_GUARD(
       if (!p || !bytes) fail(FZ_E_INVALID, "fz_program_ring_recording_workspace: bad arguments");
-      const Variant v = ring_adjoint_variant(p->g, checkpoint_rows);
+      const Variant v = block_variant(p->g, checkpoint_rows, true, false, false);
       if (block_rows % 4) fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
       if (n_rows >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
       const uint32_t B = n_rows ? ring_recording_block_rows(p->g, n_rows, v.U, block_rows) : 0;
@@ -934,36 +810,6 @@ int fz_run_recording_ring_loss_grad_stream_major(fz_program* p, const fz_loss_gr
                                                  uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream)
 {
    FZ_GUARD(return run_recording(p, ring_call_of(p, a), FZ_GRAD_STREAM_MAJOR, n_streams, rows_total, row0, n_samples, block_rows, state_out, hip_stream);)
-}
-
-int fz_program_ring_states_resources(fz_program* p, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_ring_states_resources", [&] { return ring_states_variant(p->g); });
-}
-
-long fz_program_ring_states_kernel_symbol(fz_program* p, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return ring_states_variant(p->g); });
-}
-
-long fz_program_ring_states_source(fz_program* p, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return ring_states_variant(p->g); });
-}
-
-int fz_program_ring_states_resources_for(fz_program* p, uint32_t layout, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_ring_states_resources_for", [&] { return recording_states_variant(p->g, true, layout_is_stream_major(layout)); });
-}
-
-long fz_program_ring_states_kernel_symbol_for(fz_program* p, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return recording_states_variant(p->g, true, layout_is_stream_major(layout)); });
-}
-
-long fz_program_ring_states_source_for(fz_program* p, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return recording_states_variant(p->g, true, layout_is_stream_major(layout)); });
 }
 
 int fz_program_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
@@ -999,36 +845,6 @@ int fz_run_recording_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint32
                                uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream)
 {
    FZ_GUARD(return run_recording(p, call_of(p, a), layout, n_streams, rows_total, row0, n_samples, block_rows, state_out, hip_stream);)
-}
-
-int fz_program_states_resources(fz_program* p, uint32_t layout, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_states_resources", [&] { return states_variant(p->g, layout_is_stream_major(layout)); });
-}
-
-long fz_program_states_kernel_symbol(fz_program* p, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return states_variant(p->g, layout_is_stream_major(layout)); });
-}
-
-long fz_program_states_source(fz_program* p, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return states_variant(p->g, layout_is_stream_major(layout)); });
-}
-
-int fz_program_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out)
-{
-   return grad_resources(p, out, "fz_program_loss_grad_resources_for", [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true); });
-}
-
-long fz_program_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_symbol(p, buf, cap, [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true); });
-}
-
-long fz_program_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap)
-{
-   return grad_source(p, buf, cap, [&] { return adjoint_variant(p->g, checkpoint_rows, layout_is_stream_major(layout), true); });
 }
 
 }  // extern "C"

@@ -260,28 +260,28 @@ constexpr uint32_t FZ_VF_ADJOINT_SM = 1u << 18;
 // bits.  P, U and block mean what they mean for the plain adjoint variant.
 constexpr uint32_t FZ_VF_ADJOINT_LOSS = 1u << 17;
 // internal, with FZ_VF_ADJOINT (and optionally FZ_VF_ADJOINT_SM): the BLOCK-START-STATES kernel of a recording (fz_grad.cpp:
-// fz_run_recording_grad; fz_kernel_states.hip.inc, fz_kernel_states_sm.hip.inc: texts and symbols of their own), the forward half of
-// the adjoint body alone; one more of the reserved bits.  Such a Variant is {P = 1 (stream-major: the rows of its LDS patch), U = the
-// rows of one unrolled group, block = lanes per workgroup}; fz_grad.cpp: states_variant is the one place that makes one.
+// fz_run_recording_grad; fz_kernel_states.hip.inc, fz_kernel_states_sm.hip.inc: one text per layout, symbols of their own), the forward
+// half of the adjoint body alone; one more of the reserved bits.  Such a Variant is {P = 1 (stream-major: the rows of its LDS patch),
+// U = the rows of one unrolled group, block = lanes per workgroup}; fz_grad.cpp: states_variant is the one place that makes one.
 constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // internal, with FZ_VF_ADJOINT: the adjoint kernel of a graph with delay lines in LDS (fz_grad.cpp: fz_run_block_ring_grad;
 // fz_kernel_adjoint_ring.hip.inc: a text and a symbol of its own, the pending adjoints of the deep lines in an LDS ring); the last of
 // the reserved bits 12 .. 14 that nothing used, so a forward variant naming it stays refused as reserved.  Such a Variant is {P = 1,
-// U = checkpoint rows, block = 256 / 128 / 64 lanes per workgroup}; fz_grad.cpp: ring_adjoint_variant is the one place that makes one.
+// U = checkpoint rows, block = 256 / 128 / 64 lanes per workgroup}; fz_grad.cpp: block_variant is the one place that makes one.
 // With FZ_VF_ADJOINT_LOSS next to it: the ring kernel that forms dL/dy itself (fz_run_block_ring_loss_grad: the ring kernel's text
 // with FZ_LOSS, one more symbol), the same P, U and block.
 // With FZ_VF_ADJOINT_SM next to it (with or without FZ_VF_ADJOINT_LOSS): the ring kernels for STREAM-MAJOR buffers
 // (fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major; fz_kernel_adjoint_ring_sm.hip.inc: a text of
 // its own, a symbol each), {P = rows of the LDS patch, U = the ring kernel's checkpoint
 // rows, block = 256 / 128 / 64}: rings and patches share the workgroup's LDS, so fz_grad.cpp: ring_sm_geometry chooses P and block
-// together and ring_sm_adjoint_variant is the one place that makes one.
+// together and block_variant is the one place that makes one.
 // With FZ_VF_STATES next to it (never FZ_VF_ADJOINT_LOSS): the block-start-states kernel of a ring recording
-// (fz_run_recording_ring_grad; fz_kernel_states_ring.hip.inc: a text and a symbol of its own), {P = 1, U = the rows of one unrolled
-// group, block = the ring adjoint kernel's}; fz_grad.cpp: ring_states_variant is the one place that makes one.
+// (fz_run_recording_ring_grad; fz_kernel_states.hip.inc with FZ_RING, a symbol of its own), {P = 1, U = the rows of one unrolled
+// group, block = the ring adjoint kernel's}; fz_grad.cpp: states_variant is the one place that makes one.
 // With FZ_VF_STATES and FZ_VF_ADJOINT_SM next to it: the same for STREAM-MAJOR buffers (fz_run_recording_ring_grad_stream_major;
-// fz_kernel_states_ring_sm.hip.inc: a text and a symbol of its own), {P = rows of the x-only LDS patch, U = the rows of one unrolled
-// group, block = 256 / 128 / 64}: fz_grad.cpp: ring_states_sm_geometry chooses P and block together and ring_states_sm_variant is the
-// one place that makes one.
+// fz_kernel_states_sm.hip.inc with FZ_RING, a symbol of its own), {P = rows of the x-only LDS patch, U = the rows of one unrolled
+// group, block = 256 / 128 / 64}: fz_grad.cpp: ring_sm_geometry chooses P and block together and states_variant is the one place that
+// makes one.
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte

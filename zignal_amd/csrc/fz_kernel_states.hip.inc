@@ -1,9 +1,9 @@
-// fz_states_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the BLOCK-START STATES of a recording: the first level of the
-// two-level checkpointing of fz_run_recording_grad (include/flowz_hip.h).  It runs the T rows forward like sweep 1 of
-// fz_kernel_adjoint.hip.inc -- one lane owns one stream, the generated fz_adj::fwd (fz_codegen.cpp: gen_adjoint_body) is the step, so
-// the state bits are the forward kernels' and sweep 1's -- and stores the state before rows 0, B, 2B, ... into
-// starts[ceil(T / B)][n_state][n_streams], one coalesced row per state float, and the state after row T-1 into state_out if that is
-// given.  It writes nothing else: no output frames, no checkpoints.
+// fz_states_kernel, fz_states_ring_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the BLOCK-START STATES of a recording: the
+// first level of the two-level checkpointing of fz_run_recording_grad and fz_run_recording_ring_grad (include/flowz_hip.h).  It runs the
+// T rows forward like sweep 1 of fz_kernel_adjoint.hip.inc -- one lane owns one stream, the generated fz_adj::fwd (fz_codegen.cpp:
+// gen_adjoint_body) is the step, so the state bits are the forward kernels' and sweep 1's -- and stores the state before rows 0, B, 2B,
+// ... into starts[ceil(T / B)][n_state][n_streams], one coalesced row per state float, and the state after row T-1 into state_out if
+// that is given.  It writes nothing else: no output frames, no checkpoints, no tape.
 //
 // Time-major frames [t][stream][wire]; state, parameter and coefficient rows [row][stream].  The workgroups of the last wave are masked
 // by the stream count; no barriers.
@@ -13,22 +13,43 @@
 // FZ_U * n_in registers); occupancy hides what is left.  Rows behind the last are fetched from row T-1 and not used (no branch around
 // a load).  Whether a row starts a block is a comparison of two scalars (the row, the next block's first row).
 //
+// One text, two kernels: FZ_RING (fz_graph_config.h) is the switch.  What it changes stands under `#if FZ_RING` below, five things: the LDS
+// (its declaration, the lane's column, pos[]), the load of the state rows, what a block start stores, the step, what state_out stores.
+//   FZ_RING 0: every delay line is at most 8 samples deep.  All n_state rows are register rows in the caller's order (FZ_NREG is
+//     FZ_NSTATE, register row r the caller's row r), the step is fwd(x, c, p, st, sn), a start is one coalesced store per row.  No LDS.
+//   FZ_RING 1: the graph has delay lines deeper than 8 samples, and the step is sweep 1 of fz_kernel_adjoint_ring.hip.inc, fz_adj::fwd
+//     in ring mode.  Lines of depth <= 8 are register rows, COMPACT as in the ring adjoint kernel (register row r is the caller's state
+//     row fz_reg_row[r]).  A ring line l with source node u keeps a value ring in the lane's LDS column: slot q mod D holds u[q], filled
+//     from the caller's `state` (slot D - 1 - j holds u[-1-j], the state row row0 + j); pos[l], a scalar, is the row number modulo D.
+//     Per row: the ring reads, then fz_adj::fwd, then one ds_write_b32 per line.  A lane touches only its own column: no barriers, no
+//     atomics.  Where a row starts a block the register rows go to their caller rows and every ring line is read out of LDS in the
+//     caller's order (fz_dump_state), row0 + j = ring[(pos - 1 - j) mod D], one coalesced store per row: D LDS reads and D stores per
+//     line and block, D / B per row -- the price of a start.
+//     LDS: ring[slot][lane], FZ_RING_SLOTS x FZ_BLOCK floats -- the ring adjoint kernel's bytes, so the same workgroups per CU.
+//
 // HBM bytes per stream-sample: 4 n_in + 4 n_state / B.
 //
 // Compiled by hiprtc with the build options of every other kernel: -ffp-contract=off (no FMA: one rounding per operation), correctly
 // rounded division and square root, denormals kept.
-#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_U FZ_BLOCK FZ_KERNEL
+#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_RING FZ_U FZ_BLOCK FZ_KERNEL; with FZ_RING FZ_NREG FZ_NRL
+                               // FZ_NRR FZ_RING_SLOTS and the tables fz_reg_row, fz_rl_row0 / fz_rl_depth / fz_rl_slot0, fz_rr_line / fz_rr_delay
 
 #define FZ_P 1
 typedef float V;
 typedef double VD;
 #define FZ_A(n) ((n) > 0 ? (n) : 1)
+#if FZ_RING
+#define FZ_REG_ROW(r) fz_reg_row[r]           /* the caller's state row of register row r */
+#else
+#define FZ_NREG FZ_NSTATE
+#define FZ_REG_ROW(r) r
+#endif
 
-#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd }; fwd is all this kernel calls
+#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd }, in ring mode with FZ_RING; fwd is all this kernel calls
 
-struct fz_states_args {
+struct fz_states_args {        // (one host-side image serves both modes)
    const float* in;            // [T][n_streams][n_in]
-   const float* state;         // [n_state][n_streams]   the state before the recording
+   const float* state;         // [n_state][n_streams]   the state before the recording (register and ring lines' rows)
    const float* params;        // [n_param][n_streams]
    float* starts;              // [ceil(T / B)][n_state][n_streams]   the state before rows 0, B, 2B, ...
    float* state_out;           // [n_state][n_streams]   the state after row T-1; null: not written
@@ -38,13 +59,26 @@ struct fz_states_args {
    float c[FZ_A(FZ_NCONST)];   // the program's uniform coefficients
 };
 
+#if FZ_RING
+//@splice fz_kernel_states_dump.hip.inc
+#endif
+
 extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_args a)
 {
+#if FZ_RING
+   __shared__ float fz_ring[FZ_RING_SLOTS * FZ_BLOCK];
+#endif
    const size_t ns = a.n_streams;
    const size_t s = (size_t)blockIdx.x * FZ_BLOCK + threadIdx.x;
    if (s >= ns) return;                                  // the masked tail of the last wave (no barriers below)
+#if FZ_RING
+   float* const ring = fz_ring + threadIdx.x;            // the lane's column: slot q of line l is ring[(fz_rl_slot0[l] + q) * FZ_BLOCK]
+#endif
    const unsigned T = a.n_samples, B = a.block_rows;
-   float c[FZ_A(FZ_NCONST)], p[FZ_A(FZ_NPARAM)], st[FZ_A(FZ_NSTATE)];
+   float c[FZ_A(FZ_NCONST)], p[FZ_A(FZ_NPARAM)], st[FZ_A(FZ_NREG)];
+#if FZ_RING
+   unsigned pos[FZ_NRL];                                 // the row number modulo each ring line's depth (uniform over the wave)
+#endif
 #pragma unroll
    for (int k = 0; k < FZ_NCONST; ++k) c[k] = a.c[k];
 #pragma unroll
@@ -53,7 +87,16 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_args 
    if (FZ_NPARAM == 0) p[0] = 0.f;
    st[0] = 0.f;
 #pragma unroll
-   for (int r = 0; r < FZ_NSTATE; ++r) st[r] = a.state[(size_t)r * ns + s];
+   for (int r = 0; r < FZ_NREG; ++r) st[r] = a.state[(size_t)FZ_REG_ROW(r) * ns + s];
+#if FZ_RING
+#pragma unroll
+   for (int l = 0; l < FZ_NRL; ++l) {                    // the value rings: slot D - 1 - j holds u[-1-j], the caller's state row row0 + j
+      const unsigned D = fz_rl_depth[l];
+#pragma unroll 4
+      for (unsigned j = 0; j < D; ++j) ring[(size_t)(fz_rl_slot0[l] + D - 1u - j) * FZ_BLOCK] = a.state[(size_t)(fz_rl_row0[l] + j) * ns + s];
+      pos[l] = 0u;
+   }
+#endif
 
    float xa[FZ_U][FZ_A(FZ_NIN)], xb[FZ_U][FZ_A(FZ_NIN)];
 #pragma unroll
@@ -79,16 +122,38 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_args 
          const unsigned t = t0 + j;
          if (t < T) {
             if (t == tn) {                               // (scalars both: no lane diverges)
+#if FZ_RING
+               fz_dump_state(sk, ns, st, ring, pos);
+#else
 #pragma unroll
                for (int r = 0; r < FZ_NSTATE; ++r) sk[(size_t)r * ns] = st[r];
+#endif
                sk += (size_t)FZ_NSTATE * ns;
                tn += B;
             }
+#if FZ_RING
+            float rv[FZ_A(FZ_NRR)], sn[FZ_A(FZ_NREG)], u[FZ_NRL];
+            rv[0] = 0.f;
+            sn[0] = 0.f;
+#pragma unroll
+            for (int q = 0; q < FZ_NRR; ++q) {
+               const unsigned l = fz_rr_line[q], d = fz_rr_delay[q], D = fz_rl_depth[l];
+               const unsigned slot = pos[l] >= d ? pos[l] - d : pos[l] + D - d;
+               rv[q] = ring[(size_t)(fz_rl_slot0[l] + slot) * FZ_BLOCK];
+            }
+            fz_adj::fwd(xa[j], c, p, st, rv, sn, u);
+#pragma unroll
+            for (int l = 0; l < FZ_NRL; ++l) {
+               ring[(size_t)(fz_rl_slot0[l] + pos[l]) * FZ_BLOCK] = u[l];
+               pos[l] = pos[l] + 1u == fz_rl_depth[l] ? 0u : pos[l] + 1u;
+            }
+#else
             float sn[FZ_A(FZ_NSTATE)];
             sn[0] = 0.f;
             fz_adj::fwd(xa[j], c, p, st, sn);
+#endif
 #pragma unroll
-            for (int r = 0; r < FZ_NSTATE; ++r) st[r] = sn[r];
+            for (int r = 0; r < FZ_NREG; ++r) st[r] = sn[r];
          }
       }
 #pragma unroll
@@ -97,8 +162,12 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_args 
          for (int w = 0; w < FZ_NIN; ++w) xa[j][w] = xb[j][w];
       }
    }
+#if FZ_RING
+   if (a.state_out) fz_dump_state(a.state_out + s, ns, st, ring, pos);
+#else
    if (a.state_out) {
 #pragma unroll
       for (int r = 0; r < FZ_NSTATE; ++r) a.state_out[(size_t)r * ns + s] = st[r];
    }
+#endif
 }

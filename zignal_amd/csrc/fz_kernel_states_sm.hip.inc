@@ -1,35 +1,62 @@
-// fz_states_sm_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the BLOCK-START STATES of a recording on STREAM-MAJOR
-// buffers (include/flowz_hip.h: fz_run_recording_grad with FZ_GRAD_STREAM_MAJOR).  What it computes and stores is
-// fz_kernel_states.hip.inc's -- the T rows forward with the generated fz_adj::fwd, one lane per stream; the state before rows 0, B,
-// 2B, ... of the window into starts[ceil(T / B)][n_state][n_streams], the state after the window's last row into state_out if that is
-// given, nothing else -- so the bits are the time-major kernel's.  What differs is how x arrives, and that is sweep 1 of
-// fz_kernel_adjoint_sm.hip.inc:
+// fz_states_sm_kernel, fz_states_ring_sm_kernel -- hand-written gfx950 (MI355X, CDNA4) skeleton of the BLOCK-START STATES of a
+// recording on STREAM-MAJOR buffers (include/flowz_hip.h: fz_run_recording_grad with FZ_GRAD_STREAM_MAJOR,
+// fz_run_recording_ring_grad_stream_major).  What it computes and stores is fz_kernel_states.hip.inc's -- the T rows of the window
+// forward with the generated fz_adj::fwd (fz_codegen.cpp: gen_adjoint_body), one lane per stream; the state before rows 0, B, 2B, ...
+// of the window into starts[ceil(T / B)][n_state][n_streams] in the caller's row order, the state after the window's last row into
+// state_out if that is given, nothing else -- so the bits are the time-major kernel's.  What differs is how x arrives, and that is
+// sweep 1 of fz_kernel_adjoint_sm.hip.inc:
 //
 // in is [n_streams][rows_total][n_in], the recording the window of rows [row0, row0 + n_samples).  The 64 lanes of a wave fetch a
 // PATCH of [64 streams][FZ_R rows] as float4 pieces laid along the rows (consecutive lanes take consecutive pieces of one stream's
-// run), park them in a wave-private LDS patch, and every lane reads its own row back.  The patch carries x only: a patch row is
-// FZ_R * n_in floats + 4 of padding, 64 (FZ_R n_in + 4) 4 bytes per wave.  FZ_R is a multiple of FZ_U (the rows of one unrolled
-// group of the recursion) and of 4 (fz_grad.cpp: states_sm_patch_rows).  The fetch has no branches: a piece of a missing stream is
-// fetched from the wave's last stream, a piece behind the window's last float from the head of its run, and both are parked where
-// nobody reads them; at most FZ_AFLIGHT pieces are in flight per lane before they are parked.
+// run), park them in a wave-private LDS patch, and every lane reads its own row back in groups of FZ_U.  The patch carries x only: a
+// patch row is FZ_R * n_in floats + 4 of padding, 64 (FZ_R n_in + 4) 4 bytes per wave.  FZ_R is a multiple of FZ_U (the rows of one
+// unrolled group of the recursion) and of 4 (fz_grad.cpp: states_sm_patch_rows, ring_sm_geometry).  The fetch has no branches: a piece
+// of a missing stream is fetched from the wave's last stream, a piece behind the window's last float from the head of its run, and
+// both are parked where nobody reads them; at most FZ_AFLIGHT pieces are in flight per lane before they are parked.  There is no
+// next-group prefetch into registers (xb of the time-major text): the patch is the prefetch.
 //
 // Masking, without a workgroup barrier (fz_wave_sync orders a wave's own LDS traffic; a wave past the last stream returns as a
 // whole): the last wave's missing streams shadow the wave's last stream and store nothing; a last patch shorter than FZ_R runs
 // the rows it has (a piece that straddles the window's last float is fetched whole: rows_total * n_in is a multiple of 4 floats, the
-// piece ends inside the stream's buffer).
+// piece ends inside the stream's buffer).  A block start (a comparison of two scalars: the row, the next block's first row) may fall
+// anywhere in a patch and anywhere in an unrolled group.
 //
-// HBM bytes per stream-sample: 4 n_in + 4 n_state / B.
+// One text, two kernels: FZ_RING (fz_graph_config.h) is the switch.  What it changes stands under `#if FZ_RING` below, five things: the LDS
+// (its declaration, the lane's column, pos[]), the load of the state rows, what a block start stores, the step, what state_out stores.
+//   FZ_RING 0: every delay line is at most 8 samples deep.  All n_state rows are register rows in the caller's order (FZ_NREG is
+//     FZ_NSTATE, register row r the caller's row r), the step is fwd(x, c, p, st, sn), a start is one coalesced store per row.  The LDS
+//     is the waves' patches, fz_apatch[FZ_BLOCK / 64][64 * FZ_AROW]; a graph without input wires declares none.
+//   FZ_RING 1: the graph has delay lines deeper than 8 samples; what the ring adds is the time-major text's with FZ_RING -- fz_adj::fwd
+//     in ring mode, compact register rows (fz_reg_row), the value rings of the deep lines in the lane's LDS column, pos[], the ring
+//     reads before and one ds_write_b32 per line after the step, fz_dump_state for a start and for state_out.  Where rings and patches
+//     do not simply paste together (fz_kernel_adjoint_ring_sm.hip.inc has the same points):
+//   * LDS is ONE static array: ring[slot][lane], FZ_RING_SLOTS x FZ_BLOCK floats, then the patches [FZ_BLOCK / 64][64 * FZ_AROW]
+//     (FZ_BLOCK is whole waves: they start on a 256-byte boundary).  4 FZ_BLOCK (FZ_RING_SLOTS + FZ_R n_in + 4) bytes:
+//     fz_grad.cpp: ring_sm_geometry chooses FZ_BLOCK and FZ_R together.  A graph without input wires declares no patch: the rings alone;
+//   * idle lanes of the last wave shadow the wave's last stream (prow: its patch row, its state and params rows) but own the ring
+//     column of their threadIdx.x; they store nothing -- no starts, no state_out -- and every address they form is in bounds.  A wave
+//     past the last stream returns whole.  No workgroup barrier, no atomic: fz_wave_sync orders a wave's own patch traffic, a lane's
+//     ring column is its own.
 //
-// Compiled by hiprtc with the build options of every other kernel: -ffp-contract=off, correctly rounded division and square root,
-// denormals kept.
-#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_U FZ_R FZ_BLOCK FZ_KERNEL
+// HBM bytes per stream-sample: 4 n_in + 4 n_state / B, as the time-major text.
+//
+// Compiled by hiprtc with the build options of every other kernel: -ffp-contract=off (no FMA: one rounding per operation), correctly
+// rounded division and square root, denormals kept.
+#include "fz_graph_config.h"   // generated: FZ_NIN FZ_NOUT FZ_NCONST FZ_NPARAM FZ_NSTATE FZ_RING FZ_U FZ_R FZ_BLOCK FZ_KERNEL; with FZ_RING FZ_NREG
+                               // FZ_NRL FZ_NRR FZ_RING_SLOTS and the tables fz_reg_row, fz_rl_row0 / fz_rl_depth / fz_rl_slot0, fz_rr_line / fz_rr_delay
 
 #define FZ_P 1
 typedef float V;
 typedef double VD;
 #define FZ_A(n) ((n) > 0 ? (n) : 1)
+#if FZ_RING
+#define FZ_REG_ROW(r) fz_reg_row[r]           /* the caller's state row of register row r */
+#else
+#define FZ_NREG FZ_NSTATE
+#define FZ_REG_ROW(r) r
+#endif
 
-#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd }; fwd is all this kernel calls
+#include "fz_graph_body.h"     // generated: struct fz_adj { fwd, bwd }, in ring mode with FZ_RING; fwd is all this kernel calls
 
 #if (FZ_R % 4) != 0 || (FZ_R % FZ_U) != 0 || (FZ_BLOCK % 64) != 0
 #error "stream-major states: the patch is a multiple of the unrolled group and of 4 rows, the workgroup whole waves"
@@ -40,9 +67,9 @@ typedef double VD;
 
 //@splice fz_kernel_adjoint_patch.hip.inc   (the fetch is all this kernel uses of it)
 
-struct fz_states_sm_args {
+struct fz_states_sm_args {     // (one host-side image serves both modes)
    const float* in;            // [n_streams][rows_total][n_in]
-   const float* state;         // [n_state][n_streams]   the state before the recording
+   const float* state;         // [n_state][n_streams]   the state before the recording (register and ring lines' rows)
    const float* params;        // [n_param][n_streams]
    float* starts;              // [ceil(T / B)][n_state][n_streams]   the state before rows 0, B, 2B, ... of the window
    float* state_out;           // [n_state][n_streams]   the state after the window's last row; null: not written
@@ -54,10 +81,23 @@ struct fz_states_sm_args {
    float c[FZ_A(FZ_NCONST)];   // the program's uniform coefficients
 };
 
+#if FZ_RING
+//@splice fz_kernel_states_dump.hip.inc
+#endif
+
 extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_sm_args a)
 {
+#if FZ_RING
+   // ring[slot][lane], then the waves' patches (FZ_RING_SLOTS * FZ_BLOCK floats are whole multiples of 256 bytes)
+#if FZ_NIN > 0
+   __shared__ __attribute__((aligned(16))) float fz_ring[FZ_RING_SLOTS * FZ_BLOCK + (FZ_BLOCK / 64) * 64 * FZ_AROW];
+#else
+   __shared__ float fz_ring[FZ_RING_SLOTS * FZ_BLOCK];
+#endif
+#else
 #if FZ_NIN > 0
    __shared__ __attribute__((aligned(16))) float fz_apatch[FZ_BLOCK / 64][64 * FZ_AROW];
+#endif
 #endif
    const size_t ns = a.n_streams;
    const unsigned lane = threadIdx.x & 63u;
@@ -68,16 +108,26 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_sm_ar
    const bool active = lane < rows_here;
    const unsigned prow = active ? lane : rows_here - 1u;      // idle lanes shadow the wave's last stream, store nothing
    const size_t s = s_base + prow;
+#if FZ_RING
+   float* const ring = fz_ring + threadIdx.x;                 // the lane's OWN column (an idle lane's too): slot q of line l is ring[(fz_rl_slot0[l] + q) * FZ_BLOCK]
+#endif
    const unsigned T = a.n_samples, B = a.block_rows;
    const unsigned npatch = (T + (unsigned)FZ_R - 1u) / (unsigned)FZ_R;
 #if FZ_NIN > 0
+#if FZ_RING
+   float* const patch = fz_ring + FZ_RING_SLOTS * FZ_BLOCK + wave * (64u * FZ_AROW);
+#else
    float* const patch = fz_apatch[wave];
+#endif
    const float* const mine = patch + prow * FZ_AROW;
    const size_t istride = (size_t)a.rows_total * FZ_NIN;
    const float* const gin = a.in + s_base * istride + (size_t)a.row0 * FZ_NIN;   // the wave's first run: stream s_base, row row0
 #endif
 
-   float c[FZ_A(FZ_NCONST)], p[FZ_A(FZ_NPARAM)], st[FZ_A(FZ_NSTATE)];
+   float c[FZ_A(FZ_NCONST)], p[FZ_A(FZ_NPARAM)], st[FZ_A(FZ_NREG)];
+#if FZ_RING
+   unsigned pos[FZ_NRL];                                      // the row number modulo each ring line's depth (uniform over the wave)
+#endif
 #pragma unroll
    for (int k = 0; k < FZ_NCONST; ++k) c[k] = a.c[k];
 #pragma unroll
@@ -86,7 +136,16 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_sm_ar
    if (FZ_NPARAM == 0) p[0] = 0.f;
    st[0] = 0.f;
 #pragma unroll
-   for (int r = 0; r < FZ_NSTATE; ++r) st[r] = a.state[(size_t)r * ns + s];
+   for (int r = 0; r < FZ_NREG; ++r) st[r] = a.state[(size_t)FZ_REG_ROW(r) * ns + s];
+#if FZ_RING
+#pragma unroll
+   for (int l = 0; l < FZ_NRL; ++l) {                         // the value rings: slot D - 1 - j holds u[-1-j], the caller's state row row0 + j
+      const unsigned D = fz_rl_depth[l];
+#pragma unroll 4
+      for (unsigned j = 0; j < D; ++j) ring[(size_t)(fz_rl_slot0[l] + D - 1u - j) * FZ_BLOCK] = a.state[(size_t)(fz_rl_row0[l] + j) * ns + s];
+      pos[l] = 0u;
+   }
+#endif
 
    unsigned tn = 0;                                           // the first row of the next block
    float* sk = a.starts + s;                                  // its rows of `starts`
@@ -112,24 +171,50 @@ extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_sm_ar
             const unsigned t = r0 + j0 + j;
             if (j0 + j < np) {
                if (t == tn) {                                 // (scalars both: no lane diverges)
+#if FZ_RING
+                  if (active) fz_dump_state(sk, ns, st, ring, pos);
+#else
                   if (active) {
 #pragma unroll
                      for (int r = 0; r < FZ_NSTATE; ++r) sk[(size_t)r * ns] = st[r];
                   }
+#endif
                   sk += (size_t)FZ_NSTATE * ns;
                   tn += B;
                }
+#if FZ_RING
+               float rv[FZ_A(FZ_NRR)], sn[FZ_A(FZ_NREG)], u[FZ_NRL];
+               rv[0] = 0.f;
+               sn[0] = 0.f;
+#pragma unroll
+               for (int q = 0; q < FZ_NRR; ++q) {
+                  const unsigned l = fz_rr_line[q], d = fz_rr_delay[q], D = fz_rl_depth[l];
+                  const unsigned slot = pos[l] >= d ? pos[l] - d : pos[l] + D - d;
+                  rv[q] = ring[(size_t)(fz_rl_slot0[l] + slot) * FZ_BLOCK];
+               }
+               fz_adj::fwd(x[j], c, p, st, rv, sn, u);
+#pragma unroll
+               for (int l = 0; l < FZ_NRL; ++l) {
+                  ring[(size_t)(fz_rl_slot0[l] + pos[l]) * FZ_BLOCK] = u[l];
+                  pos[l] = pos[l] + 1u == fz_rl_depth[l] ? 0u : pos[l] + 1u;
+               }
+#else
                float sn[FZ_A(FZ_NSTATE)];
                sn[0] = 0.f;
                fz_adj::fwd(x[j], c, p, st, sn);
+#endif
 #pragma unroll
-               for (int r = 0; r < FZ_NSTATE; ++r) st[r] = sn[r];
+               for (int r = 0; r < FZ_NREG; ++r) st[r] = sn[r];
             }
          }
       }
    }
+#if FZ_RING
+   if (a.state_out && active) fz_dump_state(a.state_out + s, ns, st, ring, pos);
+#else
    if (a.state_out && active) {
 #pragma unroll
       for (int r = 0; r < FZ_NSTATE; ++r) a.state_out[(size_t)r * ns + s] = st[r];
    }
+#endif
 }
