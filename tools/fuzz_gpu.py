@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Dev tool (GPU box): a long randomized parity run -- random (typed) graphs, kernels vs the oracle.
+"""Dev tool (GPU box): a long randomized parity run -- random (typed) graphs, kernels vs the oracle, on the kernel bodies of
+tests/fuzz_bodies.py (BODIES: the seed picks among them; the pinned matrix of the same bodies is tests/test_fuzz_bodies_gpu.py).
+FUZZ_TRACE=1 prints every launch with its kernel name.
 usage: tools/fuzz_gpu.py <first_seed> <count> [time limit in seconds: stops early, still prints the summary]"""
 import time
 import os
@@ -11,6 +13,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import fuzz_bodies as FB  # noqa: E402
 import randgraphs as R  # noqa: E402
 from oracle import flowz_oracle as O  # noqa: E402
 from zignal_amd import flowz as F  # noqa: E402
@@ -37,6 +40,30 @@ limit = float(sys.argv[3]) if len(sys.argv) > 3 else 1e9
 t_start, last = time.time(), first - 1
 ns, T = int(os.environ.get("FUZZ_NS", "200")), 61      # (FUZZ_NS=512: whole waves, so that the lane groups take part)
 ok = bad = skipped = refused = 0
+# the distinct variants by layout, each under one name: explicit variants of the time-major kernel (a tiled body's runs on rows here) with
+# fuzz_bodies.TOOL_EXTRA, the stream-major short and long-run ones
+ROW_BODIES = FB.tool_bodies(sm=False)
+SM_BODIES = FB.tool_bodies(sm=True)
+SM_SHORT = [b for b in SM_BODIES if b not in FB.LONG_BODIES]
+SM_LONG = [b for b in SM_BODIES if b in FB.LONG_BODIES]
+launched = {}
+
+
+def body_variant(body, sm=False):
+    return FB.variant((SM_BODIES if sm else ROW_BODIES)[body], "sm" if sm else "rows")
+
+
+def announce(body, p, v, n, T_):
+    """FUZZ_TRACE: the kernel a launch is about to run"""
+    if TRACE:
+        trace(body, p.kernel_name(v, n, T_))
+
+
+def note(body):
+    """count a launch that ran under its body's name"""
+    launched[body] = launched.get(body, 0) + 1
+
+
 for seed in range(first, first + count):
     if time.time() - t_start > limit:
         break
@@ -58,20 +85,19 @@ for seed in range(first, first + count):
         xd = torch.from_numpy(x).cuda()
         res = []
         rng = np.random.default_rng(seed)
-        for P in (1, 2, 4):
-            U = int(rng.choice([1, 3, 8, 16]))
-            LG = F.C.FZ_VF_LOCKSTEP | F.C.FZ_VF_GRID_SYNC            # round 3: lockstep workgroups, XCD-wide synchronised (ragged 200-stream grids)
-            fl = int(rng.choice([0, F.C.FZ_VF_PREFETCH3, F.C.FZ_VF_MAX_WG(2), F.C.FZ_VF_NO_STAGE_PACK, F.C.FZ_VF_LOCKSTEP, LG, LG | F.C.FZ_VF_PREFETCH3]))
-            blk = int(rng.choice([64, 128])) if (fl & F.C.FZ_VF_LOCKSTEP) else 256   # (small workgroups: several of them for 200 streams, so that barriers and counters do something)
-            trace("P", P, "U", U, "block", blk, "flags", fl)
+        for body in rng.choice(list(ROW_BODIES), 3, replace=False):
+            body = str(body)
+            v = body_variant(body)
             try:
-                y, _ = p.run_block(xd, variant=F.make_variant(P, U, blk, fl))
+                announce(body, p, v, ns, T)
+                y, _ = p.run_block(xd, variant=v)
             except F.FlowzError as e:
-                if (fl & F.C.FZ_VF_LOCKSTEP) and e.code == F.C.FZ_E_UNSUPPORTED:     # an explicit lockstep variant whose kernel has scratch is refused
+                if (v.flags & F.C.FZ_VF_LOCKSTEP) and e.code == F.C.FZ_E_UNSUPPORTED:     # an explicit lockstep variant whose kernel has scratch is refused
                     refused += 1
                     continue
                 raise
-            res.append((f"P={P} U={U} block={blk} flags={fl}", same(y.cpu().numpy(), want, np.float32)))
+            note(body)
+            res.append((body, same(y.cpu().numpy(), want, np.float32)))
         trace("f64 frames")
         y64, _ = p.run_block(xd, out_f64=True)
         res.append(("f64 frames", same(y64.cpu().numpy(), want64, np.float64)))
@@ -82,26 +108,28 @@ for seed in range(first, first + count):
         res.append((f"chained at {cut}", same(torch.cat([ya, yb]).cpu().numpy(), want, np.float32)))
         # the stream-major kernel on [stream][t][wire] buffers (first 60 samples: rows % 4 == 0)
         xs = torch.from_numpy(np.ascontiguousarray(np.transpose(x[:60], (1, 0, 2)))).cuda()
-        for P in (1, 2):
-            U = int(rng.choice([4, 8, 16, 32]))
-            trace("stream-major P", P, "U", U)
+        for body in SM_SHORT:
+            v = body_variant(body, sm=True)
             try:
-                ys, _ = p.run_block_stream_major(xs, variant=F.make_variant(P, U))
+                announce(body, p, v, ns, 60)
+                ys, _ = p.run_block_stream_major(xs, variant=v)
             except F.FlowzError as e:                     # two streams per lane with patches too large for one wave per SIMD: refused
-                if P == 2 and e.code == F.C.FZ_E_UNSUPPORTED:
+                if v.streams_per_lane == 2 and e.code == F.C.FZ_E_UNSUPPORTED:
                     continue
                 raise
-            res.append((f"stream-major P={P} U={U}", same(ys.permute(1, 0, 2).contiguous().cpu().numpy(), want[:60], np.float32)))
+            note(body)
+            res.append((body, same(ys.permute(1, 0, 2).contiguous().cpu().numpy(), want[:60], np.float32)))
         # the long-run body of the stream-major kernel (1-in/1-out graphs, >= 256 samples), automatic and 64-sample phases
         if p.n_in == 1 and p.n_out == 1 and p.n_lds_slots == 0:
             TL = 264 + 4 * int(rng.integers(0, 20))
             xl = O.synth_input(seed + 1, np.arange(ns), TL, n_wires=1)
             wl = O.compile(g, ns).run(xl)
             xsl = torch.from_numpy(np.ascontiguousarray(np.transpose(xl, (1, 0, 2)))).cuda()
-            for v in (None, F.make_variant(1, 64, 0, F.C.FZ_VF_SM_LONG), F.make_variant(2, 64, 0, F.C.FZ_VF_SM_LONG)):   # (the last: the pair body, two streams per lane)
-                label = "auto" if v is None else f"P={v.streams_per_lane} U=64"
-                trace("stream-major long", label, "T", TL)
+            for label in ["auto-sm"] + SM_LONG:                         # (the library's own choice, then one stream per lane and the pair body)
+                v = None if label == "auto-sm" else body_variant(label, sm=True)
+                announce(label, p, v if v is not None else FB.variant(None, "sm"), ns, TL)
                 ys, _ = p.run_block_stream_major(xsl, variant=v)
+                note(label)
                 res.append((f"stream-major long {label} T={TL}", same(ys.permute(1, 0, 2).contiguous().cpu().numpy(), wl, np.float32)))
         # fz_compile_typed: ResultType through inputs (random float / double wires), state and outputs
         dts = [str(rng.choice(["f32", "f64"])) for _ in range(n_in)]
@@ -138,5 +166,6 @@ for seed in range(first, first + count):
             bad += 1
             print("MISMATCH seed", seed, "typed" if typed else "plain", [n for n, r in res if not r], g, flush=True)
 print(f"fuzz seeds {first}..{last}: {ok} graphs identical, {bad} mismatching, {skipped} skipped, {refused} lockstep variants refused "
-      f"(per graph: P = 1, 2, 4 with random unroll / flags incl. lockstep and XCD-synchronised workgroups, float64 frames, a split block, the stream-major kernel short, long and pair-long, fz_compile_typed with random input types)")
+      f"(per graph: three of the distinct time-major variants of tests/fuzz_bodies.py, float64 frames, a split block, the stream-major kernel short, long and pair-long, "
+      f"fz_compile_typed with random input types; launches by body: " + ", ".join(f"{b} {n}" for b, n in sorted(launched.items())) + ")")
 sys.exit(1 if bad else 0)
