@@ -23,10 +23,11 @@ import subprocess
 import sys
 import tempfile
 
+from grad_host_harness import ADJOINT, ADJOINT_LOSS, ADJOINT_RING, ADJOINT_SM, STATES
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 PINS = os.path.join(HERE, "golden", "adjoint_code_pins.json")
 SECTIONS = (".text", ".rodata", ".note")
-ADJOINT, ADJOINT_SM, ADJOINT_LOSS, STATES, ADJOINT_RING = 1 << 27, 1 << 18, 1 << 17, 1 << 16, 1 << 14     # fz_internal.hpp
 SYMBOL = re.compile(r"fz_(adjoint|states)(_ring)?(_loss)?(_sm)?_kernel_[cu](\d+)(?:r(\d+))?b(\d+)_g[0-9a-f]{8}")
 
 

@@ -145,7 +145,7 @@ def make_inputs(p, name, ns, T, seed, ties=None, draw_params=None, special_every
 
 # ---- one launch through the C ABI ------------------------------------------------------------------------------------------------------
 # (ring, loss, window, recording) -> the entry point.  Spelled out here, not taken from zignal_amd.flowz: a test that picks the function
-# through the code under test says less.  Stream-major ring recordings are not built: no row.
+# through the code under test says less.
 ENTRY = {
     (False, False, False, False): "fz_run_block_grad",
     (False, True, False, False): "fz_run_block_loss_grad",
@@ -161,6 +161,8 @@ ENTRY = {
     (False, True, True, True): "fz_run_recording_loss_grad",
     (True, False, False, True): "fz_run_recording_ring_grad",
     (True, True, False, True): "fz_run_recording_ring_loss_grad",
+    (True, False, True, True): "fz_run_recording_ring_grad_stream_major",
+    (True, True, True, True): "fz_run_recording_ring_loss_grad_stream_major",
 }
 
 
@@ -226,7 +228,9 @@ def launch(p, d, ring=False, loss=False, window=None, recording=None, c=0, state
     fn = getattr(CA.lib, ENTRY[(bool(ring), bool(loss), window is not None, rec)])
     hs = torch.cuda.current_stream().cuda_stream
     so = outs["state_out"].mid.data_ptr() if rec and "state_out" not in leave_out else None
-    if rec and ring:
+    if rec and ring and window is not None:
+        CA.check(fn(p._h, ctypes.byref(a), ns, rows, row0, T, recording, so, hs))
+    elif rec and ring:
         CA.check(fn(p._h, ctypes.byref(a), ns, T, recording, so, hs))
     elif rec:
         CA.check(fn(p._h, ctypes.byref(a), int(window is not None), ns, rows or 0, row0, T, recording, so, hs))

@@ -20,7 +20,6 @@ import grad_fuzz_cells as GC
 F32, F64 = np.float32, np.float64
 HERE = os.path.dirname(os.path.abspath(__file__))
 MANIFEST = os.path.join(HERE, "golden", "loss_grad_fuzz_kernels.fzm.gz")
-ADJOINT, ADJOINT_SM, ADJOINT_LOSS = 1 << 27, 1 << 18, 1 << 17     # fz_internal.hpp
 K = 0.37                                                          # grad_scale of every launch: no power of two, so e * k rounds
 N_CHUNKS = 8                                                      # about six cells per test
 

@@ -33,7 +33,6 @@ F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 PINS_FILE = os.path.join(HERE, "golden", "recording_fuzz_pins.json")
 MANIFEST = os.path.join(HERE, "golden", "recording_fuzz_kernels.fzm.gz")
-ADJOINT, ADJOINT_SM, ADJOINT_LOSS, STATES = 1 << 27, 1 << 18, 1 << 17, 1 << 16      # fz_internal.hpp
 K = 0.37                                                          # grad_scale of every loss launch: no power of two, so e * k rounds
 BASE = 800                                                        # triple i of shapes(name) is drawn with seed BASE + i
 

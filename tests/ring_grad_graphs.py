@@ -1,11 +1,20 @@
 """Graphs of the ring backward tests (fz_run_block_ring_grad): delay lines deeper than 8 samples, one graph per class of thing the
-kernel does with them; the graph it refuses; and the inputs both test files draw."""
+kernel does with them; the graph it refuses; the inputs both test files draw; and the kernels the GPU tests launch
+(tests/golden/ring_grad_kernels.fzm.gz)."""
+import gzip
+import os
+import subprocess
+import sys
+import tempfile
+
 import numpy as np
 
 import graphs as G
 from graphs import DEL, IN, add, fb, fn, lit, mul, param, seq, sub, uniform
 
 F32 = np.float32
+HERE = os.path.dirname(os.path.abspath(__file__))
+MANIFEST = os.path.join(HERE, "golden", "ring_grad_kernels.fzm.gz")
 
 
 def fb9():
@@ -77,3 +86,53 @@ def inputs(p, ns, T, seed):
     ap = rng.standard_normal((p.n_param, ns)).astype(F32)
     ac = rng.standard_normal((p.n_const, ns)).astype(F32)
     return x, s0, par, yb, sb, ap, ac
+
+
+# ---- the kernels the GPU tests launch: tests/golden/ring_grad_kernels.fzm.gz -------------------------------------------------------------
+_progs = {}
+
+
+def prog(name):
+    from zignal_amd import flowz as F
+    if name not in _progs:
+        _progs[name] = F.compile(F.from_sexpr(RINGS[name]()))
+    return _progs[name]
+
+
+def kernel_requests():
+    """(program, checkpoint_rows) of every ring kernel test_ring_grad_gpu.py launches"""
+    out = [(prog(n), 0) for n in sorted(RINGS)]
+    out += [(prog(n), c) for n in ("lds_ring_comb", "biquad_comb17") for c in (1, 32)]
+    return out
+
+
+# the forward launches of test_ring_grad_gpu.py: (streams, rows) of run_block per graph (chaining: D - 2 rows; autograd: fb9)
+FORWARD_SHAPES = {n: [(65, DEEPEST[n] - 2)] for n in RINGS}
+FORWARD_SHAPES["fb9"] = FORWARD_SHAPES["fb9"] + [(130, 30)]
+
+
+def resolve():
+    """what a recording process calls (FLOWZ_HIP_MANIFEST set): every kernel of kernel_requests() and the forward kernels the chaining
+    and autograd tests launch"""
+    for p, c in kernel_requests():
+        p.ring_grad_resources(c)
+    for n, shapes in FORWARD_SHAPES.items():
+        for ns, rows in shapes:
+            prog(n).build(None, ns, rows)
+
+
+def record_manifest():
+    """record the manifest with the library as it is; needs no GPU.  build() replays every manifest under tests/golden/, so a GPU run
+    finds them built.  By hand: PYTHONPATH=. python tests/ring_grad_graphs.py"""
+    from zignal_amd import flowz as F
+    code = "import sys\nsys.path[:0] = [%r, %r]\nimport ring_grad_graphs as RG\nRG.resolve()\n" % (os.path.dirname(HERE), HERE)
+    with tempfile.TemporaryDirectory() as td:
+        raw = os.path.join(td, "manifest.fzm")
+        subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, FLOWZ_HIP_MANIFEST=raw))
+        with open(raw, "rb") as f, open(MANIFEST, "wb") as out:
+            out.write(gzip.compress(f.read(), 9, mtime=0))
+    return F.manifest_build(MANIFEST)
+
+
+if __name__ == "__main__":                         # record the kernel manifest of the library as it is
+    print("kernel manifest:", record_manifest())

@@ -14,12 +14,12 @@ import numpy as np
 import ring_grad_graphs as RG
 import ring_loss_graphs as RL
 from grad_harness import from_sm, to_sm, up4  # noqa: F401  (the transposition, under the names the users of this module know)
+from grad_host_harness import LDS_BYTES, symbol_shape
 from graphs import DEL, add
 
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 MANIFEST = os.path.join(HERE, "golden", "ring_sm_kernels.fzm.gz")
-LDS_BYTES = 163840                                                # per CU and the most one workgroup may declare (gfx950)
 
 RINGS = RG.RINGS                                                  # the eight graphs of the plain backward
 GRAPHS = RL.GRAPHS                                                # the ten of the loss: those and two with two outputs
@@ -87,9 +87,8 @@ SYMBOL = re.compile(r"fz_adjoint_ring(_loss)?_sm_kernel_c(\d+)r(\d+)b(\d+)_g")
 
 def symbol_geometry(sym):
     """(C, R, block) a stream-major ring kernel's symbol names"""
-    m = SYMBOL.match(sym)
-    assert m, sym
-    return int(m.group(2)), int(m.group(3)), int(m.group(4))
+    assert SYMBOL.match(sym), sym
+    return symbol_shape(sym, "c")
 
 
 # ---- the kernels the GPU tests launch: tests/golden/ring_sm_kernels.fzm.gz ---------------------------------------------------------------

@@ -1,9 +1,8 @@
 """Geometry, cases, launcher and kernels of the stream-major ring recording tests (fz_run_recording_ring_grad_stream_major,
 fz_run_recording_ring_loss_grad_stream_major): the graphs, triples, draws and restated answers are those of
 tests/ring_recording_graphs.py; the rule that chooses the states kernel's workgroup and patch length together, restated; the windows
-and the patch-boundary cases; ONE launch() through the C ABI with the after-checks of grad_harness.launch (whose ENTRY table has no
-row for these calls); and the kernels the GPU tests launch (tests/golden/ring_sm_recording_kernels.fzm.gz)."""
-import ctypes
+and the patch-boundary cases; launch(), grad_harness.launch on the draws of this family; and the kernels the GPU tests launch
+(tests/golden/ring_sm_recording_kernels.fzm.gz)."""
 import gzip
 import os
 import re
@@ -16,16 +15,15 @@ import numpy as np
 import grad_harness as H
 import ring_recording_graphs as R
 import ring_sm_graphs as RS
+from grad_host_harness import LDS_BYTES, symbol_shape
 
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 MANIFEST = os.path.join(HERE, "golden", "ring_sm_recording_kernels.fzm.gz")
-LDS_BYTES = RS.LDS_BYTES
 K = R.K
 GRAPHS = R.GRAPHS
 DEEPEST = R.DEEPEST
 prog = R.prog
-ENTRY = {False: "fz_run_recording_ring_grad_stream_major", True: "fz_run_recording_ring_loss_grad_stream_major"}
 BOUNDARY_GRAPHS = ("lds_ring_comb", "tap256", "biquad_comb17")    # the graphs run with block starts around a patch boundary
 STRIDES = (0, 1)                                                  # checkpoint_rows the tests ask for
 
@@ -74,9 +72,8 @@ SYMBOL = re.compile(r"fz_states_ring_sm_kernel_u(\d+)r(\d+)b(\d+)_g([0-9a-f]{8})
 
 def symbol_geometry(sym):
     """(U, R, block) the kernel's symbol names"""
-    m = SYMBOL.fullmatch(sym)
-    assert m, sym
-    return int(m.group(1)), int(m.group(2)), int(m.group(3))
+    assert SYMBOL.fullmatch(sym), sym
+    return symbol_shape(sym, "u")
 
 
 # ---- the states kernels' text: one per layout, the ring a switch (zignal_amd/csrc/fz_kernel_states{,_sm}.hip.inc) ------------------------
@@ -141,77 +138,12 @@ def forward_shape(name):
 
 # ---- one launch through the C ABI ------------------------------------------------------------------------------------------------------
 def launch(p, d, B, loss, window=None, c=0, state_grad=True, alias=False, leave_out=()):
-    """One call of fz_run_recording_ring_grad_stream_major / fz_run_recording_ring_loss_grad_stream_major on the time-major draw d of
-    ring_recording_graphs.case, in blocks of B rows (0: the library's choice): dict of the outputs asked for (numpy), "x" and "out" as
-    the window's rows, time-major ("x_buffer" / "out_buffer": the whole buffers), plus "state_out" and "starts" (the head of the
-    workspace).  window: (rows_total, row0), default windows(T)[0]; FILL lies around the window in x, dL/dy and the target.
-    param_grad, const_grad and loss start from the draw's accumulators.  c: checkpoint_rows.  alias: state0_grad is the state_grad
-    buffer.  leave_out: C names of outputs passed as null.
-    Afterwards, as grad_harness.launch: every input kept its bits (state_grad excepted when aliased); the workspace is exactly the
-    queried bytes and its surroundings and those of every output kept their sentinels; an output that is left out, has zero rows or is
-    aliased away was not written at all; the rows of in_grad / out outside the window hold what they held before the launch."""
-    import torch
-    from zignal_amd import _capi as CA
+    """grad_harness.launch of fz_run_recording_ring_grad_stream_major / fz_run_recording_ring_loss_grad_stream_major on the time-major
+    draw d of ring_recording_graphs.case (both dL/dy and the target: the call takes the one it needs), in blocks of B rows (0: the
+    library's choice), grad_scale = K.  window: (rows_total, row0), default windows(T)[0]"""
     x, s0, par, yb, tg, sb, ap, ac, al = d
-    T, ns, _ = x.shape
-    rows, row0 = windows(T)[0] if window is None else window
-    frame = lambda a: H.dev(H.to_sm(a, rows, row0, H.FILL))       # noqa: E731
-    fshape = lambda w: (ns, rows, max(w, 1))                      # noqa: E731
-    ins = {"in_": frame(x), "state": H.dev(s0), "params": H.dev(par), "target" if loss else "out_grad": frame(tg if loss else yb),
-           "state_grad": H.dev(sb) if state_grad else None}
-    before = {key: v.clone() for key, v in ins.items() if v is not None}
-    n = {"in_grad": p.n_in, "state0_grad": p.n_state, "param_grad": p.n_param, "const_grad": p.n_const, "loss": 1, "out": p.n_out,
-         "state_out": p.n_state}
-    outs = {"in_grad": H.Guarded(fshape(p.n_in)), "state0_grad": H.Guarded((max(p.n_state, 1), ns)),
-            "param_grad": H.Guarded((max(p.n_param, 1), ns), ap if p.n_param else None),
-            "const_grad": H.Guarded((max(p.n_const, 1), ns), ac if p.n_const else None)}
-    if loss:
-        outs.update(loss=H.Guarded((ns,), al), out=H.Guarded(fshape(p.n_out)))
-    outs["state_out"] = H.Guarded((max(p.n_state, 1), ns))
-    wsb = p.ring_recording_workspace_bytes(ns, T, B, c)
-    assert wsb % 4 == 0
-    ws = H.Guarded(((wsb + 3) // 4,))
-    a = CA.LossGradArgs() if loss else CA.GradArgs()
-    a.struct_size, a.checkpoint_rows = ctypes.sizeof(a), c
-    if loss:
-        a.grad_scale = K
-    for key, t in ins.items():
-        setattr(a, key, t.data_ptr() if t is not None and t.numel() else None)
-    for key, g in outs.items():
-        if key != "state_out":
-            setattr(a, key, g.mid.data_ptr() if n[key] and key not in leave_out else None)
-    if alias:
-        a.state0_grad = ins["state_grad"].data_ptr()
-    a.workspace, a.workspace_bytes = ws.mid.data_ptr(), wsb
-    so = outs["state_out"].mid.data_ptr() if "state_out" not in leave_out else None
-    CA.check(getattr(CA.lib, ENTRY[bool(loss)])(p._h, ctypes.byref(a), ns, rows, row0, T, B, so, torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
-    for key, t in before.items():
-        if not (alias and key == "state_grad"):
-            assert torch.equal(ins[key].view(torch.int32), t.view(torch.int32)), f"input {key} was written"
-    assert ws.guards_kept(), "the workspace's surroundings were written"
-    gone = {key for key in outs if key in leave_out or not n[key] or (alias and key == "state0_grad")}
-    for key, g in outs.items():
-        assert g.guards_kept(), f"the surroundings of {key} were written"
-        if key in gone:
-            assert g.untouched(), f"{key} was left out and written"
-    got = {}
-    for key, b in H.OUT.items():
-        if b not in outs or b in gone:
-            continue
-        h = outs[b].mid.cpu().numpy()
-        if b in ("in_grad", "out"):
-            assert H.outside_keeps_sentinel(h, row0, T), f"rows of {b} outside [{row0}, {row0 + T}) were written"
-            got[key + "_buffer"] = h
-            h = H.from_sm(h, T, row0)
-        got[key] = h
-    if alias and "state0_grad" not in leave_out:
-        got["state"] = ins["state_grad"].cpu().numpy()
-    if "state_out" not in leave_out:
-        got["state_out"] = outs["state_out"].mid.cpu().numpy()
-    nb = -(-T // p.ring_recording_block_rows(T, B, c))
-    got["starts"] = ws.mid[:nb * p.n_state * ns].view(nb, p.n_state, ns).cpu().numpy()
-    return got
+    return H.launch(p, (x, s0, par, tg if loss else yb, sb, ap, ac, al), ring=True, loss=loss, window=window or windows(x.shape[0])[0],
+                    recording=B, c=c, state_grad=state_grad, alias=alias, leave_out=leave_out, k=K)
 
 
 # ---- the kernels the GPU tests launch: tests/golden/ring_sm_recording_kernels.fzm.gz ---------------------------------------------------

@@ -1,6 +1,5 @@
 """Every kernel of the adjoint family compiles to the machine code it had before the loss kernels were folded into their siblings and the
 stream-major patch mover was stated once (tests/adjoint_code_pins.py; tests/golden/adjoint_code_pins.json); needs no GPU."""
-import json
 import re
 
 import pytest
@@ -8,8 +7,9 @@ import pytest
 import adjoint_code_pins as P
 import grad_graphs as GG
 import ring_sm_graphs as RS
+from grad_host_harness import code_pins
 
-WANT = json.load(open(P.PINS))
+WANT = code_pins()
 
 
 @pytest.fixture(scope="module")

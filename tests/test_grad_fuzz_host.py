@@ -3,7 +3,6 @@
 parametrised over, tests/adjoint_ref.py -- what test_grad_fuzz_gpu.py holds the kernels to -- agrees with float64 autograd and central
 differences on them, the GPU test's inputs put a signal on every adjoint, both kernels of every cell compile for gfx950 without
 scratch, and the kernel manifest next to the pins builds all of them."""
-import json
 import os
 import subprocess
 import sys
@@ -14,7 +13,7 @@ import pytest
 import adjoint_ref as A
 import grad_fuzz_cells as GC
 import grad_graphs as GG
-from test_grad_host import fd_check, inputs as smooth_inputs
+from grad_host_harness import ADJOINT, ADJOINT_SM, HERE, ROOT, code_objects, fd_check, inputs as smooth_inputs, replay, write_manifest
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
@@ -178,21 +177,17 @@ def test_the_wide_frame_graph_that_once_spilled_vgprs_does_not():
 def test_the_manifest_of_the_cells_builds_every_adjoint_kernel(tmp_path):
     """tests/golden/grad_fuzz_kernels.fzm.gz (recorded on a CPU: grad_fuzz_cells.kernel_requests, both kernels of every cell and of every
     grad_graphs.SUPPORTED graph) replayed into an empty cache: nothing fails, and resolving them all afterwards builds nothing more"""
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = ("import sys, os, json\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\n"
-            "r = F.manifest_build(%r)\n"
-            "before = sorted(os.listdir(os.environ['FLOWZ_HIP_CACHE']))\n"
-            "import grad_fuzz_cells as GC\n"
+    r = replay(GC.MANIFEST, {"FLOWZ_HIP_CACHE": str(tmp_path)})
+    objects = sorted(code_objects(tmp_path))
+    code = ("import sys\nsys.path[:0] = [%r, %r]\nfrom zignal_amd import flowz as F\nimport grad_fuzz_cells as GC\n"
             "n = 0\n"
             "for p, c, sm in GC.kernel_requests():\n"
             "    try:\n        p.grad_resources(c, stream_major=sm); n += 1\n    except F.FlowzError:\n        pass\n"
-            "print(json.dumps([r, before, sorted(os.listdir(os.environ['FLOWZ_HIP_CACHE'])), n]))\n") % (here, GC.MANIFEST)
+            "print(n)\n") % (ROOT, HERE)
     env = {k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}
-    out = subprocess.check_output([sys.executable, "-c", code], env=dict(env, FLOWZ_HIP_CACHE=str(tmp_path)), cwd=os.path.dirname(here), text=True)
-    r, before, after, n = json.loads(out.splitlines()[-1])
-    objects = [f for f in before if f.endswith(".hsaco")]
+    n = int(subprocess.check_output([sys.executable, "-c", code], env=dict(env, FLOWZ_HIP_CACHE=str(tmp_path)), cwd=ROOT, text=True).splitlines()[-1])
     assert r["failed"] == 0 and r["at_hand"] + r["built"] == r["records"] >= 2 * len(GC.CELLS), r
-    assert [f for f in after if f.endswith(".hsaco")] == objects and len(objects) <= n
+    assert sorted(code_objects(tmp_path)) == objects and len(objects) <= n
 
 
 def test_a_manifest_with_adjoint_variants_nobody_could_have_made_builds_only_the_sound_ones(tmp_path):
@@ -203,18 +198,14 @@ def test_a_manifest_with_adjoint_variants_nobody_could_have_made_builds_only_the
     text = gzip.open(GC.MANIFEST, "rb").read()
     m = None
     for m in re.finditer(rb"FZM1 (\d+) (\d+) 256 (\d+) (\d+)\n", text):
-        if int(m.group(3)) == (1 << 27) | (1 << 18) and int(m.group(1)) == 16:       # a stream-major record with R = 16: two wires at least
+        if int(m.group(3)) == ADJOINT | ADJOINT_SM and int(m.group(1)) == 16:       # a stream-major record with R = 16: two wires at least
             break
     P, U, flags, n = (int(x) for x in m.groups())
-    assert flags == (1 << 27) | (1 << 18) and P == 16
+    assert flags == ADJOINT | ADJOINT_SM and P == 16
     recipe = text[m.end():m.end() + n]
-    rec = lambda P_, U_, f_, block=256: b"FZM1 %d %d %d %d %d\n" % (P_, U_, block, f_, n) + recipe   # noqa: E731
-    bad = [rec(3, U, flags), rec(P, 64, flags), rec(128, U, flags), rec(P, U, flags | 256), rec(2, U, 1 << 27), rec(P, U, flags, 128), rec(P, 3, flags)]
-    path = tmp_path / "bad.fzm"
-    path.write_bytes(b"".join(bad) + rec(P, U, flags))
-    code = "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r, 2))" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), str(path))
-    env = {k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}
-    out = subprocess.check_output([sys.executable, "-c", code], env=dict(env, FLOWZ_HIP_CACHE=str(tmp_path / "cache")), text=True)
-    r = eval(out.splitlines()[-1])
+    rec = lambda P_, U_, f_, block=256: (P_, U_, block, f_, recipe)   # noqa: E731
+    bad = [rec(3, U, flags), rec(P, 64, flags), rec(128, U, flags), rec(P, U, flags | 256), rec(2, U, ADJOINT), rec(P, U, flags, 128), rec(P, 3, flags)]
+    write_manifest(tmp_path / "bad.fzm", bad + [rec(P, U, flags)])
+    r = replay(tmp_path / "bad.fzm", {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")}, jobs=2)
     assert r["records"] == len(bad) + 1 and r["failed"] == len(bad) and r["built"] + r["at_hand"] == 1, r
-    assert len([f for f in os.listdir(tmp_path / "cache") if f.endswith(".hsaco")]) == 1
+    assert len(code_objects(tmp_path / "cache")) == 1

@@ -89,5 +89,8 @@ def test_to_sm_and_from_sm_round_trip_at_a_row_offset():
 
 def test_launch_names_every_entry_point_itself():
     from zignal_amd import _capi as CA
-    assert set(H.ENTRY.values()) <= set(CA.EXPORTS) and len(H.ENTRY) == 14
-    assert not any(ring and window and rec for ring, _, window, rec in H.ENTRY)      # stream-major ring recordings are not built
+    assert set(H.ENTRY.values()) <= set(CA.EXPORTS) and len(H.ENTRY) == 16       # every corner: 2 x 2 x 2 x 2
+    for (ring, loss, window, rec), name in H.ENTRY.items():
+        words = name.split("_")
+        assert ("ring" in words) == ring and ("loss" in words) == loss and ("recording" in words) == rec, name
+        assert name.endswith("_stream_major") == (window and not (rec and not ring)), name      # (the plain recording call takes the layout)

@@ -2,16 +2,13 @@
 instructions (JIT for gfx950), and tests/adjoint_ref.py -- the numpy statement of the documented order the GPU tests hold the kernel
 to -- against float64 autograd and central finite differences."""
 import ctypes
-import glob
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import adjoint_ref as A
 import grad_graphs as GG
+from grad_host_harness import FakeCall, assert_no_contraction, empty_args, fd_check, inputs, kernel_ops, params_for, symbol_shape
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
@@ -50,7 +47,7 @@ def test_workspace_size_formula(name):
     for ns, T in ((1, 1), (63, 7), (1000, 1000), (65537, 33)):
         for c in (1, 2, 4, 8, 16, 32):
             assert p.grad_workspace_bytes(ns, T, c) == -(-T // c) * p.n_state * ns * 4
-        cd = int(p.grad_kernel_symbol().split("_c")[1].split("b")[0])
+        cd = symbol_shape(p.grad_kernel_symbol(), "c")[0]
         assert cd & (cd - 1) == 0 and 1 <= cd <= 16
         assert p.grad_workspace_bytes(ns, T) == p.grad_workspace_bytes(ns, T, cd)
     for bad in (3, 6, 64, 1 << 20):
@@ -67,40 +64,11 @@ def test_kernel_symbol_names_stride_block_and_graph():
 
 
 # ---- argument checks: every one fails before the device is needed ----------------------------------------------------------------
-class FakeBufs:
-    """distinct, 16-byte aligned, never dereferenced addresses for every buffer of a call"""
-
-    def __init__(self, p, ns, T):
-        self.p, self.ns, self.T = p, ns, T
-        self.ws = p.grad_workspace_bytes(ns, T)
-        base, off = 1 << 40, 0
-        sizes = {"in_": T * ns * p.n_in * 4, "state": p.n_state * ns * 4, "params": p.n_param * ns * 4, "out_grad": T * ns * p.n_out * 4,
-                 "state_grad": p.n_state * ns * 4, "in_grad": T * ns * p.n_in * 4, "state0_grad": p.n_state * ns * 4,
-                 "param_grad": p.n_param * ns * 4, "const_grad": p.n_const * ns * 4, "workspace": self.ws}
-        self.addr, self.size = {}, sizes
-        for k, n in sizes.items():
-            self.addr[k] = base + off
-            off += (max(n, 16) + 4095) // 4096 * 4096
-
-    def args(self, **over):
-        a = C.GradArgs()
-        a.struct_size = ctypes.sizeof(C.GradArgs)
-        for k, v in self.addr.items():
-            setattr(a, k, v if self.size[k] else None)
-        a.workspace_bytes = self.ws
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
-
-    def run(self, a, ns=None, T=None):
-        return C.lib.fz_run_block_grad(self.p._h, ctypes.byref(a), self.ns if ns is None else ns, self.T if T is None else T, None)
-
-
 def test_argument_checks():
     p = prog_of("df1_cascade_params6")
     assert p.n_const == 0
     q = prog_of("moog_ladder")
-    b = FakeBufs(p, 1000, 40)
+    b = FakeCall(p, 1000, 40)
     bad = [
         b.args(struct_size=ctypes.sizeof(C.GradArgs) - 8),
         b.args(struct_size=ctypes.sizeof(C.GradArgs) + 8),
@@ -135,8 +103,7 @@ def test_argument_checks():
         assert b.run(b.args(state0_grad=b.addr["state_grad"])) == C.FZ_E_NO_DEVICE, C.last_error()
         assert b.run(b.args(in_grad=None, state0_grad=None, param_grad=None, const_grad=None, state_grad=None)) == C.FZ_E_NO_DEVICE
     # an empty block is FZ_OK and touches nothing: no buffer is needed at all
-    empty = C.GradArgs()
-    empty.struct_size = ctypes.sizeof(C.GradArgs)
+    empty = empty_args()
     for ns, T in ((0, 100), (100, 0), (0, 0)):
         assert C.lib.fz_run_block_grad(p._h, ctypes.byref(empty), ns, T, None) == C.FZ_OK, C.last_error()
         assert C.lib.fz_run_block_grad(q._h, ctypes.byref(empty), ns, T, None) == C.FZ_OK, C.last_error()
@@ -154,7 +121,7 @@ def test_adjoint_kernel_jit_compiles_without_scratch(name):
     p = prog_of(name)
     r = p.grad_resources()
     assert r["scratch_bytes"] == 0 and r["vgpr_spills"] == 0, r
-    assert r["unroll"] == int(p.grad_kernel_symbol().split("_c")[1].split("b")[0])
+    assert r["unroll"] == symbol_shape(p.grad_kernel_symbol(), "c")[0]
     if name in ("df1_cascade6", "moog_ladder"):
         for c in (1, 4):
             assert p.grad_resources(c)["scratch_bytes"] == 0
@@ -162,25 +129,8 @@ def test_adjoint_kernel_jit_compiles_without_scratch(name):
 
 @pytest.mark.parametrize("name", ["df1_cascade6", "osc_chain6", "envelope_follower", "moog_ladder", "div_sqrt_exp", "rules"])
 def test_adjoint_kernel_has_no_fma(name, tmp_path, monkeypatch):
-    monkeypatch.setenv("FLOWZ_HIP_CACHE", str(tmp_path))
-    p = prog_of(name)
-    p.grad_resources()
-    objs = glob.glob(str(tmp_path / "*.hsaco"))
-    assert len(objs) == 1
-    dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", objs[0]], text=True)
-    assert p.grad_kernel_symbol() in dis
-    ops = [ln.split()[0] for ln in dis.splitlines() if ln.strip().startswith("v_")]
-    assert len(ops) > 20
-    # no contraction: the only fused multiply-adds are the refinement steps of the correctly rounded float32 division (five:
-    # v_div_scale, v_rcp, Newton steps, v_div_fmas, v_div_fixup) and square root (two after v_sqrt) -- tanh divides, so do DIV
-    # and the SQRT adjoint; graphs without them hold none at all
-    fused = [o for o in ops if o.startswith(("v_fma", "v_fmac"))]
-    divisions, roots = ops.count("v_div_fixup_f32"), ops.count("v_sqrt_f32_e32") + ops.count("v_sqrt_f32_e64")
-    assert len(fused) == 5 * divisions + 2 * roots and ops.count("v_div_fmas_f32") == divisions
-    assert not [o for o in ops if re.match(r"v_(pk_(fma|mad|mac)|mad|mac)(_mix|_mixlo|_mixhi|_legacy)?_(f16|f32|f64|bf16)", o)]
-    kinds = {k for k, *_ in p.ir()}
-    if not kinds & {"div", "tanh", "sqrt"}:
-        assert divisions == 0 and roots == 0 and not fused
+    p, _, _, every = kernel_ops(monkeypatch, tmp_path, GG.SUPPORTED[name](), "grad_resources")
+    assert_no_contraction(every, divides=bool({k for k, *_ in p.ir()} & {"div", "tanh", "sqrt"}))
 
 
 def test_forward_kernel_sources_unchanged_by_the_adjoint():
@@ -191,33 +141,6 @@ def test_forward_kernel_sources_unchanged_by_the_adjoint():
 
 
 # ---- the numpy restatement against float64 autograd and finite differences --------------------------------------------------------
-def inputs(p, ns, T, seed, scale=0.5):
-    rng = np.random.default_rng(seed)
-    x = (rng.standard_normal((T, ns, p.n_in)) * scale).astype(F32)
-    s0 = (rng.standard_normal((p.n_state, ns)) * 0.1).astype(F32)
-    par = None
-    if p.n_param:
-        par = (rng.uniform(-0.3, 0.3, (p.n_param, ns))).astype(F32)
-    yb = rng.standard_normal((T, ns, p.n_out)).astype(F32)
-    sb = rng.standard_normal((p.n_state, ns)).astype(F32)
-    return x, s0, par, yb, sb
-
-
-def params_for(name, p, ns, rng):
-    """coefficients that keep the recursions stable"""
-    if name == "moog_ladder":
-        return rng.uniform(0.05, 0.5, (1, ns)).astype(F32)
-    if name in ("df1_cascade_params6", "osc_chain6"):
-        import graphs as G
-        if name == "osc_chain6":
-            return np.asarray(G.osc_chain_params(G.SEED, np.arange(ns)), F32)
-        out = np.empty((p.n_param, ns), F32)
-        for j in range(p.n_param // 5):
-            out[5 * j:5 * j + 5] = np.asarray(G.STABLE, F32)[:, None] * rng.uniform(0.9, 1.0, (5, ns)).astype(F32)
-        return out
-    return None
-
-
 @pytest.mark.parametrize("name", sorted(GG.SUPPORTED))
 def test_reference_matches_float64_autograd(name):
     p = prog_of(name)
@@ -235,36 +158,6 @@ def test_reference_matches_float64_autograd(name):
             continue
         e = A.rel_err(g, want[k])
         assert e <= 1e-4, (k, e)
-
-
-def fd_check(p, x, s0, par, yb, sb, h=1e-6):
-    """central differences of the float64 torch forward against the numpy restatement, a few coordinates of every tensor"""
-    import torch
-
-    L = A.Layout(p)
-    ns = x.shape[1]
-    c = np.repeat(L.consts.astype(np.float64)[:, None], ns, 1)
-    base = dict(x=np.asarray(x, np.float64), state=np.asarray(s0, np.float64),
-                params=np.zeros((L.n_param, ns)) if par is None else np.asarray(par, np.float64), consts=c)
-
-    def loss(d):
-        t = {k: torch.tensor(v, dtype=torch.float64) for k, v in d.items()}
-        y, sT = A.torch_forward(L, t["x"], t["state"], t["params"], t["consts"])
-        return float((y * torch.tensor(np.asarray(yb, np.float64))).sum() + (sT * torch.tensor(np.asarray(sb, np.float64))).sum())
-    got = A.grad(p, x, yb, s0, par, sb)
-    rng = np.random.default_rng(3)
-    for k in ("x", "state", "params", "consts"):
-        if base[k].size == 0:
-            continue
-        for _ in range(6):
-            idx = tuple(rng.integers(0, n) for n in base[k].shape)
-            d1 = {kk: vv.copy() for kk, vv in base.items()}
-            d2 = {kk: vv.copy() for kk, vv in base.items()}
-            d1[k][idx] += h
-            d2[k][idx] -= h
-            fd = (loss(d1) - loss(d2)) / (2 * h)
-            g = float(got[k][idx])
-            assert abs(g - fd) <= 2e-4 * max(1.0, abs(fd)), (k, idx, g, fd)
 
 
 @pytest.mark.parametrize("name", ["df1", "div_sqrt_exp", "moog_ladder"])

@@ -2,13 +2,13 @@
 JIT for gfx950 (no scratch, no spills, a symbol of its own that names C and R), the per-layout inspection calls, the refusals, the
 argument checks, and the time-major adjoint kernel's text and symbol held to what they were before the stream-major kernel existed."""
 import ctypes
-import json
 import os
 import re
 
 import pytest
 
 import grad_graphs as GG
+from grad_host_harness import FakeCall, code_pins, empty_args, invalid
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
@@ -81,7 +81,7 @@ def test_the_two_kernels_have_texts_of_their_own():
 def test_time_major_adjoint_kernel_text_and_symbol_are_the_parents(name):
     """tests/golden/adjoint_code_pins.json holds the kernel's symbol and the hashes of its code; test_adjoint_code_pins_host.py holds the
     code the library builds now to them"""
-    pin = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))["adjoint/tm/" + name]
+    pin = code_pins()["adjoint/tm/" + name]
     assert prog_of(name).grad_kernel_symbol() == pin["symbol"] and all(len(pin[s]) == 64 for s in (".text", ".rodata", ".note"))
 
 
@@ -89,8 +89,7 @@ def test_time_major_adjoint_kernel_text_and_symbol_are_the_parents(name):
 def test_refusals_are_the_time_major_refusals(name):
     build, typed, word = GG.REFUSED[name]
     p = F.compile(F.from_sexpr(build()), typed=typed)
-    a = C.GradArgs()
-    a.struct_size = ctypes.sizeof(C.GradArgs)
+    a = empty_args()
     assert C.lib.fz_run_block_grad(p._h, ctypes.byref(a), 64, 16, None) == C.FZ_E_UNSUPPORTED
     why_tm = C.last_error()
     assert C.lib.fz_run_block_grad_stream_major(p._h, ctypes.byref(a), 64, 16, 0, 16, None) == C.FZ_E_UNSUPPORTED
@@ -104,46 +103,13 @@ def test_refusals_are_the_time_major_refusals(name):
 
 
 # ---- argument checks: every one fails before the device is needed ----------------------------------------------------------------
-class FakeBufs:
-    """distinct, 16-byte aligned, never dereferenced addresses for every buffer of a stream-major call"""
-
-    def __init__(self, p, ns, rows, T):
-        self.p, self.ns, self.rows, self.T = p, ns, rows, T
-        self.ws = p.grad_workspace_bytes(ns, T)
-        sizes = {"in_": rows * ns * p.n_in * 4, "state": p.n_state * ns * 4, "params": p.n_param * ns * 4, "out_grad": rows * ns * p.n_out * 4,
-                 "state_grad": p.n_state * ns * 4, "in_grad": rows * ns * p.n_in * 4, "state0_grad": p.n_state * ns * 4,
-                 "param_grad": p.n_param * ns * 4, "const_grad": p.n_const * ns * 4, "workspace": self.ws}
-        self.addr, self.size, off = {}, sizes, 0
-        for k, n in sizes.items():
-            self.addr[k] = (1 << 40) + off
-            off += (max(n, 16) + 4095) // 4096 * 4096
-
-    def args(self, **over):
-        a = C.GradArgs()
-        a.struct_size = ctypes.sizeof(C.GradArgs)
-        for k, v in self.addr.items():
-            setattr(a, k, v if self.size[k] else None)
-        a.workspace_bytes = self.ws
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
-
-    def run(self, a, rows=None, row0=0, T=None):
-        return C.lib.fz_run_block_grad_stream_major(self.p._h, ctypes.byref(a), self.ns, self.rows if rows is None else rows, row0,
-                                                    self.T if T is None else T, None)
-
-
-def invalid(rc, word):
-    return rc == C.FZ_E_INVALID and word in C.last_error()
-
-
 def test_argument_checks():
     p = prog_of("df1_cascade_params6")                            # 1 in, 1 out
-    b = FakeBufs(p, 1000, 48, 37)
+    b = FakeCall(p, 1000, 37, window=(48, 0))
     assert invalid(b.run(b.args(), rows=47), "rows_total")        # rows_total * n_in and * n_out off the float4 grid (one wire each)
     assert invalid(b.run(b.args(), row0=2, T=8), "row0")          # row0 * n_in and * n_out
     two_in, two_out = prog_of("rules"), prog_of("cross_wire")     # 2 in / 1 out and 1 in / 2 out: each of the four rules on its own
-    bi, bo = FakeBufs(two_in, 100, 48, 8), FakeBufs(two_out, 100, 48, 8)
+    bi, bo = FakeCall(two_in, 100, 8, window=(48, 0)), FakeCall(two_out, 100, 8, window=(48, 0))
     assert invalid(bi.run(bi.args(), rows=46), "rows_total * n_in") and invalid(bo.run(bo.args(), rows=46), "rows_total * n_in")
     assert invalid(bi.run(bi.args(), row0=2), "row0 * n_in") and invalid(bo.run(bo.args(), row0=2), "row0 * n_in")
     assert invalid(b.run(b.args(), row0=12), "beyond rows_total")  # 12 + 37 > 48
@@ -170,8 +136,7 @@ def test_argument_checks():
 
 def test_an_empty_block_is_ok_and_needs_no_buffer():
     p, q = prog_of("df1_cascade_params6"), prog_of("moog_ladder")
-    empty = C.GradArgs()
-    empty.struct_size = ctypes.sizeof(C.GradArgs)
+    empty = empty_args()
     for ns, rows, T in ((0, 100, 100), (100, 100, 0), (0, 0, 0)):
         assert C.lib.fz_run_block_grad_stream_major(p._h, ctypes.byref(empty), ns, rows, 0, T, None) == C.FZ_OK, C.last_error()
         assert C.lib.fz_run_block_grad_stream_major(q._h, ctypes.byref(empty), ns, rows, 0, T, None) == C.FZ_OK, C.last_error()

@@ -16,7 +16,7 @@ import loss_grad_fuzz as LF
 import loss_grad_ref as LR
 import trig_cells as TC
 from grad_harness import same
-from test_grad_host import inputs as smooth_inputs
+from grad_host_harness import ADJOINT, ADJOINT_LOSS, ADJOINT_SM, inputs as smooth_inputs
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
@@ -177,10 +177,10 @@ def test_the_recorded_manifest_holds_the_loss_kernels_of_the_gpu_test(tmp_path):
     raw = gzip.open(LF.MANIFEST, "rb").read()
     have = LF.records(raw)
     flags = [r[3] for r in have]
-    assert flags and all(f & LF.ADJOINT and f & LF.ADJOINT_LOSS and not f & ~(LF.ADJOINT | LF.ADJOINT_SM | LF.ADJOINT_LOSS) for f in flags)
+    assert flags and all(f & ADJOINT and f & ADJOINT_LOSS and not f & ~(ADJOINT | ADJOINT_SM | ADJOINT_LOSS) for f in flags)
     n_req = len(LF.kernel_requests())
     assert n_req == 2 * len(GC.CELLS) + 4 * len(GC.STRIDE_CELLS) + 2 * len(LF.TRIG_STRIDES) * len(TC.GRAD_GRAPHS)
-    assert sum(1 for f in flags if f & LF.ADJOINT_SM) * 2 == len(flags) <= n_req
+    assert sum(1 for f in flags if f & ADJOINT_SM) * 2 == len(flags) <= n_req
     r = F.manifest_build(LF.MANIFEST)
     assert r["failed"] == 0 and r["at_hand"] + r["built"] == r["records"] == len(have), r
     assert LF.records(LF.record(str(tmp_path / "now.fzm"))) == have

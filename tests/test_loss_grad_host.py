@@ -14,7 +14,8 @@ import pytest
 import adjoint_ref as A
 import grad_graphs as GG
 import loss_grad_ref as LR
-from test_grad_host import inputs, params_for
+from grad_host_harness import (ADJOINT, ADJOINT_LOSS, ADJOINT_SM, FakeCall, code_objects, empty_args, inputs, invalid, params_for, recipe_of, replay,
+                               symbol_shape, write_manifest)
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
@@ -22,7 +23,6 @@ F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 NEW_EXPORTS = ("fz_run_block_loss_grad", "fz_run_block_loss_grad_stream_major", "fz_program_loss_grad_resources_for",
                "fz_program_loss_grad_kernel_symbol_for", "fz_program_loss_grad_source_for")
-ADJOINT, ADJOINT_SM, ADJOINT_LOSS = 1 << 27, 1 << 18, 1 << 17     # fz_internal.hpp
 
 
 def prog_of(name):
@@ -37,22 +37,14 @@ def test_the_new_entry_points_are_declared_and_exported():
     assert "fz_loss_grad_args" in header
 
 
-def empty_args():
-    a = C.LossGradArgs()
-    a.struct_size = ctypes.sizeof(C.LossGradArgs)
-    return a
-
-
 @pytest.mark.parametrize("name", sorted(GG.REFUSED))
 def test_refusals_are_the_backwards(name):
     build, typed, word = GG.REFUSED[name]
     p = F.compile(F.from_sexpr(build()), typed=typed)
-    g = C.GradArgs()
-    g.struct_size = ctypes.sizeof(C.GradArgs)
+    g, a = empty_args(), empty_args(True)
     assert C.lib.fz_run_block_grad(p._h, ctypes.byref(g), 64, 16, None) == C.FZ_E_UNSUPPORTED
     why = C.last_error()
     assert word.lower() in why.lower()
-    a = empty_args()
     assert C.lib.fz_run_block_loss_grad(p._h, ctypes.byref(a), 64, 16, None) == C.FZ_E_UNSUPPORTED and C.last_error() == why
     assert C.lib.fz_run_block_loss_grad_stream_major(p._h, ctypes.byref(a), 64, 16, 0, 16, None) == C.FZ_E_UNSUPPORTED and C.last_error() == why
     for sm in (False, True):
@@ -63,46 +55,11 @@ def test_refusals_are_the_backwards(name):
 
 
 # ---- argument checks: every one fails before the device is needed ----------------------------------------------------------------
-class FakeBufs:
-    """distinct, 16-byte aligned, never dereferenced addresses for every buffer of a call; rows: stream-major buffers of that many rows"""
-
-    def __init__(self, p, ns, T, rows=None):
-        self.p, self.ns, self.T, self.rows = p, ns, T, rows
-        self.ws = p.grad_workspace_bytes(ns, T)
-        fr = (T if rows is None else rows) * ns * 4
-        sizes = {"in_": fr * p.n_in, "state": p.n_state * ns * 4, "params": p.n_param * ns * 4, "target": fr * p.n_out,
-                 "state_grad": p.n_state * ns * 4, "in_grad": fr * p.n_in, "state0_grad": p.n_state * ns * 4, "param_grad": p.n_param * ns * 4,
-                 "const_grad": p.n_const * ns * 4, "loss": ns * 4, "out": fr * p.n_out, "workspace": self.ws}
-        self.addr, self.size, off = {}, sizes, 0
-        for k, n in sizes.items():
-            self.addr[k] = (1 << 40) + off
-            off += (max(n, 16) + 4095) // 4096 * 4096
-
-    def args(self, **over):
-        a = empty_args()
-        for k, v in self.addr.items():
-            setattr(a, k, v if self.size[k] else None)
-        a.workspace_bytes, a.grad_scale = self.ws, 0.5
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
-
-    def run(self, a, rows=None, row0=0, T=None):
-        T = self.T if T is None else T
-        if self.rows is None:
-            return C.lib.fz_run_block_loss_grad(self.p._h, ctypes.byref(a), self.ns, T, None)
-        return C.lib.fz_run_block_loss_grad_stream_major(self.p._h, ctypes.byref(a), self.ns, self.rows if rows is None else rows, row0, T, None)
-
-
-def invalid(rc, word):
-    return rc == C.FZ_E_INVALID and word in C.last_error()
-
-
 @pytest.mark.parametrize("rows", [None, 48])
 def test_argument_checks_fail_one_by_one_with_their_reason(rows):
     p = prog_of("moog_ladder")                                    # 1 in, 1 out, state, a parameter and coefficients
     assert p.n_in == 1 and p.n_out == 1 and p.n_state and p.n_param and p.n_const
-    b = FakeBufs(p, 1000, 40, rows)
+    b = FakeCall(p, 1000, 40, loss=True, window=rows and (rows, 0))
     size = ctypes.sizeof(C.LossGradArgs)
     for bad in (size - 8, size + 8, 0, ctypes.sizeof(C.GradArgs)):
         assert invalid(b.run(b.args(struct_size=bad)), "struct_size")
@@ -123,10 +80,8 @@ def test_argument_checks_fail_one_by_one_with_their_reason(rows):
     if rows is not None:                                          # windows and alignment: fz_run_block_grad_stream_major's
         assert invalid(b.run(b.args(), rows=47), "rows_total") and invalid(b.run(b.args(), row0=2, T=8), "row0")
         assert invalid(b.run(b.args(), row0=12), "beyond rows_total")
-    big = FakeBufs(p, 1, 1, rows)
-    rc = C.lib.fz_run_block_loss_grad(p._h, ctypes.byref(big.args()), 1 << 30, 1, None) if rows is None else \
-        C.lib.fz_run_block_loss_grad_stream_major(p._h, ctypes.byref(big.args()), 1 << 30, 48, 0, 1, None)
-    assert rc == C.FZ_E_UNSUPPORTED and "2^30" in C.last_error()
+    big = FakeCall(p, 1, 1, loss=True, window=rows and (rows, 0))
+    assert big.run(big.args(), ns=1 << 30) == C.FZ_E_UNSUPPORTED and "2^30" in C.last_error()
     # what passes every check stops at the missing device (with one, fake addresses are not launched on): everything given, the exact
     # alias state0_grad == state_grad, every optional pointer NULL
     if C.lib.fz_device_count() == 0:
@@ -138,7 +93,7 @@ def test_argument_checks_fail_one_by_one_with_their_reason(rows):
 def test_an_empty_block_is_ok_and_needs_no_buffer():
     for name in ("df1_cascade_params6", "moog_ladder"):
         p = prog_of(name)
-        empty = empty_args()
+        empty = empty_args(True)
         for ns, T in ((0, 100), (100, 0), (0, 0)):
             assert C.lib.fz_run_block_loss_grad(p._h, ctypes.byref(empty), ns, T, None) == C.FZ_OK, C.last_error()
             assert C.lib.fz_run_block_loss_grad_stream_major(p._h, ctypes.byref(empty), ns, 100, 0, T, None) == C.FZ_OK, C.last_error()
@@ -185,20 +140,13 @@ def test_the_plain_adjoint_kernels_are_untouched_by_the_loss_variant(tmp_path):
 
 def test_a_manifest_with_a_sound_and_an_impossible_loss_variant_builds_one_and_refuses_one(tmp_path):
     expr = F.from_sexpr(GG.SUPPORTED["integrator"]())
-    buf = ctypes.create_string_buffer(1 << 16)
-    n = C.lib.fz_expr_recipe(expr._h, buf, 1 << 16)
-    recipe = b"typed 0\n" + buf.raw[:n]
-    rec = lambda P, U, flags: b"FZM1 %d %d 256 %d %d\n" % (P, U, flags, len(recipe)) + recipe   # noqa: E731
-    sym = F.compile(expr).loss_grad_kernel_symbol()
-    c = int(sym.split("_c")[1].split("b")[0])
+    recipe = recipe_of(GG.SUPPORTED["integrator"]())
+    c = symbol_shape(F.compile(expr).loss_grad_kernel_symbol(), "c")[0]
     path = tmp_path / "m.fzm"
-    path.write_bytes(rec(1, c, ADJOINT | ADJOINT_LOSS) + rec(1, c, ADJOINT | ADJOINT_LOSS | 256))   # (a forward flag next to it: nothing the backward makes)
-    code = "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r, 2))" % (os.path.dirname(HERE), str(path))
-    env = {k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}
-    out = subprocess.check_output([sys.executable, "-c", code], env=dict(env, FLOWZ_HIP_CACHE=str(tmp_path / "cache")), text=True)
-    r = eval(out.splitlines()[-1])
+    write_manifest(path, [(1, c, 256, ADJOINT | ADJOINT_LOSS, recipe), (1, c, 256, ADJOINT | ADJOINT_LOSS | 256, recipe)])   # (a forward flag next to it: nothing the backward makes)
+    r = replay(path, {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")}, jobs=2)
     assert r["records"] == 2 and r["built"] == 1 and r["failed"] == 1 and r["at_hand"] == 0, r
-    assert len([f for f in os.listdir(tmp_path / "cache") if f.endswith(".hsaco")]) == 1
+    assert len(code_objects(tmp_path / "cache")) == 1
     # the loss bit without the adjoint bit is no variant of anything: a caller's forward variant with it is refused as reserved
     with pytest.raises(F.FlowzError):
         F.compile(expr).build(F.make_variant(1, 8, 256, ADJOINT_LOSS))

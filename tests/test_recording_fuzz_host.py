@@ -15,7 +15,7 @@ import pytest
 import grad_fuzz_cells as GC
 import recording_fuzz as RF
 from grad_harness import same
-from test_recording_grad_host import FakeBufs
+from grad_host_harness import ADJOINT, ADJOINT_LOSS, ADJOINT_SM, STATES, FakeCall
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
@@ -175,8 +175,8 @@ def test_the_40_wire_graph_is_refused_in_stream_major_before_a_device_is_needed(
             call(True)
         assert ei.value.code == C.FZ_E_UNSUPPORTED and "LDS" in str(ei.value)
     for loss in (False, True):
-        b = FakeBufs(p, 65, 11, 4, None, loss)
-        fn = C.lib.fz_run_recording_loss_grad if loss else C.lib.fz_run_recording_grad
+        b = FakeCall(p, 65, 11, loss=loss, recording=4)
+        fn = b.fn
         a = b.args()
         assert fn(p._h, ctypes.byref(a), 1, 65, 24, 8, 11, 4, None, None) == C.FZ_E_UNSUPPORTED and "LDS" in C.last_error()
         if C.lib.fz_device_count() == 0:                          # the time-major call passes every check and stops at the device
@@ -191,7 +191,7 @@ def test_block_windows_off_the_4_row_grid_are_taken(name, loss):
     p = RF.prog(name)
     ns, T, B, row0 = RF.SM_ONLY[name]
     rows = RF.up4(row0 + T + 9) + 4
-    b = FakeBufs(p, ns, T, B, rows, loss)
+    b = FakeCall(p, ns, T, loss=loss, window=(rows, 0), recording=B)
     if C.lib.fz_device_count() == 0:
         assert b.run(b.args(), row0=row0) == C.FZ_E_NO_DEVICE, C.last_error()
         a = b.args(workspace_bytes=p.grad_workspace_bytes(ns, T))
@@ -210,13 +210,13 @@ def test_the_recorded_manifest_holds_the_kernels_of_the_gpu_test(tmp_path):
     have = RF.records(gzip.open(RF.MANIFEST, "rb").read())
     flags = [r[3] for r in have]
     with_state = [n for n in RF.NAMES if RF.prog(n).n_state]
-    states = [f for f in flags if f & RF.ADJOINT and f & RF.STATES]
+    states = [f for f in flags if f & ADJOINT and f & STATES]
     assert len(states) == sum(len(RF.layouts(n)) for n in with_state)
-    assert sum(1 for f in states if f & RF.ADJOINT_SM) == len(with_state) - len(RF.TIME_MAJOR_ONLY)
+    assert sum(1 for f in states if f & ADJOINT_SM) == len(with_state) - len(RF.TIME_MAJOR_ONLY)
     n_wide = sum(len(RF.layouts(n)) for n in RF.WIDE)
-    assert sum(1 for f in flags if f & RF.ADJOINT and f & RF.ADJOINT_LOSS) == n_wide
-    assert sum(1 for f in flags if f & RF.ADJOINT and not f & (RF.STATES | RF.ADJOINT_LOSS)) == n_wide
-    assert sum(1 for f in flags if not f & RF.ADJOINT) >= len(with_state)      # (forward kernels: one per graph, a few graphs' in two parts)
+    assert sum(1 for f in flags if f & ADJOINT and f & ADJOINT_LOSS) == n_wide
+    assert sum(1 for f in flags if f & ADJOINT and not f & (STATES | ADJOINT_LOSS)) == n_wide
+    assert sum(1 for f in flags if not f & ADJOINT) >= len(with_state)      # (forward kernels: one per graph, a few graphs' in two parts)
     r = F.manifest_build(RF.MANIFEST)
     assert r["failed"] == 0 and r["at_hand"] + r["built"] == r["records"] == len(have), r
     assert RF.records(RF.record(str(tmp_path / "now.fzm"))) == have

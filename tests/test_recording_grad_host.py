@@ -6,8 +6,6 @@ import ctypes
 import gzip
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,6 +16,8 @@ import grad_graphs as GG
 import loss_grad_ref as LR
 import recording_ref as RR
 from grad_harness import make_inputs, same
+from grad_host_harness import (ADJOINT, ADJOINT_LOSS, ADJOINT_SM, STATES, FakeCall, code_objects, empty_args, invalid, recipe_of, replay, symbol_shape,
+                               write_manifest)
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
@@ -25,7 +25,6 @@ F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 NEW_EXPORTS = ("fz_run_recording_grad", "fz_run_recording_loss_grad", "fz_program_recording_workspace", "fz_program_recording_block_rows",
                "fz_program_states_resources", "fz_program_states_kernel_symbol", "fz_program_states_source")
-ADJOINT, ADJOINT_SM, STATES = 1 << 27, 1 << 18, 1 << 16           # fz_internal.hpp
 MANIFEST = os.path.join(HERE, "golden", "recording_kernels.fzm.gz")
 TM, SM = 0, 1                                                     # FZ_GRAD_TIME_MAJOR, FZ_GRAD_STREAM_MAJOR
 FIVE = ("integrator", "df1_cascade_params6", "moog_ladder", "par4_sum", "rules")
@@ -100,53 +99,11 @@ def test_the_workspace_is_smaller_than_the_one_launch_calls_from_64_rows_on(name
 
 
 # ---- argument checks: every one fails before the device is needed ------------------------------------------------------------------
-class FakeBufs:
-    """distinct, 16-byte aligned, never dereferenced addresses for every buffer of a call; rows: stream-major buffers of that many rows"""
-
-    def __init__(self, p, ns, T, B, rows=None, loss=True):
-        self.p, self.ns, self.T, self.B, self.rows, self.loss = p, ns, T, B, rows, loss
-        self.ws = p.recording_workspace_bytes(ns, T, B, stream_major=rows is not None)
-        fr = (T if rows is None else rows) * ns * 4
-        sizes = {"in_": fr * p.n_in, "state": p.n_state * ns * 4, "params": p.n_param * ns * 4, ("target" if loss else "out_grad"): fr * p.n_out,
-                 "state_grad": p.n_state * ns * 4, "in_grad": fr * p.n_in, "state0_grad": p.n_state * ns * 4, "param_grad": p.n_param * ns * 4,
-                 "const_grad": p.n_const * ns * 4, "workspace": self.ws, "state_out": p.n_state * ns * 4}
-        if loss:
-            sizes.update(loss=ns * 4, out=fr * p.n_out)
-        self.addr, self.size, off = {}, sizes, 0
-        for k, n in sizes.items():
-            self.addr[k] = (1 << 40) + off
-            off += (2 * max(n, 16) + 4095) // 4096 * 4096       # (room behind each: a call with smaller blocks asks for a larger workspace)
-
-    def args(self, **over):
-        a = C.LossGradArgs() if self.loss else C.GradArgs()
-        a.struct_size = ctypes.sizeof(a)
-        for k, v in self.addr.items():
-            if k != "state_out":
-                setattr(a, k, v if self.size[k] else None)
-        a.workspace_bytes = self.ws
-        if self.loss:
-            a.grad_scale = 0.5
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
-
-    def run(self, a, rows=None, row0=0, T=None, B=None, state_out="given", ns=None):
-        T = self.T if T is None else T
-        fn = C.lib.fz_run_recording_loss_grad if self.loss else C.lib.fz_run_recording_grad
-        so = self.addr["state_out"] if state_out == "given" else state_out
-        layout, rt = (TM, 0) if self.rows is None else (SM, self.rows if rows is None else rows)
-        return fn(self.p._h, ctypes.byref(a), layout, self.ns if ns is None else ns, rt, row0, T, self.B if B is None else B, so, None)
-
-
-def invalid(rc, word):
-    return rc == C.FZ_E_INVALID and word in C.last_error()
-
-
 @pytest.mark.parametrize("loss", [False, True])
 @pytest.mark.parametrize("rows", [None, 48])
 def test_argument_checks_fail_one_by_one_with_their_reason(rows, loss):
     p = prog_of("moog_ladder")                                    # 1 in, 1 out, state, a parameter and coefficients
-    b = FakeBufs(p, 1000, 37, 8, rows, loss)
+    b = FakeCall(p, 1000, 37, loss=loss, window=rows and (rows, 0), recording=8)
     ybar = "target" if loss else "out_grad"
     a0 = b.args()
     size = ctypes.sizeof(a0)
@@ -171,7 +128,7 @@ def test_argument_checks_fail_one_by_one_with_their_reason(rows, loss):
     # (the tail of the whole workspace counts, not only the block launches' share of it)
     assert invalid(b.run(b.args(), state_out=b.addr["workspace"] + b.ws - 16), "overlap")
     assert invalid(b.run(b.args(state0_grad=None)), "state0_grad")      # more than one block: they chain through it
-    fn = C.lib.fz_run_recording_loss_grad if loss else C.lib.fz_run_recording_grad
+    fn = b.fn
     assert fn(p._h, None, TM, 10, 0, 0, 10, 0, None, None) == C.FZ_E_INVALID and "null arguments" in C.last_error()
     assert fn(None, ctypes.byref(a0), TM, 10, 0, 0, 10, 0, None, None) == C.FZ_E_INVALID
     assert fn(p._h, ctypes.byref(a0), 2, 10, 0, 0, 10, 0, None, None) == C.FZ_E_INVALID and "layout" in C.last_error()
@@ -188,7 +145,7 @@ def test_argument_checks_fail_one_by_one_with_their_reason(rows, loss):
         assert invalid(b.run(b.args(), row0=12), "beyond rows_total")
         assert invalid(b.run(b.args(), rows=46, row0=5), "rows_total")      # T + 9 rows with the window at row 5: off the float4 grid for one wire
         assert invalid(b.run(b.args(workspace_bytes=2 * b.ws), B=6), "row0")              # the second block's window would start at row 6
-    big = FakeBufs(p, 1, 1, 0, rows, loss)
+    big = FakeCall(p, 1, 1, loss=loss, window=rows and (rows, 0), recording=0)
     assert big.run(big.args(), ns=1 << 30) == C.FZ_E_UNSUPPORTED and "2^30" in C.last_error()
     # what passes every check stops at the missing device (with one, fake addresses are not launched on)
     if C.lib.fz_device_count() == 0:
@@ -205,8 +162,7 @@ def test_argument_checks_fail_one_by_one_with_their_reason(rows, loss):
 
 def test_an_empty_recording_is_ok_and_needs_no_buffer():
     p = prog_of("df1_cascade_params6")
-    for args, fn in ((C.GradArgs(), C.lib.fz_run_recording_grad), (C.LossGradArgs(), C.lib.fz_run_recording_loss_grad)):
-        args.struct_size = ctypes.sizeof(args)
+    for args, fn in ((empty_args(), C.lib.fz_run_recording_grad), (empty_args(True), C.lib.fz_run_recording_loss_grad)):
         for ns, T in ((0, 100), (100, 0), (0, 0)):
             assert fn(p._h, ctypes.byref(args), TM, ns, 0, 0, T, 0, None, None) == C.FZ_OK, C.last_error()
             assert fn(p._h, ctypes.byref(args), SM, ns, 100, 0, T, 0, None, None) == C.FZ_OK, C.last_error()
@@ -219,8 +175,7 @@ def test_refusals_are_the_backwards(name):
     assert C.lib.fz_program_grad_check(p._h) == C.FZ_E_UNSUPPORTED
     why = C.last_error()
     assert word.lower() in why.lower()
-    g, a = C.GradArgs(), C.LossGradArgs()
-    g.struct_size, a.struct_size = ctypes.sizeof(g), ctypes.sizeof(a)
+    g, a = empty_args(), empty_args(True)
     for layout in (TM, SM):
         assert C.lib.fz_run_recording_grad(p._h, ctypes.byref(g), layout, 64, 16 * layout, 0, 16, 0, None, None) == C.FZ_E_UNSUPPORTED and C.last_error() == why
         assert C.lib.fz_run_recording_loss_grad(p._h, ctypes.byref(a), layout, 64, 16 * layout, 0, 16, 0, None, None) == C.FZ_E_UNSUPPORTED and C.last_error() == why
@@ -257,29 +212,21 @@ def test_states_kernels_jit_compile_without_scratch_or_vgpr_spills(name, capsys)
 
 
 def test_a_manifest_with_a_sound_and_impossible_states_variants_builds_one_and_refuses_the_rest(tmp_path):
-    expr = F.from_sexpr(GG.SUPPORTED["integrator"]())
-    buf = ctypes.create_string_buffer(1 << 16)
-    n = C.lib.fz_expr_recipe(expr._h, buf, 1 << 16)
-    recipe = b"typed 0\n" + buf.raw[:n]
-    rec = lambda P, U, flags, block=256: b"FZM1 %d %d %d %d %d\n" % (P, U, block, flags, len(recipe)) + recipe   # noqa: E731
-    p = F.compile(expr)
-    u = int(re.match(r"fz_states_kernel_u(\d+)b", p.states_kernel_symbol()).group(1))
-    m = re.match(r"fz_states_sm_kernel_u(\d+)r(\d+)b", p.states_kernel_symbol(True))
-    usm, r = int(m.group(1)), int(m.group(2))
+    recipe = recipe_of(GG.SUPPORTED["integrator"]())
+    p = F.compile(F.from_sexpr(GG.SUPPORTED["integrator"]()))
+    u = symbol_shape(p.states_kernel_symbol(), "u")[0]
+    usm, r, _ = symbol_shape(p.states_kernel_symbol(True), "u")
     path = tmp_path / "m.fzm"
-    path.write_bytes(rec(1, u, ADJOINT | STATES)                              # sound
-                     + rec(1, 2 * u, ADJOINT | STATES)                        # an unroll the host does not make for this graph
-                     + rec(2, u, ADJOINT | STATES)                            # streams per lane: always 1
-                     + rec(1, u, ADJOINT | STATES, 128)                       # another workgroup
-                     + rec(2 * r, usm, ADJOINT | STATES | ADJOINT_SM)         # another patch
-                     + rec(1, u, ADJOINT | STATES | (1 << 17))                # the loss bit next to it: no kernel of anything
-                     + rec(1, u, ADJOINT | STATES | 256))                     # a forward flag next to it
-    code = "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r, 2))" % (os.path.dirname(HERE), str(path))
-    env = {k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}
-    out = subprocess.check_output([sys.executable, "-c", code], env=dict(env, FLOWZ_HIP_CACHE=str(tmp_path / "cache")), text=True)
-    res = eval(out.splitlines()[-1])
+    write_manifest(path, [(1, u, 256, ADJOINT | STATES, recipe),                              # sound
+                          (1, 2 * u, 256, ADJOINT | STATES, recipe),                          # an unroll the host does not make for this graph
+                          (2, u, 256, ADJOINT | STATES, recipe),                              # streams per lane: always 1
+                          (1, u, 128, ADJOINT | STATES, recipe),                              # another workgroup
+                          (2 * r, usm, 256, ADJOINT | STATES | ADJOINT_SM, recipe),           # another patch
+                          (1, u, 256, ADJOINT | STATES | ADJOINT_LOSS, recipe),               # the loss bit next to it: no kernel of anything
+                          (1, u, 256, ADJOINT | STATES | 256, recipe)])                       # a forward flag next to it
+    res = replay(path, {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")}, jobs=2)
     assert res["records"] == 7 and res["built"] == 1 and res["failed"] == 6 and res["at_hand"] == 0, res
-    assert len([f for f in os.listdir(tmp_path / "cache") if f.endswith(".hsaco")]) == 1
+    assert len(code_objects(tmp_path / "cache")) == 1
     # the states bit without the adjoint bit is no variant of anything: a caller's forward variant with it is refused as reserved
     with pytest.raises(F.FlowzError):
         p.build(F.make_variant(1, 8, 256, STATES))
@@ -291,7 +238,7 @@ def test_the_recorded_manifest_holds_the_kernels_of_the_gpu_tests():
     flags = [int(m.group(1)) for m in re.finditer(rb"FZM1 \d+ \d+ \d+ (\d+) \d+\n", gzip.open(MANIFEST, "rb").read())]
     states = [f for f in flags if f & ADJOINT and f & STATES]
     assert states and any(f & ADJOINT_SM for f in states) and any(not f & ADJOINT_SM for f in states)
-    assert any(f & ADJOINT and f & (1 << 17) for f in flags) and any(f & ADJOINT and not f & (STATES | 1 << 17) for f in flags)
+    assert any(f & ADJOINT and f & ADJOINT_LOSS for f in flags) and any(f & ADJOINT and not f & (STATES | ADJOINT_LOSS) for f in flags)
     r = F.manifest_build(MANIFEST)
     assert r["failed"] == 0 and r["at_hand"] + r["built"] == r["records"] == len(flags), r
 

@@ -3,12 +3,7 @@ to fz_program_grad_check's, the workspace query, the argument checks, the kernel
 texts of the other adjoint kernels (unchanged), the kernel manifest of the GPU tests, and tests/adjoint_ref.py on the ring graphs
 against float64 autograd."""
 import ctypes
-import glob
-import gzip
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,26 +11,20 @@ import pytest
 import adjoint_ref as A
 import grad_graphs as GG
 import ring_grad_graphs as RG
-from test_grad_host import FakeBufs
+import ring_loss_graphs as RL
+from grad_host_harness import (ADJOINT, ADJOINT_RING, LDS_BYTES, FakeCall, assert_no_contraction, code_pins, empty_args, kernel_ops, recorded_recipe, replay,
+                               symbol_shape, write_manifest)
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
 F32 = np.float32
-HERE = os.path.dirname(os.path.abspath(__file__))
-MANIFEST = os.path.join(HERE, "golden", "ring_grad_kernels.fzm.gz")
-LDS_BYTES = 163840
+RING_BITS = ADJOINT | ADJOINT_RING
 
-_progs = {}
-
-
-def ring_prog(name):
-    if name not in _progs:
-        _progs[name] = F.compile(F.from_sexpr(RG.RINGS[name]()))
-    return _progs[name]
+ring_prog = RG.prog
 
 
 def stride(p):
-    return int(p.ring_grad_kernel_symbol().split("_c")[1].split("b")[0])
+    return symbol_shape(p.ring_grad_kernel_symbol(), "c")[0]
 
 
 # ---- scope -------------------------------------------------------------------------------------------------------------------------
@@ -75,8 +64,7 @@ def test_refusals_keep_their_reasons(name):
         with pytest.raises(F.FlowzError) as ei:
             call()
         assert ei.value.code == C.FZ_E_UNSUPPORTED and word.lower() in str(ei.value).lower()
-    a = C.GradArgs()
-    a.struct_size = ctypes.sizeof(C.GradArgs)
+    a = empty_args()
     assert C.lib.fz_run_block_ring_grad(p._h, ctypes.byref(a), 64, 16, None) == C.FZ_E_UNSUPPORTED
 
 
@@ -94,8 +82,7 @@ def test_rings_that_fit_no_workgroup_are_refused_with_the_bytes():
         with pytest.raises(F.FlowzError) as ei:
             call()
         assert ei.value.code == C.FZ_E_UNSUPPORTED and "393216" in str(ei.value)
-    a = C.GradArgs()
-    a.struct_size = ctypes.sizeof(C.GradArgs)
+    a = empty_args()
     for ns, T in ((64, 16), (0, 0)):
         assert C.lib.fz_run_block_ring_grad(p._h, ctypes.byref(a), ns, T, None) == C.FZ_E_UNSUPPORTED
 
@@ -116,7 +103,7 @@ def test_the_plain_backward_still_refuses_the_ring_comb():
 def test_a_forward_variant_naming_the_ring_bit_is_refused_as_reserved():
     p = ring_prog("fb9")
     with pytest.raises(F.FlowzError) as ei:
-        p.kernel_name(F.make_variant(1, 8, 256, 1 << 14), 4096, 64)
+        p.kernel_name(F.make_variant(1, 8, 256, ADJOINT_RING), 4096, 64)
     assert ei.value.code == C.FZ_E_INVALID and "reserved" in str(ei.value)
 
 
@@ -160,29 +147,10 @@ def test_default_stride_counts_what_a_chunk_keeps():
 
 
 # ---- argument checks: every one fails before the device is needed, and they are fz_run_block_grad's --------------------------------
-class RingFakeBufs(FakeBufs):
-    def __init__(self, p, ns, T):
-        FakeBufs.__init__(self, _Ws(p), ns, T)
-        self.p = p
-
-    def run(self, a, ns=None, T=None):
-        return C.lib.fz_run_block_ring_grad(self.p._h, ctypes.byref(a), self.ns if ns is None else ns, self.T if T is None else T, None)
-
-
-class _Ws:
-    """a program whose grad_workspace_bytes is the ring query (FakeBufs sizes its workspace with it)"""
-
-    def __init__(self, p):
-        self._p = p
-
-    def __getattr__(self, k):
-        return self._p.ring_grad_workspace_bytes if k == "grad_workspace_bytes" else getattr(self._p, k)
-
-
 @pytest.mark.parametrize("name", ["lds_ring_comb", "biquad_comb17"])
 def test_argument_checks(name):
     p = ring_prog(name)
-    b = RingFakeBufs(p, 1000, 40)
+    b = FakeCall(p, 1000, 40, ring=True)
     bad = [
         b.args(struct_size=ctypes.sizeof(C.GradArgs) - 8),
         b.args(struct_size=ctypes.sizeof(C.GradArgs) + 8),
@@ -219,8 +187,7 @@ def test_argument_checks(name):
         assert b.run(b.args(state0_grad=b.addr["state_grad"])) == C.FZ_E_NO_DEVICE, C.last_error()
         assert b.run(b.args(in_grad=None, state0_grad=None, param_grad=None, const_grad=None, state_grad=None)) == C.FZ_E_NO_DEVICE
     # an empty block is FZ_OK and touches nothing: no buffer is needed at all
-    empty = C.GradArgs()
-    empty.struct_size = ctypes.sizeof(C.GradArgs)
+    empty = empty_args()
     for ns, T in ((0, 100), (100, 0), (0, 0)):
         assert C.lib.fz_run_block_ring_grad(p._h, ctypes.byref(empty), ns, T, None) == C.FZ_OK, C.last_error()
     empty.struct_size = 8
@@ -236,8 +203,8 @@ def test_ring_kernel_jit_compiles_without_scratch(name):
         r = p.ring_grad_resources(c)
         assert r["scratch_bytes"] == 0 and r["vgpr_spills"] == 0, (c, r)
         sym = p.ring_grad_kernel_symbol(c)
-        block = int(sym.split("_g")[0].split("b")[1])
-        assert r["unroll"] == int(sym.split("_c")[1].split("b")[0])
+        unroll, block = symbol_shape(sym, "c")
+        assert r["unroll"] == unroll
         assert r["lds_bytes"] == sum(depths) * block * 4 <= LDS_BYTES, r
         # the largest of 256 / 128 / 64 lanes that leaves room for two workgroups per compute unit, else the largest that fits one
         two = [b for b in (256, 128, 64) if 2 * sum(depths) * b * 4 <= LDS_BYTES]
@@ -249,25 +216,8 @@ def test_ring_kernel_jit_compiles_without_scratch(name):
 @pytest.mark.parametrize("name", ["lds_ring_comb", "ks_tanh11"])
 def test_ring_kernel_has_no_fma(name, tmp_path, monkeypatch):
     """the check of test_grad_host.py: test_adjoint_kernel_has_no_fma; and the kernel keeps its rings in LDS, without a barrier"""
-    monkeypatch.setenv("FLOWZ_HIP_CACHE", str(tmp_path))
-    p = F.compile(F.from_sexpr(RG.RINGS[name]()))
-    p.ring_grad_resources()
-    objs = glob.glob(str(tmp_path / "*.hsaco"))
-    assert len(objs) == 1
-    dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", objs[0]], text=True)
-    assert p.ring_grad_kernel_symbol() in dis
-    lines = [ln.split() for ln in dis.splitlines() if ln.strip()]
-    ops = [w[0] for w in lines if w[0].startswith("v_")]
-    assert len(ops) > 20
-    fused = [o for o in ops if o.startswith(("v_fma", "v_fmac"))]
-    divisions, roots = ops.count("v_div_fixup_f32"), ops.count("v_sqrt_f32_e32") + ops.count("v_sqrt_f32_e64")
-    assert len(fused) == 5 * divisions + 2 * roots and ops.count("v_div_fmas_f32") == divisions
-    assert not [o for o in ops if re.match(r"v_(pk_(fma|mad|mac)|mad|mac)(_mix|_mixlo|_mixhi|_legacy)?_(f16|f32|f64|bf16)", o)]
-    if name == "lds_ring_comb":
-        assert divisions == 0 and roots == 0 and not fused
-    every = [w[0] for w in lines]
-    assert any(o.startswith("ds_read") for o in every) and any(o.startswith("ds_write") for o in every)
-    assert "s_barrier" not in every and not [o for o in every if "atomic" in o]
+    _, _, _, every = kernel_ops(monkeypatch, tmp_path, RG.RINGS[name](), "ring_grad_resources")
+    assert_no_contraction(every, divides=name != "lds_ring_comb", lds=True)
 
 
 @pytest.mark.parametrize("name", ["df1_cascade6", "moog_ladder", "rules"])
@@ -276,7 +226,7 @@ def test_the_other_adjoint_kernels_have_the_parents_texts(name):
     the commit that folded the loss kernels into their siblings; test_adjoint_code_pins_host.py holds what the library builds now to
     them.  Here: the pins name this graph's kernels by the symbols the library gives them, and for a graph without a ring line the ring
     kernel IS the adjoint kernel."""
-    pins = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
+    pins = code_pins()
     p = F.compile(F.from_sexpr(GG.SUPPORTED[name]()))
     for sm, layout in ((False, "tm"), (True, "sm")):
         assert pins[f"adjoint/{layout}/{name}"]["symbol"] == p.grad_kernel_symbol(0, sm)
@@ -295,101 +245,27 @@ def test_the_ring_kernel_has_a_text_of_its_own():
     assert "fz_adj" not in p.source()
 
 
-# ---- the kernel manifest of the GPU tests ------------------------------------------------------------------------------------------
-def kernel_requests():
-    """(program, checkpoint_rows) of every ring kernel test_ring_grad_gpu.py launches"""
-    out = [(ring_prog(n), 0) for n in sorted(RG.RINGS)]
-    out += [(ring_prog(n), c) for n in ("lds_ring_comb", "biquad_comb17") for c in (1, 32)]
-    return out
-
-
-def record_manifest():
-    """tests/golden/ring_grad_kernels.fzm.gz: resolve every kernel of kernel_requests() -- and the forward kernels the chaining and
-    autograd tests launch -- in a process that records (FLOWZ_HIP_MANIFEST); needs no GPU.  build() replays every manifest under
-    tests/golden/, so a GPU run finds them built.  By hand: PYTHONPATH=. python tests/test_ring_grad_host.py"""
-    import sys
-    import tempfile
-    code = ("import sys\nsys.path[:0] = [%r, %r]\nimport test_ring_grad_host as T\nimport ring_grad_graphs as RG\n"
-            "for p, c in T.kernel_requests():\n    p.ring_grad_resources(c)\n"
-            "for n, shapes in T.FORWARD_SHAPES.items():\n    for ns, rows in shapes:\n        T.ring_prog(n).build(None, ns, rows)\n") % (os.path.dirname(HERE), HERE)
-    with tempfile.TemporaryDirectory() as td:
-        raw = os.path.join(td, "manifest.fzm")
-        subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, FLOWZ_HIP_MANIFEST=raw))
-        with open(raw, "rb") as f, open(MANIFEST, "wb") as out:
-            out.write(gzip.compress(f.read(), 9, mtime=0))
-    return F.manifest_build(MANIFEST)
-
-
-# the forward launches of test_ring_grad_gpu.py: (streams, rows) of run_block per graph (chaining: D - 2 rows; autograd: fb9)
-FORWARD_SHAPES = {n: [(65, RG.DEEPEST[n] - 2)] for n in RG.RINGS}
-FORWARD_SHAPES["fb9"] = FORWARD_SHAPES["fb9"] + [(130, 30)]
-
-
-def manifest_variants():
-    """(P, U, block, flags, recipe) of every record of the committed manifest"""
-    text = gzip.open(MANIFEST, "rb").read()
-    out, pos = [], 0
-    while pos < len(text):
-        eol = text.index(b"\n", pos)
-        tag, P, U, block, flags, n = text[pos:eol].split()
-        assert tag == b"FZM1"
-        out.append((int(P), int(U), int(block), int(flags), text[eol + 1:eol + 1 + int(n)]))
-        pos = eol + 1 + int(n)
-    return out
-
-
+# ---- the kernel manifest of the GPU tests (ring_grad_graphs.record_manifest records it) --------------------------------------------------
 def test_the_committed_manifest_holds_the_kernels_the_gpu_tests_launch():
-    ring_bits = (1 << 27) | (1 << 14)
-    recs = manifest_variants()
-    rings = sorted(v[:4] for v in recs if v[3] == ring_bits)
-    want = sorted((1, int(p.ring_grad_kernel_symbol(c).split("_c")[1].split("b")[0]), int(p.ring_grad_kernel_symbol(c).split("_g")[0].split("b")[1]), ring_bits)
-                  for p, c in kernel_requests())
+    recs = RL.manifest_variants(RG.MANIFEST)
+    rings = sorted(v[:4] for v in recs if v[3] == RING_BITS)
+    want = sorted((1, *symbol_shape(p.ring_grad_kernel_symbol(c), "c"), RING_BITS) for p, c in RG.kernel_requests())
     assert rings == want
     assert len(set(recs)) <= 40
     # what the library rebuilds from it is what the programs resolve now (at hand or built, none failed)
-    env = {k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}
-    out = subprocess.check_output([os.sys.executable, "-c", "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r))"
-                                   % (os.path.dirname(HERE), MANIFEST)], env=env, text=True)
-    counts = eval(out.strip().splitlines()[-1])
+    counts = replay(RG.MANIFEST)
     assert counts["failed"] == 0 and counts["records"] == len(set(recs)), counts
 
 
 def test_a_manifest_cannot_ask_for_a_ring_kernel_the_backward_would_not_make(tmp_path):
     """wrong block, a C that is no power of two <= 32, a graph without a ring: counted as failed, nothing built"""
-    text = gzip.open(MANIFEST, "rb").read()
-    ring_bits = (1 << 27) | (1 << 14)
-    pos, recipes = 0, {}
-    while pos < len(text):
-        eol = text.index(b"\n", pos)
-        _, P, U, block, flags, n = text[pos:eol].split()
-        recipes.setdefault(int(flags) == ring_bits, (int(block), text[eol + 1:eol + 1 + int(n)]))
-        pos = eol + 1 + int(n)
-    block, ring_recipe = recipes[True]
-    _, plain_recipe = F_plain_recipe(tmp_path)
+    block, ring_recipe = next((v[2], v[4]) for v in RL.manifest_variants(RG.MANIFEST) if v[3] == RING_BITS)
+    plain_recipe = recorded_recipe(tmp_path, "grad_graphs", "SUPPORTED['integrator']()", "grad_resources")
     bad = [(1, 16, 512, ring_recipe), (1, 16, block // 2 if block > 64 else 128, ring_recipe), (1, 3, block, ring_recipe), (1, 64, block, ring_recipe),
            (1, 0, block, ring_recipe), (2, 16, block, ring_recipe), (1, 16, 256, plain_recipe)]
-    path = tmp_path / "bad.fzm"
-    with open(path, "wb") as f:
-        for P, U, blk, recipe in bad:
-            f.write(b"FZM1 %d %d %d %d %d\n" % (P, U, blk, ring_bits, len(recipe)) + recipe)
-    env = dict({k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}, FLOWZ_HIP_CACHE=str(tmp_path / "cache"))
-    out = subprocess.check_output([os.sys.executable, "-c", "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r))"
-                                   % (os.path.dirname(HERE), str(path))], env=env, text=True)
-    counts = eval(out.strip().splitlines()[-1])
+    write_manifest(tmp_path / "bad.fzm", [(P, U, blk, RING_BITS, recipe) for P, U, blk, recipe in bad])
+    counts = replay(tmp_path / "bad.fzm", {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
     assert counts["failed"] == len(bad) and counts["built"] == 0 and counts["at_hand"] == 0, counts
-
-
-def F_plain_recipe(tmp_path):
-    """the recipe (input types and expression text) of a graph without a ring, as a recording process writes it"""
-    raw = tmp_path / "plain.fzm"
-    code = ("import sys\nsys.path[:0] = [%r, %r]\nimport grad_graphs as GG\nfrom zignal_amd import flowz as F\n"
-            "F.compile(F.from_sexpr(GG.SUPPORTED['integrator']())).grad_source()\nF.compile(F.from_sexpr(GG.SUPPORTED['integrator']())).grad_resources()\n"
-            ) % (os.path.dirname(HERE), HERE)
-    subprocess.check_call([os.sys.executable, "-c", code], env=dict(os.environ, FLOWZ_HIP_MANIFEST=str(raw), FLOWZ_HIP_CACHE=str(tmp_path / "c0")))
-    text = open(raw, "rb").read()
-    eol = text.index(b"\n")
-    n = int(text[:eol].split()[5])
-    return None, text[eol + 1:eol + 1 + n]
 
 
 # ---- the numpy restatement on the ring graphs against float64 autograd ---------------------------------------------------------------
@@ -423,6 +299,3 @@ def test_reference_chains_bitwise_with_a_first_block_shorter_than_the_line(name)
     for k in ("state", "params", "consts"):
         assert same(first[k], whole[k]), k
 
-
-if __name__ == "__main__":                         # record the kernel manifest of the library as it is
-    print("kernel manifest:", record_manifest())

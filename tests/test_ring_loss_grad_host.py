@@ -3,12 +3,8 @@ lines deeper than 8 samples): its scope and the refusals that stay, the calls it
 of fz_run_block_loss_grad, the kernel's resources and instructions (JIT for gfx950), the code pins' names for every other kernel, the kernel
 manifest of the GPU tests, and tests/loss_grad_ref.py on the ring graphs against float64 autograd of the mean squared error."""
 import ctypes
-import glob
-import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,24 +14,16 @@ import grad_graphs as GG
 import loss_grad_ref as LR
 import ring_grad_graphs as RG
 import ring_loss_graphs as RL
-from test_loss_grad_host import FakeBufs, invalid
-from test_ring_grad_host import F_plain_recipe, _Ws
+from grad_host_harness import (ADJOINT, ADJOINT_LOSS, ADJOINT_RING, LDS_BYTES, FakeCall, assert_no_contraction, code_pins, empty_args, invalid,
+                               kernel_ops, recorded_recipe, replay, symbol_shape, write_manifest)
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
-LDS_BYTES = 163840
-ADJOINT, ADJOINT_LOSS, ADJOINT_RING = 1 << 27, 1 << 17, 1 << 14     # fz_internal.hpp
 RING_LOSS_BITS = ADJOINT | ADJOINT_RING | ADJOINT_LOSS
 NEW_EXPORTS = ("fz_run_block_ring_loss_grad", "fz_program_ring_loss_grad_resources", "fz_program_ring_loss_grad_kernel_symbol",
                "fz_program_ring_loss_grad_source")
-
-
-def empty_args():
-    a = C.LossGradArgs()
-    a.struct_size = ctypes.sizeof(C.LossGradArgs)
-    return a
 
 
 def test_the_new_entry_points_are_declared_and_exported():
@@ -60,7 +48,7 @@ def test_the_ten_graphs_are_taken(name):
     assert "static void out(" not in p.ring_grad_source()
     # an empty block is FZ_OK with nothing touched
     for ns, T in ((0, 100), (100, 0), (0, 0)):
-        assert C.lib.fz_run_block_ring_loss_grad(p._h, ctypes.byref(empty_args()), ns, T, None) == C.FZ_OK, C.last_error()
+        assert C.lib.fz_run_block_ring_loss_grad(p._h, ctypes.byref(empty_args(True)), ns, T, None) == C.FZ_OK, C.last_error()
     # the loss calls without the rings keep refusing it
     with pytest.raises(F.FlowzError) as ei:
         p.loss_grad_resources()
@@ -81,7 +69,7 @@ def test_refusals_keep_their_reasons(name):
     why = C.last_error()
     assert word.lower() in why.lower()
     for ns, T in ((64, 16), (0, 0)):
-        assert C.lib.fz_run_block_ring_loss_grad(p._h, ctypes.byref(empty_args()), ns, T, None) == C.FZ_E_UNSUPPORTED and C.last_error() == why
+        assert C.lib.fz_run_block_ring_loss_grad(p._h, ctypes.byref(empty_args(True)), ns, T, None) == C.FZ_E_UNSUPPORTED and C.last_error() == why
     for call in (p.ring_loss_grad_kernel_symbol, p.ring_loss_grad_source, p.ring_loss_grad_resources):
         with pytest.raises(F.FlowzError) as ei:
             call()
@@ -91,7 +79,7 @@ def test_refusals_keep_their_reasons(name):
 def test_rings_that_fit_no_workgroup_are_refused_with_the_bytes():
     p = F.compile(F.from_sexpr(RG.six_lines_256()))
     for ns, T in ((64, 16), (0, 0)):
-        assert C.lib.fz_run_block_ring_loss_grad(p._h, ctypes.byref(empty_args()), ns, T, None) == C.FZ_E_UNSUPPORTED
+        assert C.lib.fz_run_block_ring_loss_grad(p._h, ctypes.byref(empty_args(True)), ns, T, None) == C.FZ_E_UNSUPPORTED
         why = C.last_error()
         assert "393216 bytes" in why and str(LDS_BYTES) in why and "LDS" in why, why
     for call in (p.ring_loss_grad_kernel_symbol, p.ring_loss_grad_source, p.ring_loss_grad_resources):
@@ -102,15 +90,14 @@ def test_rings_that_fit_no_workgroup_are_refused_with_the_bytes():
 
 def test_the_other_loss_calls_still_refuse_the_ring_comb():
     p = RL.prog("lds_ring_comb")
-    a = empty_args()
+    a = empty_args(True)
     calls = (lambda: C.lib.fz_run_block_loss_grad(p._h, ctypes.byref(a), 64, 16, None),
              lambda: C.lib.fz_run_block_loss_grad_stream_major(p._h, ctypes.byref(a), 64, 16, 0, 16, None),
              lambda: C.lib.fz_run_recording_loss_grad(p._h, ctypes.byref(a), 0, 64, 0, 0, 16, 0, None, None),
              lambda: C.lib.fz_run_recording_loss_grad(p._h, ctypes.byref(a), 1, 64, 16, 0, 16, 0, None, None))
     for call in calls:
         assert call() == C.FZ_E_UNSUPPORTED and "LDS" in C.last_error(), C.last_error()
-    g = C.GradArgs()
-    g.struct_size = ctypes.sizeof(C.GradArgs)
+    g = empty_args()
     assert C.lib.fz_run_recording_grad(p._h, ctypes.byref(g), 0, 64, 0, 0, 16, 0, None, None) == C.FZ_E_UNSUPPORTED and "LDS" in C.last_error()
     for sm in (False, True):
         for call in (p.loss_grad_kernel_symbol, p.loss_grad_resources, p.loss_grad_source):
@@ -156,21 +143,10 @@ def test_for_a_graph_without_a_ring_the_calls_are_the_loss_grad_calls(name):
 
 
 # ---- argument checks: fz_run_block_loss_grad's, before a device is needed ------------------------------------------------------------
-class RingLossFakeBufs(FakeBufs):
-    """FakeBufs of test_loss_grad_host.py with the ring backward's workspace, run through the new call"""
-
-    def __init__(self, p, ns, T):
-        FakeBufs.__init__(self, _Ws(p), ns, T)
-        self.p = p
-
-    def run(self, a, ns=None, T=None):
-        return C.lib.fz_run_block_ring_loss_grad(self.p._h, ctypes.byref(a), self.ns if ns is None else ns, self.T if T is None else T, None)
-
-
 @pytest.mark.parametrize("name", ["lds_ring_comb", "two_out_fb"])
 def test_argument_checks_fail_one_by_one_with_their_reason(name):
     p = RL.prog(name)
-    b = RingLossFakeBufs(p, 1000, 40)
+    b = FakeCall(p, 1000, 40, ring=True, loss=True)
     assert b.ws == p.ring_grad_workspace_bytes(1000, 40) > 0
     size = ctypes.sizeof(C.LossGradArgs)
     for bad in (size - 8, size + 8, 0, ctypes.sizeof(C.GradArgs)):
@@ -194,10 +170,10 @@ def test_argument_checks_fail_one_by_one_with_their_reason(name):
     assert invalid(b.run(b.args(out=b.addr["target"] + b.size["target"] - 16)), "overlap")
     assert C.lib.fz_run_block_ring_loss_grad(p._h, None, 10, 10, None) == C.FZ_E_INVALID and "null arguments" in C.last_error()
     assert C.lib.fz_run_block_ring_loss_grad(None, ctypes.byref(b.args()), 10, 10, None) == C.FZ_E_INVALID
-    big = RingLossFakeBufs(p, 1, 1)
-    assert C.lib.fz_run_block_ring_loss_grad(p._h, ctypes.byref(big.args()), 1 << 30, 1, None) == C.FZ_E_UNSUPPORTED and "2^30" in C.last_error()
+    big = FakeCall(p, 1, 1, ring=True, loss=True)
+    assert big.run(big.args(), ns=1 << 30) == C.FZ_E_UNSUPPORTED and "2^30" in C.last_error()
     # an empty block is FZ_OK and needs no buffer, but a bad struct_size is refused even then
-    empty = empty_args()
+    empty = empty_args(True)
     for ns, T in ((0, 100), (100, 0), (0, 0)):
         assert b.run(empty, ns, T) == C.FZ_OK, C.last_error()
     empty.struct_size = 8
@@ -219,8 +195,8 @@ def test_ring_loss_kernel_jit_compiles_without_scratch_with_the_ring_kernels_lds
         r, plain = p.ring_loss_grad_resources(c), p.ring_grad_resources(c)
         assert r["scratch_bytes"] == 0 and r["vgpr_spills"] == 0, (c, r)
         sym = p.ring_loss_grad_kernel_symbol(c)
-        block = int(sym.split("_g")[0].split("b")[1])
-        assert r["unroll"] == plain["unroll"] == int(sym.split("_c")[1].split("b")[0])
+        unroll, block = symbol_shape(sym, "c")
+        assert r["unroll"] == plain["unroll"] == unroll
         assert r["lds_bytes"] == plain["lds_bytes"] == sum(depths) * block * 4 <= LDS_BYTES, (r, plain)
         assert r["vgprs"] + r["agprs"] <= 256
         lines.append(f"{sym}: {r['vgprs']} VGPRs ({plain['vgprs']} plain ring), {r['sgpr_spills']} SGPR spills ({plain['sgpr_spills']} plain ring), "
@@ -232,29 +208,12 @@ def test_ring_loss_kernel_jit_compiles_without_scratch_with_the_ring_kernels_lds
 @pytest.mark.parametrize("name", ["lds_ring_comb", "two_out_fb", "ks_tanh11"])
 def test_ring_loss_kernel_has_no_fma(name, tmp_path, monkeypatch):
     """the method of test_ring_grad_host.py: test_ring_kernel_has_no_fma; and no barrier, no atomic, the rings in LDS"""
-    monkeypatch.setenv("FLOWZ_HIP_CACHE", str(tmp_path))
-    p = F.compile(F.from_sexpr(RL.GRAPHS[name]()))
-    p.ring_loss_grad_resources()
-    objs = glob.glob(str(tmp_path / "*.hsaco"))
-    assert len(objs) == 1
-    dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", objs[0]], text=True)
-    assert p.ring_loss_grad_kernel_symbol() in dis
-    lines = [ln.split() for ln in dis.splitlines() if ln.strip()]
-    ops = [w[0] for w in lines if w[0].startswith("v_")]
-    assert len(ops) > 20
-    fused = [o for o in ops if o.startswith(("v_fma", "v_fmac"))]
-    divisions, roots = ops.count("v_div_fixup_f32"), ops.count("v_sqrt_f32_e32") + ops.count("v_sqrt_f32_e64")
-    assert len(fused) == 5 * divisions + 2 * roots and ops.count("v_div_fmas_f32") == divisions
-    assert not [o for o in ops if re.match(r"v_(pk_(fma|mad|mac)|mad|mac)(_mix|_mixlo|_mixhi|_legacy)?_(f16|f32|f64|bf16)", o)]
-    if name != "ks_tanh11":
-        assert divisions == 0 and roots == 0 and not fused
-    every = [w[0] for w in lines]
-    assert any(o.startswith("ds_read") for o in every) and any(o.startswith("ds_write") for o in every)
-    assert "s_barrier" not in every and not [o for o in every if "atomic" in o]
+    _, _, _, every = kernel_ops(monkeypatch, tmp_path, RL.GRAPHS[name](), "ring_loss_grad_resources")
+    assert_no_contraction(every, divides=name == "ks_tanh11", lds=True)
 
 
 # ---- every existing kernel's code is the parent's: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py --------------
-PINS = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
+PINS = code_pins()
 
 
 def test_the_pins_cover_every_graph():
@@ -293,20 +252,16 @@ def test_the_committed_manifest_holds_exactly_the_kernels_the_gpu_tests_launch()
     got = sorted((v[:4], v[4]) for v in recs if v[3] == RING_LOSS_BITS)
     want = []
     for p, c in RL.kernel_requests():
-        sym = p.ring_loss_grad_kernel_symbol(c)
-        want.append((1, int(sym.split("_c")[1].split("b")[0]), int(sym.split("_g")[0].split("b")[1]), RING_LOSS_BITS))
+        want.append((1, *symbol_shape(p.ring_loss_grad_kernel_symbol(c), "c"), RING_LOSS_BITS))
     assert sorted(g[0] for g in got) == sorted(want) and len(set(got)) == len(got) == len(want)
     assert len({g[1] for g in got}) == len(RL.GRAPHS)             # one recipe per graph, two strides each
     # nothing else but the plain ring kernels and the forward kernels the comparisons launch
     others = [v for v in recs if v[3] != RING_LOSS_BITS]
-    assert sorted(v[:4] for v in others if v[3] & ADJOINT) == sorted((1, RL.stride(RL.prog(n)), int(RL.prog(n).ring_grad_kernel_symbol().split("_g")[0].split("b")[1]),
-                                                                     ADJOINT | ADJOINT_RING) for n in RL.GRAPHS)
+    assert sorted(v[:4] for v in others if v[3] & ADJOINT) == sorted((1, *symbol_shape(RL.prog(n).ring_grad_kernel_symbol(), "c"), ADJOINT | ADJOINT_RING)
+                                                                    for n in RL.GRAPHS)
     assert all(not (v[3] & (ADJOINT_LOSS | ADJOINT_RING)) for v in others if not v[3] & ADJOINT) and len(set(recs)) <= 60
     # what the library rebuilds from it is what the programs resolve now (at hand or built, none failed)
-    env = {k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}
-    out = subprocess.check_output([sys.executable, "-c", "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r))"
-                                   % (os.path.dirname(HERE), RL.MANIFEST)], env=env, text=True)
-    counts = eval(out.strip().splitlines()[-1])
+    counts = replay(RL.MANIFEST)
     assert counts["failed"] == 0 and counts["records"] == len(set(recs)), counts
 
 
@@ -315,17 +270,11 @@ def test_a_manifest_cannot_ask_for_a_ring_loss_kernel_the_backward_would_not_mak
     outputs -- refused by the same check, as the n_out == 0 refusal of the call itself -- cannot be written down: every expression of
     the notation has an output wire.)"""
     block, ring_recipe = next((v[2], v[4]) for v in RL.manifest_variants() if v[3] == RING_LOSS_BITS)
-    _, plain_recipe = F_plain_recipe(tmp_path)
+    plain_recipe = recorded_recipe(tmp_path, "grad_graphs", "SUPPORTED['integrator']()", "grad_resources")
     bad = [(1, 16, 512, ring_recipe), (1, 16, block // 2 if block > 64 else 128, ring_recipe), (1, 3, block, ring_recipe), (1, 64, block, ring_recipe),
            (1, 0, block, ring_recipe), (2, 16, block, ring_recipe), (1, 16, 256, plain_recipe)]
-    path = tmp_path / "bad.fzm"
-    with open(path, "wb") as f:
-        for P, U, blk, recipe in bad:
-            f.write(b"FZM1 %d %d %d %d %d\n" % (P, U, blk, RING_LOSS_BITS, len(recipe)) + recipe)
-    env = dict({k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}, FLOWZ_HIP_CACHE=str(tmp_path / "cache"))
-    out = subprocess.check_output([sys.executable, "-c", "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r))"
-                                   % (os.path.dirname(HERE), str(path))], env=env, text=True)
-    counts = eval(out.strip().splitlines()[-1])
+    write_manifest(tmp_path / "bad.fzm", [(P, U, blk, RING_LOSS_BITS, recipe) for P, U, blk, recipe in bad])
+    counts = replay(tmp_path / "bad.fzm", {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
     assert counts["failed"] == len(bad) and counts["built"] == 0 and counts["at_hand"] == 0, counts
 
 

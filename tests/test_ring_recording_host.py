@@ -5,12 +5,8 @@ scratch, no VGPR spills, the ring adjoint kernel's LDS, no FMA, no barrier, no a
 manifest of the GPU tests, and tests/recording_ref.py on the ring graphs -- the block-by-block restatement the GPU test holds the calls
 to -- against the single restated call, bit for bit, with inputs that tell a wrong chain from the right one."""
 import ctypes
-import glob
-import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -23,24 +19,18 @@ import ring_grad_graphs as RG
 import ring_recording_graphs as R
 import ring_sm_recording as S
 from grad_harness import same
+from grad_host_harness import (ADJOINT, ADJOINT_LOSS, ADJOINT_RING, ADJOINT_SM, LDS_BYTES, STATES, FakeCall, assert_no_contraction, code_objects, code_pins,
+                               empty_args, invalid, kernel_ops, recipe_of, replay, symbol_shape, write_manifest)
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
-LDS_BYTES = 163840
-ADJOINT, ADJOINT_SM, ADJOINT_LOSS, STATES, ADJOINT_RING = 1 << 27, 1 << 18, 1 << 17, 1 << 16, 1 << 14     # fz_internal.hpp
 RING_STATES_BITS = ADJOINT | STATES | ADJOINT_RING
 NEW_EXPORTS = ("fz_program_ring_recording_block_rows", "fz_program_ring_recording_workspace", "fz_run_recording_ring_grad",
                "fz_run_recording_ring_loss_grad", "fz_program_ring_states_resources", "fz_program_ring_states_kernel_symbol",
                "fz_program_ring_states_source")
 NAMES = sorted(R.GRAPHS)
-
-
-def empty_args(loss):
-    a = C.LossGradArgs() if loss else C.GradArgs()
-    a.struct_size = ctypes.sizeof(a)
-    return a
 
 
 def run_fn(loss):
@@ -217,50 +207,12 @@ def test_the_stated_figures():
 
 
 # ---- argument checks: every one fails before the device is needed --------------------------------------------------------------------
-class FakeBufs:
-    """distinct, 16-byte aligned, never dereferenced addresses for every buffer of a call"""
-
-    def __init__(self, p, ns, T, B, loss):
-        self.p, self.ns, self.T, self.B, self.loss = p, ns, T, B, loss
-        self.ws = p.ring_recording_workspace_bytes(ns, T, B)
-        fr = T * ns * 4
-        sizes = {"in_": fr * p.n_in, "state": p.n_state * ns * 4, "params": p.n_param * ns * 4, ("target" if loss else "out_grad"): fr * p.n_out,
-                 "state_grad": p.n_state * ns * 4, "in_grad": fr * p.n_in, "state0_grad": p.n_state * ns * 4, "param_grad": p.n_param * ns * 4,
-                 "const_grad": p.n_const * ns * 4, "workspace": self.ws, "state_out": p.n_state * ns * 4}
-        if loss:
-            sizes.update(loss=ns * 4, out=fr * p.n_out)
-        self.addr, self.size, off = {}, sizes, 0
-        for k, n in sizes.items():
-            self.addr[k] = (1 << 40) + off
-            off += (2 * max(n, 16) + 4095) // 4096 * 4096
-
-    def args(self, **over):
-        a = empty_args(self.loss)
-        for k, v in self.addr.items():
-            if k != "state_out":
-                setattr(a, k, v if self.size[k] else None)
-        a.workspace_bytes = self.ws
-        if self.loss:
-            a.grad_scale = 0.5
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
-
-    def run(self, a, T=None, B=None, state_out="given", ns=None):
-        so = self.addr["state_out"] if state_out == "given" else state_out
-        return run_fn(self.loss)(self.p._h, ctypes.byref(a), self.ns if ns is None else ns, self.T if T is None else T, self.B if B is None else B, so, None)
-
-
-def invalid(rc, word):
-    return rc == C.FZ_E_INVALID and word in C.last_error()
-
-
 @pytest.mark.parametrize("loss", [False, True])
 @pytest.mark.parametrize("name", ["biquad_comb17", "two_out_fb"])
 def test_argument_checks_fail_one_by_one_with_their_reason(name, loss):
     p = R.prog(name)                                              # inputs, outputs, a deep line, a per-stream coefficient
     assert p.n_in and p.n_out and p.n_param
-    b = FakeBufs(p, 1000, 37, 8, loss)
+    b = FakeCall(p, 1000, 37, ring=True, loss=loss, recording=8)
     assert b.ws == (5 * p.n_state) * 4000 + p.ring_grad_workspace_bytes(1000, 8)
     ybar = "target" if loss else "out_grad"
     a0 = b.args()
@@ -306,7 +258,7 @@ def test_argument_checks_fail_one_by_one_with_their_reason(name, loss):
         p.ring_recording_block_rows(100, 0, 3)
     # the order of run_recording: the scope, block_rows, the length, then the arguments
     assert invalid(b.run(b.args(in_=None), T=1 << 31, B=6), "multiple of 4") and invalid(b.run(b.args(in_=None), T=1 << 31), "2^31")
-    big = FakeBufs(p, 1, 1, 0, loss)
+    big = FakeCall(p, 1, 1, ring=True, loss=loss, recording=0)
     assert big.run(big.args(), ns=1 << 30) == C.FZ_E_UNSUPPORTED and "2^30" in C.last_error()
     # an empty recording is FZ_OK and needs no buffer, but a bad struct_size is refused even then
     empty = empty_args(loss)
@@ -332,7 +284,7 @@ def test_ring_states_kernel_jit_compiles_without_scratch_with_the_ring_kernels_l
     p = R.prog(name)
     r, ring = p.ring_states_resources(), p.ring_grad_resources()
     sym = p.ring_states_kernel_symbol()
-    U, block = int(sym.split("_u")[1].split("b")[0]), int(sym.split("_g")[0].split("b")[1])
+    U, block = symbol_shape(sym, "u")
     assert r["scratch_bytes"] == 0 and r["vgpr_spills"] == 0, r
     assert r["unroll"] == U and U in (1, 2, 4, 8) and U * p.n_in <= max(16, p.n_in)
     depths = [d for _, d in p.lines() if d > 8]
@@ -347,29 +299,12 @@ def test_ring_states_kernel_jit_compiles_without_scratch_with_the_ring_kernels_l
 def test_ring_states_kernel_has_no_fma_no_barrier_no_atomic(name, tmp_path, monkeypatch):
     """the method of test_ring_grad_host.py: test_ring_kernel_has_no_fma -- the only fused operations are those of the correctly rounded
     division (five each) and square root (two each) expansions"""
-    monkeypatch.setenv("FLOWZ_HIP_CACHE", str(tmp_path))
-    p = F.compile(F.from_sexpr(R.GRAPHS[name]()))
-    p.ring_states_resources()
-    objs = glob.glob(str(tmp_path / "*.hsaco"))
-    assert len(objs) == 1
-    dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", objs[0]], text=True)
-    assert p.ring_states_kernel_symbol() in dis
-    lines = [ln.split() for ln in dis.splitlines() if ln.strip()]
-    ops = [w[0] for w in lines if w[0].startswith("v_")]
-    assert len(ops) > 10
-    fused = [o for o in ops if o.startswith(("v_fma", "v_fmac"))]
-    divisions, roots = ops.count("v_div_fixup_f32"), ops.count("v_sqrt_f32_e32") + ops.count("v_sqrt_f32_e64")
-    assert len(fused) == 5 * divisions + 2 * roots and ops.count("v_div_fmas_f32") == divisions
-    assert not [o for o in ops if re.match(r"v_(pk_(fma|mad|mac)|mad|mac)(_mix|_mixlo|_mixhi|_legacy)?_(f16|f32|f64|bf16)", o)]
-    if name != "ks_tanh11":
-        assert divisions == 0 and roots == 0 and not fused
-    every = [w[0] for w in lines]
-    assert any(o.startswith("ds_read") for o in every) and any(o.startswith("ds_write") for o in every)
-    assert "s_barrier" not in every and not [o for o in every if "atomic" in o]
+    _, _, _, every = kernel_ops(monkeypatch, tmp_path, R.GRAPHS[name](), "ring_states_resources", least=10)
+    assert_no_contraction(every, divides=name == "ks_tanh11", lds=True)
 
 
 # ---- every other kernel's code is the parent's: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py ---------------
-PINS = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
+PINS = code_pins()
 
 
 def test_the_pins_cover_every_graph():
@@ -391,30 +326,19 @@ def test_every_other_kernel_has_the_parents_text():
 
 
 # ---- the kernel manifest of the GPU tests ----------------------------------------------------------------------------------------------
-def _replay(path, env_extra=None):
-    env = dict({k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}, **(env_extra or {}))
-    out = subprocess.check_output([sys.executable, "-c", "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r))"
-                                   % (os.path.dirname(HERE), str(path))], env=env, text=True)
-    return eval(out.strip().splitlines()[-1])
-
-
-def _shape(sym, letter):
-    return int(sym.split("_" + letter)[1].split("b")[0]), int(sym.split("_g")[0].split("b")[1])
-
-
 def test_the_committed_manifest_holds_exactly_the_kernels_the_gpu_tests_launch():
     import ring_loss_graphs as RL
     recs = RL.manifest_variants(R.MANIFEST)
     progs = [R.prog(n) for n in NAMES]
     got = sorted(v[:4] for v in recs if v[3] == RING_STATES_BITS)
-    assert got == sorted((1, *_shape(p.ring_states_kernel_symbol(), "u"), RING_STATES_BITS) for p in progs)
+    assert got == sorted((1, *symbol_shape(p.ring_states_kernel_symbol(), "u"), RING_STATES_BITS) for p in progs)
     assert len({v[4] for v in recs if v[3] == RING_STATES_BITS}) == len(NAMES)               # one recipe per graph
     for bits, sym in ((ADJOINT | ADJOINT_RING, F.Program.ring_grad_kernel_symbol), (ADJOINT | ADJOINT_RING | ADJOINT_LOSS, F.Program.ring_loss_grad_kernel_symbol)):
-        assert sorted(v[:4] for v in recs if v[3] == bits) == sorted((1, *_shape(sym(p, c), "c"), bits) for p in progs for c in (0, 1))
+        assert sorted(v[:4] for v in recs if v[3] == bits) == sorted((1, *symbol_shape(sym(p, c), "c"), bits) for p in progs for c in (0, 1))
     # nothing else but the forward kernels the state comparison launches
     others = [v for v in recs if not v[3] & ADJOINT]
     assert all(not (v[3] & (ADJOINT_LOSS | ADJOINT_RING | STATES)) for v in others) and len(recs) == len(set(recs)) == 5 * len(NAMES) + len(others) <= 70
-    counts = _replay(R.MANIFEST)
+    counts = replay(R.MANIFEST)
     assert counts["failed"] == 0 and counts["records"] == len(recs), counts
 
 
@@ -424,10 +348,6 @@ def test_a_manifest_cannot_ask_for_a_ring_states_kernel_the_recording_would_not_
     import ring_loss_graphs as RL
     U, block, ring_recipe = next((v[1], v[2], v[4]) for v in RL.manifest_variants(R.MANIFEST) if v[3] == RING_STATES_BITS)
 
-    def recipe_of(sexpr):
-        buf = ctypes.create_string_buffer(1 << 16)
-        n = C.lib.fz_expr_recipe(F.from_sexpr(sexpr)._h, buf, 1 << 16)
-        return b"typed 0\n" + buf.raw[:n]
     plain, refused = recipe_of(GG.SUPPORTED["integrator"]()), recipe_of(RG.six_lines_256())
     bad = [(1, U, 512, RING_STATES_BITS, ring_recipe), (1, U, block // 2 if block > 64 else 128, RING_STATES_BITS, ring_recipe),
            (1, 2 * U, block, RING_STATES_BITS, ring_recipe), (1, U // 2, block, RING_STATES_BITS, ring_recipe), (1, 0, block, RING_STATES_BITS, ring_recipe),
@@ -435,13 +355,10 @@ def test_a_manifest_cannot_ask_for_a_ring_states_kernel_the_recording_would_not_
            (1, U, block, RING_STATES_BITS | ADJOINT_SM, ring_recipe), (1, U, block, RING_STATES_BITS | 256, ring_recipe),
            (1, U, 256, RING_STATES_BITS, plain), (1, 8, 64, RING_STATES_BITS, refused)]
     good = [(1, U, block, RING_STATES_BITS, ring_recipe)]
-    path = tmp_path / "bad.fzm"
-    with open(path, "wb") as f:
-        for P, u, blk, bits, recipe in bad + good:
-            f.write(b"FZM1 %d %d %d %d %d\n" % (P, u, blk, bits, len(recipe)) + recipe)
-    counts = _replay(path, {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
+    write_manifest(tmp_path / "bad.fzm", bad + good)
+    counts = replay(tmp_path / "bad.fzm", {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
     assert counts["failed"] == len(bad) and counts["built"] == 1 and counts["at_hand"] == 0, counts
-    assert len([f for f in os.listdir(tmp_path / "cache") if f.endswith(".hsaco")]) == 1
+    assert len(code_objects(tmp_path / "cache")) == 1
 
 
 # ---- the restatement: block by block in reverse is the single call, bit for bit --------------------------------------------------------

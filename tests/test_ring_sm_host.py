@@ -4,12 +4,8 @@ rule that chooses the workgroup and the patch length together (restated in tests
 shortest patch fit no workgroup, the argument checks of the stream-major siblings, the kernels' resources and instructions (JIT for
 gfx950), the code pins' names for every other kernel, the kernel manifest of the GPU tests, and the restatement on transposed arrays."""
 import ctypes
-import glob
-import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,25 +15,18 @@ import grad_graphs as GG
 import ring_grad_graphs as RG
 import ring_loss_graphs as RL
 import ring_sm_graphs as RS
-from test_ring_grad_host import F_plain_recipe
+from grad_host_harness import (ADJOINT, ADJOINT_LOSS, ADJOINT_RING, ADJOINT_SM, LDS_BYTES, STATES, FakeCall, assert_no_contraction, code_pins, empty_args,
+                               invalid, kernel_ops, recorded_recipe, replay, write_manifest)
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
-LDS_BYTES = RS.LDS_BYTES
-ADJOINT, ADJOINT_SM, ADJOINT_LOSS, STATES, ADJOINT_RING = 1 << 27, 1 << 18, 1 << 17, 1 << 16, 1 << 14     # fz_internal.hpp
 RING_SM = ADJOINT | ADJOINT_RING | ADJOINT_SM
 RING_LOSS_SM = RING_SM | ADJOINT_LOSS
 NEW_EXPORTS = ("fz_run_block_ring_grad_stream_major", "fz_run_block_ring_loss_grad_stream_major", "fz_program_ring_grad_resources_for",
                "fz_program_ring_grad_kernel_symbol_for", "fz_program_ring_grad_source_for", "fz_program_ring_loss_grad_resources_for",
                "fz_program_ring_loss_grad_kernel_symbol_for", "fz_program_ring_loss_grad_source_for")
-
-
-def empty_args(loss):
-    a = C.LossGradArgs() if loss else C.GradArgs()
-    a.struct_size = ctypes.sizeof(a)
-    return a
 
 
 def run_sm(p, a, loss, ns, rows, row0, T):
@@ -210,47 +199,11 @@ def test_rings_plus_the_shortest_patch_that_fit_no_workgroup_are_refused_with_th
 
 
 # ---- argument checks: those of the stream-major siblings, before a device is needed ------------------------------------------------
-class FakeBufs:
-    """distinct, 16-byte aligned, never dereferenced addresses for every buffer of a stream-major ring call"""
-
-    def __init__(self, p, loss, ns, T, rows):
-        self.p, self.loss, self.ns, self.T, self.rows = p, loss, ns, T, rows
-        self.ws = p.ring_grad_workspace_bytes(ns, T)
-        fr = rows * ns * 4
-        sizes = {"in_": fr * p.n_in, "state": p.n_state * ns * 4, "params": p.n_param * ns * 4, "target" if loss else "out_grad": fr * p.n_out,
-                 "state_grad": p.n_state * ns * 4, "in_grad": fr * p.n_in, "state0_grad": p.n_state * ns * 4, "param_grad": p.n_param * ns * 4,
-                 "const_grad": p.n_const * ns * 4, "workspace": self.ws}
-        if loss:
-            sizes.update(loss=ns * 4, out=fr * p.n_out)
-        self.addr, self.size, off = {}, sizes, 0
-        for k, n in sizes.items():
-            self.addr[k] = (1 << 40) + off
-            off += (max(n, 16) + 4095) // 4096 * 4096
-
-    def args(self, **over):
-        a = empty_args(self.loss)
-        for k, v in self.addr.items():
-            setattr(a, k, v if self.size[k] else None)
-        a.workspace_bytes = self.ws
-        if self.loss:
-            a.grad_scale = 0.5
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
-
-    def run(self, a, rows=None, row0=0, T=None, ns=None):
-        return run_sm(self.p, a, self.loss, self.ns if ns is None else ns, self.rows if rows is None else rows, row0, self.T if T is None else T)
-
-
-def invalid(rc, word):
-    return rc == C.FZ_E_INVALID and word in C.last_error()
-
-
 @pytest.mark.parametrize("loss", [False, True])
 @pytest.mark.parametrize("name", ["lds_ring_comb", "two_out_fb"])
 def test_argument_checks_fail_one_by_one_with_their_reason(name, loss):
     p = RS.prog(name)
-    b = FakeBufs(p, loss, 1000, 40, 48)
+    b = FakeCall(p, 1000, 40, ring=True, loss=loss, window=(48, 0))
     second = "target" if loss else "out_grad"
     assert b.ws == p.ring_grad_workspace_bytes(1000, 40) > 0
     size = ctypes.sizeof(C.LossGradArgs if loss else C.GradArgs)
@@ -319,29 +272,12 @@ def test_the_kernels_jit_compile_without_scratch_within_the_lds(name, capsys):
 def test_the_kernels_have_no_fma_no_barrier_and_no_atomic(name, loss, c, tmp_path, monkeypatch):
     """the method of test_ring_grad_host.py: test_ring_kernel_has_no_fma -- on every graph, at the default C and at C = 1 (the two graphs
     with two outputs have the loss kernel only, as everywhere in this file)"""
-    monkeypatch.setenv("FLOWZ_HIP_CACHE", str(tmp_path))
-    p = F.compile(F.from_sexpr(RS.GRAPHS[name]()))
-    (p.ring_loss_grad_resources if loss else p.ring_grad_resources)(c, stream_major=True)
-    objs = glob.glob(str(tmp_path / "*.hsaco"))
-    assert len(objs) == 1
-    dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", objs[0]], text=True)
-    assert (p.ring_loss_grad_kernel_symbol if loss else p.ring_grad_kernel_symbol)(c, stream_major=True) in dis
-    lines = [ln.split() for ln in dis.splitlines() if ln.strip()]
-    ops = [w[0] for w in lines if w[0].startswith("v_")]
-    assert len(ops) > 20
-    fused = [o for o in ops if o.startswith(("v_fma", "v_fmac"))]
-    divisions, roots = ops.count("v_div_fixup_f32"), ops.count("v_sqrt_f32_e32") + ops.count("v_sqrt_f32_e64")
-    assert len(fused) == 5 * divisions + 2 * roots and ops.count("v_div_fmas_f32") == divisions
-    assert not [o for o in ops if re.match(r"v_(pk_(fma|mad|mac)|mad|mac)(_mix|_mixlo|_mixhi|_legacy)?_(f16|f32|f64|bf16)", o)]
-    if name != "ks_tanh11":
-        assert divisions == 0 and roots == 0 and not fused
-    every = [w[0] for w in lines]
-    assert any(o.startswith("ds_read") for o in every) and any(o.startswith("ds_write") for o in every)
-    assert "s_barrier" not in every and not [o for o in every if "atomic" in o]
+    _, _, _, every = kernel_ops(monkeypatch, tmp_path, RS.GRAPHS[name](), "ring_loss_grad_resources" if loss else "ring_grad_resources", c, stream_major=True)
+    assert_no_contraction(every, divides=name == "ks_tanh11", lds=True)
 
 
 # ---- every existing kernel's code is the parent's: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py -------------
-PINS = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
+PINS = code_pins()
 
 
 def test_the_pins_cover_every_graph():
@@ -368,13 +304,6 @@ def test_every_other_kernel_has_the_parents_text():
 
 
 # ---- the kernel manifest of the GPU tests ------------------------------------------------------------------------------------------
-def build_manifest(path, env_extra=None):
-    env = dict({k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}, **(env_extra or {}))
-    out = subprocess.check_output([sys.executable, "-c", "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r))"
-                                   % (os.path.dirname(HERE), str(path))], env=env, text=True)
-    return eval(out.strip().splitlines()[-1])
-
-
 def test_the_committed_manifest_holds_exactly_the_kernels_the_gpu_tests_launch():
     recs = RS.manifest_variants(RS.MANIFEST)
     for bits, loss in ((RING_SM, False), (RING_LOSS_SM, True)):
@@ -389,7 +318,7 @@ def test_the_committed_manifest_holds_exactly_the_kernels_the_gpu_tests_launch()
     others = [v for v in recs if v[3] not in (RING_SM, RING_LOSS_SM)]
     assert all(v[3] in (ADJOINT | ADJOINT_RING, ADJOINT | ADJOINT_RING | ADJOINT_LOSS) and v[0] == 1 for v in others if v[3] & ADJOINT)
     assert all(not (v[3] & (ADJOINT_LOSS | ADJOINT_RING | STATES)) for v in others if not v[3] & ADJOINT) and len(set(recs)) <= 64
-    counts = build_manifest(RS.MANIFEST)
+    counts = replay(RS.MANIFEST)
     assert counts["failed"] == 0 and counts["records"] == len(set(recs)), counts
 
 
@@ -399,14 +328,8 @@ def test_a_manifest_cannot_ask_for_a_kernel_the_backward_would_not_make(tmp_path
     p = RS.prog("lds_ring_comb")
     C_, R, block = RS.geometry(p)
     ring_recipe = next(v[4] for v in RS.manifest_variants(RS.MANIFEST) if v[:4] == (R, C_, block, RING_SM))
-    _, plain_recipe = F_plain_recipe(tmp_path)
-    raw = tmp_path / "refused.fzm"
-    code = ("import sys\nsys.path[:0] = [%r, %r]\nimport ring_sm_graphs as RS\nfrom zignal_amd import flowz as F\n"
-            "F.compile(F.from_sexpr(RS.three_wires_612())).ring_grad_resources()\n") % (os.path.dirname(HERE), HERE)
-    subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, FLOWZ_HIP_MANIFEST=str(raw), FLOWZ_HIP_CACHE=str(tmp_path / "c1")))
-    text = open(raw, "rb").read()
-    eol = text.index(b"\n")
-    refused_recipe = text[eol + 1:eol + 1 + int(text[:eol].split()[5])]
+    plain_recipe = recorded_recipe(tmp_path, "grad_graphs", "SUPPORTED['integrator']()", "grad_resources")
+    refused_recipe = recorded_recipe(tmp_path, "ring_sm_graphs", "three_wires_612()", "ring_grad_resources")
     bad = []
     for bits in (RING_SM, RING_LOSS_SM):
         bad += [(R, C_, 256 if block != 256 else 128, bits, ring_recipe), (R, C_, 512, bits, ring_recipe), (R // 2, C_, block, bits, ring_recipe),
@@ -414,18 +337,12 @@ def test_a_manifest_cannot_ask_for_a_kernel_the_backward_would_not_make(tmp_path
                 (R, 0, block, bits, ring_recipe), (R, C_, block, bits | STATES, ring_recipe), (R, C_, block, bits, plain_recipe),
                 (8, 8, 64, bits, refused_recipe)]
     bad.append((R, 8, block, ADJOINT | STATES | ADJOINT_RING | ADJOINT_SM, ring_recipe))     # (stream-major ring recordings are not built)
-    path = tmp_path / "bad.fzm"
-    with open(path, "wb") as f:
-        for P, U, blk, bits, recipe in bad:
-            f.write(b"FZM1 %d %d %d %d %d\n" % (P, U, blk, bits, len(recipe)) + recipe)
-    counts = build_manifest(path, {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
+    write_manifest(tmp_path / "bad.fzm", bad)
+    counts = replay(tmp_path / "bad.fzm", {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
     assert counts["failed"] == len(bad) and counts["built"] == 0 and counts["at_hand"] == 0, counts
     # and the same record with the right numbers is built
-    good = tmp_path / "good.fzm"
-    with open(good, "wb") as f:
-        f.write(b"FZM1 %d %d %d %d %d\n" % (R, C_, block, RING_SM, len(ring_recipe)) + ring_recipe)
-        f.write(b"FZM1 %d %d %d %d %d\n" % (4, 4, 64, RING_LOSS_SM, len(refused_recipe)) + refused_recipe)   # (checkpoint_rows = 4: taken)
-    counts = build_manifest(good, {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
+    write_manifest(tmp_path / "good.fzm", [(R, C_, block, RING_SM, ring_recipe), (4, 4, 64, RING_LOSS_SM, refused_recipe)])   # (checkpoint_rows = 4: taken)
+    counts = replay(tmp_path / "good.fzm", {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
     assert counts["failed"] == 0 and counts["built"] == 2, counts
 
 

@@ -5,12 +5,8 @@ stay, the calls they ARE for a graph without a deep line, the rule that chooses 
 scratch, no VGPR spill, no FMA, no barrier, no atomic), every argument check with its reason, the kernel manifest of the GPU tests,
 the code pins' names for every kernel, and the restatement on transposed arrays."""
 import ctypes
-import glob
-import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -24,27 +20,21 @@ import ring_recording_graphs as R
 import ring_sm_graphs as RS
 import ring_sm_recording as S
 from grad_harness import same
+from grad_host_harness import (ADJOINT, ADJOINT_LOSS, ADJOINT_RING, ADJOINT_SM, LDS_BYTES, STATES, FakeCall, assert_no_contraction, code_objects, code_pins,
+                               empty_args, invalid, kernel_ops, recipe_of, replay, write_manifest)
 from zignal_amd import _capi as C
 from zignal_amd import flowz as F
 
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
-LDS_BYTES = 163840
-ADJOINT, ADJOINT_SM, ADJOINT_LOSS, STATES, ADJOINT_RING = 1 << 27, 1 << 18, 1 << 17, 1 << 16, 1 << 14     # fz_internal.hpp
 BITS = ADJOINT | STATES | ADJOINT_RING | ADJOINT_SM
 NEW_EXPORTS = ("fz_run_recording_ring_grad_stream_major", "fz_run_recording_ring_loss_grad_stream_major", "fz_program_ring_states_resources_for",
                "fz_program_ring_states_kernel_symbol_for", "fz_program_ring_states_source_for")
 NAMES = sorted(S.GRAPHS)
 
 
-def empty_args(loss):
-    a = C.LossGradArgs() if loss else C.GradArgs()
-    a.struct_size = ctypes.sizeof(a)
-    return a
-
-
 def run_fn(loss):
-    return getattr(C.lib, S.ENTRY[loss])
+    return getattr(C.lib, H.ENTRY[(True, loss, True, True)])
 
 
 def three_wires():
@@ -159,7 +149,7 @@ def test_three_wires_612_is_refused_at_the_default_stride_and_taken_at_four():
         assert run_sm(p._h, ctypes.byref(a), 64, 16, 0, 16, None) == C.FZ_E_UNSUPPORTED and C.last_error() == why     # (the block call's reason)
         a.checkpoint_rows = 4
         assert run_fn(loss)(p._h, ctypes.byref(a), 0, 16, 0, 16, 0, None, None) == C.FZ_OK, C.last_error()
-        b = FakeBufs(p, 100, 16, 4, loss, c=4)
+        b = FakeCall(p, 100, 16, ring=True, loss=loss, window=(None, 0), recording=4, c=4)
         if C.lib.fz_device_count() == 0:
             assert b.run(b.args(checkpoint_rows=4)) == C.FZ_E_NO_DEVICE, C.last_error()
 
@@ -268,78 +258,21 @@ def test_a_states_kernel_that_fits_no_workgroup_is_refused_with_the_bytes():
 def test_the_kernel_compiles_without_scratch_or_spill_and_has_no_fma_no_barrier_no_atomic(name, tmp_path, monkeypatch, capsys):
     """the method of test_ring_recording_host.py: the only fused operations are those of the correctly rounded division (five each) and
     square root (two each) expansions"""
-    monkeypatch.setenv("FLOWZ_HIP_CACHE", str(tmp_path))
-    p = F.compile(F.from_sexpr(S.GRAPHS[name]()))
-    r = p.ring_states_resources(stream_major=True)
+    p, r, _, every = kernel_ops(monkeypatch, tmp_path, S.GRAPHS[name](), "ring_states_resources", least=10, stream_major=True)
     assert r["scratch_bytes"] == 0 and r["vgpr_spills"] == 0 and r["vgprs"] + r["agprs"] <= 256, r
-    objs = glob.glob(str(tmp_path / "*.hsaco"))
-    assert len(objs) == 1
-    dis = subprocess.check_output(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", objs[0]], text=True)
+    assert_no_contraction(every, divides=name == "ks_tanh11", lds=True)
     sym = p.ring_states_kernel_symbol(stream_major=True)
-    assert sym in dis
-    lines = [ln.split() for ln in dis.splitlines() if ln.strip()]
-    ops = [w[0] for w in lines if w[0].startswith("v_")]
-    assert len(ops) > 10
-    fused = [o for o in ops if o.startswith(("v_fma", "v_fmac"))]
-    divisions, roots = ops.count("v_div_fixup_f32"), ops.count("v_sqrt_f32_e32") + ops.count("v_sqrt_f32_e64")
-    assert len(fused) == 5 * divisions + 2 * roots and ops.count("v_div_fmas_f32") == divisions
-    assert not [o for o in ops if re.match(r"v_(pk_(fma|mad|mac)|mad|mac)(_mix|_mixlo|_mixhi|_legacy)?_(f16|f32|f64|bf16)", o)]
-    if name != "ks_tanh11":
-        assert divisions == 0 and roots == 0 and not fused
-    every = [w[0] for w in lines]
-    assert any(o.startswith("ds_read") for o in every) and any(o.startswith("ds_write") for o in every)
-    assert "s_barrier" not in every and not [o for o in every if "atomic" in o]
     with capsys.disabled():                                       # (SGPR spills are reported, not asserted: correct, slower)
         print(f"\n{sym}: {r['vgprs']} VGPRs, {r['sgprs']} SGPRs, {r['sgpr_spills']} SGPR spills, {r['lds_bytes']} B LDS")
 
 
 # ---- argument checks: every one fails before the device is needed --------------------------------------------------------------------
-class FakeBufs:
-    """distinct, 16-byte aligned, never dereferenced addresses for every buffer of a call over a window of T rows at row0 of `rows`"""
-
-    def __init__(self, p, ns, T, B, loss, rows=None, row0=0, c=0):
-        self.p, self.ns, self.T, self.B, self.loss = p, ns, T, B, loss
-        self.rows, self.row0 = H.up4(row0 + T) if rows is None else rows, row0
-        self.ws = p.ring_recording_workspace_bytes(ns, T, B, c)
-        fr = self.rows * ns * 4
-        sizes = {"in_": fr * p.n_in, "state": p.n_state * ns * 4, "params": p.n_param * ns * 4, ("target" if loss else "out_grad"): fr * p.n_out,
-                 "state_grad": p.n_state * ns * 4, "in_grad": fr * p.n_in, "state0_grad": p.n_state * ns * 4, "param_grad": p.n_param * ns * 4,
-                 "const_grad": p.n_const * ns * 4, "workspace": self.ws, "state_out": p.n_state * ns * 4}
-        if loss:
-            sizes.update(loss=ns * 4, out=fr * p.n_out)
-        self.addr, self.size, off = {}, sizes, 0
-        for k, n in sizes.items():
-            self.addr[k] = (1 << 40) + off
-            off += (2 * max(n, 16) + 4095) // 4096 * 4096
-
-    def args(self, **over):
-        a = empty_args(self.loss)
-        for k, v in self.addr.items():
-            if k != "state_out":
-                setattr(a, k, v if self.size[k] else None)
-        a.workspace_bytes = self.ws
-        if self.loss:
-            a.grad_scale = 0.5
-        for k, v in over.items():
-            setattr(a, k, v)
-        return a
-
-    def run(self, a, T=None, B=None, state_out="given", ns=None, rows=None, row0=None):
-        so = self.addr["state_out"] if state_out == "given" else state_out
-        return run_fn(self.loss)(self.p._h, ctypes.byref(a), self.ns if ns is None else ns, self.rows if rows is None else rows,
-                                 self.row0 if row0 is None else row0, self.T if T is None else T, self.B if B is None else B, so, None)
-
-
-def invalid(rc, word):
-    return rc == C.FZ_E_INVALID and word in C.last_error()
-
-
 @pytest.mark.parametrize("loss", [False, True])
 @pytest.mark.parametrize("name", ["biquad_comb17", "two_out_fb"])
 def test_argument_checks_fail_one_by_one_with_their_reason(name, loss):
     p = S.prog(name)                                              # inputs, outputs, a deep line, a per-stream coefficient
     assert p.n_in and p.n_out and p.n_param
-    b = FakeBufs(p, 1000, 36, 8, loss, rows=48, row0=4)
+    b = FakeCall(p, 1000, 36, ring=True, loss=loss, window=(48, 4), recording=8)
     assert b.ws == (5 * p.n_state) * 4000 + p.ring_grad_workspace_bytes(1000, 8)
     ybar = "target" if loss else "out_grad"
     a0 = b.args()
@@ -384,7 +317,7 @@ def test_argument_checks_fail_one_by_one_with_their_reason(name, loss):
     assert invalid(b.run(b.args(), T=1 << 31, rows=0, row0=0), "2^31")
     # the order of run_recording: the scope, the length, then the arguments
     assert invalid(b.run(b.args(in_=None), T=1 << 31), "2^31")
-    big = FakeBufs(p, 1, 4, 0, loss)
+    big = FakeCall(p, 1, 4, ring=True, loss=loss, window=(None, 0), recording=0)
     assert big.run(big.args(), ns=1 << 30) == C.FZ_E_UNSUPPORTED and "2^30" in C.last_error()
     # an empty recording is FZ_OK and needs no buffer, but a bad struct_size is refused even then
     empty = empty_args(loss)
@@ -407,7 +340,7 @@ def test_argument_checks_fail_one_by_one_with_their_reason(name, loss):
 
 
 # ---- every kernel's name is the pinned one: tests/golden/adjoint_code_pins.json, held by test_adjoint_code_pins_host.py -----------------
-PINS = json.load(open(os.path.join(HERE, "golden", "adjoint_code_pins.json")))
+PINS = code_pins()
 
 
 def test_the_pinned_names_are_still_produced():
@@ -427,13 +360,6 @@ def test_the_pinned_names_are_still_produced():
 
 
 # ---- the kernel manifest of the GPU tests ----------------------------------------------------------------------------------------------
-def build_manifest(path, env_extra=None):
-    env = dict({k: v for k, v in os.environ.items() if k != "FLOWZ_HIP_MANIFEST"}, **(env_extra or {}))
-    out = subprocess.check_output([sys.executable, "-c", "import sys\nsys.path.insert(0, %r)\nfrom zignal_amd import flowz as F\nprint(F.manifest_build(%r))"
-                                   % (os.path.dirname(HERE), str(path))], env=env, text=True)
-    return eval(out.strip().splitlines()[-1])
-
-
 def test_the_committed_manifest_holds_exactly_the_kernels_the_gpu_tests_launch():
     recs = S.manifest_variants(S.MANIFEST)
     progs = [S.prog(n) for n in NAMES]
@@ -450,7 +376,7 @@ def test_the_committed_manifest_holds_exactly_the_kernels_the_gpu_tests_launch()
     forward = [v for v in recs if not v[3] & ADJOINT]
     assert all(not (v[3] & (ADJOINT_LOSS | ADJOINT_RING | STATES)) for v in forward)
     assert len(recs) == len(set(recs)) == 10 * len(NAMES) + len(forward) <= 120
-    counts = build_manifest(S.MANIFEST)
+    counts = replay(S.MANIFEST)
     assert counts["failed"] == 0 and counts["records"] == len(recs), counts
 
 
@@ -461,28 +387,19 @@ def test_a_manifest_cannot_ask_for_a_states_kernel_the_recording_would_not_make(
     U, R_, block = S.geometry(p)
     recipe = next(v[4] for v in S.manifest_variants(S.MANIFEST) if v[:4] == (R_, U, block, BITS))
 
-    def recipe_of(sexpr):
-        buf = ctypes.create_string_buffer(1 << 16)
-        n = C.lib.fz_expr_recipe(F.from_sexpr(sexpr)._h, buf, 1 << 16)
-        return b"typed 0\n" + buf.raw[:n]
     plain, refused = recipe_of(GG.SUPPORTED["integrator"]()), recipe_of(RG.six_lines_256())
     bad = [(R_, U, 256 if block != 256 else 128, BITS, recipe), (R_, U, 64 if block != 64 else 128, BITS, recipe), (R_, U, 512, BITS, recipe),
            (R_ // 2, U, block, BITS, recipe), (2 * R_, U, block, BITS, recipe), (1, U, block, BITS, recipe),
            (R_, U // 2, block, BITS, recipe), (R_, 2 * U, block, BITS, recipe), (R_, 0, block, BITS, recipe),
            (R_, U, block, BITS | ADJOINT_LOSS, recipe), (R_, U, block, BITS | 256, recipe),
            (32, 8, 256, BITS, plain), (4, 4, 64, BITS | ADJOINT_LOSS, plain), (8, 8, 64, BITS, refused)]
-    path = tmp_path / "bad.fzm"
-    with open(path, "wb") as f:
-        for P, u, blk, bits, rec in bad:
-            f.write(b"FZM1 %d %d %d %d %d\n" % (P, u, blk, bits, len(rec)) + rec)
-    counts = build_manifest(path, {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
+    write_manifest(tmp_path / "bad.fzm", bad)
+    counts = replay(tmp_path / "bad.fzm", {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
     assert counts["failed"] == len(bad) and counts["built"] == 0 and counts["at_hand"] == 0, counts
-    good = tmp_path / "good.fzm"
-    with open(good, "wb") as f:
-        f.write(b"FZM1 %d %d %d %d %d\n" % (R_, U, block, BITS, len(recipe)) + recipe)
-    counts = build_manifest(good, {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
+    write_manifest(tmp_path / "good.fzm", [(R_, U, block, BITS, recipe)])
+    counts = replay(tmp_path / "good.fzm", {"FLOWZ_HIP_CACHE": str(tmp_path / "cache")})
     assert counts["failed"] == 0 and counts["built"] == 1, counts
-    assert len([f for f in os.listdir(tmp_path / "cache") if f.endswith(".hsaco")]) == 1
+    assert len(code_objects(tmp_path / "cache")) == 1
 
 
 # ---- the restatement on transposed arrays ----------------------------------------------------------------------------------------------
