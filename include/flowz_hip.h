@@ -699,6 +699,54 @@ long fz_program_ring_loss_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_
 long fz_program_ring_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
 int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
 
+/* fz_run_block_far_grad, fz_run_block_far_loss_grad -- the two one-launch calls for graphs with delay lines DEEPER THAN 256 SAMPLES
+ * (echoes, reverb combs, low plucked strings), whose rings live in HBM: a call family next to the fz_run_block_ring_grad family, as
+ * that one stands next to fz_run_block_grad.  fz_grad_args and fz_loss_grad_args are taken unchanged; time-major frames only.
+ *
+ * THE CONTRACT.  Rules 1 - 4 of the ORDER OF OPERATIONS of fz_run_block_grad do not mention depth, and THE RULE of
+ * fz_run_block_loss_grad applies as written: the bits are defined.  What is new is where a far line's adjoints lie in the caller's
+ * state rows.  The `depth` state rows of such a line are ring slots and one more row holds the phase p (fz_program_lines): the value
+ * u[q] of the line's source sits in slot (p0 + q) mod D for every position q, negative ones included, with p0 the phase before the
+ * block -- before the block and, the phase being p0 + T then, after it.  Hence:
+ *   state_grad, state0_grad: row row0 + k of a far line is the adjoint of SLOT k of the state after the block (state_grad) and before
+ *     it (state0_grad).  The kernel's adjoint ring is loaded from state_grad and stored to state0_grad by the identity map, without a
+ *     permutation, so state0_grad of block 2 passed as state_grad of block 1 gives the bits of one block of 2T, also where a block is
+ *     shorter than the line.  The phase row of state_grad is never read; the phase row of state0_grad is written +0.0f.
+ *   the phase is taken from `state` as the forward takes it -- uniform over the streams, the first active lane's value per wave -- and
+ *     reduced modulo D: whatever the row holds, no access leaves the line's rows.
+ * The bits do not depend on the checkpoint stride, the path (below), the lanes per workgroup or the stream count.
+ *
+ * Scope (fz_program_far_grad_check): fz_program_ring_grad_check's, plus float delay lines deeper than 256 samples.  Still refused,
+ * with the reasons they have there: typed programs, float64 nodes, complex wires, modulators, LDS rings that fit no workgroup.  For a
+ * graph without a far line these calls ARE the fz_..._ring_ calls: the same kernel, symbol, workspace and bits.  Every other call of
+ * the backward keeps refusing a graph with a far line.
+ *
+ * The kernel, fz_adjoint_far_kernel_c<C>b<lanes>_g<tag> (fz_adjoint_far_loss_kernel_... under the loss): register lines and LDS ring
+ * lines are what they are in the ring kernel.  Of a far line the forward sweep writes the source's value of every row into the tape
+ * (the far lines are further tape lines) and reads its delayed values back from the tape rows it wrote -- for t < d from the caller's
+ * slot (p0 + t - d) mod D.  STATIC RULE 1: a far read at least C rows old is requested with its chunk's x rows; a younger one is a
+ * load of its own in front of its row.  The pending adjoints live in an adjoint ring in the workspace, one coalesced row per slot.
+ * STATIC RULE 2: when every far read is at least C rows old and any two reads of one far line are at least C apart, no slot is touched
+ * twice within a chunk: the chunk's slots are requested together with its x and tape rows, added to in registers and stored once
+ * (the fast path: echoes, combs).  Otherwise every row loads, adds and stores in program order (the per-row path: a dependent memory
+ * round trip per row).  The far lines use no LDS; lanes per workgroup: the ring rule's answer for the LDS ring lines alone, 256
+ * without any.  C: checkpoint_rows, or for 0 the library default -- 16, halved while
+ * C * (n_register_state + n_in + n_ring_reads + n_far_reads + (n_far_lines + n_far_reads)) exceeds 64: the ring rule with the far
+ * reads among the ring reads, plus the slots a row of the fast path keeps in registers.
+ * Workspace: (ceil(n_samples / C) * n_register_state + n_samples * (n_ring_lines + n_far_lines) + sum of the far depths) * n_streams
+ * * 4 bytes; fz_program_far_grad_workspace answers it.  Checks: those of fz_run_block_grad / fz_run_block_loss_grad, in their order,
+ * before a device is needed; a short workspace names fz_program_far_grad_workspace. */
+int fz_program_far_grad_check(const fz_program* p);
+int fz_program_far_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_samples, uint32_t checkpoint_rows, uint64_t* bytes);
+int fz_program_far_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out);
+long fz_program_far_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+long fz_program_far_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+int fz_run_block_far_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
+int fz_program_far_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows, fz_kernel_resources* out);
+long fz_program_far_loss_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+long fz_program_far_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
+int fz_run_block_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
+
 /* fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major -- the two one-launch calls of the
  * fz_run_block_ring_grad family on STREAM-MAJOR buffers.  The args structs are taken unchanged.
  *

@@ -68,7 +68,16 @@ The two legs must agree bit for bit -- dL/dx, the state gradient, the loss -- be
 than the route beyond the route's own spread says so.  The table goes to stdout and to profiles/r16/ring_sm_recording.txt (the --loss table
 is appended to it).
 
-usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings]
+--far: the forward / backward table for graphs with delay lines deeper than 256 samples, run_block against run_block_far_grad
+(fz_run_block_far_grad: the far adjoint kernel, rings in HBM) with every gradient and the default checkpoint stride -- workloads.far_comb
+(300 samples), a 2000-sample comb and far_tap1 (~(0.4*_1[_300] + 0.3*_1[_1] + 0.2*_1[_20] + _2): the per-row path) -- and next to them, in
+the same run, the LDS ring kernel on ~(0.5 * _1[_256] + _2), the nearest yardstick.  1 048 576 x 1024 and 65 536 x 4096, time-major; the
+method of --rings (one process, legs interleaved, medians of 2 x --steps HIP-event timings per leg).  Before a time is printed the backward
+at the default stride agrees bit for bit with the one at C = 1 (another chunking, and for far_tap1 the other path).  HBM traffic by the
+formula of DESIGN.md 9.11 (counted from the code, not measured) as a fraction of 8 TB/s.  There is no pass mark.  The table goes to stdout
+and to profiles/r17/far_grad.txt.
+
+usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings] [--far]
        (--rings takes --layout compare, alone or with --loss; --rings --recording takes --layout stream-major|compare, alone or with --loss)
 """
 import argparse
@@ -421,6 +430,98 @@ def rings_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
+def _comb(depth):
+    return lambda: W.fb(W.add(W.mul(W.lit(0.5), W.DEL(1, depth)), W.IN(2)))
+
+
+FAR_GRAPHS = {"far_comb": W.far_comb, "comb2000": _comb(2000),
+              "far_tap1": lambda: W.fb(W.add(W.add(W.add(W.mul(W.lit(0.4), W.DEL(1, 300)), W.mul(W.lit(0.3), W.DEL(1, 1))), W.mul(W.lit(0.2), W.DEL(1, 20))), W.IN(2))),
+              "comb256": _comb(256)}
+
+
+def far_bench(a, torch):
+    """forward against the far backward of graphs with delay lines in HBM, and the LDS ring kernel on a 256-sample comb next to them,
+    interleaved in one process"""
+    import time
+    lines = []
+
+    def say(line):
+        print(line, flush=True)
+        lines.append(line)
+    props = torch.cuda.get_device_properties(0)
+    say(f"# command: tools/grad_bench.py --far --steps {a.steps} --legs {a.legs}")
+    say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
+    say("# fwd = run_block (library default plan); bwd = run_block_far_grad, every gradient, default checkpoint stride; time-major frames;")
+    say(f"# HIP events, {a.steps} launches per leg and pass, a forward and a backward pass over the legs; spread = max - min of the forward's own repeats;")
+    say("# the backward at the default stride agrees bit for bit with the one at C = 1 (dL/dx, the state gradient) before a time is printed;")
+    say("# bytes per stream-sample: fwd 4 (n_in + n_out + n_far_lines + n_far_reads); bwd 4 (3 n_in + n_out) + 8 n_register_state / C")
+    say("#   + 4 (n_ring_lines + n_far_lines) + 4 n_ring_reads + 8 n_far_reads (values) + 4 n_far_lines + 8 n_far_reads - 4 n_full_depth_reads (adjoint ring;")
+    say("#   the per-row path stores rule 2's reset as well: + 4 n_far_lines),")
+    say("#   + 16 (sum of the far depths) / T once per block -- counted from the code")
+    say(f"{'graph':16s} {'streams x T':>16s} {'fwd ms':>9s} {'spread':>7s} {'bwd ms':>9s} {'bwd/fwd':>8s} {'fwd /8TB/s':>10s} {'bwd /8TB/s':>10s} {'C':>3s} {'path':>7s} {'vgprs':>6s} {'sgpr spills':>11s} {'lds':>6s}  adjoint kernel")
+    shapes = SHAPES["large"] + SHAPES["small"] if a.legs == "all" else SHAPES[a.legs]
+    for ns, T in shapes:
+        x = torch.empty((T, ns, 1), dtype=torch.float32, device="cuda")
+        F.synth_fill(x, seed=W.SEED)
+        gy = torch.empty_like(x)
+        F.synth_fill(gy, seed=W.SEED + 1)
+        y = torch.empty_like(x)
+        for name, fn in FAR_GRAPHS.items():
+            prog = F.compile(F.from_sexpr(fn()))
+            s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+            st = s0.clone()
+
+            def fwd():
+                st.copy_(s0)
+                prog.run_block(x, state=st, out=y)
+
+            def bwd(c=0):
+                return prog.run_block_far_grad(x, gy, s0, None, state_grad=s0, checkpoint_rows=c)
+            fwd()                                              # JIT, allocator; and the two strides agree bit for bit
+            r0 = bwd()
+            r1 = bwd(1)
+            torch.cuda.synchronize()
+            for key in ("x", "state"):
+                assert torch.equal(r0[key].view(torch.int32), r1[key].view(torch.int32)), f"{name} {ns} x {T}: {key} at the default stride and at C = 1 differs"
+            del r0, r1
+            torch.cuda.empty_cache()
+            legs = {"fwd": fwd, "bwd": bwd}
+            t_end = time.time() + 0.1
+            while time.time() < t_end:                          # at least 100 ms of the yardstick before the first timing
+                fwd()
+                torch.cuda.synchronize()
+            got = {k: [] for k in legs}
+            for order in (list(legs), list(legs)[::-1]):
+                for k in order:
+                    got[k] += samples(legs[k], a.steps, torch)
+            med = {k: float(np.median(v)) for k, v in got.items()}
+            res, src = prog.far_grad_resources(), prog.far_grad_source()
+            C = res["unroll"]
+            depth = dict(prog.lines())
+            depths = list(depth.values())
+            n_reg, n_rl, n_fl = sum(d for d in depths if d <= 8), sum(1 for d in depths if 8 < d <= 256), sum(1 for d in depths if d > 256)
+            reads = {(a_, b_) for k, a_, b_, _ in prog.ir() if k == "delay"}
+            n_rr = sum(1 for a_, _ in reads if 8 < depth[a_] <= 256)
+            n_fr, n_full = sum(1 for a_, _ in reads if depth[a_] > 256), sum(1 for a_, b_ in reads if depth[a_] > 256 and b_ == depth[a_])
+            far_slots = sum(d for d in depths if d > 256)
+            fbytes = 4.0 * ns * T * (prog.n_in + prog.n_out + n_fl + n_fr)
+            path = "-" if not n_fl else "fast" if "#define FZ_FAR_FAST 1 " in src else "per-row"
+            bbytes = ns * T * (4.0 * (3 * prog.n_in + prog.n_out) + 8.0 * n_reg / C + 4.0 * (n_rl + n_fl) + 4.0 * n_rr + 8.0 * n_fr
+                               + 4.0 * n_fl * (2 if path == "per-row" else 1) + 8.0 * n_fr - 4.0 * n_full) + 16.0 * far_slots * ns
+            say(f"{name:16s} {f'{ns} x {T}':>16s} {med['fwd']:9.3f} {max(got['fwd']) - min(got['fwd']):7.3f} {med['bwd']:9.3f} {med['bwd'] / med['fwd']:8.2f} "
+                f"{fbytes / (med['fwd'] / 1e3) / HBM:10.3f} {bbytes / (med['bwd'] / 1e3) / HBM:10.3f} {C:3d} {path:>7s} {res['vgprs'] + res['agprs']:6d} {res['sgpr_spills']:11d} "
+                f"{res['lds_bytes']:6d}  {prog.far_grad_kernel_symbol()}")
+            say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
+            del s0, st
+            torch.cuda.empty_cache()
+        del x, gy, y
+        torch.cuda.empty_cache()
+    out = os.path.join(ROOT, "profiles", "r17", "far_grad.txt")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def rings_compare_bench(a, torch):
     """the ring backward on stream-major buffers (plain, or with a.loss under the squared-error loss) against transpose + the time-major
     ring call + transpose, interleaved in one process; the two legs agree bit for bit before a time is printed"""
@@ -762,10 +863,13 @@ def main():
     ap.add_argument("--loss", action="store_true", help="the fused squared-error backward against forward + torch MSE + backward, both layouts")
     ap.add_argument("--recording", action="store_true", help="the backward of a whole recording against the one-launch call and blocks chained by hand")
     ap.add_argument("--rings", action="store_true", help="forward against the ring backward of graphs with delay lines deeper than 8 samples; with --loss: their fused squared-error backward against the route; with --recording: the backward of a whole recording of them")
+    ap.add_argument("--far", action="store_true", help="forward against the far backward of graphs with delay lines deeper than 256 samples, the LDS ring kernel on a 256-sample comb next to them")
     a = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
+    if a.far:
+        return far_bench(a, torch)
     if a.rings and a.recording and a.layout != "time-major":
         return rings_recording_sm_bench(a, torch)
     if a.rings and a.recording:

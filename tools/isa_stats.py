@@ -13,6 +13,10 @@ usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par
        tools/isa_stats.py ringlossgrad [graph] [--layout stream-major]
                                                            the same line for the kernel of fz_run_block_ring_loss_grad, next to the plain
                                                            ring kernel's figures (graph: also a name of tests/ring_loss_graphs.py)
+       tools/isa_stats.py fargrad [graph]                  the same lines for the kernel of fz_run_block_far_grad (delay lines deeper than
+                                                           256 samples, rings in HBM), with the path its static rule picks (graph: a name
+                                                           of tests/far_grad_graphs.py, comb2000, or any ringgrad graph)
+       tools/isa_stats.py farlossgrad [graph]              the same for the kernel of fz_run_block_far_loss_grad, next to the plain far kernel
        tools/isa_stats.py ringstates [graph] [--layout stream-major]
                                                            the block-start-states kernel of fz_run_recording_ring_grad next to the ring
                                                            adjoint kernel: registers, spills, scratch, LDS bytes, and the ds_* and
@@ -40,7 +44,8 @@ GRAPHS = {"cascade6": lambda: G.df1_cascade(6), "par4": G.par4_sum, "par4f": G.p
           "tanh": lambda: ("tanh", G.IN(1)), "exp": lambda: ("exp", G.IN(1)), "sqrt": lambda: ("sqrt", G.IN(1)), "min": lambda: ("min", G.IN(1), G.lit(0.5)),
           "sin": lambda: ("sin", G.IN(1)), "cos": lambda: ("cos", G.IN(1)), "log": lambda: ("log", G.IN(1)),
           "wire": lambda: G.IN(1), "cascade_params6": lambda: G.df1_cascade_params(6),
-          "comb256": lambda: G.fb(G.add(G.mul(G.lit(0.5), G.DEL(1, 256)), G.IN(2)))}
+          "comb256": lambda: G.fb(G.add(G.mul(G.lit(0.5), G.DEL(1, 256)), G.IN(2))),
+          "comb2000": lambda: G.fb(G.add(G.mul(G.lit(0.5), G.DEL(1, 2000)), G.IN(2)))}
 
 
 def valu_count(expr, P, U=1, block=256, flags=0):
@@ -86,16 +91,21 @@ def states_line(name, sm):
             f"{r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills, {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS")
 
 
-def ring_grad_lines(name, loss=False, sm=False):
+def ring_grad_lines(name, loss=False, sm=False, far=False):
     """the ring adjoint kernel at the default stride C, and its ds_* / vector-memory instructions per row of a chunk: the difference of
     the kernels at C and C / 2 over C / 2 rows -- both sweeps unroll a chunk, everything outside the chunks cancels.
     loss: the kernel of fz_run_block_ring_loss_grad, with the plain ring kernel's registers and spills next to its own.
     sm: the kernels for stream-major buffers (their per-row ds_* include the row's frames read from and written to the LDS patch; the
-    patch fetch and flush are outside the chunks and cancel)"""
+    patch fetch and flush are outside the chunks and cancel)
+    far: the kernels of the far family (fz_run_block_far_grad, fz_run_block_far_loss_grad; time-major only), with the path of sweep 2"""
+    import far_grad_graphs as FG
     import ring_loss_graphs as RL
-    build = RL.GRAPHS.get(name) or GRAPHS[name]
+    build = (FG.FARS.get(name) if far else None) or RL.GRAPHS.get(name) or GRAPHS[name]
     p = F.compile(F.from_sexpr(build()))
-    resources = (lambda q, c=0: q.ring_loss_grad_resources(c, stream_major=sm)) if loss else (lambda q, c=0: q.ring_grad_resources(c, stream_major=sm))
+    if far:
+        resources = (lambda q, c=0: q.far_loss_grad_resources(c)) if loss else (lambda q, c=0: q.far_grad_resources(c))
+    else:
+        resources = (lambda q, c=0: q.ring_loss_grad_resources(c, stream_major=sm)) if loss else (lambda q, c=0: q.ring_grad_resources(c, stream_major=sm))
     r = resources(p)
     C = r["unroll"]
 
@@ -118,11 +128,18 @@ def ring_grad_lines(name, loss=False, sm=False):
             os.environ.pop("FLOWZ_HIP_CACHE", None)
         else:
             os.environ["FLOWZ_HIP_CACHE"] = old
-    plain = p.ring_grad_resources(0, stream_major=sm) if loss else None
-    sym = p.ring_loss_grad_kernel_symbol(0, stream_major=sm) if loss else p.ring_grad_kernel_symbol(0, stream_major=sm)
+    if far:
+        plain = p.far_grad_resources(0) if loss else None
+        sym = p.far_loss_grad_kernel_symbol(0) if loss else p.far_grad_kernel_symbol(0)
+        src = p.far_grad_source(0)
+        sym += " (" + ("no far line" if "FZ_FAR_FAST" not in src else "fast path" if "#define FZ_FAR_FAST 1 " in src else "per-row path") + ")"
+    else:
+        plain = p.ring_grad_resources(0, stream_major=sm) if loss else None
+        sym = p.ring_loss_grad_kernel_symbol(0, stream_major=sm) if loss else p.ring_grad_kernel_symbol(0, stream_major=sm)
+    kin = "plain far" if far else "plain ring"
     out = [f"{name} {sym}: C {C}, {r['vgprs'] + r['agprs']} VGPRs"
-           + (f" (plain ring {plain['vgprs'] + plain['agprs']})" if loss else "") + f", {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills"
-           + (f" (plain ring {plain['vgpr_spills']} / {plain['sgpr_spills']})" if loss else "") + f", {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS",
+           + (f" ({kin} {plain['vgprs'] + plain['agprs']})" if loss else "") + f", {r['vgpr_spills']} VGPR / {r['sgpr_spills']} SGPR spills"
+           + (f" ({kin} {plain['vgpr_spills']} / {plain['sgpr_spills']})" if loss else "") + f", {r['scratch_bytes']} B scratch, {r['lds_bytes']} B LDS",
            "  in the kernel: " + ", ".join(f"{v} {k}" for k, v in whole.items())]
     if half:
         out.append("  per row (both sweeps): " + ", ".join(f"{(whole[k] - half[k]) / (C - C // 2):.2f} {k}" for k in whole))
@@ -184,6 +201,9 @@ def main():
         return
     if a and a[0] == "ringlossgrad":
         print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring", loss=True, sm=sm)))
+        return
+    if a and a[0] in ("fargrad", "farlossgrad"):
+        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "far_comb", loss=a[0] == "farlossgrad", far=True)))
         return
     if a and a[0] == "states":
         print(states_line(a[1] if len(a) > 1 else "cascade_params6", len(a) > 2 and a[2] == "sm"))

@@ -12,6 +12,11 @@ time-major frames, the backward is Program.run_block_ring_grad (include/flowz_hi
 run_rings(..., stream_major=True) takes the stream-major tensors of run(..., stream_major=True): the forward is
 Program.run_block_stream_major, the backward Program.run_block_ring_grad_stream_major, and nothing is transposed.
 
+run_far(prog, x, state, params, consts) is run_rings() for graphs with delay lines deeper than 256 samples as well (echoes, reverb
+combs, low plucked strings), whose rings live in HBM: time-major frames only, the backward is Program.run_block_far_grad
+(include/flowz_hip.h: fz_run_block_far_grad).  The rows of such a line in `state` are ring slots and one more row holds the phase: a
+zero state has phase 0, and the state gradient's phase rows are zero.  run_rings() keeps refusing such graphs.
+
 mse(prog, x, target, ...) is the mean squared error of one block against a target as ONE launch (Program.run_block_loss_grad:
 the adjoint kernel forms y, the error and dL/dy itself), where run() followed by ((y - target) ** 2).mean() is a forward launch,
 several elementwise kernels and the backward launch.
@@ -19,6 +24,8 @@ several elementwise kernels and the backward launch.
 mse_rings(prog, x, target, ...) is mse() for every graph run_rings() takes, time-major (Program.run_block_ring_loss_grad: the ring
 adjoint kernel with the loss formed in it); mse() keeps refusing graphs with delay lines deeper than 8 samples.
 mse_rings(..., stream_major=True) is the same on stream-major tensors (Program.run_block_ring_loss_grad_stream_major).
+
+mse_far(prog, x, target, ...) is mse_rings() for every graph run_far() takes, time-major (Program.run_block_far_loss_grad).
 
 mse_recording(prog, x, target, ...) is the same loss over a whole recording of many blocks in bounded workspace
 (Program.run_recording_loss_grad: one forward launch that keeps the state before every block, then the loss kernel block by block
@@ -47,8 +54,12 @@ def _apply_consts(prog: Program, consts):
 
 
 def _front_door(prog: Program, x, consts, rings):
-    """the checks every public function starts with, in this order: the graph is supported, 2-D frames have one input wire, consts fit"""
-    if rings:
+    """the checks every public function starts with, in this order: the graph is supported, 2-D frames have one input wire, consts fit.
+    rings: False (the plain family), True (the ring family) or "far" (the far family)"""
+    if rings == "far":
+        if not prog.far_grad_supported():
+            raise FlowzError(C.FZ_E_UNSUPPORTED, prog.far_grad_unsupported_reason())
+    elif rings:
         if not prog.ring_grad_supported():
             raise FlowzError(C.FZ_E_UNSUPPORTED, prog.ring_grad_unsupported_reason())
     elif not prog.grad_supported():
@@ -62,7 +73,7 @@ def _front_door(prog: Program, x, consts, rings):
 
 def _backward_call(prog: Program, rings, stream_major, loss=False, recording=False):
     """the bound Program method of one corner of the backward family"""
-    name = ("run_recording_" if recording else "run_block_") + ("ring_" if rings else "") + ("loss_grad" if loss else "grad")
+    name = ("run_recording_" if recording else "run_block_") + ("far_" if rings == "far" else "ring_" if rings else "") + ("loss_grad" if loss else "grad")
     # (the plain recording calls take the layout as a keyword; every other stream-major corner is a method of its own)
     return getattr(prog, name + ("_stream_major" if stream_major and (rings or not recording) else ""))
 
@@ -144,6 +155,15 @@ def run_rings(prog: Program, x, state=None, params=None, consts=None, stream_maj
     return _run(prog, x, state, params, consts, stream_major, True)
 
 
+def run_far(prog: Program, x, state=None, params=None, consts=None):
+    """run_rings() for graphs with delay lines deeper than 256 samples -- and every graph run_rings() takes --, time-major frames only:
+    returns (y [T, n_streams, n_out], state after the block).  The forward is Program.run_block, the backward
+    Program.run_block_far_grad.  The rows of a line deeper than 256 samples are ring slots in `state` and in its gradient, and the
+    line's phase row (behind all line rows) is 0 in a zero state and has a zero gradient.  Chaining it over consecutive blocks
+    back-propagates through time across them: the state after a block carries the phase the next block starts from."""
+    return _run(prog, x, state, params, consts, False, "far")
+
+
 class _Mse(torch.autograd.Function):
     """the loss of one block, or (block_rows not None) of a whole recording, which also returns the state after it"""
 
@@ -195,6 +215,14 @@ def mse_rings(prog: Program, x, target, state=None, params=None, consts=None, st
     (Program.run_block_ring_loss_grad_stream_major)."""
     _front_door(prog, x, consts, True)
     return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), True, None)
+
+
+def mse_far(prog: Program, x, target, state=None, params=None, consts=None):
+    """mse_rings() for graphs with delay lines deeper than 256 samples -- and every graph mse_rings() takes --, time-major frames only:
+    the scalar ((y - target) ** 2).mean() of one block, differentiable in x, state, params and consts.  One launch, made in the forward
+    (Program.run_block_far_loss_grad, include/flowz_hip.h: fz_run_block_far_loss_grad); backward() applies the upstream scalar."""
+    _front_door(prog, x, consts, "far")
+    return _Mse.apply(prog, x, target, state, params, consts, False, "far", None)
 
 
 def mse_recording(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0, stream_major=False):

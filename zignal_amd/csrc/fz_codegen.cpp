@@ -29,6 +29,7 @@ extern const char* const kSkeletonAdjoint;       // fz_kernel_adjoint.hip.inc: a
 extern const char* const kSkeletonAdjointSm;
 extern const char* const kSkeletonAdjointRing;
 extern const char* const kSkeletonAdjointRingSm;
+extern const char* const kSkeletonAdjointFar;    // fz_kernel_adjoint_far.hip.inc: delay lines deeper than 256 samples, rings in HBM
 extern const char* const kSkeletonStates;        // fz_kernel_states.hip.inc: plain and, with FZ_RING, ring
 extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: the same
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
@@ -39,7 +40,7 @@ extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the 
 // text and "_loss" in the symbol, fz_<head>[_loss]<tail>_kernel_<c|u><U>[r<P>]b<block>.  The states rows' text is chosen by the layout
 // alone: the ring is FZ_RING in its configuration.
 struct AdjointRow {
-   uint32_t bits;               // of FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM
+   uint32_t bits;               // of FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_FAR
    const char *head, *tail;     // of the symbol's stem
    std::string text;            // the hand-written kernel
    bool patch_rows;             // the symbol carries r<P>: the rows of the LDS patch of the stream-major frames
@@ -51,13 +52,14 @@ static const AdjointRow& adjoint_row(const Variant& v)
       {FZ_VF_ADJOINT_SM, "fz_adjoint", "_sm", kSkeletonAdjointSm, true},
       {FZ_VF_ADJOINT_RING, "fz_adjoint_ring", "", kSkeletonAdjointRing, false},
       {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_adjoint_ring", "_sm", kSkeletonAdjointRingSm, true},
+      {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, "fz_adjoint_far", "", kSkeletonAdjointFar, false},
       {FZ_VF_STATES, "fz_states", "", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_SM, "fz_states", "_sm", kSkeletonStatesSm, true},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_states", "_ring_sm", kSkeletonStatesSm, true},
    };
    for (const AdjointRow& r : rows)
-      if (r.bits == (v.flags & (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM)) && !((v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_LOSS))) return r;
+      if (r.bits == (v.flags & (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_FAR)) && !((v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_LOSS))) return r;
    fail(FZ_E_INVALID, "internal: no kernel of the adjoint family has the flags " + std::to_string(v.flags));
 }
 
@@ -779,7 +781,8 @@ static std::string gen_body_waves(const Graph& g, uint32_t W)
 
 std::string gen_body(const Graph& g, const Variant& v)
 {
-   if (v.flags & FZ_VF_ADJOINT) return gen_adjoint_body(g, (v.flags & FZ_VF_ADJOINT_LOSS) != 0, (v.flags & FZ_VF_ADJOINT_RING) != 0);
+   if (v.flags & FZ_VF_ADJOINT)
+      return gen_adjoint_body(g, (v.flags & FZ_VF_ADJOINT_LOSS) != 0, (v.flags & FZ_VF_ADJOINT_RING) != 0, !(v.flags & FZ_VF_ADJOINT_FAR) ? 0 : far_fast_path(g, v.U) ? 2 : 1);
    if (const uint32_t W = ws_parts(v.flags)) return gen_body_waves(g, W);
    if (v.flags & FZ_VF_STAGE_PACK) return gen_body_skew(g, g.split);
    return gen_body_frames(g, v);
@@ -1097,6 +1100,19 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
       table("fz_rl_slot0", rl.n_rl(), [&](size_t i) { return rl.rl_slot0[i]; }, "per ring line: its first LDS slot");
       table("fz_rr_line", rl.n_rr(), [&](size_t i) { return rl.reads[i].first; }, "per ring read: its ring line");
       table("fz_rr_delay", rl.n_rr(), [&](size_t i) { return rl.reads[i].second; }, "per ring read: its delay in samples");
+      if (v.flags & FZ_VF_ADJOINT_FAR) {
+         o << "#define FZ_NFL " << rl.n_fl() << "   // far lines: delay lines deeper than " << kLdsMaxDepth << " samples, rings in HBM\n";
+         o << "#define FZ_NFR " << rl.n_fr() << "   // far reads: distinct (far line, delay) pairs\n";
+         o << "#define FZ_FAR_SLOTS " << rl.far_slots << "   // rows of the adjoint ring in the workspace: the sum of the far lines' depths\n";
+         o << "#define FZ_FAR_FAST " << (far_fast_path(g, v.U) ? 1 : 0) << "   // 1: no slot is touched twice within a chunk -- the pending adjoints travel with the chunk's rows\n";
+         table("fz_fl_row0", rl.n_fl(), [&](size_t i) { return g.lines[rl.fl_line[i]].row0; }, "per far line: its first state row");
+         table("fz_fl_depth", rl.n_fl(), [&](size_t i) { return g.lines[rl.fl_line[i]].depth; }, "per far line: its depth = its ring slots");
+         table("fz_fl_slot0", rl.n_fl(), [&](size_t i) { return rl.fl_slot0[i]; }, "per far line: its first row of the adjoint ring");
+         table("fz_fl_phase_row", rl.n_fl(), [&](size_t i) { return g.lines[rl.fl_line[i]].phase_row; }, "per far line: the state row of its ring phase");
+         table("fz_fr_line", rl.n_fr(), [&](size_t i) { return rl.far_reads[i].first; }, "per far read: its far line");
+         table("fz_fr_delay", rl.n_fr(), [&](size_t i) { return rl.far_reads[i].second; }, "per far read: its delay in samples");
+         table("fz_fr_chunked", rl.n_fr(), [&](size_t i) { return far_read_with_chunk(rl.far_reads[i].second, v.U) ? 1u : 0u; }, "per far read: 1 = sweep 1 requests it with the chunk's x rows");
+      }
    }
    if (v.flags & FZ_VF_STATES) {
       o << "#define FZ_RING " << ((v.flags & FZ_VF_ADJOINT_RING) ? 1 : 0) << "   // 1: the delay lines deeper than " << kRegMaxDepth << " samples keep value rings in LDS\n";
@@ -1122,12 +1138,26 @@ int RingLayout::read_index(uint32_t ring_line, uint32_t delay) const
    return -1;
 }
 
+int RingLayout::far_read_index(uint32_t far_line, uint32_t delay) const
+{
+   for (size_t i = 0; i < far_reads.size(); ++i)
+      if (far_reads[i].first == far_line && far_reads[i].second == delay) return (int)i;
+   return -1;
+}
+
 RingLayout ring_layout(const Graph& g)
 {
    RingLayout rl;
    for (size_t l = 0; l < g.lines.size(); ++l) {
       const Line& L = g.lines[l];
-      if (L.in_lds) {
+      rl.far_of_line.push_back(L.far ? (int)rl.fl_line.size() : -1);
+      if (L.far) {                                          // (neither register rows nor LDS slots: fz_kernel_adjoint_far.hip.inc)
+         rl.reg0.push_back(-1);
+         rl.ring_of_line.push_back(-1);
+         rl.fl_line.push_back((uint32_t)l);
+         rl.fl_slot0.push_back(rl.far_slots);
+         rl.far_slots += L.depth;
+      } else if (L.in_lds) {
          rl.reg0.push_back(-1);
          rl.ring_of_line.push_back((int)rl.rl_line.size());
          rl.rl_line.push_back((uint32_t)l);
@@ -1141,10 +1171,34 @@ RingLayout ring_layout(const Graph& g)
    }
    for (const Node& nd : g.nodes) {
       if (nd.kind != FZ_IR_DELAY) continue;
-      const int k = rl.ring_of_line[(size_t)g.line_of_node[nd.a]];
+      const int k = rl.ring_of_line[(size_t)g.line_of_node[nd.a]], f = rl.far_of_line[(size_t)g.line_of_node[nd.a]];
       if (k >= 0 && rl.read_index((uint32_t)k, nd.b) < 0) rl.reads.emplace_back((uint32_t)k, nd.b);
+      if (f >= 0 && rl.far_read_index((uint32_t)f, nd.b) < 0) rl.far_reads.emplace_back((uint32_t)f, nd.b);
    }
    return rl;
+}
+
+// ---- the far kernel's two static rules (their one home; fz_internal.hpp declares them, include/flowz_hip.h states them) ----------------
+// Sweep 1 reads a far line's values back from the tape rows it wrote itself.  A read at least C rows old reads a row written before
+// its chunk began, whichever row of the chunk asks: it is requested with the chunk's x rows.  A younger read is a load of its own in
+// front of its row (the forward shortens the chunk instead, below kFarMinDelay: here the chunk is the checkpoint stride and stays).
+bool far_read_with_chunk(uint32_t delay, uint32_t C) { return delay >= C; }
+
+// Sweep 2 takes the fast path when no slot of the adjoint ring is touched twice within a chunk of C rows: every far read at least C
+// rows old (its target is no row's own slot within the chunk), and any two reads of one far line at least C apart (no two rows share
+// a target).  A line's depth is its deepest read, so every other read is then at most D - C: no target wraps onto a row's own slot
+// either, and the read at the full depth finds the slot its own row just reset.
+bool far_fast_path(const Graph& g, uint32_t C)
+{
+   const RingLayout rl = ring_layout(g);
+   for (size_t i = 0; i < rl.far_reads.size(); ++i) {
+      if (rl.far_reads[i].second < C) return false;
+      for (size_t j = 0; j < i; ++j) {
+         const uint32_t a = rl.far_reads[i].second, b = rl.far_reads[j].second;
+         if (rl.far_reads[i].first == rl.far_reads[j].first && (a > b ? a - b : b - a) < C) return false;
+      }
+   }
+   return true;
 }
 
 // struct fz_adj: fwd() -- the state after one step, from the state before it and the step's frame (the forward step() of gen_body for
@@ -1161,10 +1215,25 @@ RingLayout ring_layout(const Graph& g)
 // (a read at the full depth finds the slot just reset), receive rule 3's additions in registers in its order and are stored once.
 // Without it -- every ring-free graph -- the text is byte for byte what it was.
 // loss and ring (fz_kernel_adjoint_ring.hip.inc with FZ_LOSS): out() takes rv as well -- a delayed read of a ring line is rv[read] there too.
-std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
+// far (FZ_VF_ADJOINT_FAR, fz_kernel_adjoint_far.hip.inc; always with ring): the lines in HBM are neither register rows nor LDS slots.
+// A delayed read of one is rv[n ring reads + far read], fwd() hands its source value out in u[n ring lines + far line], and bwd()
+// treats its pending adjoints as it treats a ring line's, in one of two places.  far == 1, the per-row path: the ring column is the
+// global pointer `fa` with stride `ns` (row fz_fl_slot0 + slot of the workspace ring, fpt[far line] = the slot of the row) -- load,
+// add, store in program order.  far == 2, the fast path: the kernel has requested the row's slots with the chunk's rows -- f2[far
+// line] is rule 2's slot, fq[far read] comes in as the pending adjoint the read adds into (-0.0f at the full depth: the slot just
+// reset) and goes out as what the kernel stores there.
+std::string gen_adjoint_body(const Graph& g, bool loss, bool ring, int far)
 {
    std::ostringstream o;
    const RingLayout rl = ring ? ring_layout(g) : RingLayout();
+   auto far_line = [&](size_t line) { return far ? rl.far_of_line[line] : -1; };
+   auto far_read_of = [&](const Node& nd) { return rl.far_read_index((uint32_t)far_line((size_t)g.line_of_node[nd.a]), nd.b); };
+   auto far_slot = [&](int f, uint32_t d) {                // the workspace-ring row of far line f `d` rows back
+      const uint32_t D = g.lines[rl.fl_line[(size_t)f]].depth, s0 = rl.fl_slot0[(size_t)f];
+      const std::string pt = "fpt[" + std::to_string(f) + "]";
+      const std::string q = d == 0 || d == D ? pt : "(" + pt + " >= " + std::to_string(d) + "u ? " + pt + " - " + std::to_string(d) + "u : " + pt + " + " + std::to_string(D - d) + "u)";
+      return "fa[(size_t)(" + std::to_string(s0) + "u + " + q + ") * ns]";
+   };
    // ring mode: the ring line a line is (-1: a register line), the ring read a DELAY node is, the slot of a ring line `d` rows back
    auto ring_line = [&](size_t line) { return ring ? rl.ring_of_line[line] : -1; };
    auto read_of = [&](const Node& nd) { return rl.read_index((uint32_t)ring_line((size_t)g.line_of_node[nd.a]), nd.b); };
@@ -1195,6 +1264,7 @@ std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
             case FZ_IR_PARAM: o << "p[" << nd.a << "]"; break;
             case FZ_IR_DELAY:
                if (ring_line((size_t)g.line_of_node[nd.a]) >= 0) o << "rv[" << read_of(nd) << "]";
+               else if (far_line((size_t)g.line_of_node[nd.a]) >= 0) o << "rv[" << rl.n_rr() + (uint32_t)far_read_of(nd) << "]";
                else o << "s[" << row(nd.a, nd.b) << "]";
                break;
             default: o << op_expr(nd.kind, false, [&](uint32_t k, bool) { return val(operand(nd, k)); });
@@ -1220,6 +1290,10 @@ std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
          o << "      u[" << ring_line(l) << "] = " << val(L.src) << ";\n";
          continue;
       }
+      if (far_line(l) >= 0) {
+         o << "      u[" << rl.n_rl() + (uint32_t)far_line(l) << "] = " << val(L.src) << ";\n";
+         continue;
+      }
       const uint32_t r0 = ring ? (uint32_t)rl.reg0[l] : L.row0;
       o << "      sn[" << r0 << "] = " << val(L.src) << ";\n";
       for (uint32_t a = 1; a < L.depth; ++a) o << "      sn[" << r0 + a << "] = s[" << r0 + a - 1 << "];\n";
@@ -1227,7 +1301,16 @@ std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
    o << "   }\n";
    o << "   // one step backwards: yb = dL/dy of the step, R = the pending line adjoints (the state after the step on entry, before it on\n"
         "   // return), pb / cb += this step's parameter / coefficient adjoints, xb = dL/dx of the step\n";
-   if (ring) {
+   if (far) {
+      o << "   // (ring, pt: the ring lines' pending adjoints in the lane's LDS column, the row number modulo each line's depth; the far lines':\n";
+      o << (far == 2 ? "   //  f2[far line] = the slot of the row, fq[far read] = the pending adjoint the read adds into, in and out)\n"
+                     : "   //  fa = the lane's column of the workspace ring, stride ns; fpt[far line] = the slot of the row)\n");
+      o << "   __device__ __forceinline__ static void bwd(const float* x, const float* c, const float* p, const float* s, const float* rv, const float* yb,\n"
+           "                                              float* xb, float* R, float* pb, float* cb, float* ring, const unsigned* pt, "
+        << (far == 2 ? "const float* f2, float* fq" : "float* fa, const unsigned* fpt, size_t ns") << ")\n   {\n";
+      o << "      (void)x; (void)c; (void)p; (void)s; (void)rv; (void)yb; (void)xb; (void)R; (void)pb; (void)cb; (void)ring; (void)pt; "
+        << (far == 2 ? "(void)f2; (void)fq;" : "(void)fa; (void)fpt; (void)ns;") << "\n";
+   } else if (ring) {
       o << "   // (ring: the lane's LDS column of the ring lines' pending adjoints; pt[line]: the row number modulo the line's depth)\n";
       o << "   __device__ __forceinline__ static void bwd(const float* x, const float* c, const float* p, const float* s, const float* rv, const float* yb,\n"
            "                                              float* xb, float* R, float* pb, float* cb, float* ring, const unsigned* pt)\n   {\n";
@@ -1255,6 +1338,14 @@ std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
          o << "      " << slot(ring_line(l), 0) << " = -0.0f;\n";
          continue;
       }
+      if (far_line(l) >= 0) {                              // (fast path: the kernel resets the slot when it stores the row's slots)
+         if (far == 2) o << "      " << adj(L.src) << " = " << adj(L.src) << " + f2[" << far_line(l) << "];\n";
+         else {
+            o << "      " << adj(L.src) << " = " << adj(L.src) << " + " << far_slot(far_line(l), 0) << ";\n";
+            o << "      " << far_slot(far_line(l), 0) << " = -0.0f;\n";
+         }
+         continue;
+      }
       const uint32_t r0 = ring ? (uint32_t)rl.reg0[l] : L.row0;
       o << "      " << adj(L.src) << " = " << adj(L.src) << " + R[" << r0 << "];\n";
       for (uint32_t a = 0; a + 1 < L.depth; ++a) o << "      R[" << r0 + a << "] = R[" << r0 + a + 1 << "];\n";
@@ -1265,6 +1356,16 @@ std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
       for (size_t i = 0; i < rl.reads.size(); ++i) {
          const uint32_t D = g.lines[rl.rl_line[rl.reads[i].first]].depth;
          o << "      float q" << i << "r = " << (rl.reads[i].second == D ? std::string("-0.0f") : slot((int)rl.reads[i].first, rl.reads[i].second)) << ";\n";
+      }
+   }
+   if (far) {
+      o << "      // the same for the far reads\n";
+      for (size_t i = 0; i < rl.far_reads.size(); ++i) {
+         const uint32_t D = g.lines[rl.fl_line[rl.far_reads[i].first]].depth;
+         o << "      float qf" << i << "r = ";
+         if (far == 2) o << "fq[" << i << "]";
+         else o << (rl.far_reads[i].second == D ? std::string("-0.0f") : far_slot((int)rl.far_reads[i].first, rl.far_reads[i].second));
+         o << ";\n";
       }
    }
    o << "      // 3. consumers in decreasing node order\n";
@@ -1287,6 +1388,10 @@ std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
          case FZ_IR_DELAY: {
             if (ring_line((size_t)g.line_of_node[nd.a]) >= 0) {
                o << "      q" << read_of(nd) << "r = q" << read_of(nd) << "r + " << gk << ";\n";
+               break;
+            }
+            if (far_line((size_t)g.line_of_node[nd.a]) >= 0) {
+               o << "      qf" << far_read_of(nd) << "r = qf" << far_read_of(nd) << "r + " << gk << ";\n";
                break;
             }
             const uint32_t r = row(nd.a, nd.b);
@@ -1328,6 +1433,10 @@ std::string gen_adjoint_body(const Graph& g, bool loss, bool ring)
    if (ring) {
       o << "      // the ring reads' pending adjoints back into their slots, once each\n";
       for (size_t i = 0; i < rl.reads.size(); ++i) o << "      " << slot((int)rl.reads[i].first, rl.reads[i].second) << " = q" << i << "r;\n";
+   }
+   for (size_t i = 0; far && i < rl.far_reads.size(); ++i) {
+      if (far == 2) o << "      fq[" << i << "] = qf" << i << "r;\n";
+      else o << "      " << far_slot((int)rl.far_reads[i].first, rl.far_reads[i].second) << " = qf" << i << "r;\n";
    }
    o << "      // 4. the step's input adjoints (+0 for a wire no adjoint reaches)\n";
    for (uint32_t w = 0; w < g.n_in; ++w) {

@@ -6,6 +6,8 @@
 //   fz_run_block_grad[_stream_major]                  fz_kernel_adjoint.hip.inc         fz_kernel_adjoint_sm.hip.inc
 //   fz_run_block_ring_grad[_stream_major]             fz_kernel_adjoint_ring.hip.inc    fz_kernel_adjoint_ring_sm.hip.inc
 //     (delay lines in LDS: FZ_VF_ADJOINT_RING)
+//   fz_run_block_far_grad                             fz_kernel_adjoint_far.hip.inc     (not built)
+//     (delay lines in HBM as well: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR)
 //   fz_run_recording_grad: the block-start states     fz_kernel_states.hip.inc          fz_kernel_states_sm.hip.inc
 //     (FZ_VF_STATES)
 //   fz_run_recording_ring_grad[_stream_major]:        the same text with FZ_RING        the same text with FZ_RING
@@ -13,7 +15,9 @@
 //
 // Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the four adjoint kernels forms dL/dy itself, from a
 // target: the same text with FZ_LOSS, the same C, workgroup and workspace.  The ring calls share the checks and the launch with the
-// others; for a graph without a ring line each IS its plain sibling (same Variant, kernel, symbol, workspace, bits).  The backward of a
+// others; for a graph without a ring line each IS its plain sibling (same Variant, kernel, symbol, workspace, bits).  The far calls
+// stand to the ring calls as those stand to the plain ones: for a graph without a line deeper than 256 samples each IS its ring
+// sibling; with one, the far kernel keeps the pending adjoints of such a line in a ring in the workspace.  The backward of a
 // recording is two-level checkpointing: one launch of the states kernel, then the block launches above from the last block to the first.
 #include <cmath>
 #include <algorithm>
@@ -28,14 +32,14 @@ namespace fz {
 constexpr uint32_t kGradBlock = 256;          // lanes (= streams) per workgroup of the adjoint kernel
 constexpr uint32_t kGradMaxCheckpoint = 32;   // the chunk is unrolled: every step's state and frame stay in registers
 
-std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds)
+std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds, bool rings_in_hbm)
 {
    if (g.typed) return "typed programs (fz_compile_typed) are not supported by the backward";
    if (g.n_mod) return "sample-rate modulators (fz_modulator) are not supported by the backward";
    for (uint8_t part : g.out_part)
       if (part) return "complex wires are not supported by the backward";
    for (const Line& L : g.lines) {
-      if (L.far) return "delay lines deeper than 256 samples (rings in HBM) are not supported by the backward";
+      if (L.far && !(rings_in_lds && rings_in_hbm)) return "delay lines deeper than 256 samples (rings in HBM) are not supported by the backward";
       if (L.in_lds && !rings_in_lds) return "delay lines deeper than 8 samples (rings in LDS) are not supported by the backward";
       if (L.part || L.f64) return "complex or double delay lines are not supported by the backward";
    }
@@ -53,10 +57,13 @@ std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds)
 // ring reads (for a graph without a ring line the two count the same).  Measured: no graph of tests/test_grad_host.py spills; random graphs
 // (tests/grad_fuzz_cells.py) do spill SGPRs into VGPR lanes -- one-state graphs at C = 16 as well as 72-state ones at C = 1, with two
 // coefficients as with twenty, so counting n_const here removes nothing -- and none uses scratch: correct, slower.
+// The far kernel (a graph with a line deeper than 256 samples): the far reads count among the ring reads, and a row of the fast path
+// keeps its slots of the adjoint ring as well -- one per far line (rule 2's) and one per far read (rule 3's target): per row
+// n_register_state + n_in + n_ring_reads + n_far_reads + (n_far_lines + n_far_reads), whichever path the chunk then takes.
 static uint32_t grad_default_checkpoint(const Graph& g, bool ring)
 {
    const RingLayout rl = ring ? ring_layout(g) : RingLayout{};
-   const uint32_t per_row = std::max<uint32_t>(ring ? rl.n_reg() + g.n_in + rl.n_rr() : g.n_state + g.n_in, 1);
+   const uint32_t per_row = std::max<uint32_t>(ring ? rl.n_reg() + g.n_in + rl.n_rr() + 2 * rl.n_fr() + rl.n_fl() : g.n_state + g.n_in, 1);
    uint32_t C = 16;
    while (C > 1 && C * per_row > 64) C /= 2;
    return C;
@@ -133,17 +140,18 @@ static uint32_t checkpoint_of(const Graph& g, uint32_t checkpoint_rows, bool rin
    return checkpoint_rows;
 }
 
-static void require_supported(const Graph& g, bool rings_in_lds = false)
+static void require_supported(const Graph& g, bool rings_in_lds = false, bool rings_in_hbm = false)
 {
-   const std::string why = grad_unsupported_reason(g, rings_in_lds);
+   const std::string why = grad_unsupported_reason(g, rings_in_lds, rings_in_hbm);
    if (!why.empty()) fail(FZ_E_UNSUPPORTED, why);
 }
 
 // The scope of a call, before anything else is asked of it.  ring: the call is of the ring family -- the ring scope and the ring-fit
-// refusal in fz_program_ring_grad_check's words, whichever kernel and layout the call goes on to ask for.
-static void require_scope(const Graph& g, bool ring)
+// refusal in fz_program_ring_grad_check's words, whichever kernel and layout the call goes on to ask for.  far: the call is of the far
+// family (fz_run_block_far_*) -- the ring scope plus float lines deeper than 256 samples, which take no LDS.
+static void require_scope(const Graph& g, bool ring, bool far = false)
 {
-   require_supported(g, ring);
+   require_supported(g, ring, far);
    if (!ring) return;
    const LaneLds rings{ring_layout(g).slots};
    if (!ring_sm_geometry(rings, 1, 1).block)
@@ -165,15 +173,22 @@ static uint32_t family_bits(bool ring, bool stream_major) { return (ring ? FZ_VF
 // (same kernel, symbol, workspace, bits).  With a ring line the ring kernel's C, and on stream-major buffers R and the block are chosen
 // together: R0 = grad_sm_patch_rows(g, C), Rmin = max(4, C) (multiples of 4 and of C); its patch keeps its padding whatever the wires.
 // loss: the kernel forms dL/dy itself (FZ_VF_ADJOINT_LOSS next to the family bits); C, block and workspace do not change with it.
-static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring, bool stream_major, bool loss)
+// far: the call is of the far family (a ring call as well); for a graph without a line deeper than 256 samples its Variant is the ring
+// call's.  With one: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, the far kernel's C (grad_default_checkpoint), and the workgroup the ring
+// rule gives the graph's LDS ring lines alone -- the far lines take no LDS --, 256 lanes without any.  Time-major frames only.
+static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring, bool stream_major, bool loss, bool far = false)
 {
-   require_scope(g, ring);
-   const uint32_t slots = ring ? ring_layout(g).slots : 0u, wires = g.n_in + g.n_out;
+   ring = ring || far;
+   require_scope(g, ring, far);
+   const RingLayout rl = ring ? ring_layout(g) : RingLayout{};
+   const uint32_t slots = rl.slots, wires = g.n_in + g.n_out;
+   const bool far_lines = rl.n_fl() != 0;
+   if (far_lines && stream_major) fail(FZ_E_UNSUPPORTED, "delay lines deeper than 256 samples (rings in HBM) are not supported by the backward on stream-major buffers");
    Variant v;
    v.P = 1;
-   v.U = checkpoint_of(g, checkpoint_rows, slots != 0);
+   v.U = checkpoint_of(g, checkpoint_rows, slots != 0 || far_lines);
    v.block = kGradBlock;
-   v.flags = adjoint_flags(g, family_bits(slots != 0, stream_major), loss);
+   v.flags = adjoint_flags(g, family_bits(slots != 0 || far_lines, stream_major) | (far_lines ? FZ_VF_ADJOINT_FAR : 0u), loss);
    if (slots) {
       const LaneLds lane{slots, stream_major ? wires : 0u, stream_major ? 4u : 0u};
       const uint32_t Rmin = stream_major ? std::max<uint32_t>(4u, v.U) : 1u;
@@ -235,9 +250,10 @@ static Variant states_variant(const Graph& g, bool ring, bool stream_major)
 // (the makers answer with the plain Variant), the loss next to FZ_VF_STATES.
 bool grad_variant_fits(const Graph& g, const Variant& v)
 {
-   const bool ring = v.flags & FZ_VF_ADJOINT_RING, sm = v.flags & FZ_VF_ADJOINT_SM, loss = v.flags & FZ_VF_ADJOINT_LOSS;
+   const bool ring = v.flags & FZ_VF_ADJOINT_RING, sm = v.flags & FZ_VF_ADJOINT_SM, loss = v.flags & FZ_VF_ADJOINT_LOSS, far = v.flags & FZ_VF_ADJOINT_FAR;
    try {
-      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss) : states_variant(g, ring, sm);
+      // (the far bit without the ring bit, next to FZ_VF_STATES or on a graph without a far line: no maker answers with it)
+      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss, far) : states_variant(g, ring, sm);
       return w.P == v.P && w.U == v.U && w.block == v.block && w.flags == v.flags;
    } catch (const Error&) {
       return false;                                         // (a graph, a stride or a patch the call refuses)
@@ -257,14 +273,20 @@ static uint64_t workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t n_s
 }
 
 // the ring kernel's workspace: the register rows before every chunk, then the tape -- every row's ring-line source values
-// (include/flowz_hip.h: fz_program_ring_grad_workspace states it)
+// (include/flowz_hip.h: fz_program_ring_grad_workspace states it).  The far kernel's: the far lines are further tape lines, and behind
+// the tape lies the adjoint ring, one row per slot of every far line (fz_program_far_grad_workspace states it; a graph without a far
+// line has neither)
 static uint64_t ring_workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t n_samples, const Variant& v)
 {
    if (!(v.flags & FZ_VF_ADJOINT_RING)) return workspace_bytes(g, n_streams, n_samples, v.U);
    const RingLayout rl = ring_layout(g);
    const uint64_t chunks = ((uint64_t)n_samples + v.U - 1) / v.U;
-   return (chunks * rl.n_reg() + (uint64_t)n_samples * rl.n_rl()) * n_streams * 4u;
+   return (chunks * rl.n_reg() + (uint64_t)n_samples * (rl.n_rl() + rl.n_fl()) + rl.far_slots) * n_streams * 4u;
 }
+
+// (the far kernel's two static rules -- which far reads of sweep 1 travel with their chunk's x rows, which path sweep 2 takes -- are
+// far_read_with_chunk and far_fast_path in fz_codegen.cpp, next to ring_layout: the code generator writes them into the kernel's
+// configuration and links without this file; include/flowz_hip.h states them)
 
 // The rows per block of a recording of T rows (the one home of this rule; include/flowz_hip.h states it).  block_rows == 0: the B that
 // minimises the row sets kept, ceil(B / C) + ceil(T / B) -- sqrt(T * C) rounded up to a multiple of lcm(4, C) = max(4, C) (time-major
@@ -370,6 +392,7 @@ struct GradCall {
    float grad_scale;
    float *loss, *out;
    bool ring = false;          // the call is of the ring family (fz_run_block_ring_*, fz_run_recording_ring_*): its scope, Variant and workspace
+   bool far = false;           // the call is of the far family (fz_run_block_far_*): a ring call that takes lines deeper than 256 samples too
 };
 
 template <class Args>
@@ -405,6 +428,15 @@ static GradCall ring_call_of(fz_program* p, const Args* a)
    return call;
 }
 
+// the same for a call of the far family
+template <class Args>
+static GradCall far_call_of(fz_program* p, const Args* a)
+{
+   GradCall call = ring_call_of(p, a);
+   call.far = true;
+   return call;
+}
+
 // what a recording adds to the checks of a block: its own workspace size (and the call that answers it), and state_out as one more output
 struct RecordingCheck {
    uint64_t need;
@@ -420,7 +452,7 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
 {
    const GradCall* const a = &call;
    const Graph& g = p->g;
-   const Variant v = block_variant(g, a->checkpoint_rows, a->ring, sm != nullptr, a->loss_rule);
+   const Variant v = block_variant(g, a->checkpoint_rows, a->ring, sm != nullptr, a->loss_rule, a->far);
    *vout = v;
    if (!block_has_work(n_streams, n_samples)) return false;   // an empty block: nothing to differentiate, nothing touched
    if (sm) {
@@ -438,7 +470,7 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
    if (a->loss_rule && !a->ybar) fail(FZ_E_INVALID, "target is null: the loss compares the outputs with it");
    require_pointer(a->ybar, g.n_out, "out_grad", "output wires");
    const uint64_t need = rec ? rec->need : ring_workspace_bytes(g, n_streams, n_samples, v);
-   const std::string ws_fn = rec ? (a->ring ? "fz_program_ring_recording_workspace" : "fz_program_recording_workspace") : a->ring ? "fz_program_ring_grad_workspace" : "fz_program_grad_workspace";
+   const std::string ws_fn = rec ? (a->ring ? "fz_program_ring_recording_workspace" : "fz_program_recording_workspace") : a->far ? "fz_program_far_grad_workspace" : a->ring ? "fz_program_ring_grad_workspace" : "fz_program_grad_workspace";
    if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: " + ws_fn + " says " + std::to_string(need) + " bytes");
    if (need && a->workspace_bytes < need)
       fail(FZ_E_INVALID, "workspace_bytes " + std::to_string(a->workspace_bytes) + " is less than the " + std::to_string(need) + " bytes " + ws_fn + " asks for");
@@ -679,6 +711,8 @@ FZ_INSPECTION(ring_grad, , "fz_program_ring_grad_resources", FZ_ARG_C, block_var
 FZ_INSPECTION(ring_grad, _for, "fz_program_ring_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, true, FZ_SM, false))
 FZ_INSPECTION(ring_loss_grad, , "fz_program_ring_loss_grad_resources", FZ_ARG_C, block_variant(p->g, checkpoint_rows, true, false, true))
 FZ_INSPECTION(ring_loss_grad, _for, "fz_program_ring_loss_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, true, FZ_SM, true))
+FZ_INSPECTION(far_grad, , "fz_program_far_grad_resources", FZ_ARG_C, block_variant(p->g, checkpoint_rows, true, false, false, true))
+FZ_INSPECTION(far_loss_grad, , "fz_program_far_loss_grad_resources", FZ_ARG_C, block_variant(p->g, checkpoint_rows, true, false, true, true))
 FZ_INSPECTION(states, , "fz_program_states_resources", FZ_ARG_LAYOUT, states_variant(p->g, false, FZ_SM))
 FZ_INSPECTION(ring_states, , "fz_program_ring_states_resources", , states_variant(p->g, true, false))
 FZ_INSPECTION(ring_states, _for, "fz_program_ring_states_resources_for", FZ_ARG_LAYOUT, states_variant(p->g, true, FZ_SM))
@@ -763,6 +797,32 @@ int fz_run_block_ring_loss_grad_stream_major(fz_program* p, const fz_loss_grad_a
 int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
    FZ_GUARD(return run_grad(p, ring_call_of(p, a), n_streams, n_samples, hip_stream);)
+}
+
+int fz_program_far_grad_check(const fz_program* p)
+{
+   FZ_GUARD(
+      if (!p) fail(FZ_E_INVALID, "null program");
+      require_scope(p->g, true, true);
+      return FZ_OK;)
+}
+
+int fz_program_far_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_samples, uint32_t checkpoint_rows, uint64_t* bytes)
+{
+   FZ_GUARD(
+      if (!p || !bytes) fail(FZ_E_INVALID, "fz_program_far_grad_workspace: bad arguments");
+      *bytes = ring_workspace_bytes(p->g, n_streams, n_samples, block_variant(p->g, checkpoint_rows, true, false, false, true));
+      return FZ_OK;)
+}
+
+int fz_run_block_far_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
+{
+   FZ_GUARD(return run_grad(p, far_call_of(p, a), n_streams, n_samples, hip_stream);)
+}
+
+int fz_run_block_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
+{
+   FZ_GUARD(return run_grad(p, far_call_of(p, a), n_streams, n_samples, hip_stream);)
 }
 
 int fz_program_ring_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows)

@@ -283,6 +283,14 @@ constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // group, block = 256 / 128 / 64}: fz_grad.cpp: ring_sm_geometry chooses P and block together and states_variant is the one place that
 // makes one.
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
+// internal, with FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING (optionally FZ_VF_ADJOINT_LOSS; never FZ_VF_ADJOINT_SM or FZ_VF_STATES): the
+// adjoint kernel of a graph with delay lines DEEPER THAN 256 SAMPLES, whose rings live in HBM (fz_grad.cpp: fz_run_block_far_grad,
+// fz_run_block_far_loss_grad; fz_kernel_adjoint_far.hip.inc: a text and a symbol of its own, the pending adjoints of the far lines
+// in a ring in the workspace).  The flag 1u is one of the reserved ones -- a forward variant naming it stays refused -- and the flags
+// 1u, 2u and 4u otherwise mean something next to FZ_VF_PCM16 only (FZ_VF_PCM16_IN / _OUT / _B16 below); next to FZ_VF_ADJOINT 1u is this.
+// Such a Variant is {P = 1, U = checkpoint rows, block = the ring rule's answer for the graph's LDS ring lines alone, 256 without
+// any}; fz_grad.cpp: block_variant is the one place that makes one, and only for a graph that has a far line.
+constexpr uint32_t FZ_VF_ADJOINT_FAR = 1u;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte
 // accesses).  FZ_VF_ST_MERGE means for it what it means for the frame kernel.  Such a Variant shares the kernel cache and the manifests
@@ -341,7 +349,10 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v);
 // loss: also out(), the step's output values (FZ_VF_ADJOINT_LOSS).  ring: the body of fz_kernel_adjoint_ring.hip.inc (FZ_VF_ADJOINT_RING):
 // register rows compact, the lines in LDS read through rv[] and their adjoints kept in an LDS ring; without it the text is unchanged.
 // Both: out() takes rv[] too (fz_kernel_adjoint_ring.hip.inc with FZ_LOSS)
-std::string gen_adjoint_body(const Graph& g, bool loss = false, bool ring = false);
+// far (FZ_VF_ADJOINT_FAR, with ring): the body of fz_kernel_adjoint_far.hip.inc -- the far lines' reads follow the ring reads in
+// rv[], their source values the ring lines' in u[]; 1: bwd() keeps their pending adjoints in the workspace ring (the per-row path),
+// 2: in the registers the kernel hands it (the fast path); fz_codegen.cpp: far_fast_path chooses
+std::string gen_adjoint_body(const Graph& g, bool loss = false, bool ring = false, int far = 0);
 // How the ring adjoint kernel lays a graph out (fz_codegen.cpp; the one home of these counts for fz_grad.cpp too): the lines of depth
 // <= 8 keep compact REGISTER rows, every `in_lds` line is a RING LINE with its slots in the lane's LDS column, and the distinct
 // (ring line, delay) pairs the graph reads are the RING READS, in node order.
@@ -353,17 +364,34 @@ struct RingLayout {
    std::vector<uint32_t> rl_slot0;   // per ring line: its first LDS slot
    std::vector<std::pair<uint32_t, uint32_t>> reads;   // (ring line, delay)
    uint32_t slots = 0;               // LDS slots per lane: the sum of the ring lines' depths
+   // the FAR lines (Line::far, deeper than 256 samples: fz_kernel_adjoint_far.hip.inc), neither register rows nor ring lines
+   std::vector<int> far_of_line;     // per line: its far line index, -1 for any other line
+   std::vector<uint32_t> fl_line;    // per far line: index into Graph::lines
+   std::vector<uint32_t> fl_slot0;   // per far line: its first row of the adjoint ring in the workspace
+   std::vector<std::pair<uint32_t, uint32_t>> far_reads;   // (far line, delay), in node order
+   uint32_t far_slots = 0;           // rows of the adjoint ring in the workspace: the sum of the far lines' depths
    uint32_t n_reg() const { return (uint32_t)reg_row.size(); }
    uint32_t n_rl() const { return (uint32_t)rl_line.size(); }
    uint32_t n_rr() const { return (uint32_t)reads.size(); }
+   uint32_t n_fl() const { return (uint32_t)fl_line.size(); }
+   uint32_t n_fr() const { return (uint32_t)far_reads.size(); }
    int read_index(uint32_t ring_line, uint32_t delay) const;   // -1: no such read
+   int far_read_index(uint32_t far_line, uint32_t delay) const;   // -1: no such read
 };
 RingLayout ring_layout(const Graph& g);
 // the node kinds gen_adjoint_body writes (fz_codegen.cpp); grad_unsupported_reason refuses a graph with any other
 bool adjoint_takes(uint32_t kind);
 // why the backward of a block does not support this graph ("" = it does): fz_grad.cpp
 // rings_in_lds: float delay lines in LDS (depth 9 .. 256) are no objection -- the scope of fz_run_block_ring_grad
-std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds = false);
+// rings_in_hbm (with rings_in_lds): float delay lines deeper than 256 samples are none either -- the scope of fz_run_block_far_grad
+std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds = false, bool rings_in_hbm = false);
+// the far adjoint kernel's two static rules (fz_codegen.cpp, next to ring_layout, is their one home; include/flowz_hip.h states
+// them).  A far read of sweep 1 is requested with its chunk's x rows when the row it reads was written before the chunk began; else
+// it is a load of its own in front of its row.  Sweep 2 takes the fast path -- a chunk's pending adjoints requested together, added to in registers, stored
+// once -- when no slot is touched twice within a chunk of C rows: every far read at least C rows old, any two of one line at least
+// C apart; else the per-row path.
+bool far_read_with_chunk(uint32_t delay, uint32_t C);
+bool far_fast_path(const Graph& g, uint32_t C);
 // could the backward have made this Variant of the adjoint family (FZ_VF_ADJOINT and the family bits next to it) for this graph?
 // The flag set names the call; v fits when that call, asked for v's stride, makes exactly v: fz_grad.cpp
 bool grad_variant_fits(const Graph& g, const Variant& v);

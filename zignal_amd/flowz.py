@@ -375,6 +375,8 @@ _GRAD_ENTRY = {
     (True, False, True, True): "fz_run_recording_ring_grad_stream_major",
     (True, True, True, True): "fz_run_recording_ring_loss_grad_stream_major",
 }
+# the far family (delay lines deeper than 256 samples): one block of time-major frames, by loss
+_FAR_GRAD_ENTRY = {False: "fz_run_block_far_grad", True: "fz_run_block_far_loss_grad"}
 
 
 class Program:
@@ -953,6 +955,54 @@ class Program:
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, window, (float(grad_scale), out),
                               (int(block_rows), workspace))
 
+    # -- the backward of a block with delay lines deeper than 256 samples (fz_run_block_far_grad): the far call family ------------------
+    def far_grad_supported(self) -> bool:
+        """True when fz_run_block_far_grad takes this program: what ring_grad_supported() takes, and graphs with float delay lines
+        deeper than 256 samples, whose rings live in HBM (far_grad_unsupported_reason() says why not)."""
+        return C.lib.fz_program_far_grad_check(self._h) == C.FZ_OK
+
+    def far_grad_unsupported_reason(self) -> str:
+        return "" if self.far_grad_supported() else C.last_error()
+
+    def far_grad_workspace_bytes(self, n_streams: int, T: int, checkpoint_rows: int = 0) -> int:
+        """workspace bytes of run_block_far_grad / run_block_far_loss_grad: checkpoints, the tape (ring and far lines) and the adjoint
+        ring of the far lines, one row per slot"""
+        return _out(ctypes.c_uint64, C.lib.fz_program_far_grad_workspace, self._h, int(n_streams), int(T), int(checkpoint_rows))
+
+    def far_grad_resources(self, c: int = 0) -> dict:
+        """grad_resources() of the kernel of run_block_far_grad at checkpoint stride c (0: the library default); 'lds_bytes' = the
+        adjoint rings of the LDS ring lines alone: the far lines take none"""
+        return _resources(C.lib.fz_program_far_grad_resources, self._h, int(c))
+
+    def far_grad_kernel_symbol(self, c: int = 0) -> str:
+        return _name(C.lib.fz_program_far_grad_kernel_symbol, self._h, int(c))
+
+    def far_grad_source(self, c: int = 0) -> str:
+        return _text(C.lib.fz_program_far_grad_source, self._h, int(c))
+
+    def run_block_far_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0):
+        """run_block_ring_grad for graphs with delay lines deeper than 256 samples (fz_run_block_far_grad): the same arguments, the same
+        result dict; time-major frames only.  The rows of such a line in `state`, state_grad and the "state" result are ring SLOTS, and
+        its phase row follows the line rows (zero in "state").  For a graph run_block_ring_grad takes it is run_block_ring_grad."""
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None, ring=True, far=True)
+
+    def far_loss_grad_resources(self, c: int = 0) -> dict:
+        """far_grad_resources() of the kernel of run_block_far_loss_grad at checkpoint stride c (0: the library default)"""
+        return _resources(C.lib.fz_program_far_loss_grad_resources, self._h, int(c))
+
+    def far_loss_grad_kernel_symbol(self, c: int = 0) -> str:
+        return _name(C.lib.fz_program_far_loss_grad_kernel_symbol, self._h, int(c))
+
+    def far_loss_grad_source(self, c: int = 0) -> str:
+        return _text(C.lib.fz_program_far_loss_grad_source, self._h, int(c))
+
+    def run_block_far_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
+                                checkpoint_rows: int = 0):
+        """run_block_ring_loss_grad for graphs with delay lines deeper than 256 samples (fz_run_block_far_loss_grad): the same
+        arguments, the same result dict, the rule of run_block_loss_grad and then the order of run_block_far_grad; time-major frames
+        only, the workspace of run_block_far_grad.  For a graph run_block_ring_loss_grad takes it is run_block_ring_loss_grad."""
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), None), ring=True, far=True)
+
     # -- the backward of a whole recording with delay lines deeper than 8 samples (fz_run_recording_ring_grad) -----------------------
     def ring_recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
         """the rows per block run_recording_ring_grad cuts a recording of T rows into (block_rows = 0: the library's choice, which
@@ -1014,15 +1064,17 @@ class Program:
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad),
                               (float(grad_scale), out), (int(block_rows), workspace), ring=True)
 
-    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None, ring=False):
+    def _run_grad(self, x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, window, loss=None, recording=None, ring=False, far=False):
         """both frame layouts; window: None (time-major frames) or (row0, n_samples, in_grad) of stream-major buffers; loss: None, or
         (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
         (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is of the ring family:
         run_block_ring_grad / run_block_ring_loss_grad, or with recording run_recording_ring_grad / run_recording_ring_loss_grad, and their
-        _stream_major twins"""
+        _stream_major twins; far (with ring, one block of time-major frames): run_block_far_grad / run_block_far_loss_grad"""
         import torch
 
-        if ring:
+        if far:
+            _require(self.far_grad_supported(), self.far_grad_unsupported_reason())
+        elif ring:
             _require(self.ring_grad_supported(), self.ring_grad_unsupported_reason())
         else:
             _require(self.grad_supported(), self.grad_unsupported_reason())
@@ -1085,7 +1137,7 @@ class Program:
                     torch.zeros(gshape, dtype=torch.float32, device=dev)
         state0_grad = out.get("state")
         if recording is None:
-            wsb = (self.ring_grad_workspace_bytes if ring else self.grad_workspace_bytes)(ns, T, checkpoint_rows)
+            wsb = (self.far_grad_workspace_bytes if far else self.ring_grad_workspace_bytes if ring else self.grad_workspace_bytes)(ns, T, checkpoint_rows)
         else:
             wsb = self.ring_recording_workspace_bytes(ns, T, recording[0], checkpoint_rows) if ring else \
                 self.recording_workspace_bytes(ns, T, recording[0], checkpoint_rows, window is not None)
@@ -1121,7 +1173,7 @@ class Program:
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
         hs = torch.cuda.current_stream().cuda_stream
-        fn = getattr(C.lib, _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
+        fn = getattr(C.lib, _FAR_GRAD_ENTRY[loss is not None] if far else _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
         if recording is not None and ring and window is not None:     # ring recording window
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
         elif recording is not None and ring:                          # ring recording
