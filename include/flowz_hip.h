@@ -917,6 +917,62 @@ int fz_program_ring_states_resources_for(fz_program* p, uint32_t layout, fz_kern
 long fz_program_ring_states_kernel_symbol_for(fz_program* p, uint32_t layout, char* buf, size_t cap);
 long fz_program_ring_states_source_for(fz_program* p, uint32_t layout, char* buf, size_t cap);
 
+/* fz_run_recording_far_grad, fz_run_recording_far_loss_grad -- fz_run_recording_ring_grad / fz_run_recording_ring_loss_grad for
+ * graphs with delay lines DEEPER THAN 256 SAMPLES (rings in HBM): the third pair of members of the far call family, the gradient of
+ * a whole recording of T time-major rows in a workspace that does not hold a tape of T rows per far line.
+ *
+ * NO NEW RULE.  Every output bit -- in_grad, state0_grad, param_grad, const_grad, loss, out -- is that of fz_run_block_far_grad /
+ * fz_run_block_far_loss_grad over the same T rows, whatever block_rows is: far blocks chain bitwise through state0_grad slot for
+ * slot, also where a block is shorter than a line is deep (fz_run_block_far_grad says so).  starts[k], at the head of the workspace,
+ * and state_out, if not NULL, have the bits of fz_run_block's state after k B / T rows, the far lines' rows included: the value u[q]
+ * in slot (p0 + q) mod D, the phase row (p0 + k B) mod D / (p0 + T) mod D as the forward writes it.  fz_grad_args and
+ * fz_loss_grad_args are taken unchanged, the accumulators are ADDED TO, state0_grad may be state_grad.
+ *
+ * Scope: that of fz_program_far_grad_check.  For a graph without a line deeper than 256 samples these calls ARE
+ * fz_run_recording_ring_grad / fz_run_recording_ring_loss_grad (and so, without a deep line at all, the FZ_GRAD_TIME_MAJOR
+ * fz_run_recording_grad / fz_run_recording_loss_grad): the same states kernel, B, workspace and bits.  fz_run_recording_*,
+ * fz_run_recording_ring_*, fz_program_ring_recording_* and fz_program_ring_states_* keep refusing graphs with such lines.
+ * Time-major frames only.
+ *
+ * How: one launch of the FAR STATES kernel writes starts[ceil(T / B)][n_state][n_streams] (and state_out); then the far adjoint or
+ * far loss kernel is launched, unchanged, per block from the last to the first, with state = starts[k] and state_grad = the
+ * state0_grad of the launch before it.  The far states kernel is the ring states kernel with sweep 1 of the far adjoint kernel as
+ * its step.  It keeps a far line as a WORKING VALUE RING in the caller's own slot format in the rows of the workspace behind
+ * `starts` -- rows of the block workspace, which no launch has used yet, so the workspace does not grow --, filled once from
+ * `state` by the identity map; per row one load per far read and one store per far line, no tape; at a block start a line's D slots
+ * are copied row for row.  STATIC RULE: the rows go in groups of U, and a far read at a delay of at least 2 U -- its slot was
+ * written before the next group's x rows are requested -- is requested with them; a younger read is a load of its own in front of
+ * its row (same-lane program order).  HBM bytes per stream-sample: 4 n_in + 4 n_far_lines + 4 n_far_reads + (4 n_state + 4 * sum of
+ * the far depths) / B.
+ *
+ * B: block_rows, capped at T; for block_rows == 0 the least B with B^2 (n_register_state + C (n_ring_lines + n_far_lines)) >=
+ * T n_state C, rounded up to a multiple of max(4, C), and B = T when that is not smaller than T -- the ring rule with the far lines
+ * among the tape lines (C: the far kernel's checkpoint stride; n_state counts a far line's D slots and its phase row, so a block
+ * start costs D + 1 rows per far line and the blocks are long).  The rows kept per stream are ceil(T / B) n_state + ceil(B / C)
+ * n_register_state + B (n_ring_lines + n_far_lines) + the sum of the far depths.  Without a far line this is the ring rule.
+ * fz_program_far_recording_block_rows answers the B a call will use.
+ * WORKSPACE: ceil(T / B) * n_state * n_streams * 4 bytes plus fz_program_far_grad_workspace(n_streams, B, C);
+ * fz_program_far_recording_workspace answers it.
+ *
+ * Checks, all before a device is needed and in this order: the refusals of fz_program_far_grad_check; block_rows a multiple of 4;
+ * n_samples < 2^31; those of the one-launch far call over the T rows (state_out counted as an output) with this call's workspace
+ * size -- a short workspace names fz_program_far_recording_workspace; those of every block launch; with more than one block,
+ * state0_grad not NULL.  n_streams == 0 or n_samples == 0: FZ_OK, nothing is touched.  Asynchronous on hip_stream.
+ *
+ * The far states kernel is a kernel of its own, fz_states_far_kernel_u<U>b<lanes>_g<tag> (U rows per unrolled group, at most 8; the
+ * lanes and lds_bytes of the far adjoint kernel: the LDS ring lines' alone); fz_program_far_states_* inspect it like
+ * fz_program_ring_states_*. */
+int fz_program_far_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows);
+int fz_program_far_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
+                                       uint64_t* bytes);
+int fz_run_recording_far_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows, float* state_out,
+                              void* hip_stream);
+int fz_run_recording_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows,
+                                   float* state_out, void* hip_stream);
+int fz_program_far_states_resources(fz_program* p, fz_kernel_resources* out);
+long fz_program_far_states_kernel_symbol(fz_program* p, char* buf, size_t cap);
+long fz_program_far_states_source(fz_program* p, char* buf, size_t cap);
+
 /* ------------------------------------------------------------------------------------------
  * 16-bit PCM frames.  fz_run_block_pcm16 is fz_run_block for a block whose frames are int16 on one side or on both: the caller
  * sends and receives 2 bytes per sample instead of 4, the conversions happen in the kernel.

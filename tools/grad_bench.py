@@ -77,7 +77,15 @@ at the default stride agrees bit for bit with the one at C = 1 (another chunking
 formula of DESIGN.md 9.11 (counted from the code, not measured) as a fraction of 8 TB/s.  There is no pass mark.  The table goes to stdout
 and to profiles/r17/far_grad.txt.
 
+--far --recording: the squared-error backward of a whole recording of graphs with delay lines deeper than 256 samples,
+run_recording_far_loss_grad (fz_run_recording_far_loss_grad: one far states launch, then the far loss kernel per block in reverse), with
+the legs, the shapes, the method and the mark of --rings --recording: one = the one-launch run_block_far_loss_grad where its workspace
+fits; route = run_block per block for the states, copying the state rows before each block, then run_block_far_loss_grad per block in
+reverse at the same B.  workloads.far_comb (300 samples) and ~(0.5*_1[_2000] + _2).  The table, the workspaces and B go to stdout and to
+profiles/r18/far_recording.txt.
+
 usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings] [--far]
+       (--far takes --recording)
        (--rings takes --layout compare, alone or with --loss; --rings --recording takes --layout stream-major|compare, alone or with --loss)
 """
 import argparse
@@ -672,24 +680,29 @@ def rings_loss_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
-def rings_recording_bench(a, torch):
+FAR_REC_GRAPHS = {"far_comb": W.far_comb, "comb2000": _comb(2000)}
+
+
+def rings_recording_bench(a, torch, far=False):
     """the squared-error backward of a whole recording of graphs with delay lines in LDS: the recording call, the one-launch call, and
-    blocks chained by hand"""
+    blocks chained by hand.  far: the same for graphs with delay lines in HBM, through the far family's calls"""
     import time
     lines = []
+    fam = "far" if far else "ring"
+    call = lambda prog, what: getattr(prog, what.replace("ring", fam))   # noqa: E731  (the family's method of that name)
 
     def say(line):
         print(line, flush=True)
         lines.append(line)
     props = torch.cuda.get_device_properties(0)
-    say(f"# command: tools/grad_bench.py --rings --recording --steps {a.steps} --legs {a.legs}")
+    say(f"# command: tools/grad_bench.py {'--far' if far else '--rings'} --recording --steps {a.steps} --legs {a.legs}")
     say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
-    say("# rec = one run_recording_ring_loss_grad call; one = one run_block_ring_loss_grad launch over all rows (where its workspace fits);")
-    say("# route = run_block per block into a scratch y for the states, then run_block_ring_loss_grad per block in reverse (same B as rec); time-major frames")
+    say(f"# rec = one run_recording_{fam}_loss_grad call; one = one run_block_{fam}_loss_grad launch over all rows (where its workspace fits);")
+    say(f"# route = run_block per block into a scratch y for the states, then run_block_{fam}_loss_grad per block in reverse (same B as rec); time-major frames")
     say(f"# HIP events, {a.steps} calls per leg and pass, a forward and a backward pass over the legs; spread = max - min of a leg's own repeats;")
     say("# mark = rec median <= route median + the route's spread")
     say(f"{'graph':16s} {'streams x T':>16s} {'B':>5s} {'route ms':>9s} {'spread':>7s} {'rec ms':>9s} {'spread':>7s} {'one ms':>9s} {'spread':>7s} "
-        f"{'rec/route':>9s} {'rec/one':>8s} {'mark':>5s} {'ws rec MB':>10s} {'ws route MB':>11s} {'ws one MB':>10s}  ring states kernel")
+        f"{'rec/route':>9s} {'rec/one':>8s} {'mark':>5s} {'ws rec MB':>10s} {'ws route MB':>11s} {'ws one MB':>10s}  {fam} states kernel")
     shapes = REC_SHAPES["small"] + REC_SHAPES["large"] if a.legs == "all" else REC_SHAPES[a.legs]
     want = ("x", "state", "params", "consts", "loss")
     for ns, T in shapes:
@@ -698,20 +711,20 @@ def rings_recording_bench(a, torch):
         target = torch.empty_like(x)
         F.synth_fill(target, seed=W.SEED + 1)
         n = float(ns) * T
-        for name, fn in RING_GRAPHS.items():
+        for name, fn in (FAR_REC_GRAPHS if far else RING_GRAPHS).items():
             prog = F.compile(F.from_sexpr(fn()))
             s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
-            B = prog.ring_recording_block_rows(T)
+            B = call(prog, "ring_recording_block_rows")(T)
             nb = (T + B - 1) // B
-            ws_rec, ws_one = prog.ring_recording_workspace_bytes(ns, T), prog.ring_grad_workspace_bytes(ns, T)
+            ws_rec, ws_one = call(prog, "ring_recording_workspace_bytes")(ns, T), call(prog, "ring_grad_workspace_bytes")(ns, T)
             # the route keeps the state before every block itself, a scratch y of one block, and one block's ring workspace
-            ws_route = nb * prog.n_state * ns * 4 + B * ns * prog.n_out * 4 + prog.ring_grad_workspace_bytes(ns, B)
+            ws_route = nb * prog.n_state * ns * 4 + B * ns * prog.n_out * 4 + call(prog, "ring_grad_workspace_bytes")(ns, B)
             ws = torch.empty(ws_rec // 4, dtype=torch.float32, device="cuda")
             states = torch.empty((nb + 1, prog.n_state, ns), dtype=torch.float32, device="cuda")
             y = torch.empty((B, ns, 1), dtype=torch.float32, device="cuda")
 
             def rec():
-                r = prog.run_recording_ring_loss_grad(x, target, s0, None, grad_scale=2.0 / n, want=want, workspace=ws)
+                r = call(prog, "run_recording_ring_loss_grad")(x, target, s0, None, grad_scale=2.0 / n, want=want, workspace=ws)
                 return r["loss"].double().sum() / n
 
             def route():
@@ -723,14 +736,14 @@ def rings_recording_bench(a, torch):
                 acc, sg = {}, None
                 for k in range(nb - 1, -1, -1):
                     rows = min(B, T - k * B)
-                    r = prog.run_block_ring_loss_grad(x[k * B:k * B + rows], target[k * B:k * B + rows], states[k], None, state_grad=sg, grad_scale=2.0 / n,
-                                                      want=want, accum=acc)
+                    r = call(prog, "run_block_ring_loss_grad")(x[k * B:k * B + rows], target[k * B:k * B + rows], states[k], None, state_grad=sg,
+                                                               grad_scale=2.0 / n, want=want, accum=acc)
                     # (the accumulators the next launch adds to: only those the graph has rows of)
                     acc, sg = {k: r[k] for k, rows_k in (("params", prog.n_param), ("consts", prog.n_const), ("loss", 1)) if rows_k}, r["state"]
                 return acc["loss"].double().sum() / n
 
             def one():
-                r = prog.run_block_ring_loss_grad(x, target, s0, None, grad_scale=2.0 / n, want=want)
+                r = call(prog, "run_block_ring_loss_grad")(x, target, s0, None, grad_scale=2.0 / n, want=want)
                 return r["loss"].double().sum() / n
             legs = {"route": route, "rec": rec}
             if ws_one + (4 << 30) < torch.cuda.mem_get_info()[0]:
@@ -752,13 +765,13 @@ def rings_recording_bench(a, torch):
             ratio_one = f"{med['rec'] / med['one']:8.3f}" if "one" in med else f"{'-':>8s}"
             say(f"{name:16s} {f'{ns} x {T}':>16s} {B:5d} {med['route']:9.3f} {sp['route']:7.3f} {med['rec']:9.3f} {sp['rec']:7.3f} {one_s} "
                 f"{med['rec'] / med['route']:9.3f} {ratio_one} {'yes' if med['rec'] <= med['route'] + sp['route'] else 'NO':>5s} {ws_rec / 2**20:10.1f} "
-                f"{ws_route / 2**20:11.1f} {ws_one / 2**20:10.1f}  {prog.ring_states_kernel_symbol()}")
+                f"{ws_route / 2**20:11.1f} {ws_one / 2**20:10.1f}  {call(prog, 'ring_states_kernel_symbol')()}")
             say("#   all timings ms: " + "; ".join(f"{k} " + " ".join(f"{t:.3f}" for t in v) for k, v in got.items()))
             del s0, ws, states, y
             torch.cuda.empty_cache()
         del x, target
         torch.cuda.empty_cache()
-    out = os.path.join(ROOT, "profiles", "r14", "ring_recording.txt")
+    out = os.path.join(ROOT, "profiles", "r18", "far_recording.txt") if far else os.path.join(ROOT, "profiles", "r14", "ring_recording.txt")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -863,11 +876,13 @@ def main():
     ap.add_argument("--loss", action="store_true", help="the fused squared-error backward against forward + torch MSE + backward, both layouts")
     ap.add_argument("--recording", action="store_true", help="the backward of a whole recording against the one-launch call and blocks chained by hand")
     ap.add_argument("--rings", action="store_true", help="forward against the ring backward of graphs with delay lines deeper than 8 samples; with --loss: their fused squared-error backward against the route; with --recording: the backward of a whole recording of them")
-    ap.add_argument("--far", action="store_true", help="forward against the far backward of graphs with delay lines deeper than 256 samples, the LDS ring kernel on a 256-sample comb next to them")
+    ap.add_argument("--far", action="store_true", help="forward against the far backward of graphs with delay lines deeper than 256 samples, the LDS ring kernel on a 256-sample comb next to them; with --recording: the backward of a whole recording of them against the one-launch call and blocks chained by hand")
     a = ap.parse_args()
     import torch
 
     torch.cuda.set_device(0)
+    if a.far and a.recording:
+        return rings_recording_bench(a, torch, far=True)
     if a.far:
         return far_bench(a, torch)
     if a.rings and a.recording and a.layout != "time-major":

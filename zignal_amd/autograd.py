@@ -36,6 +36,10 @@ mse_recording_rings(prog, x, target, ...) is mse_recording() for every graph run
 graphs with delay lines deeper than 8 samples.
 mse_recording_rings(..., stream_major=True) is the same on stream-major tensors (Program.run_recording_ring_loss_grad_stream_major):
 a batch of recordings lying as [batch, time] is fitted in bounded workspace without a transposed copy.
+
+mse_recording_far(prog, x, target, ...) is mse_recording_rings() for every graph run_far() takes, time-major
+(Program.run_recording_far_loss_grad: the far states kernel, then the far loss kernel block by block); mse_recording_rings() keeps
+refusing graphs with delay lines deeper than 256 samples.
 """
 from __future__ import annotations
 
@@ -245,4 +249,16 @@ def mse_recording_rings(prog: Program, x, target, state=None, params=None, const
     (Program.run_recording_ring_loss_grad_stream_major); block_rows times n_in and n_out are then multiples of 4."""
     _front_door(prog, x, consts, True)
     loss, state_out = _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), True, int(block_rows))
+    return loss, state_out.detach()
+
+
+def mse_recording_far(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0):
+    """mse_recording_rings() for graphs with delay lines deeper than 256 samples -- and every graph mse_recording_rings() takes --,
+    time-major frames only: returns (loss, state_out) over a whole recording in bounded workspace
+    (Program.far_recording_workspace_bytes: the state before every block plus one block's checkpoints, tape and adjoint ring;
+    block_rows = 0 lets the library choose, otherwise a multiple of 4).  The gradients have the bits of mse_far()'s over the same rows
+    (include/flowz_hip.h: fz_run_recording_far_loss_grad); state_out carries the far lines' slots and phase rows, so it is the `state`
+    of the next call."""
+    _front_door(prog, x, consts, "far")
+    loss, state_out = _Mse.apply(prog, x, target, state, params, consts, False, "far", int(block_rows))
     return loss, state_out.detach()

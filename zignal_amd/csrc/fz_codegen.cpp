@@ -32,6 +32,7 @@ extern const char* const kSkeletonAdjointRingSm;
 extern const char* const kSkeletonAdjointFar;    // fz_kernel_adjoint_far.hip.inc: delay lines deeper than 256 samples, rings in HBM
 extern const char* const kSkeletonStates;        // fz_kernel_states.hip.inc: plain and, with FZ_RING, ring
 extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: the same
+extern const char* const kSkeletonStatesFar;     // fz_kernel_states_far.hip.inc: the states kernel of a graph with rings in HBM
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
@@ -57,6 +58,7 @@ static const AdjointRow& adjoint_row(const Variant& v)
       {FZ_VF_STATES | FZ_VF_ADJOINT_SM, "fz_states", "_sm", kSkeletonStatesSm, true},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_states", "_ring_sm", kSkeletonStatesSm, true},
+      {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, "fz_states", "_far", kSkeletonStatesFar, false},
    };
    for (const AdjointRow& r : rows)
       if (r.bits == (v.flags & (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_FAR)) && !((v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_LOSS))) return r;
@@ -782,7 +784,9 @@ static std::string gen_body_waves(const Graph& g, uint32_t W)
 std::string gen_body(const Graph& g, const Variant& v)
 {
    if (v.flags & FZ_VF_ADJOINT)
-      return gen_adjoint_body(g, (v.flags & FZ_VF_ADJOINT_LOSS) != 0, (v.flags & FZ_VF_ADJOINT_RING) != 0, !(v.flags & FZ_VF_ADJOINT_FAR) ? 0 : far_fast_path(g, v.U) ? 2 : 1);
+      // (the far states kernel calls fwd() alone, which is one text on either path of bwd(): it takes the per-row one)
+      return gen_adjoint_body(g, (v.flags & FZ_VF_ADJOINT_LOSS) != 0, (v.flags & FZ_VF_ADJOINT_RING) != 0,
+                              !(v.flags & FZ_VF_ADJOINT_FAR) ? 0 : !(v.flags & FZ_VF_STATES) && far_fast_path(g, v.U) ? 2 : 1);
    if (const uint32_t W = ws_parts(v.flags)) return gen_body_waves(g, W);
    if (v.flags & FZ_VF_STAGE_PACK) return gen_body_skew(g, g.split);
    return gen_body_frames(g, v);
@@ -1104,14 +1108,15 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
          o << "#define FZ_NFL " << rl.n_fl() << "   // far lines: delay lines deeper than " << kLdsMaxDepth << " samples, rings in HBM\n";
          o << "#define FZ_NFR " << rl.n_fr() << "   // far reads: distinct (far line, delay) pairs\n";
          o << "#define FZ_FAR_SLOTS " << rl.far_slots << "   // rows of the adjoint ring in the workspace: the sum of the far lines' depths\n";
-         o << "#define FZ_FAR_FAST " << (far_fast_path(g, v.U) ? 1 : 0) << "   // 1: no slot is touched twice within a chunk -- the pending adjoints travel with the chunk's rows\n";
+         if (!(v.flags & FZ_VF_STATES)) o << "#define FZ_FAR_FAST " << (far_fast_path(g, v.U) ? 1 : 0) << "   // 1: no slot is touched twice within a chunk -- the pending adjoints travel with the chunk's rows\n";
          table("fz_fl_row0", rl.n_fl(), [&](size_t i) { return g.lines[rl.fl_line[i]].row0; }, "per far line: its first state row");
          table("fz_fl_depth", rl.n_fl(), [&](size_t i) { return g.lines[rl.fl_line[i]].depth; }, "per far line: its depth = its ring slots");
          table("fz_fl_slot0", rl.n_fl(), [&](size_t i) { return rl.fl_slot0[i]; }, "per far line: its first row of the adjoint ring");
          table("fz_fl_phase_row", rl.n_fl(), [&](size_t i) { return g.lines[rl.fl_line[i]].phase_row; }, "per far line: the state row of its ring phase");
          table("fz_fr_line", rl.n_fr(), [&](size_t i) { return rl.far_reads[i].first; }, "per far read: its far line");
          table("fz_fr_delay", rl.n_fr(), [&](size_t i) { return rl.far_reads[i].second; }, "per far read: its delay in samples");
-         table("fz_fr_chunked", rl.n_fr(), [&](size_t i) { return far_read_with_chunk(rl.far_reads[i].second, v.U) ? 1u : 0u; }, "per far read: 1 = sweep 1 requests it with the chunk's x rows");
+         if (v.flags & FZ_VF_STATES) table("fz_fr_ahead", rl.n_fr(), [&](size_t i) { return far_read_with_next_group(rl.far_reads[i].second, v.U) ? 1u : 0u; }, "per far read: 1 = requested with the next group's x rows");
+         else table("fz_fr_chunked", rl.n_fr(), [&](size_t i) { return far_read_with_chunk(rl.far_reads[i].second, v.U) ? 1u : 0u; }, "per far read: 1 = sweep 1 requests it with the chunk's x rows");
       }
    }
    if (v.flags & FZ_VF_STATES) {
@@ -1183,6 +1188,12 @@ RingLayout ring_layout(const Graph& g)
 // its chunk began, whichever row of the chunk asks: it is requested with the chunk's x rows.  A younger read is a load of its own in
 // front of its row (the forward shortens the chunk instead, below kFarMinDelay: here the chunk is the checkpoint stride and stays).
 bool far_read_with_chunk(uint32_t delay, uint32_t C) { return delay >= C; }
+
+// The far states kernel (fz_kernel_states_far.hip.inc) requests the x rows of the NEXT group of U rows before the current group runs.
+// A far read may travel with them when the slot it reads was written before that request is issued, whichever row of the next group
+// asks: the youngest source row is that of the group's last row, t0 + 2U - 1 - delay, and it must lie before t0.  A younger read is a
+// load of its own in front of its row.
+bool far_read_with_next_group(uint32_t delay, uint32_t U) { return delay >= 2 * U; }
 
 // Sweep 2 takes the fast path when no slot of the adjoint ring is touched twice within a chunk of C rows: every far read at least C
 // rows old (its target is no row's own slot within the chunk), and any two reads of one far line at least C apart (no two rows share

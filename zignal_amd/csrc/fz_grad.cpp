@@ -12,6 +12,8 @@
 //     (FZ_VF_STATES)
 //   fz_run_recording_ring_grad[_stream_major]:        the same text with FZ_RING        the same text with FZ_RING
 //     the same (FZ_VF_STATES | FZ_VF_ADJOINT_RING)
+//   fz_run_recording_far_grad: the same               fz_kernel_states_far.hip.inc      (not built)
+//     (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR)
 //
 // Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the four adjoint kernels forms dL/dy itself, from a
 // target: the same text with FZ_LOSS, the same C, workgroup and workspace.  The ring calls share the checks and the launch with the
@@ -166,6 +168,9 @@ static uint32_t adjoint_flags(const Graph& g, uint32_t family_bits, bool loss)
    return FZ_VF_ADJOINT | family_bits | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
 }
 
+// (the far kernels are built for time-major frames only: the one reason both makers give)
+static const char* const kFarStreamMajor = "delay lines deeper than 256 samples (rings in HBM) are not supported by the backward on stream-major buffers";
+
 static uint32_t family_bits(bool ring, bool stream_major) { return (ring ? FZ_VF_ADJOINT_RING : 0u) | (stream_major ? FZ_VF_ADJOINT_SM : 0u); }
 
 // The Variant of a block's backward, whichever call asks: {P = 1 (stream-major: the patch rows R -- codegen puts them into FZ_R and the
@@ -183,7 +188,7 @@ static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring
    const RingLayout rl = ring ? ring_layout(g) : RingLayout{};
    const uint32_t slots = rl.slots, wires = g.n_in + g.n_out;
    const bool far_lines = rl.n_fl() != 0;
-   if (far_lines && stream_major) fail(FZ_E_UNSUPPORTED, "delay lines deeper than 256 samples (rings in HBM) are not supported by the backward on stream-major buffers");
+   if (far_lines && stream_major) fail(FZ_E_UNSUPPORTED, kFarStreamMajor);
    Variant v;
    v.P = 1;
    v.U = checkpoint_of(g, checkpoint_rows, slots != 0 || far_lines);
@@ -215,15 +220,22 @@ static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring
 // of 4 and of U); a graph without input wires declares no patch.  R0 is twice the plain states kernel's -- one stream's run is two
 // cache lines, the 256-byte in-run of the forward stream-major long-run bodies: where the rings bound the workgroup anyway the longer
 // run costs no occupancy.  Static, not measured against R0 = states_sm_patch_rows(g).
-static Variant states_variant(const Graph& g, bool ring, bool stream_major)
+// far: as for block_variant -- the scope of the far backward; without a line deeper than 256 samples the ring states Variant itself.
+// With one: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR next to FZ_VF_STATES (fz_kernel_states_far.hip.inc), the same U, and the workgroup
+// the ring rule gives the graph's LDS ring lines alone, 256 lanes without any -- the far adjoint kernel's.  Time-major frames only.
+static Variant states_variant(const Graph& g, bool ring, bool stream_major, bool far = false)
 {
-   require_scope(g, ring);
-   const uint32_t slots = ring ? ring_layout(g).slots : 0u;
+   ring = ring || far;
+   require_scope(g, ring, far);
+   const RingLayout rl = ring ? ring_layout(g) : RingLayout{};
+   const uint32_t slots = rl.slots;
+   const bool far_lines = rl.n_fl() != 0;
+   if (far_lines && stream_major) fail(FZ_E_UNSUPPORTED, kFarStreamMajor);
    Variant v;
    v.P = 1;
    v.U = states_unroll(g);
    v.block = kGradBlock;
-   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | family_bits(slots != 0, stream_major);
+   v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | family_bits(slots != 0 || far_lines, stream_major) | (far_lines ? FZ_VF_ADJOINT_FAR : 0u);
    if (slots) {
       const LaneLds lane{slots, stream_major ? g.n_in : 0u, stream_major && g.n_in ? 4u : 0u};
       const uint32_t Rmin = stream_major ? std::max<uint32_t>(4u, v.U) : 1u;
@@ -252,8 +264,9 @@ bool grad_variant_fits(const Graph& g, const Variant& v)
 {
    const bool ring = v.flags & FZ_VF_ADJOINT_RING, sm = v.flags & FZ_VF_ADJOINT_SM, loss = v.flags & FZ_VF_ADJOINT_LOSS, far = v.flags & FZ_VF_ADJOINT_FAR;
    try {
-      // (the far bit without the ring bit, next to FZ_VF_STATES or on a graph without a far line: no maker answers with it)
-      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss, far) : states_variant(g, ring, sm);
+      // (the far bit without the ring bit or on a graph without a far line: no maker answers with it; next to FZ_VF_STATES the states
+      //  maker answers with its own U, at most 8, and never with the loss or the stream-major bit beside the far one)
+      const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss, far) : states_variant(g, ring, sm, far);
       return w.P == v.P && w.U == v.U && w.block == v.block && w.flags == v.flags;
    } catch (const Error&) {
       return false;                                         // (a graph, a stride or a patch the call refuses)
@@ -306,12 +319,16 @@ static uint32_t recording_block_rows(uint32_t T, uint32_t C, uint32_t block_rows
 // ceil(T / B) n_state of starts, ceil(B / C) n_register_state of checkpoints and B n_ring_lines of tape; block_rows == 0 starts from
 // the continuous minimiser of their sum, the least B with B^2 (n_register_state + C n_ring_lines) >= T n_state C, rounded up like
 // recording_block_rows.  Without a ring line the rule IS recording_block_rows.
-static uint32_t ring_recording_block_rows(const Graph& g, uint32_t T, uint32_t C, uint32_t block_rows)
+// far: the recording of the far family -- the far lines are further tape lines of a block, B n_far_lines rows more, so they count with
+// the ring lines (n_state counts their slots and phase rows: a block start costs D + 1 rows per far line, so the blocks are long);
+// the sum of their depths, the adjoint ring, does not depend on B.  Without a far line the rule IS the ring rule.
+static uint32_t ring_recording_block_rows(const Graph& g, uint32_t T, uint32_t C, uint32_t block_rows, bool far = false)
 {
    const RingLayout rl = ring_layout(g);
-   if (!rl.n_rl()) return recording_block_rows(T, C, block_rows);
+   const uint32_t lines = rl.n_rl() + (far ? rl.n_fl() : 0u);
+   if (!lines) return recording_block_rows(T, C, block_rows);
    if (block_rows) return std::min(block_rows, T);
-   const uint64_t m = std::max<uint32_t>(4u, C), den = (uint64_t)rl.n_reg() + (uint64_t)C * rl.n_rl(), num = (uint64_t)T * g.n_state * C;
+   const uint64_t m = std::max<uint32_t>(4u, C), den = (uint64_t)rl.n_reg() + (uint64_t)C * lines, num = (uint64_t)T * g.n_state * C;
    uint64_t B = (uint64_t)std::ceil(std::sqrt((double)num / (double)den));
    while (B && (B - 1) * (B - 1) * den >= num) --B;          // (whatever sqrt rounded: B is the least integer with B^2 den >= num)
    while (B * B * den < num) ++B;
@@ -392,7 +409,7 @@ struct GradCall {
    float grad_scale;
    float *loss, *out;
    bool ring = false;          // the call is of the ring family (fz_run_block_ring_*, fz_run_recording_ring_*): its scope, Variant and workspace
-   bool far = false;           // the call is of the far family (fz_run_block_far_*): a ring call that takes lines deeper than 256 samples too
+   bool far = false;           // the call is of the far family (fz_run_block_far_*, fz_run_recording_far_*): a ring call that takes lines deeper than 256 samples too
 };
 
 template <class Args>
@@ -470,7 +487,7 @@ static bool check_grad(fz_program* p, const GradCall& call, uint64_t n_streams, 
    if (a->loss_rule && !a->ybar) fail(FZ_E_INVALID, "target is null: the loss compares the outputs with it");
    require_pointer(a->ybar, g.n_out, "out_grad", "output wires");
    const uint64_t need = rec ? rec->need : ring_workspace_bytes(g, n_streams, n_samples, v);
-   const std::string ws_fn = rec ? (a->ring ? "fz_program_ring_recording_workspace" : "fz_program_recording_workspace") : a->far ? "fz_program_far_grad_workspace" : a->ring ? "fz_program_ring_grad_workspace" : "fz_program_grad_workspace";
+   const std::string ws_fn = rec ? (a->far ? "fz_program_far_recording_workspace" : a->ring ? "fz_program_ring_recording_workspace" : "fz_program_recording_workspace") : a->far ? "fz_program_far_grad_workspace" : a->ring ? "fz_program_ring_grad_workspace" : "fz_program_grad_workspace";
    if (need && !a->workspace) fail(FZ_E_INVALID, "workspace is null: " + ws_fn + " says " + std::to_string(need) + " bytes");
    if (need && a->workspace_bytes < need)
       fail(FZ_E_INVALID, "workspace_bytes " + std::to_string(a->workspace_bytes) + " is less than the " + std::to_string(need) + " bytes " + ws_fn + " asks for");
@@ -558,7 +575,8 @@ static uint64_t recording_workspace_bytes(const Graph& g, uint64_t n_streams, ui
 }
 
 // the workspace of a ring recording (the one home of this rule): the block-start states, then one block's ring workspace -- v is the
-// block launches' Variant; for a graph without a ring line this is recording_workspace_bytes
+// block launches' Variant; for a graph without a ring line this is recording_workspace_bytes.  The far family's is the same sum with the
+// far block Variant (ring_workspace_bytes counts the far lines' tape and adjoint ring then): no rule of its own
 static uint64_t ring_recording_workspace_bytes(const Graph& g, uint64_t n_streams, uint32_t T, uint32_t B, const Variant& v)
 {
    return T ? starts_bytes(g, n_streams, T, B) + ring_workspace_bytes(g, n_streams, B, v) : 0;
@@ -567,16 +585,18 @@ static uint64_t ring_recording_workspace_bytes(const Graph& g, uint64_t n_stream
 // The backward of a recording: the states kernel once, then the block launches from the last block to the first (the contract is in
 // include/flowz_hip.h).  Every check -- of the call over its T rows, then of every block launch as a direct call would be checked --
 // runs before a device is needed.  call.ring: the recording of the ring family, in either layout -- the scope, the states kernel, B
-// and the workspace are that family's, the rest is shared.
+// and the workspace are that family's, the rest is shared.  call.far: the recording of the far family (time-major frames) -- the same
+// again with the far makers; the far states kernel keeps its working rings in the rows behind `starts`, the head of the block
+// workspace, which no block launch has used yet, and the block launches are the far adjoint kernels unchanged.
 static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
                          uint32_t block_rows, float* state_out, void* stream)
 {
    const Graph& g = p->g;
    const bool stream_major = layout_is_stream_major(layout);
-   require_scope(g, call.ring);                            // (scope first: the refusals of fz_program_grad_check, fz_program_ring_grad_check)
+   require_scope(g, call.ring, call.far);                  // (scope first: the refusals of fz_program_grad_check, fz_program_ring_grad_check, fz_program_far_grad_check)
    // (a graph without delay lines launches no states kernel: its LDS patch is not asked to fit)
-   const Variant sv = !g.n_state ? Variant{} : states_variant(g, call.ring, stream_major);
-   auto rows_per_block = [&](uint32_t C) { return call.ring ? ring_recording_block_rows(g, n_samples, C, block_rows) : recording_block_rows(n_samples, C, block_rows); };
+   const Variant sv = !g.n_state ? Variant{} : states_variant(g, call.ring, stream_major, call.far);
+   auto rows_per_block = [&](uint32_t C) { return call.ring ? ring_recording_block_rows(g, n_samples, C, block_rows, call.far) : recording_block_rows(n_samples, C, block_rows); };
    if (!stream_major && block_rows % 4)
       fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
    if (!stream_major && (row0 || (rows_total && rows_total != n_samples)))
@@ -587,7 +607,7 @@ static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, u
    Variant v;
    {
       // (C is needed for the workspace the checks ask for; block_variant validates checkpoint_rows and the loss's outputs)
-      const Variant v0 = block_variant(g, call.checkpoint_rows, call.ring, stream_major, call.loss_rule);
+      const Variant v0 = block_variant(g, call.checkpoint_rows, call.ring, stream_major, call.loss_rule, call.far);
       const uint32_t B0 = n_samples ? rows_per_block(v0.U) : 0;
       const RecordingCheck rec{call.ring ? ring_recording_workspace_bytes(g, n_streams, n_samples, B0, v0) : recording_workspace_bytes(g, n_streams, n_samples, B0, v0.U), state_out};
       if (!check_grad(p, call, n_streams, n_samples, sm, &v, &rec)) return FZ_OK;
@@ -704,7 +724,7 @@ int fz_program_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t 
       return grad_source(p, buf, cap, [&] { return VARIANT; });                                                              \
    }
 
-// (block_variant(g, C, ring, stream-major, loss) and states_variant(g, ring, stream-major) are the two makers)
+// (block_variant(g, C, ring, stream-major, loss, far) and states_variant(g, ring, stream-major, far) are the two makers)
 FZ_INSPECTION(grad, _for, "fz_program_grad_resources", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, false, FZ_SM, false))
 FZ_INSPECTION(loss_grad, _for, "fz_program_loss_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, false, FZ_SM, true))
 FZ_INSPECTION(ring_grad, , "fz_program_ring_grad_resources", FZ_ARG_C, block_variant(p->g, checkpoint_rows, true, false, false))
@@ -716,6 +736,7 @@ FZ_INSPECTION(far_loss_grad, , "fz_program_far_loss_grad_resources", FZ_ARG_C, b
 FZ_INSPECTION(states, , "fz_program_states_resources", FZ_ARG_LAYOUT, states_variant(p->g, false, FZ_SM))
 FZ_INSPECTION(ring_states, , "fz_program_ring_states_resources", , states_variant(p->g, true, false))
 FZ_INSPECTION(ring_states, _for, "fz_program_ring_states_resources_for", FZ_ARG_LAYOUT, states_variant(p->g, true, FZ_SM))
+FZ_INSPECTION(far_states, , "fz_program_far_states_resources", , states_variant(p->g, true, false, true))
 #undef FZ_INSPECTION
 #undef FZ_SM
 #undef FZ_ARG_LAYOUT
@@ -823,6 +844,41 @@ int fz_run_block_far_grad(fz_program* p, const fz_grad_args* a, uint64_t n_strea
 int fz_run_block_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
    FZ_GUARD(return run_grad(p, far_call_of(p, a), n_streams, n_samples, hip_stream);)
+}
+
+int fz_program_far_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows)
+{
+   FZ_GUARD(
+      if (!p || !rows) fail(FZ_E_INVALID, "fz_program_far_recording_block_rows: bad arguments");
+      const Variant v = block_variant(p->g, checkpoint_rows, true, false, false, true);
+      if (n_rows >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
+      *rows = n_rows ? ring_recording_block_rows(p->g, n_rows, v.U, block_rows, true) : 0;
+      return FZ_OK;)
+}
+
+int fz_program_far_recording_workspace(const fz_program* p, uint64_t n_streams, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows,
+                                       uint64_t* bytes)
+{
+   FZ_GUARD(
+      if (!p || !bytes) fail(FZ_E_INVALID, "fz_program_far_recording_workspace: bad arguments");
+      const Variant v = block_variant(p->g, checkpoint_rows, true, false, false, true);
+      if (block_rows % 4) fail(FZ_E_INVALID, "block_rows must be a multiple of 4 on time-major frames: the blocks are pointer offsets and keep the 16-byte alignment");
+      if (n_rows >= (1u << 31)) fail(FZ_E_INVALID, "a recording must be shorter than 2^31 rows");
+      const uint32_t B = n_rows ? ring_recording_block_rows(p->g, n_rows, v.U, block_rows, true) : 0;
+      *bytes = ring_recording_workspace_bytes(p->g, n_streams, n_rows, B, v);
+      return FZ_OK;)
+}
+
+int fz_run_recording_far_grad(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows, float* state_out,
+                              void* hip_stream)
+{
+   FZ_GUARD(return run_recording(p, far_call_of(p, a), FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
+}
+
+int fz_run_recording_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, uint32_t block_rows,
+                                   float* state_out, void* hip_stream)
+{
+   FZ_GUARD(return run_recording(p, far_call_of(p, a), FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
 }
 
 int fz_program_ring_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows)

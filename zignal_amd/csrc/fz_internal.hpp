@@ -283,13 +283,17 @@ constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // group, block = 256 / 128 / 64}: fz_grad.cpp: ring_sm_geometry chooses P and block together and states_variant is the one place that
 // makes one.
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
-// internal, with FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING (optionally FZ_VF_ADJOINT_LOSS; never FZ_VF_ADJOINT_SM or FZ_VF_STATES): the
+// internal, with FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING (optionally FZ_VF_ADJOINT_LOSS; never FZ_VF_ADJOINT_SM): the
 // adjoint kernel of a graph with delay lines DEEPER THAN 256 SAMPLES, whose rings live in HBM (fz_grad.cpp: fz_run_block_far_grad,
 // fz_run_block_far_loss_grad; fz_kernel_adjoint_far.hip.inc: a text and a symbol of its own, the pending adjoints of the far lines
 // in a ring in the workspace).  The flag 1u is one of the reserved ones -- a forward variant naming it stays refused -- and the flags
 // 1u, 2u and 4u otherwise mean something next to FZ_VF_PCM16 only (FZ_VF_PCM16_IN / _OUT / _B16 below); next to FZ_VF_ADJOINT 1u is this.
 // Such a Variant is {P = 1, U = checkpoint rows, block = the ring rule's answer for the graph's LDS ring lines alone, 256 without
 // any}; fz_grad.cpp: block_variant is the one place that makes one, and only for a graph that has a far line.
+// With FZ_VF_STATES next to the two (never FZ_VF_ADJOINT_LOSS): the block-start-states kernel of a far recording
+// (fz_run_recording_far_grad; fz_kernel_states_far.hip.inc: a text and a symbol of its own, the far lines' values in a working ring in
+// the workspace), {P = 1, U = the rows of one unrolled group, at most 8, block = the far adjoint kernel's}; fz_grad.cpp:
+// states_variant is the one place that makes one, and only for a graph that has a far line.
 constexpr uint32_t FZ_VF_ADJOINT_FAR = 1u;
 // internal: the kernel for 16-bit PCM frames (fz_pcm16.cpp, fz_kernel_pcm16.hip.inc), one of the reserved bits -- no caller's variant
 // names it -- and, meaningful with it only, three more: `in` is int16, `out` is int16, the int16 rows are off the dword grid (2-byte
@@ -391,6 +395,9 @@ std::string grad_unsupported_reason(const Graph& g, bool rings_in_lds = false, b
 // once -- when no slot is touched twice within a chunk of C rows: every far read at least C rows old, any two of one line at least
 // C apart; else the per-row path.
 bool far_read_with_chunk(uint32_t delay, uint32_t C);
+// the far states kernel's static rule (the same home): a far read travels with the next group's x rows when its delay is at least
+// two groups of U rows -- the slot it reads was written before the request is issued; else it is a load of its own in front of its row
+bool far_read_with_next_group(uint32_t delay, uint32_t U);
 bool far_fast_path(const Graph& g, uint32_t C);
 // could the backward have made this Variant of the adjoint family (FZ_VF_ADJOINT and the family bits next to it) for this graph?
 // The flag set names the call; v fits when that call, asked for v's stride, makes exactly v: fz_grad.cpp

@@ -375,8 +375,9 @@ _GRAD_ENTRY = {
     (True, False, True, True): "fz_run_recording_ring_grad_stream_major",
     (True, True, True, True): "fz_run_recording_ring_loss_grad_stream_major",
 }
-# the far family (delay lines deeper than 256 samples): one block of time-major frames, by loss
-_FAR_GRAD_ENTRY = {False: "fz_run_block_far_grad", True: "fz_run_block_far_loss_grad"}
+# the far family (delay lines deeper than 256 samples), time-major frames: by (loss, recording)
+_FAR_GRAD_ENTRY = {(False, False): "fz_run_block_far_grad", (True, False): "fz_run_block_far_loss_grad",
+                   (False, True): "fz_run_recording_far_grad", (True, True): "fz_run_recording_far_loss_grad"}
 
 
 class Program:
@@ -1003,6 +1004,42 @@ class Program:
         only, the workspace of run_block_far_grad.  For a graph run_block_ring_loss_grad takes it is run_block_ring_loss_grad."""
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), None), ring=True, far=True)
 
+    # -- the backward of a whole recording with delay lines deeper than 256 samples (fz_run_recording_far_grad) ----------------------
+    def far_recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
+        """the rows per block run_recording_far_grad cuts a recording of T rows into (block_rows = 0: the library's choice, which
+        counts the far lines among the tape lines; include/flowz_hip.h has the rule).  Without a far line: ring_recording_block_rows"""
+        return _out(ctypes.c_uint32, C.lib.fz_program_far_recording_block_rows, self._h, int(T), int(block_rows), int(checkpoint_rows))
+
+    def far_recording_workspace_bytes(self, n_streams: int, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
+        """workspace bytes of run_recording_far_grad / run_recording_far_loss_grad: the block-start states, then one block's far workspace"""
+        return _out(ctypes.c_uint64, C.lib.fz_program_far_recording_workspace, self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows))
+
+    def far_states_resources(self) -> dict:
+        """grad_resources() of the block-start-states kernel of a far recording; 'unroll' = the rows of its unrolled group, 'lds_bytes' =
+        the value rings of the LDS ring lines of one workgroup (the far lines keep their working rings in the workspace)"""
+        return _resources(C.lib.fz_program_far_states_resources, self._h)
+
+    def far_states_kernel_symbol(self) -> str:
+        return _name(C.lib.fz_program_far_states_kernel_symbol, self._h)
+
+    def far_states_source(self) -> str:
+        return _text(C.lib.fz_program_far_states_source, self._h)
+
+    def run_recording_far_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0,
+                               block_rows: int = 0, workspace=None):
+        """run_block_far_grad over a whole recording in bounded workspace (fz_run_recording_far_grad), as run_recording_ring_grad is to
+        run_block_ring_grad: every bit is run_block_far_grad's over the same rows, "state_out" may be named in want.  Time-major
+        frames only.  For a graph run_recording_ring_grad takes it is run_recording_ring_grad."""
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None, None, (int(block_rows), workspace),
+                              ring=True, far=True)
+
+    def run_recording_far_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT,
+                                    accum=None, checkpoint_rows: int = 0, block_rows: int = 0, out=None, workspace=None):
+        """run_block_far_loss_grad over a whole recording (fz_run_recording_far_loss_grad): the arguments, results and bits of the
+        one-launch call over the same rows, plus "state_out" in want.  Time-major frames only."""
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), out),
+                              (int(block_rows), workspace), ring=True, far=True)
+
     # -- the backward of a whole recording with delay lines deeper than 8 samples (fz_run_recording_ring_grad) -----------------------
     def ring_recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
         """the rows per block run_recording_ring_grad cuts a recording of T rows into (block_rows = 0: the library's choice, which
@@ -1069,7 +1106,8 @@ class Program:
         (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
         (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is of the ring family:
         run_block_ring_grad / run_block_ring_loss_grad, or with recording run_recording_ring_grad / run_recording_ring_loss_grad, and their
-        _stream_major twins; far (with ring, one block of time-major frames): run_block_far_grad / run_block_far_loss_grad"""
+        _stream_major twins; far (with ring, time-major frames): run_block_far_grad / run_block_far_loss_grad, or with recording
+        run_recording_far_grad / run_recording_far_loss_grad"""
         import torch
 
         if far:
@@ -1139,7 +1177,8 @@ class Program:
         if recording is None:
             wsb = (self.far_grad_workspace_bytes if far else self.ring_grad_workspace_bytes if ring else self.grad_workspace_bytes)(ns, T, checkpoint_rows)
         else:
-            wsb = self.ring_recording_workspace_bytes(ns, T, recording[0], checkpoint_rows) if ring else \
+            wsb = self.far_recording_workspace_bytes(ns, T, recording[0], checkpoint_rows) if far else \
+                self.ring_recording_workspace_bytes(ns, T, recording[0], checkpoint_rows) if ring else \
                 self.recording_workspace_bytes(ns, T, recording[0], checkpoint_rows, window is not None)
             if "state_out" in want:
                 out["state_out"] = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=dev)
@@ -1173,7 +1212,7 @@ class Program:
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
         hs = torch.cuda.current_stream().cuda_stream
-        fn = getattr(C.lib, _FAR_GRAD_ENTRY[loss is not None] if far else _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
+        fn = getattr(C.lib, _FAR_GRAD_ENTRY[(loss is not None, recording is not None)] if far else _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
         if recording is not None and ring and window is not None:     # ring recording window
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
         elif recording is not None and ring:                          # ring recording
