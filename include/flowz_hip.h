@@ -701,7 +701,8 @@ int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint6
 
 /* fz_run_block_far_grad, fz_run_block_far_loss_grad -- the two one-launch calls for graphs with delay lines DEEPER THAN 256 SAMPLES
  * (echoes, reverb combs, low plucked strings), whose rings live in HBM: a call family next to the fz_run_block_ring_grad family, as
- * that one stands next to fz_run_block_grad.  fz_grad_args and fz_loss_grad_args are taken unchanged; time-major frames only.
+ * that one stands next to fz_run_block_grad.  fz_grad_args and fz_loss_grad_args are taken unchanged; time-major frames (stream-major buffers:
+ * fz_run_block_far_grad_stream_major below).
  *
  * THE CONTRACT.  Rules 1 - 4 of the ORDER OF OPERATIONS of fz_run_block_grad do not mention depth, and THE RULE of
  * fz_run_block_loss_grad applies as written: the bits are defined.  What is new is where a far line's adjoints lie in the caller's
@@ -718,8 +719,8 @@ int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint6
  *
  * Scope (fz_program_far_grad_check): fz_program_ring_grad_check's, plus float delay lines deeper than 256 samples.  Still refused,
  * with the reasons they have there: typed programs, float64 nodes, complex wires, modulators, LDS rings that fit no workgroup.  For a
- * graph without a far line these calls ARE the fz_..._ring_ calls: the same kernel, symbol, workspace and bits.  Every other call of
- * the backward keeps refusing a graph with a far line.
+ * graph without a far line these calls ARE the fz_..._ring_ calls: the same kernel, symbol, workspace and bits.  Every call of
+ * the backward outside the far family keeps refusing a graph with a far line.
  *
  * The kernel, fz_adjoint_far_kernel_c<C>b<lanes>_g<tag> (fz_adjoint_far_loss_kernel_... under the loss): register lines and LDS ring
  * lines are what they are in the ring kernel.  Of a far line the forward sweep writes the source's value of every row into the tape
@@ -746,6 +747,43 @@ int fz_program_far_loss_grad_resources(fz_program* p, uint32_t checkpoint_rows, 
 long fz_program_far_loss_grad_kernel_symbol(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
 long fz_program_far_loss_grad_source(fz_program* p, uint32_t checkpoint_rows, char* buf, size_t cap);
 int fz_run_block_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream);
+
+/* fz_run_block_far_grad_stream_major, fz_run_block_far_loss_grad_stream_major -- the two one-launch calls of the
+ * fz_run_block_far_grad family on STREAM-MAJOR buffers (a [batch, time] tensor as it lies).  The args structs are taken unchanged.
+ *
+ * THE CONTRACT IS A REFERENCE: every output bit is that of fz_run_block_far_grad / fz_run_block_far_loss_grad on the transposed
+ * buffers.  Windows (rows_total, row0, n_samples) and the alignment of the buffers are those of fz_run_block_grad_stream_major: only
+ * the rows of the window of in_grad (and of out) are written.  state, state_grad, state0_grad, params, the accumulators and the
+ * workspace are [row][n_streams] in both layouts, so a far line's slot rows and phase row are those of fz_run_block_far_grad: the
+ * phase is read from `state` and reduced modulo D, the phase row of state0_grad is written +0.0f, the phase row of state_grad is
+ * never read, and blocks chain through state0_grad slot for slot as they do there.
+ *
+ * Scope: fz_program_far_grad_check's.  For a graph without a far line these calls ARE fz_run_block_ring_grad_stream_major /
+ * fz_run_block_ring_loss_grad_stream_major (which for a graph without a ring line are the plain stream-major calls): the same
+ * kernel, symbol, workspace and bits.  Checks: those of fz_run_block_ring_grad_stream_major, in its order, before a device is needed;
+ * a short workspace names fz_program_far_grad_workspace, which answers both layouts.
+ *
+ * The kernel, fz_adjoint_far_sm_kernel_c<C>r<R>b<lanes>_g<tag> (fz_adjoint_far_loss_sm_kernel_...): the far kernel's sweeps, C, static
+ * rules and paths; the frames move through a wave-private LDS patch of R rows as in the stream-major ring kernel.  The far lines use
+ * no LDS: lanes per workgroup and R are the stream-major ring rule's answer for the LDS ring lines alone plus the patches, R
+ * starting from half the ring kernels' longest patch and never below max(4, C) (a 1-in / 1-out graph without an LDS ring line at
+ * C = 16: 256 lanes, R = 16, 36 864 bytes).  A graph whose LDS rings plus the shortest patch
+ * fit no workgroup is refused with the bytes named.  fz_program_far_grad_*_for / fz_program_far_loss_grad_*_for inspect the kernel
+ * of either layout (FZ_GRAD_TIME_MAJOR: what fz_program_far_grad_* answer).
+ *
+ * Not built for graphs with a far line: the recording calls on stream-major buffers (fz_run_recording_ring_grad_stream_major keeps
+ * refusing), a forward body for HBM rings on stream-major buffers (fz_run_block_stream_major keeps refusing), double or complex far
+ * lines. */
+int fz_run_block_far_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
+                                       void* hip_stream);
+int fz_run_block_far_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                            uint32_t n_samples, void* hip_stream);
+int fz_program_far_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out);
+long fz_program_far_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+long fz_program_far_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+int fz_program_far_loss_grad_resources_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, fz_kernel_resources* out);
+long fz_program_far_loss_grad_kernel_symbol_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
+long fz_program_far_loss_grad_source_for(fz_program* p, uint32_t checkpoint_rows, uint32_t layout, char* buf, size_t cap);
 
 /* fz_run_block_ring_grad_stream_major, fz_run_block_ring_loss_grad_stream_major -- the two one-launch calls of the
  * fz_run_block_ring_grad family on STREAM-MAJOR buffers.  The args structs are taken unchanged.

@@ -77,6 +77,11 @@ at the default stride agrees bit for bit with the one at C = 1 (another chunking
 formula of DESIGN.md 9.11 (counted from the code, not measured) as a fraction of 8 TB/s.  There is no pass mark.  The table goes to stdout
 and to profiles/r17/far_grad.txt.
 
+--far --layout compare [--loss]: the far backward on stream-major buffers, run_block_far_grad_stream_major
+(fz_run_block_far_grad_stream_major; with --loss run_block_far_loss_grad_stream_major), against the route a caller with stream-major
+buffers had before it existed, with the legs, the method and the mark of --rings --layout compare: workloads.far_comb, the 2000-sample
+comb and far_tap1.  The table goes to stdout and to profiles/r19/far_stream_major.txt.
+
 --far --recording: the squared-error backward of a whole recording of graphs with delay lines deeper than 256 samples,
 run_recording_far_loss_grad (fz_run_recording_far_loss_grad: one far states launch, then the far loss kernel per block in reverse), with
 the legs, the shapes, the method and the mark of --rings --recording: one = the one-launch run_block_far_loss_grad where its workspace
@@ -85,7 +90,7 @@ reverse at the same B.  workloads.far_comb (300 samples) and ~(0.5*_1[_2000] + _
 profiles/r18/far_recording.txt.
 
 usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings] [--far]
-       (--far takes --recording)
+       (--far takes --recording, or --layout compare, alone or with --loss)
        (--rings takes --layout compare, alone or with --loss; --rings --recording takes --layout stream-major|compare, alone or with --loss)
 """
 import argparse
@@ -530,25 +535,28 @@ def far_bench(a, torch):
         f.write("\n".join(lines) + "\n")
 
 
-def rings_compare_bench(a, torch):
+def rings_compare_bench(a, torch, far=False):
     """the ring backward on stream-major buffers (plain, or with a.loss under the squared-error loss) against transpose + the time-major
-    ring call + transpose, interleaved in one process; the two legs agree bit for bit before a time is printed"""
+    ring call + transpose, interleaved in one process; the two legs agree bit for bit before a time is printed.  far: the same for
+    graphs with delay lines in HBM, through the far family's calls"""
     import time
     lines = []
+    fam = "far" if far else "ring"
 
     def say(line):
         print(line, flush=True)
         lines.append(line)
     props = torch.cuda.get_device_properties(0)
     loss = bool(a.loss)
-    call = "run_block_ring_loss_grad" if loss else "run_block_ring_grad"
-    say(f"# command: tools/grad_bench.py --rings --layout compare{' --loss' if loss else ''} --steps {a.steps} --legs {a.legs}")
+    call = f"run_block_{fam}_loss_grad" if loss else f"run_block_{fam}_grad"
+    say(f"# command: tools/grad_bench.py {'--far' if far else '--rings'} --layout compare{' --loss' if loss else ''} --steps {a.steps} --legs {a.legs}")
     say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
     say(f"# sm = one {call}_stream_major launch on [n_streams, T] buffers; route = fz_transpose_frames of x and of {'the target' if loss else 'dL/dy'}, {call}, fz_transpose_frames of dL/dx back;")
     say(f"# every gradient, default checkpoint stride; HIP events, {a.steps} launches per leg and pass, a forward and a")
     say("# backward pass over the legs; spread = max - min of the route's own repeats; the legs agree bit for bit (dL/dx, the state gradient" + (", the loss" if loss else "") + ") before a time is printed")
-    say(f"{'graph':16s} {'streams x T':>16s} {'route ms':>9s} {'spread':>7s} {'sm ms':>9s} {'sm/route':>9s} {'slower':>6s} {'C':>3s} {'R':>3s} {'lanes':>5s} {'vgprs':>6s} {'sgpr spills':>11s} {'lds':>6s}  stream-major ring kernel")
+    say(f"{'graph':16s} {'streams x T':>16s} {'route ms':>9s} {'spread':>7s} {'sm ms':>9s} {'sm/route':>9s} {'slower':>6s} {'C':>3s} {'R':>3s} {'lanes':>5s} {'vgprs':>6s} {'sgpr spills':>11s} {'lds':>6s}  stream-major {fam} kernel")
     shapes = SHAPES["large"] + SHAPES["small"] if a.legs == "all" else SHAPES[a.legs]
+    graphs = {k: v for k, v in FAR_GRAPHS.items() if k != "comb256"} if far else RING_GRAPHS
     for ns, T in shapes:
         x_sm = torch.empty((ns, T, 1), dtype=torch.float32, device="cuda")
         F.synth_fill(x_sm, seed=W.SEED)
@@ -558,24 +566,25 @@ def rings_compare_bench(a, torch):
         x_tm, yt_tm = (torch.empty((T, ns, 1), dtype=torch.float32, device="cuda") for _ in range(2))
         n = float(ns) * T
         want = ("x", "state", "params", "consts") + (("loss",) if loss else ())
-        for name, fn in RING_GRAPHS.items():
+        for name, fn in graphs.items():
             prog = F.compile(F.from_sexpr(fn()))
             s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
+            tm_call, sm_call = getattr(prog, call), getattr(prog, call + "_stream_major")
 
             def route():
                 F.frames_from_stream_major(x_sm, 0, out=x_tm)
                 F.frames_from_stream_major(yt_sm, 0, out=yt_tm)
                 if loss:
-                    r = prog.run_block_ring_loss_grad(x_tm, yt_tm, s0, None, state_grad=s0, grad_scale=2.0 / n, want=want)
+                    r = tm_call(x_tm, yt_tm, s0, None, state_grad=s0, grad_scale=2.0 / n, want=want)
                 else:
-                    r = prog.run_block_ring_grad(x_tm, yt_tm, s0, None, state_grad=s0)
+                    r = tm_call(x_tm, yt_tm, s0, None, state_grad=s0)
                 F.frames_to_stream_major(r["x"], out=gx_back)
                 return r
 
             def sm():
                 if loss:
-                    return prog.run_block_ring_loss_grad_stream_major(x_sm, yt_sm, s0, None, state_grad=s0, grad_scale=2.0 / n, want=want, in_grad=gx_sm)
-                return prog.run_block_ring_grad_stream_major(x_sm, yt_sm, s0, None, state_grad=s0, in_grad=gx_sm)
+                    return sm_call(x_sm, yt_sm, s0, None, state_grad=s0, grad_scale=2.0 / n, want=want, in_grad=gx_sm)
+                return sm_call(x_sm, yt_sm, s0, None, state_grad=s0, in_grad=gx_sm)
             legs = {"route": route, "sm": sm}
             first = {k: f() for k, f in legs.items()}           # JIT, allocator; and the legs agree bit for bit
             torch.cuda.synchronize()
@@ -594,8 +603,8 @@ def rings_compare_bench(a, torch):
                     got[k] += samples(legs[k], a.steps, torch)
             med = {k: float(np.median(v)) for k, v in got.items()}
             spread = max(got["route"]) - min(got["route"])
-            res = (prog.ring_loss_grad_resources if loss else prog.ring_grad_resources)(0, stream_major=True)
-            sym = (prog.ring_loss_grad_kernel_symbol if loss else prog.ring_grad_kernel_symbol)(0, stream_major=True)
+            res = getattr(prog, f"{fam}_loss_grad_resources" if loss else f"{fam}_grad_resources")(0, stream_major=True)
+            sym = getattr(prog, f"{fam}_loss_grad_kernel_symbol" if loss else f"{fam}_grad_kernel_symbol")(0, stream_major=True)
             R, lanes = int(sym.split("_g")[0].split("r")[-1].split("b")[0]), int(sym.split("_g")[0].split("b")[-1])
             say(f"{name:16s} {f'{ns} x {T}':>16s} {med['route']:9.3f} {spread:7.3f} {med['sm']:9.3f} {med['sm'] / med['route']:9.3f} "
                 f"{'YES' if med['sm'] > med['route'] + spread else 'no':>6s} {res['unroll']:3d} {R:3d} {lanes:5d} {res['vgprs'] + res['agprs']:6d} "
@@ -605,7 +614,7 @@ def rings_compare_bench(a, torch):
             torch.cuda.empty_cache()
         del x_sm, yt_sm, gx_sm, gx_back, x_tm, yt_tm
         torch.cuda.empty_cache()
-    out = os.path.join(ROOT, "profiles", "r15", "ring_stream_major.txt")
+    out = os.path.join(ROOT, "profiles", "r19", "far_stream_major.txt") if far else os.path.join(ROOT, "profiles", "r15", "ring_stream_major.txt")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "a" if loss and os.path.exists(out) else "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -883,6 +892,8 @@ def main():
     torch.cuda.set_device(0)
     if a.far and a.recording:
         return rings_recording_bench(a, torch, far=True)
+    if a.far and a.layout == "compare":
+        return rings_compare_bench(a, torch, far=True)
     if a.far:
         return far_bench(a, torch)
     if a.rings and a.recording and a.layout != "time-major":

@@ -13,10 +13,13 @@ usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par
        tools/isa_stats.py ringlossgrad [graph] [--layout stream-major]
                                                            the same line for the kernel of fz_run_block_ring_loss_grad, next to the plain
                                                            ring kernel's figures (graph: also a name of tests/ring_loss_graphs.py)
-       tools/isa_stats.py fargrad [graph]                  the same lines for the kernel of fz_run_block_far_grad (delay lines deeper than
+       tools/isa_stats.py fargrad [graph] [--layout stream-major]
+                                                           the same lines for the kernel of fz_run_block_far_grad (delay lines deeper than
                                                            256 samples, rings in HBM), with the path its static rule picks (graph: a name
-                                                           of tests/far_grad_graphs.py, comb2000, or any ringgrad graph)
-       tools/isa_stats.py farlossgrad [graph]              the same for the kernel of fz_run_block_far_loss_grad, next to the plain far kernel
+                                                           of tests/far_grad_graphs.py, comb2000, or any ringgrad graph); --layout
+                                                           stream-major: the kernel of fz_run_block_far_grad_stream_major
+       tools/isa_stats.py farlossgrad [graph] [--layout stream-major]
+                                                           the same for the kernel of fz_run_block_far_loss_grad, next to the plain far kernel
        tools/isa_stats.py ringstates [graph] [--layout stream-major]
                                                            the block-start-states kernel of fz_run_recording_ring_grad next to the ring
                                                            adjoint kernel: registers, spills, scratch, LDS bytes, and the ds_* and
@@ -100,13 +103,14 @@ def ring_grad_lines(name, loss=False, sm=False, far=False):
     loss: the kernel of fz_run_block_ring_loss_grad, with the plain ring kernel's registers and spills next to its own.
     sm: the kernels for stream-major buffers (their per-row ds_* include the row's frames read from and written to the LDS patch; the
     patch fetch and flush are outside the chunks and cancel)
-    far: the kernels of the far family (fz_run_block_far_grad, fz_run_block_far_loss_grad; time-major only), with the path of sweep 2"""
+    far: the kernels of the far family (fz_run_block_far_grad, fz_run_block_far_loss_grad, sm: their _stream_major twins), with the
+    path of sweep 2"""
     import far_grad_graphs as FG
     import ring_loss_graphs as RL
     build = (FG.FARS.get(name) if far else None) or RL.GRAPHS.get(name) or GRAPHS[name]
     p = F.compile(F.from_sexpr(build()))
     if far:
-        resources = (lambda q, c=0: q.far_loss_grad_resources(c)) if loss else (lambda q, c=0: q.far_grad_resources(c))
+        resources = (lambda q, c=0: q.far_loss_grad_resources(c, stream_major=sm)) if loss else (lambda q, c=0: q.far_grad_resources(c, stream_major=sm))
     else:
         resources = (lambda q, c=0: q.ring_loss_grad_resources(c, stream_major=sm)) if loss else (lambda q, c=0: q.ring_grad_resources(c, stream_major=sm))
     r = resources(p)
@@ -132,8 +136,8 @@ def ring_grad_lines(name, loss=False, sm=False, far=False):
         else:
             os.environ["FLOWZ_HIP_CACHE"] = old
     if far:
-        plain = p.far_grad_resources(0) if loss else None
-        sym = p.far_loss_grad_kernel_symbol(0) if loss else p.far_grad_kernel_symbol(0)
+        plain = p.far_grad_resources(0, stream_major=sm) if loss else None
+        sym = p.far_loss_grad_kernel_symbol(0, stream_major=sm) if loss else p.far_grad_kernel_symbol(0, stream_major=sm)
         src = p.far_grad_source(0)
         sym += " (" + ("no far line" if "FZ_FAR_FAST" not in src else "fast path" if "#define FZ_FAR_FAST 1 " in src else "per-row path") + ")"
     else:
@@ -229,7 +233,7 @@ def main():
         print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring", loss=True, sm=sm)))
         return
     if a and a[0] in ("fargrad", "farlossgrad"):
-        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "far_comb", loss=a[0] == "farlossgrad", far=True)))
+        print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "far_comb", loss=a[0] == "farlossgrad", sm=sm, far=True)))
         return
     if a and a[0] == "states":
         print(states_line(a[1] if len(a) > 1 else "cascade_params6", len(a) > 2 and a[2] == "sm"))

@@ -202,6 +202,14 @@ def _load():
         "fz_program_far_loss_grad_kernel_symbol": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_far_loss_grad_source": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_run_block_far_loss_grad": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u64, u32, P]),
+        "fz_run_block_far_grad_stream_major": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, u32, u32, P]),
+        "fz_run_block_far_loss_grad_stream_major": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u64, u32, u32, u32, P]),
+        "fz_program_far_grad_resources_for": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_far_grad_kernel_symbol_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_far_grad_source_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_far_loss_grad_resources_for": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_far_loss_grad_kernel_symbol_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_far_loss_grad_source_for": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_far_recording_block_rows": (ctypes.c_int, [P, u32, u32, u32, ctypes.POINTER(u32)]),
         "fz_program_far_recording_workspace": (ctypes.c_int, [P, u64, u32, u32, u32, ctypes.POINTER(u64)]),
         "fz_run_recording_far_grad": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, u32, P, P]),

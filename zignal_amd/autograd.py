@@ -13,9 +13,12 @@ run_rings(..., stream_major=True) takes the stream-major tensors of run(..., str
 Program.run_block_stream_major, the backward Program.run_block_ring_grad_stream_major, and nothing is transposed.
 
 run_far(prog, x, state, params, consts) is run_rings() for graphs with delay lines deeper than 256 samples as well (echoes, reverb
-combs, low plucked strings), whose rings live in HBM: time-major frames only, the backward is Program.run_block_far_grad
+combs, low plucked strings), whose rings live in HBM: time-major frames, the backward is Program.run_block_far_grad
 (include/flowz_hip.h: fz_run_block_far_grad).  The rows of such a line in `state` are ring slots and one more row holds the phase: a
 zero state has phase 0, and the state gradient's phase rows are zero.  run_rings() keeps refusing such graphs.
+run_far(..., stream_major=True) takes the stream-major tensors of run(..., stream_major=True): the backward is
+Program.run_block_far_grad_stream_major on the tensors as they lie; the forward has no stream-major body for rings in HBM and goes
+through the layout adapter (two extra passes over the frames).
 
 mse(prog, x, target, ...) is the mean squared error of one block against a target as ONE launch (Program.run_block_loss_grad:
 the adjoint kernel forms y, the error and dL/dy itself), where run() followed by ((y - target) ** 2).mean() is a forward launch,
@@ -26,6 +29,8 @@ adjoint kernel with the loss formed in it); mse() keeps refusing graphs with del
 mse_rings(..., stream_major=True) is the same on stream-major tensors (Program.run_block_ring_loss_grad_stream_major).
 
 mse_far(prog, x, target, ...) is mse_rings() for every graph run_far() takes, time-major (Program.run_block_far_loss_grad).
+mse_far(..., stream_major=True) is the same on stream-major tensors (Program.run_block_far_loss_grad_stream_major): one launch on a
+[batch, time] tensor as it lies, no forward launch and nothing transposed.
 
 mse_recording(prog, x, target, ...) is the same loss over a whole recording of many blocks in bounded workspace
 (Program.run_recording_loss_grad: one forward launch that keeps the state before every block, then the loss kernel block by block
@@ -46,7 +51,7 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-from .flowz import FlowzError, Program
+from .flowz import FlowzError, Program, frames_from_stream_major, frames_to_stream_major
 from . import _capi as C
 
 
@@ -104,8 +109,13 @@ class _Block(torch.autograd.Function):
         _apply_consts(prog, consts)
         ctx.rings = rings
         st = state.detach().clone() if state is not None else None    # (the caller's state is never advanced in place)
-        fwd = prog.run_block_stream_major if stream_major else prog.run_block
-        y, st = fwd(x.detach(), st, params.detach() if params is not None else None)
+        if stream_major and rings == "far" and not prog.ring_grad_supported():
+            # (a line in HBM: no forward body for it on stream-major buffers -- the layout adapter around the time-major forward)
+            y, st = prog.run_block(frames_from_stream_major(x.detach()), st, params.detach() if params is not None else None)
+            y = frames_to_stream_major(y)
+        else:
+            fwd = prog.run_block_stream_major if stream_major else prog.run_block
+            y, st = fwd(x.detach(), st, params.detach() if params is not None else None)
         ctx.prog = prog
         ctx.stream_major = stream_major
         ctx.consts = consts.detach().clone() if consts is not None else None
@@ -159,13 +169,18 @@ def run_rings(prog: Program, x, state=None, params=None, consts=None, stream_maj
     return _run(prog, x, state, params, consts, stream_major, True)
 
 
-def run_far(prog: Program, x, state=None, params=None, consts=None):
-    """run_rings() for graphs with delay lines deeper than 256 samples -- and every graph run_rings() takes --, time-major frames only:
+def run_far(prog: Program, x, state=None, params=None, consts=None, stream_major=False):
+    """run_rings() for graphs with delay lines deeper than 256 samples -- and every graph run_rings() takes --, time-major frames:
     returns (y [T, n_streams, n_out], state after the block).  The forward is Program.run_block, the backward
     Program.run_block_far_grad.  The rows of a line deeper than 256 samples are ring slots in `state` and in its gradient, and the
     line's phase row (behind all line rows) is 0 in a zero state and has a zero gradient.  Chaining it over consecutive blocks
-    back-propagates through time across them: the state after a block carries the phase the next block starts from."""
-    return _run(prog, x, state, params, consts, False, "far")
+    back-propagates through time across them: the state after a block carries the phase the next block starts from.
+    stream_major: the tensor shapes of run(..., stream_major=True) -- x [n_streams, T, n_in], or [n_streams, T] for one input wire, y
+    [n_streams, T, n_out].  The backward is Program.run_block_far_grad_stream_major on the tensors as they lie: it costs no extra pass.
+    The forward does: there is no forward kernel body for rings in HBM on stream-major buffers, so x is transposed
+    (frames_from_stream_major), run through Program.run_block and y transposed back (frames_to_stream_major) -- two extra passes over
+    the frames.  The state rows are [row, n_streams] in either layout, so blocks chain as in the time-major call."""
+    return _run(prog, x, state, params, consts, stream_major, "far")
 
 
 class _Mse(torch.autograd.Function):
@@ -221,12 +236,14 @@ def mse_rings(prog: Program, x, target, state=None, params=None, consts=None, st
     return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), True, None)
 
 
-def mse_far(prog: Program, x, target, state=None, params=None, consts=None):
-    """mse_rings() for graphs with delay lines deeper than 256 samples -- and every graph mse_rings() takes --, time-major frames only:
+def mse_far(prog: Program, x, target, state=None, params=None, consts=None, stream_major=False):
+    """mse_rings() for graphs with delay lines deeper than 256 samples -- and every graph mse_rings() takes --, time-major frames:
     the scalar ((y - target) ** 2).mean() of one block, differentiable in x, state, params and consts.  One launch, made in the forward
-    (Program.run_block_far_loss_grad, include/flowz_hip.h: fz_run_block_far_loss_grad); backward() applies the upstream scalar."""
+    (Program.run_block_far_loss_grad, include/flowz_hip.h: fz_run_block_far_loss_grad); backward() applies the upstream scalar.
+    stream_major: the tensor shapes of mse(..., stream_major=True), a [batch, time] tensor as it lies for one wire: one launch of
+    Program.run_block_far_loss_grad_stream_major, no forward launch, nothing transposed."""
     _front_door(prog, x, consts, "far")
-    return _Mse.apply(prog, x, target, state, params, consts, False, "far", None)
+    return _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), "far", None)
 
 
 def mse_recording(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0, stream_major=False):

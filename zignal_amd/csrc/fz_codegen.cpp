@@ -30,6 +30,7 @@ extern const char* const kSkeletonAdjointSm;
 extern const char* const kSkeletonAdjointRing;
 extern const char* const kSkeletonAdjointRingSm;
 extern const char* const kSkeletonAdjointFar;    // fz_kernel_adjoint_far.hip.inc: delay lines deeper than 256 samples, rings in HBM
+extern const char* const kSkeletonAdjointFarSm;  // fz_kernel_adjoint_far_sm.hip.inc: the same on stream-major buffers
 extern const char* const kSkeletonStates;        // fz_kernel_states.hip.inc: plain and, with FZ_RING, ring
 extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: the same
 extern const char* const kSkeletonStatesFar;     // fz_kernel_states_far.hip.inc: the states kernel of a graph with rings in HBM
@@ -54,6 +55,7 @@ static const AdjointRow& adjoint_row(const Variant& v)
       {FZ_VF_ADJOINT_RING, "fz_adjoint_ring", "", kSkeletonAdjointRing, false},
       {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_adjoint_ring", "_sm", kSkeletonAdjointRingSm, true},
       {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, "fz_adjoint_far", "", kSkeletonAdjointFar, false},
+      {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR | FZ_VF_ADJOINT_SM, "fz_adjoint_far", "_sm", kSkeletonAdjointFarSm, true},
       {FZ_VF_STATES, "fz_states", "", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_SM, "fz_states", "_sm", kSkeletonStatesSm, true},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStates, false},

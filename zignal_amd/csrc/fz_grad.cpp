@@ -6,7 +6,7 @@
 //   fz_run_block_grad[_stream_major]                  fz_kernel_adjoint.hip.inc         fz_kernel_adjoint_sm.hip.inc
 //   fz_run_block_ring_grad[_stream_major]             fz_kernel_adjoint_ring.hip.inc    fz_kernel_adjoint_ring_sm.hip.inc
 //     (delay lines in LDS: FZ_VF_ADJOINT_RING)
-//   fz_run_block_far_grad                             fz_kernel_adjoint_far.hip.inc     (not built)
+//   fz_run_block_far_grad[_stream_major]              fz_kernel_adjoint_far.hip.inc     fz_kernel_adjoint_far_sm.hip.inc
 //     (delay lines in HBM as well: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR)
 //   fz_run_recording_grad: the block-start states     fz_kernel_states.hip.inc          fz_kernel_states_sm.hip.inc
 //     (FZ_VF_STATES)
@@ -15,7 +15,7 @@
 //   fz_run_recording_far_grad: the same               fz_kernel_states_far.hip.inc      (not built)
 //     (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR)
 //
-// Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the four adjoint kernels forms dL/dy itself, from a
+// Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the adjoint kernels forms dL/dy itself, from a
 // target: the same text with FZ_LOSS, the same C, workgroup and workspace.  The ring calls share the checks and the launch with the
 // others; for a graph without a ring line each IS its plain sibling (same Variant, kernel, symbol, workspace, bits).  The far calls
 // stand to the ring calls as those stand to the plain ones: for a graph without a line deeper than 256 samples each IS its ring
@@ -168,7 +168,8 @@ static uint32_t adjoint_flags(const Graph& g, uint32_t family_bits, bool loss)
    return FZ_VF_ADJOINT | family_bits | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
 }
 
-// (the far kernels are built for time-major frames only: the one reason both makers give)
+// (the far states kernel is built for time-major frames only: the reason states_variant gives; the far adjoint kernel has a text for
+//  either layout)
 static const char* const kFarStreamMajor = "delay lines deeper than 256 samples (rings in HBM) are not supported by the backward on stream-major buffers";
 
 static uint32_t family_bits(bool ring, bool stream_major) { return (ring ? FZ_VF_ADJOINT_RING : 0u) | (stream_major ? FZ_VF_ADJOINT_SM : 0u); }
@@ -180,7 +181,14 @@ static uint32_t family_bits(bool ring, bool stream_major) { return (ring ? FZ_VF
 // loss: the kernel forms dL/dy itself (FZ_VF_ADJOINT_LOSS next to the family bits); C, block and workspace do not change with it.
 // far: the call is of the far family (a ring call as well); for a graph without a line deeper than 256 samples its Variant is the ring
 // call's.  With one: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, the far kernel's C (grad_default_checkpoint), and the workgroup the ring
-// rule gives the graph's LDS ring lines alone -- the far lines take no LDS --, 256 lanes without any.  Time-major frames only.
+// rule gives the graph's LDS ring lines alone -- the far lines take no LDS --, 256 lanes without any.  On stream-major buffers
+// (fz_kernel_adjoint_far_sm.hip.inc) the same rule chooses R and the block together over those LDS ring slots -- none for a graph
+// whose deep lines are all far -- and the patch: the ring call's Rmin and its refusal when nothing fits, and R0 =
+// max(grad_sm_patch_rows(g, C) / 2, Rmin), HALF the ring call's: one stream's run is half a cache line in the wider frame.  Measured
+// (profiles/r19/far_stream_major.txt): the far kernel waits on the tape and the adjoint ring in HBM, a dependent round trip per row
+// on the per-row path, and hides that behind waves; with the ring call's R0 (69 632 bytes of patches per 256 lanes, 138 registers:
+// two waves per SIMD) a 2000-sample comb at 1 048 576 x 1024 took 1.16 x the time of the transposing route, with half of it (36 864
+// bytes, 121 registers: four waves) 0.87 x; the 65 536 x 4096 lines pay 0.05 of the route's time for the shorter runs.
 static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring, bool stream_major, bool loss, bool far = false)
 {
    ring = ring || far;
@@ -188,16 +196,17 @@ static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring
    const RingLayout rl = ring ? ring_layout(g) : RingLayout{};
    const uint32_t slots = rl.slots, wires = g.n_in + g.n_out;
    const bool far_lines = rl.n_fl() != 0;
-   if (far_lines && stream_major) fail(FZ_E_UNSUPPORTED, kFarStreamMajor);
    Variant v;
    v.P = 1;
    v.U = checkpoint_of(g, checkpoint_rows, slots != 0 || far_lines);
    v.block = kGradBlock;
    v.flags = adjoint_flags(g, family_bits(slots != 0 || far_lines, stream_major) | (far_lines ? FZ_VF_ADJOINT_FAR : 0u), loss);
-   if (slots) {
+   if (slots || (far_lines && stream_major)) {
       const LaneLds lane{slots, stream_major ? wires : 0u, stream_major ? 4u : 0u};
       const uint32_t Rmin = stream_major ? std::max<uint32_t>(4u, v.U) : 1u;
-      const RingSmGeometry geo = ring_sm_geometry(lane, stream_major ? grad_sm_patch_rows(g, v.U) : 1u, Rmin);
+      // (far lines: R0 is half the ring kernel's, see above)
+      const uint32_t R0 = !stream_major ? 1u : far_lines ? std::max(grad_sm_patch_rows(g, v.U) / 2, Rmin) : grad_sm_patch_rows(g, v.U);
+      const RingSmGeometry geo = ring_sm_geometry(lane, R0, Rmin);
       if (!geo.block)                                       // (stream-major only: rings alone fit, require_scope has asked)
          fail(FZ_E_UNSUPPORTED, "stream-major ring backward: the rings of the delay lines deeper than 8 samples (" + std::to_string(slots) + " samples) plus a patch of " +
                                    std::to_string(Rmin) + " rows of " + std::to_string(wires) + " wires, " + std::to_string(lane.bytes(64, Rmin)) +
@@ -265,7 +274,8 @@ bool grad_variant_fits(const Graph& g, const Variant& v)
    const bool ring = v.flags & FZ_VF_ADJOINT_RING, sm = v.flags & FZ_VF_ADJOINT_SM, loss = v.flags & FZ_VF_ADJOINT_LOSS, far = v.flags & FZ_VF_ADJOINT_FAR;
    try {
       // (the far bit without the ring bit or on a graph without a far line: no maker answers with it; next to FZ_VF_STATES the states
-      //  maker answers with its own U, at most 8, and never with the loss or the stream-major bit beside the far one)
+      //  maker answers with its own U, at most 8, and never with the loss or the stream-major bit beside the far one; next to the
+      //  stream-major bit the block maker answers with its own R in P: 1, a non-power of two or an R below C is none)
       const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss, far) : states_variant(g, ring, sm, far);
       return w.P == v.P && w.U == v.U && w.block == v.block && w.flags == v.flags;
    } catch (const Error&) {
@@ -733,6 +743,8 @@ FZ_INSPECTION(ring_loss_grad, , "fz_program_ring_loss_grad_resources", FZ_ARG_C,
 FZ_INSPECTION(ring_loss_grad, _for, "fz_program_ring_loss_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, true, FZ_SM, true))
 FZ_INSPECTION(far_grad, , "fz_program_far_grad_resources", FZ_ARG_C, block_variant(p->g, checkpoint_rows, true, false, false, true))
 FZ_INSPECTION(far_loss_grad, , "fz_program_far_loss_grad_resources", FZ_ARG_C, block_variant(p->g, checkpoint_rows, true, false, true, true))
+FZ_INSPECTION(far_grad, _for, "fz_program_far_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, true, FZ_SM, false, true))
+FZ_INSPECTION(far_loss_grad, _for, "fz_program_far_loss_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, true, FZ_SM, true, true))
 FZ_INSPECTION(states, , "fz_program_states_resources", FZ_ARG_LAYOUT, states_variant(p->g, false, FZ_SM))
 FZ_INSPECTION(ring_states, , "fz_program_ring_states_resources", , states_variant(p->g, true, false))
 FZ_INSPECTION(ring_states, _for, "fz_program_ring_states_resources_for", FZ_ARG_LAYOUT, states_variant(p->g, true, FZ_SM))
@@ -844,6 +856,22 @@ int fz_run_block_far_grad(fz_program* p, const fz_grad_args* a, uint64_t n_strea
 int fz_run_block_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t n_samples, void* hip_stream)
 {
    FZ_GUARD(return run_grad(p, far_call_of(p, a), n_streams, n_samples, hip_stream);)
+}
+
+int fz_run_block_far_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
+                                       void* hip_stream)
+{
+   FZ_GUARD(
+      const SmWindow w{rows_total, row0};
+      return run_grad(p, far_call_of(p, a), n_streams, n_samples, hip_stream, &w);)
+}
+
+int fz_run_block_far_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                            uint32_t n_samples, void* hip_stream)
+{
+   FZ_GUARD(
+      const SmWindow w{rows_total, row0};
+      return run_grad(p, far_call_of(p, a), n_streams, n_samples, hip_stream, &w);)
 }
 
 int fz_program_far_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows)

@@ -283,14 +283,17 @@ constexpr uint32_t FZ_VF_STATES = 1u << 16;
 // group, block = 256 / 128 / 64}: fz_grad.cpp: ring_sm_geometry chooses P and block together and states_variant is the one place that
 // makes one.
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
-// internal, with FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING (optionally FZ_VF_ADJOINT_LOSS; never FZ_VF_ADJOINT_SM): the
+// internal, with FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING (optionally FZ_VF_ADJOINT_LOSS): the
 // adjoint kernel of a graph with delay lines DEEPER THAN 256 SAMPLES, whose rings live in HBM (fz_grad.cpp: fz_run_block_far_grad,
 // fz_run_block_far_loss_grad; fz_kernel_adjoint_far.hip.inc: a text and a symbol of its own, the pending adjoints of the far lines
 // in a ring in the workspace).  The flag 1u is one of the reserved ones -- a forward variant naming it stays refused -- and the flags
 // 1u, 2u and 4u otherwise mean something next to FZ_VF_PCM16 only (FZ_VF_PCM16_IN / _OUT / _B16 below); next to FZ_VF_ADJOINT 1u is this.
 // Such a Variant is {P = 1, U = checkpoint rows, block = the ring rule's answer for the graph's LDS ring lines alone, 256 without
 // any}; fz_grad.cpp: block_variant is the one place that makes one, and only for a graph that has a far line.
-// With FZ_VF_STATES next to the two (never FZ_VF_ADJOINT_LOSS): the block-start-states kernel of a far recording
+// With FZ_VF_ADJOINT_SM next to the two (with or without FZ_VF_ADJOINT_LOSS): the far kernels for STREAM-MAJOR buffers
+// (fz_run_block_far_grad_stream_major, fz_run_block_far_loss_grad_stream_major; fz_kernel_adjoint_far_sm.hip.inc: a text of its own),
+// {P = the patch rows R, U = checkpoint rows, block}: the stream-major ring rule over the LDS ring lines alone, from half its R0.
+// With FZ_VF_STATES next to the two (never FZ_VF_ADJOINT_LOSS or FZ_VF_ADJOINT_SM): the block-start-states kernel of a far recording
 // (fz_run_recording_far_grad; fz_kernel_states_far.hip.inc: a text and a symbol of its own, the far lines' values in a working ring in
 // the workspace), {P = 1, U = the rows of one unrolled group, at most 8, block = the far adjoint kernel's}; fz_grad.cpp:
 // states_variant is the one place that makes one, and only for a graph that has a far line.

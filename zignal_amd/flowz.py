@@ -378,6 +378,8 @@ _GRAD_ENTRY = {
 # the far family (delay lines deeper than 256 samples), time-major frames: by (loss, recording)
 _FAR_GRAD_ENTRY = {(False, False): "fz_run_block_far_grad", (True, False): "fz_run_block_far_loss_grad",
                    (False, True): "fz_run_recording_far_grad", (True, True): "fz_run_recording_far_loss_grad"}
+# (loss): the far family's one-launch calls on stream-major buffers; its recording calls are built for time-major frames only
+_FAR_GRAD_SM_ENTRY = {False: "fz_run_block_far_grad_stream_major", True: "fz_run_block_far_loss_grad_stream_major"}
 
 
 class Program:
@@ -970,16 +972,17 @@ class Program:
         ring of the far lines, one row per slot"""
         return _out(ctypes.c_uint64, C.lib.fz_program_far_grad_workspace, self._h, int(n_streams), int(T), int(checkpoint_rows))
 
-    def far_grad_resources(self, c: int = 0) -> dict:
+    def far_grad_resources(self, c: int = 0, stream_major: bool = False) -> dict:
         """grad_resources() of the kernel of run_block_far_grad at checkpoint stride c (0: the library default); 'lds_bytes' = the
-        adjoint rings of the LDS ring lines alone: the far lines take none"""
-        return _resources(C.lib.fz_program_far_grad_resources, self._h, int(c))
+        adjoint rings of the LDS ring lines alone: the far lines take none.  stream_major: the kernel of
+        run_block_far_grad_stream_major ('lds_bytes': those rings and the patches)"""
+        return _resources(C.lib.fz_program_far_grad_resources_for, self._h, int(c), int(bool(stream_major)))
 
-    def far_grad_kernel_symbol(self, c: int = 0) -> str:
-        return _name(C.lib.fz_program_far_grad_kernel_symbol, self._h, int(c))
+    def far_grad_kernel_symbol(self, c: int = 0, stream_major: bool = False) -> str:
+        return _name(C.lib.fz_program_far_grad_kernel_symbol_for, self._h, int(c), int(bool(stream_major)))
 
-    def far_grad_source(self, c: int = 0) -> str:
-        return _text(C.lib.fz_program_far_grad_source, self._h, int(c))
+    def far_grad_source(self, c: int = 0, stream_major: bool = False) -> str:
+        return _text(C.lib.fz_program_far_grad_source_for, self._h, int(c), int(bool(stream_major)))
 
     def run_block_far_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0):
         """run_block_ring_grad for graphs with delay lines deeper than 256 samples (fz_run_block_far_grad): the same arguments, the same
@@ -987,15 +990,24 @@ class Program:
         its phase row follows the line rows (zero in "state").  For a graph run_block_ring_grad takes it is run_block_ring_grad."""
         return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None, ring=True, far=True)
 
-    def far_loss_grad_resources(self, c: int = 0) -> dict:
-        """far_grad_resources() of the kernel of run_block_far_loss_grad at checkpoint stride c (0: the library default)"""
-        return _resources(C.lib.fz_program_far_loss_grad_resources, self._h, int(c))
+    def run_block_far_grad_stream_major(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None,
+                                        checkpoint_rows: int = 0, row0: int = 0, n_samples: Optional[int] = None, in_grad=None):
+        """run_block_far_grad on stream-major buffers (fz_run_block_far_grad_stream_major): the arguments, windows and result dict of
+        run_block_ring_grad_stream_major; not a bit differs from run_block_far_grad on the transposed frames.  The state rows are
+        [row, n_streams] in both layouts: a far line's slot rows and phase row are run_block_far_grad's.  For a graph
+        run_block_ring_grad_stream_major takes it is run_block_ring_grad_stream_major."""
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad), ring=True, far=True)
 
-    def far_loss_grad_kernel_symbol(self, c: int = 0) -> str:
-        return _name(C.lib.fz_program_far_loss_grad_kernel_symbol, self._h, int(c))
+    def far_loss_grad_resources(self, c: int = 0, stream_major: bool = False) -> dict:
+        """far_grad_resources() of the kernel of run_block_far_loss_grad at checkpoint stride c (0: the library default);
+        stream_major: of run_block_far_loss_grad_stream_major"""
+        return _resources(C.lib.fz_program_far_loss_grad_resources_for, self._h, int(c), int(bool(stream_major)))
 
-    def far_loss_grad_source(self, c: int = 0) -> str:
-        return _text(C.lib.fz_program_far_loss_grad_source, self._h, int(c))
+    def far_loss_grad_kernel_symbol(self, c: int = 0, stream_major: bool = False) -> str:
+        return _name(C.lib.fz_program_far_loss_grad_kernel_symbol_for, self._h, int(c), int(bool(stream_major)))
+
+    def far_loss_grad_source(self, c: int = 0, stream_major: bool = False) -> str:
+        return _text(C.lib.fz_program_far_loss_grad_source_for, self._h, int(c), int(bool(stream_major)))
 
     def run_block_far_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT, accum=None,
                                 checkpoint_rows: int = 0):
@@ -1003,6 +1015,15 @@ class Program:
         arguments, the same result dict, the rule of run_block_loss_grad and then the order of run_block_far_grad; time-major frames
         only, the workspace of run_block_far_grad.  For a graph run_block_ring_loss_grad takes it is run_block_ring_loss_grad."""
         return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), None), ring=True, far=True)
+
+    def run_block_far_loss_grad_stream_major(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0,
+                                             want=LOSS_GRAD_WANT, accum=None, checkpoint_rows: int = 0, row0: int = 0,
+                                             n_samples: Optional[int] = None, in_grad=None, out=None):
+        """run_block_far_loss_grad on stream-major buffers (fz_run_block_far_loss_grad_stream_major): the arguments, windows and
+        result dict of run_block_ring_loss_grad_stream_major, in_grad and out included; not a bit differs from run_block_far_loss_grad
+        on the transposed frames.  For a graph run_block_ring_loss_grad_stream_major takes it is that call."""
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, _window(x, row0, n_samples, in_grad), (float(grad_scale), out),
+                              ring=True, far=True)
 
     # -- the backward of a whole recording with delay lines deeper than 256 samples (fz_run_recording_far_grad) ----------------------
     def far_recording_block_rows(self, T: int, block_rows: int = 0, checkpoint_rows: int = 0) -> int:
@@ -1106,8 +1127,8 @@ class Program:
         (grad_scale, out tensor or None) of the squared-error backward, whose target comes as out_grad; recording: None (one block), or
         (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is of the ring family:
         run_block_ring_grad / run_block_ring_loss_grad, or with recording run_recording_ring_grad / run_recording_ring_loss_grad, and their
-        _stream_major twins; far (with ring, time-major frames): run_block_far_grad / run_block_far_loss_grad, or with recording
-        run_recording_far_grad / run_recording_far_loss_grad"""
+        _stream_major twins; far (with ring): run_block_far_grad / run_block_far_loss_grad and their _stream_major twins, or with
+        recording (time-major frames) run_recording_far_grad / run_recording_far_loss_grad"""
         import torch
 
         if far:
@@ -1212,7 +1233,8 @@ class Program:
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
         hs = torch.cuda.current_stream().cuda_stream
-        fn = getattr(C.lib, _FAR_GRAD_ENTRY[(loss is not None, recording is not None)] if far else _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
+        fn = getattr(C.lib, _FAR_GRAD_SM_ENTRY[loss is not None] if far and window is not None else
+                     _FAR_GRAD_ENTRY[(loss is not None, recording is not None)] if far else _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
         if recording is not None and ring and window is not None:     # ring recording window
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
         elif recording is not None and ring:                          # ring recording
