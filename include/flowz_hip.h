@@ -722,8 +722,9 @@ int fz_run_block_ring_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint6
  * graph without a far line these calls ARE the fz_..._ring_ calls: the same kernel, symbol, workspace and bits.  Every call of
  * the backward outside the far family keeps refusing a graph with a far line.
  *
- * The kernel, fz_adjoint_far_kernel_c<C>b<lanes>_g<tag> (fz_adjoint_far_loss_kernel_... under the loss): register lines and LDS ring
- * lines are what they are in the ring kernel.  Of a far line the forward sweep writes the source's value of every row into the tape
+ * The kernel, fz_adjoint_far_kernel_c<C>b<lanes>_g<tag> (fz_adjoint_far_loss_kernel_... under the loss), is the ring kernel's text
+ * with its far mode compiled in (in every layout, and for the states kernel of a recording: one text, a compile-time switch, a
+ * symbol of its own): register lines and LDS ring lines are what they are in the ring kernel.  Of a far line the forward sweep writes the source's value of every row into the tape
  * (the far lines are further tape lines) and reads its delayed values back from the tape rows it wrote -- for t < d from the caller's
  * slot (p0 + t - d) mod D.  STATIC RULE 1: a far read at least C rows old is requested with its chunk's x rows; a younger one is a
  * load of its own in front of its row.  The pending adjoints live in an adjoint ring in the workspace, one coalesced row per slot.

@@ -6,14 +6,19 @@ on the compiler, like the code ids of tests/golden/graph_pins.json.
 The kernels: for every graph of grad_graphs.SUPPORTED the adjoint, loss and states kernel in both layouts at the default stride; for every
 ring graph (ring_sm_graphs.GRAPHS, which holds those of ring_grad_graphs, ring_loss_graphs and ring_recording_graphs) at every stride of
 ring_sm_graphs.STRIDES the ring and ring loss kernel in both layouts -- where the geometry rule refuses, the pin is the refusal's text --
-and the ring states kernel in both layouts.
+and the ring states kernel in both layouts; for every far graph (far_grad_graphs.FARS) the far and far loss kernel in both layouts at
+the default stride, for those of far_grad_graphs.STRIDES at C = 1 and C = 32 as well -- the strides the GPU tests launch; a refusal is
+pinned as for the ring entries -- and the time-major far states kernel.
 
 The committed file was written by pins() from the parent commit of the change that folded the loss kernels into their siblings, in a
 checkout of its own:
     PYTHONPATH=<parent checkout>:tests python tests/adjoint_code_pins.py > tests/golden/adjoint_code_pins.json
 The ring_states/sm/* entries are younger than that kernel: they were written the same way from the parent commit of the change that
 folded the four block-start-states texts into one per layout (the commit that added the stream-major ring states kernel), with the
-requests() of this file; the 214 entries the file held before came out of that tree byte for byte as they stood."""
+requests() of this file; the 214 entries the file held before came out of that tree byte for byte as they stood.
+The far/*, far_loss/* and far_states/* entries are younger still: they were written the same way from the parent commit of the change
+that folded the three far texts into their ring siblings (FZ_FAR next to FZ_RING), before any text was merged, with the requests() of
+this file; the 224 entries the file held before came out of that tree byte for byte as they stood, so the file only gained lines."""
 import hashlib
 import json
 import os
@@ -23,12 +28,12 @@ import subprocess
 import sys
 import tempfile
 
-from grad_host_harness import ADJOINT, ADJOINT_LOSS, ADJOINT_RING, ADJOINT_SM, STATES
+from grad_host_harness import ADJOINT, ADJOINT_FAR, ADJOINT_LOSS, ADJOINT_RING, ADJOINT_SM, STATES
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PINS = os.path.join(HERE, "golden", "adjoint_code_pins.json")
 SECTIONS = (".text", ".rodata", ".note")
-SYMBOL = re.compile(r"fz_(adjoint|states)(_ring)?(_loss)?(_sm)?_kernel_[cu](\d+)(?:r(\d+))?b(\d+)_g[0-9a-f]{8}")
+SYMBOL = re.compile(r"fz_(adjoint|states)(_ring|_far)?(_loss)?(_sm)?_kernel_[cu](\d+)(?:r(\d+))?b(\d+)_g[0-9a-f]{8}")
 
 
 def elf_sections(data):
@@ -49,12 +54,14 @@ def variant_of(symbol):
     """(P, U, block, flags) of the Variant a kernel symbol of the family names"""
     m = SYMBOL.fullmatch(symbol)
     assert m, symbol
-    flags = ADJOINT | (STATES if m.group(1) == "states" else 0) | (ADJOINT_RING if m.group(2) else 0) | (ADJOINT_LOSS if m.group(3) else 0) | (ADJOINT_SM if m.group(4) else 0)
+    rings = {None: 0, "_ring": ADJOINT_RING, "_far": ADJOINT_RING | ADJOINT_FAR}[m.group(2)]
+    flags = ADJOINT | (STATES if m.group(1) == "states" else 0) | rings | (ADJOINT_LOSS if m.group(3) else 0) | (ADJOINT_SM if m.group(4) else 0)
     return int(m.group(6) or 1), int(m.group(5)), int(m.group(7)), flags
 
 
 def requests():
     """(label, s-expression of the graph, name of the Program method that answers the symbol, its arguments)"""
+    import far_grad_graphs as FG
     import grad_graphs as GG
     import ring_grad_graphs as RG
     import ring_loss_graphs as RL
@@ -76,6 +83,13 @@ def requests():
                 layout = "sm" if sm else "tm"
                 out.append((f"ring/{layout}/c{c}/{name}", RS.GRAPHS[name](), "ring_grad_kernel_symbol", (c, sm)))
                 out.append((f"ring_loss/{layout}/c{c}/{name}", RS.GRAPHS[name](), "ring_loss_grad_kernel_symbol", (c, sm)))
+    for name in sorted(FG.FARS):
+        out.append((f"far_states/tm/{name}", FG.FARS[name](), "far_states_kernel_symbol", ()))
+        for c in (0, 1, 32) if name in FG.STRIDES else (0,):
+            for sm in (False, True):
+                layout = "sm" if sm else "tm"
+                out.append((f"far/{layout}/c{c}/{name}", FG.FARS[name](), "far_grad_kernel_symbol", (c, sm)))
+                out.append((f"far_loss/{layout}/c{c}/{name}", FG.FARS[name](), "far_loss_grad_kernel_symbol", (c, sm)))
     return out
 
 

@@ -22,7 +22,7 @@ from zignal_amd import flowz as F
 F32 = np.float32
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-ADJOINT, ADJOINT_SM, ADJOINT_LOSS, STATES, ADJOINT_RING = 1 << 27, 1 << 18, 1 << 17, 1 << 16, 1 << 14     # fz_internal.hpp
+ADJOINT, ADJOINT_SM, ADJOINT_LOSS, STATES, ADJOINT_RING, ADJOINT_FAR = 1 << 27, 1 << 18, 1 << 17, 1 << 16, 1 << 14, 1     # fz_internal.hpp
 LDS_BYTES = 163840                                                # per CU and the most one workgroup may declare (gfx950)
 
 

@@ -5,6 +5,7 @@ import re
 import pytest
 
 import adjoint_code_pins as P
+import far_grad_graphs as FG
 import grad_graphs as GG
 import ring_sm_graphs as RS
 from grad_host_harness import code_pins
@@ -40,6 +41,10 @@ def test_the_pins_cover_every_graph_kernel_layout_and_stride():
         assert {f"ring_states/tm/{name}", f"ring_states/sm/{name}"} <= set(WANT)
         for c in RS.STRIDES:
             assert {f"{kind}/{layout}/c{c}/{name}" for kind in ("ring", "ring_loss") for layout in ("tm", "sm")} <= set(WANT)
+    for name in FG.FARS:
+        assert f"far_states/tm/{name}" in WANT
+        for c in (0, 1, 32) if name in FG.STRIDES else (0,):
+            assert {f"{kind}/{layout}/c{c}/{name}" for kind in ("far", "far_loss") for layout in ("tm", "sm")} <= set(WANT)
     for label, pin in WANT.items():
         assert set(pin) in ({"refused"}, {"symbol"} | set(P.SECTIONS)), label
         if "symbol" in pin:
@@ -58,7 +63,7 @@ def test_the_loss_kernel_is_not_the_plain_kernel(now):
     """the compile-time switch selects code: a loss kernel shares no .text, no descriptor's metadata and no symbol with its sibling"""
     for label, pin in now.items():
         kind, rest = label.split("/", 1)
-        if kind in ("loss", "ring_loss") and "symbol" in pin:
-            plain = now[{"loss": "adjoint", "ring_loss": "ring"}[kind] + "/" + rest]
+        if kind in ("loss", "ring_loss", "far_loss") and "symbol" in pin:
+            plain = now[{"loss": "adjoint", "ring_loss": "ring", "far_loss": "far"}[kind] + "/" + rest]
             assert pin[".text"] != plain[".text"] and pin[".note"] != plain[".note"] and pin["symbol"] == plain["symbol"].replace("_kernel_", "_loss_kernel_", 1) \
                 .replace("_sm_loss_kernel_", "_loss_sm_kernel_"), label

@@ -245,13 +245,13 @@ def test_far_kernel_has_no_fma(name, loss, tmp_path, monkeypatch):
 def test_the_far_kernel_has_a_text_of_its_own():
     p = far_prog("far_mixed")
     src = p.far_grad_source()
-    assert "fz_adj_far_args" in src and "FZ_FAR_SLOTS" in src and "__syncthreads" not in src and "atomicAdd" not in src and "__shared__" in src
+    assert "#define FZ_FAR 1 " in src and "#define FZ_FAR_SLOTS " in src.split("// ==== fz_graph_body.h ====")[0] and "__syncthreads" not in src and "atomicAdd" not in src and "__shared__" in src
     assert "#define FZ_LOSS 0 " in src and "static void out(" not in src
     lsrc = p.far_loss_grad_source()
     assert "#define FZ_LOSS 1 " in lsrc and "static void out(" in lsrc
     assert lsrc.split("// ==== fz_block_kernel.hip.inc ====")[1] == src.split("// ==== fz_block_kernel.hip.inc ====")[1]
     ring = RG.prog("biquad_comb17").ring_grad_source()
-    assert "fz_adj_far_args" not in ring and "FZ_NFL" not in ring
+    assert "#define FZ_FAR 0 " in ring and "FZ_NFL" not in ring.split("// ==== fz_graph_body.h ====")[0]
 
 
 # ---- the static rule that picks the path -------------------------------------------------------------------------------------------------

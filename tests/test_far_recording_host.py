@@ -331,9 +331,11 @@ def test_far_states_kernel_has_no_fma_no_barrier_no_atomic(name, tmp_path, monke
 def test_the_far_states_kernel_has_a_text_of_its_own():
     p = prog("far_mixed")
     src = p.far_states_source()
-    assert "fz_states_args" in src and "fz_dump_far" in src and "fz_dump_state" in src and "FZ_FAR_SLOTS" in src
-    assert "__syncthreads" not in src and "atomicAdd" not in src and "__shared__" in src and "FZ_FAR_FAST" not in src.split("// ==== fz_graph_body.h ====")[0]
-    assert "fz_dump_far" not in RG.prog("biquad_comb17").ring_states_source() and "fz_fr_ahead" not in p.far_grad_source()
+    cfg = src.split("// ==== fz_graph_body.h ====")[0]
+    assert "fz_states_args" in src and "#define FZ_FAR 1 " in cfg and "#define FZ_RING 1 " in cfg and "#define FZ_FAR_SLOTS " in cfg
+    assert "__syncthreads" not in src and "atomicAdd" not in src and "__shared__" in src and "FZ_FAR_FAST" not in cfg
+    ring = RG.prog("biquad_comb17").ring_states_source().split("// ==== fz_graph_body.h ====")[0]
+    assert "#define FZ_FAR 0 " in ring and "FZ_NFL" not in ring and "fz_fr_ahead" not in p.far_grad_source().split("// ==== fz_graph_body.h ====")[0]
 
 
 def ahead(p):

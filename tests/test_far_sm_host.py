@@ -69,7 +69,7 @@ def test_the_graphs_are_taken(name):
         sym = (p.far_loss_grad_kernel_symbol if loss else p.far_grad_kernel_symbol)(0, stream_major=True)
         assert re.fullmatch(r"fz_adjoint_far_%ssm_kernel_c(1|2|4|8|16)r(4|8|16|32|64)b(256|128|64)_g%s" % ("loss_" if loss else "", tag), sym), sym
         src = (p.far_loss_grad_source if loss else p.far_grad_source)(0, stream_major=True)
-        assert "fz_adj_far_sm_args" in src and "#define FZ_LOSS %d " % loss in src and "#define FZ_R " in src and "#define FZ_FAR_SLOTS " in src
+        assert "#define FZ_FAR 1 " in src and "#define FZ_LOSS %d " % loss in src and "#define FZ_R " in src and "#define FZ_FAR_SLOTS " in src
         assert "__syncthreads" not in src and "atomic" not in src.split("extern \"C\"")[1]
         assert ("static void out(" in src) == loss
         # the generated body is the time-major far kernel's: it is layout-free
@@ -78,6 +78,8 @@ def test_the_graphs_are_taken(name):
         for ns, T in ((0, 100), (100, 0), (0, 0)):                # an empty block is FZ_OK with nothing touched
             assert run_sm(p, empty_args(loss), loss, ns, 100, 0, T) == C.FZ_OK, C.last_error()
     assert FS.symbol_geometry(p.far_grad_kernel_symbol(0, True)) == FS.symbol_geometry(p.far_loss_grad_kernel_symbol(0, True))
+    plain = F.compile(F.from_sexpr(GG.SUPPORTED["df1_cascade6"]())).grad_source(0, stream_major=True).split("// ==== fz_graph_body.h ====")[0]
+    assert "FZ_FAR" not in plain and "FZ_NFL" not in plain and "FZ_NFR" not in plain   # (the plain stream-major kernel names no far macro)
 
 
 @pytest.mark.parametrize("name", sorted(n for n in GG.REFUSED if n not in ("lds_ring_comb", "far_comb")))

@@ -518,7 +518,7 @@ def far_bench(a, torch):
             n_fr, n_full = sum(1 for a_, _ in reads if depth[a_] > 256), sum(1 for a_, b_ in reads if depth[a_] > 256 and b_ == depth[a_])
             far_slots = sum(d for d in depths if d > 256)
             fbytes = 4.0 * ns * T * (prog.n_in + prog.n_out + n_fl + n_fr)
-            path = "-" if not n_fl else "fast" if "#define FZ_FAR_FAST 1 " in src else "per-row"
+            path = "-" if not n_fl else "fast" if "#define FZ_FAR_FAST 1 " in src.split("// ==== fz_graph_body.h ====")[0] else "per-row"
             bbytes = ns * T * (4.0 * (3 * prog.n_in + prog.n_out) + 8.0 * n_reg / C + 4.0 * (n_rl + n_fl) + 4.0 * n_rr + 8.0 * n_fr
                                + 4.0 * n_fl * (2 if path == "per-row" else 1) + 8.0 * n_fr - 4.0 * n_full) + 16.0 * far_slots * ns
             say(f"{name:16s} {f'{ns} x {T}':>16s} {med['fwd']:9.3f} {max(got['fwd']) - min(got['fwd']):7.3f} {med['bwd']:9.3f} {med['bwd'] / med['fwd']:8.2f} "

@@ -138,8 +138,8 @@ def ring_grad_lines(name, loss=False, sm=False, far=False):
     if far:
         plain = p.far_grad_resources(0, stream_major=sm) if loss else None
         sym = p.far_loss_grad_kernel_symbol(0, stream_major=sm) if loss else p.far_grad_kernel_symbol(0, stream_major=sm)
-        src = p.far_grad_source(0)
-        sym += " (" + ("no far line" if "FZ_FAR_FAST" not in src else "fast path" if "#define FZ_FAR_FAST 1 " in src else "per-row path") + ")"
+        cfg = p.far_grad_source(0).split("// ==== fz_graph_body.h ====")[0]     # (the generated configuration: one text holds both modes)
+        sym += " (" + ("no far line" if "#define FZ_FAR 1 " not in cfg else "fast path" if "#define FZ_FAR_FAST 1 " in cfg else "per-row path") + ")"
     else:
         plain = p.ring_grad_resources(0, stream_major=sm) if loss else None
         sym = p.ring_loss_grad_kernel_symbol(0, stream_major=sm) if loss else p.ring_grad_kernel_symbol(0, stream_major=sm)
@@ -194,7 +194,7 @@ def ring_states_lines(name, sm=False, far=False):
         import re
         src = p.far_states_source()
         table = [re.search(r"%s\[\d+\] = \{([^}]*)\}" % t, src) for t in ("fz_fr_delay", "fz_fr_ahead")]
-        if "FZ_NFL" in src and all(table):
+        if "#define FZ_FAR 1 " in src.split("// ==== fz_graph_body.h ====")[0] and all(table):
             out.append("  far reads at delays {" + table[0].group(1) + "}: with the next group's x rows {" + table[1].group(1) + "}")
         else:
             out.append("  no far line: the ring states kernel")

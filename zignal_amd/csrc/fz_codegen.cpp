@@ -27,20 +27,18 @@ extern const char* const kSkeletonBody_wave_split;
 extern const char* const kSkeletonBody_frames;
 extern const char* const kSkeletonAdjoint;       // fz_kernel_adjoint.hip.inc: a kernel text of its own, like the five below
 extern const char* const kSkeletonAdjointSm;
-extern const char* const kSkeletonAdjointRing;
-extern const char* const kSkeletonAdjointRingSm;
-extern const char* const kSkeletonAdjointFar;    // fz_kernel_adjoint_far.hip.inc: delay lines deeper than 256 samples, rings in HBM
-extern const char* const kSkeletonAdjointFarSm;  // fz_kernel_adjoint_far_sm.hip.inc: the same on stream-major buffers
-extern const char* const kSkeletonStates;        // fz_kernel_states.hip.inc: plain and, with FZ_RING, ring
-extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: the same
-extern const char* const kSkeletonStatesFar;     // fz_kernel_states_far.hip.inc: the states kernel of a graph with rings in HBM
+extern const char* const kSkeletonAdjointRing;   // fz_kernel_adjoint_ring.hip.inc: rings in LDS and, with FZ_FAR, delay lines deeper than 256 samples, rings in HBM
+extern const char* const kSkeletonAdjointRingSm; // fz_kernel_adjoint_ring_sm.hip.inc: the same on stream-major buffers
+extern const char* const kSkeletonStates;        // fz_kernel_states.hip.inc: plain, with FZ_RING ring, and with FZ_FAR next to it far
+extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: plain and ring (no far mode)
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
 // The adjoint family (fz_grad.cpp), layout x rings plus the states kernels: one row per combination of the family bits next to
 // FZ_VF_ADJOINT, found by exact match: a row per symbol stem.  The loss selects no row: it is FZ_LOSS in the configuration of the row's
 // text and "_loss" in the symbol, fz_<head>[_loss]<tail>_kernel_<c|u><U>[r<P>]b<block>.  The states rows' text is chosen by the layout
-// alone: the ring is FZ_RING in its configuration.
+// alone: the ring is FZ_RING in its configuration.  Neither do the rings in HBM select a text: a far row has its ring sibling's, with
+// FZ_FAR 1 in its configuration.
 struct AdjointRow {
    uint32_t bits;               // of FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_FAR
    const char *head, *tail;     // of the symbol's stem
@@ -54,13 +52,13 @@ static const AdjointRow& adjoint_row(const Variant& v)
       {FZ_VF_ADJOINT_SM, "fz_adjoint", "_sm", kSkeletonAdjointSm, true},
       {FZ_VF_ADJOINT_RING, "fz_adjoint_ring", "", kSkeletonAdjointRing, false},
       {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_adjoint_ring", "_sm", kSkeletonAdjointRingSm, true},
-      {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, "fz_adjoint_far", "", kSkeletonAdjointFar, false},
-      {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR | FZ_VF_ADJOINT_SM, "fz_adjoint_far", "_sm", kSkeletonAdjointFarSm, true},
+      {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, "fz_adjoint_far", "", kSkeletonAdjointRing, false},
+      {FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR | FZ_VF_ADJOINT_SM, "fz_adjoint_far", "_sm", kSkeletonAdjointRingSm, true},
       {FZ_VF_STATES, "fz_states", "", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_SM, "fz_states", "_sm", kSkeletonStatesSm, true},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_states", "_ring_sm", kSkeletonStatesSm, true},
-      {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, "fz_states", "_far", kSkeletonStatesFar, false},
+      {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, "fz_states", "_far", kSkeletonStates, false},
    };
    for (const AdjointRow& r : rows)
       if (r.bits == (v.flags & (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_FAR)) && !((v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_LOSS))) return r;
@@ -1106,6 +1104,7 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v)
       table("fz_rl_slot0", rl.n_rl(), [&](size_t i) { return rl.rl_slot0[i]; }, "per ring line: its first LDS slot");
       table("fz_rr_line", rl.n_rr(), [&](size_t i) { return rl.reads[i].first; }, "per ring read: its ring line");
       table("fz_rr_delay", rl.n_rr(), [&](size_t i) { return rl.reads[i].second; }, "per ring read: its delay in samples");
+      o << "#define FZ_FAR " << ((v.flags & FZ_VF_ADJOINT_FAR) ? 1 : 0) << "   // 1: the delay lines deeper than " << kLdsMaxDepth << " samples keep their rings in HBM\n";
       if (v.flags & FZ_VF_ADJOINT_FAR) {
          o << "#define FZ_NFL " << rl.n_fl() << "   // far lines: delay lines deeper than " << kLdsMaxDepth << " samples, rings in HBM\n";
          o << "#define FZ_NFR " << rl.n_fr() << "   // far reads: distinct (far line, delay) pairs\n";
@@ -1158,7 +1157,7 @@ RingLayout ring_layout(const Graph& g)
    for (size_t l = 0; l < g.lines.size(); ++l) {
       const Line& L = g.lines[l];
       rl.far_of_line.push_back(L.far ? (int)rl.fl_line.size() : -1);
-      if (L.far) {                                          // (neither register rows nor LDS slots: fz_kernel_adjoint_far.hip.inc)
+      if (L.far) {                                          // (neither register rows nor LDS slots: FZ_FAR in fz_kernel_adjoint_ring.hip.inc)
          rl.reg0.push_back(-1);
          rl.ring_of_line.push_back(-1);
          rl.fl_line.push_back((uint32_t)l);
@@ -1191,7 +1190,7 @@ RingLayout ring_layout(const Graph& g)
 // front of its row (the forward shortens the chunk instead, below kFarMinDelay: here the chunk is the checkpoint stride and stays).
 bool far_read_with_chunk(uint32_t delay, uint32_t C) { return delay >= C; }
 
-// The far states kernel (fz_kernel_states_far.hip.inc) requests the x rows of the NEXT group of U rows before the current group runs.
+// The far states kernel (fz_kernel_states.hip.inc with FZ_FAR) requests the x rows of the NEXT group of U rows before the current group runs.
 // A far read may travel with them when the slot it reads was written before that request is issued, whichever row of the next group
 // asks: the youngest source row is that of the group's last row, t0 + 2U - 1 - delay, and it must lie before t0.  A younger read is a
 // load of its own in front of its row.
@@ -1228,7 +1227,7 @@ bool far_fast_path(const Graph& g, uint32_t C)
 // (a read at the full depth finds the slot just reset), receive rule 3's additions in registers in its order and are stored once.
 // Without it -- every ring-free graph -- the text is byte for byte what it was.
 // loss and ring (fz_kernel_adjoint_ring.hip.inc with FZ_LOSS): out() takes rv as well -- a delayed read of a ring line is rv[read] there too.
-// far (FZ_VF_ADJOINT_FAR, fz_kernel_adjoint_far.hip.inc; always with ring): the lines in HBM are neither register rows nor LDS slots.
+// far (FZ_VF_ADJOINT_FAR, fz_kernel_adjoint_ring.hip.inc with FZ_FAR; always with ring): the lines in HBM are neither register rows nor LDS slots.
 // A delayed read of one is rv[n ring reads + far read], fwd() hands its source value out in u[n ring lines + far line], and bwd()
 // treats its pending adjoints as it treats a ring line's, in one of two places.  far == 1, the per-row path: the ring column is the
 // global pointer `fa` with stride `ns` (row fz_fl_slot0 + slot of the workspace ring, fpt[far line] = the slot of the row) -- load,

@@ -6,13 +6,13 @@
 //   fz_run_block_grad[_stream_major]                  fz_kernel_adjoint.hip.inc         fz_kernel_adjoint_sm.hip.inc
 //   fz_run_block_ring_grad[_stream_major]             fz_kernel_adjoint_ring.hip.inc    fz_kernel_adjoint_ring_sm.hip.inc
 //     (delay lines in LDS: FZ_VF_ADJOINT_RING)
-//   fz_run_block_far_grad[_stream_major]              fz_kernel_adjoint_far.hip.inc     fz_kernel_adjoint_far_sm.hip.inc
+//   fz_run_block_far_grad[_stream_major]              the same text with FZ_FAR         the same text with FZ_FAR
 //     (delay lines in HBM as well: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR)
 //   fz_run_recording_grad: the block-start states     fz_kernel_states.hip.inc          fz_kernel_states_sm.hip.inc
 //     (FZ_VF_STATES)
 //   fz_run_recording_ring_grad[_stream_major]:        the same text with FZ_RING        the same text with FZ_RING
 //     the same (FZ_VF_STATES | FZ_VF_ADJOINT_RING)
-//   fz_run_recording_far_grad: the same               fz_kernel_states_far.hip.inc      (not built)
+//   fz_run_recording_far_grad: the same               the same text with FZ_FAR too     (not built)
 //     (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR)
 //
 // Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the adjoint kernels forms dL/dy itself, from a
@@ -182,7 +182,7 @@ static uint32_t family_bits(bool ring, bool stream_major) { return (ring ? FZ_VF
 // far: the call is of the far family (a ring call as well); for a graph without a line deeper than 256 samples its Variant is the ring
 // call's.  With one: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, the far kernel's C (grad_default_checkpoint), and the workgroup the ring
 // rule gives the graph's LDS ring lines alone -- the far lines take no LDS --, 256 lanes without any.  On stream-major buffers
-// (fz_kernel_adjoint_far_sm.hip.inc) the same rule chooses R and the block together over those LDS ring slots -- none for a graph
+// (fz_kernel_adjoint_ring_sm.hip.inc with FZ_FAR) the same rule chooses R and the block together over those LDS ring slots -- none for a graph
 // whose deep lines are all far -- and the patch: the ring call's Rmin and its refusal when nothing fits, and R0 =
 // max(grad_sm_patch_rows(g, C) / 2, Rmin), HALF the ring call's: one stream's run is half a cache line in the wider frame.  Measured
 // (profiles/r19/far_stream_major.txt): the far kernel waits on the tape and the adjoint ring in HBM, a dependent round trip per row
@@ -230,7 +230,7 @@ static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring
 // cache lines, the 256-byte in-run of the forward stream-major long-run bodies: where the rings bound the workgroup anyway the longer
 // run costs no occupancy.  Static, not measured against R0 = states_sm_patch_rows(g).
 // far: as for block_variant -- the scope of the far backward; without a line deeper than 256 samples the ring states Variant itself.
-// With one: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR next to FZ_VF_STATES (fz_kernel_states_far.hip.inc), the same U, and the workgroup
+// With one: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR next to FZ_VF_STATES (fz_kernel_states.hip.inc with FZ_FAR), the same U, and the workgroup
 // the ring rule gives the graph's LDS ring lines alone, 256 lanes without any -- the far adjoint kernel's.  Time-major frames only.
 static Variant states_variant(const Graph& g, bool ring, bool stream_major, bool far = false)
 {

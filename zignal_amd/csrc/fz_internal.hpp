@@ -285,16 +285,16 @@ constexpr uint32_t FZ_VF_STATES = 1u << 16;
 constexpr uint32_t FZ_VF_ADJOINT_RING = 1u << 14;
 // internal, with FZ_VF_ADJOINT | FZ_VF_ADJOINT_RING (optionally FZ_VF_ADJOINT_LOSS): the
 // adjoint kernel of a graph with delay lines DEEPER THAN 256 SAMPLES, whose rings live in HBM (fz_grad.cpp: fz_run_block_far_grad,
-// fz_run_block_far_loss_grad; fz_kernel_adjoint_far.hip.inc: a text and a symbol of its own, the pending adjoints of the far lines
+// fz_run_block_far_loss_grad; fz_kernel_adjoint_ring.hip.inc with FZ_FAR: the ring text, a symbol of its own, the pending adjoints of the far lines
 // in a ring in the workspace).  The flag 1u is one of the reserved ones -- a forward variant naming it stays refused -- and the flags
 // 1u, 2u and 4u otherwise mean something next to FZ_VF_PCM16 only (FZ_VF_PCM16_IN / _OUT / _B16 below); next to FZ_VF_ADJOINT 1u is this.
 // Such a Variant is {P = 1, U = checkpoint rows, block = the ring rule's answer for the graph's LDS ring lines alone, 256 without
 // any}; fz_grad.cpp: block_variant is the one place that makes one, and only for a graph that has a far line.
 // With FZ_VF_ADJOINT_SM next to the two (with or without FZ_VF_ADJOINT_LOSS): the far kernels for STREAM-MAJOR buffers
-// (fz_run_block_far_grad_stream_major, fz_run_block_far_loss_grad_stream_major; fz_kernel_adjoint_far_sm.hip.inc: a text of its own),
+// (fz_run_block_far_grad_stream_major, fz_run_block_far_loss_grad_stream_major; fz_kernel_adjoint_ring_sm.hip.inc with FZ_FAR),
 // {P = the patch rows R, U = checkpoint rows, block}: the stream-major ring rule over the LDS ring lines alone, from half its R0.
 // With FZ_VF_STATES next to the two (never FZ_VF_ADJOINT_LOSS or FZ_VF_ADJOINT_SM): the block-start-states kernel of a far recording
-// (fz_run_recording_far_grad; fz_kernel_states_far.hip.inc: a text and a symbol of its own, the far lines' values in a working ring in
+// (fz_run_recording_far_grad; fz_kernel_states.hip.inc with FZ_RING and FZ_FAR: a symbol of its own, the far lines' values in a working ring in
 // the workspace), {P = 1, U = the rows of one unrolled group, at most 8, block = the far adjoint kernel's}; fz_grad.cpp:
 // states_variant is the one place that makes one, and only for a graph that has a far line.
 constexpr uint32_t FZ_VF_ADJOINT_FAR = 1u;
@@ -356,7 +356,7 @@ std::string gen_adjoint_config(const Graph& g, const Variant& v);
 // loss: also out(), the step's output values (FZ_VF_ADJOINT_LOSS).  ring: the body of fz_kernel_adjoint_ring.hip.inc (FZ_VF_ADJOINT_RING):
 // register rows compact, the lines in LDS read through rv[] and their adjoints kept in an LDS ring; without it the text is unchanged.
 // Both: out() takes rv[] too (fz_kernel_adjoint_ring.hip.inc with FZ_LOSS)
-// far (FZ_VF_ADJOINT_FAR, with ring): the body of fz_kernel_adjoint_far.hip.inc -- the far lines' reads follow the ring reads in
+// far (FZ_VF_ADJOINT_FAR, with ring): the body of fz_kernel_adjoint_ring.hip.inc with FZ_FAR -- the far lines' reads follow the ring reads in
 // rv[], their source values the ring lines' in u[]; 1: bwd() keeps their pending adjoints in the workspace ring (the per-row path),
 // 2: in the registers the kernel hands it (the fast path); fz_codegen.cpp: far_fast_path chooses
 std::string gen_adjoint_body(const Graph& g, bool loss = false, bool ring = false, int far = 0);
@@ -371,7 +371,7 @@ struct RingLayout {
    std::vector<uint32_t> rl_slot0;   // per ring line: its first LDS slot
    std::vector<std::pair<uint32_t, uint32_t>> reads;   // (ring line, delay)
    uint32_t slots = 0;               // LDS slots per lane: the sum of the ring lines' depths
-   // the FAR lines (Line::far, deeper than 256 samples: fz_kernel_adjoint_far.hip.inc), neither register rows nor ring lines
+   // the FAR lines (Line::far, deeper than 256 samples: FZ_FAR in fz_kernel_adjoint_ring.hip.inc), neither register rows nor ring lines
    std::vector<int> far_of_line;     // per line: its far line index, -1 for any other line
    std::vector<uint32_t> fl_line;    // per far line: index into Graph::lines
    std::vector<uint32_t> fl_slot0;   // per far line: its first row of the adjoint ring in the workspace
