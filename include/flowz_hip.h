@@ -772,9 +772,9 @@ int fz_run_block_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64
  * fit no workgroup is refused with the bytes named.  fz_program_far_grad_*_for / fz_program_far_loss_grad_*_for inspect the kernel
  * of either layout (FZ_GRAD_TIME_MAJOR: what fz_program_far_grad_* answer).
  *
- * Not built for graphs with a far line: the recording calls on stream-major buffers (fz_run_recording_ring_grad_stream_major keeps
- * refusing), a forward body for HBM rings on stream-major buffers (fz_run_block_stream_major keeps refusing), double or complex far
- * lines. */
+ * Recordings of such graphs on stream-major buffers: fz_run_recording_far_grad_for / fz_run_recording_far_loss_grad_for with
+ * FZ_GRAD_STREAM_MAJOR, below (fz_run_recording_ring_grad_stream_major keeps refusing).  Not built for graphs with a far line: a
+ * forward body for HBM rings on stream-major buffers (fz_run_block_stream_major keeps refusing), double or complex far lines. */
 int fz_run_block_far_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
                                        void* hip_stream);
 int fz_run_block_far_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
@@ -971,7 +971,7 @@ long fz_program_ring_states_source_for(fz_program* p, uint32_t layout, char* buf
  * fz_run_recording_ring_grad / fz_run_recording_ring_loss_grad (and so, without a deep line at all, the FZ_GRAD_TIME_MAJOR
  * fz_run_recording_grad / fz_run_recording_loss_grad): the same states kernel, B, workspace and bits.  fz_run_recording_*,
  * fz_run_recording_ring_*, fz_program_ring_recording_* and fz_program_ring_states_* keep refusing graphs with such lines.
- * Time-major frames only.
+ * Time-major frames; stream-major buffers: the _for calls below.
  *
  * How: one launch of the FAR STATES kernel writes starts[ceil(T / B)][n_state][n_streams] (and state_out); then the far adjoint or
  * far loss kernel is launched, unchanged, per block from the last to the first, with state = starts[k] and state_grad = the
@@ -1011,6 +1011,54 @@ int fz_run_recording_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, ui
 int fz_program_far_states_resources(fz_program* p, fz_kernel_resources* out);
 long fz_program_far_states_kernel_symbol(fz_program* p, char* buf, size_t cap);
 long fz_program_far_states_source(fz_program* p, char* buf, size_t cap);
+
+/* fz_run_recording_far_grad_for, fz_run_recording_far_loss_grad_for -- the same with the layout as an ARGUMENT, the argument list of
+ * fz_run_recording_grad / fz_run_recording_loss_grad: with FZ_GRAD_STREAM_MAJOR a graph with delay lines in HBM is fitted to a batch
+ * of recordings lying as [batch, time], buffers [n_streams][rows_total][wire], the recording the window of rows
+ * [row0, row0 + n_samples), without a transposed copy of the frames.  With FZ_GRAD_TIME_MAJOR the calls ARE fz_run_recording_far_grad /
+ * fz_run_recording_far_loss_grad (row0 0 and rows_total 0 or n_samples: time-major frames have no window): the same checks, kernels
+ * and bits.
+ *
+ * THE CONTRACT IS A REFERENCE.  Every output bit -- in_grad, state0_grad, param_grad, const_grad, loss, out -- is that of
+ * fz_run_recording_far_grad / fz_run_recording_far_loss_grad on the transposed buffers (and so that of the one-launch
+ * fz_run_block_far_grad_stream_major / fz_run_block_far_loss_grad_stream_major over the same window), whatever block_rows is.
+ * starts[k] at the head of the workspace and state_out, if not NULL, have the bits of fz_run_block's state, the far lines' slots
+ * (u[q] in slot (p0 + q) mod D) and phase rows included.  Windows, alignment and the rows outside the window, which are never
+ * written, are those of fz_run_recording_grad with FZ_GRAD_STREAM_MAJOR: block k is the window row0 + k B, and every such window
+ * passes the checks of fz_run_block_far_grad_stream_major.  fz_grad_args and fz_loss_grad_args are taken unchanged.
+ *
+ * B and the workspace: fz_program_far_recording_block_rows and fz_program_far_recording_workspace answer both layouts -- C, the
+ * tape, the adjoint ring, the checkpoints and the block-start states do not depend on the layout (the workspace query asks for a
+ * block_rows that is a multiple of 4 in either layout).
+ *
+ * Scope: that of fz_program_far_grad_check, plus the LDS refusals of the two stream-major kernels.  For a graph without a line deeper
+ * than 256 samples the stream-major calls ARE fz_run_recording_ring_grad_stream_major / fz_run_recording_ring_loss_grad_stream_major
+ * (and so, without a deep line at all, fz_run_recording_grad / fz_run_recording_loss_grad with FZ_GRAD_STREAM_MAJOR): the same states
+ * kernel, B, workspace and bits.  Every other recording call keeps refusing graphs with far lines; double or complex far lines stay
+ * refused.
+ *
+ * Checks, all before a device is needed, in the order of fz_run_recording_ring_grad_stream_major: the refusals of
+ * fz_program_far_grad_check; the states kernel's LDS; n_samples < 2^31; the block kernel's LDS; those of the one-launch stream-major
+ * far call over the window (state_out counted as an output) with this call's workspace size -- a short workspace names
+ * fz_program_far_recording_workspace; with more than one block, state0_grad not NULL; those of every block launch.  n_streams == 0
+ * or n_samples == 0: FZ_OK, nothing is touched.  Asynchronous on hip_stream.
+ *
+ * The stream-major far states kernel, fz_states_far_sm_kernel_u<U>r<R>b<lanes>_g<tag>, is the stream-major ring states kernel with
+ * what the far mode adds to the time-major one: the working value ring of a far line in the rows of the workspace behind `starts`,
+ * one load per far read and one store per far line and row, the reads at a delay of at least 2 U requested one group of U rows
+ * ahead, a line's D slots copied row for row at a block start.  x moves through a wave-private LDS patch of R rows; the far lines
+ * take no LDS: lds_bytes = 4 * lanes * (LDS ring samples + R * n_in + 4).  R runs over the R of fz_states_sm_kernel (never below
+ * max(4, U)) -- half the ring states kernel's: a far kernel waits on rows in HBM and needs waves more than a longer run -- halved
+ * down to max(4, U); per R the lanes over 256 / 128 / 64, as for the ring states kernel (a 1-in graph without an LDS ring line:
+ * 256 lanes, R = 32, 36 864 bytes).  HBM bytes per stream-sample: those of the time-major far states kernel.  The _for inspection
+ * calls answer for a layout (FZ_GRAD_TIME_MAJOR: fz_program_far_states_*). */
+int fz_run_recording_far_grad_for(fz_program* p, const fz_grad_args* a, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                  uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream);
+int fz_run_recording_far_loss_grad_for(fz_program* p, const fz_loss_grad_args* a, uint32_t layout, uint64_t n_streams, uint32_t rows_total,
+                                       uint32_t row0, uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream);
+int fz_program_far_states_resources_for(fz_program* p, uint32_t layout, fz_kernel_resources* out);
+long fz_program_far_states_kernel_symbol_for(fz_program* p, uint32_t layout, char* buf, size_t cap);
+long fz_program_far_states_source_for(fz_program* p, uint32_t layout, char* buf, size_t cap);
 
 /* ------------------------------------------------------------------------------------------
  * 16-bit PCM frames.  fz_run_block_pcm16 is fz_run_block for a block whose frames are int16 on one side or on both: the caller

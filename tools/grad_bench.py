@@ -89,8 +89,15 @@ fits; route = run_block per block for the states, copying the state rows before 
 reverse at the same B.  workloads.far_comb (300 samples) and ~(0.5*_1[_2000] + _2).  The table, the workspaces and B go to stdout and to
 profiles/r18/far_recording.txt.
 
+--far --recording --layout stream-major|compare [--loss]: the backward of a whole recording of such graphs on stream-major buffers,
+run_recording_far_grad(stream_major=True) (fz_run_recording_far_grad_for with FZ_GRAD_STREAM_MAJOR; with --loss
+run_recording_far_loss_grad), with the legs, the shapes, the method and the mark of --rings --recording --layout compare: route =
+fz_transpose_frames of x and of dL/dy (or the target), the time-major far recording at the same B, fz_transpose_frames of dL/dx back.
+workloads.far_comb, the 2000-sample comb and far_tap1.  The table goes to stdout and to profiles/r20/far_sm_recording.txt (the --loss
+table is appended to it).
+
 usage: tools/grad_bench.py [--warmup W] [--steps K] [--legs small|large|all] [--layout time-major|stream-major|compare] [--loss] [--recording] [--rings] [--far]
-       (--far takes --recording, or --layout compare, alone or with --loss)
+       (--far takes --recording, or --layout compare, alone or with --loss; --far --recording takes --layout stream-major|compare, alone or with --loss)
        (--rings takes --layout compare, alone or with --loss; --rings --recording takes --layout stream-major|compare, alone or with --loss)
 """
 import argparse
@@ -786,10 +793,11 @@ def rings_recording_bench(a, torch, far=False):
         f.write("\n".join(lines) + "\n")
 
 
-def rings_recording_sm_bench(a, torch):
+def rings_recording_sm_bench(a, torch, far=False):
     """the backward of a whole recording of graphs with delay lines in LDS on stream-major buffers (plain, or with a.loss under the
     squared-error loss), alone (--layout stream-major) or against transpose + the time-major ring recording + transpose (--layout
-    compare), interleaved in one process; the two legs agree bit for bit before a time is printed"""
+    compare), interleaved in one process; the two legs agree bit for bit before a time is printed.  far: the same for graphs with delay
+    lines in HBM, the far family's calls"""
     import time
     lines = []
 
@@ -798,15 +806,16 @@ def rings_recording_sm_bench(a, torch):
         lines.append(line)
     props = torch.cuda.get_device_properties(0)
     loss, both = bool(a.loss), a.layout == "compare"
-    call = "run_recording_ring_loss_grad" if loss else "run_recording_ring_grad"
-    say(f"# command: tools/grad_bench.py --rings --recording --layout {a.layout}{' --loss' if loss else ''} --steps {a.steps} --legs {a.legs}")
+    call = "run_recording_" + ("far" if far else "ring") + ("_loss_grad" if loss else "_grad")
+    sm_call = call + "(stream_major=True)" if far else call + "_stream_major"
+    say(f"# command: tools/grad_bench.py {'--far' if far else '--rings'} --recording --layout {a.layout}{' --loss' if loss else ''} --steps {a.steps} --legs {a.legs}")
     say(f"# date {datetime.date.today().isoformat()}, board {props.name or 'unnamed'} ({getattr(props, 'gcnArchName', '?')})")
-    say(f"# sm = one {call}_stream_major call on [n_streams, T] buffers; route = fz_transpose_frames of x and of {'the target' if loss else 'dL/dy'}, {call}, fz_transpose_frames of dL/dx back;")
+    say(f"# sm = one {sm_call} call on [n_streams, T] buffers; route = fz_transpose_frames of x and of {'the target' if loss else 'dL/dy'}, {call}, fz_transpose_frames of dL/dx back;")
     say(f"# every gradient, default checkpoint stride and B; HIP events, {a.steps} calls per leg and pass, a forward and a backward pass over the legs;")
     say("# spread = max - min of the route's own repeats; the legs agree bit for bit (dL/dx, the state gradient" + (", the loss" if loss else "") + ") before a time is printed;")
     say("# slower = sm median > route median + the route's spread")
     say(f"{'graph':16s} {'streams x T':>16s} {'B':>5s} {'route ms':>9s} {'spread':>7s} {'sm ms':>9s} {'sm/route':>9s} {'slower':>6s} {'ws MB':>9s} {'U':>3s} {'R':>3s} {'lanes':>5s} {'vgprs':>6s} "
-        f"{'sgpr spills':>11s} {'lds':>6s}  stream-major ring states kernel")
+        f"{'sgpr spills':>11s} {'lds':>6s}  stream-major {'far' if far else 'ring'} states kernel")
     shapes = REC_SHAPES["small"] + REC_SHAPES["large"] if a.legs == "all" else REC_SHAPES[a.legs]
     for ns, T in shapes:
         x_sm = torch.empty((ns, T, 1), dtype=torch.float32, device="cuda")
@@ -819,10 +828,13 @@ def rings_recording_sm_bench(a, torch):
             x_tm, yt_tm = (torch.empty((T, ns, 1), dtype=torch.float32, device="cuda") for _ in range(2))
         n = float(ns) * T
         want = ("x", "state", "params", "consts") + (("loss",) if loss else ())
-        for name, fn in RING_GRAPHS.items():
+        for name, fn in ({k: v for k, v in FAR_GRAPHS.items() if k != "comb256"} if far else RING_GRAPHS).items():
             prog = F.compile(F.from_sexpr(fn()))
             s0 = torch.zeros((prog.n_state, ns), dtype=torch.float32, device="cuda")
-            B, ws_bytes = prog.ring_recording_block_rows(T), prog.ring_recording_workspace_bytes(ns, T)
+            if far:
+                B, ws_bytes = prog.far_recording_block_rows(T), prog.far_recording_workspace_bytes(ns, T)
+            else:
+                B, ws_bytes = prog.ring_recording_block_rows(T), prog.ring_recording_workspace_bytes(ns, T)
             ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device="cuda")
             kw = dict(grad_scale=2.0 / n) if loss else {}
 
@@ -834,6 +846,8 @@ def rings_recording_sm_bench(a, torch):
                 return r
 
             def sm():
+                if far:
+                    return getattr(prog, call)(x_sm, yt_sm, s0, None, state_grad=s0, want=want, in_grad=gx_sm, workspace=ws, stream_major=True, **kw)
                 return getattr(prog, call + "_stream_major")(x_sm, yt_sm, s0, None, state_grad=s0, want=want, in_grad=gx_sm, workspace=ws, **kw)
             legs = {"route": route, "sm": sm} if both else {"sm": sm}
             first = {k: f() for k, f in legs.items()}           # JIT, allocator; and the legs agree bit for bit
@@ -854,7 +868,8 @@ def rings_recording_sm_bench(a, torch):
                 for k in order:
                     got[k] += samples(legs[k], a.steps, torch)
             med = {k: float(np.median(v)) for k, v in got.items()}
-            res, sym = prog.ring_states_resources(stream_major=True), prog.ring_states_kernel_symbol(stream_major=True)
+            res, sym = (prog.far_states_resources if far else prog.ring_states_resources)(stream_major=True), \
+                (prog.far_states_kernel_symbol if far else prog.ring_states_kernel_symbol)(stream_major=True)
             R, lanes = int(sym.split("_g")[0].split("r")[-1].split("b")[0]), int(sym.split("_g")[0].split("b")[-1])
             if both:
                 spread = max(got["route"]) - min(got["route"])
@@ -870,7 +885,7 @@ def rings_recording_sm_bench(a, torch):
         if both:
             del gx_back, x_tm, yt_tm
         torch.cuda.empty_cache()
-    out = os.path.join(ROOT, "profiles", "r16", "ring_sm_recording.txt")
+    out = os.path.join(ROOT, "profiles", "r20", "far_sm_recording.txt") if far else os.path.join(ROOT, "profiles", "r16", "ring_sm_recording.txt")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "a" if loss and os.path.exists(out) else "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -890,6 +905,8 @@ def main():
     import torch
 
     torch.cuda.set_device(0)
+    if a.far and a.recording and a.layout != "time-major":
+        return rings_recording_sm_bench(a, torch, far=True)
     if a.far and a.recording:
         return rings_recording_bench(a, torch, far=True)
     if a.far and a.layout == "compare":

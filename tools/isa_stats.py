@@ -26,9 +26,12 @@ usage: tools/isa_stats.py [graph] [P] [U] [block] [flags]   (graph: cascade6|par
                                                            vector-memory instructions in the kernel (graph: as for ringlossgrad, or `all`:
                                                            the ten of tests/ring_loss_graphs.py); --layout stream-major: the kernel of
                                                            fz_run_recording_ring_grad_stream_major, with its patch rows R and lanes
-       tools/isa_stats.py farstates [graph]                the same lines for the block-start-states kernel of fz_run_recording_far_grad next
+       tools/isa_stats.py farstates [graph] [--layout stream-major]
+                                                           the same lines for the block-start-states kernel of fz_run_recording_far_grad next
                                                            to the far adjoint kernel, with its prefetch table (graph: as for fargrad, or
-                                                           `all`: the eight of tests/far_grad_graphs.py)
+                                                           `all`: the eight of tests/far_grad_graphs.py); --layout stream-major: the kernel
+                                                           of fz_run_recording_far_grad_for with FZ_GRAD_STREAM_MAJOR, with its patch rows R
+                                                           and lanes
 """
 import glob
 import os
@@ -158,15 +161,16 @@ def ring_states_lines(name, sm=False, far=False):
     U rows (U ring-read sets, U ds_write per ring line, the next group's U x loads) plus the two state dumps (block start, state_out).
     sm: the kernel for stream-major buffers (its ds_* include the patch: the fetched pieces parked, the group's own-row reads; its
     vector-memory loads are the patch fetch, the state and the coefficients)
-    far: the far states kernel (fz_run_recording_far_grad; time-major only) next to the far adjoint kernel: per row of the group one
-    vector-memory load per far read (those at a delay of at least 2 U with the next group's x rows: the table) and one store per far
-    line; the two dumps copy a far line's slots in a loop of four"""
+    far: the far states kernel (fz_run_recording_far_grad; with sm fz_run_recording_far_grad_for on stream-major buffers) next to the
+    far adjoint kernel of the layout: per row of the group one vector-memory load per far read (those at a delay of at least 2 U with
+    the next group's x rows, on stream-major buffers a group ahead of the patch's rows: the table) and one store per far line; the two
+    dumps copy a far line's slots in a loop of four"""
     import far_grad_graphs as FG
     import ring_loss_graphs as RL
     build = (FG.FARS.get(name) if far else None) or RL.GRAPHS.get(name) or GRAPHS[name]
     p = F.compile(F.from_sexpr(build()))
-    states_resources = (lambda q: q.far_states_resources()) if far else (lambda q: q.ring_states_resources(stream_major=sm))
-    r, ring = states_resources(p), p.far_grad_resources(0) if far else p.ring_grad_resources(0, stream_major=sm)
+    states_resources = (lambda q: q.far_states_resources(stream_major=sm)) if far else (lambda q: q.ring_states_resources(stream_major=sm))
+    r, ring = states_resources(p), p.far_grad_resources(0, stream_major=sm) if far else p.ring_grad_resources(0, stream_major=sm)
     old = os.environ.get("FLOWZ_HIP_CACHE")
     try:
         with tempfile.TemporaryDirectory() as td:
@@ -183,7 +187,7 @@ def ring_states_lines(name, sm=False, far=False):
     n = {"ds_read": sum(o.startswith("ds_read") for o in ops), "ds_write": sum(o.startswith("ds_write") for o in ops),
          "vmem_load": sum("load" in o for o in vmem), "vmem_store": sum("store" in o for o in vmem), "valu": sum(o.startswith("v_") for o in ops),
          "s_barrier": ops.count("s_barrier"), "atomic": sum("atomic" in o for o in ops)}
-    sym = p.far_states_kernel_symbol() if far else p.ring_states_kernel_symbol(stream_major=sm)
+    sym = p.far_states_kernel_symbol(stream_major=sm) if far else p.ring_states_kernel_symbol(stream_major=sm)
     geo = f"R {sym.split('_g')[0].split('r')[-1].split('b')[0]}, {sym.split('_g')[0].split('b')[-1]} lanes, " if sm else ""
     kin = "far adjoint" if far else "ring adjoint"
     out = [f"{name} {sym}: U {r['unroll']}, {geo}{r['vgprs'] + r['agprs']} VGPRs ({kin} {ring['vgprs'] + ring['agprs']}), "
@@ -192,7 +196,7 @@ def ring_states_lines(name, sm=False, far=False):
            "  in the kernel: " + ", ".join(f"{v} {k}" for k, v in n.items())]
     if far:
         import re
-        src = p.far_states_source()
+        src = p.far_states_source(stream_major=sm)
         table = [re.search(r"%s\[\d+\] = \{([^}]*)\}" % t, src) for t in ("fz_fr_delay", "fz_fr_ahead")]
         if "#define FZ_FAR 1 " in src.split("// ==== fz_graph_body.h ====")[0] and all(table):
             out.append("  far reads at delays {" + table[0].group(1) + "}: with the next group's x rows {" + table[1].group(1) + "}")
@@ -224,7 +228,7 @@ def main():
             import far_grad_graphs as FG
             names = sorted(FG.FARS)
         for n in names:
-            print("\n".join(ring_states_lines(n, far=True)))
+            print("\n".join(ring_states_lines(n, sm, far=True)))
         return
     if a and a[0] == "ringgrad":
         print("\n".join(ring_grad_lines(a[1] if len(a) > 1 else "ldsring", sm=sm)))

@@ -217,6 +217,11 @@ def _load():
         "fz_program_far_states_resources": (ctypes.c_int, [P, ctypes.POINTER(KernelResources)]),
         "fz_program_far_states_kernel_symbol": (ctypes.c_long, [P, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_far_states_source": (ctypes.c_long, [P, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_run_recording_far_grad_for": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u32, u64, u32, u32, u32, u32, P, P]),
+        "fz_run_recording_far_loss_grad_for": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u32, u64, u32, u32, u32, u32, P, P]),
+        "fz_program_far_states_resources_for": (ctypes.c_int, [P, u32, ctypes.POINTER(KernelResources)]),
+        "fz_program_far_states_kernel_symbol_for": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_far_states_source_for": (ctypes.c_long, [P, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_run_block_ring_grad_stream_major": (ctypes.c_int, [P, ctypes.POINTER(GradArgs), u64, u32, u32, u32, P]),
         "fz_run_block_ring_loss_grad_stream_major": (ctypes.c_int, [P, ctypes.POINTER(LossGradArgs), u64, u32, u32, u32, P]),
         "fz_program_ring_grad_resources_for": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),

@@ -45,6 +45,8 @@ a batch of recordings lying as [batch, time] is fitted in bounded workspace with
 mse_recording_far(prog, x, target, ...) is mse_recording_rings() for every graph run_far() takes, time-major
 (Program.run_recording_far_loss_grad: the far states kernel, then the far loss kernel block by block); mse_recording_rings() keeps
 refusing graphs with delay lines deeper than 256 samples.
+mse_recording_far(..., stream_major=True) is the same on stream-major tensors (Program.run_recording_far_loss_grad with
+stream_major=True): a batch of recordings lying as [batch, time] is fitted in bounded workspace without a transposed copy.
 """
 from __future__ import annotations
 
@@ -83,8 +85,8 @@ def _front_door(prog: Program, x, consts, rings):
 def _backward_call(prog: Program, rings, stream_major, loss=False, recording=False):
     """the bound Program method of one corner of the backward family"""
     name = ("run_recording_" if recording else "run_block_") + ("far_" if rings == "far" else "ring_" if rings else "") + ("loss_grad" if loss else "grad")
-    # (the plain recording calls take the layout as a keyword; every other stream-major corner is a method of its own)
-    return getattr(prog, name + ("_stream_major" if stream_major and (rings or not recording) else ""))
+    # (the plain and the far recording calls take the layout as a keyword; every other stream-major corner is a method of its own)
+    return getattr(prog, name + ("_stream_major" if stream_major and (rings is True or not recording) else ""))
 
 
 _WANT = ("x", "state", "params", "consts")
@@ -196,7 +198,7 @@ class _Mse(torch.autograd.Function):
         n = xx.shape[0] * xx.shape[1] * prog.n_out                    # elements of y: the mean is over all of them
         kw = {}
         if recording:
-            kw = {"block_rows": int(block_rows)} if rings else {"block_rows": int(block_rows), "stream_major": bool(stream_major)}
+            kw = {"block_rows": int(block_rows)} if rings is True else {"block_rows": int(block_rows), "stream_major": bool(stream_major)}
         # the one call: the loss and every gradient asked for, dL/dy = (y - target) * 2 / n formed in the kernel
         r = _backward_call(prog, rings, stream_major, True, recording)(
             xx, target.detach().contiguous(), state.detach() if state is not None else None,
@@ -269,13 +271,17 @@ def mse_recording_rings(prog: Program, x, target, state=None, params=None, const
     return loss, state_out.detach()
 
 
-def mse_recording_far(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0):
+def mse_recording_far(prog: Program, x, target, state=None, params=None, consts=None, block_rows=0, stream_major=False):
     """mse_recording_rings() for graphs with delay lines deeper than 256 samples -- and every graph mse_recording_rings() takes --,
-    time-major frames only: returns (loss, state_out) over a whole recording in bounded workspace
+    time-major frames: returns (loss, state_out) over a whole recording in bounded workspace
     (Program.far_recording_workspace_bytes: the state before every block plus one block's checkpoints, tape and adjoint ring;
     block_rows = 0 lets the library choose, otherwise a multiple of 4).  The gradients have the bits of mse_far()'s over the same rows
     (include/flowz_hip.h: fz_run_recording_far_loss_grad); state_out carries the far lines' slots and phase rows, so it is the `state`
-    of the next call."""
+    of the next call.
+    stream_major: the tensor shapes of mse_recording(..., stream_major=True), a [batch, time] tensor as it lies for one wire
+    (Program.run_recording_far_loss_grad(stream_major=True), fz_run_recording_far_loss_grad_for); block_rows times n_in and n_out are
+    then multiples of 4.  The forward needs no stream-major body for rings in HBM: the recording call yields the loss and state_out
+    itself, nothing is transposed."""
     _front_door(prog, x, consts, "far")
-    loss, state_out = _Mse.apply(prog, x, target, state, params, consts, False, "far", int(block_rows))
+    loss, state_out = _Mse.apply(prog, x, target, state, params, consts, bool(stream_major), "far", int(block_rows))
     return loss, state_out.detach()

@@ -30,7 +30,7 @@ extern const char* const kSkeletonAdjointSm;
 extern const char* const kSkeletonAdjointRing;   // fz_kernel_adjoint_ring.hip.inc: rings in LDS and, with FZ_FAR, delay lines deeper than 256 samples, rings in HBM
 extern const char* const kSkeletonAdjointRingSm; // fz_kernel_adjoint_ring_sm.hip.inc: the same on stream-major buffers
 extern const char* const kSkeletonStates;        // fz_kernel_states.hip.inc: plain, with FZ_RING ring, and with FZ_FAR next to it far
-extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: plain and ring (no far mode)
+extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: the same three modes on stream-major buffers
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
 
@@ -59,6 +59,7 @@ static const AdjointRow& adjoint_row(const Variant& v)
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING, "fz_states", "_ring", kSkeletonStates, false},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM, "fz_states", "_ring_sm", kSkeletonStatesSm, true},
       {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR, "fz_states", "_far", kSkeletonStates, false},
+      {FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR | FZ_VF_ADJOINT_SM, "fz_states", "_far_sm", kSkeletonStatesSm, true},
    };
    for (const AdjointRow& r : rows)
       if (r.bits == (v.flags & (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_FAR)) && !((v.flags & FZ_VF_STATES) && (v.flags & FZ_VF_ADJOINT_LOSS))) return r;

@@ -12,7 +12,7 @@
 //     (FZ_VF_STATES)
 //   fz_run_recording_ring_grad[_stream_major]:        the same text with FZ_RING        the same text with FZ_RING
 //     the same (FZ_VF_STATES | FZ_VF_ADJOINT_RING)
-//   fz_run_recording_far_grad: the same               the same text with FZ_FAR too     (not built)
+//   fz_run_recording_far_grad[_for]: the same         the same text with FZ_FAR too     the same text with FZ_FAR too
 //     (FZ_VF_STATES | FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR)
 //
 // Under a squared-error loss (FZ_VF_ADJOINT_LOSS, the ..._loss_grad calls) each of the adjoint kernels forms dL/dy itself, from a
@@ -168,10 +168,6 @@ static uint32_t adjoint_flags(const Graph& g, uint32_t family_bits, bool loss)
    return FZ_VF_ADJOINT | family_bits | (loss ? FZ_VF_ADJOINT_LOSS : 0u);
 }
 
-// (the far states kernel is built for time-major frames only: the reason states_variant gives; the far adjoint kernel has a text for
-//  either layout)
-static const char* const kFarStreamMajor = "delay lines deeper than 256 samples (rings in HBM) are not supported by the backward on stream-major buffers";
-
 static uint32_t family_bits(bool ring, bool stream_major) { return (ring ? FZ_VF_ADJOINT_RING : 0u) | (stream_major ? FZ_VF_ADJOINT_SM : 0u); }
 
 // The Variant of a block's backward, whichever call asks: {P = 1 (stream-major: the patch rows R -- codegen puts them into FZ_R and the
@@ -231,7 +227,12 @@ static Variant block_variant(const Graph& g, uint32_t checkpoint_rows, bool ring
 // run costs no occupancy.  Static, not measured against R0 = states_sm_patch_rows(g).
 // far: as for block_variant -- the scope of the far backward; without a line deeper than 256 samples the ring states Variant itself.
 // With one: FZ_VF_ADJOINT_RING | FZ_VF_ADJOINT_FAR next to FZ_VF_STATES (fz_kernel_states.hip.inc with FZ_FAR), the same U, and the workgroup
-// the ring rule gives the graph's LDS ring lines alone, 256 lanes without any -- the far adjoint kernel's.  Time-major frames only.
+// the ring rule gives the graph's LDS ring lines alone, 256 lanes without any -- the far adjoint kernel's.  On stream-major buffers
+// (fz_kernel_states_sm.hip.inc with FZ_FAR) the ring rule chooses R and the block together over those LDS ring slots -- none for a
+// graph whose deep lines are all far -- and the x-only patch, with the ring call's Rmin and its refusal when nothing fits, and R0 =
+// max(states_sm_patch_rows(g), Rmin), HALF the ring states kernel's: the plain states kernel's whole-cache-line run.  A far kernel
+// waits on rows in HBM, a load per far read and row, and hides that behind waves rather than behind a longer run (block_variant's
+// measured argument for the far adjoint kernel).  Static, not measured against the ring kernel's R0.
 static Variant states_variant(const Graph& g, bool ring, bool stream_major, bool far = false)
 {
    ring = ring || far;
@@ -239,16 +240,17 @@ static Variant states_variant(const Graph& g, bool ring, bool stream_major, bool
    const RingLayout rl = ring ? ring_layout(g) : RingLayout{};
    const uint32_t slots = rl.slots;
    const bool far_lines = rl.n_fl() != 0;
-   if (far_lines && stream_major) fail(FZ_E_UNSUPPORTED, kFarStreamMajor);
    Variant v;
    v.P = 1;
    v.U = states_unroll(g);
    v.block = kGradBlock;
    v.flags = FZ_VF_ADJOINT | FZ_VF_STATES | family_bits(slots != 0 || far_lines, stream_major) | (far_lines ? FZ_VF_ADJOINT_FAR : 0u);
-   if (slots) {
+   if (slots || (far_lines && stream_major)) {
       const LaneLds lane{slots, stream_major ? g.n_in : 0u, stream_major && g.n_in ? 4u : 0u};
       const uint32_t Rmin = stream_major ? std::max<uint32_t>(4u, v.U) : 1u;
-      const RingSmGeometry geo = ring_sm_geometry(lane, stream_major ? 2 * states_sm_patch_rows(g) : 1u, Rmin);
+      // (far lines: R0 is half the ring kernel's, see above)
+      const uint32_t R0 = !stream_major ? 1u : far_lines ? std::max(states_sm_patch_rows(g), Rmin) : 2 * states_sm_patch_rows(g);
+      const RingSmGeometry geo = ring_sm_geometry(lane, R0, Rmin);
       if (!geo.block)                                       // (stream-major only, as above)
          fail(FZ_E_UNSUPPORTED, "stream-major ring recording: the rings of the delay lines deeper than 8 samples (" + std::to_string(slots) + " samples) plus a patch of " +
                                    std::to_string(Rmin) + " rows of " + std::to_string(g.n_in) + " input wires, " + std::to_string(lane.bytes(64, Rmin)) +
@@ -274,8 +276,8 @@ bool grad_variant_fits(const Graph& g, const Variant& v)
    const bool ring = v.flags & FZ_VF_ADJOINT_RING, sm = v.flags & FZ_VF_ADJOINT_SM, loss = v.flags & FZ_VF_ADJOINT_LOSS, far = v.flags & FZ_VF_ADJOINT_FAR;
    try {
       // (the far bit without the ring bit or on a graph without a far line: no maker answers with it; next to FZ_VF_STATES the states
-      //  maker answers with its own U, at most 8, and never with the loss or the stream-major bit beside the far one; next to the
-      //  stream-major bit the block maker answers with its own R in P: 1, a non-power of two or an R below C is none)
+      //  maker answers with its own U, at most 8, never with the loss, and beside the stream-major bit with its own R in P; next to
+      //  the stream-major bit the block maker answers with its own R in P: 1, a non-power of two or an R below C is none)
       const Variant w = !(v.flags & FZ_VF_STATES) ? block_variant(g, v.U, ring, sm, loss, far) : states_variant(g, ring, sm, far);
       return w.P == v.P && w.U == v.U && w.block == v.block && w.flags == v.flags;
    } catch (const Error&) {
@@ -595,9 +597,10 @@ static uint64_t ring_recording_workspace_bytes(const Graph& g, uint64_t n_stream
 // The backward of a recording: the states kernel once, then the block launches from the last block to the first (the contract is in
 // include/flowz_hip.h).  Every check -- of the call over its T rows, then of every block launch as a direct call would be checked --
 // runs before a device is needed.  call.ring: the recording of the ring family, in either layout -- the scope, the states kernel, B
-// and the workspace are that family's, the rest is shared.  call.far: the recording of the far family (time-major frames) -- the same
+// and the workspace are that family's, the rest is shared.  call.far: the recording of the far family, in either layout -- the same
 // again with the far makers; the far states kernel keeps its working rings in the rows behind `starts`, the head of the block
-// workspace, which no block launch has used yet, and the block launches are the far adjoint kernels unchanged.
+// workspace, which no block launch has used yet, and the block launches are the far adjoint kernels unchanged.  C, B and the
+// workspace do not depend on the layout.
 static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
                          uint32_t block_rows, float* state_out, void* stream)
 {
@@ -749,6 +752,7 @@ FZ_INSPECTION(states, , "fz_program_states_resources", FZ_ARG_LAYOUT, states_var
 FZ_INSPECTION(ring_states, , "fz_program_ring_states_resources", , states_variant(p->g, true, false))
 FZ_INSPECTION(ring_states, _for, "fz_program_ring_states_resources_for", FZ_ARG_LAYOUT, states_variant(p->g, true, FZ_SM))
 FZ_INSPECTION(far_states, , "fz_program_far_states_resources", , states_variant(p->g, true, false, true))
+FZ_INSPECTION(far_states, _for, "fz_program_far_states_resources_for", FZ_ARG_LAYOUT, states_variant(p->g, true, FZ_SM, true))
 #undef FZ_INSPECTION
 #undef FZ_SM
 #undef FZ_ARG_LAYOUT
@@ -907,6 +911,18 @@ int fz_run_recording_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, ui
                                    float* state_out, void* hip_stream)
 {
    FZ_GUARD(return run_recording(p, far_call_of(p, a), FZ_GRAD_TIME_MAJOR, n_streams, 0, 0, n_samples, block_rows, state_out, hip_stream);)
+}
+
+int fz_run_recording_far_grad_for(fz_program* p, const fz_grad_args* a, uint32_t layout, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
+                                  uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream)
+{
+   FZ_GUARD(return run_recording(p, far_call_of(p, a), layout, n_streams, rows_total, row0, n_samples, block_rows, state_out, hip_stream);)
+}
+
+int fz_run_recording_far_loss_grad_for(fz_program* p, const fz_loss_grad_args* a, uint32_t layout, uint64_t n_streams, uint32_t rows_total,
+                                       uint32_t row0, uint32_t n_samples, uint32_t block_rows, float* state_out, void* hip_stream)
+{
+   FZ_GUARD(return run_recording(p, far_call_of(p, a), layout, n_streams, rows_total, row0, n_samples, block_rows, state_out, hip_stream);)
 }
 
 int fz_program_ring_recording_block_rows(const fz_program* p, uint32_t n_rows, uint32_t block_rows, uint32_t checkpoint_rows, uint32_t* rows)

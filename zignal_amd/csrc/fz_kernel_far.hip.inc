@@ -1,6 +1,6 @@
-// What the far modes (FZ_FAR) of fz_kernel_adjoint_ring.hip.inc, fz_kernel_adjoint_ring_sm.hip.inc and fz_kernel_states.hip.inc share: the
-// slot arithmetic of a FAR line's ring in HBM and the value of a far read.  Spliced into each of them under `#if FZ_FAR` (embed.py),
-// behind FZ_NT and the generated tables fz_fl_* / fz_fr_*.
+// What the far modes (FZ_FAR) of fz_kernel_adjoint_ring.hip.inc, fz_kernel_adjoint_ring_sm.hip.inc, fz_kernel_states.hip.inc and
+// fz_kernel_states_sm.hip.inc share: the slot arithmetic of a FAR line's ring in HBM and the value of a far read.  Spliced into each
+// of them under `#if FZ_FAR` (embed.py), behind FZ_NT and the generated tables fz_fl_* / fz_fr_*.
 
 // the slot `d` rows back from `slot` in a ring of D slots (slot < D, d <= D; d == D: the slot itself)
 __device__ __forceinline__ static unsigned fz_far_back(unsigned slot, unsigned d, unsigned D) { return slot >= d ? slot - d : slot + D - d; }

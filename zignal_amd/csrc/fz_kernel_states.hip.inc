@@ -100,19 +100,6 @@ struct fz_states_args {        // (one host-side image serves every mode)
 #endif
 #if FZ_FAR
 //@splice fz_kernel_far.hip.inc
-
-// the far lines' rows of a state dump: every slot of the working ring as it is, the phase row the slot of the row the dump stands before.
-// dst and wr are the lane's columns
-static __device__ __forceinline__ void fz_dump_far(float* dst, size_t ns, const float* wr, const unsigned* fslot)
-{
-#pragma unroll
-   for (int f = 0; f < FZ_NFL; ++f) {
-      const unsigned D = fz_fl_depth[f];
-#pragma unroll 4
-      for (unsigned k = 0; k < D; ++k) dst[(size_t)(fz_fl_row0[f] + k) * ns] = wr[(size_t)(fz_fl_slot0[f] + k) * ns];
-      dst[(size_t)fz_fl_phase_row[f] * ns] = (float)fslot[f];
-   }
-}
 #endif
 
 extern "C" __global__ __launch_bounds__(FZ_BLOCK) void FZ_KERNEL(fz_states_args a)

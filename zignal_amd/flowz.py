@@ -378,8 +378,9 @@ _GRAD_ENTRY = {
 # the far family (delay lines deeper than 256 samples), time-major frames: by (loss, recording)
 _FAR_GRAD_ENTRY = {(False, False): "fz_run_block_far_grad", (True, False): "fz_run_block_far_loss_grad",
                    (False, True): "fz_run_recording_far_grad", (True, True): "fz_run_recording_far_loss_grad"}
-# (loss): the far family's one-launch calls on stream-major buffers; its recording calls are built for time-major frames only
-_FAR_GRAD_SM_ENTRY = {False: "fz_run_block_far_grad_stream_major", True: "fz_run_block_far_loss_grad_stream_major"}
+# the far family on stream-major buffers, by (loss, recording): the recording calls take the layout as an argument
+_FAR_GRAD_SM_ENTRY = {(False, False): "fz_run_block_far_grad_stream_major", (True, False): "fz_run_block_far_loss_grad_stream_major",
+                      (False, True): "fz_run_recording_far_grad_for", (True, True): "fz_run_recording_far_loss_grad_for"}
 
 
 class Program:
@@ -1035,30 +1036,46 @@ class Program:
         """workspace bytes of run_recording_far_grad / run_recording_far_loss_grad: the block-start states, then one block's far workspace"""
         return _out(ctypes.c_uint64, C.lib.fz_program_far_recording_workspace, self._h, int(n_streams), int(T), int(block_rows), int(checkpoint_rows))
 
-    def far_states_resources(self) -> dict:
+    def far_states_resources(self, stream_major: bool = False) -> dict:
         """grad_resources() of the block-start-states kernel of a far recording; 'unroll' = the rows of its unrolled group, 'lds_bytes' =
-        the value rings of the LDS ring lines of one workgroup (the far lines keep their working rings in the workspace)"""
-        return _resources(C.lib.fz_program_far_states_resources, self._h)
+        the value rings of the LDS ring lines of one workgroup (the far lines keep their working rings in the workspace).
+        stream_major: the kernel of run_recording_far_grad(stream_major=True) ('lds_bytes': those rings and the x-only patches)"""
+        return _resources(C.lib.fz_program_far_states_resources_for, self._h, int(bool(stream_major)))
 
-    def far_states_kernel_symbol(self) -> str:
-        return _name(C.lib.fz_program_far_states_kernel_symbol, self._h)
+    def far_states_kernel_symbol(self, stream_major: bool = False) -> str:
+        return _name(C.lib.fz_program_far_states_kernel_symbol_for, self._h, int(bool(stream_major)))
 
-    def far_states_source(self) -> str:
-        return _text(C.lib.fz_program_far_states_source, self._h)
+    def far_states_source(self, stream_major: bool = False) -> str:
+        return _text(C.lib.fz_program_far_states_source_for, self._h, int(bool(stream_major)))
 
     def run_recording_far_grad(self, x, out_grad, state=None, params=None, state_grad=None, want=GRAD_WANT, accum=None, checkpoint_rows: int = 0,
-                               block_rows: int = 0, workspace=None):
+                               block_rows: int = 0, workspace=None, stream_major: bool = False, row0: int = 0, n_samples: Optional[int] = None,
+                               in_grad=None):
         """run_block_far_grad over a whole recording in bounded workspace (fz_run_recording_far_grad), as run_recording_ring_grad is to
-        run_block_ring_grad: every bit is run_block_far_grad's over the same rows, "state_out" may be named in want.  Time-major
-        frames only.  For a graph run_recording_ring_grad takes it is run_recording_ring_grad."""
-        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows, None, None, (int(block_rows), workspace),
-                              ring=True, far=True)
+        run_block_ring_grad: every bit is run_block_far_grad's over the same rows, "state_out" may be named in want.  For a graph
+        run_recording_ring_grad takes it is run_recording_ring_grad.
+        stream_major (fz_run_recording_far_grad_for with FZ_GRAD_STREAM_MAJOR): x [n_streams, rows, n_in] (or [n_streams, rows] for
+        one input wire: a [batch, time] tensor as it lies), the shapes, windows (row0, n_samples, in_grad) and result dict of
+        run_recording_ring_grad_stream_major; not a bit differs from the time-major call on the transposed frames, nor from
+        run_block_far_grad_stream_major over the same window.  Without it there is no window: row0 0, n_samples None or T, in_grad None."""
+        if not stream_major:
+            _require(int(row0) == 0 and (n_samples is None or int(n_samples) == x.shape[0]) and in_grad is None,
+                     "run_recording_far_grad takes time-major frames unless stream_major: no window (row0, n_samples, in_grad)")
+        return self._run_grad(x, out_grad, state, params, state_grad, want, accum, checkpoint_rows,
+                              _window(x, row0, n_samples, in_grad) if stream_major else None, None, (int(block_rows), workspace), ring=True, far=True)
 
     def run_recording_far_loss_grad(self, x, target, state=None, params=None, state_grad=None, grad_scale: float = 1.0, want=LOSS_GRAD_WANT,
-                                    accum=None, checkpoint_rows: int = 0, block_rows: int = 0, out=None, workspace=None):
+                                    accum=None, checkpoint_rows: int = 0, block_rows: int = 0, out=None, workspace=None,
+                                    stream_major: bool = False, row0: int = 0, n_samples: Optional[int] = None, in_grad=None):
         """run_block_far_loss_grad over a whole recording (fz_run_recording_far_loss_grad): the arguments, results and bits of the
-        one-launch call over the same rows, plus "state_out" in want.  Time-major frames only."""
-        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows, None, (float(grad_scale), out),
+        one-launch call over the same rows, plus "state_out" in want.  stream_major (fz_run_recording_far_loss_grad_for with
+        FZ_GRAD_STREAM_MAJOR): the arguments, windows and result dict of run_recording_ring_loss_grad_stream_major, in_grad and out
+        included; not a bit differs from the time-major call on the transposed frames."""
+        if not stream_major:
+            _require(int(row0) == 0 and (n_samples is None or int(n_samples) == x.shape[0]) and in_grad is None,
+                     "run_recording_far_loss_grad takes time-major frames unless stream_major: no window (row0, n_samples, in_grad)")
+        return self._run_grad(x, target, state, params, state_grad, want, accum, checkpoint_rows,
+                              _window(x, row0, n_samples, in_grad) if stream_major else None, (float(grad_scale), out),
                               (int(block_rows), workspace), ring=True, far=True)
 
     # -- the backward of a whole recording with delay lines deeper than 8 samples (fz_run_recording_ring_grad) -----------------------
@@ -1128,7 +1145,7 @@ class Program:
         (block_rows, workspace tensor or None) of the calls over a whole recording; ring: the call is of the ring family:
         run_block_ring_grad / run_block_ring_loss_grad, or with recording run_recording_ring_grad / run_recording_ring_loss_grad, and their
         _stream_major twins; far (with ring): run_block_far_grad / run_block_far_loss_grad and their _stream_major twins, or with
-        recording (time-major frames) run_recording_far_grad / run_recording_far_loss_grad"""
+        recording run_recording_far_grad / run_recording_far_loss_grad in either layout"""
         import torch
 
         if far:
@@ -1233,9 +1250,12 @@ class Program:
         a.workspace_bytes = ws.numel() * 4
         # (the workspace goes back to torch's caching allocator when this returns: it reuses the memory in the order of the stream)
         hs = torch.cuda.current_stream().cuda_stream
-        fn = getattr(C.lib, _FAR_GRAD_SM_ENTRY[loss is not None] if far and window is not None else
+        fn = getattr(C.lib, _FAR_GRAD_SM_ENTRY[(loss is not None, recording is not None)] if far and window is not None else
                      _FAR_GRAD_ENTRY[(loss is not None, recording is not None)] if far else _GRAD_ENTRY[(bool(ring), loss is not None, window is not None, recording is not None)])
-        if recording is not None and ring and window is not None:     # ring recording window
+        if recording is not None and far and window is not None:      # far recording window: the layout is an argument
+            C.check(fn(self._h, ctypes.byref(a), 1, int(ns), int(rows), row0, int(T), recording[0],    # (1: FZ_GRAD_STREAM_MAJOR)
+                       ptr(out.get("state_out"), self.n_state), hs))
+        elif recording is not None and ring and window is not None:   # ring recording window
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(rows), row0, int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
         elif recording is not None and ring:                          # ring recording
             C.check(fn(self._h, ctypes.byref(a), int(ns), int(T), recording[0], ptr(out.get("state_out"), self.n_state), hs))
