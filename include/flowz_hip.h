@@ -463,7 +463,8 @@ int  fz_run_block_window(fz_program* p, const float* in, float* out, float* stat
  * Waves fetch [64 streams][unroll samples] patches along the rows and transpose them through LDS.  One
  * stream per lane (no lane or stage packing: VALU-bound for deep graphs at large stream counts), no delay
  * lines beyond 256 samples, float32 frames; rows_total * n_in, row0 * n_in (and the same for n_out) must
- * be multiples of 4 floats.  For the fastest path convert once with fz_transpose_frames instead.      */
+ * be multiples of 4 floats.  For the fastest path convert once with fz_transpose_frames instead.  A graph
+ * with a delay line beyond 256 samples runs on these buffers through fz_run_block_far_stream_major.      */
 int  fz_run_block_stream_major(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
                                uint32_t rows_total, uint32_t row0, uint32_t n_samples, const fz_variant* v, void* hip_stream);
 uint32_t fz_recommended_tile_streams(const fz_program* p);
@@ -773,8 +774,9 @@ int fz_run_block_far_loss_grad(fz_program* p, const fz_loss_grad_args* a, uint64
  * of either layout (FZ_GRAD_TIME_MAJOR: what fz_program_far_grad_* answer).
  *
  * Recordings of such graphs on stream-major buffers: fz_run_recording_far_grad_for / fz_run_recording_far_loss_grad_for with
- * FZ_GRAD_STREAM_MAJOR, below (fz_run_recording_ring_grad_stream_major keeps refusing).  Not built for graphs with a far line: a
- * forward body for HBM rings on stream-major buffers (fz_run_block_stream_major keeps refusing), double or complex far lines. */
+ * FZ_GRAD_STREAM_MAJOR, below (fz_run_recording_ring_grad_stream_major keeps refusing).  The forward of such graphs on stream-major
+ * buffers: fz_run_block_far_stream_major (fz_run_block_stream_major keeps refusing).  Not built for graphs with a far line: double
+ * or complex far lines. */
 int fz_run_block_far_grad_stream_major(fz_program* p, const fz_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0, uint32_t n_samples,
                                        void* hip_stream);
 int fz_run_block_far_loss_grad_stream_major(fz_program* p, const fz_loss_grad_args* a, uint64_t n_streams, uint32_t rows_total, uint32_t row0,
@@ -1122,6 +1124,51 @@ int  fz_run_block_pcm16_stream_major(fz_program* p, const void* in, void* out, f
 int  fz_program_pcm16_stream_major_resources(fz_program* p, uint32_t in_type, uint32_t out_type, fz_kernel_resources* out);
 long fz_program_pcm16_stream_major_kernel_symbol(fz_program* p, uint32_t in_type, uint32_t out_type, char* buf, size_t cap);
 long fz_program_pcm16_stream_major_source(fz_program* p, uint32_t in_type, uint32_t out_type, char* buf, size_t cap);
+
+/* ------------------------------------------------------------------------------------------
+ * Delay lines deeper than 256 samples on STREAM-MAJOR buffers, forward.  fz_run_block_far_stream_major is fz_run_block_stream_major
+ * for a graph whose deepest lines keep their rings in HBM: in [n_streams][rows_total][n_in], out [n_streams][rows_total][n_out],
+ * float32, a [batch, time] tensor as it lies; the block is the window of rows [row0, row0 + n_samples), rows outside it are never
+ * touched.  state and params are fz_run_block's ([row][n_streams]); the far rings are read and written where they are, in the rows
+ * of `state`.  The bits of `out` and of every state row -- register rows, LDS-ring rows, far slots, phase rows -- are fz_run_block's
+ * on the transposed frames, so blocks of either call chain on one state buffer.  One launch on hip_stream, no host synchronisation.
+ * For a graph WITHOUT a line deeper than 256 samples the call is fz_run_block_stream_major with a NULL variant: same kernel, same
+ * bits, same refusals.
+ *
+ * The kernel (fz_kernel_far_sm.hip.inc): one stream per lane; whole chunks of R rows travel as 16-byte pieces through a wave-private
+ * LDS patch, the rows behind the last whole chunk run one step at a time.  Every step appends one row per far line; inside whole
+ * chunks a far read comes from a register buffer requested one group of G unrolled rows ahead, behind them from a load in front of
+ * its row.  THE GROUP RULE: a read requested a group ahead must touch no slot that the group in between writes, 2 G <=
+ * far_min_read (the youngest read served from a ring in HBM, at least 9); G is the largest power of two not above
+ * min(16, far_min_read / 2), halved, not below 4, while the two read buffers, 2 G n_far_reads registers, pass 64.  THE LDS RULE:
+ * delay lines of 9 .. 256 samples of the same graph keep their rings in LDS, ring[slot][lane]; rings and patches share the
+ * workgroup's LDS, 4 n_lds_slots lanes + (lanes / 64) * 64 * (4 R (n_in + n_out) + 16) bytes.  R runs from the shortest power of two,
+ * at least 16, at which one stream's run in the wider frame is 128 bytes (32 rows for one wire) down to 16, per R the lanes over
+ * 256, 128, 64: the first pair that fits 160 KiB twice, failing that once.
+ *
+ * Checks, in this order and before a device is needed: rows_total > 0; the scope (fz_program_far_stream_major_check asks without a
+ * device); an empty block is FZ_OK; row0 + n_samples <= rows_total; the alignment rule of fz_run_block_stream_major (rows_total *
+ * wires and row0 * wires multiples of 4 floats per side, fz_last_error() names the side); a pointer the graph needs is not NULL
+ * (named); pointers 16-byte aligned; 2^30 streams or more FZ_E_UNSUPPORTED.  `in` and `out` must not overlap.
+ *
+ * Scope: fz_compile programs with float far lines.  FZ_E_UNSUPPORTED with the reason in fz_last_error(): fz_compile_typed programs,
+ * complex wires, sample-rate modulators, double or complex far lines, a graph whose LDS rings plus the shortest patch fit no
+ * workgroup (the bytes named).  Frames are float32: the call has no float64-frames form (FZ_VF_OUT_F64 belongs to a variant, and
+ * this call takes none); float64 nodes evaluate in double and narrow to the float32 frame as in fz_run_block.
+ * Everything else keeps refusing these graphs on stream-major buffers: fz_run_block_stream_major, fz_bank_process_stream_major,
+ * fz_bank_process_host_stream_major, the PCM calls, fz_program_tune.
+ * Not built: double or complex far lines, the bank, PCM frames and fz_program_tune on this path (its plan is static).
+ * ---------------------------------------------------------------------------------------- */
+/* FZ_OK, or FZ_E_UNSUPPORTED with the reason in fz_last_error(); host only */
+int  fz_program_far_stream_major_check(const fz_program* p);
+int  fz_run_block_far_stream_major(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
+                                   uint32_t rows_total, uint32_t row0, uint32_t n_samples, void* hip_stream);
+/* The kernel the call runs, without a device: its registers, scratch and LDS (`unroll` = G; lds_bytes by the LDS rule above), its
+ * symbol fz_far_sm_kernel_g<G>r<R>b<lanes per workgroup>_g<graph tag>, and its whole source.  A graph without a far line: what
+ * fz_program_kernel_resources / _kernel_symbol / fz_program_source answer for {0, 0, 0, FZ_VF_STREAM_MAJOR}. */
+int  fz_program_far_stream_major_resources(fz_program* p, fz_kernel_resources* out);
+long fz_program_far_stream_major_kernel_symbol(fz_program* p, char* buf, size_t cap);
+long fz_program_far_stream_major_source(fz_program* p, char* buf, size_t cap);
 
 /* ------------------------------------------------------------------------------------------
  * fz_bank -- device-resident closure state for n_streams streams: the `state_` member of

@@ -256,6 +256,11 @@ def _load():
         "fz_program_pcm16_stream_major_resources": (ctypes.c_int, [P, u32, u32, ctypes.POINTER(KernelResources)]),
         "fz_program_pcm16_stream_major_kernel_symbol": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_program_pcm16_stream_major_source": (ctypes.c_long, [P, u32, u32, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_far_stream_major_check": (ctypes.c_int, [P]),
+        "fz_run_block_far_stream_major": (ctypes.c_int, [P, P, P, P, P, u64, u32, u32, u32, P]),
+        "fz_program_far_stream_major_resources": (ctypes.c_int, [P, ctypes.POINTER(KernelResources)]),
+        "fz_program_far_stream_major_kernel_symbol": (ctypes.c_long, [P, ctypes.c_char_p, ctypes.c_size_t]),
+        "fz_program_far_stream_major_source": (ctypes.c_long, [P, ctypes.c_char_p, ctypes.c_size_t]),
         "fz_bank_process_pcm16_stream_major": (ctypes.c_int, [P, P, P, u32, u32, u32, u32, u32, P]),
         "fz_bank_process_host_pcm16_stream_major": (ctypes.c_int, [P, P, P, u32]),
         "fz_device_count": (ctypes.c_int, []),

@@ -16,9 +16,9 @@ run_far(prog, x, state, params, consts) is run_rings() for graphs with delay lin
 combs, low plucked strings), whose rings live in HBM: time-major frames, the backward is Program.run_block_far_grad
 (include/flowz_hip.h: fz_run_block_far_grad).  The rows of such a line in `state` are ring slots and one more row holds the phase: a
 zero state has phase 0, and the state gradient's phase rows are zero.  run_rings() keeps refusing such graphs.
-run_far(..., stream_major=True) takes the stream-major tensors of run(..., stream_major=True): the backward is
-Program.run_block_far_grad_stream_major on the tensors as they lie; the forward has no stream-major body for rings in HBM and goes
-through the layout adapter (two extra passes over the frames).
+run_far(..., stream_major=True) takes the stream-major tensors of run(..., stream_major=True): the forward is
+Program.run_block_far_stream_major, the backward Program.run_block_far_grad_stream_major, both on the tensors as they lie: nothing is
+transposed.
 
 mse(prog, x, target, ...) is the mean squared error of one block against a target as ONE launch (Program.run_block_loss_grad:
 the adjoint kernel forms y, the error and dL/dy itself), where run() followed by ((y - target) ** 2).mean() is a forward launch,
@@ -53,7 +53,7 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-from .flowz import FlowzError, Program, frames_from_stream_major, frames_to_stream_major
+from .flowz import FlowzError, Program
 from . import _capi as C
 
 
@@ -111,13 +111,9 @@ class _Block(torch.autograd.Function):
         _apply_consts(prog, consts)
         ctx.rings = rings
         st = state.detach().clone() if state is not None else None    # (the caller's state is never advanced in place)
-        if stream_major and rings == "far" and not prog.ring_grad_supported():
-            # (a line in HBM: no forward body for it on stream-major buffers -- the layout adapter around the time-major forward)
-            y, st = prog.run_block(frames_from_stream_major(x.detach()), st, params.detach() if params is not None else None)
-            y = frames_to_stream_major(y)
-        else:
-            fwd = prog.run_block_stream_major if stream_major else prog.run_block
-            y, st = fwd(x.detach(), st, params.detach() if params is not None else None)
+        # (a line in HBM on stream-major buffers: the far forward call; for every other graph it is run_block_stream_major itself)
+        fwd = prog.run_block if not stream_major else prog.run_block_far_stream_major if rings == "far" else prog.run_block_stream_major
+        y, st = fwd(x.detach(), st, params.detach() if params is not None else None)
         ctx.prog = prog
         ctx.stream_major = stream_major
         ctx.consts = consts.detach().clone() if consts is not None else None
@@ -178,10 +174,9 @@ def run_far(prog: Program, x, state=None, params=None, consts=None, stream_major
     line's phase row (behind all line rows) is 0 in a zero state and has a zero gradient.  Chaining it over consecutive blocks
     back-propagates through time across them: the state after a block carries the phase the next block starts from.
     stream_major: the tensor shapes of run(..., stream_major=True) -- x [n_streams, T, n_in], or [n_streams, T] for one input wire, y
-    [n_streams, T, n_out].  The backward is Program.run_block_far_grad_stream_major on the tensors as they lie: it costs no extra pass.
-    The forward does: there is no forward kernel body for rings in HBM on stream-major buffers, so x is transposed
-    (frames_from_stream_major), run through Program.run_block and y transposed back (frames_to_stream_major) -- two extra passes over
-    the frames.  The state rows are [row, n_streams] in either layout, so blocks chain as in the time-major call."""
+    [n_streams, T, n_out].  The forward is Program.run_block_far_stream_major, the backward Program.run_block_far_grad_stream_major,
+    both on the tensors as they lie: neither costs an extra pass, and y has the bits of the time-major call's y transposed.  The
+    state rows are [row, n_streams] in either layout, so blocks chain as in the time-major call."""
     return _run(prog, x, state, params, consts, stream_major, "far")
 
 

@@ -33,6 +33,7 @@ extern const char* const kSkeletonStates;        // fz_kernel_states.hip.inc: pl
 extern const char* const kSkeletonStatesSm;      // fz_kernel_states_sm.hip.inc: the same three modes on stream-major buffers
 extern const char* const kSkeletonPcm16;     // fz_kernel_pcm16.hip.inc: the frame walk for 16-bit PCM frames, behind the common head
 extern const char* const kSkeletonPcm16Sm;   // fz_kernel_pcm16_sm.hip.inc: the same for stream-major buffers
+extern const char* const kSkeletonFarSm;     // fz_kernel_far_sm.hip.inc: the forward of far lines on stream-major buffers, behind the common head
 
 // The adjoint family (fz_grad.cpp), layout x rings plus the states kernels: one row per combination of the family bits next to
 // FZ_VF_ADJOINT, found by exact match: a row per symbol stem.  The loss selects no row: it is FZ_LOSS in the configuration of the row's
@@ -72,9 +73,10 @@ const std::string& skeleton_source(const Variant& v)
    static const std::string head = kSkeletonHead, sm = head + kSkeletonBody_sm_common;
    static const std::string sm_pair = sm + kSkeletonBody_sm_pair, sm_long = sm + kSkeletonBody_sm_long, sm_short = sm + kSkeletonBody_sm_short,
                             ws = head + kSkeletonBody_wave_split, fr = head + kSkeletonBody_frames;
-   static const std::string pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm;
+   static const std::string pcm = head + kSkeletonPcm16, pcm_sm = head + kSkeletonPcm16Sm, far_sm = head + kSkeletonFarSm;
    if (v.flags & FZ_VF_ADJOINT) return adjoint_row(v).text;
    if (v.flags & FZ_VF_PCM16) return (v.flags & FZ_VF_PCM16_SM) ? pcm_sm : pcm;
+   if (is_far_sm(v.flags)) return far_sm;
    if (v.flags & FZ_VF_STREAM_MAJOR) return !(v.flags & FZ_VF_SM_LONG) ? sm_short : v.P == 2 ? sm_pair : sm_long;
    return ws_parts(v.flags) ? ws : fr;
 }
@@ -96,6 +98,8 @@ std::string kernel_name(const Graph& g, const Variant& v)
       return "fz_pcm16_kernel_i" + std::to_string((v.flags & FZ_VF_PCM16_IN) ? 1 : 0) + "o" + std::to_string((v.flags & FZ_VF_PCM16_OUT) ? 1 : 0) + "p" +
              std::to_string(v.P) + "u" + std::to_string(v.U) + "b" + std::to_string(v.block) + ((v.flags & FZ_VF_PCM16_B16) ? "h" : "") +
              ((v.flags & FZ_VF_ST_MERGE) ? "m" : "");
+   // (the forward of far lines on stream-major buffers: rows of an unrolled group, rows of the patch, lanes)
+   if (is_far_sm(v.flags)) return "fz_far_sm_kernel_g" + std::to_string(v.U) + "r" + std::to_string(v.P) + "b" + std::to_string(v.block);
    std::string n = "fz_block_kernel_p" + std::to_string(v.P) + "u" + std::to_string(v.U) + "b" + std::to_string(v.block);
    if ((v.flags & FZ_VF_STAGE_PACK) && g.split.ok) n += "s" + std::to_string(g.split.K) + (g.split.m > 1 ? "a" + std::to_string(g.split.m) : "");
    if (ws_parts(v.flags)) n += "w" + std::to_string(ws_parts(v.flags)) + (ws_io(v.flags) ? (ws_io_waves(v.flags) == 2 ? "io2" : "io") : "");
@@ -130,7 +134,7 @@ RingPlan ring_plan(const Graph& g, const Variant& v)
 {
    RingPlan rp;
    rp.slots = g.n_lds_slots;
-   if (!g.n_lds_slots || (v.flags & (FZ_VF_STREAM_MAJOR | FZ_VF_STAGE_PACK)) || ws_parts(v.flags) || v.P > 4 || v.U < 2) return rp;
+   if (!g.n_lds_slots || (v.flags & (FZ_VF_STREAM_MAJOR | FZ_VF_STAGE_PACK)) || is_far_sm(v.flags) || ws_parts(v.flags) || v.P > 4 || v.U < 2) return rp;
    const uint32_t TW = 4 / v.P;
    uint32_t min_read = ~0u;
    std::set<std::pair<uint32_t, uint32_t>> reads;
@@ -182,7 +186,7 @@ struct RingRead { uint32_t line, d, m, nv; };              // m: slots between t
 static std::vector<RingRead> ring_reads(const Graph& g, const Variant& v, const RingPlan& rp)
 {
    std::vector<RingRead> r;
-   if (!rp.vec && ((v.flags & FZ_VF_STREAM_MAJOR) || v.U < 2)) return r;
+   if (!rp.vec && ((v.flags & FZ_VF_STREAM_MAJOR) || is_far_sm(v.flags) || v.U < 2)) return r;
    for (const Node& nd : g.nodes) {
       if (nd.kind != FZ_IR_DELAY) continue;
       const uint32_t l = (uint32_t)g.line_of_node[nd.a];
@@ -208,7 +212,9 @@ std::string gen_config(const Graph& g, const Variant& v)
    o << "#define FZ_NPARAM " << g.n_param << "\n";
    o << "#define FZ_NMOD " << g.n_mod << "\n";
    o << "#define FZ_NSTATE " << g.n_state << "\n";
-   o << "#define FZ_P " << v.P << "\n";
+   // (the far stream-major forward carries its patch rows in P: FZ_R; the body is compiled for one stream per lane)
+   o << "#define FZ_P " << (is_far_sm(v.flags) ? 1u : v.P) << "\n";
+   if (is_far_sm(v.flags)) o << "#define FZ_R " << v.P << "\n";
    o << "#define FZ_U " << v.U << "\n";
    o << "#define FZ_BLOCK " << v.block << "\n";
    o << "#define FZ_FLAGS " << v.flags << "u\n";

@@ -27,6 +27,7 @@
 #include <utility>
 #include <vector>
 
+#include "fz_inspect.hpp"
 #include "fz_runtime.hpp"
 
 namespace fz {
@@ -665,35 +666,6 @@ static int run_recording(fz_program* p, const GradCall& call, uint32_t layout, u
    return FZ_OK;
 }
 
-// the inspection calls of a kernel of the family, given the maker of its Variant: resources (`fn` names the call in the refusal; `unroll`
-// = the checkpoint stride), symbol, source
-template <class Maker>
-static int grad_resources(fz_program* p, fz_kernel_resources* out, const char* fn, Maker make)
-{
-   FZ_GUARD(
-      if (!p || !out) fail(FZ_E_INVALID, std::string(fn) + ": bad arguments");
-      *out = resources_of(p, make());
-      return FZ_OK;)
-}
-
-template <class Maker>
-static long grad_symbol(fz_program* p, char* buf, size_t cap, Maker make)
-{
-   return string_result(buf, cap, [&] {
-      if (!p) fail(FZ_E_INVALID, "null program");
-      return kernel_symbol(p->g, make());
-   });
-}
-
-template <class Maker>
-static long grad_source(fz_program* p, char* buf, size_t cap, Maker make)
-{
-   return string_result(buf, cap, [&] {
-      if (!p) fail(FZ_E_INVALID, "null program");
-      return full_source(p->g, make());
-   });
-}
-
 }  // namespace fz
 
 using namespace fz;
@@ -717,26 +689,10 @@ int fz_program_grad_workspace(const fz_program* p, uint64_t n_streams, uint32_t 
       return FZ_OK;)
 }
 
-// The inspection calls of one kernel of the family -- fz_program_<stem>_resources<suf>, fz_program_<stem>_kernel_symbol<suf> and
-// fz_program_<stem>_source<suf> (include/flowz_hip.h declares each) -- from one statement of its Variant.  `who` names the resources
-// call in its refusal; ARGS is what the calls take between the program and their results, every argument with its comma.
+// The inspection calls of every kernel of the family, one FZ_INSPECTION (fz_inspect.hpp) per kernel.
 #define FZ_ARG_C uint32_t checkpoint_rows,
 #define FZ_ARG_LAYOUT uint32_t layout,
 #define FZ_SM layout_is_stream_major(layout)
-#define FZ_INSPECTION(stem, suf, who, ARGS, VARIANT)                                                                         \
-   int fz_program_##stem##_resources##suf(fz_program* p, ARGS fz_kernel_resources* out)                                      \
-   {                                                                                                                         \
-      return grad_resources(p, out, who, [&] { return VARIANT; });                                                           \
-   }                                                                                                                         \
-   long fz_program_##stem##_kernel_symbol##suf(fz_program* p, ARGS char* buf, size_t cap)                                    \
-   {                                                                                                                         \
-      return grad_symbol(p, buf, cap, [&] { return VARIANT; });                                                              \
-   }                                                                                                                         \
-   long fz_program_##stem##_source##suf(fz_program* p, ARGS char* buf, size_t cap)                                           \
-   {                                                                                                                         \
-      return grad_source(p, buf, cap, [&] { return VARIANT; });                                                              \
-   }
-
 // (block_variant(g, C, ring, stream-major, loss, far) and states_variant(g, ring, stream-major, far) are the two makers)
 FZ_INSPECTION(grad, _for, "fz_program_grad_resources", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, false, FZ_SM, false))
 FZ_INSPECTION(loss_grad, _for, "fz_program_loss_grad_resources_for", FZ_ARG_C FZ_ARG_LAYOUT, block_variant(p->g, checkpoint_rows, false, FZ_SM, true))
@@ -753,7 +709,6 @@ FZ_INSPECTION(ring_states, , "fz_program_ring_states_resources", , states_varian
 FZ_INSPECTION(ring_states, _for, "fz_program_ring_states_resources_for", FZ_ARG_LAYOUT, states_variant(p->g, true, FZ_SM))
 FZ_INSPECTION(far_states, , "fz_program_far_states_resources", , states_variant(p->g, true, false, true))
 FZ_INSPECTION(far_states, _for, "fz_program_far_states_resources_for", FZ_ARG_LAYOUT, states_variant(p->g, true, FZ_SM, true))
-#undef FZ_INSPECTION
 #undef FZ_SM
 #undef FZ_ARG_LAYOUT
 #undef FZ_ARG_C

@@ -308,6 +308,14 @@ constexpr uint32_t FZ_VF_PCM16_IN = 1u, FZ_VF_PCM16_OUT = 2u, FZ_VF_PCM16_B16 = 
 // more of the reserved bits.  Such a Variant is {P = 1, U = rows per chunk, block = 64, flags = these two + the IN / OUT bits}
 // (fz_pcm16.cpp: pcm16_sm_chunk_rows is the one home of U).
 constexpr uint32_t FZ_VF_PCM16_SM = 1u << 13;
+// internal: the FORWARD kernel for stream-major float32 buffers of a graph with delay lines deeper than 256 samples, rings in HBM
+// (fz_far_sm.cpp: fz_run_block_far_stream_major; fz_kernel_far_sm.hip.inc behind the common head, a text and a symbol of its own).
+// Its flag set is the two reserved bits that read "stream-major, far" WITHOUT FZ_VF_ADJOINT, and exactly those: no maker of the
+// adjoint family produces it (each sets bit 27), no caller's variant names it (check_request refuses both bits).  Such a Variant is
+// {P = the patch rows R, U = the rows G of one unrolled group, block = lanes per workgroup}; codegen puts R into FZ_R and compiles
+// the body for one stream per lane.  fz_far_sm.cpp: far_sm_plan is the one place that makes one.
+constexpr uint32_t FZ_VF_FAR_SM = FZ_VF_ADJOINT_SM | FZ_VF_ADJOINT_FAR;
+inline bool is_far_sm(uint32_t flags) { return flags == FZ_VF_FAR_SM; }
 constexpr uint32_t kChipCUs = 256;       // MI355X (gfx950): 8 XCDs x 32 CUs -- what chip_cus() answers on a box without a GPU
 unsigned chip_cus();                     // compute units of the current device (fz_launch.cpp)
 
@@ -410,6 +418,10 @@ bool grad_variant_fits(const Graph& g, const Variant& v);
 std::string pcm16_unsupported_reason(const Graph& g);
 bool pcm16_variant_fits(const Graph& g, const Variant& v);
 bool pcm16_sm_variant_fits(const Graph& g, const Variant& v);      // ... that fz_run_block_pcm16_stream_major could have made
+// The forward of far lines on stream-major buffers (fz_far_sm.cpp): why fz_run_block_far_stream_major does not take this graph ("" =
+// it does), and whether v is the Variant it makes for it
+std::string far_sm_unsupported_reason(const Graph& g);
+bool far_sm_variant_fits(const Graph& g, const Variant& v);
 
 // ---- runtime ---------------------------------------------------------------------------------------------
 // what the code object's metadata says the kernel needs (AMDGPU msgpack notes)
@@ -526,6 +538,10 @@ int launch_pcm16(fz_program* p, const void* in, void* out, float* state, const f
 // fz_run_block_pcm16_stream_major: the same for the window [row0, row0 + n_samples) of stream-major buffers
 int launch_pcm16_sm(fz_program* p, const void* in, void* out, float* state, const float* params, uint64_t n_streams, uint32_t rows_total,
                     uint32_t row0, uint32_t n_samples, uint32_t in_type, uint32_t out_type, void* stream);
+// fz_run_block_far_stream_major: the forward of a graph with far lines on the window of stream-major float32 buffers (fz_far_sm.cpp);
+// a graph without a far line: fz_run_block_stream_major with a null variant
+int launch_far_sm(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams, uint32_t rows_total,
+                  uint32_t row0, uint32_t n_samples, void* stream);
 int tune(fz_program* p, const float* in, float* out, float* state, const float* params, uint64_t n_streams,
          uint32_t n_samples, uint32_t tile_streams, void* stream, fz_variant* chosen, float* chosen_ms, bool implicit = false);
 std::vector<fz_variant> tune_candidates(const Graph& g, uint64_t n_streams, uint32_t n_samples, uint32_t tile_streams);
@@ -549,4 +565,5 @@ struct NoJitScope {
 bool kernel_at_hand(fz_program* p, const Variant& v);
 std::string kernel_code_id(fz_program* p, const Variant& v);
 int manifest_build(const std::string& path, unsigned n_workers, uint32_t counts[4]);   // fz_manifest.cpp
+
 }  // namespace fz

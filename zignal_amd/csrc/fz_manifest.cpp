@@ -45,10 +45,11 @@ void manifest_record(const fz_program* p, const Variant& v)
 // What a record's variant must satisfy before anything is generated from it: a forward kernel runs 1, 2 or 4 streams per lane.  A
 // variant of the adjoint family has rules of its own and one home for them, fz_grad.cpp: grad_variant_fits -- asked below, once the
 // record's graph is compiled; a PCM variant passes the forward rule and then fz_pcm16.cpp: pcm16_variant_fits, or pcm16_sm_variant_fits
-// where it names the kernel for stream-major buffers.
+// where it names the kernel for stream-major buffers.  The forward of far lines on stream-major buffers carries its patch rows in P and has
+// one home for its rule as well, fz_far_sm.cpp: far_sm_variant_fits.
 static bool variant_is_sane(const Variant& v)
 {
-   if (v.flags & FZ_VF_ADJOINT) return true;
+   if ((v.flags & FZ_VF_ADJOINT) || is_far_sm(v.flags)) return true;
    return (v.P == 1 || v.P == 2 || v.P == 4) && v.U != 0 && v.U <= 128 && v.block != 0 && v.block % 64 == 0 && v.block <= 1024;
 }
 
@@ -104,6 +105,7 @@ int manifest_build(const std::string& path, unsigned n_workers, uint32_t counts[
       for (const Variant& v : kv.second) {
          if ((v.flags & FZ_VF_ADJOINT) && !grad_variant_fits(p->g, v)) ++counts[3];   // (no variant a backward makes for this graph: its flag set, stride, workgroup, patch rows)
          else if ((v.flags & FZ_VF_PCM16) && !((v.flags & FZ_VF_PCM16_SM) ? pcm16_sm_variant_fits(p->g, v) : pcm16_variant_fits(p->g, v))) ++counts[3];   // (no variant fz_run_block_pcm16 makes, or a graph it refuses)
+         else if (is_far_sm(v.flags) && !far_sm_variant_fits(p->g, v)) ++counts[3];   // (not the variant fz_run_block_far_stream_major makes for this graph)
          else items.push_back(Item{p, v});
       }
    }

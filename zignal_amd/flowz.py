@@ -785,6 +785,62 @@ class Program:
                                                       torch.cuda.current_stream().cuda_stream))
         return out, state
 
+    # -- delay lines deeper than 256 samples on stream-major buffers, forward (fz_run_block_far_stream_major) --------
+    def far_stream_major_supported(self) -> bool:
+        """True when fz_run_block_far_stream_major takes this program (far_stream_major_unsupported_reason() says why not)."""
+        return C.lib.fz_program_far_stream_major_check(self._h) == C.FZ_OK
+
+    def far_stream_major_unsupported_reason(self) -> str:
+        return "" if self.far_stream_major_supported() else C.last_error()
+
+    def far_stream_major_resources(self) -> dict:
+        """registers / scratch / LDS bytes of the kernel run_block_far_stream_major runs (JITs it; needs no GPU); 'unroll' = the rows G
+        of one unrolled group"""
+        return _resources(C.lib.fz_program_far_stream_major_resources, self._h)
+
+    def far_stream_major_kernel_symbol(self) -> str:
+        """fz_far_sm_kernel_g<G>r<R>b<lanes>_g<graph tag>; a graph without a far line: run_block_stream_major's default kernel"""
+        return _name(C.lib.fz_program_far_stream_major_kernel_symbol, self._h)
+
+    def far_stream_major_source(self) -> str:
+        """that kernel's whole source: generated configuration and body, the common head, the stream-major far walk"""
+        return _text(C.lib.fz_program_far_stream_major_source, self._h)
+
+    def run_block_far_stream_major(self, x, state=None, params=None, out=None, row0=0, n_samples=None):
+        """run_block_stream_major for a graph with delay lines deeper than 256 samples (rings in HBM): x is a CUDA float32 tensor
+        [n_streams, rows, n_in] (or [n_streams, rows] for one wire: a [batch, time] tensor as it lies), out [n_streams, rows, n_out].
+        The block is the window of rows [row0, row0 + n_samples) (default: to the end); rows of out outside it are not written.
+        out and state are bit for bit run_block's on the transposed frames; the far rings are read and written in the rows of state.
+        rows * wires and row0 * wires are multiples of 4.  A graph without such a line runs run_block_stream_major's default kernel.
+        Returns (out, state)."""
+        import torch
+
+        if not x.is_cuda:
+            raise NoDeviceError(C.FZ_E_NO_DEVICE, "run_block_far_stream_major needs CUDA (ROCm) tensors: zignal_amd has no CPU path")
+        if x.dim() == 2:
+            x = x.unsqueeze(-1)
+        _check_frames(x, _bi.max(self.n_in, 1))
+        ns, rows, _ = x.shape
+        row0 = int(row0)
+        T = rows - row0 if n_samples is None else int(n_samples)
+        _require(row0 >= 0 and T >= 0, "row0 / n_samples: a window inside the buffers")
+        if out is None:
+            out = torch.zeros((ns, rows, self.n_out), dtype=torch.float32, device=x.device)
+        _check_dev(out, (ns, rows, self.n_out), "out")
+        if state is None:
+            state = torch.zeros((_bi.max(self.n_state, 1), ns), dtype=torch.float32, device=x.device)
+        if self.n_state:
+            _check_dev(state, (self.n_state, ns), "state")
+        pp = None
+        if self.n_param:
+            if params is None:
+                raise FlowzError(C.FZ_E_INVALID, f"params: the graph has {self.n_param} per-stream coefficient(s), none given")
+            pp = _check_dev(params, (self.n_param, ns), "params").data_ptr()
+        C.check(C.lib.fz_run_block_far_stream_major(self._h, x.data_ptr() if self.n_in else None, out.data_ptr() if self.n_out else None,
+                                                    state.data_ptr() if self.n_state else None, pp, ns, rows, row0, T,
+                                                    torch.cuda.current_stream().cuda_stream))
+        return out, state
+
     # -- the backward of a block (fz_run_block_grad) ------------------------------------------------
     GRAD_WANT = ("x", "state", "params", "consts")
 
